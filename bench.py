@@ -7,6 +7,12 @@ R = 16 rotations, every rotation a training sample:
     16 Huber losses (code/trainer.py:345-348), backward of their sum,
     gradient all-reduce over RCCL when N > 1, ONE Adam step (code/trainer.py:383).
 Inputs (heightmaps, labels, weights) are resident in HBM when the timed region starts.
+The warm-up and timed steps run Adam at learning rate 0: every step still computes and writes the whole
+update (moments, bias correction, parameters), but starts from the same weights, so what a step computes
+does not depend on how the fp32 atomics of the previous steps' weight gradients happened to round - two
+runs with the same arguments agree to the rounding of one step.  (Training on, Adam's early steps move
+weights whose gradient is rounding noise by +-lr with whatever sign the noise has, and the runs drift
+apart.)  The learning rate is restored before the --full side measurements.
 fp32 in, fp32 out (the reference runs apex O0 = fp32 and parity is gated in fp32, SURVEY.md
 section 7); the convolutions run on the fp16 matrix cores as scaled two-piece split products
 (three MFMA terms) with fp32-class accuracy (csrc/gemm.cuh, operand kind 3).
@@ -15,7 +21,10 @@ section 7); the convolutions run on the fp16 matrix cores as scaled two-piece sp
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints
+the line; every side measurement (host enqueue, the single-sample step, forward-only sweep, batched
+scenes, config 3 / 4 / 5 legs, per-kernel rooflines, blocking all-reduce, CPU baseline) runs only
+with --full.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -247,6 +256,28 @@ def kernel_roofline(step_fn, eng, dev, terms, ms_per_step, step_rl, n_prof=3, pm
     return rl
 
 
+DUMP_SAMPLE = 1 << 22      # elements kept of a flat parameter / gradient buffer by --dump-outputs (fixed seeded sample)
+DUMP_LIMIT = 64 * 10 ** 6  # bytes, all dumped arrays together
+
+
+def dump_outputs(path, named, model):
+    """--dump-outputs: the arrays the last timed step handed its caller - loss vector(s) and Q maps (`named`, device tensors)
+    - and the model state it left: BatchNorm running statistics in full, and the same fixed seeded sample of the flat
+    parameters (after the Adam step) and of the flat gradient (24.4 M floats each: 98 MB in full).  float32, <name>.npy."""
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in named.items()}
+    arrays["bn_buffers"] = model._flat_bufs.detach().float().cpu().numpy()
+    n = model._flat_params.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(idx).to(model._flat_params.device)
+    arrays["params_sample"] = model._flat_params.detach()[idx].float().cpu().numpy()
+    arrays["grads_sample"] = model.flat_grads().detach()[idx].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "outputs to dump: %d bytes" % total
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 DETAIL_FILE = "bench_detail.json"
 LINE_LIMIT = 1900          # the driver keeps a 2000-character tail of stdout and parses the last line: the whole line must fit in it
 
@@ -363,11 +394,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--cpu-samples", type=int, default=16, help="reference-schedule samples timed on the host at the best thread setting (16 = one full pass, the default; 0 = skip)")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement: host enqueue, single-sample step, forward sweep, "
+                         "batched scenes, config 3 / 4 / 5 legs, per-kernel rooflines, blocking all-reduce, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, Q maps, BN statistics, a fixed sample of the parameters "
+                         "and gradients) as DIR/<name>.npy, float32")
+    ap.add_argument("--cpu-samples", type=int, default=16, help="--full: reference-schedule samples timed on the host at the best thread setting (16 = one full pass, the default; 0 = skip)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-kernel rooflines")
     ap.add_argument("--batched-scenes", type=int, default=4,
-                    help="also time a config-4 style step with this many scenes per engine call (0 = skip)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE.json config 3 / 4 / 5 legs")
+                    help="--full: also time a config-4 style step with this many scenes per engine call (0 = skip)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the BASELINE.json config 3 / 4 / 5 legs")
     ap.add_argument("--leg", choices=("headline", "config3", "config4", "config5"), default="headline",
                     help="what a timed step is (under any --gpus N): the headline 1 scene x 16 rotations per GPU; config3 = E + S + ES "
                          "heads in bf16 per GPU; config4 = 8 scenes x 16 rotations per GPU + all-reduce; config5 = S=1824, 4 of the "
@@ -380,6 +417,8 @@ def main():
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: blocking gradient all-reduce after the backward instead of the one hidden under its second half")
     ap.add_argument("--serialize", action="store_true", help="one HIP stream, launches in issue order (per-kernel durations of a rocprofv3 trace stay per kernel)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.train_only:
         args.cpu_samples, args.batched_scenes, args.no_configs, args.no_roofline = 0, 0, True, True
     if args.serialize:
@@ -470,7 +509,8 @@ def main():
                         "fwd + Huber + bwd + all-reduce + Adam" % len(rots))
 
         def step():
-            return tr.train_batch(depth_d, mdepth_d, 0, rots, labels_d, grad_sync=sync)
+            loss, q = tr.train_batch(depth_d, mdepth_d, 0, rots, labels_d, grad_sync=sync, return_q=True)
+            return {"loss": loss, "q": q}
     elif leg == "config4":
         nb = args.scenes_per_rank                                     # 64 scenes over 8 GPUs = 8 per GPU (BASELINE.json configs[3])
         sc = [synthetic.heightmap_scene(200 + nb * rank + k) for k in range(nb)]
@@ -481,7 +521,8 @@ def main():
                     "+ bwd, one gradient all-reduce, one Adam step; a pass = one scene x 16 rotations" % (nb, nb * (R + 1), nb * R))
 
         def step():
-            return tr.train_batch(d8_d, m8_d, 0, [rots] * nb, lab8_d, grad_sync=sync)
+            loss, q = tr.train_batch(d8_d, m8_d, 0, [rots] * nb, lab8_d, grad_sync=sync, return_q=True)
+            return {"loss": loss, "q": q}
     elif leg == "config5":
         dbig, mbig = synthetic.heightmap_scene(4, size=640, n_boxes=8)    # the same scene on every rank: the ranks share its 32 rotations
         dbig_d, mdb_d = on_dev(dbig), on_dev(dbig * mbig[0])
@@ -495,7 +536,8 @@ def main():
                     "streams), dense 38x38 Q maps, Huber on [0,0,0,0], bwd, gradient all-reduce, Adam; a pass = all 32 rotations")
 
         def step():
-            return tr.train_batch(dbig_d, mdb_d, 0, r5, l5_d, grad_sync=sync)
+            loss, q = tr.train_batch(dbig_d, mdb_d, 0, r5, l5_d, grad_sync=sync, return_q=True)
+            return {"loss": loss, "q": q}
     else:                                                             # config3
         md2_d = on_dev(depth * (masks[1] + masks[2]))
         lab1_d = on_dev(synthetic.uniform(5, "bench/labels_c3", 1, 0.0, 1.5), np.float32)
@@ -506,9 +548,12 @@ def main():
                     "fwd + Huber + bwd + all-reduce + Adam per head; a pass = the three heads")
 
         def step():
-            tr.train_batch(depth_d, mdepth_d, 0, rots, labels_d, grad_sync=sync)
-            tr.train_batch(depth_d, mdepth_d, 1, rots, labels_d, grad_sync=sync)
-            return tr.train_batch(depth_d, md2_d, 2, [0], lab1_d, grad_sync=sync)       # ES: rotation 0 only (code/models.py:418)
+            res = {}
+            res["loss_style0"], res["q_style0"] = tr.train_batch(depth_d, mdepth_d, 0, rots, labels_d, grad_sync=sync, return_q=True)
+            res["loss_style1"], res["q_style1"] = tr.train_batch(depth_d, mdepth_d, 1, rots, labels_d, grad_sync=sync, return_q=True)
+            res["loss_style2"], res["q_style2"] = tr.train_batch(depth_d, md2_d, 2, [0], lab1_d, grad_sync=sync,
+                                                                 return_q=True)       # ES: rotation 0 only (code/models.py:418)
+            return res
 
     def barrier():
         if distributed:
@@ -517,22 +562,26 @@ def main():
         torch.cuda.synchronize(dev)
 
     import models
+    lr0, tr.optimizer.lr = tr.optimizer.lr, 0.0
     for _ in range(args.warmup):
         step()
     barrier()
     del ar_events[:]
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        res = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    tr.optimizer.lr = lr0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, tr.model)
     if distributed:
         import torch.distributed as dist
         on_host = dist.get_backend() == "gloo"
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if on_host else dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-    assert bool(torch.isfinite(loss).all()), "non-finite loss in the timed region"
+    assert all(bool(torch.isfinite(v).all()) for k, v in res.items() if k.startswith("loss")), "non-finite loss in the timed region"
     ms_per_step = elapsed / args.steps * 1e3
     passes_per_s = world * units_per_step * args.steps / elapsed
 
@@ -556,30 +605,31 @@ def main():
         ar = [a.elapsed_time(b) for a, b in ar_events]
         out["allreduce_overlapped"] = not args.no_overlap
         out["allreduce_exposed_ms_per_step"] = float(np.sum(ar)) / args.steps      # launch-stream time inside the sync hooks (hipEvents)
-        # the collective itself: blocking all-reduce of the (trunk, head) gradient ranges of the last step, hipEvents around it
         tid, hid = tr.model._saved[2], tr.model._saved[3]
-        t_ar = []
-        for _ in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            parallel.allreduce_grads(tr.model, tid, hid)
-            e1.record()
-            torch.cuda.synchronize(dev)
-            t_ar.append(e0.elapsed_time(e1))
-        out["allreduce_ms"] = float(np.min(t_ar))
         out["allreduce_bytes"] = 4 * sum(n for _, n in parallel.grad_segments(tr.model.HEAD_OUT, tid, hid))
         out["allreduce_backend"] = torch.distributed.get_backend()
         out["rccl_world"] = torch.distributed.get_world_size()         # what the process group saw, not what WORLD_SIZE asked for
         out["device_count"] = torch.cuda.device_count()
-        devs = [None] * world
-        torch.distributed.all_gather_object(devs, "%s:%d" % (os.uname().nodename, torch.cuda.current_device()))
-        out["devices_seen"] = len(set(devs))
+        if args.full:
+            # the collective itself: blocking all-reduce of the (trunk, head) gradient ranges of the last step, hipEvents around it
+            t_ar = []
+            for _ in range(3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                parallel.allreduce_grads(tr.model, tid, hid)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                t_ar.append(e0.elapsed_time(e1))
+            out["allreduce_ms"] = float(np.min(t_ar))
+            devs = [None] * world
+            torch.distributed.all_gather_object(devs, "%s:%d" % (os.uname().nodename, torch.cuda.current_device()))
+            out["devices_seen"] = len(set(devs))
     out["roofline"] = {"step": step_rl}
 
-    if rank == 0 and world == 1 and leg in ("config3", "config5") and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and leg in ("config3", "config5") and not args.no_roofline:
         eng = models._ENGINES[(local_rank, input_size, 1)]
         out["roofline"] = kernel_roofline(step, eng, dev, 1, ms_per_step, step_rl)
-    if rank == 0 and world == 1 and leg == "headline" and not args.train_only:
+    if args.full and rank == 0 and world == 1 and leg == "headline" and not args.train_only:
         # host time to ENQUEUE one step (no synchronisation inside): how far the launch path is from being host-bound
         torch.cuda.synchronize(dev)
         t_h = time.perf_counter()

@@ -205,19 +205,56 @@ def test_dtype_casts_select_and_restore_the_operand_precision():
     assert net.precision == "fp32"
 
 
-_REF_CODE = "/root/reference/code"
+# What the drop-in sits in front of: the reference's code/ directory with its own utils.py and a
+# trainer.py that imports from `utils` and `models`.  The test writes a stand-in for the two files: the names the reference's
+# callers take from `utils` (code/robot.py:97, code/main.py:253,264, code/trainer.py:9) and the two imports of code/trainer.py:9-10.
+_STANDIN_UTILS = r"""
+import numpy as np
+import torch.nn as nn
+import torch.nn.functional as F
+
+
+def euler2rotm(theta):
+    cx, cy, cz = np.cos(theta)
+    sx, sy, sz = np.sin(theta)
+    rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return rz @ ry @ rx
+
+
+def rotm2euler(r):
+    return np.array([np.arctan2(r[2, 1], r[2, 2]), np.arcsin(-r[2, 0]), np.arctan2(r[1, 0], r[0, 0])])
+
+
+def get_pointcloud(color_img, depth_img, camera_intrinsics):
+    raise NotImplementedError
+
+
+def get_best_grasp_angle(*args):
+    raise NotImplementedError
+
+
+def get_best_suction_angle(*args):
+    raise NotImplementedError
+
+
+class CrossEntropyLoss2d(nn.Module):
+    def __init__(self, weight=None):
+        super().__init__()
+        self.weight = weight
+
+    def forward(self, inputs, targets):
+        return F.nll_loss(F.log_softmax(inputs, dim=1), targets, self.weight)
+"""
+
+_STANDIN_TRAINER = r"""
+from utils import CrossEntropyLoss2d
+from models import reactive_net, reinforcement_net
+"""
 
 _DROPIN_PROBE = r'''
-import sys, types
-# what the reference's modules import at the top and this image lacks (unused by the names checked here)
-for name in ("cv2", "matplotlib", "matplotlib.pyplot", "apex", "apex.amp"):
-    if name not in sys.modules:
-        try:
-            __import__(name)
-        except ImportError:
-            sys.modules[name] = types.ModuleType(name)
-sys.modules["apex"].amp = sys.modules["apex.amp"]
-sys.modules["matplotlib"].pyplot = sys.modules["matplotlib.pyplot"]
+import sys
 import utils                                           # code/main.py:19, code/robot.py:4
 assert utils.__file__.endswith("smg-multimodal-grasping_amd/utils.py"), utils.__file__
 assert callable(utils.get_heightmap) and utils.get_heightmap.__module__ == "utils"          # the HIP-backed one
@@ -237,27 +274,32 @@ from trainer import Trainer                            # code/main.py:17
 import trainer, models, smg_hip
 assert trainer.__file__.endswith("smg-multimodal-grasping_amd/trainer.py") and hasattr(trainer, "FusedAdam")
 assert models.__file__.endswith("smg-multimodal-grasping_amd/models.py")
-# the advertised mixed mode: the REFERENCE's trainer.py on this repo's models.py
+# the advertised mixed mode: the reference's trainer.py (its imports, code/trainer.py:9-10) on this repo's models.py
 import importlib.util
-spec = importlib.util.spec_from_file_location("ref_trainer", "%s/trainer.py")
+spec = importlib.util.spec_from_file_location("ref_trainer", sys.argv[1])
 ref_trainer = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(ref_trainer)
 assert ref_trainer.reinforcement_net is models.reinforcement_net
 assert ref_trainer.CrossEntropyLoss2d is utils.CrossEntropyLoss2d
 print("dropin ok")
-''' % _REF_CODE
+'''
 
 
-@pytest.mark.skipif(not os.path.isdir(_REF_CODE), reason="build container only: nothing of the reference travels")
-def test_dropin_module_path_as_integration_md_prescribes():
+def test_dropin_module_path_as_integration_md_prescribes(tmp_path):
     """INTEGRATION.md section 1: PYTHONPATH=<repo>/smg-multimodal-grasping_amd:<reference>/code.  The package's utils.py
     shadows the reference's: `import utils` must still give the reference's callers their names (code/robot.py:4,97,
-    code/main.py:19,253,264, code/trainer.py:9) while get_heightmap, Trainer and the nets resolve to the HIP-backed ones."""
+    code/main.py:19,253,264, code/trainer.py:9) while get_heightmap, Trainer and the nets resolve to the HIP-backed ones.
+    <reference>/code is a stand-in directory written here (_STANDIN_UTILS, _STANDIN_TRAINER)."""
     import subprocess
     import sys
     from helpers import PKG
-    env = dict(os.environ, PYTHONPATH=PKG + os.pathsep + _REF_CODE)
-    r = subprocess.run([sys.executable, "-c", _DROPIN_PROBE], env=env, cwd="/tmp", capture_output=True, text=True, timeout=300)
+    ref_code = tmp_path / "code"
+    ref_code.mkdir()
+    (ref_code / "utils.py").write_text(_STANDIN_UTILS)
+    (ref_code / "trainer.py").write_text(_STANDIN_TRAINER)
+    env = dict(os.environ, PYTHONPATH=PKG + os.pathsep + str(ref_code))
+    r = subprocess.run([sys.executable, "-c", _DROPIN_PROBE, str(ref_code / "trainer.py")], env=env, cwd=str(tmp_path),
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "dropin ok" in r.stdout, r.stdout + r.stderr
 
 
@@ -286,3 +328,16 @@ def test_bench_final_line_is_compact():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c["cpu_baseline"], k
     assert abs(c["roofline"]["frac"] - c["roofline"]["achieved"] / c["roofline"]["peak"]) < 1e-3
+
+
+def test_bench_options_full_and_dump_outputs():
+    """bench.py offers --full (the side measurements) and --dump-outputs DIR, and refuses a run without timed steps - all before
+    it touches a GPU."""
+    import subprocess
+    import sys
+    bench = os.path.join(REPO, "bench.py")
+    r = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+    r = subprocess.run([sys.executable, bench, "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, r.stderr

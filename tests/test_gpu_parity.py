@@ -1750,7 +1750,7 @@ def test_bench_two_ranks_config4_leg_on_one_gpu(gpu):
     from helpers import REPO
     env = dict(os.environ, SMG_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--leg", "config4", "--scenes-per-rank", "2",
-                        "--steps", "2", "--warmup", "1", "--train-only"], capture_output=True, text=True, env=env, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--train-only", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     out = json.loads(line)
@@ -1773,7 +1773,7 @@ def test_bench_two_ranks_strong_scaling_leg_on_one_gpu(gpu):
     from helpers import REPO
     env = dict(os.environ, SMG_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--scaling", "strong", "--steps", "2", "--warmup", "1",
-                        "--train-only"], capture_output=True, text=True, env=env, timeout=900)
+                        "--train-only", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     assert len(line) < 2000
@@ -1873,7 +1873,7 @@ def test_rccl_world1_allreduce_paths_execute_and_leave_the_step_unchanged(gpu):
 
 
 def test_bench_rccl_world1_line(gpu):
-    """`RANK=0 WORLD_SIZE=1 SMG_FORCE_ALLREDUCE=1 python bench.py --train-only`: the bench's distributed leg over RCCL with one rank -
+    """`RANK=0 WORLD_SIZE=1 SMG_FORCE_ALLREDUCE=1 python bench.py --train-only --full`: the bench's distributed leg over RCCL with one rank -
     the line reports what the process group saw (`allreduce_backend == "nccl"`, `rccl_world == 1`), the blocking collective's time and
     the exposed time of the overlapped one."""
     import json
@@ -1886,13 +1886,53 @@ def test_bench_rccl_world1_line(gpu):
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                SMG_FORCE_ALLREDUCE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("SMG_BENCH_BACKEND", None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--train-only"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--train-only", "--full"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     print("bench rccl world-1:", {k: out.get(k) for k in ("allreduce_backend", "rccl_world", "allreduce_ms", "allreduce_exposed_ms_per_step", "ms_per_step")})
     assert out["allreduce_backend"] == "nccl" and out["rccl_world"] == 1 and out["n_gpus"] == 1
     assert out["allreduce_overlapped"] is True and out["allreduce_ms"] > 0 and out["allreduce_bytes"] == 4 * (6953856 + 160896)
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(gpu, tmp_path):
+    """`python bench.py --steps 3 --warmup 2 --dump-outputs DIR`, twice: the plain run times exactly --steps steps and carries no side
+    measurement (those need --full); the dump holds the last step's losses and Q maps, the BN statistics and the same seeded sample of
+    parameters and gradients, float32, at most 64 MB.  Two runs with the same arguments compute the same: the timed steps run Adam at
+    learning rate 0, so every step starts from the same weights (bit-identical parameters) and the outputs differ only by the fp32
+    atomics' rounding within one step - the gradient bound of test_rccl_world1_allreduce_paths_execute_and_leave_the_step_unchanged.
+    (Training on, two runs drift apart: the first Adam step moves noise-level weights by +-lr with the sign the atomics' order picks, and
+    after two steps the gradients already differ by ~3e-3 of their norm.)"""
+    import json
+    import os
+    import subprocess
+    import sys
+    from helpers import REPO
+    runs = []
+    for tag in ("a", "b"):
+        d = str(tmp_path / tag)
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", d],
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert out["steps"] == 3 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["unit"] == "passes/s"
+        assert out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-4 * out["value"]
+        for k in ("sweep_fwd_ms", "train_step_ms", "host_enqueue_ms_per_step", "batched4_ms", "config3_ms", "cpu_baseline"):
+            assert k not in out, k
+        assert set(out["roofline"]) == {"step"}
+        names = sorted(f[:-4] for f in os.listdir(d))
+        assert names == ["bn_buffers", "grads_sample", "loss", "params_sample", "q"], names
+        arr = {n: np.load(os.path.join(d, n + ".npy")) for n in names}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arr.values())
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 * 10 ** 6
+        assert arr["loss"].shape == (16,) and arr["q"].shape[0] == 16 and arr["params_sample"].shape == arr["grads_sample"].shape == (1 << 22,)
+        runs.append(arr)
+    a, b = runs
+    assert np.array_equal(a["params_sample"], b["params_sample"])
+    for k in ("loss", "q", "bn_buffers"):
+        assert np.abs(a[k] - b[k]).max() <= 1e-6 * np.abs(a[k]).max(), k
+    assert np.linalg.norm(a["grads_sample"] - b["grads_sample"]) <= 1e-5 * np.linalg.norm(a["grads_sample"])
 
 
 @pytest.mark.parametrize("size,rots", [(232, [1, 6, 10, 13]), (256, [3, 11])])
