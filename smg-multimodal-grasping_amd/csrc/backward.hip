@@ -1,10 +1,6 @@
 // backward.hip - the backward walk: replaces loss.backward() of Trainer.backprop (code/trainer.py:350-351).
 #include "engine.h"
 
-#ifndef SMG_D3_TH8
-#define SMG_D3_TH8 0      // dev A/B: 1 = the 3x3 data gradient of the big planes on 16 x 8 tiles, three workgroups per CU (round 6: built, parity green, measured SLOWER - DESIGN.md section 5.0)
-#endif
-
 // ------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------
@@ -347,9 +343,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 a.wu = e->packed_u + e->pk_hd[b][i]; a.bt = bn_table(e, e->sb_tab[b][i], e->max_streams, 0, kBottleneck, P + d.n2.w, P + d.n2.b);
                 BY(e, ESZ(e) * NS * pl.HW * (kGrowth + 2 * kBottleneck));      // gradient in, mask source in, dy out
                 ProfScope ps(e, st, K_D3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth);
-                const bool th8 = SMG_D3_TH8 && halo_tile(pl, NS) == 16 && e->prec == 0 && kSplitOp == 3 && pl.H % 8 == 0 && pl.W % 16 == 0;
-                TraceScope ts(st, K_D3, th8 ? dim3((pl.H / 8) * ((pl.W + 15) / 16), NS)
-                                            : halo_tile(pl, NS) == 16 ? dim3(((pl.H + 15) / 16) * ((pl.W + 15) / 16), NS) : dim3(((pl.H + 7) / 8) * ((pl.W + 7) / 8), NS, kBottleneck / 64));
+                TraceScope ts(st, K_D3, halo_tile(pl, NS) == 16 ? dim3(((pl.H + 15) / 16) * ((pl.W + 15) / 16), NS) : dim3(((pl.H + 7) / 8) * ((pl.W + 7) / 8), NS, kBottleneck / 64));
                 if (halo_tile(pl, NS) == 16) {
                     static bool raised[64][3] = {};          // the 16x16 kernel needs more than the default 64 KB of dynamic LDS
                     if (!raised[e->device & 63][e->prec]) {
@@ -358,11 +352,6 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                         raised[e->device & 63][e->prec] = true;
                     }
                     a.tiles_x = (pl.W + 15) / 16; a.cg_per_wg = kBottleneck / 32;
-                    if (th8) {
-                        // 16 x 8 tiles (halo.cuh): one MFMA tile per wave, 52.7 KB of LDS - three workgroups per CU instead of two
-                        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_dgrad_kernel<16, 0, false, 8>), dim3((pl.H / 8) * a.tiles_x, NS), dim3(256),
-                                           (HaloDgradSGeo<16, 0, 8>::smem_bytes(kBottleneck)), st, a);
-                    } else
                     if (pl.H % 16 || pl.W % 16) {      // tiles hang over the edge: the bounds-checked instantiation
                         PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_dgrad_kernel<16, PREC, true>), dim3(((pl.H + 15) / 16) * a.tiles_x, NS), dim3(256),
                                            (HaloDgradSGeo<16, PREC>::smem_bytes(kBottleneck)), st, a));
@@ -371,11 +360,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                                            (HaloDgradSGeo<16, PREC>::smem_bytes(kBottleneck)), st, a));
                     }
                 } else {
-                    static bool raised8[64][3] = {};         // two buffers of a whole kernel row's weights: past the default 64 KB in the fp32-class mode
-                    if (!raised8[e->device & 63][e->prec]) {
-                        PREC_DISPATCH(e, (void)hipFuncSetAttribute((const void*)conv3x3_halo_dgrad_kernel<8, PREC>, hipFuncAttributeMaxDynamicSharedMemorySize, (HaloDgradSGeo<8, PREC>::smem_bytes(kBottleneck))));
-                        raised8[e->device & 63][e->prec] = true;
-                    }
+                    static_assert(HaloDgradSGeo<8, 0>::smem_bytes(kBottleneck) <= 64 * 1024, "a tap per stage: inside the default 64 KB of dynamic LDS");
                     a.tiles_x = (pl.W + 7) / 8; a.cg_per_wg = 1;      // small planes: one 64-channel group per workgroup
                     PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_dgrad_kernel<8, PREC>), dim3(((pl.H + 7) / 8) * a.tiles_x, NS, kBottleneck / 64), dim3(256),
                                        (HaloDgradSGeo<8, PREC>::smem_bytes(kBottleneck)), st, a));

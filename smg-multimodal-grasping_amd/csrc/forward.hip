@@ -2,13 +2,6 @@
 // (code/models.py:361-586, :72-296) for one (trunk, head).
 #include "engine.h"
 
-#ifndef SMG_C1WS_BN
-#define SMG_C1WS_BN 128     // dev A/B: 64 = two 64-column workgroups per 64-row tile (rounds 3-5)
-#endif
-#ifndef SMG_FWD16_WS
-#define SMG_FWD16_WS 0
-#endif
-
 // Host-side checks of a batch against the engine (index ranges, capacities).
 int validate_batch(const smg_engine* e, const smg_batch* B) {
     const int NS = B->n_streams, NP = B->n_pairs;
@@ -190,26 +183,25 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                     const int small_wgs = 320;      // (160 / 640: 24.4 / 24.6 ms per step against 24.6; 512 / 1024 slower on the 17-stream step)
                     const int wg128 = ns * pl.HWp / 128, wg64 = ns * pl.HWp / 64 * 2;
                     if (!e->generic_c1 && e->prec == 0 && !(pl.HWp % 128 == 0 && wg128 >= small_wgs) && wg64 >= small_wgs && d.cin % 32 == 0 && pl.HWp % 64 == 0) {
-                        // wave-specialised 64 x 64 x 32 (ws.cuh)
+                        // wave-specialised 64 x 128 x 32 (ws.cuh)
                         Fwd1x1WsArgs a{};
                         a.src = xs(b); a.lds_ = Ct; a.pl = pl; a.K = d.cin;
                         a.bt = t1; a.fresh0 = i == 0 ? d.cin : d.cin - kGrowth; a.fsum = xsum; a.fsq = xsq; a.fstride = Ct; a.eps = kEps;
                         a.tw_mean = const_cast<float*>(t1.mean); a.tw_invstd = const_cast<float*>(t1.invstd);
                         a.wp = e->packed_u + e->pk_c1[b][i]; a.N = kBottleneck; a.asc = asc_n1(e, b, (int)i);
                         a.dst = bt; a.ldd = kBottleneck; a.dsum = bsum; a.dsq = bsq; a.dstride = kBottleneck;
-                        constexpr int WBN = SMG_C1WS_BN;                     // 128: one workgroup per 64-row tile covers all 128 output columns (ws.cuh)
-                        using WG_ = WsGeoT<np_of(fwd_op(0)), WBN>;
-                        const int nM = ns * pl.HWp / 64, nN = kBottleneck / WBN;
+                        using WG_ = WsGeoT<np_of(fwd_op(0))>;                // one workgroup per 64-row tile covers all 128 output columns
+                        const int nM = ns * pl.HWp / 64, nN = kBottleneck / WG_::BN;
                         a.tm = TileMap{nM, nN, 0};
                         BY(e, ESZ(e) * ns * pl.HW * (d.cin + kBottleneck));
                         ProfScope ps(e, cs, K_C1, 2.0 * ns * pl.HW * d.cin * kBottleneck);
                         const size_t smem = WG_::smem_bytes(d.cin);
                         static bool raised[64] = {};
                         if (!raised[e->device & 63]) {
-                            (void)hipFuncSetAttribute((const void*)conv1x1_fwd_ws_kernel<0, WBN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                            (void)hipFuncSetAttribute((const void*)conv1x1_fwd_ws_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                             raised[e->device & 63] = true;
                         }
-                        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv1x1_fwd_ws_kernel<0, WBN>), dim3(tile_grid(a.tm)), dim3(512), smem, cs, a);
+                        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv1x1_fwd_ws_kernel<0>), dim3(tile_grid(a.tm)), dim3(512), smem, cs, a);
                     } else
                     if (pl.HWp % 128 == 0 && wg128 >= small_wgs) run(CfgP128x128{});
                     else if (wg64 < small_wgs) run(CfgP32x64{});
@@ -248,15 +240,6 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                         if (pl.H % 16 || pl.W % 16) {      // tiles hang over the edge: the bounds-checked instantiation
                             PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_fwd_kernel<16, PREC, true>), dim3(banded_grid(a.n_tiles, ns)), dim3(256),
                                                (HaloFwdSGeo<16, PREC>::smem_bytes(kBottleneck)), cs, a));
-                        } else if (SMG_FWD16_WS) {      // (dev A/B, -DSMG_FWD16_WS=1: the wave-specialised form on the 16 x 16 tiles too)
-                            static bool raised16[64][3] = {};
-                            if (!raised16[e->device & 63][e->prec]) {
-                                PREC_DISPATCH(e, (void)hipFuncSetAttribute((const void*)conv3x3_halo_fwd_kernel<16, PREC, false, SMG_FWD16_WS != 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                           (HaloFwdSGeo<16, PREC>::smem_bytes_ws(kBottleneck))));
-                                raised16[e->device & 63][e->prec] = true;
-                            }
-                            PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_fwd_kernel<16, PREC, false, SMG_FWD16_WS != 0>), dim3(banded_grid(a.n_tiles, ns)), dim3(512),
-                                               (HaloFwdSGeo<16, PREC>::smem_bytes_ws(kBottleneck)), cs, a));
                         } else {
                             PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_fwd_kernel<16, PREC>), dim3(banded_grid(a.n_tiles, ns)), dim3(256),
                                                (HaloFwdSGeo<16, PREC>::smem_bytes(kBottleneck)), cs, a));

@@ -25,44 +25,31 @@
 #pragma once
 #include "gemm.cuh"
 
-// waves per SIMD the register allocator is held to (512 / n registers per lane); three for the 16 x 16 forward: 168 VGPRs with 128 bytes
-// of scratch, 64 -> 111 us per launch
-namespace smg { constexpr int kHaloFwdWaves = 2, kHaloWgradWaves = 2; }
-#ifndef SMG_HALO_REGFRAG
-#define SMG_HALO_REGFRAG 1      // dev A/B: 0 = every activation fragment of the TS = 16 forward / data gradient read from LDS (rounds 2-5)
-#endif
-#ifndef SMG_D3_ST8
-#define SMG_D3_ST8 1            // dev A/B: 3 = the 8 x 8 data gradient stages a whole kernel row's weights (rounds 4-5: 65 KB of LDS, two workgroups per CU)
-#endif
-#ifndef SMG_HALO_DMA
-#define SMG_HALO_DMA 1          // dev A/B: 0 = the TS = 16 data gradient's weights register-staged through two LDS buffers, one stage ahead (rounds 2-5)
-#endif
-
 namespace smg {
 
-template <int TS, int TH_ = TS>
+// waves per SIMD the register allocator is held to (512 / n registers per lane); three for the 16 x 16 forward: 168 VGPRs with 128 bytes
+// of scratch, 64 -> 111 us per launch
+constexpr int kHaloFwdWaves = 2, kHaloWgradWaves = 2;
+
+template <int TS>
 struct HaloGeo {
     static_assert(TS == 16 || TS == 8, "tile side");
-    static_assert(TH_ == TS || (TS == 16 && TH_ == 8), "tile height: square, or 16 wide x 8 high");
-    static constexpr int T = TS, TH = TH_, W = TS + 2, HH = TH + 2, PX = W * HH, NPIX = TS * TH;
+    static constexpr int T = TS, W = TS + 2, PX = W * W, NPIX = TS * TS;
     static constexpr int MT = NPIX == 256 ? 2 : 1;     // 32-pixel MFMA tiles per wave
     static constexpr int WQ = NPIX / (32 * MT);        // waves that split the pixels (4 / 2)
     static constexpr int WX = 4 / WQ;                  // the other wave factor (1 / 2)
     static constexpr int ROWS = 32 / TS;               // pixel rows per MFMA tile (2 / 4)
-    static constexpr int RP = MT + 2;                  // row pairs a wave's register-resident fragments span (rowi): 4 (16 x 16) / 3 (16 x 8)
-    static constexpr int RSTEP = TS == 16 ? (TH == 16 ? 2 : 4) : 0;      // distance of the two rows of a pair
+    static constexpr int RP = MT + 2;                  // row pairs a wave's register-resident fragments span (rowi): 4 at TS = 16
+    static constexpr int RSTEP = TS == 16 ? 2 : 0;     // distance of the two rows of a pair
     // pixel (row, col) inside the tile of MFMA-tile row i (0..31) of tile m of pixel-wave wq
     __device__ static __forceinline__ int row(int wq, int m, int i) { return (wq * MT + m) * ROWS + i / TS; }
     __device__ static __forceinline__ int col(int i) { return i % TS; }
     // TS = 16, kernels that derive their activation fragments in registers (round 6): the two pixel rows of a wave's tile m are rows
     // 4 wq + m and 4 wq + m + 2 - INTERLEAVED with the other tile's - so that the fragment of kernel row dy of tile m, input rows
     // (4 wq + m + dy, 4 wq + m + dy + 2), is the row pair i = m + dy of FOUR pairs (i = 0..3) that serve all six (tile, kernel row)
-    // combinations of the wave (consecutive rows would need six).  16 x 8 tiles (one MFMA tile per wave): rows wq and wq + 4, pairs
-    // i = dy of THREE.
-    __device__ static __forceinline__ int rowi(int wq, int m, int i) {
-        return TS == 16 ? (TH == 16 ? 4 * wq + m + 2 * (i / TS) : wq + 4 * (i / TS)) : row(wq, m, i);
-    }
-    __device__ static __forceinline__ int pair0(int wq) { return TH == 16 ? 4 * wq : wq; }      // first halo row of the wave's pair 0
+    // combinations of the wave (consecutive rows would need six).
+    __device__ static __forceinline__ int rowi(int wq, int m, int i) { return TS == 16 ? 4 * wq + m + 2 * (i / TS) : row(wq, m, i); }
+    __device__ static __forceinline__ int pair0(int wq) { return 4 * wq; }      // first halo row of the wave's pair 0
 };
 
 // compile-time loop: f(integral_constant<int, B>) ... f(integral_constant<int, N - 1>) (DPP controls must be immediates)
@@ -151,19 +138,20 @@ __device__ __forceinline__ bool banded_tile(int n_tiles, int streams, int& tile,
 }
 static inline unsigned banded_grid(int n_tiles, int streams) { return 8u * (unsigned)((n_tiles * streams + 7) / 8); }
 
-// WS (wave-specialised form, 512 threads): waves 0..3 are the kernel's four matrix waves and do nothing but fragment reads and
-// MFMAs; waves 4..7 fetch, transform and store the NEXT chunk into a second (halo, weights) buffer meanwhile - one barrier per chunk.
+// WS (wave-specialised form, 512 threads; TS = 8 only): waves 0..3 are the kernel's four matrix waves and do nothing but fragment reads
+// and MFMAs; waves 4..7 fetch, transform and store the NEXT chunk into a second (halo, weights) buffer meanwhile - one barrier per chunk.
 // Measured on the plain kernel (round 5, per launch at TS = 16 / 8): 67.5 / 17.3 us as built, 38.7 / 12.1 with the loads and the
 // transform removed, 37.1 / 12.2 with the taps removed - its two halves run one after the other even at two workgroups per CU.
 template <int TS, int PREC = 0, bool RAG = false, bool WS = false>
 static __global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : kHaloFwdWaves) void conv3x3_halo_fwd_kernel(const Halo3x3FwdArgs a) {
+    static_assert(!WS || TS == 8, "wave-specialised form: 8 x 8 tiles only");
     constexpr bool kEdge = TS == 8 || RAG;
     using G = HaloFwdSGeo<TS, PREC>;
     using ST = act_t<PREC>;
     constexpr int OP = fwd_op(PREC), NP = G::NP, CK = G::CK, K8C = G::K8C, KSTEP = CK / 16;
     constexpr int MT = G::MT, A_N = G::A_N, B_N = G::B_N, LDH = G::LDH, ESZ = ST::size, E = 16 / ESZ;
     constexpr int BUF_BYTES = WS ? (G::A_UNITS + G::BU) * 16 : 0;       // WS: two (halo, weights) buffers, the weights exactly BU units
-    constexpr bool kRegFrag = TS == 16 && OP != 0 && SMG_HALO_REGFRAG;                       // activation fragments of a chunk from four row pairs + DPP column shifts (taps16 below)
+    constexpr bool kRegFrag = TS == 16 && OP != 0;                       // activation fragments of a chunk from four row pairs + DPP column shifts (taps16 below)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* As = reinterpret_cast<char*>(smem);                // [piece][k8][LDH] units          (WS: of the buffer being read)
     char* Bs = As + G::A_UNITS * 16;                         // [piece][tap][k8][32] units
@@ -201,8 +189,8 @@ static __global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : kHaloFwdWaves) void
     }
     const char* src_n = static_cast<const char*>(a.src) + (int64_t)ESZ * n * a.pl.HWp * a.lds_;
     const u32x4* wu = a.wu;
-    constexpr int NSET = 1;              // register sets of loads in flight (WS with two sets, loads two chunks ahead: 63.2 -> 72.8 us per launch at TS = 16 - the
-                                         // 128-register budget of the 16-wave CU is gone - and 15.3 -> 15.2 at TS = 8: one chunk of taps covers the loads)
+    constexpr int NSET = 1;              // register sets of loads in flight (WS with two sets, loads two chunks ahead: 15.3 -> 15.2 us per launch - one
+                                         // chunk of taps covers the loads)
     float4 ra_[NSET][A_N]; u32x4 rb_[NSET][B_N];
     using Set0 = std::integral_constant<int, 0>;
     auto g_load = [&](int chunk, auto SET) {
@@ -529,34 +517,29 @@ struct Halo3x3DgradArgs {
 // barrier per stage, prefetched into registers under the stage's MFMAs.  A stage is two k16-steps (32 gradient channels)
 // per pixel tile; after the ninth tap of a chunk the epilogue applies the ReLU mask and collects the norm2 sums.
 // ------------------------------------------------------------------------------------
-template <int TS, int PREC, int TH = TS> struct HaloDgradSGeo : HaloGeo<TS, TH> {
-    using G = HaloGeo<TS, TH>;
+template <int TS, int PREC> struct HaloDgradSGeo : HaloGeo<TS> {
+    using G = HaloGeo<TS>;
     static constexpr int NP = np_of(bwd_op(PREC));
     static constexpr int BU = NP * 4 * 32;                               // weight units per (tap, 32-channel chunk): 384 / 256 / 128
     static constexpr int LDH = G::PX;
-    static constexpr int A_UNITS_ = NP * 4 * LDH;
+    static constexpr int A_UNITS = NP * 4 * LDH;
     static constexpr int A_N = (G::PX * (PREC ? 4 : 8) + 255) / 256;     // 16-byte slots per thread (32 gradient channels per pixel)
     static constexpr int NCW = G::WX;                                    // output-channel chunks per stage
     // taps per stage.  16 x 16 tiles: one kernel row (a stage per tap spent more on its barrier than on its 12 MFMAs).  8 x 8 tiles: ONE tap
     // (round 6) - two buffers of a whole row's weights for 64 output channels made 65 KB of LDS, two workgroups per CU, and the 850
     // workgroups of a 17-stream launch on the 40^2 planes ran in TWO rounds (per-workgroup stamps: the second starts 10 us in; span 18.5-20.8 us
     // for lives of 8-9); a tap per stage is 33 KB - four per CU, one round.
-    static constexpr int ST = TS == 8 ? SMG_D3_ST8 : 3;
+    static constexpr int ST = TS == 8 ? 1 : 3;
     static constexpr int B_UNITS = NCW * ST * BU;                        // per buffer
     static constexpr int B_N = (B_UNITS + 255) / 256;
     static constexpr int B_PAD = B_N * 256;                              // units per buffer incl. the padding the last copy round touches
-    // (16 x 8 tiles: the halo area is rounded up to two ring buffers - it hosts buffers 2 and 3 of the weights' LDS-DMA ring once the
-    //  gradient fragments are in registers; 52.7 KB, three workgroups per CU)
-    static constexpr int A_UNITS = (TH != TS && A_UNITS_ < 2 * B_PAD) ? 2 * B_PAD : A_UNITS_;
     __host__ __device__ static constexpr int smem_bytes(int C) { return (A_UNITS + 2 * B_PAD) * 16 + (4 * C + 256 + 128) * 4; }
 };
 
-// TH = 8 with TS = 16 (round 6): 16 x 8 tiles, one MFMA tile per wave - half the accumulators, fragments and mask prefetch per wave,
-// 52.7 KB of LDS: THREE workgroups per CU where the 16 x 16 form (252 registers, 66 KB) holds two.
-template <int TS, int PREC = 0, bool RAG = false, int TH = TS>
-static __global__ __launch_bounds__(256, TS == 8 ? 4 : (TH == TS ? 2 : 3)) void conv3x3_halo_dgrad_kernel(const Halo3x3DgradArgs a) {
+template <int TS, int PREC = 0, bool RAG = false>
+static __global__ __launch_bounds__(256, TS == 8 ? 4 : 2) void conv3x3_halo_dgrad_kernel(const Halo3x3DgradArgs a) {
     constexpr bool kEdge = TS == 8 || RAG;
-    using G = HaloDgradSGeo<TS, PREC, TH>;
+    using G = HaloDgradSGeo<TS, PREC>;
     using GT = grd_t<PREC>;
     using XT = act_t<PREC>;
     constexpr int OP = bwd_op(PREC), NP = G::NP, HDS_BU = G::BU, GSZ = GT::size, XSZ = XT::size, E = 16 / GSZ, SPP = 32 / E;   // SPP: slots per pixel
@@ -564,10 +547,10 @@ static __global__ __launch_bounds__(256, TS == 8 ? 4 : (TH == TS ? 2 : 3)) void 
     // gradient fragments resident in registers: four row pairs + DPP column shifts (below).  Precision mode 0 only: in the 16-bit modes the
     // resident fragments take the bounds-checked instantiation from 161 to 169 registers - two waves per SIMD instead of three, 62.9 -> 70.6 us
     // per launch on config 5's planes - and gain nothing where they fit (45.6 us both ways on config 3's)
-    constexpr bool kRegFrag = TS == 16 && OP == 3 && SMG_HALO_REGFRAG;
+    constexpr bool kRegFrag = TS == 16 && OP == 3;
     // ... and with the halo out of LDS after the prologue, the weights of the stages stream through a RING of four LDS buffers by LDS-DMA
     // (two behind the halo, two in the halo's own area once the fragments are in registers), three stages ahead of the MFMAs - see below
-    constexpr bool kDma = kRegFrag && G::NCW == 1 && G::B_UNITS % 256 == 0 && 2 * G::B_PAD <= G::A_UNITS && SMG_HALO_DMA;
+    constexpr bool kDma = kRegFrag && G::NCW == 1 && G::B_UNITS % 256 == 0 && 2 * G::B_PAD <= G::A_UNITS;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* As = reinterpret_cast<char*>(smem);                            // [piece][k8][LDH] units
     char* Bs = As + G::A_UNITS * 16;                                     // [2][NCW][3 taps][piece][k8][32] units
@@ -576,7 +559,7 @@ static __global__ __launch_bounds__(256, TS == 8 ? 4 : (TH == TS ? 2 : 3)) void 
     const int wq = wave % G::WQ, wc = wave / G::WQ;     // pixel slice, output-channel chunk of the stage
     const int n = blockIdx.y;
     const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
-    const int y0 = ty * TH, x0 = tx * TS;
+    const int y0 = ty * TS, x0 = tx * TS;
     const int C = a.C;
     // dev stamps (SMG_TRACE_KIND=5): start | halo staged | first output-channel group's 9 stages | its epilogue | end
     unsigned long long* trace = (g_smg_trace && t == 0) ? g_smg_trace + 8 * ((size_t)blockIdx.x + (size_t)gridDim.x * (blockIdx.y + (size_t)gridDim.y * blockIdx.z)) : nullptr;

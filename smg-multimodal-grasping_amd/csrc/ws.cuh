@@ -9,6 +9,10 @@
 //   waves 4..7  producers: global loads (two k-tiles in flight), BN + ReLU + split, LDS stores of k-tile kt + 1
 // One barrier per k-tile.  Every SIMD holds one consumer and one producer wave of the workgroup, so the MFMA pipe works
 // while the VALU splits the next tile - inside one workgroup, whatever else is resident.
+// 64 x 128 tiles (round 6): ONE workgroup per 64-row tile covers all 128 output columns - the activations are loaded, BN + ReLU'd
+// and split once instead of once per 64-column tile (the producers' instruction work per output halves; the small planes' waves are
+// issue-bound, DESIGN.md section 9), each consumer wave carries two accumulator tiles.  62 KB of LDS at K = 992: two per CU,
+// 425 workgroups of a 17-stream 40^2 launch in one round.
 // Same arithmetic, LDS images and epilogue as FwdConvP<GemmCfg<64, 64, 32, 2, 2, 1, true>, F_ONE> (results equal to fp32
 // summation order: the k order per accumulator is unchanged).
 #pragma once
@@ -28,11 +32,11 @@ struct Fwd1x1WsArgs {
     TileMap tm;                                    // XCD-aware order: the N tiles of one M tile are consecutive on one XCD
 };
 
-template <int NP_, int BN_ = 64>
+template <int NP_>
 struct WsGeoT {
     static constexpr int NP = NP_;                                    // pieces per operand (3: bf16 split, 2: fp16 split)
-    static constexpr int BM = 64, BN = BN_, BK = 32, K8 = BK / 8;
-    static constexpr int TN = BN / 64;                                // 32-column accumulator tiles per consumer wave (2 x 2 waves)
+    static constexpr int BM = 64, BN = 128, BK = 32, K8 = BK / 8;
+    static constexpr int TN = 2;                                      // 32-column accumulator tiles per consumer wave (2 x 2 waves)
     static constexpr int LDUA = BM + 2, LDUB = BN;                    // A rows padded as in GemmCfg (64 / BK units)
     static constexpr int A_BYTES = NP * K8 * LDUA * 16, B_BYTES = NP * K8 * LDUB * 16;
     static constexpr int A_N = BM * (BK / 4) / 256;                   // 2 float4 per producer thread
@@ -41,17 +45,10 @@ struct WsGeoT {
     __host__ __device__ static constexpr int smem_bytes(int K) { return TILE_BYTES + 3 * K * 4; }
 };
 
-using WsGeo = WsGeoT<np_of(fwd_op(0))>;
-// BN = 128 (round 6): ONE workgroup per 64-row tile covers all 128 output columns - the activations are loaded, BN + ReLU'd and split
-// once instead of once per 64-column tile (the producers' instruction work per output halves; the small planes' waves are
-// issue-bound, DESIGN.md section 9), each consumer wave carries two accumulator tiles.  62 KB of LDS at K = 992: two per CU,
-// 425 workgroups of a 17-stream 40^2 launch in one round.
-using WsGeo128 = WsGeoT<np_of(fwd_op(0)), 128>;
-
-template <int PREC = 0, int BN = 64>
+template <int PREC = 0>
 static __global__ __launch_bounds__(512, 1) void conv1x1_fwd_ws_kernel(const Fwd1x1WsArgs a) {
     static_assert(PREC == 0, "fp32 storage only");
-    using G = WsGeoT<np_of(fwd_op(0)), BN>;
+    using G = WsGeoT<np_of(fwd_op(0))>;
     constexpr int TN = G::TN;
     constexpr int OP = fwd_op(PREC), NP = G::NP;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -136,7 +133,7 @@ static __global__ __launch_bounds__(512, 1) void conv1x1_fwd_ws_kernel(const Fwd
     if (role == 1) s_store(0, 0, ra[0], rb[0]);
     __syncthreads();
 
-    // ---- consumers: accumulator and fragment geometry (2 x 2 waves, one 32 x 32 tile each)
+    // ---- consumers: accumulator and fragment geometry (2 x 2 waves, two 32 x 32 tiles each)
     f32x16 acc[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j)
@@ -156,7 +153,7 @@ static __global__ __launch_bounds__(512, 1) void conv1x1_fwd_ws_kernel(const Fwd
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bf[j][pc] = *reinterpret_cast<const u32x4*>(B + ((pc * G::K8 + k8) * G::LDUB + wn0 + 32 * j + l31) * 16);
             }
-            if constexpr (OP == 3) {             // term groups outermost, tiles innermost: consecutive MFMAs never share an accumulator (TN = 2)
+            if constexpr (OP == 3) {             // term groups outermost, tiles innermost: consecutive MFMAs never share an accumulator
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc[j] = mfma_f16(af[0], bf[j][1], acc[j]);
 #pragma unroll
