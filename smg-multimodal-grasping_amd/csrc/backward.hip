@@ -71,11 +71,10 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         BnBwdApplyArgs a{};
         a.g = e->G[b]; a.ldg = Ct; a.gcoff = d.cin; a.x = e->X[b]; a.ldx = Ct; a.xcoff = d.cin; a.pl = pl; a.C = kGrowth;
         a.xsum = fsum(e, e->st_X[b]); a.xsq = fsq(e, e->st_X[b]); a.xstride = Ct; a.xtab = stat_table(e, e->sx_tab[b], e->max_streams, Ct);
-        a.s1 = b1(e, e->bs_X[b]); a.s2 = b2(e, e->bs_X[b]); a.sstride = Ct; a.scoff = d.cin; a.gamma = nullptr; a.eps = kEps;
+        a.s1 = b1(e, e->st_X[b]); a.s2 = b2(e, e->st_X[b]); a.sstride = Ct; a.scoff = d.cin; a.gamma = nullptr; a.eps = kEps;
         a.out = GSb; a.ldo = kGrowth; a.amax = split16 ? gamax_of(e, b, i, 0) : nullptr;
-        BY(e, ESZ(e) * NS * pl.HW * 3 * kGrowth);
-        ProfScope ps(e, cs, K_OTHER, 0);
-        PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(bn_bwd_apply_kernel<PREC>), dim3((pl.HWp + bn_apply_rows(PREC) - 1) / bn_apply_rows(PREC), NS), dim3(256), 0, cs, a));
+        PREC_DISPATCH(e, launch_kernel(e, bn_bwd_apply_kernel<PREC>, dim3((pl.HWp + bn_apply_rows(PREC) - 1) / bn_apply_rows(PREC), NS), dim3(256), 0, cs,
+                                       K_OTHER, 0, ESZ(e) * NS * pl.HW * 3 * kGrowth, false, a));
     };
 
     if (ph_a) {
@@ -84,9 +83,8 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         a.h1 = e->H1; a.p4 = p4; a.hsum = fsum(e, e->st_H1); a.hsq = fsq(e, e->st_H1);
         a.gamma = P + Hd.n1.w; a.beta = P + Hd.n1.b; a.eps = kEps; a.w2p = e->packed_f + e->pk_head1;
         a.dq = dq; a.out_ch = e->head_out; a.OH = e->OH; a.OW = e->OW; a.dh1 = e->DH1;
-        a.o1 = b1(e, e->bs_H1); a.o2 = b2(e, e->bs_H1); a.dbeta = Gr + Hd.n1.b; a.dgamma = Gr + Hd.n1.w; a.dw2 = Gr + Hd.c1.w;
-        ProfScope ps(e, st, K_OTHER, 0);
-        hipLaunchKernelGGL(value_bwd_kernel, dim3((p4.HW + 63) / 64, NP), dim3(256), 0, st, a);
+        a.o1 = b1(e, e->st_H1); a.o2 = b2(e, e->st_H1); a.dbeta = Gr + Hd.n1.b; a.dgamma = Gr + Hd.n1.w; a.dw2 = Gr + Hd.c1.w;
+        launch_kernel(e, value_bwd_kernel, dim3((p4.HW + 63) / 64, NP), dim3(256), 0, st, K_OTHER, 0, 0, false, a);
     }
     int chunk4, cps4;
     pick_chunk(p4, NP, 2 * kFeat / 64, chunk4, cps4);
@@ -95,14 +93,14 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         BwdWeightP<CfgW64x64, W_ONE, C_IDENT, kPdWgrad, true, decltype(ptag)::value, true> p{};      // fp32 head buffers in every mode
         p.gbuf = e->DH1; p.ldg = kHeadMid; p.gcoff = 0; p.xbuf = e->H1; p.ldx = kHeadMid; p.xcoff = 0; p.pa = p4; p.MA = kHeadMid;
         p.xsum = fsum(e, e->st_H1); p.xsq = fsq(e, e->st_H1); p.xstride = kHeadMid;
-        p.s1 = b1(e, e->bs_H1); p.s2 = b2(e, e->bs_H1); p.sstride = kHeadMid; p.scoff = 0; p.agamma = P + Hd.n1.w;
+        p.s1 = b1(e, e->st_H1); p.s2 = b2(e, e->st_H1); p.sstride = kHeadMid; p.scoff = 0; p.agamma = P + Hd.n1.w;
         p.bbuf = e->F; p.ldb = 2 * kFeat; p.pb = p4; p.NB = 2 * kFeat;
         p.bsum = fsum(e, e->st_F); p.bsq = fsq(e, e->st_F); p.bstride = 2 * kFeat; p.bgamma = P + Hd.n0.w; p.bbeta = P + Hd.n0.b;
         p.eps = kEps; p.chunk = chunk4; p.chunks_per_stream = cps4; p.n_chunks = NP * cps4;
         p.dw = Gr + Hd.c0.w; p.ldw_out = 2 * kFeat;
         if (fork(e->ev_misc)) return -5;
-        BY(e, 4.0 * NP * p4.HW * (2 * kHeadMid + 2 * kFeat));
-        return launch_wgrad(e, s2, p, dim3(1, 2 * kFeat / 64, NP * cps4), K_HW0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid, 1, C_IDENT);
+        return launch_wgrad(e, s2, p, dim3(1, 2 * kFeat / 64, NP * cps4), K_HW0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid,
+                            4.0 * NP * p4.HW * (2 * kHeadMid + 2 * kFeat), 1, C_IDENT);
         };
         PREC_DISPATCH(e, if (int rc = go(PTAG)) return rc);
     }
@@ -112,28 +110,27 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 BwdDataP<Cfg, false, E_STORE, true, decltype(ptag)::value, true> p{};      // fp32 head buffers in every mode
         p.gbuf = e->DH1; p.ldg = kHeadMid; p.gcoff = 0; p.xbuf = e->H1; p.ldx = kHeadMid; p.xcoff = 0; p.pa = p4; p.KA = kHeadMid;
         p.xsum = fsum(e, e->st_H1); p.xsq = fsq(e, e->st_H1); p.xstride = kHeadMid;
-        p.s1 = b1(e, e->bs_H1); p.s2 = b2(e, e->bs_H1); p.sstride = kHeadMid; p.scoff = 0; p.agamma = P + Hd.n1.w;
+        p.s1 = b1(e, e->st_H1); p.s2 = b2(e, e->st_H1); p.sstride = kHeadMid; p.scoff = 0; p.agamma = P + Hd.n1.w;
         p.wp = e->packed_u + e->pk_hd0; p.K8tot = kHeadMid / 8; p.ldn = 2 * kFeat; p.wcol0 = 0; p.N = 2 * kFeat;
         p.mbuf = e->F; p.ldm = 2 * kFeat; p.mcoff = 0; p.pm = p4;
         p.msum = fsum(e, e->st_F); p.msq = fsq(e, e->st_F); p.mstride = 2 * kFeat; p.egamma = P + Hd.n0.w; p.ebeta = P + Hd.n0.b;
         p.dst = e->DF; p.ldd = 2 * kFeat; p.dcoff = 0;
-        p.o1 = b1(e, e->bs_F); p.o2 = b2(e, e->bs_F); p.ostride = 2 * kFeat; p.ocoff = 0;
+        p.o1 = b1(e, e->st_F); p.o2 = b2(e, e->st_F); p.ostride = 2 * kFeat; p.ocoff = 0;
         p.dbeta = Gr + Hd.n0.b; p.dgamma = Gr + Hd.n0.w; p.rep_stride = 0; p.eps = kEps;
-        BY(e, 4.0 * NP * p4.HW * (2 * kHeadMid + 2 * 2 * kFeat));
-        launch_gemm(e, st, p, dim3(NP * p4.HWp / Cfg::BM, 2 * kFeat / Cfg::BN), K_HD0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid);
+        launch_gemm(e, st, p, dim3(NP * p4.HWp / Cfg::BM, 2 * kFeat / Cfg::BN), K_HD0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid,
+                    4.0 * NP * p4.HW * (2 * kHeadMid + 2 * 2 * kFeat));
             };
             PREC_DISPATCH(e, if (p4.HWp % 128 == 0) run(CfgP128x128{}, PTAG); else run(CfgP64x128{}, PTAG));
     }
     {   // head norm0 backward + concat backward + norm5 backward -> G'_4
         Norm5BwdArgs a;
         a.DF = e->DF; a.F = e->F; a.p4 = p4; a.fsum = fsum(e, e->st_F); a.fsq = fsq(e, e->st_F);
-        a.f1 = b1(e, e->bs_F); a.f2 = b2(e, e->bs_F); a.hgamma = P + Hd.n0.w;
+        a.f1 = b1(e, e->st_F); a.f2 = b2(e, e->st_F); a.hgamma = P + Hd.n0.w;
         a.x4 = e->X[3]; a.xsum = fsum(e, e->st_X[3]); a.xsq = fsq(e, e->st_X[3]); a.gamma5 = P + T.norm5.w; a.eps = kEps;
         a.user_ptr = e->d_user_ptr; a.user_pair = e->d_user_pair; a.user_slot = e->d_user_slot;
-        a.G4 = e->G[3]; a.SA = b1(e, e->bs_X[3]); a.SB = b2(e, e->bs_X[3]);
+        a.G4 = e->G[3]; a.SA = b1(e, e->st_X[3]); a.SB = b2(e, e->st_X[3]);
         a.dbeta5 = Gr + T.norm5.b; a.dgamma5 = Gr + T.norm5.w; a.chunk = 16;
-        ProfScope ps(e, st, K_OTHER, 0);
-        PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(norm5_bwd_kernel<PREC>), dim3(4, NS, (p4.HW + 15) / 16), dim3(256), 0, st, a));
+        PREC_DISPATCH(e, launch_kernel(e, norm5_bwd_kernel<PREC>, dim3(4, NS, (p4.HW + 15) / 16), dim3(256), 0, st, K_OTHER, 0, 0, false, a));
     }
     }   // ph_a: head
     // Buffers of a dense layer's finished gradients (GS: its 32 output channels, D2: its bottleneck, D2S: D2's block scales): a ring of
@@ -155,7 +152,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
     // workspace.  (The side stream is the longer one in a single-sample step: 29 reduce launches of ~7.5 us less on it.)
     ReduceArgs pend3{}; pend3.Z = 0;
     int pend3_half = 0;
-    auto flush_pending_reduce = [&]() { if (pend3.Z) { launch_reduce2(e, s2, K_W3, pend3, ReduceArgs{}); pend3.Z = 0; } };
+    auto flush_pending_reduce = [&]() { if (pend3.Z) { launch_reduce2(e, s2, pend3, ReduceArgs{}); pend3.Z = 0; } };
     auto issue_wgrads = [&](int b, int i) -> int {
         const Plane pl = e->p_blk[b];
         const int Ct = kBlockCtot[b];
@@ -168,7 +165,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         else {
             gsrc.g = el(e, e->G[b], d.cin); gsrc.ldg = Ct; gsrc.x = el(e, e->X[b], d.cin); gsrc.ldx = Ct;
             gsrc.xsum = fsum(e, e->st_X[b]) + d.cin; gsrc.xsq = fsq(e, e->st_X[b]) + d.cin;
-            gsrc.s1 = b1(e, e->bs_X[b]) + d.cin; gsrc.s2 = b2(e, e->bs_X[b]) + d.cin; gsrc.sstride = Ct; gsrc.eps = kEps;
+            gsrc.s1 = b1(e, e->st_X[b]) + d.cin; gsrc.s2 = b2(e, e->st_X[b]) + d.cin; gsrc.sstride = Ct; gsrc.eps = kEps;
         }
         ReduceArgs red3{}; red3.Z = 0;            // the 3x3 weight gradient's reduction, launched together with the 1x1 one below
         int64_t part3_floats = 0;                 // ... and the partial-tile floats it occupies
@@ -190,30 +187,28 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             a.part = part3;
             a.groups = groups; a.streams = NS;
             const unsigned w3_grid = (unsigned)(((groups * NS + 7) / 8) * 8 * (kBottleneck / 32));      // (see the kernel: channel groups of a tile group share an XCD)
-            {
-                BY(e, ESZ(e) * NS * pl.HW * (kGrowth + kBottleneck));
-                ProfScope ps(e, s2, K_W3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth);
-                if (ts == 16) {
-                    PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_wgrad_kernel<16, PREC>), dim3(w3_grid), dim3(256),
-                                                        (HaloWgradSGeo<16, PREC>::smem_bytes()), s2, a));
-                } else {
-                    PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_wgrad_kernel<8, PREC>), dim3(w3_grid), dim3(256),
-                                                        (HaloWgradSGeo<8, PREC>::smem_bytes()), s2, a));
-                }
+            const double flops = 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth, bytes = ESZ(e) * NS * pl.HW * (kGrowth + kBottleneck);
+            if (ts == 16) {
+                PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_wgrad_kernel<16, PREC>, dim3(w3_grid), dim3(256), HaloWgradSGeo<16, PREC>::smem_bytes(), s2,
+                                               K_W3, flops, bytes, false, a));
+            } else {
+                PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_wgrad_kernel<8, PREC>, dim3(w3_grid), dim3(256), HaloWgradSGeo<8, PREC>::smem_bytes(), s2,
+                                               K_W3, flops, bytes, false, a));
             }
             red3.part = part3; red3.Z = groups * NS; red3.taps = 9; red3.rows = kGrowth; red3.cols = kBottleneck; red3.ldp = kBottleneck;
             red3.z_stride = (int64_t)9 * kGrowth * kBottleneck; red3.tap_stride = (int64_t)kGrowth * kBottleneck;
             red3.dw = Gr + d.c2.w; red3.ldw_out = kBottleneck * 9; red3.cmap = C_3x3;
             part3_floats = (int64_t)groups * NS * 9 * kGrowth * kBottleneck;
             if (pair_reduce) {       // this layer's reduce rides with the next layer's (or the final flush)
-                if (pend3.Z) { launch_reduce2(e, s2, K_W3, pend3, red3); pend3.Z = 0; }
+                if (pend3.Z) { launch_reduce2(e, s2, pend3, red3); pend3.Z = 0; }
                 else pend3 = red3;
                 pend3_half ^= 1;
                 red3.Z = 0; part3_floats = 0;
             }
         } else {   // conv2 weight gradient (generic implicit GEMM, one launch slice per tap)
             flush_pending_reduce();
-            const int chunk = 512, cps = (pl.HWp + chunk - 1) / chunk;   // latency-bound: many short workgroups
+            int chunk, cps;
+            pick_chunk(pl, NS, 9, chunk, cps);      // (9 workgroups per chunk: one per tap)
             BwdWeightP<CfgW32x128, W_THREE, C_3x3, kPdWgrad, false> p{};
             p.gbuf = lb.GS; p.ldg = kGrowth; p.gcoff = 0; p.xbuf = nullptr; p.pa = pl; p.MA = kGrowth;
             p.bbuf = bt; p.ldb = kBottleneck; p.pb = pl; p.NB = kBottleneck;
@@ -221,8 +216,8 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             p.bgamma = P + d.n2.w; p.bbeta = P + d.n2.b; p.eps = kEps;
             p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
             p.dw = Gr + d.c2.w; p.ldw_out = kBottleneck * 9;
-            BY(e, ESZ(e) * NS * pl.HW * (kGrowth + kBottleneck));
-            if (int rc = launch_wgrad(e, s2, p, dim3(1, 1, 9 * NS * cps), K_W3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth, 9, C_3x3)) return rc;
+            if (int rc = launch_wgrad(e, s2, p, dim3(1, 1, 9 * NS * cps), K_W3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth,
+                                      ESZ(e) * NS * pl.HW * (kGrowth + kBottleneck), 9, C_3x3)) return rc;
         }
         // conv1 weight gradient, wave-specialised (wsw.cuh): 128 x 128 tiles, 32-pixel k-tiles, loader + matrix waves - for the partial-tile
         // form (more than four streams, or "deterministic") on layers of more than 64 input channels (a half-empty 128-column tile
@@ -240,29 +235,20 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             const bool w1_part = e->deterministic || NS > 4;
             const int64_t need = (int64_t)a.n_chunks * G::BM * a.ldp;
             int64_t off1 = part3_floats;
-            if (red3.Z && (!w1_part || off1 + need > e->part_floats)) { launch_reduce2(e, s2, K_W3, red3, ReduceArgs{}); red3.Z = 0; off1 = 0; }
+            if (red3.Z && (!w1_part || off1 + need > e->part_floats)) { launch_reduce2(e, s2, red3, ReduceArgs{}); red3.Z = 0; off1 = 0; }
             a.part = (w1_part && off1 + need <= e->part_floats) ? e->part + off1 : nullptr;
             if (w1_part && !a.part && e->deterministic)
                 return fail(-12, "deterministic: a weight-gradient launch needs " + std::to_string(need) + " partial-tile floats, the workspace holds " + std::to_string(e->part_floats - off1));
             a.tm = TileMap{a.n_chunks, nt, 0};
-            const size_t smem = G::smem_bytes(chunk);
-            static bool raised[64] = {};
-            if (!raised[e->device & 63]) {
-                (void)hipFuncSetAttribute((const void*)conv1x1_wgrad_ws_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                raised[e->device & 63] = true;
-            }
-            {
-                BY(e, 4.0 * NS * pl.HW * (kBottleneck + d.cin));
-                ProfScope ps(e, s2, K_W1, 2.0 * NS * pl.HW * d.cin * kBottleneck);
-                hipLaunchKernelGGL(conv1x1_wgrad_ws_kernel, dim3(tile_grid(a.tm)), dim3(512), smem, s2, a);
-            }
+            launch_kernel(e, conv1x1_wgrad_ws_kernel, dim3(tile_grid(a.tm)), dim3(512), G::smem_bytes(chunk), s2, K_W1,
+                          2.0 * NS * pl.HW * d.cin * kBottleneck, 4.0 * NS * pl.HW * (kBottleneck + d.cin), false, a);
             ReduceArgs red1{}; red1.Z = 0;
             if (a.part) {
                 red1.part = a.part; red1.Z = a.n_chunks; red1.taps = 1; red1.rows = G::BM; red1.cols = d.cin; red1.ldp = a.ldp;
                 red1.z_stride = (int64_t)G::BM * a.ldp; red1.tap_stride = (int64_t)a.n_chunks * G::BM * a.ldp;
                 red1.dw = a.dw; red1.ldw_out = d.cin; red1.cmap = C_IDENT;
             }
-            launch_reduce2(e, s2, K_W1, red3, red1);
+            launch_reduce2(e, s2, red3, red1);
         } else {   // conv1 weight gradient.  ~320 workgroups: it shares the chip with the data-gradient chain on the other stream
             // (256..384 measure the same, 512 / 768 / 1024 cost the step 0.15 / 0.35 / 0.75 ms)
             using Cfg = CfgW128x64;
@@ -281,7 +267,6 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 p.bgamma = P + d.n1.w; p.bbeta = P + d.n1.b; p.eps = kEps;
                 p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
                 p.dw = Gr + d.c1.w; p.ldw_out = d.cin;
-                BY(e, ESZ(e) * NS * pl.HW * (kBottleneck + d.cin));
                 // partial tiles + the fixed-order reduce (reproducible; since reduce_partials splits the partials over four waves it
                 // beats 128 x 64 fp32 atomics per workgroup); a few streams: host-launch-bound, atomics save the reduce launches
                 const bool w1_part = e->deterministic || NS > 4;
@@ -289,9 +274,10 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 // reduction runs first and the workspace is reused)
                 ReduceArgs red1{}; red1.Z = 0;
                 int64_t off1 = part3_floats;
-                if (red3.Z && (!w1_part || off1 + (int64_t)NS * cps * Cfg::BM * nt * Cfg::BN > e->part_floats)) { launch_reduce2(e, s2, K_W3, red3, ReduceArgs{}); red3.Z = 0; off1 = 0; }
-                if (int rc = launch_wgrad(e, s2, p, dim3(1, nt, NS * cps), K_W1, 2.0 * NS * pl.HW * d.cin * kBottleneck, 1, C_IDENT, w1_part, off1, &red1)) return rc;
-                launch_reduce2(e, s2, K_W1, red3, red1);
+                if (red3.Z && (!w1_part || off1 + (int64_t)NS * cps * Cfg::BM * nt * Cfg::BN > e->part_floats)) { launch_reduce2(e, s2, red3, ReduceArgs{}); red3.Z = 0; off1 = 0; }
+                if (int rc = launch_wgrad(e, s2, p, dim3(1, nt, NS * cps), K_W1, 2.0 * NS * pl.HW * d.cin * kBottleneck,
+                                          ESZ(e) * NS * pl.HW * (kBottleneck + d.cin), 1, C_IDENT, w1_part, off1, &red1)) return rc;
+                launch_reduce2(e, s2, red3, red1);
                 return 0;
             };
             PREC_DISPATCH(e, if (int rc = go(PTAG)) return rc);
@@ -303,7 +289,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         flush_pending_reduce();
         HIP_OK(hipEventRecord(e->ev_end, s2));
         HIP_OK(hipStreamWaitEvent(st, e->ev_end, 0));
-        HIP_OK(hipGetLastError());
+        if (int rc = walk_status(e)) return rc;
         e->have_fwd = false; e->bw_phase0_done = false; e->prof_stage = -1;
         return 0;
     };
@@ -329,7 +315,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             GradSrc gsrc{};
             gsrc.g = el(e, e->G[b], d.cin); gsrc.ldg = Ct; gsrc.x = el(e, e->X[b], d.cin); gsrc.ldx = Ct;
             gsrc.xsum = fsum(e, e->st_X[b]) + d.cin; gsrc.xsq = fsq(e, e->st_X[b]) + d.cin;
-            gsrc.s1 = b1(e, e->bs_X[b]) + d.cin; gsrc.s2 = b2(e, e->bs_X[b]) + d.cin; gsrc.sstride = Ct; gsrc.eps = kEps;
+            gsrc.s1 = b1(e, e->st_X[b]) + d.cin; gsrc.s2 = b2(e, e->st_X[b]) + d.cin; gsrc.sstride = Ct; gsrc.eps = kEps;
             if (e->generic3x3 || (gs_materialised && !gs_on_side(pl))) {
                 launch_gs_apply(b, i, st, GSb);
                 if (gs_materialised) { gsrc = GradSrc{}; gsrc.g = GSb; gsrc.ldg = kGrowth; gsrc.amax = gamax_of(e, b, i, 0); }
@@ -339,31 +325,24 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 Halo3x3DgradArgs a;
                 a.g = gsrc; a.pl = pl; a.C = kBottleneck;
                 a.mbuf = bt;
-                a.dst = split16 ? e->DY2 : D2b; a.o1 = b1(e, e->bs_Bt[b][i]); a.o2 = b2(e, e->bs_Bt[b][i]); a.ostride = kBottleneck;
+                a.dst = split16 ? e->DY2 : D2b; a.o1 = b1(e, e->st_Bt[b][i]); a.o2 = b2(e, e->st_Bt[b][i]); a.ostride = kBottleneck;
                 a.wu = e->packed_u + e->pk_hd[b][i]; a.bt = bn_table(e, e->sb_tab[b][i], e->max_streams, 0, kBottleneck, P + d.n2.w, P + d.n2.b);
-                BY(e, ESZ(e) * NS * pl.HW * (kGrowth + 2 * kBottleneck));      // gradient in, mask source in, dy out
-                ProfScope ps(e, st, K_D3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth);
-                TraceScope ts(st, K_D3, halo_tile(pl, NS) == 16 ? dim3(((pl.H + 15) / 16) * ((pl.W + 15) / 16), NS) : dim3(((pl.H + 7) / 8) * ((pl.W + 7) / 8), NS, kBottleneck / 64));
+                // (traced launches: dev stamps with SMG_TRACE_KIND=5)
+                const double flops = 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth;
+                const double bytes = ESZ(e) * NS * pl.HW * (kGrowth + 2 * kBottleneck);      // gradient in, mask source in, dy out
                 if (halo_tile(pl, NS) == 16) {
-                    static bool raised[64][3] = {};          // the 16x16 kernel needs more than the default 64 KB of dynamic LDS
-                    if (!raised[e->device & 63][e->prec]) {
-                        PREC_DISPATCH(e, (void)hipFuncSetAttribute((const void*)conv3x3_halo_dgrad_kernel<16, PREC>, hipFuncAttributeMaxDynamicSharedMemorySize, (HaloDgradSGeo<16, PREC>::smem_bytes(kBottleneck))));
-                        PREC_DISPATCH(e, (void)hipFuncSetAttribute((const void*)conv3x3_halo_dgrad_kernel<16, PREC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (HaloDgradSGeo<16, PREC>::smem_bytes(kBottleneck))));
-                        raised[e->device & 63][e->prec] = true;
-                    }
                     a.tiles_x = (pl.W + 15) / 16; a.cg_per_wg = kBottleneck / 32;
                     if (pl.H % 16 || pl.W % 16) {      // tiles hang over the edge: the bounds-checked instantiation
-                        PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_dgrad_kernel<16, PREC, true>), dim3(((pl.H + 15) / 16) * a.tiles_x, NS), dim3(256),
-                                           (HaloDgradSGeo<16, PREC>::smem_bytes(kBottleneck)), st, a));
+                        PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_dgrad_kernel<16, PREC, true>, dim3(((pl.H + 15) / 16) * a.tiles_x, NS), dim3(256),
+                                                       HaloDgradSGeo<16, PREC>::smem_bytes(kBottleneck), st, K_D3, flops, bytes, true, a));
                     } else {
-                        PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_dgrad_kernel<16, PREC>), dim3((pl.H / 16) * a.tiles_x, NS), dim3(256),
-                                           (HaloDgradSGeo<16, PREC>::smem_bytes(kBottleneck)), st, a));
+                        PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_dgrad_kernel<16, PREC>, dim3((pl.H / 16) * a.tiles_x, NS), dim3(256),
+                                                       HaloDgradSGeo<16, PREC>::smem_bytes(kBottleneck), st, K_D3, flops, bytes, true, a));
                     }
                 } else {
-                    static_assert(HaloDgradSGeo<8, 0>::smem_bytes(kBottleneck) <= 64 * 1024, "a tap per stage: inside the default 64 KB of dynamic LDS");
                     a.tiles_x = (pl.W + 7) / 8; a.cg_per_wg = 1;      // small planes: one 64-channel group per workgroup
-                    PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_dgrad_kernel<8, PREC>), dim3(((pl.H + 7) / 8) * a.tiles_x, NS, kBottleneck / 64), dim3(256),
-                                       (HaloDgradSGeo<8, PREC>::smem_bytes(kBottleneck)), st, a));
+                    PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_dgrad_kernel<8, PREC>, dim3(((pl.H + 7) / 8) * a.tiles_x, NS, kBottleneck / 64), dim3(256),
+                                                   HaloDgradSGeo<8, PREC>::smem_bytes(kBottleneck), st, K_D3, flops, bytes, true, a));
                 }
             } else {   // conv2 (3x3) data gradient -> dy of relu2/norm2 (D2) + norm2 sums (generic implicit GEMM)
                 auto run = [&](auto tag) {
@@ -375,10 +354,10 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                     p.msum = fsum(e, e->st_Bt[b][i]); p.msq = fsq(e, e->st_Bt[b][i]); p.mstride = kBottleneck;
                     p.egamma = P + d.n2.w; p.ebeta = P + d.n2.b;
                     p.dst = split16 ? e->DY2 : D2b; p.ldd = kBottleneck; p.dcoff = 0;
-                    p.o1 = b1(e, e->bs_Bt[b][i]); p.o2 = b2(e, e->bs_Bt[b][i]); p.ostride = kBottleneck; p.ocoff = 0;
+                    p.o1 = b1(e, e->st_Bt[b][i]); p.o2 = b2(e, e->st_Bt[b][i]); p.ostride = kBottleneck; p.ocoff = 0;
                     p.dbeta = Gr + d.n2.b; p.dgamma = Gr + d.n2.w; p.eps = kEps;
-                    BY(e, ESZ(e) * NS * pl.HW * (kGrowth + 2 * kBottleneck));
-                    launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, kBottleneck / Cfg::BN), K_D3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth);
+                    launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, kBottleneck / Cfg::BN), K_D3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth,
+                                ESZ(e) * NS * pl.HW * (kGrowth + 2 * kBottleneck));
                 };
                 if (pl.HWp % 128 == 0) run(CfgP128x128{}); else run(CfgP64x128{});
             }
@@ -386,22 +365,19 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 BnBwdApplySplitArgs a{};
                 a.g = e->DY2; a.x = bt; a.pl = pl;
                 a.xsum = fsum(e, e->st_Bt[b][i]); a.xsq = fsq(e, e->st_Bt[b][i]); a.xstride = kBottleneck; a.xtab = !e->generic3x3 ? stat_table(e, e->sb_tab[b][i], e->max_streams, kBottleneck) : StatTab{};
-                a.s1 = b1(e, e->bs_Bt[b][i]); a.s2 = b2(e, e->bs_Bt[b][i]); a.sstride = kBottleneck;
+                a.s1 = b1(e, e->st_Bt[b][i]); a.s2 = b2(e, e->st_Bt[b][i]); a.sstride = kBottleneck;
                 a.gamma = P + d.n2.w; a.eps = kEps; a.out = reinterpret_cast<u32x4*>(D2b); a.binv = lb.D2S;
                 if (!e->generic3x3) { a.dbeta = Gr + d.n2.b; a.dgamma = Gr + d.n2.w; }   // the halo dgrad leaves these to us
-                BY(e, 4.0 * NS * pl.HW * 3 * kBottleneck);
-                ProfScope ps(e, st, K_OTHER, 0);
-                hipLaunchKernelGGL(bn_bwd_apply_split_kernel, dim3(pl.HWp / kScaleBlock, NS), dim3(256), 0, st, a);
+                launch_kernel(e, bn_bwd_apply_split_kernel, dim3(pl.HWp / kScaleBlock, NS), dim3(256), 0, st, K_OTHER, 0, 4.0 * NS * pl.HW * 3 * kBottleneck, false, a);
             } else {   // 16-bit modes: norm2 backward applied once, in place: D2 <- gamma2*invstd*(dy - s1/n - xhat*s2/n)
                 BnBwdApplyArgs a{};
                 a.g = D2b; a.ldg = kBottleneck; a.gcoff = 0; a.x = bt; a.ldx = kBottleneck; a.xcoff = 0; a.pl = pl; a.C = kBottleneck;
                 a.xsum = fsum(e, e->st_Bt[b][i]); a.xsq = fsq(e, e->st_Bt[b][i]); a.xstride = kBottleneck; a.xtab = !e->generic3x3 ? stat_table(e, e->sb_tab[b][i], e->max_streams, kBottleneck) : StatTab{};
-                a.s1 = b1(e, e->bs_Bt[b][i]); a.s2 = b2(e, e->bs_Bt[b][i]); a.sstride = kBottleneck; a.scoff = 0;
+                a.s1 = b1(e, e->st_Bt[b][i]); a.s2 = b2(e, e->st_Bt[b][i]); a.sstride = kBottleneck; a.scoff = 0;
                 a.gamma = P + d.n2.w; a.eps = kEps; a.out = D2b; a.ldo = kBottleneck; a.amax = nullptr;
                 if (!e->generic3x3) { a.dbeta = Gr + d.n2.b; a.dgamma = Gr + d.n2.w; }   // the halo dgrad leaves these to us
-                BY(e, ESZ(e) * NS * pl.HW * 3 * kBottleneck);
-                ProfScope ps(e, st, K_OTHER, 0);
-                PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(bn_bwd_apply_kernel<PREC>), dim3((pl.HWp + bn_apply_rows(PREC) - 1) / bn_apply_rows(PREC), NS), dim3(256), 0, st, a));
+                PREC_DISPATCH(e, launch_kernel(e, bn_bwd_apply_kernel<PREC>, dim3((pl.HWp + bn_apply_rows(PREC) - 1) / bn_apply_rows(PREC), NS), dim3(256), 0, st,
+                                               K_OTHER, 0, ESZ(e) * NS * pl.HW * 3 * kBottleneck, false, a));
             }
             // the layer's weight gradients: ONE fork per layer, behind the norm2 apply (GS and D2 are both final there)
             if (fork(e->ev_d2[lb.ring % kRing])) return -5;
@@ -435,10 +411,10 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                     p.msum = fsum(e, e->st_X[b]); p.msq = fsq(e, e->st_X[b]); p.mstride = Ct; p.mtab = stat_table(e, e->sx_tab[b], e->max_streams, Ct);
                     p.egamma = P + d.n1.w + cs; p.ebeta = P + d.n1.b + cs;
                     p.dst = e->G[b]; p.ldd = Ct; p.dcoff = cs;
-                    p.o1 = b1(e, e->bs_X[b]); p.o2 = b2(e, e->bs_X[b]); p.ostride = Ct; p.ocoff = cs;
+                    p.o1 = b1(e, e->st_X[b]); p.o2 = b2(e, e->st_X[b]); p.ostride = Ct; p.ocoff = cs;
                     p.dbeta = e->dbscr + e->db_off[b][i] + cs; p.dgamma = e->dbscr + e->db_off[b][i] + d.cin + cs; p.rep_stride = e->db_total; p.eps = kEps;
-                    BY(e, ESZ(e) * NS * pl.HW * (kBottleneck + 3.0 * p.N));          // dy in; x in, G' read + written
-                    launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, (p.N + Cfg::BN - 1) / Cfg::BN), K_D1, 2.0 * NS * pl.HW * p.N * kBottleneck);
+                    launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, (p.N + Cfg::BN - 1) / Cfg::BN), K_D1, 2.0 * NS * pl.HW * p.N * kBottleneck,
+                                ESZ(e) * NS * pl.HW * (kBottleneck + 3.0 * p.N));          // dy in; x in, G' read + written
                 };
                 PREC_DISPATCH(e, if (pl.HWp % 128 == 0) run(CfgP128x64{}, PTAG); else run(CfgP64x64{}, PTAG));
             }
@@ -459,9 +435,9 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                     p.mbuf = e->X[b]; p.ldm = Ct;
                     p.msum = fsum(e, e->st_X[b]); p.msq = fsq(e, e->st_X[b]); p.mstride = Ct; p.mtab = stat_table(e, e->sx_tab[b], e->max_streams, Ct);
                     p.dst = e->G[b]; p.ldd = Ct;
-                    p.o1 = b1(e, e->bs_X[b]); p.o2 = b2(e, e->bs_X[b]); p.ostride = Ct; p.rep_stride = e->db_total; p.eps = kEps;
-                    BY(e, ESZ(e) * NS * pl.HW * ((double)p.nseg * kBottleneck + 3.0 * cs));
-                    launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, (cs + Cfg::BN - 1) / Cfg::BN), K_D1, 2.0 * NS * pl.HW * cs * kBottleneck * p.nseg);
+                    p.o1 = b1(e, e->st_X[b]); p.o2 = b2(e, e->st_X[b]); p.ostride = Ct; p.rep_stride = e->db_total; p.eps = kEps;
+                    launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, (cs + Cfg::BN - 1) / Cfg::BN), K_D1, 2.0 * NS * pl.HW * cs * kBottleneck * p.nseg,
+                                ESZ(e) * NS * pl.HW * ((double)p.nseg * kBottleneck + 3.0 * cs));
                 };
                 // mode 0, 128-row tiles: 32-deep k-tiles with ONE tile of loads in flight - the staging registers of two 16-deep
                 // tiles, half the barriers (k-loop 65k -> 50k cycles per workgroup, launches -7 %; same k16 order, same bits)
@@ -480,22 +456,22 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 BwdWeightP<MC<CfgW128x128, decltype(ptag)::value>, W_POOL, C_IDENT, 1, true, decltype(ptag)::value> p{};      // (one k-tile in flight: the pooling fetch holds 4 float4 per slot, three tiles of them leave one workgroup per CU)
                 p.gbuf = e->G[b]; p.ldg = Ct; p.gcoff = 0; p.xbuf = e->X[b]; p.ldx = Ct; p.xcoff = 0; p.pa = pl; p.MA = C0;
                 p.xsum = fsum(e, e->st_X[b]); p.xsq = fsq(e, e->st_X[b]); p.xstride = Ct;
-                p.s1 = b1(e, e->bs_X[b]); p.s2 = b2(e, e->bs_X[b]); p.sstride = Ct; p.scoff = 0; p.agamma = nullptr;
+                p.s1 = b1(e, e->st_X[b]); p.s2 = b2(e, e->st_X[b]); p.sstride = Ct; p.scoff = 0; p.agamma = nullptr;
                 p.bbuf = e->X[b - 1]; p.ldb = Cp; p.pb = pp; p.NB = Cp;
                 p.bsum = fsum(e, e->st_X[b - 1]); p.bsq = fsq(e, e->st_X[b - 1]); p.bstride = Cp;
                 p.bgamma = P + T.tnorm[b - 1].w; p.bbeta = P + T.tnorm[b - 1].b; p.eps = kEps;
                 p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
                 p.dw = Gr + T.tconv[b - 1].w; p.ldw_out = Cp;
                 if (fork(e->ev_misc)) return -5;
-                BY(e, ESZ(e) * NS * (2.0 * pl.HW * C0 + (double)pp.HW * Cp));
                 flush_pending_reduce();      // (the partial-tile workspace is about to be reused from its start)
-                return launch_wgrad(e, s2, p, dim3(C0 / 128, Cp / 128, NS * cps), K_TW, 2.0 * NS * pl.HW * Cp * C0, 1, C_IDENT);
+                return launch_wgrad(e, s2, p, dim3(C0 / 128, Cp / 128, NS * cps), K_TW, 2.0 * NS * pl.HW * Cp * C0,
+                                    ESZ(e) * NS * (2.0 * pl.HW * C0 + (double)pp.HW * Cp), 1, C_IDENT);
                 };
                 PREC_DISPATCH(e, if (int rc = go(PTAG)) return rc);
             }
             if (pp.H != 2 * pl.H || pp.W != 2 * pl.W) {
-                ProfScope ps(e, st, K_OTHER, 0);
-                PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(zero_uncovered_kernel<PREC>), dim3(256, NS), dim3(256), 0, st, (void*)e->G[b - 1], Cp, pp, 2 * pl.H, 2 * pl.W, Cp));
+                PREC_DISPATCH(e, launch_kernel(e, zero_uncovered_kernel<PREC>, dim3(256, NS), dim3(256), 0, st, K_OTHER, 0, 0, false,
+                                               (void*)e->G[b - 1], Cp, pp, 2 * pl.H, 2 * pl.W, Cp));
             }
             {
                 auto run = [&](auto tag, auto ptag) {
@@ -503,16 +479,16 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 BwdDataP<Cfg, false, E_UNPOOL, true, decltype(ptag)::value> p{};
                 p.gbuf = e->G[b]; p.ldg = Ct; p.gcoff = 0; p.xbuf = e->X[b]; p.ldx = Ct; p.xcoff = 0; p.pa = pl; p.KA = C0;
                 p.xsum = fsum(e, e->st_X[b]); p.xsq = fsq(e, e->st_X[b]); p.xstride = Ct;
-                p.s1 = b1(e, e->bs_X[b]); p.s2 = b2(e, e->bs_X[b]); p.sstride = Ct; p.scoff = 0; p.agamma = nullptr;
+                p.s1 = b1(e, e->st_X[b]); p.s2 = b2(e, e->st_X[b]); p.sstride = Ct; p.scoff = 0; p.agamma = nullptr;
                 p.wp = e->packed_u + e->pk_td[b - 1]; p.K8tot = C0 / 8; p.ldn = Cp; p.wcol0 = 0; p.N = Cp;
                 p.mbuf = e->X[b - 1]; p.ldm = Cp; p.mcoff = 0; p.pm = pp;
                 p.msum = fsum(e, e->st_X[b - 1]); p.msq = fsq(e, e->st_X[b - 1]); p.mstride = Cp;
                 p.egamma = P + T.tnorm[b - 1].w; p.ebeta = P + T.tnorm[b - 1].b;
                 p.dst = e->G[b - 1]; p.ldd = Cp; p.dcoff = 0;
-                p.o1 = b1(e, e->bs_X[b - 1]); p.o2 = b2(e, e->bs_X[b - 1]); p.ostride = Cp; p.ocoff = 0;
+                p.o1 = b1(e, e->st_X[b - 1]); p.o2 = b2(e, e->st_X[b - 1]); p.ostride = Cp; p.ocoff = 0;
                 p.dbeta = e->dbscr + e->db_toff[b - 1]; p.dgamma = e->dbscr + e->db_toff[b - 1] + Cp; p.rep_stride = e->db_total; p.eps = kEps;
-                BY(e, ESZ(e) * NS * (2.0 * pl.HW * C0 + 2.0 * pp.HW * Cp));
-                launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, Cp / Cfg::BN), K_TD, 2.0 * NS * pl.HW * Cp * C0);
+                launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, Cp / Cfg::BN), K_TD, 2.0 * NS * pl.HW * Cp * C0,
+                            ESZ(e) * NS * (2.0 * pl.HW * C0 + 2.0 * pp.HW * Cp));
             };
             PREC_DISPATCH(e, run(CfgP64x128{}, PTAG));   // the 128-row variant of the unpool epilogue spills registers
             }
@@ -524,17 +500,16 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         Pool0BwdArgs a;
         a.G1 = e->G[0]; a.X1 = e->X[0]; a.ld1 = kBlockCtot[0]; a.p1 = e->p_blk[0];
         a.xsum = fsum(e, e->st_X[0]); a.xsq = fsq(e, e->st_X[0]); a.xstride = kBlockCtot[0];
-        a.SA = b1(e, e->bs_X[0]); a.SB = b2(e, e->bs_X[0]); a.sstride = kBlockCtot[0];
+        a.SA = b1(e, e->st_X[0]); a.SB = b2(e, e->st_X[0]); a.sstride = kBlockCtot[0];
         a.argmax = e->argmax; a.stem = e->stem; a.ps = e->p_stem;
         a.ssum = fsum(e, e->st_stem); a.ssq = fsq(e, e->st_stem);
         a.gamma = P + T.norm0.w; a.beta = P + T.norm0.b; a.eps = kEps;
-        a.DY0 = e->DY0; a.o1 = b1(e, e->bs_stem); a.o2 = b2(e, e->bs_stem);
+        a.DY0 = e->DY0; a.o1 = b1(e, e->st_stem); a.o2 = b2(e, e->st_stem);
         a.dbeta = Gr + T.norm0.b; a.dgamma = Gr + T.norm0.w;
-        ProfScope ps(e, st, K_OTHER, 0);
         if (e->p_stem.H % 8 || e->p_stem.W % 8) return fail(-22, "stem plane must tile by 8 (input_size multiple of 16)");
         a.tiles_per_wg = 8;          // 4..20 measure the same; 1 costs 0.7 ms per step in atomics
         const int n_t = (e->p_stem.H / 8) * (e->p_stem.W / 8);
-        PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(pool0_bwd_kernel<PREC>), dim3((n_t + a.tiles_per_wg - 1) / a.tiles_per_wg, NS), dim3(256), 0, st, a));
+        PREC_DISPATCH(e, launch_kernel(e, pool0_bwd_kernel<PREC>, dim3((n_t + a.tiles_per_wg - 1) / a.tiles_per_wg, NS), dim3(256), 0, st, K_OTHER, 0, 0, false, a));
     }
     {   // conv0 weight gradient (no data gradient: the image needs none)
         const Plane ps_ = e->p_stem;
@@ -546,14 +521,14 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         BwdWeightP<WCfg, SM, SM == W_STEM1 ? C_STEM1 : C_STEM, kPdWgrad, true, decltype(ptag)::value> p{};      // (fp32 image / stem plane in every mode)
         p.gbuf = e->DY0; p.ldg = 64; p.gcoff = 0; p.xbuf = e->stem; p.ldx = 64; p.xcoff = 0; p.pa = ps_; p.MA = 64;
         p.xsum = fsum(e, e->st_stem); p.xsq = fsq(e, e->st_stem); p.xstride = 64;
-        p.s1 = b1(e, e->bs_stem); p.s2 = b2(e, e->bs_stem); p.sstride = 64; p.scoff = 0; p.agamma = P + T.norm0.w;
+        p.s1 = b1(e, e->st_stem); p.s2 = b2(e, e->st_stem); p.sstride = 64; p.scoff = 0; p.agamma = P + T.norm0.w;
         p.bbuf = e->img4; p.ldb = 4; p.pb = e->p_img; p.NB = SM == W_STEM1 ? 64 : 196;
         p.eps = kEps; p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
         p.dw = Gr + T.conv0.w; p.ldw_out = 147;
         if (fork(e->ev_misc)) return -5;
-        BY(e, 4.0 * NS * (2.0 * ps_.HW * 64 + (double)e->p_img.HW * (SM == W_STEM1 ? 1 : 4)));
         flush_pending_reduce();      // (the partial-tile workspace is about to be reused from its start)
-        return launch_wgrad(e, s2, p, dim3(1, 1, NS * cps), K_SW, 2.0 * NS * ps_.HW * 64 * 147, 1, SM == W_STEM1 ? C_STEM1 : C_STEM);
+        return launch_wgrad(e, s2, p, dim3(1, 1, NS * cps), K_SW, 2.0 * NS * ps_.HW * 64 * 147,
+                            4.0 * NS * (2.0 * ps_.HW * 64 + (double)e->p_img.HW * (SM == W_STEM1 ? 1 : 4)), 1, SM == W_STEM1 ? C_STEM1 : C_STEM);
         };
         if (e->f_stem1) { PREC_DISPATCH(e, if (int rc = go(PTAG, std::integral_constant<int, W_STEM1>{})) return rc); }
         else { PREC_DISPATCH(e, if (int rc = go(PTAG, std::integral_constant<int, W_STEM>{})) return rc); }
@@ -566,16 +541,15 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         // half must not touch a single element of them (it would re-write a stale local value over the reduced one).
         const int first_b = 2 * kBlockLayers[0];
         const int seg0 = ph_b ? 0 : first_b, seg1 = ph_a ? e->n_dbseg : first_b;
-        ProfScope ps(e, st, K_OTHER, 0);
-        hipLaunchKernelGGL(db_flush_kernel, dim3(4, seg1 - seg0 + 1), dim3(256), 0, st,
-                           reinterpret_cast<const DbSegD*>(e->d_dbseg + (size_t)e->f_trunk * e->n_dbseg) + seg0,
-                           e->dbscr, e->db_total, kDbRep, Gr,
-                           ph_b ? b1(e, e->bs_stem) : nullptr, ph_b ? b2(e, e->bs_stem) : nullptr, NS, Gr + T.norm0.b, Gr + T.norm0.w);
+        launch_kernel(e, db_flush_kernel, dim3(4, seg1 - seg0 + 1), dim3(256), 0, st, K_OTHER, 0, 0, false,
+                      reinterpret_cast<const DbSegD*>(e->d_dbseg + (size_t)e->f_trunk * e->n_dbseg) + seg0,
+                      e->dbscr, e->db_total, kDbRep, Gr,
+                      ph_b ? b1(e, e->st_stem) : nullptr, ph_b ? b2(e, e->st_stem) : nullptr, NS, Gr + T.norm0.b, Gr + T.norm0.w);
     }
     flush_pending_reduce();
     HIP_OK(hipEventRecord(e->ev_end, s2));          // join: everything after the backward (or this half of it) sees every gradient
     HIP_OK(hipStreamWaitEvent(st, e->ev_end, 0));
-    HIP_OK(hipGetLastError());
+    if (int rc = walk_status(e)) return rc;
     e->bw_phase0_done = phases == 1;
     return 0;
 }

@@ -114,8 +114,7 @@ struct smg_engine {
     // kernels' tails).  They go to kDbRep replicas of a compact scratch instead (replica = workgroup index mod kDbRep);
     // db_flush_kernel sums the replicas into the gradient array at the end of the backward (half) and re-zeroes them.
     float* dbscr = nullptr; int db_total = 0; int db_off[4][24] = {}; int db_toff[3] = {}; struct DbSeg* d_dbseg = nullptr; int n_dbseg = 0;
-    StatArr st_stem, st_X[4], st_F, st_H1; std::vector<StatArr> st_Bt[4];
-    StatArr bs_stem, bs_X[4], bs_F, bs_H1; std::vector<StatArr> bs_Bt[4];
+    StatArr st_stem, st_X[4], st_F, st_H1; std::vector<StatArr> st_Bt[4];      // one carve for both arenas: fsum / fsq and b1 / b2 take the same handles
     // packed weights: split bf16 units for the MFMA GEMMs (packed_u) and fp32 K-major layouts for the halo 3x3
     // kernels / the value convolution (packed_f)
     u32x4* packed_u = nullptr; int64_t packed_units = 0;
@@ -171,7 +170,7 @@ struct smg_engine {
     bool prof = false; std::vector<ProfRec> recs; std::vector<hipEvent_t> ev_pool;
     // totals per kind in slot 0, and the share of dense block b (kernels issued inside its layer loops) in slot 1 + b
     double prof_ms[5][K_COUNT] = {}; int64_t prof_n[5][K_COUNT] = {}; double prof_flops[5][K_COUNT] = {}; double prof_bytes[5][K_COUNT] = {}; int prof_stage = -1;
-    double next_bytes = 0;     // algorithmic HBM bytes of the next profiled launch (set with BY() right before it)
+    int launch_rc = 0;         // error code of the first launch launch_kernel refused since the last walk_status (smg_last_error() says why)
 };
 
 // Tile side of the LDS-halo 3x3 kernels for a plane: 16 where it tiles exactly, else 8 (ragged edges masked) - and 8
@@ -232,14 +231,10 @@ static hipEvent_t prof_event(smg_engine* e) {
     if (!e->ev_pool.empty()) { hipEvent_t ev = e->ev_pool.back(); e->ev_pool.pop_back(); return ev; }
     hipEvent_t ev; (void)hipEventCreate(&ev); return ev;
 }
-// Algorithmic HBM bytes of the launch that follows: what the kernel must move once (inputs read once, outputs written
-// once, fp32), the yardstick of bench.py's HBM roofline.
-#define BY(e, x) ((e)->next_bytes = (double)(x))
 #define ESZ(e) ((e)->prec ? 2.0 : 4.0)      // bytes per element of the mode-typed buffers (X, Bt, G', GS, D2)
 struct ProfScope {
     smg_engine* e; hipStream_t st; int kind; double flops, bytes; hipEvent_t a{}, b{};
-    ProfScope(smg_engine* e_, hipStream_t s, int k, double f) : e(e_), st(s), kind(k), flops(f), bytes(e_->next_bytes) {
-        e->next_bytes = 0;
+    ProfScope(smg_engine* e_, hipStream_t s, int k, double f, double by) : e(e_), st(s), kind(k), flops(f), bytes(by) {
         if (e->prof) { a = prof_event(e); b = prof_event(e); (void)hipEventRecord(a, st); }
     }
     ~ProfScope() {
@@ -257,17 +252,17 @@ struct ProfScope {
         default: { constexpr int PREC = 0; CALL; } break;                 \
     }
 
-// Dev instrumentation: per-workgroup phase stamps of ONE launch (SMG_TRACE_KIND = kernel class, SMG_TRACE_SKIP = how many
-// launches of that class to skip).  The kernels store s_memtime at up to five points (slots 0..4) and the device-wide
+// Dev instrumentation: per-workgroup phase stamps of ONE traced launch (SMG_TRACE_KIND = kernel class, SMG_TRACE_SKIP = how many
+// traced launches of that class to skip).  The kernels store s_memtime at up to five points (slots 0..4) and the device-wide
 // 100 MHz counter at start / end (slots 5, 6) through g_smg_trace; the scope prints the mean phase lengths.
 namespace {   // per translation unit: the scope writes THIS unit's g_smg_trace (a shared inline copy would write another unit's)
 struct TraceScope {
     hipStream_t st; int kind; dim3 grid; const char* what; unsigned long long* tbuf = nullptr; size_t n_wg = 0;
-    TraceScope(hipStream_t s, int k, dim3 g, const char* w = "") : st(s), kind(k), grid(g), what(w) {
+    TraceScope(hipStream_t s, int k, dim3 g, bool traced, const char* w) : st(s), kind(k), grid(g), what(w) {
         static const int tr_kind = getenv("SMG_TRACE_KIND") ? atoi(getenv("SMG_TRACE_KIND")) : -1;
         static const int tr_skip = getenv("SMG_TRACE_SKIP") ? atoi(getenv("SMG_TRACE_SKIP")) : 0;
         static int tr_seen = 0;
-        if (!(kind == tr_kind && tr_seen++ == tr_skip)) return;
+        if (!(traced && kind == tr_kind && tr_seen++ == tr_skip)) return;
         n_wg = (size_t)grid.x * grid.y * grid.z;
         (void)hipMalloc((void**)&tbuf, n_wg * 64);
         (void)hipMemsetAsync(tbuf, 0, n_wg * 64, st);
@@ -303,21 +298,51 @@ struct TraceScope {
         }
         if (extra > 0) fprintf(stderr, "[smg trace]   slot 1 -> slot 7: %.0f cycles/WG (mean)\n", extra / live);
         fprintf(stderr, "[smg trace] kind %d grid %ux%ux%u live %zu: init %.0f | first tile %.0f | k-loop %.0f | epilogue %.0f cycles/WG (mean); span %.1f us, %.2f workgroups resident per CU, mean life %.1f us  %.160s\n",
-                kind, grid.x, grid.y, grid.z, live, sum[0] / live, sum[1] / live, sum[2] / live, sum[3] / live, span, resid, life / live * 0.01, strstr(what, "[P = ") ? strstr(what, "[P = ") : what);
+                kind, grid.x, grid.y, grid.z, live, sum[0] / live, sum[1] / live, sum[2] / live, sum[3] / live, span, resid, life / live * 0.01, strstr(what, "[KArgs = ") ? strstr(what, "[KArgs = ") : what);
     }
 };
 }  // namespace
 
-template <class P>
-static void launch_gemm(smg_engine* e, hipStream_t st, P p, dim3 grid, int kind, double flops) {
-    const size_t smem = (size_t)(GeoOf<P>::TILE_FLOATS + p.param_floats()) * sizeof(float);
-    if (smem > 64 * 1024) {      // more dynamic LDS than the default limit: raise it once per (instantiation, device)
-        static bool raised[64] = {};
-        if (!raised[e->device & 63]) {
-            (void)hipFuncSetAttribute((const void*)gemm_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            raised[e->device & 63] = true;
+// Lets `kernel` take up to a CU's 160 KiB of dynamic LDS instead of the default 64 KB, once per (kernel, device).
+static void raise_lds_limit(const smg_engine* e, const void* kernel) {
+    static struct { const void* kernel; int device; } raised[64];
+    static int n_raised = 0;
+    for (int i = 0; i < n_raised; ++i)
+        if (raised[i].kernel == kernel && raised[i].device == e->device) return;
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (n_raised < 64) raised[n_raised++] = {kernel, e->device};
+}
+
+// Every kernel launch of the walks.  It is profiled as class `kind` with its flops and its algorithmic HBM bytes: what the kernel
+// must move once (inputs read once, outputs written once), the yardstick of bench.py's HBM roofline.  A `traced` launch can take
+// the dev phase stamps (TraceScope).  A launch of more than 64 KB of dynamic LDS raises the kernel's limit; one of more than a CU's
+// 160 KiB is refused, and the walk returns its error (walk_status).
+template <class... KArgs, class... Args>
+static void launch_kernel(smg_engine* e, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t smem, hipStream_t st, int kind,
+                          double flops, double bytes, bool traced, const Args&... args) {
+    if (smem > 64 * 1024) {
+        if (smem > 160 * 1024) {
+            if (!e->launch_rc)
+                e->launch_rc = fail(-12, std::string(kKindNames[kind]) + ": a launch needs " + std::to_string(smem) + " B of dynamic LDS, a CU has 160 KiB");
+            return;
         }
+        raise_lds_limit(e, (const void*)kernel);
     }
+    TraceScope ts(st, kind, grid, traced, __PRETTY_FUNCTION__);
+    ProfScope ps(e, st, kind, flops, bytes);
+    hipLaunchKernelGGL(kernel, grid, block, smem, st, args...);
+}
+
+// The end of a walk: the first launch launch_kernel refused, else any launch error HIP recorded.
+static int walk_status(smg_engine* e) {
+    if (const int rc = e->launch_rc) { e->launch_rc = 0; return rc; }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+template <class P>
+static void launch_gemm(smg_engine* e, hipStream_t st, P p, dim3 grid, int kind, double flops, double bytes) {
+    const size_t smem = (size_t)(GeoOf<P>::TILE_FLOATS + p.param_floats()) * sizeof(float);
     p.tm = TileMap{0, 0, 0};
     if constexpr (P::kSwizzle == 1) {            // x = M tiles, y = N tiles sharing one A operand
         if (grid.y > 1 && grid.z == 1) {
@@ -332,11 +357,7 @@ static void launch_gemm(smg_engine* e, hipStream_t st, P p, dim3 grid, int kind,
             grid = dim3(tile_grid(p.tm), 1, 1);
         }
     }
-    TraceScope ts(st, kind, grid, __PRETTY_FUNCTION__);
-    {
-        ProfScope ps(e, st, kind, flops);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_kernel<P>), dim3((unsigned)(grid.x * grid.y * grid.z)), dim3(256), smem, st, p, (int)grid.x, (int)grid.y);
-    }
+    launch_kernel(e, gemm_kernel<P>, dim3((unsigned)(grid.x * grid.y * grid.z)), dim3(256), smem, st, kind, flops, bytes, true, p, (int)grid.x, (int)grid.y);
 }
 
 // Weight-gradient launch: partial tiles to the workspace + one reduce kernel (falls back to
@@ -344,7 +365,7 @@ static void launch_gemm(smg_engine* e, hipStream_t st, P p, dim3 grid, int kind,
 // part_off: first float of the partial-tile workspace this launch may use (a dense layer's two weight gradients keep their partial
 // tiles side by side and share ONE reduce launch: `defer` receives this launch's reduction instead of it being launched here).
 template <class P>
-static int launch_wgrad(smg_engine* e, hipStream_t st, P& p, dim3 grid, int kind, double flops, int taps, int cmap, bool use_part = true,
+static int launch_wgrad(smg_engine* e, hipStream_t st, P& p, dim3 grid, int kind, double flops, double bytes, int taps, int cmap, bool use_part = true,
                         int64_t part_off = 0, ReduceArgs* defer = nullptr) {
     using C = typename P::Cfg;
     const int64_t ldp = (int64_t)grid.y * C::BN, rowsp = (int64_t)grid.x * C::BM;
@@ -353,7 +374,7 @@ static int launch_wgrad(smg_engine* e, hipStream_t st, P& p, dim3 grid, int kind
     if (use_part && !p.part && e->deterministic)      // never a silent loss of the bit-reproducibility the option promises
         return fail(-12, "deterministic: a weight-gradient launch needs " + std::to_string(need) + " partial-tile floats, the workspace holds " +
                              std::to_string(e->part_floats - part_off) + " (smaller batch per call, or a larger engine)");
-    launch_gemm(e, st, p, grid, kind, flops);
+    launch_gemm(e, st, p, grid, kind, flops, bytes);
     if (defer) defer->Z = 0;
     if (p.part) {
         ReduceArgs r;
@@ -362,18 +383,17 @@ static int launch_wgrad(smg_engine* e, hipStream_t st, P& p, dim3 grid, int kind
         r.dw = p.dw; r.ldw_out = p.ldw_out; r.cmap = cmap;
         if (defer) { *defer = r; return 0; }
         const int total = taps * p.MA * p.NB;
-        ProfScope ps(e, st, K_OTHER, 0);       // (the reduce is profiled with the element-wise kernels: a class's launches are its GEMM kernels only)
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3((total + 63) / 64), dim3(256), 0, st, r, ReduceArgs{}, (total + 63) / 64);
+        // (the reduce is profiled with the element-wise kernels: a class's launches are its GEMM kernels only)
+        launch_kernel(e, reduce_partials_kernel, dim3((total + 63) / 64), dim3(256), 0, st, K_OTHER, 0, 0, false, r, ReduceArgs{}, (total + 63) / 64);
     }
     return 0;
 }
 // ONE launch for two pending reductions (either may be empty: Z == 0)
-static void launch_reduce2(smg_engine* e, hipStream_t st, int kind, const ReduceArgs& ra, const ReduceArgs& rb) {
+static void launch_reduce2(smg_engine* e, hipStream_t st, const ReduceArgs& ra, const ReduceArgs& rb) {
     const int ba = ra.Z ? (ra.taps * ra.rows * ra.cols + 63) / 64 : 0, bb = rb.Z ? (rb.taps * rb.rows * rb.cols + 63) / 64 : 0;
     if (ba + bb == 0) return;
-    (void)kind;
-    ProfScope ps(e, st, K_OTHER, 0);           // (one launch serves the layer's 3x3 AND 1x1 partial tiles: profiled with the element-wise kernels)
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(ba + bb), dim3(256), 0, st, ra, rb, ba);
+    // (one launch serves the layer's 3x3 AND 1x1 partial tiles: profiled with the element-wise kernels)
+    launch_kernel(e, reduce_partials_kernel, dim3(ba + bb), dim3(256), 0, st, K_OTHER, 0, 0, false, ra, rb, ba);
 }
 
 // element `elems` of a mode-typed buffer (X, Bt, G, GS, D2): 4-byte elements in mode 0, 2-byte elements in modes 1 / 2

@@ -81,8 +81,6 @@ static int engine_build(smg_engine* e) {
     e->st_F = carve(NP, 2 * kFeat);
     e->st_H1 = carve(NP, kHeadMid);
     e->fstat_span = e->bstat_span = off;
-    e->bs_stem = e->st_stem; e->bs_F = e->st_F; e->bs_H1 = e->st_H1;
-    for (int b = 0; b < 4; ++b) { e->bs_X[b] = e->st_X[b]; e->bs_Bt[b] = e->st_Bt[b]; }
     if (2 * off > kStatRepStride) return fail(-22, "batch too large for the statistic arenas (kStatRepStride in gemm.cuh)");
     ALLOC(e->fstat, kFStatRep > 1 ? (int64_t)kFStatRep * kStatRepStride : 2 * off);
     ALLOC(e->bstat, (int64_t)kStatRep * kStatRepStride);      // kStatRep replicas (gemm.cuh: stat_get / stat_rep), 2 * off doubles used of each
@@ -747,7 +745,7 @@ int smg_profile_read(smg_engine* e, int kind, double* ms, int64_t* launches, dou
     return 0;
 }
 
-// Algorithmic HBM bytes (see BY()) accumulated for one class since smg_profile_enable; call after smg_profile_read.
+// Algorithmic HBM bytes (launch_kernel's `bytes`) accumulated for one class since smg_profile_enable; call after smg_profile_read.
 int smg_profile_read_bytes(smg_engine* e, int kind, double* bytes) {
     if (!e || kind < 0 || kind >= 5 * K_COUNT || !bytes) return fail(-22, "bad profile query");
     *bytes = e->prof_bytes[kind / K_COUNT][kind % K_COUNT];

@@ -80,14 +80,12 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
     {
         const unsigned n_pack = (unsigned)(e->h_pack[trunk_id].size() + e->h_pack_head[head_id].size());
         if (e->prec == 0 && kSplitOp == 3) {       // scales of the fp16-split operands: weight headers + activation scales (gemm.cuh, operand kind 3)
-            ProfScope ps(e, st, K_OTHER, 0);
-            hipLaunchKernelGGL(scale_kernel, dim3(1, n_pack + (unsigned)e->n_asc), dim3(1024), 0, st,
-                               e->d_pack + (trunk_id * 3 + head_id) * e->pack_stride, (int)n_pack, e->d_asc + (trunk_id * 3 + head_id) * e->n_asc,
-                               net->params, e->packed_u, e->asc, e->prec);
+            launch_kernel(e, scale_kernel, dim3(1, n_pack + (unsigned)e->n_asc), dim3(1024), 0, st, K_OTHER, 0, 0, false,
+                          e->d_pack + (trunk_id * 3 + head_id) * e->pack_stride, (int)n_pack, e->d_asc + (trunk_id * 3 + head_id) * e->n_asc,
+                          net->params, e->packed_u, e->asc, e->prec);
         }
-        ProfScope ps(e, st, K_OTHER, 0);
-        hipLaunchKernelGGL(pack_weights_kernel, dim3(64, n_pack), dim3(256), 0, st,
-                           e->d_pack + (trunk_id * 3 + head_id) * e->pack_stride, net->params, e->packed_u, e->packed_f, e->prec);
+        launch_kernel(e, pack_weights_kernel, dim3(64, n_pack), dim3(256), 0, st, K_OTHER, 0, 0, false,
+                      e->d_pack + (trunk_id * 3 + head_id) * e->pack_stride, net->params, e->packed_u, e->packed_f, e->prec);
     }
     const float* P = net->params;
 
@@ -100,8 +98,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
         BnStatArgs a;
         a.sum = sum; a.sq = sq; a.sstride = sstride; a.eps = kEps; a.inv_count = 1.0 / (double)count;
         a.mean = const_cast<float*>(t.mean); a.invstd = const_cast<float*>(t.invstd); a.ld = t.ld; a.c0 = c0; a.C = C; a.rows = rows;
-        ProfScope ps(e, cs, K_OTHER, 0);
-        hipLaunchKernelGGL(bn_stat_kernel, dim3((rows * C + 255) / 256), dim3(256), 0, cs, a);
+        launch_kernel(e, bn_stat_kernel, dim3((rows * C + 255) / 256), dim3(256), 0, cs, K_OTHER, 0, 0, false, a);
     };
     // Units [u_lo, u_hi) of the chain: unit 0 = input preparation + stem + pool0, then one unit per dense layer and per
     // transition.  The caller alternates the chains unit by unit, so that both have work queued from the start (a chain
@@ -122,8 +119,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
             a.stream_image = e->d_stream_image + s0; a.stream_affine = e->d_affine + 6 * s0; a.stream_rotated = e->d_stream_rot + s0;
             a.img4 = img4; a.img1 = stem1 ? img4 : nullptr; a.HWp = e->p_img.HWp;
             a.masks = B->masks_dev; a.stream_mask_a = e->d_stage + e->so_ma + s0; a.stream_mask_b = e->d_stage + e->so_mb + s0;
-            ProfScope ps(e, cs, K_OTHER, 0);
-            hipLaunchKernelGGL(prep_rotate_kernel, dim3((e->S * e->S + 255) / 256, ns), dim3(256), 0, cs, a);
+            launch_kernel(e, prep_rotate_kernel, dim3((e->S * e->S + 255) / 256, ns), dim3(256), 0, cs, K_OTHER, 0, 0, false, a);
         }
         if (head_unit) {   // stem conv0 7x7/2
             auto run = [&](auto tag, auto ptag, auto mtag) {
@@ -134,8 +130,8 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                 p.wp = e->packed_u + (SM == F_STEM1 ? e->pk_conv0_1 : e->pk_conv0); p.K8tot = (SM == F_STEM1 ? 64 : 224) / 8; p.N = 64;
                 p.dst = stem; p.ldd = 64; p.dcoff = 0;
                 p.dsum = st_off(fsum(e, e->st_stem), 64); p.dsq = st_off(fsq(e, e->st_stem), 64); p.dstride = 64;
-                BY(e, 4.0 * ns * ((double)e->p_img.HW * (SM == F_STEM1 ? 1 : 4) + (double)e->p_stem.HW * 64));
-                launch_gemm(e, cs, p, dim3(ns * e->p_stem.HWp / Cfg::BM, 1), K_STEM, 2.0 * ns * e->p_stem.HW * 64 * 147);
+                launch_gemm(e, cs, p, dim3(ns * e->p_stem.HWp / Cfg::BM, 1), K_STEM, 2.0 * ns * e->p_stem.HW * 64 * 147,
+                            4.0 * ns * ((double)e->p_img.HW * (SM == F_STEM1 ? 1 : 4) + (double)e->p_stem.HW * 64));
             };
             if (stem1) { PREC_DISPATCH(e, if (e->p_stem.HWp % 128 == 0) run(CfgP128x64{}, PTAG, std::integral_constant<int, F_STEM1>{}); else run(CfgP64x64{}, PTAG, std::integral_constant<int, F_STEM1>{})); }
             else { PREC_DISPATCH(e, if (e->p_stem.HWp % 128 == 0) run(CfgP128x64{}, PTAG, std::integral_constant<int, F_STEM>{}); else run(CfgP64x64{}, PTAG, std::integral_constant<int, F_STEM>{})); }
@@ -147,8 +143,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
             a.x1 = xs(0); a.ldx = kBlockCtot[0]; a.po = e->p_blk[0];
             a.dsum = st_off(fsum(e, e->st_X[0]), kBlockCtot[0]); a.dsq = st_off(fsq(e, e->st_X[0]), kBlockCtot[0]); a.dstride = kBlockCtot[0];
             a.argmax = e->argmax + (int64_t)s0 * e->p_blk[0].HWp * 64;
-            ProfScope ps(e, cs, K_OTHER, 0);
-            PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(pool0_kernel<PREC>), dim3(e->p_blk[0].HWp / 64, ns), dim3(256), 0, cs, a));
+            PREC_DISPATCH(e, launch_kernel(e, pool0_kernel<PREC>, dim3(e->p_blk[0].HWp / 64, ns), dim3(256), 0, cs, K_OTHER, 0, 0, false, a));
         }
         for (int b = 0; b < 4; ++b) {
             e->prof_stage = b;
@@ -173,8 +168,8 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                         p.wp = e->packed_u + e->pk_c1[b][i]; p.K8tot = d.cin / 8; p.N = kBottleneck;
                         p.dst = bt; p.ldd = kBottleneck; p.dcoff = 0;
                         p.dsum = bsum; p.dsq = bsq; p.dstride = kBottleneck;
-                        BY(e, ESZ(e) * ns * pl.HW * (d.cin + kBottleneck));
-                        launch_gemm(e, cs, p, dim3(ns * pl.HWp / Cfg::BM, kBottleneck / Cfg::BN), K_C1, 2.0 * ns * pl.HW * d.cin * kBottleneck);
+                        launch_gemm(e, cs, p, dim3(ns * pl.HWp / Cfg::BM, kBottleneck / Cfg::BN), K_C1, 2.0 * ns * pl.HW * d.cin * kBottleneck,
+                                    ESZ(e) * ns * pl.HW * (d.cin + kBottleneck));
                     };
                     auto run = [&](auto tag) { PREC_DISPATCH(e, run_p(tag, PTAG)); };
                     // 128x128 tiles where the plane tiles by 128 rows and the launch still fills the chip; else 64x64 (BK = 32) -
@@ -193,15 +188,8 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                         using WG_ = WsGeoT<np_of(fwd_op(0))>;                // one workgroup per 64-row tile covers all 128 output columns
                         const int nM = ns * pl.HWp / 64, nN = kBottleneck / WG_::BN;
                         a.tm = TileMap{nM, nN, 0};
-                        BY(e, ESZ(e) * ns * pl.HW * (d.cin + kBottleneck));
-                        ProfScope ps(e, cs, K_C1, 2.0 * ns * pl.HW * d.cin * kBottleneck);
-                        const size_t smem = WG_::smem_bytes(d.cin);
-                        static bool raised[64] = {};
-                        if (!raised[e->device & 63]) {
-                            (void)hipFuncSetAttribute((const void*)conv1x1_fwd_ws_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                            raised[e->device & 63] = true;
-                        }
-                        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv1x1_fwd_ws_kernel<0>), dim3(tile_grid(a.tm)), dim3(512), smem, cs, a);
+                        launch_kernel(e, conv1x1_fwd_ws_kernel<0>, dim3(tile_grid(a.tm)), dim3(512), WG_::smem_bytes(d.cin), cs, K_C1,
+                                      2.0 * ns * pl.HW * d.cin * kBottleneck, ESZ(e) * ns * pl.HW * (d.cin + kBottleneck), false, a);
                     } else
                     if (pl.HWp % 128 == 0 && wg128 >= small_wgs) run(CfgP128x128{});
                     else if (wg64 < small_wgs) run(CfgP32x64{});
@@ -218,31 +206,22 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                     a.dst = xs(b); a.ldd = Ct; a.dcoff = d.cin;
                     a.dsum = xsum; a.dsq = xsq; a.dstride = Ct;
                     a.wu = e->packed_u + e->pk_hf[b][i]; a.asc = asc_n2(e, b, (int)i);
-                    BY(e, ESZ(e) * ns * pl.HW * (kBottleneck + kGrowth));
-                    ProfScope ps(e, cs, K_C3, 2.0 * ns * pl.HW * 9 * kBottleneck * kGrowth);
-                    TraceScope ts(cs, K_C3, dim3(banded_grid(halo_tile(pl, ns) == 16 ? ((pl.H + 15) / 16) * ((pl.W + 15) / 16) : ((pl.H + 7) / 8) * ((pl.W + 7) / 8), ns)));      // dev stamps: SMG_TRACE_KIND=2
-                    if (halo_tile(pl, ns) == 8) {
+                    const double flops = 2.0 * ns * pl.HW * 9 * kBottleneck * kGrowth, bytes = ESZ(e) * ns * pl.HW * (kBottleneck + kGrowth);
+                    if (halo_tile(pl, ns) == 8) {      // (traced launches, as the 16 x 16 ones: dev stamps with SMG_TRACE_KIND=2)
                         // small planes: the wave-specialised form (halo.cuh; 17.1 -> 15.2 us per launch.  At TS = 16 it measures
                         // 67.8 -> 62.8 us serialised and nothing on the step - two forward chains already fill each other's gaps there)
+                        // (two (halo, weights) buffers: 51 KB as built, 76 KB - past the 64 KB default - in the -DSMG_SPLIT16=0 A/B build)
                         a.tiles_x = (pl.W + 7) / 8; a.n_tiles = ((pl.H + 7) / 8) * a.tiles_x; a.streams = ns;
-                        static bool raised8[64][3] = {};      // two (halo, weights) buffers: 51 KB as built, 76 KB in the -DSMG_SPLIT16=0 A/B build (three pieces) - past the 64 KB default
-                        if (!raised8[e->device & 63][e->prec]) {
-                            PREC_DISPATCH(e, if ((HaloFwdSGeo<8, PREC>::smem_bytes_ws(kBottleneck)) > 64 * 1024)
-                                                 (void)hipFuncSetAttribute((const void*)conv3x3_halo_fwd_kernel<8, PREC, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                           (HaloFwdSGeo<8, PREC>::smem_bytes_ws(kBottleneck))));
-                            raised8[e->device & 63][e->prec] = true;
-                        }
-                        PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_fwd_kernel<8, PREC, false, true>), dim3(banded_grid(a.n_tiles, ns)), dim3(512),
-                                           (HaloFwdSGeo<8, PREC>::smem_bytes_ws(kBottleneck)), cs, a));
-                    } else
-                    if (halo_tile(pl, ns) == 16) {
+                        PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_fwd_kernel<8, PREC, false, true>, dim3(banded_grid(a.n_tiles, ns)), dim3(512),
+                                                       HaloFwdSGeo<8, PREC>::smem_bytes_ws(kBottleneck), cs, K_C3, flops, bytes, true, a));
+                    } else {
                         a.tiles_x = (pl.W + 15) / 16; a.n_tiles = ((pl.H + 15) / 16) * a.tiles_x; a.streams = ns;
                         if (pl.H % 16 || pl.W % 16) {      // tiles hang over the edge: the bounds-checked instantiation
-                            PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_fwd_kernel<16, PREC, true>), dim3(banded_grid(a.n_tiles, ns)), dim3(256),
-                                               (HaloFwdSGeo<16, PREC>::smem_bytes(kBottleneck)), cs, a));
+                            PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_fwd_kernel<16, PREC, true>, dim3(banded_grid(a.n_tiles, ns)), dim3(256),
+                                                           HaloFwdSGeo<16, PREC>::smem_bytes(kBottleneck), cs, K_C3, flops, bytes, true, a));
                         } else {
-                            PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(conv3x3_halo_fwd_kernel<16, PREC>), dim3(banded_grid(a.n_tiles, ns)), dim3(256),
-                                               (HaloFwdSGeo<16, PREC>::smem_bytes(kBottleneck)), cs, a));
+                            PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_fwd_kernel<16, PREC>, dim3(banded_grid(a.n_tiles, ns)), dim3(256),
+                                                           HaloFwdSGeo<16, PREC>::smem_bytes(kBottleneck), cs, K_C3, flops, bytes, true, a));
                         }
                     }
                 } else {   // norm2 + relu + conv2 (3x3, 128 -> 32), appended to the block buffer (generic implicit GEMM)
@@ -255,8 +234,8 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                         p.wp = e->packed_u + e->pk_g3f[b][i]; p.K8tot = 9 * kBottleneck / 8; p.N = kGrowth;
                         p.dst = xs(b); p.ldd = Ct; p.dcoff = d.cin;
                         p.dsum = xsum; p.dsq = xsq; p.dstride = Ct;
-                        BY(e, ESZ(e) * ns * pl.HW * (kBottleneck + kGrowth));
-                        launch_gemm(e, cs, p, dim3(ns * pl.HWp / Cfg::BM, 1), K_C3, 2.0 * ns * pl.HW * 9 * kBottleneck * kGrowth);
+                        launch_gemm(e, cs, p, dim3(ns * pl.HWp / Cfg::BM, 1), K_C3, 2.0 * ns * pl.HW * 9 * kBottleneck * kGrowth,
+                                    ESZ(e) * ns * pl.HW * (kBottleneck + kGrowth));
                     };
                     if (pl.HWp % 128 == 0) run(CfgP128x32{}); else run(CfgP64x32{});
                 }
@@ -280,8 +259,8 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                     p.wp = e->packed_u + e->pk_t[b]; p.K8tot = Ct / 8; p.N = Ct / 2;
                     p.dst = xs(b + 1); p.ldd = Cn; p.dcoff = 0;
                     p.dsum = st_off(fsum(e, e->st_X[b + 1]), Cn); p.dsq = st_off(fsq(e, e->st_X[b + 1]), Cn); p.dstride = Cn;
-                    BY(e, ESZ(e) * ns * ((double)pl.HW * Ct + (double)pn.HW * (Ct / 2)));
-                    launch_gemm(e, cs, p, dim3(ns * pn.HWp / Cfg::BM, (Ct / 2) / Cfg::BN), K_TRANS, 2.0 * ns * pn.HW * Ct * (Ct / 2));
+                    launch_gemm(e, cs, p, dim3(ns * pn.HWp / Cfg::BM, (Ct / 2) / Cfg::BN), K_TRANS, 2.0 * ns * pn.HW * Ct * (Ct / 2),
+                                ESZ(e) * ns * ((double)pl.HW * Ct + (double)pn.HW * (Ct / 2)));
                 };
                 PREC_DISPATCH(e, if (pn.HWp % 128 == 0) run(CfgP128x128{}, PTAG); else run(CfgP64x128{}, PTAG));
             }
@@ -315,8 +294,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
         a.gamma = P + T.norm5.w; a.beta = P + T.norm5.b; a.eps = kEps;
         a.pair_a = e->d_pair_a; a.pair_b = e->d_pair_b; a.F = e->F;
         a.fsum = fsum(e, e->st_F); a.fsq = fsq(e, e->st_F); a.chunk = 64;
-        ProfScope ps(e, st, K_OTHER, 0);
-        PREC_DISPATCH(e, hipLaunchKernelGGL(HIP_KERNEL_NAME(feat_kernel<PREC>), dim3(2, NP, (p4.HW + 63) / 64), dim3(256), 0, st, a));
+        PREC_DISPATCH(e, launch_kernel(e, feat_kernel<PREC>, dim3(2, NP, (p4.HW + 63) / 64), dim3(256), 0, st, K_OTHER, 0, 0, false, a));
     }
     {   // head norm0 + relu + conv0 (1x1, 2048 -> 64)
         const BnTab th = bn_table(e, e->sf_tab, e->max_pairs, 0, 2 * kFeat, P + Hd.n0.w, P + Hd.n0.b);
@@ -330,8 +308,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
         p.wp = e->packed_u + e->pk_head0; p.K8tot = 2 * kFeat / 8; p.N = kHeadMid;
         p.dst = e->H1; p.ldd = kHeadMid; p.dcoff = 0;
         p.dsum = fsum(e, e->st_H1); p.dsq = fsq(e, e->st_H1); p.dstride = kHeadMid;
-        BY(e, 4.0 * NP * p4.HW * (2 * kFeat + kHeadMid));
-        launch_gemm(e, st, p, dim3(NP * p4.HWp / Cfg::BM, 1), K_HEAD0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid);
+        launch_gemm(e, st, p, dim3(NP * p4.HWp / Cfg::BM, 1), K_HEAD0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid, 4.0 * NP * p4.HW * (2 * kFeat + kHeadMid));
             };
             PREC_DISPATCH(e, if (p4.HWp % 128 == 0) run(CfgP128x64{}, PTAG); else run(CfgP64x64{}, PTAG));
     }
@@ -340,18 +317,16 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
         a.h1 = e->H1; a.p4 = p4; a.hsum = fsum(e, e->st_H1); a.hsq = fsq(e, e->st_H1);
         a.gamma = P + Hd.n1.w; a.beta = P + Hd.n1.b; a.eps = kEps;
         a.w2p = e->packed_f + e->pk_head1; a.q = q_out; a.out_ch = e->head_out; a.OH = e->OH; a.OW = e->OW;
-        ProfScope ps(e, st, K_OTHER, 0);
-        hipLaunchKernelGGL(value_conv_kernel, dim3(NP * e->head_out * e->OH * e->OW), dim3(256), 0, st, a);
+        launch_kernel(e, value_conv_kernel, dim3(NP * e->head_out * e->OH * e->OW), dim3(256), 0, st, K_OTHER, 0, 0, false, a);
     }
     {   // BN running statistics, in the reference's update order - and, with or without an update, the reference's NaN propagation: a
         // non-finite batch statistic of a stream (pair) turns the Q values of every sample that uses it into NaN
-        ProfScope ps(e, st, K_OTHER, 0);
-        hipLaunchKernelGGL(bn_update_kernel, dim3(8, (unsigned)e->n_bnupd), dim3(256), 0, st,
-                           e->d_bnupd + (trunk_id * 3 + head_id) * e->bnupd_stride,
-                           e->fstat, e->fstat + e->fstat_span, net->bufs, net->nbt, e->d_seq_t, n_seq_t, e->d_seq_h, n_seq_h,
-                           e->d_pair_a, e->d_pair_b, NP, e->head_out * e->OH * e->OW, q_out, NS, (n_seq_t || n_seq_h) ? 1 : 0);
+        launch_kernel(e, bn_update_kernel, dim3(8, (unsigned)e->n_bnupd), dim3(256), 0, st, K_OTHER, 0, 0, false,
+                      e->d_bnupd + (trunk_id * 3 + head_id) * e->bnupd_stride,
+                      e->fstat, e->fstat + e->fstat_span, net->bufs, net->nbt, e->d_seq_t, n_seq_t, e->d_seq_h, n_seq_h,
+                      e->d_pair_a, e->d_pair_b, NP, e->head_out * e->OH * e->OW, q_out, NS, (n_seq_t || n_seq_h) ? 1 : 0);
     }
-    HIP_OK(hipGetLastError());
+    if (int rc = walk_status(e)) return rc;
     e->f_stem1 = B->heightmaps_dev != nullptr;
     e->bw_phase0_done = false;
     e->have_fwd = true; e->f_trunk = trunk_id; e->f_head = head_id; e->f_streams = NS; e->f_pairs = NP;
