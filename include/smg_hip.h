@@ -42,7 +42,7 @@ typedef struct smg_engine smg_engine;
 const char* smg_last_error(void);
 /* ABI revision of this header: a binding must refuse a library whose smg_version() differs (stale .so) and should
  * compare its own struct sizes with smg_abi_struct_bytes(0 = smg_batch, 1 = smg_net, 2 = smg_adam) before the first call. */
-#define SMG_ABI_VERSION 4
+#define SMG_ABI_VERSION 5
 int smg_version(void);
 int smg_abi_struct_bytes(int which);
 
@@ -145,6 +145,15 @@ int smg_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id,
 int smg_loss(smg_engine* e, int mode, const float* q_dev, const float* labels_dev, int n_pairs,
              float* loss_dev, float* dq_dev, void* stream);
 
+/* Whole-map loss for a dense Q map (inputs larger than S = 640: OH x OW values per pair), the per-pixel formulation of the Huber
+ * of code/trainer.py:345-348; one-channel heads only (head_out != 1 returns -22 and launches nothing).  q, label, weight and dq are
+ * [n_pairs][1][OH][OW]; weight_dev == NULL means all ones, a weight of exactly 0 masks its element.
+ *     loss[j] = sum over the map of w * huber(q - label)        dq = w * huber'(q - label)
+ * The call marks the saved forward "dense dq": the next smg_backward / smg_backward_phase(.., 0) of that forward runs the head's
+ * value-convolution backward in its dense form (see "head_bwd" below).  smg_loss and every later smg_forward clear the mark. */
+int smg_loss_map(smg_engine* e, const float* q_dev, const float* label_dev, const float* weight_dev, int n_pairs,
+                 float* loss_dev, float* dq_dev, void* stream);
+
 /* Backward of the last smg_forward: accumulates (+=) d(sum of losses)/d(param) into
  * net->grads for the trunk and head that forward used.  Replaces loss.backward() at
  * code/trainer.py:350-351. */
@@ -179,10 +188,16 @@ int smg_engine_set_precision(smg_engine* e, int precision);
 /* Engine switches by name.  "deterministic" (0 / 1): the 1x1-convolution weight gradients (conv1 of every dense layer,
  * the largest gradient tensors) are reduced from partial tiles in a fixed order instead of fp32 atomics, so the trunk's
  * convolution weight gradients of two identical calls are bit-identical like the reference's (code/trainer.py:350-351 on one
- * device); BatchNorm affine gradients and the head's value convolution keep their fp32 atomics.  (Since round 3 the fixed-order
+ * device); BatchNorm affine gradients and the head's value convolution (in its per-element form, see "head_bwd") keep their fp32 atomics.  (Since round 3 the fixed-order
  * path is also the default for batches of more than four streams whenever the partial tiles fit the workspace - it is the
  * faster one there; the option guarantees it for every batch: a launch whose partial tiles do not fit the workspace fails
  * with -12 instead of falling back to atomics.)
+ * "head_bwd" (0 / 1 / 2): the form of the head's value-convolution backward.  1: the per-element form - every feature pixel walks the
+ * output elements it feeds, skips zero dq and adds its share of the 20x20 weight gradient with fp32 atomics; right for the single
+ * element smg_loss mode 0 sets.  2: the dense form - a data pass over the 400 taps and a weight pass that owns every element of
+ * the weight gradient (no atomics, pairs in index order: bit-identical between identical calls); right for a whole map.
+ * 0 (default): the dense form after smg_loss_map, else the per-element form.  A 3-class head always runs the per-element form,
+ * and so does smg_train_step_graph (its loss is smg_loss).
  * "serialize" (0 / 1): every kernel on the caller's stream in issue order instead of two concurrent chains (profiling).
  * "debug_stop" (tests only; -1 = off): the next smg_backward returns behind the launches of dense layer (block, layer) =
  * (value / 100, value % 100), 0-based - or, with value % 100 == 50, in front of that block's first layer - with both streams

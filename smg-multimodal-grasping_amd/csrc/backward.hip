@@ -21,7 +21,7 @@ static void pick_chunk(const Plane& pl, int n_planes, int tiles_per_chunk, int& 
 // phases: bit 0 = the head and dense blocks 4, 3, 2 (down to the gradient of block 1's buffer), bit 1 = dense block 1, pool0 and
 // the stem.  Between the two halves every gradient of [transition1 .. norm5] and of the head is final on `st`: a data-parallel
 // caller starts their all-reduce there and hides it under the second half (smg_backward_phase).
-int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t st, int phases) {
+int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t st, int phases, bool elem_head) {
     if (!e->have_fwd) return fail(-22, "smg_backward without a preceding smg_forward");
     if (!net->grads) return fail(-22, "net.grads is NULL");
     // phase bookkeeping: the second half continues the first half of the SAME forward (statistic arenas, ring position, G' buffers)
@@ -84,7 +84,18 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         a.gamma = P + Hd.n1.w; a.beta = P + Hd.n1.b; a.eps = kEps; a.w2p = e->packed_f + e->pk_head1;
         a.dq = dq; a.out_ch = e->head_out; a.OH = e->OH; a.OW = e->OW; a.dh1 = e->DH1;
         a.o1 = b1(e, e->st_H1); a.o2 = b2(e, e->st_H1); a.dbeta = Gr + Hd.n1.b; a.dgamma = Gr + Hd.n1.w; a.dw2 = Gr + Hd.c1.w;
-        launch_kernel(e, value_bwd_kernel, dim3((p4.HW + 63) / 64, NP), dim3(256), 0, st, K_OTHER, 0, 0, false, a);
+        // a dense dq (smg_loss_map's mark, or "head_bwd" = 2) takes the two-pass form without atomics on the weight gradient; one-channel heads only
+        const bool dense = !elem_head && e->head_out == 1 && (e->head_bwd == 2 || (e->head_bwd == 0 && e->f_dense_dq));
+        if (!dense) {
+            launch_kernel(e, value_bwd_kernel, dim3((p4.HW + 63) / 64, NP), dim3(256), 0, st, K_OTHER, 0, 0, false, a);
+        } else {
+            launch_kernel(e, value_bwd_dense_kernel, dim3((p4.HW + 63) / 64, NP), dim3(256), value_bwd_dense_lds(e->OH, e->OW), st, K_OTHER, 0, 0, false, a);
+            ValueWgradDenseArgs w;
+            w.h1 = a.h1; w.p4 = p4; w.hsum = a.hsum; w.hsq = a.hsq; w.gamma = a.gamma; w.beta = a.beta; w.eps = kEps;
+            w.dq = dq; w.OH = e->OH; w.OW = e->OW; w.n_pairs = NP; w.dw2 = a.dw2;
+            w.RC = std::min(e->OH, 64); w.OWp = (e->OW + 3) / 4 * 4; w.Wp = w.OWp + kVFrame;
+            launch_kernel(e, value_wgrad_dense_kernel, dim3(20, kHeadMid / 4), dim3(256), value_wgrad_dense_lds(w), st, K_OTHER, 0, 0, false, w);
+        }
     }
     int chunk4, cps4;
     pick_chunk(p4, NP, 2 * kFeat / 64, chunk4, cps4);

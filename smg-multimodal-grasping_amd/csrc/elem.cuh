@@ -494,6 +494,177 @@ static __global__ __launch_bounds__(256) void value_bwd_kernel(const ValueBwdArg
     }
 }
 
+// The same backward for a DENSE dq (a whole weighted map per pair, smg_loss_map), one-channel heads only.  value_bwd_kernel above
+// walks the output elements a pixel feeds and adds four fp32 atomics per non-zero dq and tap: fine for the one element the Huber
+// of code/trainer.py:345 reads, 1444 x 400 x 64 = 37 M atomics per pair onto 25 600 addresses for a full 38 x 38 map.  Here the
+// work is split by what it reuses:
+//   value_bwd_dense_kernel   (data pass)   dact, DH1, the norm1 sums - per workgroup 64 pixels of one pair, looping over the 400
+//                                          TAPS: one float4 of packed weights per tap serves the thread's four pixels, dq comes
+//                                          from a zero-framed copy in LDS (no bounds test in the loop);
+//   value_wgrad_dense_kernel (weight pass) dW - per workgroup one tap row and channel quad, pairs in index order, every element of
+//                                          dW written by exactly one thread: a fixed summation order and no atomic at all.
+constexpr int kVFrame = 19;     // the 20 x 20 window reaches 19 outputs up / left of a pixel
+static inline size_t value_bwd_dense_lds(int OH, int OW) { return (size_t)(OH + 2 * kVFrame) * (OW + 2 * kVFrame) * sizeof(float); }
+
+static __global__ __launch_bounds__(256) void value_bwd_dense_kernel(const ValueBwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];    // dq of the pair in a frame of zeros: [OH + 38][OW + 38]
+    __shared__ float prm[256];
+    __shared__ float red[2][16][64];
+    const int j = blockIdx.y, t = threadIdx.x, cq = t & 15, slot = t >> 4;
+    const int PW = a.OW + 2 * kVFrame, PH = a.OH + 2 * kVFrame;
+    if (t < 64) {
+        float mean, invstd;
+        bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
+        prm[t] = a.gamma[t] * invstd; prm[64 + t] = a.beta[t]; prm[128 + t] = mean; prm[192 + t] = invstd;
+    }
+    for (int i = t; i < PH * PW; i += 256) {
+        const int y = i / PW - kVFrame, x = i % PW - kVFrame;
+        smem[i] = (y >= 0 && y < a.OH && x >= 0 && x < a.OW) ? a.dq[((int64_t)j * a.OH + y) * a.OW + x] : 0.f;
+    }
+    __syncthreads();
+    // frame position of output (py, px) for each of the thread's four pixels; output (py - ty, px - tx) lies ty rows and tx columns
+    // in front of it (rows -19 .. OH + 18 of the frame: always inside)
+    int base[4]; bool live[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int p = blockIdx.x * 64 + slot + 16 * i;
+        live[i] = p < a.p4.HW;
+        const int py = live[i] ? p / a.p4.W : 0, px = live[i] ? p - py * a.p4.W : 0;
+        base[i] = (py + kVFrame) * PW + px + kVFrame;
+    }
+    float dact[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) dact[i][c] = 0.f;
+    const float* wq = a.w2p + 4 * cq;
+    for (int ty = 0; ty < 20; ++ty) {
+#pragma unroll 5
+        for (int tx = 0; tx < 20; ++tx) {
+            const float4 w = ld4(wq + (ty * 20 + tx) * 64);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float g = smem[base[i] - ty * PW - tx];
+                dact[i][0] = fmaf(g, w.x, dact[i][0]); dact[i][1] = fmaf(g, w.y, dact[i][1]);
+                dact[i][2] = fmaf(g, w.z, dact[i][2]); dact[i][3] = fmaf(g, w.w, dact[i][3]);
+            }
+        }
+    }
+    float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (!live[i]) continue;
+        const int64_t row = (int64_t)j * a.p4.HWp + blockIdx.x * 64 + slot + 16 * i;
+        const float4 hv = ld4(a.h1 + row * 64 + 4 * cq);
+        const float h[4] = {hv.x, hv.y, hv.z, hv.w};
+        float dy[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float act = fmaxf(bn1(h[c], prm[128 + 4 * cq + c], prm[4 * cq + c], prm[64 + 4 * cq + c]), 0.f);
+            dy[c] = act > 0.f ? dact[i][c] : 0.f;
+            s1[c] += dy[c];
+            s2[c] += dy[c] * ((h[c] - prm[128 + 4 * cq + c]) * prm[192 + 4 * cq + c]);
+        }
+        *reinterpret_cast<float4*>(a.dh1 + row * 64 + 4 * cq) = make_float4(dy[0], dy[1], dy[2], dy[3]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { red[0][slot][4 * cq + c] = s1[c]; red[1][slot][4 * cq + c] = s2[c]; }
+    __syncthreads();
+    if (t < 128) {     // (the per-channel norm1 sums keep their one atomic per workgroup, as in value_bwd_kernel)
+        const int q = t >> 6, c = t & 63;
+        float tot = 0.f;
+        for (int k = 0; k < 16; ++k) tot += red[q][k][c];
+        atomicAdd((q ? a.o2 : a.o1) + (int64_t)j * 64 + c + stat_rep(), (double)tot);
+        atomicAdd((q ? a.dgamma : a.dbeta) + c, tot);
+    }
+}
+
+// dW[c][ty][tx] += sum over pairs, oy, ox of dq[j][oy][ox] * act[j][oy + ty][ox + tx][c].
+// Workgroup = (tap row ty, channel quad): 20 x 16 of them.  Per pair (in index order) and chunk of up to 64 output rows it stages
+// the BN + ReLU activations of the feature rows those outputs meet under this tap row - [rows][Wp][4 channels], columns past the
+// plane zero-filled - and the dq rows (zero-filled to a multiple of four columns); thread (row, channel) slides along its row four
+// outputs at a time: 4 dq values and 23 activations feed 80 multiply-adds into its 20 per-tap-column accumulators (fp32 along a
+// row, carried in fp64 from row chunk to row chunk and pair to pair).  The rows meet in LDS (fp64, over the staging area) in row
+// order, and one thread per element adds the rounded total to the gradient array.
+struct ValueWgradDenseArgs {
+    const float* h1; Plane p4;
+    const double* hsum; const double* hsq;
+    const float* gamma; const float* beta; float eps;
+    const float* dq; int OH, OW, n_pairs;
+    float* dw2;                               // native [1][64][20][20]
+    int RC, OWp, Wp;                          // output rows per chunk (<= 64), OW rounded up to 4, OWp + 19 staged columns
+};
+static inline size_t value_wgrad_dense_lds(const ValueWgradDenseArgs& a) {
+    const size_t stage = ((size_t)a.RC * a.Wp * 4 + (size_t)a.RC * a.OWp) * sizeof(float), meet = 64 * 80 * sizeof(double);
+    return std::max(stage, meet) + 16 * sizeof(float);
+}
+
+static __global__ __launch_bounds__(256) void value_wgrad_dense_kernel(const ValueWgradDenseArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* acts = smem;                                   // [RC][Wp] float4
+    float* dqs = acts + (size_t)a.RC * a.Wp * 4;          // [RC][OWp]
+    double* red = reinterpret_cast<double*>(smem);        // [64][20][4], once the last chunk has been read
+    float* prm = smem + max(a.RC * (a.Wp * 4 + a.OWp), 64 * 80 * 2);      // mean[4], scale[4], beta[4]
+    const int ty = blockIdx.x, cq = blockIdx.y, t = threadIdx.x, c = t & 3, g = t >> 2;
+    const int W = a.p4.W;
+    double tot[20];
+#pragma unroll
+    for (int k = 0; k < 20; ++k) tot[k] = 0.0;
+    for (int j = 0; j < a.n_pairs; ++j) {
+        if (t < 4) {
+            float mean, invstd;
+            bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + 4 * cq + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
+            prm[t] = mean; prm[4 + t] = a.gamma[4 * cq + t] * invstd; prm[8 + t] = a.beta[4 * cq + t];
+        }
+        for (int r0 = 0; r0 < a.OH; r0 += a.RC) {
+            const int nr = min(a.RC, a.OH - r0);
+            __syncthreads();        // the parameters are written; the previous chunk has been read
+            for (int i = t; i < nr * a.Wp; i += 256) {
+                const int row = i / a.Wp, x = i - row * a.Wp;
+                float4 v = zero4();
+                if (x < W) v = bnrelu4(ld4(a.h1 + ((int64_t)j * a.p4.HWp + (r0 + row + ty) * W + x) * 64 + 4 * cq), prm, 4);
+                *reinterpret_cast<float4*>(acts + (size_t)i * 4) = v;
+            }
+            for (int i = t; i < nr * a.OWp; i += 256) {
+                const int row = i / a.OWp, x = i - row * a.OWp;
+                dqs[i] = x < a.OW ? a.dq[((int64_t)j * a.OH + r0 + row) * a.OW + x] : 0.f;
+            }
+            __syncthreads();
+            if (g < nr) {
+                float acc[20];
+#pragma unroll
+                for (int k = 0; k < 20; ++k) acc[k] = 0.f;
+                const float* ar = acts + (size_t)g * a.Wp * 4 + c;
+                const float* dr = dqs + g * a.OWp;
+                for (int ox = 0; ox < a.OWp; ox += 4) {
+                    const float4 d4 = ld4(dr + ox);
+                    const float d[4] = {d4.x, d4.y, d4.z, d4.w};
+                    float av[23];
+#pragma unroll
+                    for (int k = 0; k < 23; ++k) av[k] = ar[(ox + k) * 4];
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+#pragma unroll
+                        for (int tx = 0; tx < 20; ++tx) acc[tx] = fmaf(d[b], av[b + tx], acc[tx]);
+                }
+#pragma unroll
+                for (int k = 0; k < 20; ++k) tot[k] += (double)acc[k];
+            }
+        }
+    }
+    __syncthreads();             // the staging area becomes the meeting place
+#pragma unroll
+    for (int tx = 0; tx < 20; ++tx) red[g * 80 + tx * 4 + c] = tot[tx];
+    __syncthreads();
+    if (t < 80) {
+        double sum = 0.0;
+        for (int k = 0; k < 64; ++k) sum += red[k * 80 + t];
+        const int tx = t >> 2, ch = 4 * cq + (t & 3);
+        float* dst = a.dw2 + (int64_t)ch * 400 + ty * 20 + tx;
+        *dst = *dst + (float)sum;       // one writer per element
+    }
+}
+
 // ------------------------------------------------------------------------------------
 // norm5 backward (no ReLU) fused with the head's norm0 backward and the two-stream
 // concat backward: for stream s, sum over every (pair, slot) that consumed its
@@ -984,6 +1155,34 @@ static __global__ void loss_kernel(int mode, const float* q, const float* labels
             for (int c = 0; c < 3; ++c) dj[c] = sm[c] - (c == y ? 1.f : 0.f);
         }
     }
+}
+
+// Whole-map Huber (smg_loss_map): loss[j] = sum over the map of w * huber(q - label), dq = w * huber'(q - label), the Huber of
+// code/trainer.py:345-348 per element; weight == nullptr: all ones, a weight of 0 masks its element.  One workgroup per pair: thread t takes elements t, t + 256, ...
+// in that order, and the 256 partial sums meet in LDS in a fixed tree.
+static __global__ __launch_bounds__(256) void loss_map_kernel(const float* q, const float* label, const float* weight, int per_pair,
+                                                              float* loss, float* dq) {
+    __shared__ float red[256];
+    const int j = blockIdx.x, t = threadIdx.x;
+    const int64_t o = (int64_t)j * per_pair;
+    float sum = 0.f;
+    for (int i = t; i < per_pair; i += 256) {
+        const float d = q[o + i] - label[o + i];
+        const float w = weight ? weight[o + i] : 1.f;
+        float l, g;
+        if (fabsf(d) < 1.f) { l = 0.5f * (d * d); g = d; }
+        else { l = fabsf(d) - 0.5f; g = d > 0.f ? 1.f : -1.f; }
+        // a weight of exactly zero masks the element whatever q holds there (no -0, no 0 * inf)
+        sum += w == 0.f ? 0.f : w * l;
+        dq[o + i] = w == 0.f ? 0.f : w * g;
+    }
+    red[t] = sum;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) red[t] += red[t + s];
+        __syncthreads();
+    }
+    if (t == 0) loss[j] = red[0];
 }
 
 // ------------------------------------------------------------------------------------

@@ -138,6 +138,8 @@ struct smg_engine {
     // last forward
     bool have_fwd = false; int f_trunk = 0, f_head = 0, f_streams = 0, f_pairs = 0;
     bool bw_phase0_done = false;   // smg_backward_phase(0) ran on the last forward and its second half is still due (reset by every forward / precision change)
+    bool f_dense_dq = false;   // smg_loss_map produced the dq of the last forward: its backward takes the dense head form (cleared by smg_loss and by every forward)
+    int head_bwd = 0;          // smg_engine_set_option("head_bwd"): 0 follow f_dense_dq, 1 always value_bwd_kernel, 2 always the dense form (one-channel heads)
     bool f_stem1 = false;      // the last forward ran the one-channel stem (heightmap input form): img4 holds [streams][HWp] single floats
     int* d_stream_image = nullptr; int* d_stream_rot = nullptr; int* d_pair_a = nullptr; int* d_pair_b = nullptr;
     int* d_seq_t = nullptr; int* d_seq_h = nullptr; int* d_user_ptr = nullptr; int* d_user_pair = nullptr; int* d_user_slot = nullptr;
@@ -441,4 +443,5 @@ static BnTab bn_table(smg_engine* e, int64_t at, int rows_max, int r0, int C, co
 int validate_batch(const smg_engine* e, const smg_batch* B);
 void fill_stage(const smg_engine* e, const smg_batch* B, int* h);
 int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, const smg_batch* B, float* q_out, hipStream_t st);
-int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t st, int phases = 3);
+// elem_head: the head's value-convolution backward in its per-element form whatever the mark and the "head_bwd" option say (the captured step)
+int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t st, int phases = 3, bool elem_head = false);

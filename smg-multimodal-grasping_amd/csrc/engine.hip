@@ -278,7 +278,7 @@ static int engine_build(smg_engine* e) {
 // Everything a captured step bakes into its nodes: a call with another key is captured anew (the old graph is dropped).
 struct StepKey {
     const void* params; const void* grads; const void* bufs; const void* nbt;
-    int trunk_id, head_id, n_streams, n_pairs, n_images, hm_size, n_seq_t, n_seq_h, n_masks, loss_mode, prec, deterministic;
+    int trunk_id, head_id, n_streams, n_pairs, n_images, hm_size, n_seq_t, n_seq_h, n_masks, loss_mode, prec, deterministic, head_bwd;
     const void* images; const void* heightmaps; const void* masks; double mean, stdv;
     const void* labels; const void* q; const void* loss; const void* dq; const void* m; const void* v; float lr, b1, b2, eps;
     hipStream_t stream;
@@ -310,7 +310,8 @@ static int step_body(smg_engine* e, const smg_net* net, int trunk_id, int head_i
     if (int rc = do_forward(e, net, trunk_id, head_id, B, q, st)) return rc;
     const int per_pair = e->head_out * e->OH * e->OW;
     hipLaunchKernelGGL(loss_kernel, dim3((B->n_pairs + 63) / 64), dim3(64), 0, st, loss_mode, (const float*)q, labels, B->n_pairs, per_pair, loss, dq);
-    if (int rc = do_backward(e, net, dq, st)) return rc;
+    e->f_dense_dq = false;
+    if (int rc = do_backward(e, net, dq, st, 3, true)) return rc;      // the step's loss is smg_loss: the per-element head backward
     const float* sc = reinterpret_cast<const float*>(e->d_stage + e->so_adam);
     const int64_t off[2] = {t0, h0}, cnt[2] = {tn, hn};
     for (int k = 0; k < 2; ++k) {
@@ -427,6 +428,7 @@ int smg_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, co
     if (!net->params || !net->bufs || !net->nbt) return fail(-22, "net arrays are NULL");
     if (trunk_id < 0 || trunk_id > 2 || head_id < 0 || head_id > 2) return fail(-22, "trunk_id / head_id out of range");
     HIP_OK(hipSetDevice(e->device));
+    e->f_dense_dq = false;
     return do_forward(e, net, trunk_id, head_id, batch, q_out_dev, (hipStream_t)stream);
 }
 
@@ -439,6 +441,19 @@ int smg_loss(smg_engine* e, int mode, const float* q_dev, const float* labels_de
     const int per_pair = e->head_out * e->OH * e->OW;
     hipLaunchKernelGGL(loss_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, mode, q_dev, labels_dev, n_pairs, per_pair, loss_dev, dq_dev);
     HIP_OK(hipGetLastError());
+    e->f_dense_dq = false;
+    return 0;
+}
+
+int smg_loss_map(smg_engine* e, const float* q_dev, const float* label_dev, const float* weight_dev, int n_pairs,
+                 float* loss_dev, float* dq_dev, void* stream) {
+    if (!e || !q_dev || !label_dev || !loss_dev || !dq_dev) return fail(-22, "NULL argument");
+    if (e->head_out != 1) return fail(-22, "smg_loss_map: the whole-map Huber needs a one-channel head (head_out == 1)");
+    if (n_pairs < 1 || n_pairs > e->max_pairs) return fail(-22, "n_pairs exceeds the engine's max_pairs");
+    HIP_OK(hipSetDevice(e->device));
+    hipLaunchKernelGGL(loss_map_kernel, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, q_dev, label_dev, weight_dev, e->OH * e->OW, loss_dev, dq_dev);
+    HIP_OK(hipGetLastError());
+    e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0)
     return 0;
 }
 
@@ -478,7 +493,7 @@ int smg_train_step_graph(smg_engine* e, const smg_net* net, int trunk_id, int he
     key.params = net->params; key.grads = net->grads; key.bufs = net->bufs; key.nbt = net->nbt;
     key.trunk_id = trunk_id; key.head_id = head_id; key.n_streams = B->n_streams; key.n_pairs = B->n_pairs; key.n_images = B->n_images;
     key.hm_size = B->hm_size; key.n_seq_t = B->bn_seq_trunk ? B->n_bn_seq_trunk : 0; key.n_seq_h = B->bn_seq_head ? B->n_bn_seq_head : 0;
-    key.n_masks = B->masks_dev ? B->n_masks : 0; key.loss_mode = loss_mode; key.prec = e->prec; key.deterministic = e->deterministic;
+    key.n_masks = B->masks_dev ? B->n_masks : 0; key.loss_mode = loss_mode; key.prec = e->prec; key.deterministic = e->deterministic; key.head_bwd = e->head_bwd;
     key.images = B->images_nchw_dev; key.heightmaps = B->heightmaps_dev; key.masks = B->masks_dev; key.mean = B->image_mean; key.stdv = B->image_std;
     key.labels = labels_dev; key.q = q_out_dev; key.loss = loss_out_dev; key.dq = dq_dev; key.m = adam->m; key.v = adam->v;
     key.lr = adam->lr; key.b1 = adam->beta1; key.b2 = adam->beta2; key.eps = adam->eps; key.stream = caller;
@@ -515,7 +530,7 @@ int smg_train_step_graph(smg_engine* e, const smg_net* net, int trunk_id, int he
         if (err != hipSuccess) rc = fail(-5, std::string("hipGraphLaunch: ") + hipGetErrorString(err));
         // what the step leaves behind on the host side, as the eager calls would
         e->have_fwd = true; e->bw_phase0_done = false; e->f_trunk = trunk_id; e->f_head = head_id; e->f_streams = B->n_streams; e->f_pairs = B->n_pairs;
-        e->f_stem1 = B->heightmaps_dev != nullptr;
+        e->f_stem1 = B->heightmaps_dev != nullptr; e->f_dense_dq = false;
     }
     e->capturing = false;
     if (rc == 0) {
@@ -540,6 +555,10 @@ int smg_engine_set_option(smg_engine* e, const char* name, int value) {
     if (!e || !name) return fail(-22, "NULL argument");
     const std::string s(name);
     if (s == "deterministic") { e->deterministic = value != 0; return 0; }
+    if (s == "head_bwd") {
+        if (value < 0 || value > 2) return fail(-22, "head_bwd must be 0 (follow smg_loss_map's mark), 1 (per-element form) or 2 (dense form)");
+        e->head_bwd = value; return 0;
+    }
     if (s == "serialize") { e->serialize = value != 0; return 0; }
     if (s == "debug_stop") { e->dbg_stop = value; return 0; }
     return fail(-22, "unknown engine option '" + s + "'");

@@ -349,21 +349,9 @@ class Trainer(object):
         print('Training loss: %f' % (loss_value))
         return loss_value
 
-    def train_batch(self, depth_heightmap, m_depth_heightmap, style, rotations, labels, grad_sync=None, return_q=False):
-        """Batched form of backprop: every (scene, rotation) is a training sample (forward as
-        branch C, Huber / CE against its label); the gradient of the SUM of the losses is
-        accumulated in one backward pass (each scene's masked stream is walked once with the summed
-        gradient - exact, the trunk is linear in its output gradient), then ONE Adam step.  Equals
-        that many reference backprop calls with the optimizer step deferred to the end.
-
-        One scene: 2-D heightmaps, `rotations` a list of rotation indices.  Several scenes
-        (SURVEY.md config 4): heightmaps [n_scenes, H, H], `rotations` a list of lists; labels are
-        flat, scene-major.  `grad_sync(model, trunk_id, head_id)` is the data-parallel hook
-        (parallel.allreduce_grads) called between backward and Adam; a hook with `.overlapped` set (parallel.OverlappedGradSync)
-        gets `.start()` after the first half of the backward and `.finish()` after the second.  Returns the loss vector."""
-        model = self.model
-        self.optimizer.zero_grad()
-        model._require_gpu()
+    def _scenes_to_device(self, depth_heightmap, m_depth_heightmap, rotations):
+        """The (depth, masked depth) heightmaps of one scene (2-D) or several ([n_scenes, H, H]) as the interleaved device tensor
+        [2 * n_scenes, H, H] float64 that model.run reads, and `rotations` as one list per scene."""
         if torch.is_tensor(depth_heightmap) and depth_heightmap.is_cuda:
             # device-resident inputs (float64 heightmaps, float32 labels): nothing crosses PCIe and - unlike a pageable
             # host-to-device copy - nothing makes the host wait for the previous step's kernels
@@ -379,7 +367,25 @@ class Trainer(object):
                 d, m, rotations = d[None], m[None], [list(rotations)]
             hm = np.empty((2 * d.shape[0],) + d.shape[1:], dtype=np.float64)
             hm[0::2], hm[1::2] = d, m
-            hm = torch.from_numpy(hm).to(model._flat_params.device)
+            hm = torch.from_numpy(hm).to(self.model._flat_params.device)
+        return hm, rotations
+
+    def train_batch(self, depth_heightmap, m_depth_heightmap, style, rotations, labels, grad_sync=None, return_q=False):
+        """Batched form of backprop: every (scene, rotation) is a training sample (forward as
+        branch C, Huber / CE against its label); the gradient of the SUM of the losses is
+        accumulated in one backward pass (each scene's masked stream is walked once with the summed
+        gradient - exact, the trunk is linear in its output gradient), then ONE Adam step.  Equals
+        that many reference backprop calls with the optimizer step deferred to the end.
+
+        One scene: 2-D heightmaps, `rotations` a list of rotation indices.  Several scenes
+        (SURVEY.md config 4): heightmaps [n_scenes, H, H], `rotations` a list of lists; labels are
+        flat, scene-major.  `grad_sync(model, trunk_id, head_id)` is the data-parallel hook
+        (parallel.allreduce_grads) called between backward and Adam; a hook with `.overlapped` set (parallel.OverlappedGradSync)
+        gets `.start()` after the first half of the backward and `.finish()` after the second.  Returns the loss vector."""
+        model = self.model
+        self.optimizer.zero_grad()
+        model._require_gpu()
+        hm, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
         num = model.gnum_rotations                     # code/models.py:522,545,568 (gnum for every style)
         rots = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
         dev = model._flat_params.device
@@ -401,6 +407,11 @@ class Trainer(object):
         loss = torch.empty(n, dtype=torch.float32, device=dev)
         dq = torch.empty_like(q)
         eng.loss(0 if self.method == 'reinforcement' else 1, q.data_ptr(), lab.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
+        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
+        return (loss, q) if return_q else loss
+
+    def _backward_and_step(self, token, dq, trunk_id, head_id, grad_sync):
+        model = self.model
         if grad_sync is not None and getattr(grad_sync, "overlapped", False):
             # the all-reduce of everything behind dense block 1 (most of the parameters) runs under the second half of the backward
             model._engine_backward(token, dq, phase=0)
@@ -412,7 +423,104 @@ class Trainer(object):
             if grad_sync is not None:
                 grad_sync(model, trunk_id, head_id)
         self.optimizer.step()
+
+    # ---- dense Q maps (heightmaps larger than 224^2: one Q value per 20x20 window of the feature plane) ------------------------
+    @staticmethod
+    def dense_map_size(heightmap_size):
+        """Side OH = OW of the Q map of a heightmap_size^2 heightmap: the padded input (code/trainer.py:165-173) through the
+        DenseNet-121 strides (stem conv, pool0, three transitions) and the head's 20x20 valid convolution.  224 -> 1, 240 -> 3,
+        320 -> 10, 640 -> 38."""
+        hm = int(heightmap_size)
+        diag = np.ceil(float(2 * hm) * np.sqrt(2) / 32) * 32
+        n = 2 * hm + 2 * int((diag - 2 * hm) / 2)
+        n = (n - 1) // 2 + 1          # conv0: 7x7, stride 2, padding 3
+        n = (n - 1) // 2 + 1          # pool0: 3x3, stride 2, padding 1
+        for _ in range(3):
+            n //= 2                   # transition average pools
+        return n - 20 + 1
+
+    def forward_dense(self, depth_heightmap, m_depth_heightmap, style=0, is_target=False, specific_rotation=-1, return_device=False):
+        """Trainer.forward(..., is_volatile=True) without the scalar-per-rotation restriction: the whole Q map of every evaluated
+        rotation, float64 [R, OH, OW] (R rows from the sweep, 1 from a specific rotation or style 2) - or the float32 device
+        tensor of that shape if asked.  Rotation choice and BN bookkeeping are forward's; a 224^2 heightmap gives [R, 1, 1] with
+        forward's values.  Reinforcement method only (the reactive head's output is a class distribution, not a map of values)."""
+        if self.method != 'reinforcement':
+            raise ValueError("forward_dense: reinforcement method only")
+        model = self.model_target if is_target else self.model
+        with np.errstate(divide="ignore", invalid="ignore"):
+            q = self._evaluate(model, depth_heightmap, m_depth_heightmap, style, True, specific_rotation)
+        self._last_q = q
+        q = q.reshape(q.shape[0], q.shape[2], q.shape[3])
+        return q if return_device else q.cpu().numpy().astype(np.float64)
+
+    def best_dense_action(self, depth_heightmap, m_depth_heightmap, style=0, is_target=False):
+        """The best (rotation, pixel) of the sweep's dense Q maps, found on the device (smg_argmax over the flattened [R, OH, OW]:
+        lowest index on ties like np.argmax, a NaN wins); the host reads back one (index, value) pair.
+        Returns {"rotation", "pixel": (oy, ox), "conf"}."""
+        q = self.forward_dense(depth_heightmap, m_depth_heightmap, style, is_target, return_device=True)
+        dev = q.device
+        idx = torch.empty(1, dtype=torch.int32, device=dev)
+        val = torch.empty(1, dtype=torch.float32, device=dev)
+        smg_hip.argmax(q.data_ptr(), q.numel(), idx.data_ptr(), val.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        i = int(idx.cpu().numpy()[0])
+        _, OH, OW = q.shape
+        return {"rotation": i // (OH * OW), "pixel": ((i // OW) % OH, i % OW), "conf": float(val.cpu().numpy().astype(np.float64)[0])}
+
+    def train_batch_maps(self, depth_heightmap, m_depth_heightmap, style, rotations, label_maps, weight_maps=None, grad_sync=None, return_q=False):
+        """train_batch with a whole label map per sample - the per-pixel formulation: the loss of sample j is
+        sum over its Q map of weight * Huber(q - label) (smg_loss_map; `weight_maps` None = all ones, a weight of 0 masks its
+        pixel), the gradient of the SUM of the losses goes back in one backward pass - the head's value convolution in its dense
+        form - and ONE Adam step follows.  Scenes, rotations, host or device inputs and `grad_sync` as in train_batch;
+        `label_maps` / `weight_maps` are [n_samples, OH, OW] (dense_map_size), scene-major.  Reinforcement method only.
+        Returns the loss vector (and q [n_samples, 1, OH, OW] if asked)."""
+        if self.method != 'reinforcement':
+            raise ValueError("train_batch_maps: reinforcement method only (a map of Q values; the reactive head is a classifier)")
+        per_scene = np.ndim(depth_heightmap) == 3
+        n = sum(len(r) for r in rotations) if per_scene else len(rotations)
+        side = self.dense_map_size(np.shape(depth_heightmap)[-1])
+        for name, maps in (("label_maps", label_maps), ("weight_maps", weight_maps)):
+            if maps is not None and tuple(maps.shape if torch.is_tensor(maps) else np.shape(maps)) != (n, side, side):
+                raise ValueError("%s must be [%d samples, %d, %d] for a %d^2 heightmap, got %s"
+                                 % (name, n, side, side, np.shape(depth_heightmap)[-1], tuple(np.shape(maps))))
+        model = self.model
+        self.optimizer.zero_grad()
+        model._require_gpu()
+        dev = model._flat_params.device
+        hm, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
+        rots = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
+
+        def to_dev(maps):      # (uploaded BEFORE the forward is enqueued, like train_batch's labels)
+            if torch.is_tensor(maps):
+                return maps.to(device=dev, dtype=torch.float32).contiguous()
+            return torch.as_tensor(np.ascontiguousarray(maps, dtype=np.float32), device=dev)
+        lab = to_dev(label_maps)
+        wgt = None if weight_maps is None else to_dev(weight_maps)
+        q = model.run(style, rots, model.gnum_rotations, heightmaps=hm, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
+        eng, token, trunk_id, head_id = model._saved
+        assert tuple(q.shape) == (n, 1, side, side), (tuple(q.shape), n, side)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        dq = torch.empty_like(q)
+        eng.loss_map(q.data_ptr(), lab.data_ptr(), None if wgt is None else wgt.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
+        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
         return (loss, q) if return_q else loss
+
+    def train_batch_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, grad_sync=None, return_q=False):
+        """train_batch_maps with ONE trained pixel per sample: `pixels` holds an (oy, ox) per sample, `labels` its target value -
+        expressed as a one-hot weight map with the label at that pixel.  Pixel (0, 0) is the element train_batch trains."""
+        lab = np.asarray(labels, dtype=np.float32).reshape(-1)
+        pix = np.asarray(pixels, dtype=np.int64).reshape(-1, 2)
+        side = self.dense_map_size(np.shape(depth_heightmap)[-1])
+        if len(pix) != len(lab):
+            raise ValueError("one (oy, ox) and one label per sample")
+        if len(pix) and (pix.min() < 0 or pix.max() >= side):
+            raise ValueError("pixels must lie inside the %d x %d Q map" % (side, side))
+        label_maps = np.zeros((len(lab), side, side), dtype=np.float32)
+        weight_maps = np.zeros_like(label_maps)
+        k = np.arange(len(lab))
+        label_maps[k, pix[:, 0], pix[:, 1]] = lab
+        weight_maps[k, pix[:, 0], pix[:, 1]] = 1.0
+        return self.train_batch_maps(depth_heightmap, m_depth_heightmap, style, rotations, label_maps, weight_maps, grad_sync, return_q)
 
     # The single-sample step of Trainer.backprop as ONE replayed hipGraph (smg_train_step_graph): ~560 launches of 2-20 us each are
     # enqueued by one hipGraphLaunch instead of one by one (same results, bit for bit at zero learning rate).  It saves a little host time

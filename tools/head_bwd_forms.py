@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""A/B of the two forms of the head's value-convolution backward on a DENSE dq (engine option "head_bwd": 1 = the per-element
+form with its fp32 atomics, 2 = the dense two-pass form).
+
+Config-5 geometry: a 640^2 heightmap (S = 1824, 38 x 38 Q maps over 57^2 feature planes), 4 rotations of 32 as samples, full
+weight maps.  Each repeat runs forward + smg_loss_map untimed, then times ONLY the smg_backward call between two events on the
+launch stream; the forms alternate inside one process, after a warm-up of each.  Prints one line per repeat and a JSON summary:
+median / min / max per form, the baseline's repeat-to-repeat spread and the ratio of the medians.
+
+    python tools/head_bwd_forms.py [--repeats 7] [--warmup 2] > profiles/head_bwd_forms.txt
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "smg-multimodal-grasping_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--size", type=int, default=640, help="heightmap side (640 -> S = 1824)")
+    ap.add_argument("--rotations", type=int, default=4)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("head_bwd_forms: no GPU visible (a timing needs the MI355X)")
+    import synthetic
+    from oracle import affordance as orc
+    from trainer import Trainer
+
+    tr = Trainer('reinforcement', 0.5, False, None, False)
+    sd = synthetic.make_state_dict(orc.state_layout(1), 0)
+    tr.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    model = tr.model
+    model.gnum_rotations = model.snum_rotations = 32
+    depth, masks = synthetic.heightmap_scene(4, size=args.size, n_boxes=8)
+    hm, rots = tr._scenes_to_device(depth, depth * masks[0], list(range(5, 5 + args.rotations)))
+    side, n = Trainer.dense_map_size(args.size), args.rotations
+    dev = model._flat_params.device
+    lab = torch.as_tensor(synthetic.uniform(5, "ab/lab", n * side * side, -1.5, 2.5).astype(np.float32), device=dev)
+    wgt = torch.as_tensor(synthetic.uniform(5, "ab/w", n * side * side, 0.05, 1.0).astype(np.float32), device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    loss = torch.empty(n, dtype=torch.float32, device=dev)
+    head = "graspnet_val.grasp-val-conv1.weight"
+
+    def one(form):
+        """forward + loss (untimed), then the timed backward; returns (ms, the value convolution's weight gradient)"""
+        q = model.run(0, rots, 32, heightmaps=hm, mean=tr.image_mean, std=tr.image_std, keep_for_backward=True, update_bn=False)
+        eng = model._saved[0]
+        eng.set_option("head_bwd", form)
+        dq = torch.empty_like(q)
+        eng.loss_map(q.data_ptr(), lab.data_ptr(), wgt.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
+        model.flat_grads().zero_()
+        net = model._net_struct(True)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        t0.record()
+        eng.backward(net, dq.data_ptr(), stream)
+        t1.record()
+        t1.synchronize()
+        eng.set_option("head_bwd", 0)
+        off, cnt = next((o, int(np.prod(s))) for nm, k, o, s in model._layout if nm == head and k == 0)
+        return t0.elapsed_time(t1), model.flat_grads()[off:off + cnt].clone()
+
+    print("# %d^2 heightmap, %d rotations (%d streams), %d x %d maps, full weight maps; the backward call only, ms" % (args.size, n, n + 1, side, side))
+    times, grads = {1: [], 2: []}, {}
+    for _ in range(args.warmup):
+        for form in (1, 2):
+            one(form)
+    for rep in range(args.repeats):
+        for form in ((1, 2) if rep % 2 == 0 else (2, 1)):
+            ms, g = one(form)
+            times[form].append(ms)
+            grads[form] = g
+            print("repeat %d head_bwd=%d backward %.3f ms" % (rep, form, ms), flush=True)
+    eng = model._saved[0]
+    med = {f: float(np.median(times[f])) for f in times}
+    d = float((grads[1].double() - grads[2].double()).norm() / grads[1].double().norm())
+    print(json.dumps({
+        "tool": "head_bwd_forms", "input_size": eng.S, "samples": n, "streams": n + 1, "map": [side, side], "repeats": args.repeats,
+        "per_element_ms": {"median": med[1], "min": min(times[1]), "max": max(times[1])},
+        "dense_ms": {"median": med[2], "min": min(times[2]), "max": max(times[2])},
+        "baseline_spread_ms": max(times[1]) - min(times[1]),
+        "dense_over_per_element": med[2] / med[1],
+        "value_conv_wgrad_rel_distance": d,
+    }))
+
+
+if __name__ == "__main__":
+    main()
