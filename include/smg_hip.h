@@ -42,7 +42,7 @@ typedef struct smg_engine smg_engine;
 const char* smg_last_error(void);
 /* ABI revision of this header: a binding must refuse a library whose smg_version() differs (stale .so) and should
  * compare its own struct sizes with smg_abi_struct_bytes(0 = smg_batch, 1 = smg_net, 2 = smg_adam) before the first call. */
-#define SMG_ABI_VERSION 5
+#define SMG_ABI_VERSION 6
 int smg_version(void);
 int smg_abi_struct_bytes(int which);
 
@@ -154,6 +154,20 @@ int smg_loss(smg_engine* e, int mode, const float* q_dev, const float* labels_de
 int smg_loss_map(smg_engine* e, const float* q_dev, const float* label_dev, const float* weight_dev, int n_pairs,
                  float* loss_dev, float* dq_dev, void* stream);
 
+/* Whole-map cross entropy for the dense class maps of a 3-class head (reactive_net on inputs larger than S = 640): the reference's
+ * CrossEntropyLoss2d (code/utils.py:306-313: NLLLoss2d(log_softmax(x, dim=1)), class weights {1, 1, 0}: code/trainer.py:38-60)
+ * applied to the whole head output instead of the one pixel of code/trainer.py:296-299.  head_out != 3 returns -22 and launches
+ * nothing.  q and dq are [n_pairs][3][OH][OW]; label is [n_pairs][1][OH][OW], float32 class indices as in smg_loss mode 1: 0 and 1
+ * carry weight 1, anything else is class 2 ("no loss", weight 0) - the mask of the unlabelled pixels.  With P = OH * OW, per pair:
+ *     nll_p   = logsumexp(q[:, p]) - q[y_p, p]          W = number of pixels of class 0 / 1
+ *     loss[j] = (sum of nll_p over those pixels) / W     (torch's weighted-mean nll_loss; 0 when W == 0, not 0/0)
+ *     dq[c,p] = (softmax(q[:, p])[c] - [c == y_p]) / W   (exactly 0 in all three channels of a class-2 pixel, whatever q holds)
+ * Per pixel the arithmetic is smg_loss mode 1's: a map with exactly one labelled pixel reproduces its loss and dq bit for bit.
+ * Like smg_loss_map the call marks the saved forward "dense dq" (see "head_bwd" below); smg_loss and every later smg_forward
+ * clear the mark. */
+int smg_loss_map_ce(smg_engine* e, const float* q_dev, const float* label_dev, int n_pairs,
+                    float* loss_dev, float* dq_dev, void* stream);
+
 /* Backward of the last smg_forward: accumulates (+=) d(sum of losses)/d(param) into
  * net->grads for the trunk and head that forward used.  Replaces loss.backward() at
  * code/trainer.py:350-351. */
@@ -196,8 +210,9 @@ int smg_engine_set_precision(smg_engine* e, int precision);
  * output elements it feeds, skips zero dq and adds its share of the 20x20 weight gradient with fp32 atomics; right for the single
  * element smg_loss mode 0 sets.  2: the dense form - a data pass over the 400 taps and a weight pass that owns every element of
  * the weight gradient (no atomics, pairs in index order: bit-identical between identical calls); right for a whole map.
- * 0 (default): the dense form after smg_loss_map, else the per-element form.  A 3-class head always runs the per-element form,
- * and so does smg_train_step_graph (its loss is smg_loss).
+ * 0 (default): the dense form after smg_loss_map / smg_loss_map_ce, else the per-element form.  A 3-class head follows the same
+ * rule as a one-channel head (its dense form loops over the three output channels).  smg_train_step_graph always runs the
+ * per-element form (its loss is smg_loss).
  * "serialize" (0 / 1): every kernel on the caller's stream in issue order instead of two concurrent chains (profiling).
  * "debug_stop" (tests only; -1 = off): the next smg_backward returns behind the launches of dense layer (block, layer) =
  * (value / 100, value % 100), 0-based - or, with value % 100 == 50, in front of that block's first layer - with both streams

@@ -84,17 +84,25 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         a.gamma = P + Hd.n1.w; a.beta = P + Hd.n1.b; a.eps = kEps; a.w2p = e->packed_f + e->pk_head1;
         a.dq = dq; a.out_ch = e->head_out; a.OH = e->OH; a.OW = e->OW; a.dh1 = e->DH1;
         a.o1 = b1(e, e->st_H1); a.o2 = b2(e, e->st_H1); a.dbeta = Gr + Hd.n1.b; a.dgamma = Gr + Hd.n1.w; a.dw2 = Gr + Hd.c1.w;
-        // a dense dq (smg_loss_map's mark, or "head_bwd" = 2) takes the two-pass form without atomics on the weight gradient; one-channel heads only
-        const bool dense = !elem_head && e->head_out == 1 && (e->head_bwd == 2 || (e->head_bwd == 0 && e->f_dense_dq));
+        // a dense dq (the mark of smg_loss_map / smg_loss_map_ce, or "head_bwd" = 2) takes the two-pass form without atomics on the weight
+        // gradient, one-channel and 3-class heads alike
+        const bool dense = !elem_head && (e->head_bwd == 2 || (e->head_bwd == 0 && e->f_dense_dq));
         if (!dense) {
             launch_kernel(e, value_bwd_kernel, dim3((p4.HW + 63) / 64, NP), dim3(256), 0, st, K_OTHER, 0, 0, false, a);
         } else {
-            launch_kernel(e, value_bwd_dense_kernel, dim3((p4.HW + 63) / 64, NP), dim3(256), value_bwd_dense_lds(e->OH, e->OW), st, K_OTHER, 0, 0, false, a);
             ValueWgradDenseArgs w;
             w.h1 = a.h1; w.p4 = p4; w.hsum = a.hsum; w.hsq = a.hsq; w.gamma = a.gamma; w.beta = a.beta; w.eps = kEps;
             w.dq = dq; w.OH = e->OH; w.OW = e->OW; w.n_pairs = NP; w.dw2 = a.dw2;
             w.RC = std::min(e->OH, 64); w.OWp = (e->OW + 3) / 4 * 4; w.Wp = w.OWp + kVFrame;
-            launch_kernel(e, value_wgrad_dense_kernel, dim3(20, kHeadMid / 4), dim3(256), value_wgrad_dense_lds(w), st, K_OTHER, 0, 0, false, w);
+            const dim3 dgrid((p4.HW + 63) / 64, NP);
+            if (e->head_out == 1) {
+                launch_kernel(e, value_bwd_dense_kernel, dgrid, dim3(256), value_bwd_dense_lds(e->OH, e->OW), st, K_OTHER, 0, 0, false, a);
+                launch_kernel(e, value_wgrad_dense_kernel, dim3(20, kHeadMid / 4), dim3(256), value_wgrad_dense_lds(w), st, K_OTHER, 0, 0, false, w);
+            } else {
+                // (38 x 38 maps: 78 528 B of dynamic LDS - launch_kernel raises the kernel's limit)
+                launch_kernel(e, value_bwd_dense3_kernel, dgrid, dim3(256), value_bwd_dense3_lds(e->OH, e->OW), st, K_OTHER, 0, 0, false, a);
+                launch_kernel(e, value_wgrad_dense3_kernel, dim3(20, kHeadMid / 4, 3), dim3(256), value_wgrad_dense_lds(w), st, K_OTHER, 0, 0, false, w);
+            }
         }
     }
     int chunk4, cps4;

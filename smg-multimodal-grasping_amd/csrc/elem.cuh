@@ -494,15 +494,17 @@ static __global__ __launch_bounds__(256) void value_bwd_kernel(const ValueBwdArg
     }
 }
 
-// The same backward for a DENSE dq (a whole weighted map per pair, smg_loss_map), one-channel heads only.  value_bwd_kernel above
+// The same backward for a DENSE dq (a whole weighted map per pair: smg_loss_map on a one-channel head, smg_loss_map_ce on a
+// 3-class one, whose two kernels follow their one-channel originals below).  value_bwd_kernel above
 // walks the output elements a pixel feeds and adds four fp32 atomics per non-zero dq and tap: fine for the one element the Huber
-// of code/trainer.py:345 reads, 1444 x 400 x 64 = 37 M atomics per pair onto 25 600 addresses for a full 38 x 38 map.  Here the
-// work is split by what it reuses:
+// of code/trainer.py:345 reads, 1444 x 400 x 64 = 37 M atomics per pair and output channel onto 25 600 addresses for a full
+// 38 x 38 map.  Here the work is split by what it reuses:
 //   value_bwd_dense_kernel   (data pass)   dact, DH1, the norm1 sums - per workgroup 64 pixels of one pair, looping over the 400
-//                                          TAPS: one float4 of packed weights per tap serves the thread's four pixels, dq comes
-//                                          from a zero-framed copy in LDS (no bounds test in the loop);
-//   value_wgrad_dense_kernel (weight pass) dW - per workgroup one tap row and channel quad, pairs in index order, every element of
-//                                          dW written by exactly one thread: a fixed summation order and no atomic at all.
+//                                          TAPS: one float4 of packed weights per tap and output channel serves the thread's
+//                                          four pixels, dq comes from a zero-framed copy in LDS (no bounds test in the loop);
+//   value_wgrad_dense_kernel (weight pass) dW - per workgroup one tap row and channel quad (and output channel), pairs in index
+//                                          order, every element of dW written by exactly one thread: a fixed summation order
+//                                          and no atomic at all.
 constexpr int kVFrame = 19;     // the 20 x 20 window reaches 19 outputs up / left of a pixel
 static inline size_t value_bwd_dense_lds(int OH, int OW) { return (size_t)(OH + 2 * kVFrame) * (OW + 2 * kVFrame) * sizeof(float); }
 
@@ -579,6 +581,91 @@ static __global__ __launch_bounds__(256) void value_bwd_dense_kernel(const Value
     }
 }
 
+// The data pass of a 3-class head: the frame holds the three dq maps, [3][OH + 38][OW + 38] (69 312 B at 38 x 38: above the
+// 64 KB default, the launch path raises the kernel's limit), and every tap reads three float4 of packed weights and twelve frame
+// values.  The parameter and reduction arrays follow the frame in the DYNAMIC area: the raised limit of 160 KiB is the whole CU's, so a
+// kernel that takes it must not hold static LDS beside it (the raise is refused and the launch fails).  A kernel of its own, not a template shared with the one above: sharing the body moved the one-channel kernel's register
+// allocation and instruction order, and its code object is pinned by the bit-identity tests of the one-channel path.
+static inline size_t value_bwd_dense3_lds(int OH, int OW) { return 3 * value_bwd_dense_lds(OH, OW) + (256 + 2 * 16 * 64) * sizeof(float); }
+static __global__ __launch_bounds__(256) void value_bwd_dense3_kernel(const ValueBwdArgs a) {
+    constexpr int OC = 3;
+    extern __shared__ __attribute__((aligned(16))) float smem[];    // dq of the pair in a frame of zeros: [OC][OH + 38][OW + 38]
+    const int j = blockIdx.y, t = threadIdx.x, cq = t & 15, slot = t >> 4;
+    const int PW = a.OW + 2 * kVFrame, PH = a.OH + 2 * kVFrame;
+    float* prm = smem + OC * PH * PW;                                                  // [256]
+    float (*red)[16][64] = reinterpret_cast<float (*)[16][64]>(prm + 256);             // [2][16][64]
+    if (t < 64) {
+        float mean, invstd;
+        bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
+        prm[t] = a.gamma[t] * invstd; prm[64 + t] = a.beta[t]; prm[128 + t] = mean; prm[192 + t] = invstd;
+    }
+#pragma unroll
+    for (int o = 0; o < OC; ++o)
+        for (int i = t; i < PH * PW; i += 256) {
+            const int y = i / PW - kVFrame, x = i % PW - kVFrame;
+            smem[o * PH * PW + i] = (y >= 0 && y < a.OH && x >= 0 && x < a.OW) ? a.dq[(((int64_t)j * OC + o) * a.OH + y) * a.OW + x] : 0.f;
+        }
+    __syncthreads();
+    // frame position of output (py, px) for each of the thread's four pixels; output (py - ty, px - tx) lies ty rows and tx columns
+    // in front of it (rows -19 .. OH + 18 of the frame: always inside)
+    int base[4]; bool live[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int p = blockIdx.x * 64 + slot + 16 * i;
+        live[i] = p < a.p4.HW;
+        const int py = live[i] ? p / a.p4.W : 0, px = live[i] ? p - py * a.p4.W : 0;
+        base[i] = (py + kVFrame) * PW + px + kVFrame;
+    }
+    float dact[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) dact[i][c] = 0.f;
+    const float* wq = a.w2p + 4 * cq;
+    for (int ty = 0; ty < 20; ++ty) {
+#pragma unroll 5
+        for (int tx = 0; tx < 20; ++tx) {
+#pragma unroll
+            for (int o = 0; o < OC; ++o) {
+                const float4 w = ld4(wq + (o * 400 + ty * 20 + tx) * 64);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float g = smem[o * PH * PW + base[i] - ty * PW - tx];
+                    dact[i][0] = fmaf(g, w.x, dact[i][0]); dact[i][1] = fmaf(g, w.y, dact[i][1]);
+                    dact[i][2] = fmaf(g, w.z, dact[i][2]); dact[i][3] = fmaf(g, w.w, dact[i][3]);
+                }
+            }
+        }
+    }
+    float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (!live[i]) continue;
+        const int64_t row = (int64_t)j * a.p4.HWp + blockIdx.x * 64 + slot + 16 * i;
+        const float4 hv = ld4(a.h1 + row * 64 + 4 * cq);
+        const float h[4] = {hv.x, hv.y, hv.z, hv.w};
+        float dy[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float act = fmaxf(bn1(h[c], prm[128 + 4 * cq + c], prm[4 * cq + c], prm[64 + 4 * cq + c]), 0.f);
+            dy[c] = act > 0.f ? dact[i][c] : 0.f;
+            s1[c] += dy[c];
+            s2[c] += dy[c] * ((h[c] - prm[128 + 4 * cq + c]) * prm[192 + 4 * cq + c]);
+        }
+        *reinterpret_cast<float4*>(a.dh1 + row * 64 + 4 * cq) = make_float4(dy[0], dy[1], dy[2], dy[3]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { red[0][slot][4 * cq + c] = s1[c]; red[1][slot][4 * cq + c] = s2[c]; }
+    __syncthreads();
+    if (t < 128) {     // (the per-channel norm1 sums keep their one atomic per workgroup, as in value_bwd_kernel)
+        const int q = t >> 6, c = t & 63;
+        float tot = 0.f;
+        for (int k = 0; k < 16; ++k) tot += red[q][k][c];
+        atomicAdd((q ? a.o2 : a.o1) + (int64_t)j * 64 + c + stat_rep(), (double)tot);
+        atomicAdd((q ? a.dgamma : a.dbeta) + c, tot);
+    }
+}
+
 // dW[c][ty][tx] += sum over pairs, oy, ox of dq[j][oy][ox] * act[j][oy + ty][ox + tx][c].
 // Workgroup = (tap row ty, channel quad): 20 x 16 of them.  Per pair (in index order) and chunk of up to 64 output rows it stages
 // the BN + ReLU activations of the feature rows those outputs meet under this tap row - [rows][Wp][4 channels], columns past the
@@ -591,7 +678,7 @@ struct ValueWgradDenseArgs {
     const double* hsum; const double* hsq;
     const float* gamma; const float* beta; float eps;
     const float* dq; int OH, OW, n_pairs;
-    float* dw2;                               // native [1][64][20][20]
+    float* dw2;                               // native [out][64][20][20]
     int RC, OWp, Wp;                          // output rows per chunk (<= 64), OW rounded up to 4, OWp + 19 staged columns
 };
 static inline size_t value_wgrad_dense_lds(const ValueWgradDenseArgs& a) {
@@ -661,6 +748,78 @@ static __global__ __launch_bounds__(256) void value_wgrad_dense_kernel(const Val
         for (int k = 0; k < 64; ++k) sum += red[k * 80 + t];
         const int tx = t >> 2, ch = 4 * cq + (t & 3);
         float* dst = a.dw2 + (int64_t)ch * 400 + ty * 20 + tx;
+        *dst = *dst + (float)sum;       // one writer per element
+    }
+}
+
+// The weight pass of a 3-class head, dW [3][64][20][20]: the output channel is the third grid dimension - 20 x 16 x 3 workgroups, the
+// activations staged once per output channel (60 per-tap-column accumulators in fp32 and fp64 per thread would not fit the
+// register file without scratch).  Same order of summation per element as the kernel above; a kernel of its own for the same reason
+// as value_bwd_dense3_kernel.
+static __global__ __launch_bounds__(256) void value_wgrad_dense3_kernel(const ValueWgradDenseArgs a) {
+    constexpr int OC = 3;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* acts = smem;                                   // [RC][Wp] float4
+    float* dqs = acts + (size_t)a.RC * a.Wp * 4;          // [RC][OWp]
+    double* red = reinterpret_cast<double*>(smem);        // [64][20][4], once the last chunk has been read
+    float* prm = smem + max(a.RC * (a.Wp * 4 + a.OWp), 64 * 80 * 2);      // mean[4], scale[4], beta[4]
+    const int ty = blockIdx.x, cq = blockIdx.y, t = threadIdx.x, c = t & 3, g = t >> 2;
+    const int o = blockIdx.z;
+    const int W = a.p4.W;
+    double tot[20];
+#pragma unroll
+    for (int k = 0; k < 20; ++k) tot[k] = 0.0;
+    for (int j = 0; j < a.n_pairs; ++j) {
+        if (t < 4) {
+            float mean, invstd;
+            bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + 4 * cq + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
+            prm[t] = mean; prm[4 + t] = a.gamma[4 * cq + t] * invstd; prm[8 + t] = a.beta[4 * cq + t];
+        }
+        for (int r0 = 0; r0 < a.OH; r0 += a.RC) {
+            const int nr = min(a.RC, a.OH - r0);
+            __syncthreads();        // the parameters are written; the previous chunk has been read
+            for (int i = t; i < nr * a.Wp; i += 256) {
+                const int row = i / a.Wp, x = i - row * a.Wp;
+                float4 v = zero4();
+                if (x < W) v = bnrelu4(ld4(a.h1 + ((int64_t)j * a.p4.HWp + (r0 + row + ty) * W + x) * 64 + 4 * cq), prm, 4);
+                *reinterpret_cast<float4*>(acts + (size_t)i * 4) = v;
+            }
+            for (int i = t; i < nr * a.OWp; i += 256) {
+                const int row = i / a.OWp, x = i - row * a.OWp;
+                dqs[i] = x < a.OW ? a.dq[(((int64_t)j * OC + o) * a.OH + r0 + row) * a.OW + x] : 0.f;
+            }
+            __syncthreads();
+            if (g < nr) {
+                float acc[20];
+#pragma unroll
+                for (int k = 0; k < 20; ++k) acc[k] = 0.f;
+                const float* ar = acts + (size_t)g * a.Wp * 4 + c;
+                const float* dr = dqs + g * a.OWp;
+                for (int ox = 0; ox < a.OWp; ox += 4) {
+                    const float4 d4 = ld4(dr + ox);
+                    const float d[4] = {d4.x, d4.y, d4.z, d4.w};
+                    float av[23];
+#pragma unroll
+                    for (int k = 0; k < 23; ++k) av[k] = ar[(ox + k) * 4];
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+#pragma unroll
+                        for (int tx = 0; tx < 20; ++tx) acc[tx] = fmaf(d[b], av[b + tx], acc[tx]);
+                }
+#pragma unroll
+                for (int k = 0; k < 20; ++k) tot[k] += (double)acc[k];
+            }
+        }
+    }
+    __syncthreads();             // the staging area becomes the meeting place
+#pragma unroll
+    for (int tx = 0; tx < 20; ++tx) red[g * 80 + tx * 4 + c] = tot[tx];
+    __syncthreads();
+    if (t < 80) {
+        double sum = 0.0;
+        for (int k = 0; k < 64; ++k) sum += red[k * 80 + t];
+        const int tx = t >> 2, ch = 4 * cq + (t & 3);
+        float* dst = a.dw2 + ((int64_t)o * 64 + ch) * 400 + ty * 20 + tx;
         *dst = *dst + (float)sum;       // one writer per element
     }
 }
@@ -1183,6 +1342,56 @@ static __global__ __launch_bounds__(256) void loss_map_kernel(const float* q, co
         __syncthreads();
     }
     if (t == 0) loss[j] = red[0];
+}
+
+// Whole-map cross entropy of a 3-class head (smg_loss_map_ce): the reference's CrossEntropyLoss2d (code/utils.py:306-313, class
+// weights {1, 1, 0}: code/trainer.py:38-60) on the whole head output instead of the one pixel of code/trainer.py:296-299 - torch's
+// weighted-mean nll_loss per pair.  q [n][3][P], label [n][1][P] float class indices (anything but 0 / 1 is class 2, "no loss"):
+//     nll_p = logsumexp(q[:, p]) - q[y_p, p],  W = number of pixels of class 0 / 1,  loss = sum nll_p / W,
+//     dq[c][p] = (softmax(q[:, p])[c] - [c == y_p]) / W;   class-2 pixels: no term, dq exactly 0 whatever q holds;  W == 0: loss 0, dq 0.
+// Per pixel the arithmetic of loss_kernel mode 1, operation for operation (a map with one weighted pixel reproduces it bit for
+// bit: x / 1 and 1 * x are exact).  One workgroup per pair, two passes: the two sums (thread t takes pixels t, t + 256, ... in that
+// order, the 256 partial sums meet in LDS in a fixed tree), then dq.
+static __global__ __launch_bounds__(256) void loss_map_ce_kernel(const float* q, const float* label, int P, float* loss, float* dq) {
+    __shared__ float red[2][256];
+    const int j = blockIdx.x, t = threadIdx.x;
+    const float* qj = q + (int64_t)j * 3 * P;
+    const float* lj = label + (int64_t)j * P;
+    float* dj = dq + (int64_t)j * 3 * P;
+    float sum = 0.f, cnt = 0.f;
+    for (int p = t; p < P; p += 256) {
+        const float lf = lj[p];
+        if (lf != 0.f && lf != 1.f) continue;
+        const float q0 = qj[p], q1 = qj[P + p], q2 = qj[2 * P + p];
+        const float m = fmaxf(q0, fmaxf(q1, q2));
+        const float e0 = expf(q0 - m), e1 = expf(q1 - m), e2 = expf(q2 - m);
+        const float se = e0 + e1 + e2, lse = logf(se) + m;
+        sum += lse - (lf == 0.f ? q0 : q1);
+        cnt += 1.f;
+    }
+    red[0][t] = sum; red[1][t] = cnt;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) { red[0][t] += red[0][t + s]; red[1][t] += red[1][t + s]; }
+        __syncthreads();
+    }
+    const float W = red[1][0];
+    if (t == 0) loss[j] = W > 0.f ? red[0][0] / W : 0.f;
+    const float scale = 1.f / W;                 // (unused when W == 0: every pixel is masked then)
+    for (int p = t; p < P; p += 256) {
+        const float lf = lj[p];
+        float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+        if (lf == 0.f || lf == 1.f) {
+            const float q0 = qj[p], q1 = qj[P + p], q2 = qj[2 * P + p];
+            const float m = fmaxf(q0, fmaxf(q1, q2));
+            const float e0 = expf(q0 - m), e1 = expf(q1 - m), e2 = expf(q2 - m);
+            const float se = e0 + e1 + e2;
+            d0 = scale * (e0 / se - (lf == 0.f ? 1.f : 0.f));
+            d1 = scale * (e1 / se - (lf == 1.f ? 1.f : 0.f));
+            d2 = scale * (e2 / se - 0.f);
+        }
+        dj[p] = d0; dj[P + p] = d1; dj[2 * P + p] = d2;
+    }
 }
 
 // ------------------------------------------------------------------------------------

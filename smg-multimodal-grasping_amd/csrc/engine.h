@@ -138,8 +138,8 @@ struct smg_engine {
     // last forward
     bool have_fwd = false; int f_trunk = 0, f_head = 0, f_streams = 0, f_pairs = 0;
     bool bw_phase0_done = false;   // smg_backward_phase(0) ran on the last forward and its second half is still due (reset by every forward / precision change)
-    bool f_dense_dq = false;   // smg_loss_map produced the dq of the last forward: its backward takes the dense head form (cleared by smg_loss and by every forward)
-    int head_bwd = 0;          // smg_engine_set_option("head_bwd"): 0 follow f_dense_dq, 1 always value_bwd_kernel, 2 always the dense form (one-channel heads)
+    bool f_dense_dq = false;   // smg_loss_map / smg_loss_map_ce produced the dq of the last forward: its backward takes the dense head form (cleared by smg_loss and by every forward)
+    int head_bwd = 0;          // smg_engine_set_option("head_bwd"): 0 follow f_dense_dq, 1 always value_bwd_kernel, 2 always the dense form
     bool f_stem1 = false;      // the last forward ran the one-channel stem (heightmap input form): img4 holds [streams][HWp] single floats
     int* d_stream_image = nullptr; int* d_stream_rot = nullptr; int* d_pair_a = nullptr; int* d_pair_b = nullptr;
     int* d_seq_t = nullptr; int* d_seq_h = nullptr; int* d_user_ptr = nullptr; int* d_user_pair = nullptr; int* d_user_slot = nullptr;

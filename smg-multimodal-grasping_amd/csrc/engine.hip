@@ -457,6 +457,17 @@ int smg_loss_map(smg_engine* e, const float* q_dev, const float* label_dev, cons
     return 0;
 }
 
+int smg_loss_map_ce(smg_engine* e, const float* q_dev, const float* label_dev, int n_pairs, float* loss_dev, float* dq_dev, void* stream) {
+    if (!e || !q_dev || !label_dev || !loss_dev || !dq_dev) return fail(-22, "NULL argument");
+    if (e->head_out != 3) return fail(-22, "smg_loss_map_ce: the whole-map cross entropy needs a 3-class head (head_out == 3)");
+    if (n_pairs < 1 || n_pairs > e->max_pairs) return fail(-22, "n_pairs exceeds the engine's max_pairs");
+    HIP_OK(hipSetDevice(e->device));
+    hipLaunchKernelGGL(loss_map_ce_kernel, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, q_dev, label_dev, e->OH * e->OW, loss_dev, dq_dev);
+    HIP_OK(hipGetLastError());
+    e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0)
+    return 0;
+}
+
 int smg_backward(smg_engine* e, const smg_net* net, const float* dq_dev, void* stream) {
     if (!e || !net || !dq_dev) return fail(-22, "NULL argument");
     HIP_OK(hipSetDevice(e->device));
@@ -556,7 +567,7 @@ int smg_engine_set_option(smg_engine* e, const char* name, int value) {
     const std::string s(name);
     if (s == "deterministic") { e->deterministic = value != 0; return 0; }
     if (s == "head_bwd") {
-        if (value < 0 || value > 2) return fail(-22, "head_bwd must be 0 (follow smg_loss_map's mark), 1 (per-element form) or 2 (dense form)");
+        if (value < 0 || value > 2) return fail(-22, "head_bwd must be 0 (follow the mark of smg_loss_map / smg_loss_map_ce), 1 (per-element form) or 2 (dense form)");
         e->head_bwd = value; return 0;
     }
     if (s == "serialize") { e->serialize = value != 0; return 0; }

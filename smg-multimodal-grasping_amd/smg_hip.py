@@ -36,7 +36,7 @@ class SmgAdam(C.Structure):
                 ("step_trunk", C.c_int), ("step_head", C.c_int)]
 
 
-ABI_VERSION = 5     # SMG_ABI_VERSION of include/smg_hip.h this binding was written against
+ABI_VERSION = 6     # SMG_ABI_VERSION of include/smg_hip.h this binding was written against
 
 _lib = None
 
@@ -77,6 +77,7 @@ def lib():
     L.smg_forward.argtypes = [C.c_void_p, C.POINTER(SmgNet), C.c_int, C.c_int, C.POINTER(SmgBatch), C.c_void_p, C.c_void_p]
     L.smg_loss.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smg_loss_map_ce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_backward.argtypes = [C.c_void_p, C.POINTER(SmgNet), C.c_void_p, C.c_void_p]
     if hasattr(L, "smg_backward_phase"):          # (absent from the dev builds tools/ab_kernels.sh compares against)
         L.smg_backward_phase.argtypes = [C.c_void_p, C.POINTER(SmgNet), C.c_void_p, C.c_void_p, C.c_int]
@@ -106,7 +107,7 @@ EXPORTS = (
     "smg_last_error", "smg_version", "smg_abi_struct_bytes", "smg_engine_set_option", "smg_layout_count", "smg_layout_param_floats", "smg_layout_buffer_floats",
     "smg_layout_nbt_count", "smg_layout_entry", "smg_layout_trunk_range", "smg_layout_head_range",
     "smg_engine_create", "smg_engine_destroy", "smg_engine_workspace_bytes", "smg_engine_geometry",
-    "smg_forward", "smg_loss", "smg_loss_map", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
+    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
     "smg_profile_enable", "smg_profile_kinds", "smg_profile_kind_name", "smg_profile_read", "smg_profile_read_bytes",
 )
 
@@ -246,6 +247,11 @@ class Engine(object):
         """smg_loss_map: the weighted whole-map Huber of a one-channel head; `weight_maps` None = all ones.  Marks the saved
         forward so that its backward runs the dense head form."""
         check(lib().smg_loss_map(self.h, q, label_maps, weight_maps, n_pairs, loss_out, dq_out, stream))
+
+    def loss_map_ce(self, q, label_maps, n_pairs, loss_out, dq_out, stream):
+        """smg_loss_map_ce: the whole-map cross entropy of a 3-class head, `label_maps` float32 class indices (0 / 1, anything else =
+        class 2 = unlabelled).  Marks the saved forward so that its backward runs the dense head form."""
+        check(lib().smg_loss_map_ce(self.h, q, label_maps, n_pairs, loss_out, dq_out, stream))
 
     def backward(self, net, dq, stream, phase=None):
         """phase None: the whole backward; 0 / 1: its two halves (smg_backward_phase)."""

@@ -522,6 +522,91 @@ class Trainer(object):
         weight_maps[k, pix[:, 0], pix[:, 1]] = 1.0
         return self.train_batch_maps(depth_heightmap, m_depth_heightmap, style, rotations, label_maps, weight_maps, grad_sync, return_q)
 
+    # ---- dense class maps (reactive method on heightmaps larger than 224^2: three logits per 20x20 window of the feature plane) ---
+    def _require_reactive(self, what):
+        if self.method != 'reactive':
+            raise ValueError("%s: reactive method only (three class logits per pixel; the reinforcement head's maps are "
+                             "forward_dense / train_batch_maps)" % what)
+
+    def forward_class_maps(self, depth_heightmap, m_depth_heightmap, style=0, specific_rotation=-1, logits=False, return_device=False):
+        """The reactive Trainer.forward(..., is_volatile=True) without the one-pixel restriction: the class probabilities of every
+        evaluated rotation, float64 [R, 3, OH, OW] (softmax over axis 1 on the device, as forward's; `logits` = the raw head
+        output instead) - or the float32 device tensor of that shape if asked.  Rotation choice and BN bookkeeping are forward's;
+        a 224^2 heightmap gives [R, 3, 1, 1] whose element [0, 0, 0, 0] is forward's P(success).  Reactive method only."""
+        self._require_reactive("forward_class_maps")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            q = self._evaluate(self.model, depth_heightmap, m_depth_heightmap, style, True, specific_rotation)
+        self._last_q = q
+        p = q if logits else torch.softmax(q, dim=1)
+        return p if return_device else p.cpu().numpy().astype(np.float64)
+
+    def best_class_map_action(self, depth_heightmap, m_depth_heightmap, style=0):
+        """The (rotation, pixel) of the sweep with the largest P(class 0), found on the device (smg_argmax over the flattened
+        [R, OH, OW]: lowest index on ties like np.argmax); the host reads back one (index, value) pair.
+        Returns {"rotation", "pixel": (oy, ox), "conf"}."""
+        p = self.forward_class_maps(depth_heightmap, m_depth_heightmap, style, return_device=True)
+        p0 = p[:, 0].contiguous()
+        dev = p0.device
+        idx = torch.empty(1, dtype=torch.int32, device=dev)
+        val = torch.empty(1, dtype=torch.float32, device=dev)
+        smg_hip.argmax(p0.data_ptr(), p0.numel(), idx.data_ptr(), val.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        i = int(idx.cpu().numpy()[0])
+        _, OH, OW = p0.shape
+        return {"rotation": i // (OH * OW), "pixel": ((i // OW) % OH, i % OW), "conf": float(val.cpu().numpy().astype(np.float64)[0])}
+
+    def train_batch_class_maps(self, depth_heightmap, m_depth_heightmap, style, rotations, label_maps, grad_sync=None, return_q=False):
+        """train_batch with a whole map of class labels per sample - the reference's own criterion (CrossEntropyLoss2d,
+        code/utils.py:306-313, class weights {1, 1, 0}) on the whole head output: the loss of sample j is the mean over its
+        labelled pixels (classes 0 / 1) of the cross entropy, class 2 masks a pixel ("no loss", code/trainer.py:38-60); a map
+        without a labelled pixel gives loss 0 and no gradient (smg_loss_map_ce).  The gradient of the SUM of the losses goes back
+        in one backward pass, then ONE Adam step.  Scenes, rotations, host or device inputs and `grad_sync` as in
+        train_batch_maps; `label_maps` is [n_samples, OH, OW] (dense_map_size), scene-major; host arrays are checked for values
+        outside {0, 1, 2}, device tensors are not read back.  Reactive method only.
+        Returns the loss vector (and the logits q [n_samples, 3, OH, OW] if asked)."""
+        self._require_reactive("train_batch_class_maps")
+        per_scene = np.ndim(depth_heightmap) == 3
+        n = sum(len(r) for r in rotations) if per_scene else len(rotations)
+        side = self.dense_map_size(np.shape(depth_heightmap)[-1])
+        if tuple(label_maps.shape if torch.is_tensor(label_maps) else np.shape(label_maps)) != (n, side, side):
+            raise ValueError("label_maps must be [%d samples, %d, %d] for a %d^2 heightmap, got %s"
+                             % (n, side, side, np.shape(depth_heightmap)[-1], tuple(np.shape(label_maps))))
+        lab_h = None
+        if not torch.is_tensor(label_maps):
+            lab_h = np.ascontiguousarray(label_maps, dtype=np.float32)
+            if not np.isin(lab_h, (0.0, 1.0, 2.0)).all():      # (torch's nll_loss raises on a class index outside [0, 3), as in train_batch)
+                raise ValueError("label maps must hold class indices 0, 1 or 2")
+        model = self.model
+        self.optimizer.zero_grad()
+        model._require_gpu()
+        dev = model._flat_params.device
+        hm, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
+        rots = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
+        # (uploaded BEFORE the forward is enqueued, like train_batch's labels)
+        lab = label_maps.to(device=dev, dtype=torch.float32).contiguous() if lab_h is None else torch.as_tensor(lab_h, device=dev)
+        q = model.run(style, rots, model.gnum_rotations, heightmaps=hm, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
+        eng, token, trunk_id, head_id = model._saved
+        assert tuple(q.shape) == (n, 3, side, side), (tuple(q.shape), n, side)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        dq = torch.empty_like(q)
+        eng.loss_map_ce(q.data_ptr(), lab.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
+        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
+        return (loss, q) if return_q else loss
+
+    def train_batch_class_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, grad_sync=None, return_q=False):
+        """train_batch_class_maps with ONE labelled pixel per sample: `pixels` holds an (oy, ox) per sample, `labels` its class -
+        a label map of class 2 ("no loss") everywhere else.  On a 224^2 heightmap pixel (0, 0) is the element train_batch trains."""
+        lab = np.asarray(labels, dtype=np.float32).reshape(-1)
+        pix = np.asarray(pixels, dtype=np.int64).reshape(-1, 2)
+        side = self.dense_map_size(np.shape(depth_heightmap)[-1])
+        if len(pix) != len(lab):
+            raise ValueError("one (oy, ox) and one label per sample")
+        if len(pix) and (pix.min() < 0 or pix.max() >= side):
+            raise ValueError("pixels must lie inside the %d x %d class map" % (side, side))
+        label_maps = np.full((len(lab), side, side), 2.0, dtype=np.float32)
+        label_maps[np.arange(len(lab)), pix[:, 0], pix[:, 1]] = lab
+        return self.train_batch_class_maps(depth_heightmap, m_depth_heightmap, style, rotations, label_maps, grad_sync, return_q)
+
     # The single-sample step of Trainer.backprop as ONE replayed hipGraph (smg_train_step_graph): ~560 launches of 2-20 us each are
     # enqueued by one hipGraphLaunch instead of one by one (same results, bit for bit at zero learning rate).  It saves a little host time
     # (1.8 ms per step instead of 2.3) and costs latency: the graph's ~560 dependent nodes execute no faster than the same launches from

@@ -6,8 +6,11 @@ Config-5 geometry: a 640^2 heightmap (S = 1824, 38 x 38 Q maps over 57^2 feature
 weight maps.  Each repeat runs forward + smg_loss_map untimed, then times ONLY the smg_backward call between two events on the
 launch stream; the forms alternate inside one process, after a warm-up of each.  Prints one line per repeat and a JSON summary:
 median / min / max per form, the baseline's repeat-to-repeat spread and the ratio of the medians.
+--classes 3: the same protocol on the 3-class head of a reactive trainer - label maps of classes 0 / 1 on every pixel, the dq of
+smg_loss_map_ce.
 
     python tools/head_bwd_forms.py [--repeats 7] [--warmup 2] > profiles/head_bwd_forms.txt
+    python tools/head_bwd_forms.py --classes 3 > profiles/head_bwd_forms_3class.txt
 """
 import argparse
 import json
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=640, help="heightmap side (640 -> S = 1824)")
     ap.add_argument("--rotations", type=int, default=4)
+    ap.add_argument("--classes", type=int, default=1, choices=(1, 3), help="1: reinforcement head + smg_loss_map; 3: reactive head + smg_loss_map_ce")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("head_bwd_forms: no GPU visible (a timing needs the MI355X)")
@@ -36,8 +40,8 @@ def main():
     from oracle import affordance as orc
     from trainer import Trainer
 
-    tr = Trainer('reinforcement', 0.5, False, None, False)
-    sd = synthetic.make_state_dict(orc.state_layout(1), 0)
+    tr = Trainer('reinforcement' if args.classes == 1 else 'reactive', 0.5, False, None, False)
+    sd = synthetic.make_state_dict(orc.state_layout(args.classes), 0)
     tr.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
     model = tr.model
     model.gnum_rotations = model.snum_rotations = 32
@@ -47,6 +51,8 @@ def main():
     dev = model._flat_params.device
     lab = torch.as_tensor(synthetic.uniform(5, "ab/lab", n * side * side, -1.5, 2.5).astype(np.float32), device=dev)
     wgt = torch.as_tensor(synthetic.uniform(5, "ab/w", n * side * side, 0.05, 1.0).astype(np.float32), device=dev)
+    if args.classes == 3:      # every pixel labelled 0 or 1
+        lab = torch.as_tensor(np.floor(synthetic.uniform(5, "ab/cls", n * side * side, 0.0, 2.0)).astype(np.float32), device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     loss = torch.empty(n, dtype=torch.float32, device=dev)
     head = "graspnet_val.grasp-val-conv1.weight"
@@ -57,7 +63,10 @@ def main():
         eng = model._saved[0]
         eng.set_option("head_bwd", form)
         dq = torch.empty_like(q)
-        eng.loss_map(q.data_ptr(), lab.data_ptr(), wgt.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
+        if args.classes == 1:
+            eng.loss_map(q.data_ptr(), lab.data_ptr(), wgt.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
+        else:
+            eng.loss_map_ce(q.data_ptr(), lab.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
         model.flat_grads().zero_()
         net = model._net_struct(True)
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -70,7 +79,8 @@ def main():
         off, cnt = next((o, int(np.prod(s))) for nm, k, o, s in model._layout if nm == head and k == 0)
         return t0.elapsed_time(t1), model.flat_grads()[off:off + cnt].clone()
 
-    print("# %d^2 heightmap, %d rotations (%d streams), %d x %d maps, full weight maps; the backward call only, ms" % (args.size, n, n + 1, side, side))
+    print("# %d^2 heightmap, %d rotations (%d streams), %d x %d maps, %s; the backward call only, ms"
+          % (args.size, n, n + 1, side, side, "full weight maps" if args.classes == 1 else "3 classes, every pixel labelled 0 / 1"))
     times, grads = {1: [], 2: []}, {}
     for _ in range(args.warmup):
         for form in (1, 2):
@@ -85,7 +95,7 @@ def main():
     med = {f: float(np.median(times[f])) for f in times}
     d = float((grads[1].double() - grads[2].double()).norm() / grads[1].double().norm())
     print(json.dumps({
-        "tool": "head_bwd_forms", "input_size": eng.S, "samples": n, "streams": n + 1, "map": [side, side], "repeats": args.repeats,
+        "tool": "head_bwd_forms", **({} if args.classes == 1 else {"classes": args.classes}), "input_size": eng.S, "samples": n, "streams": n + 1, "map": [side, side], "repeats": args.repeats,
         "per_element_ms": {"median": med[1], "min": min(times[1]), "max": max(times[1])},
         "dense_ms": {"median": med[2], "min": min(times[2]), "max": max(times[2])},
         "baseline_spread_ms": max(times[1]) - min(times[1]),
