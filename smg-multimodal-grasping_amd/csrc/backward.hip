@@ -4,20 +4,6 @@
 // ------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------
-// Pixel-chunk size of a weight-gradient launch: enough workgroups to fill the chip
-// (~768) but no more - every workgroup ends with one fp32 atomicAdd per output element.
-// Chunks are sized over the plane's VALID rows: every chunk starts inside [0, HW), so every workgroup of the launch stores its
-// partial tile (a chunk that starts in the plane's padding rows - up to 127 of them since make_plane pads the big planes to 128
-// rows - would leave without storing, and reduce_partials_kernel would add whatever the workspace held there).  The last chunk
-// may run into the padding (the kernels clamp its length to HWp; padding rows hold zero gradients).
-static void pick_chunk(const Plane& pl, int n_planes, int tiles_per_chunk, int& chunk, int& cps, int target = 768) {
-    const int want = (target + tiles_per_chunk - 1) / tiles_per_chunk;
-    cps = (want + n_planes - 1) / n_planes;
-    if (cps < 1) cps = 1;
-    chunk = ((pl.HW + cps - 1) / cps + 63) / 64 * 64;
-    cps = (pl.HW + chunk - 1) / chunk;
-}
-
 // phases: bit 0 = the head and dense blocks 4, 3, 2 (down to the gradient of block 1's buffer), bit 1 = dense block 1, pool0 and
 // the stem.  Between the two halves every gradient of [transition1 .. norm5] and of the head is final on `st`: a data-parallel
 // caller starts their all-reduce there and hides it under the second half (smg_backward_phase).
@@ -77,6 +63,9 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                                        K_OTHER, 0, ESZ(e) * NS * pl.HW * 3 * kGrowth, false, a));
     };
 
+    // the partial-tile workspace of this call and its pending reductions (wgrad_plan.h has the rules)
+    PartialTiles tiles(e->part_floats, NS, e->deterministic);
+
     if (ph_a) {
     {   // value conv backward + relu1 + norm1 sums
         ValueBwdArgs a;
@@ -118,8 +107,9 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         p.eps = kEps; p.chunk = chunk4; p.chunks_per_stream = cps4; p.n_chunks = NP * cps4;
         p.dw = Gr + Hd.c0.w; p.ldw_out = 2 * kFeat;
         if (fork(e->ev_misc)) return -5;
-        return launch_wgrad(e, s2, p, dim3(1, 2 * kFeat / 64, NP * cps4), K_HW0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid,
-                            4.0 * NP * p4.HW * (2 * kHeadMid + 2 * kFeat), 1, C_IDENT);
+        const dim3 grid(1, 2 * kFeat / 64, NP * cps4);
+        return launch_wgrad(e, s2, p, grid, K_HW0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid,
+                            4.0 * NP * p4.HW * (2 * kHeadMid + 2 * kFeat), 1, C_IDENT, tiles, tiles.place_alone(wgrad_partial_floats(p, grid)));
         };
         PREC_DISPATCH(e, if (int rc = go(PTAG)) return rc);
     }
@@ -164,68 +154,50 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         const int r = ring_pos(b, i);
         return LayerBuf{e->GS[r % kRing], e->D2[r % kRing], e->D2S[r % kRing], r};
     };
-    // The two weight gradients of dense layer (b, i) and their shared reduce, on the side stream (which must already wait for the
+    // The form that applies the BN backward while loading the G' / X slices of dense layer d's 32 output channels
+    auto fused_gsrc = [&](int b, const DenseLayerRef& d) {
+        const int Ct = kBlockCtot[b];
+        GradSrc g{};
+        g.g = el(e, e->G[b], d.cin); g.ldg = Ct; g.x = el(e, e->X[b], d.cin); g.ldx = Ct;
+        g.xsum = fsum(e, e->st_X[b]) + d.cin; g.xsq = fsq(e, e->st_X[b]) + d.cin;
+        g.s1 = b1(e, e->st_X[b]) + d.cin; g.s2 = b2(e, e->st_X[b]) + d.cin; g.sstride = Ct; g.eps = kEps;
+        return g;
+    };
+    // The two weight gradients of dense layer (b, i) and their reduce launches, on the side stream (which must already wait for the
     // layer's D2 / GS).
-    // Few-stream calls without "deterministic" (the 1x1 weight gradient adds with atomics, only the 3x3 one leaves partial tiles): the
-    // reduce of layer l waits for layer l - 1's and ONE launch serves both - the partial tiles alternate between the two halves of the
-    // workspace.  (The side stream is the longer one in a single-sample step: 29 reduce launches of ~7.5 us less on it.)
-    ReduceArgs pend3{}; pend3.Z = 0;
-    int pend3_half = 0;
-    auto flush_pending_reduce = [&]() { if (pend3.Z) { launch_reduce2(e, s2, pend3, ReduceArgs{}); pend3.Z = 0; } };
     auto issue_wgrads = [&](int b, int i) -> int {
         const Plane pl = e->p_blk[b];
         const int Ct = kBlockCtot[b];
         const DenseLayerRef& d = T.layers[b][i];
         float* bt = el(e, e->Bt, e->bt_off[b][i]);
         const LayerBuf lb = buf_of(b, i);
+        const WgradPlan w = plan_layer_wgrads(pl, d.cin, NS, e->prec, split16, e->deterministic, e->part_floats, e->generic3x3, e->generic_w1);
         GradSrc gsrc{};
         if (gs_on_side(pl)) launch_gs_apply(b, i, s2, lb.GS);
         if (gs_materialised) { gsrc.g = lb.GS; gsrc.ldg = kGrowth; gsrc.amax = gamax_of(e, b, i, 0); }
-        else {
-            gsrc.g = el(e, e->G[b], d.cin); gsrc.ldg = Ct; gsrc.x = el(e, e->X[b], d.cin); gsrc.ldx = Ct;
-            gsrc.xsum = fsum(e, e->st_X[b]) + d.cin; gsrc.xsq = fsq(e, e->st_X[b]) + d.cin;
-            gsrc.s1 = b1(e, e->st_X[b]) + d.cin; gsrc.s2 = b2(e, e->st_X[b]) + d.cin; gsrc.sstride = Ct; gsrc.eps = kEps;
-        }
-        ReduceArgs red3{}; red3.Z = 0;            // the 3x3 weight gradient's reduction, launched together with the 1x1 one below
-        int64_t part3_floats = 0;                 // ... and the partial-tile floats it occupies
+        else gsrc = fused_gsrc(b, d);
         if (!e->generic3x3) {
             // conv2 weight gradient with the activation halo resident in LDS (halo.cuh)
-            const int ts = halo_tile(pl, NS);
+            const PartialTiles::Slot at = tiles.place_halo3x3(w.w3.groups);
+            if (at.refused) return fail(-12, tiles.refusal());
+            launch_reduce2(e, s2, at.first);
             Halo3x3WgradArgs a;
             a.g = gsrc; a.pl = pl; a.src = bt; a.C = kBottleneck;
-            const int th = 8;                              // tiles are ts x 8 pixels
             a.bt = bn_table(e, e->sb_tab[b][i], e->max_streams, 0, kBottleneck, P + d.n2.w, P + d.n2.b);
             a.asc = asc_n2(e, b, i);
-            a.tiles_x = (pl.W + ts - 1) / ts; a.n_tiles = ((pl.H + th - 1) / th) * a.tiles_x;
-            a.tiles_per_wg = w3_tiles_per_wg(a.n_tiles, ts, NS, e->part_floats, (double)ts / th);
-            const int groups = (a.n_tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
-            if ((int64_t)groups * NS * 9 * 32 * kBottleneck > e->part_floats) return fail(-12, "partial-gradient workspace too small");
-            const bool pair_reduce = !e->deterministic && NS <= 4 && (int64_t)groups * NS * 9 * 32 * kBottleneck * 2 <= e->part_floats;
-            if (!pair_reduce) flush_pending_reduce();
-            float* part3 = e->part + (pair_reduce && pend3_half ? e->part_floats / 2 : 0);
-            a.part = part3;
-            a.groups = groups; a.streams = NS;
-            const unsigned w3_grid = (unsigned)(((groups * NS + 7) / 8) * 8 * (kBottleneck / 32));      // (see the kernel: channel groups of a tile group share an XCD)
+            a.tiles_x = w.w3.tiles_x; a.n_tiles = w.w3.n_tiles; a.tiles_per_wg = w.w3.tiles_per_wg;
+            a.part = part_at(e, at);
+            a.groups = w.w3.groups; a.streams = NS;
             const double flops = 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth, bytes = ESZ(e) * NS * pl.HW * (kGrowth + kBottleneck);
-            if (ts == 16) {
-                PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_wgrad_kernel<16, PREC>, dim3(w3_grid), dim3(256), HaloWgradSGeo<16, PREC>::smem_bytes(), s2,
+            if (w.w3.ts == 16) {
+                PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_wgrad_kernel<16, PREC>, dim3(w.w3_grid), dim3(256), HaloWgradSGeo<16, PREC>::smem_bytes(), s2,
                                                K_W3, flops, bytes, false, a));
             } else {
-                PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_wgrad_kernel<8, PREC>, dim3(w3_grid), dim3(256), HaloWgradSGeo<8, PREC>::smem_bytes(), s2,
+                PREC_DISPATCH(e, launch_kernel(e, conv3x3_halo_wgrad_kernel<8, PREC>, dim3(w.w3_grid), dim3(256), HaloWgradSGeo<8, PREC>::smem_bytes(), s2,
                                                K_W3, flops, bytes, false, a));
             }
-            red3.part = part3; red3.Z = groups * NS; red3.taps = 9; red3.rows = kGrowth; red3.cols = kBottleneck; red3.ldp = kBottleneck;
-            red3.z_stride = (int64_t)9 * kGrowth * kBottleneck; red3.tap_stride = (int64_t)kGrowth * kBottleneck;
-            red3.dw = Gr + d.c2.w; red3.ldw_out = kBottleneck * 9; red3.cmap = C_3x3;
-            part3_floats = (int64_t)groups * NS * 9 * kGrowth * kBottleneck;
-            if (pair_reduce) {       // this layer's reduce rides with the next layer's (or the final flush)
-                if (pend3.Z) { launch_reduce2(e, s2, pend3, red3); pend3.Z = 0; }
-                else pend3 = red3;
-                pend3_half ^= 1;
-                red3.Z = 0; part3_floats = 0;
-            }
+            launch_reduce2(e, s2, tiles.launched(at, reduce_tap_inner(a.part, w.w3.groups * NS, Gr + d.c2.w)));
         } else {   // conv2 weight gradient (generic implicit GEMM, one launch slice per tap)
-            flush_pending_reduce();
             int chunk, cps;
             pick_chunk(pl, NS, 9, chunk, cps);      // (9 workgroups per chunk: one per tap)
             BwdWeightP<CfgW32x128, W_THREE, C_3x3, kPdWgrad, false> p{};
@@ -235,69 +207,42 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             p.bgamma = P + d.n2.w; p.bbeta = P + d.n2.b; p.eps = kEps;
             p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
             p.dw = Gr + d.c2.w; p.ldw_out = kBottleneck * 9;
-            if (int rc = launch_wgrad(e, s2, p, dim3(1, 1, 9 * NS * cps), K_W3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth,
-                                      ESZ(e) * NS * pl.HW * (kGrowth + kBottleneck), 9, C_3x3)) return rc;
+            const dim3 grid(1, 1, 9 * NS * cps);
+            if (int rc = launch_wgrad(e, s2, p, grid, K_W3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth,
+                                      ESZ(e) * NS * pl.HW * (kGrowth + kBottleneck), 9, C_3x3, tiles, tiles.place_alone(wgrad_partial_floats(p, grid)))) return rc;
         }
-        // conv1 weight gradient, wave-specialised (wsw.cuh): 128 x 128 tiles, 32-pixel k-tiles, loader + matrix waves - for the partial-tile
-        // form (more than four streams, or "deterministic") on layers of more than 64 input channels (a half-empty 128-column tile
-        // costs block 1's first layer 77 -> 107 us; few-stream calls keep the generic kernel's 128 x 64 atomics: 7.3 -> 7.5 ms per single-sample step)
-        if (split16 && !e->generic_w1 && d.cin > 64 && (e->deterministic || NS > 4)) {
+        if (w.w1_ws) {   // conv1 weight gradient, wave-specialised (wsw.cuh)
             using G = WswGeo;
-            const int nt = (d.cin + G::BN - 1) / G::BN;
-            int chunk, cps;
-            pick_chunk(pl, NS, nt, chunk, cps, 320);      // (256 / 512 / 768 workgroups: 16.45-16.62 / 16.64-16.67 / 16.73-16.82 ms per step against 16.47-16.53)
+            static_assert(G::BN == kW1WsTileN, "plan_layer_wgrads counts this kernel's column tiles");
             Wgrad1x1WsArgs a{};
             a.d2 = reinterpret_cast<const u32x4*>(lb.D2); a.binv = lb.D2S; a.x = e->X[b]; a.ldb = Ct; a.pl = pl; a.NB = d.cin;
             a.btab = stat_table(e, e->sx_tab[b], e->max_streams, Ct); a.bgamma = P + d.n1.w; a.bbeta = P + d.n1.b; a.basc = asc_n1(e, b, i);
-            a.chunk = chunk; a.chunks_per_stream = cps; a.n_chunks = NS * cps;
-            a.dw = Gr + d.c1.w; a.ldw_out = d.cin; a.ldp = nt * G::BN;
-            const bool w1_part = e->deterministic || NS > 4;
-            const int64_t need = (int64_t)a.n_chunks * G::BM * a.ldp;
-            int64_t off1 = part3_floats;
-            if (red3.Z && (!w1_part || off1 + need > e->part_floats)) { launch_reduce2(e, s2, red3, ReduceArgs{}); red3.Z = 0; off1 = 0; }
-            a.part = (w1_part && off1 + need <= e->part_floats) ? e->part + off1 : nullptr;
-            if (w1_part && !a.part && e->deterministic)
-                return fail(-12, "deterministic: a weight-gradient launch needs " + std::to_string(need) + " partial-tile floats, the workspace holds " + std::to_string(e->part_floats - off1));
-            a.tm = TileMap{a.n_chunks, nt, 0};
-            launch_kernel(e, conv1x1_wgrad_ws_kernel, dim3(tile_grid(a.tm)), dim3(512), G::smem_bytes(chunk), s2, K_W1,
+            a.chunk = w.chunk; a.chunks_per_stream = w.cps; a.n_chunks = NS * w.cps;
+            a.dw = Gr + d.c1.w; a.ldw_out = d.cin; a.ldp = w.nt * G::BN;
+            const PartialTiles::Slot at = tiles.place_behind3x3((int64_t)a.n_chunks * G::BM * a.ldp);
+            launch_reduce2(e, s2, at.first);
+            if (at.refused) return fail(-12, tiles.refusal());
+            a.part = part_at(e, at);
+            a.tm = TileMap{a.n_chunks, w.nt, 0};
+            launch_kernel(e, conv1x1_wgrad_ws_kernel, dim3(tile_grid(a.tm)), dim3(512), G::smem_bytes(w.chunk), s2, K_W1,
                           2.0 * NS * pl.HW * d.cin * kBottleneck, 4.0 * NS * pl.HW * (kBottleneck + d.cin), false, a);
-            ReduceArgs red1{}; red1.Z = 0;
-            if (a.part) {
-                red1.part = a.part; red1.Z = a.n_chunks; red1.taps = 1; red1.rows = G::BM; red1.cols = d.cin; red1.ldp = a.ldp;
-                red1.z_stride = (int64_t)G::BM * a.ldp; red1.tap_stride = (int64_t)a.n_chunks * G::BM * a.ldp;
-                red1.dw = a.dw; red1.ldw_out = d.cin; red1.cmap = C_IDENT;
-            }
-            launch_reduce2(e, s2, red3, red1);
-        } else {   // conv1 weight gradient.  ~320 workgroups: it shares the chip with the data-gradient chain on the other stream
-            // (256..384 measure the same, 512 / 768 / 1024 cost the step 0.15 / 0.35 / 0.75 ms)
+            ReduceArgs red1{};
+            if (a.part) red1 = reduce_chunk_major(a.part, a.n_chunks, 1, G::BM, d.cin, G::BM, a.ldp, a.dw, d.cin, C_IDENT);
+            launch_reduce2(e, s2, tiles.launched(at, red1));
+        } else {   // conv1 weight gradient, generic
             using Cfg = CfgW128x64;
-            const int nt = (d.cin + Cfg::BN - 1) / Cfg::BN;
-            int chunk, cps;
-            // 16-bit storage: the k-loop is a third as long, the 128 x 64 atomics per workgroup are not - half as many workgroups
-            // on many-stream batches (config 3: 28.9 -> 28.5 ms at 160; 120 / 80: 28.6 / 28.8; S = 1824 with 5 streams: 320 stays)
-            // few-stream calls on the atomics form: 128 (every workgroup adds a 128 x 64 tile with fp32 atomics; single-sample step 5.9 -> 5.65 ms;
-            // 64 / 192 / 320: 6.0 / 5.7 / 5.9)
-            pick_chunk(pl, NS, nt, chunk, cps, (e->prec && NS >= 16) ? 160 : (NS <= 4 && !e->deterministic) ? 128 : 320);
+            static_assert(Cfg::BN == kW1TileN, "plan_layer_wgrads counts this kernel's column tiles");
             auto go = [&](auto ptag) -> int {
                 BwdWeightP<MC<Cfg, decltype(ptag)::value>, W_ONE, C_IDENT, kPdWgrad, false, decltype(ptag)::value> p{};
                 p.gbuf = lb.D2; p.ldg = kBottleneck; p.gcoff = 0; p.xbuf = nullptr; p.pa = pl; p.MA = kBottleneck; p.binv = lb.D2S; p.basc = asc_n1(e, b, i);
                 p.bbuf = e->X[b]; p.ldb = Ct; p.pb = pl; p.NB = d.cin;
                 p.bsum = fsum(e, e->st_X[b]); p.bsq = fsq(e, e->st_X[b]); p.bstride = Ct; p.btab = stat_table(e, e->sx_tab[b], e->max_streams, Ct);
                 p.bgamma = P + d.n1.w; p.bbeta = P + d.n1.b; p.eps = kEps;
-                p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
+                p.chunk = w.chunk; p.chunks_per_stream = w.cps; p.n_chunks = NS * w.cps;
                 p.dw = Gr + d.c1.w; p.ldw_out = d.cin;
-                // partial tiles + the fixed-order reduce (reproducible; since reduce_partials splits the partials over four waves it
-                // beats 128 x 64 fp32 atomics per workgroup); a few streams: host-launch-bound, atomics save the reduce launches
-                const bool w1_part = e->deterministic || NS > 4;
-                // both reductions of the layer in ONE launch: the 1x1 partial tiles go behind the 3x3 ones (if they fit; else the 3x3
-                // reduction runs first and the workspace is reused)
-                ReduceArgs red1{}; red1.Z = 0;
-                int64_t off1 = part3_floats;
-                if (red3.Z && (!w1_part || off1 + (int64_t)NS * cps * Cfg::BM * nt * Cfg::BN > e->part_floats)) { launch_reduce2(e, s2, red3, ReduceArgs{}); red3.Z = 0; off1 = 0; }
-                if (int rc = launch_wgrad(e, s2, p, dim3(1, nt, NS * cps), K_W1, 2.0 * NS * pl.HW * d.cin * kBottleneck,
-                                          ESZ(e) * NS * pl.HW * (kBottleneck + d.cin), 1, C_IDENT, w1_part, off1, &red1)) return rc;
-                launch_reduce2(e, s2, red3, red1);
-                return 0;
+                const dim3 grid(1, w.nt, NS * w.cps);
+                return launch_wgrad(e, s2, p, grid, K_W1, 2.0 * NS * pl.HW * d.cin * kBottleneck,
+                                    ESZ(e) * NS * pl.HW * (kBottleneck + d.cin), 1, C_IDENT, tiles, tiles.place_behind3x3(wgrad_partial_floats(p, grid)));
             };
             PREC_DISPATCH(e, if (int rc = go(PTAG)) return rc);
         }
@@ -305,7 +250,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
     };
     // debug_stop (engine.h): leave the backward here - both streams joined, the forward's state consumed
     auto debug_stop = [&]() -> int {
-        flush_pending_reduce();
+        launch_reduce2(e, s2, tiles.drain());
         HIP_OK(hipEventRecord(e->ev_end, s2));
         HIP_OK(hipStreamWaitEvent(st, e->ev_end, 0));
         if (int rc = walk_status(e)) return rc;
@@ -331,10 +276,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             // [px][32]) for the 3x3 data- and weight-gradient kernels.  They can also apply it while loading the G' / X
             // slices (GradSrc with x set): one launch less on the dependency chain, but measured 0.5 ms per step slower on
             // many-stream batches - two strided 128-B-per-pixel reads replace one dense one in both consumers.
-            GradSrc gsrc{};
-            gsrc.g = el(e, e->G[b], d.cin); gsrc.ldg = Ct; gsrc.x = el(e, e->X[b], d.cin); gsrc.ldx = Ct;
-            gsrc.xsum = fsum(e, e->st_X[b]) + d.cin; gsrc.xsq = fsq(e, e->st_X[b]) + d.cin;
-            gsrc.s1 = b1(e, e->st_X[b]) + d.cin; gsrc.s2 = b2(e, e->st_X[b]) + d.cin; gsrc.sstride = Ct; gsrc.eps = kEps;
+            GradSrc gsrc = fused_gsrc(b, d);
             if (e->generic3x3 || (gs_materialised && !gs_on_side(pl))) {
                 launch_gs_apply(b, i, st, GSb);
                 if (gs_materialised) { gsrc = GradSrc{}; gsrc.g = GSb; gsrc.ldg = kGrowth; gsrc.amax = gamax_of(e, b, i, 0); }
@@ -482,9 +424,9 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
                 p.dw = Gr + T.tconv[b - 1].w; p.ldw_out = Cp;
                 if (fork(e->ev_misc)) return -5;
-                flush_pending_reduce();      // (the partial-tile workspace is about to be reused from its start)
-                return launch_wgrad(e, s2, p, dim3(C0 / 128, Cp / 128, NS * cps), K_TW, 2.0 * NS * pl.HW * Cp * C0,
-                                    ESZ(e) * NS * (2.0 * pl.HW * C0 + (double)pp.HW * Cp), 1, C_IDENT);
+                const dim3 grid(C0 / 128, Cp / 128, NS * cps);
+                return launch_wgrad(e, s2, p, grid, K_TW, 2.0 * NS * pl.HW * Cp * C0,
+                                    ESZ(e) * NS * (2.0 * pl.HW * C0 + (double)pp.HW * Cp), 1, C_IDENT, tiles, tiles.place_alone(wgrad_partial_floats(p, grid)));
                 };
                 PREC_DISPATCH(e, if (int rc = go(PTAG)) return rc);
             }
@@ -545,9 +487,10 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         p.eps = kEps; p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
         p.dw = Gr + T.conv0.w; p.ldw_out = 147;
         if (fork(e->ev_misc)) return -5;
-        flush_pending_reduce();      // (the partial-tile workspace is about to be reused from its start)
-        return launch_wgrad(e, s2, p, dim3(1, 1, NS * cps), K_SW, 2.0 * NS * ps_.HW * 64 * 147,
-                            4.0 * NS * (2.0 * ps_.HW * 64 + (double)e->p_img.HW * (SM == W_STEM1 ? 1 : 4)), 1, SM == W_STEM1 ? C_STEM1 : C_STEM);
+        const dim3 grid(1, 1, NS * cps);
+        return launch_wgrad(e, s2, p, grid, K_SW, 2.0 * NS * ps_.HW * 64 * 147,
+                            4.0 * NS * (2.0 * ps_.HW * 64 + (double)e->p_img.HW * (SM == W_STEM1 ? 1 : 4)), 1, SM == W_STEM1 ? C_STEM1 : C_STEM,
+                            tiles, tiles.place_alone(wgrad_partial_floats(p, grid)));
         };
         if (e->f_stem1) { PREC_DISPATCH(e, if (int rc = go(PTAG, std::integral_constant<int, W_STEM1>{})) return rc); }
         else { PREC_DISPATCH(e, if (int rc = go(PTAG, std::integral_constant<int, W_STEM>{})) return rc); }
@@ -565,7 +508,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                       e->dbscr, e->db_total, kDbRep, Gr,
                       ph_b ? b1(e, e->st_stem) : nullptr, ph_b ? b2(e, e->st_stem) : nullptr, NS, Gr + T.norm0.b, Gr + T.norm0.w);
     }
-    flush_pending_reduce();
+    launch_reduce2(e, s2, tiles.drain());
     HIP_OK(hipEventRecord(e->ev_end, s2));          // join: everything after the backward (or this half of it) sees every gradient
     HIP_OK(hipStreamWaitEvent(st, e->ev_end, 0));
     if (int rc = walk_status(e)) return rc;

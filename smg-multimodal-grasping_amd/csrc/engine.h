@@ -175,37 +175,6 @@ struct smg_engine {
     int launch_rc = 0;         // error code of the first launch launch_kernel refused since the last walk_status (smg_last_error() says why)
 };
 
-// Tile side of the LDS-halo 3x3 kernels for a plane: 16 where it tiles exactly, else 8 (ragged edges masked) - and 8
-// as well when the launch would have fewer than 320 16x16 tiles (few streams per call; 80x80 planes of a 9-stream
-// forward chain): four times the workgroups fill the chip (forward sweep 9.05 -> 8.77 ms, single-rotation forward
-// 4.3 -> 3.6 ms).
-static inline int halo_tile(const Plane& p, int n_streams = 1 << 20) {
-    // (tiles that hang over the edge are masked: S = 1824's 456^2 / 228^2 / 114^2 planes take 16 x 16 tiles too - round 5)
-    return (int64_t)((p.H + 15) / 16) * ((p.W + 15) / 16) * n_streams >= 200 ? 16 : 8;      // (round 5, 320 -> 200: a single-sample step's 160^2 planes and the 80^2 planes of
-                                                                                            //  an 8-stream forward chain take 16 x 16 tiles - step 5.71 -> 5.63 ms, headline 16.0 both ways; 100: the 17-stream
-                                                                                            //  40^2 planes would too, 16.05)
-}
-
-// 3x3 weight-gradient halo kernel: tiles per workgroup.  The launch runs in rounds of 512 resident workgroups (2 per
-// CU), each lasting tiles_per_wg tile-times plus a fixed prologue + 9-tap flush (~0.6 of a 16x16 tile-time, measured);
-// take the run length with the shortest total (e.g. 100 tiles x 17 streams -> 7, 25 tiles -> 4), then lengthen it
-// until the partial tiles fit the workspace.
-static int w3_tiles_per_wg(int n_tiles, int ts, int n_streams, int64_t part_floats, double fix_scale = 1.0) {
-    const double fix = (ts == 16 ? 0.6 : 2.4) * fix_scale;
-    double best = 1e30;
-    int tpw_best = 1;
-    for (int tpw = 1; tpw <= n_tiles; ++tpw) {
-        const int g = (n_tiles + tpw - 1) / tpw;
-        const int rounds = (g * (kBottleneck / 32) * n_streams + 511) / 512;
-        const double cost = rounds * (tpw + fix);
-        if (cost < best - 1e-9) { best = cost; tpw_best = tpw; }
-    }
-    // (taking the LONGEST run length within 4-40 % of the shortest total - fewer partial tiles for the reduce to read back - measured
-    //  17.3-17.4 against 17.27 ms per step: the partial-tile traffic is not what the side stream waits for)
-    while (tpw_best < n_tiles && (int64_t)((n_tiles + tpw_best - 1) / tpw_best) * n_streams * 9 * 32 * kBottleneck > part_floats) ++tpw_best;
-    return tpw_best;
-}
-
 static Plane make_plane(int H, int W) {
     // rows per stream: a multiple of 64 (tiles and scale blocks never straddle two streams) - of 128 on the big planes, so that the
     // 128-row tile configurations serve them whatever the input size (S = 1824: 456^2 = 207 936 = 64 x 3249 pixels took 64-row tiles)
@@ -362,40 +331,37 @@ static void launch_gemm(smg_engine* e, hipStream_t st, P p, dim3 grid, int kind,
     launch_kernel(e, gemm_kernel<P>, dim3((unsigned)(grid.x * grid.y * grid.z)), dim3(256), smem, st, kind, flops, bytes, true, p, (int)grid.x, (int)grid.y);
 }
 
-// Weight-gradient launch: partial tiles to the workspace + one reduce kernel (falls back to
-// atomics if the workspace is too small for this launch).
-// part_off: first float of the partial-tile workspace this launch may use (a dense layer's two weight gradients keep their partial
-// tiles side by side and share ONE reduce launch: `defer` receives this launch's reduction instead of it being launched here).
-template <class P>
-static int launch_wgrad(smg_engine* e, hipStream_t st, P& p, dim3 grid, int kind, double flops, double bytes, int taps, int cmap, bool use_part = true,
-                        int64_t part_off = 0, ReduceArgs* defer = nullptr) {
-    using C = typename P::Cfg;
-    const int64_t ldp = (int64_t)grid.y * C::BN, rowsp = (int64_t)grid.x * C::BM;
-    const int64_t need = (int64_t)grid.z * rowsp * ldp;
-    p.part = (use_part && part_off + need <= e->part_floats) ? e->part + part_off : nullptr;
-    if (use_part && !p.part && e->deterministic)      // never a silent loss of the bit-reproducibility the option promises
-        return fail(-12, "deterministic: a weight-gradient launch needs " + std::to_string(need) + " partial-tile floats, the workspace holds " +
-                             std::to_string(e->part_floats - part_off) + " (smaller batch per call, or a larger engine)");
-    launch_gemm(e, st, p, grid, kind, flops, bytes);
-    if (defer) defer->Z = 0;
-    if (p.part) {
-        ReduceArgs r;
-        r.part = p.part; r.Z = p.n_chunks; r.taps = taps; r.rows = p.MA; r.cols = p.NB; r.ldp = (int)ldp;
-        r.z_stride = rowsp * ldp; r.tap_stride = (int64_t)p.n_chunks * rowsp * ldp;
-        r.dw = p.dw; r.ldw_out = p.ldw_out; r.cmap = cmap;
-        if (defer) { *defer = r; return 0; }
-        const int total = taps * p.MA * p.NB;
-        // (the reduce is profiled with the element-wise kernels: a class's launches are its GEMM kernels only)
-        launch_kernel(e, reduce_partials_kernel, dim3((total + 63) / 64), dim3(256), 0, st, K_OTHER, 0, 0, false, r, ReduceArgs{}, (total + 63) / 64);
-    }
-    return 0;
-}
-// ONE launch for two pending reductions (either may be empty: Z == 0)
-static void launch_reduce2(smg_engine* e, hipStream_t st, const ReduceArgs& ra, const ReduceArgs& rb) {
-    const int ba = ra.Z ? (ra.taps * ra.rows * ra.cols + 63) / 64 : 0, bb = rb.Z ? (rb.taps * rb.rows * rb.cols + 63) / 64 : 0;
+// ONE launch for two pending reductions (either may be empty: Z == 0) - the one place that launches reduce_partials_kernel
+static void launch_reduce2(smg_engine* e, hipStream_t st, const ReducePair& r) {
+    const int ba = ReducePair::blocks(r.a), bb = ReducePair::blocks(r.b);
     if (ba + bb == 0) return;
-    // (one launch serves the layer's 3x3 AND 1x1 partial tiles: profiled with the element-wise kernels)
-    launch_kernel(e, reduce_partials_kernel, dim3(ba + bb), dim3(256), 0, st, K_OTHER, 0, 0, false, ra, rb, ba);
+    // (one launch serves the layer's 3x3 AND 1x1 partial tiles: profiled with the element-wise kernels - a class's launches are its
+    // GEMM kernels only)
+    launch_kernel(e, reduce_partials_kernel, dim3(ba + bb), dim3(256), 0, st, K_OTHER, 0, 0, false, r.a, r.b, ba);
+}
+
+// Floats of the partial tiles an implicit-GEMM weight-gradient launch of `grid` leaves (x, y: tiles; z: pixel chunks x taps)
+template <class P>
+static int64_t wgrad_partial_floats(const P&, dim3 grid) {
+    return (int64_t)grid.z * (grid.x * P::Cfg::BM) * ((int64_t)grid.y * P::Cfg::BN);
+}
+// the partial tiles of a launch placed at `at` (nullptr: it adds with fp32 atomics)
+static inline float* part_at(const smg_engine* e, const PartialTiles::Slot& at) { return at.off >= 0 ? e->part + at.off : nullptr; }
+// Weight-gradient launch: partial tiles at the slot the workspace's owner gave it (or fp32 atomics), then the reduce launch the
+// owner says is due once it has this launch's reduction.
+template <class P>
+static int launch_wgrad(smg_engine* e, hipStream_t st, P& p, dim3 grid, int kind, double flops, double bytes, int taps, int cmap,
+                        PartialTiles& tiles, const PartialTiles::Slot& at) {
+    using C = typename P::Cfg;
+    launch_reduce2(e, st, at.first);
+    if (at.refused)      // never a silent loss of the bit-reproducibility the option promises
+        return fail(-12, tiles.refusal() + " (smaller batch per call, or a larger engine)");
+    p.part = part_at(e, at);
+    launch_gemm(e, st, p, grid, kind, flops, bytes);
+    ReduceArgs r{};
+    if (p.part) r = reduce_chunk_major(p.part, p.n_chunks, taps, p.MA, p.NB, (int64_t)grid.x * C::BM, (int64_t)grid.y * C::BN, p.dw, p.ldw_out, cmap);
+    launch_reduce2(e, st, tiles.launched(at, r));
+    return 0;
 }
 
 // element `elems` of a mode-typed buffer (X, Bt, G, GS, D2): 4-byte elements in mode 0, 2-byte elements in modes 1 / 2

@@ -58,12 +58,8 @@ static int engine_build(smg_engine* e) {
     e->part_floats = (int64_t)24 << 20;   // partial weight-gradient tiles: 96 MB, or what the 3x3 launches of a full batch want
     for (int b = 0; b < 4; ++b) {
         const Plane& pl = e->p_blk[b];
-        for (int ts : {halo_tile(pl), 8}) {
-            const int th = 8;                                    // weight-gradient tiles are ts x 8 pixels
-            const int nt = ((pl.H + th - 1) / th) * ((pl.W + ts - 1) / ts);
-            const int tpw = w3_tiles_per_wg(nt, ts, NS, INT64_MAX, (double)ts / th);
-            e->part_floats = std::max<int64_t>(e->part_floats, (int64_t)((nt + tpw - 1) / tpw) * NS * 9 * 32 * kBottleneck);
-        }
+        for (int ts : {halo_tile(pl), 8})
+            e->part_floats = std::max(e->part_floats, w3_partial_floats(w3_tiling(pl, ts, NS, INT64_MAX).groups, NS));
     }
     ALLOC(e->part, e->part_floats);
     ALLOC(e->F, (int64_t)NP * e->p_blk[3].HWp * 2 * kFeat);

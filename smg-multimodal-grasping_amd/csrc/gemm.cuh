@@ -51,6 +51,8 @@
 
 #include <type_traits>
 
+#include "wgrad_plan.h"      // Plane, ReduceArgs and the weight gradients' column maps (host-only header)
+
 // k-tiles of global loads in flight per policy family (register ring depth of the staging pipeline) and the waves per SIMD a few
 // kernels are held to - every value below was A/B-measured on the box (profiles/README.md) and is frozen here.
 namespace smg {
@@ -81,8 +83,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // one 16-byte unit (HIP's uint4 struct keeps register arrays in scratch)
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-struct Plane { int H, W, HW, HWp; };
 
 // ------------------------------------------------------------------------------------
 // Split precision.
@@ -2331,7 +2331,6 @@ struct BwdDataGroupP {
 //   [cout][cin][kh][kw] layout (C_IDENT / C_3x3 / C_STEM index maps).
 // ------------------------------------------------------------------------------------
 enum { W_ONE = 0, W_THREE = 1, W_POOL = 2, W_STEM = 3, W_STEM1 = 4 };      // W_STEM1: one-channel image plane, 49 taps (see F_STEM1)
-enum { C_IDENT = 0, C_3x3 = 1, C_STEM = 2, C_STEM1 = 3 };                  // C_STEM1: column = tap, written to all three input channels
 
 // PREC: the engine's precision mode; F32IO: every buffer is fp32 whatever the mode (head conv0; the stem's image / plane).
 template <class Cfg_, int BMODE, int CMAP, int PD_ = kPdWgrad, bool AFF = true, int PREC = 0, bool F32IO_ = false>
@@ -2668,13 +2667,7 @@ struct BwdWeightP {
     }
 };
 
-// Sum the partial weight-gradient tiles of one launch over its pixel chunks and add the
-// result into the gradient array (reference layout).  Deterministic, no atomics.
-//   value(tap, row, col) = sum_z part[tap*tap_stride + z*z_stride + row*ldp + col]
-struct ReduceArgs {
-    const float* part; int Z, taps, rows, cols, ldp; int64_t z_stride, tap_stride;
-    float* dw; int ldw_out, cmap;
-};
+// reduce_partials_kernel sums the partial weight-gradient tiles of a launch as its ReduceArgs (wgrad_plan.h) describe them.
 // A workgroup sums 64 elements: its four waves take every fourth partial tile each (coalesced 256-byte reads, four loads in
 // flight per lane) and meet in LDS - a fixed order, so the result is reproducible.  (One thread per element over all Z partials
 // was a serial chain of Z / 4 memory round trips on a grid of 144 workgroups: 10-12 us per launch, 189 launches per step.)

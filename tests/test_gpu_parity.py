@@ -1994,3 +1994,50 @@ def test_weight_gradient_chunks_never_start_in_the_plane_padding(gpu, size, rots
         assert rel <= 3e-2, (n, rel)
     print("S=%d, %d streams, deterministic: dense block 1's 1x1 and the transitions' weight gradients vs the sum of single-rotation calls: worst relative error %.2e"
           % (S, len(rots) + 1, worst))
+
+
+@pytest.mark.parametrize("rots", [[5], [1, 6, 10]])
+def test_few_stream_paired_3x3_reduces_read_no_stale_partial_tiles(gpu, rots):
+    """Calls of at most four streams without "deterministic" pair the 3x3 weight-gradient reduce of dense layer l with layer l - 1's:
+    one reduce launch serves both, and the partial tiles alternate between the two halves of the workspace (PartialTiles,
+    csrc/wgrad_plan.h).  A reduce that read the wrong half, or a half rewritten before its reduction was launched, would add another
+    layer's or another call's tiles.  Detector (that of test_weight_gradient_chunks_never_start_in_the_plane_padding, on the path that
+    test does not reach): the 58 conv2 weight gradients of a 2-stream and of a 4-stream call must be bit-identical before and after
+    an unrelated call whose gradients are 1000x larger.  They must also equal, bit for bit, those of the same call under
+    "deterministic", where the 3x3 tiles sit at offset 0 and their reduce shares a launch with the 1x1's: the same values summed in
+    the same order."""
+    from trainer import Trainer
+    import synthetic
+    tr = Trainer('reinforcement', 0.5, False, None, False)
+    sd = synthetic.make_state_dict(orc.state_layout(1), 7)
+    tr.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    tr.model.gnum_rotations = tr.model.snum_rotations = 16
+    tr.optimizer.lr = 0.0
+    depth, masks = synthetic.heightmap_scene(11)
+    depth_b, masks_b = synthetic.heightmap_scene(12)
+    assert depth.shape == (224, 224)            # S = 640: the smallest input the head's 20x20 convolution admits
+    with torch.no_grad():
+        q = tr.model.run(0, [rots], 16, heightmaps=torch.from_numpy(np.stack([depth, depth * masks[0]])).cuda(), mean=tr.image_mean, std=tr.image_std)
+    q0 = q.reshape(len(rots), -1)[:, 0].double().cpu().numpy()
+    labels_small = (q0 - 1e-3).tolist()          # |d| = 1e-3: dL/dq = d
+    labels_big = [float(v) + 50.0 for v in q0]   # |d| >= 1: dL/dq = -1, a thousand times the above
+    conv2 = [(n, p) for n, p in tr.model.named_parameters() if n.startswith("grasp_depth_trunk") and n.endswith(".conv2.weight")]
+    assert len(conv2) == 58
+
+    def run(d, m, labels):
+        tr.train_batch(d, m, 0, rots, labels)
+        return {n: p.grad.clone() for n, p in conv2}
+    g_a = run(depth, depth * masks[0], labels_small)
+    run(depth_b, depth_b * masks_b[2], labels_big)
+    g_c = run(depth, depth * masks[0], labels_small)
+    assert all(float(g.abs().max()) > 0 for g in g_a.values())
+    differing = [n for n in g_a if not torch.equal(g_a[n], g_c[n])]
+    assert not differing, differing[:5]
+    eng = engine_of(tr.model)
+    try:
+        eng.set_option("deterministic", 1)
+        g_d = run(depth, depth * masks[0], labels_small)
+    finally:
+        eng.set_option("deterministic", 0)
+    differing = [n for n in g_a if not torch.equal(g_a[n], g_d[n])]
+    assert not differing, differing[:5]
