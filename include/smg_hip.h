@@ -42,7 +42,7 @@ typedef struct smg_engine smg_engine;
 const char* smg_last_error(void);
 /* ABI revision of this header: a binding must refuse a library whose smg_version() differs (stale .so) and should
  * compare its own struct sizes with smg_abi_struct_bytes(0 = smg_batch, 1 = smg_net, 2 = smg_adam) before the first call. */
-#define SMG_ABI_VERSION 6
+#define SMG_ABI_VERSION 7
 int smg_version(void);
 int smg_abi_struct_bytes(int which);
 
@@ -168,6 +168,53 @@ int smg_loss_map(smg_engine* e, const float* q_dev, const float* label_dev, cons
 int smg_loss_map_ce(smg_engine* e, const float* q_dev, const float* label_dev, int n_pairs,
                     float* loss_dev, float* dq_dev, void* stream);
 
+/* ---- dense Q maps in the scene frame ----------------------------------------------------------------------------------------
+ * A dense Q map lives in the ROTATED frame of its rotation, one value per 32 input pixels.  These three entry points undo
+ * F.affine_grid / F.grid_sample (code/models.py:372-382) and the head's 20x20 window geometry, so that a caller can read, pick and
+ * train Q values at HEIGHTMAP pixels.  For a heightmap of side hm (code/trainer.py:165-173): pad = int((ceil(2 hm sqrt(2) / 32) * 32
+ * - 2 hm) / 2), S = 2 hm + 2 pad (the engine's input size), OH = OW = S / 32 - 19 (the engine's).  Coordinates are (x = column,
+ * y = row); all arithmetic is double:
+ *   1. heightmap pixel (iy, ix) is the centre of its 2x2 replicated block of the padded input: x = 2 ix + 0.5 + pad, y likewise;
+ *   2. normalised as align_corners=True does: u = 2 (x, y) / (S - 1) - 1;
+ *   3. the forward computed rotated[p] = image[A p], A = the 2x2 part of the sample's theta (the six float32 numbers the forward
+ *      used, widened to double): the scene point u is seen in that rotation at p = A^T u (the transpose, not a recomputed inverse);
+ *   4. back to pixels: (px, py) = (p + 1) / 2 * (S - 1);
+ *   5. map element (oy, ox) is the head's window over input pixels 32 ox .. 32 ox + 639, centre 32 ox + 319.5:
+ *      qx = (px - 319.5) / 32, qy = (py - 319.5) / 32;
+ *   6. the pixel is VALID in that rotation when 0 <= qx <= OW - 1 and 0 <= qy <= OH - 1; its value is the bilinear interpolation of
+ *      the map at (qy, qx) - x0 = min(floor(qx), OW - 2), fx = qx - x0, the same in y,
+ *      (1 - fy) ((1 - fx) Q[y0][x0] + fx Q[y0][x0 + 1]) + fy ((1 - fx) Q[y0 + 1][x0] + fx Q[y0 + 1][x0 + 1]) - rounded to float32 once;
+ *   7. an invalid pixel has the value -inf: no window of the head is centred there.
+ * affine_host: 6 float32 per map / pair, row-major 2x3 as in smg_batch.stream_affine; the translation column must be zero.
+ * map_stride: element distance between consecutive maps in q_dev - OH * OW for the output of a one-channel head, 3 * OH * OW to
+ * address one class plane of a [R][3][OH][OW] tensor.
+ * All three return -22 and launch nothing when hm_size does not pad to the engine's S, when the map is 1 x 1 (S = 640: no extent
+ * to interpolate over), and for n_maps < 1 / K < 1. */
+
+/* out_dev float32 [n_maps][hm_size][hm_size]: every map in the scene frame, -inf at invalid pixels. */
+int smg_scene_maps(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host,
+                   int hm_size, float* out_dev, void* stream);
+
+/* The largest valid value of those scene-frame maps and its flattened index into [n_maps][hm_size][hm_size], without writing the
+ * maps: idx_out_dev int32[1], val_out_dev float32[1].  The rules are smg_argmax's (lowest index on ties, a NaN wins) with invalid
+ * pixels skipped; the result is bit-reproducible (per-workgroup partials in a scratch the engine owns, reduced by a second launch;
+ * no atomics) and equals smg_argmax over smg_scene_maps' output.  Index -1, value -inf when no pixel is valid. */
+int smg_scene_argmax(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host,
+                     int hm_size, int* idx_out_dev, float* val_out_dev, void* stream);
+
+/* Huber loss on K labelled heightmap pixels per pair, one-channel heads only (head_out != 1 returns -22): q and dq are
+ * [n_pairs][1][OH][OW]; pixels_dev int32 [n_pairs][K][2] = (iy, ix); label_dev, weight_dev float32 [n_pairs][K] (weight_dev NULL =
+ * all ones, a weight of exactly 0 masks its point).  With v_k the interpolated value of point k in its pair's rotation (double,
+ * not rounded) and the Huber of code/trainer.py:345-348:
+ *     loss[j] = sum_k w_k huber(v_k - label_k)
+ *     dq[j][oy][ox] = sum_k w_k huber'(v_k - label_k) * (bilinear weight of (oy, ox) at point k)
+ * accumulated in double in point order and rounded once; every element of dq is written, duplicate points add up, no atomics
+ * (bit-identical between identical calls).  A point that is invalid in its pair's rotation contributes nothing (a caller refuses
+ * it first).  Marks the saved forward "dense dq" exactly as smg_loss_map does. */
+int smg_loss_scene(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs, int K,
+                   const int* pixels_dev, const float* label_dev, const float* weight_dev,
+                   float* loss_dev, float* dq_dev, void* stream);
+
 /* Backward of the last smg_forward: accumulates (+=) d(sum of losses)/d(param) into
  * net->grads for the trunk and head that forward used.  Replaces loss.backward() at
  * code/trainer.py:350-351. */
@@ -210,7 +257,7 @@ int smg_engine_set_precision(smg_engine* e, int precision);
  * output elements it feeds, skips zero dq and adds its share of the 20x20 weight gradient with fp32 atomics; right for the single
  * element smg_loss mode 0 sets.  2: the dense form - a data pass over the 400 taps and a weight pass that owns every element of
  * the weight gradient (no atomics, pairs in index order: bit-identical between identical calls); right for a whole map.
- * 0 (default): the dense form after smg_loss_map / smg_loss_map_ce, else the per-element form.  A 3-class head follows the same
+ * 0 (default): the dense form after smg_loss_map / smg_loss_map_ce / smg_loss_scene, else the per-element form.  A 3-class head follows the same
  * rule as a one-channel head (its dense form loops over the three output channels).  smg_train_step_graph always runs the
  * per-element form (its loss is smg_loss).
  * "serialize" (0 / 1): every kernel on the caller's stream in issue order instead of two concurrent chains (profiling).

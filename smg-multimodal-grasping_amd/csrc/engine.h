@@ -14,6 +14,7 @@
 
 #include "../../include/smg_hip.h"
 #include "elem.cuh"
+#include "scene.cuh"
 #include "gemm.cuh"
 #include "halo.cuh"
 #include "ws.cuh"
@@ -144,6 +145,8 @@ struct smg_engine {
     int* d_stream_image = nullptr; int* d_stream_rot = nullptr; int* d_pair_a = nullptr; int* d_pair_b = nullptr;
     int* d_seq_t = nullptr; int* d_seq_h = nullptr; int* d_user_ptr = nullptr; int* d_user_pair = nullptr; int* d_user_slot = nullptr;
     float* d_affine = nullptr;
+    // smg_scene_argmax: one (value, index) partial per workgroup of a launch (kSceneMaps maps x scene_tiles tiles of the largest heightmap this S serves)
+    float* scene_val = nullptr; int* scene_idx = nullptr; int scene_tiles = 0;
     // batch description staging: one pinned ping-pong host block -> one device block per forward
     int* d_stage = nullptr; int* h_stage[2] = {}; hipEvent_t ev_stage[2] = {}; int stage_ints = 0, stage_turn = 0;
     int so_image = 0, so_rot = 0, so_pa = 0, so_pb = 0, so_seq_t = 0, so_seq_h = 0, so_uptr = 0, so_upair = 0, so_uslot = 0, so_aff = 0, so_ma = 0, so_mb = 0, so_adam = 0;

@@ -52,6 +52,9 @@ static int engine_build(smg_engine* e) {
         HIP_OK(hipEventCreateWithFlags(&e->ev_side[k], hipEventDisableTiming));
     }
     ALLOC(e->DY2, (int64_t)NS * e->p_blk[0].HWp * kBottleneck);
+    e->scene_tiles = (int)(((int64_t)(S / 2) * (S / 2) + kSceneTile - 1) / kSceneTile);      // (a heightmap of side hm pads to S >= 2 hm)
+    ALLOC(e->scene_val, (int64_t)kSceneMaps * e->scene_tiles);
+    ALLOC(e->scene_idx, (int64_t)kSceneMaps * e->scene_tiles);
     HIP_OK(hipEventCreateWithFlags(&e->ev_misc, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&e->ev_end, hipEventDisableTiming));
     HIP_OK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
@@ -387,7 +390,7 @@ void smg_engine_destroy(smg_engine* e) {
     (void)hipDeviceSynchronize();
     void* ptrs[] = {e->img4, e->stem, e->DY0, e->argmax, e->X[0], e->X[1], e->X[2], e->X[3], e->G[0], e->G[1], e->G[2], e->G[3],
                     e->Bt, e->DY2, e->part, e->F, e->DF, e->H1, e->DH1, e->fstat, e->bstat, e->dbscr, e->d_dbseg, e->asc, e->d_asc, e->gamax, e->packed_u, e->packed_f, e->stab, e->d_pack, e->d_bnupd,
-                    e->d_stage};
+                    e->d_stage, e->scene_val, e->scene_idx};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->dbg_gsnap) (void)hipFree(e->dbg_gsnap);
     step_graph_drop(e);
@@ -461,6 +464,102 @@ int smg_loss_map_ce(smg_engine* e, const float* q_dev, const float* label_dev, i
     hipLaunchKernelGGL(loss_map_ce_kernel, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, q_dev, label_dev, e->OH * e->OW, loss_dev, dq_dev);
     HIP_OK(hipGetLastError());
     e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0)
+    return 0;
+}
+
+// ---- scene-frame Q maps (scene.cuh) -------------------------------------------------
+// The geometry of a hm_size^2 heightmap on this engine, or -22: the padding of code/trainer.py:165-173 must give the engine's S, and
+// the map must have an extent to interpolate over.
+static int scene_geometry(const smg_engine* e, int hm_size, const char* who, SceneGeo* g) {
+    if (hm_size < 1 || hm_size > e->S / 2) return fail(-22, std::string(who) + ": hm_size does not pad to the engine's input size");
+    const double diag = std::ceil((double)(2 * hm_size) * std::sqrt(2.0) / 32.0) * 32.0;
+    const int pad = (int)((diag - (double)(2 * hm_size)) / 2.0);
+    if (2 * hm_size + 2 * pad != e->S) return fail(-22, std::string(who) + ": hm_size does not pad to the engine's input size");
+    if (e->OH < 2 || e->OW < 2) return fail(-22, std::string(who) + ": a 1 x 1 Q map (S = 640) has no extent to interpolate over");
+    if ((size_t)e->OH * e->OW * (sizeof(float) + sizeof(double)) > 48 * 1024) return fail(-22, std::string(who) + ": the Q map does not fit the kernels' LDS staging");
+    g->hm = hm_size; g->pad = pad; g->S = e->S; g->OH = e->OH; g->OW = e->OW; g->inv_sm1 = 1.0 / (double)(e->S - 1);
+    return 0;
+}
+// the translation column of every matrix must be zero (models.rotation_theta's is): the chain is p = A^T u
+static int scene_affines_ok(const float* affine_host, int n, const char* who) {
+    for (int m = 0; m < n; ++m)
+        if (affine_host[6 * (int64_t)m + 2] != 0.f || affine_host[6 * (int64_t)m + 5] != 0.f)
+            return fail(-22, std::string(who) + ": the affine matrices must be rotations about the centre (zero translation column)");
+    return 0;
+}
+// the 2x2 parts of maps [m0, m0 + n) as kernel arguments
+static SceneAffine scene_affine(const float* affine_host, int m0, int n) {
+    SceneAffine a;
+    memset(&a, 0, sizeof(a));
+    for (int m = 0; m < n; ++m) {
+        const float* th = affine_host + 6 * (int64_t)(m0 + m);
+        a.a[m][0] = th[0]; a.a[m][1] = th[1]; a.a[m][2] = th[3]; a.a[m][3] = th[4];
+    }
+    return a;
+}
+
+int smg_scene_maps(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
+                   float* out_dev, void* stream) {
+    if (!e || !q_dev || !affine_host || !out_dev) return fail(-22, "NULL argument");
+    if (n_maps < 1 || map_stride < 0) return fail(-22, "smg_scene_maps: n_maps < 1 or a negative map_stride");
+    SceneGeo g;
+    if (int rc = scene_geometry(e, hm_size, "smg_scene_maps", &g)) return rc;
+    if (int rc = scene_affines_ok(affine_host, n_maps, "smg_scene_maps")) return rc;
+    HIP_OK(hipSetDevice(e->device));
+    const int64_t npix = (int64_t)hm_size * hm_size;
+    const int vec4 = npix % 4 == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 15) == 0;
+    const int tiles = (int)((npix + kSceneTile - 1) / kSceneTile);
+    for (int m0 = 0; m0 < n_maps; m0 += kSceneMaps) {
+        const int n = std::min(kSceneMaps, n_maps - m0);
+        const SceneAffine a = scene_affine(affine_host, m0, n);
+        hipLaunchKernelGGL(scene_map_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
+                           q_dev, map_stride, m0, a, g, out_dev, vec4);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smg_scene_argmax(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
+                     int* idx_out_dev, float* val_out_dev, void* stream) {
+    if (!e || !q_dev || !affine_host || !idx_out_dev || !val_out_dev) return fail(-22, "NULL argument");
+    if (n_maps < 1 || map_stride < 0) return fail(-22, "smg_scene_argmax: n_maps < 1 or a negative map_stride");
+    SceneGeo g;
+    if (int rc = scene_geometry(e, hm_size, "smg_scene_argmax", &g)) return rc;
+    const int64_t npix = (int64_t)hm_size * hm_size;
+    if ((int64_t)n_maps * npix > 0x7fffffff) return fail(-22, "smg_scene_argmax: the flattened index does not fit int32");
+    if (int rc = scene_affines_ok(affine_host, n_maps, "smg_scene_argmax")) return rc;
+    HIP_OK(hipSetDevice(e->device));
+    const int tiles = (int)((npix + kSceneTile - 1) / kSceneTile);      // <= e->scene_tiles: hm_size <= S / 2
+    for (int m0 = 0; m0 < n_maps; m0 += kSceneMaps) {      // (groups follow each other on the stream: the partials are reused)
+        const int n = std::min(kSceneMaps, n_maps - m0);
+        const SceneAffine a = scene_affine(affine_host, m0, n);
+        hipLaunchKernelGGL(scene_argmax_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
+                           q_dev, map_stride, m0, a, g, e->scene_val, e->scene_idx);
+        hipLaunchKernelGGL(scene_argmax_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
+                           (const int*)e->scene_idx, tiles * n, m0 > 0 ? 1 : 0, idx_out_dev, val_out_dev);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smg_loss_scene(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs, int K, const int* pixels_dev,
+                   const float* label_dev, const float* weight_dev, float* loss_dev, float* dq_dev, void* stream) {
+    if (!e || !q_dev || !affine_host || !pixels_dev || !label_dev || !loss_dev || !dq_dev) return fail(-22, "NULL argument");
+    if (e->head_out != 1) return fail(-22, "smg_loss_scene: the scene-pixel Huber needs a one-channel head (head_out == 1)");
+    if (n_pairs < 1 || n_pairs > e->max_pairs) return fail(-22, "n_pairs exceeds the engine's max_pairs");
+    if (K < 1) return fail(-22, "smg_loss_scene: K < 1");
+    SceneGeo g;
+    if (int rc = scene_geometry(e, hm_size, "smg_loss_scene", &g)) return rc;
+    if (int rc = scene_affines_ok(affine_host, n_pairs, "smg_loss_scene")) return rc;
+    HIP_OK(hipSetDevice(e->device));
+    for (int m0 = 0; m0 < n_pairs; m0 += kSceneMaps) {
+        const int n = std::min(kSceneMaps, n_pairs - m0);
+        const SceneAffine a = scene_affine(affine_host, m0, n);
+        hipLaunchKernelGGL(loss_scene_kernel, dim3(n), dim3(256), (size_t)g.OH * g.OW * (sizeof(double) + sizeof(float)), (hipStream_t)stream,
+                           q_dev, m0, a, g, K, pixels_dev, label_dev, weight_dev, loss_dev, dq_dev);
+    }
+    HIP_OK(hipGetLastError());
+    e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0), as after smg_loss_map
     return 0;
 }
 

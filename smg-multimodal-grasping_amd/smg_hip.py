@@ -36,7 +36,7 @@ class SmgAdam(C.Structure):
                 ("step_trunk", C.c_int), ("step_head", C.c_int)]
 
 
-ABI_VERSION = 6     # SMG_ABI_VERSION of include/smg_hip.h this binding was written against
+ABI_VERSION = 7     # SMG_ABI_VERSION of include/smg_hip.h this binding was written against
 
 _lib = None
 
@@ -78,6 +78,10 @@ def lib():
     L.smg_loss.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_map_ce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smg_scene_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]
+    L.smg_scene_argmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smg_loss_scene.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_backward.argtypes = [C.c_void_p, C.POINTER(SmgNet), C.c_void_p, C.c_void_p]
     if hasattr(L, "smg_backward_phase"):          # (absent from the dev builds tools/ab_kernels.sh compares against)
         L.smg_backward_phase.argtypes = [C.c_void_p, C.POINTER(SmgNet), C.c_void_p, C.c_void_p, C.c_int]
@@ -107,7 +111,7 @@ EXPORTS = (
     "smg_last_error", "smg_version", "smg_abi_struct_bytes", "smg_engine_set_option", "smg_layout_count", "smg_layout_param_floats", "smg_layout_buffer_floats",
     "smg_layout_nbt_count", "smg_layout_entry", "smg_layout_trunk_range", "smg_layout_head_range",
     "smg_engine_create", "smg_engine_destroy", "smg_engine_workspace_bytes", "smg_engine_geometry",
-    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
+    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_argmax", "smg_loss_scene", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
     "smg_profile_enable", "smg_profile_kinds", "smg_profile_kind_name", "smg_profile_read", "smg_profile_read_bytes",
 )
 
@@ -252,6 +256,30 @@ class Engine(object):
         """smg_loss_map_ce: the whole-map cross entropy of a 3-class head, `label_maps` float32 class indices (0 / 1, anything else =
         class 2 = unlabelled).  Marks the saved forward so that its backward runs the dense head form."""
         check(lib().smg_loss_map_ce(self.h, q, label_maps, n_pairs, loss_out, dq_out, stream))
+
+    @staticmethod
+    def _affines(affine, n):
+        a = np.ascontiguousarray(affine, dtype=np.float32).reshape(-1)
+        if a.size != 6 * n:
+            raise ValueError("need 6 affine numbers per map, got %d for %d maps" % (a.size, n))
+        return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+    def scene_maps(self, q, map_stride, n_maps, affine, hm_size, out, stream):
+        """smg_scene_maps: the n_maps Q maps at `q` (device, `map_stride` elements apart) rotated back by their `affine`
+        (host, 6 float32 each: models.rotation_theta) and upsampled to `out` [n_maps, hm_size, hm_size]; -inf where invalid."""
+        a, p = self._affines(affine, n_maps)
+        check(lib().smg_scene_maps(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), out, stream))
+
+    def scene_argmax(self, q, map_stride, n_maps, affine, hm_size, idx_out, val_out, stream):
+        """smg_scene_argmax: the best valid (map, iy, ix) of those scene-frame maps as a flattened index, without writing them."""
+        a, p = self._affines(affine, n_maps)
+        check(lib().smg_scene_argmax(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), idx_out, val_out, stream))
+
+    def loss_scene(self, q, affine, hm_size, n_pairs, K, pixels, labels, weights, loss_out, dq_out, stream):
+        """smg_loss_scene: the weighted Huber on K heightmap pixels (int32 [n_pairs, K, 2] = iy, ix) per pair, dq on the map;
+        `weights` None = all ones.  Marks the saved forward so that its backward runs the dense head form."""
+        a, p = self._affines(affine, n_pairs)
+        check(lib().smg_loss_scene(self.h, q, p, int(hm_size), int(n_pairs), int(K), pixels, labels, weights, loss_out, dq_out, stream))
 
     def backward(self, net, dq, stream, phase=None):
         """phase None: the whole backward; 0 / 1: its two halves (smg_backward_phase)."""

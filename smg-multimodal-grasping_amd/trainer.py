@@ -522,6 +522,159 @@ class Trainer(object):
         weight_maps[k, pix[:, 0], pix[:, 1]] = 1.0
         return self.train_batch_maps(depth_heightmap, m_depth_heightmap, style, rotations, label_maps, weight_maps, grad_sync, return_q)
 
+    # ---- dense Q maps in the scene frame: rotated back and bilinearly upsampled onto the heightmap's pixels ---------------------------
+    @staticmethod
+    def _scene_geometry(heightmap_size):
+        """(pad, S, side) of a heightmap_size^2 heightmap (code/trainer.py:165-173); ValueError where the Q map is 1 x 1."""
+        hm = int(heightmap_size)
+        pad = int((np.ceil(float(2 * hm) * np.sqrt(2) / 32) * 32 - 2 * hm) / 2)
+        S = 2 * hm + 2 * pad
+        side = S // 32 - 19
+        if side < 2:
+            raise ValueError("a %d^2 heightmap gives a %d x %d Q map: nothing to interpolate over (the scene-frame interface "
+                             "needs a heightmap larger than 224^2)" % (hm, side, side))
+        return pad, S, side
+
+    @staticmethod
+    def scene_to_map(heightmap_size, rotation, num_rotations, pixels):
+        """Where heightmap pixels lie on the dense Q map of `rotation` (of `num_rotations`): `pixels` [..., 2] = (iy, ix) ->
+        (qy, qx, valid), float64 map coordinates and whether a window of the head is centred there (0 <= q <= side - 1 on both
+        axes).  `rotation` is one index or an array that broadcasts against pixels[..., 0].  The chain of include/smg_hip.h in
+        float64 on the host: pixel -> centre of its 2x2 block of the padded input -> align_corners=True normalisation -> A^T u with
+        A the 2x2 part of models.rotation_theta (the float32 numbers the forward samples with) -> input pixels -> (p - 319.5) / 32."""
+        from models import rotation_theta
+        pad, S, side = Trainer._scene_geometry(heightmap_size)
+        pix = np.asarray(pixels)
+        if pix.shape[-1:] != (2,):
+            raise ValueError("pixels must be [..., 2] = (iy, ix)")
+        rot = np.broadcast_to(np.asarray(rotation), pix.shape[:-1])
+        A = np.zeros(pix.shape[:-1] + (4,), dtype=np.float64)
+        for r in np.unique(rot):
+            th = rotation_theta(int(r), num_rotations).astype(np.float64)
+            A[rot == r] = (th[0], th[1], th[3], th[4])
+        x = 2.0 * pix[..., 1].astype(np.float64) + 0.5 + pad
+        y = 2.0 * pix[..., 0].astype(np.float64) + 0.5 + pad
+        ux, uy = 2.0 * x / (S - 1) - 1.0, 2.0 * y / (S - 1) - 1.0
+        px = (A[..., 0] * ux + A[..., 2] * uy + 1.0) / 2.0 * (S - 1)
+        py = (A[..., 1] * ux + A[..., 3] * uy + 1.0) / 2.0 * (S - 1)
+        qx, qy = (px - 319.5) / 32.0, (py - 319.5) / 32.0
+        valid = (qx >= 0) & (qx <= side - 1) & (qy >= 0) & (qy <= side - 1)
+        return qy, qx, valid
+
+    def _require_scene(self, what, depth_heightmap):
+        if self.method != 'reinforcement':
+            raise ValueError("%s: reinforcement method only" % what)
+        return self._scene_geometry(np.shape(depth_heightmap)[-1])
+
+    def _scene_rotations(self, model, style, specific_rotation):
+        """The (rotation, num_rotations) of every row of forward_dense's result, in _evaluate's order."""
+        if specific_rotation == -1 and style == 0:
+            return [(r, model.gnum_rotations) for r in range(model.gnum_rotations)]
+        if specific_rotation == -1 and style == 1:
+            return [(r, model.snum_rotations) for r in range(model.snum_rotations)]
+        return [(0 if style == 2 else specific_rotation, model.gnum_rotations)]
+
+    def forward_scene(self, depth_heightmap, m_depth_heightmap, style=0, is_target=False, specific_rotation=-1, return_device=False):
+        """forward_dense in the SCENE frame: every evaluated rotation's Q map rotated back and bilinearly upsampled onto the
+        heightmap's pixels (smg_scene_maps), float64 [R, hm, hm] - or the float32 device tensor - with -inf where no window of
+        the head is centred in that rotation.  Element [r, iy, ix] is the Q value of acting at heightmap pixel (iy, ix) with
+        rotation r: the same scene point in every rotation.  Rotation choice and BN bookkeeping are forward's (style 2 is
+        rotation 0).  Reinforcement method, heightmaps larger than 224^2."""
+        import models
+        self._require_scene("forward_scene", depth_heightmap)
+        model = self.model_target if is_target else self.model
+        q = self.forward_dense(depth_heightmap, m_depth_heightmap, style, is_target, specific_rotation, return_device=True)
+        dev = q.device
+        R, OH, OW = q.shape
+        hm = int(np.shape(depth_heightmap)[-1])
+        aff = [models.rotation_theta(r, num) for r, num in self._scene_rotations(model, style, specific_rotation)]
+        assert len(aff) == R
+        eng = models.get_engine(dev.index or 0, self._scene_geometry(hm)[1], model.HEAD_OUT, 1, 1)
+        out = torch.empty((R, hm, hm), dtype=torch.float32, device=dev)
+        eng.scene_maps(q.data_ptr(), OH * OW, R, aff, hm, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return out if return_device else out.cpu().numpy().astype(np.float64)
+
+    def best_scene_action(self, depth_heightmap, m_depth_heightmap, style=0, is_target=False):
+        """The best (rotation, heightmap pixel) of the sweep, found on the device without materialising the scene-frame maps
+        (smg_scene_argmax: lowest index of the flattened [R, hm, hm] on ties like np.argmax, a NaN wins, pixels without a window
+        are never picked); the host reads back one (index, value) pair.
+        Returns {"rotation", "pixel": (iy, ix), "conf", "map_pixel": (qy, qx)} - `pixel` in heightmap pixels, `map_pixel` its
+        float position on that rotation's Q map (scene_to_map)."""
+        import models
+        self._require_scene("best_scene_action", depth_heightmap)
+        model = self.model_target if is_target else self.model
+        q = self.forward_dense(depth_heightmap, m_depth_heightmap, style, is_target, return_device=True)
+        dev = q.device
+        R, OH, OW = q.shape
+        hm = int(np.shape(depth_heightmap)[-1])
+        rots = self._scene_rotations(model, style, -1)
+        eng = models.get_engine(dev.index or 0, self._scene_geometry(hm)[1], model.HEAD_OUT, 1, 1)
+        idx = torch.empty(1, dtype=torch.int32, device=dev)
+        val = torch.empty(1, dtype=torch.float32, device=dev)
+        eng.scene_argmax(q.data_ptr(), OH * OW, R, [models.rotation_theta(r, num) for r, num in rots], hm, idx.data_ptr(), val.data_ptr(),
+                         torch.cuda.current_stream(dev).cuda_stream)
+        i = int(idx.cpu().numpy()[0])
+        row, iy, ix = i // (hm * hm), (i // hm) % hm, i % hm
+        qy, qx, _ = self.scene_to_map(hm, rots[row][0], rots[row][1], (iy, ix))
+        return {"rotation": rots[row][0], "pixel": (iy, ix), "conf": float(val.cpu().numpy().astype(np.float64)[0]),
+                "map_pixel": (float(qy), float(qx))}
+
+    def train_batch_scene_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, weights=None, grad_sync=None,
+                                 return_q=False):
+        """train_batch_maps with the labels at HEIGHTMAP pixels: sample j trains K scene pixels - `pixels` [n_samples, K, 2] =
+        (iy, ix) ([n_samples, 2] for K = 1), `labels` / `weights` [n_samples, K] (weights None = all ones) - through the bilinear
+        interpolation of its Q map at those points: loss_j = sum_k w * Huber(v_k - label_k) (smg_loss_scene), whose gradient
+        spreads over the four map elements around each point.  A pixel without a window of the head in its sample's rotation
+        (scene_to_map's `valid`) raises ValueError before anything runs.  The gradient of the SUM of the losses goes back in one
+        backward pass (dense head form), then ONE Adam step.  Scenes, rotations and `grad_sync` as in train_batch_maps; host
+        arrays.  Reinforcement method only.  Returns the loss vector (and q [n_samples, 1, OH, OW] if asked)."""
+        import models
+        _, _, side = self._require_scene("train_batch_scene_pixels", depth_heightmap)
+        per_scene = np.ndim(depth_heightmap) == 3
+        flat_rots = [r for rs in rotations for r in rs] if per_scene else list(rotations)
+        n = len(flat_rots)
+        hm = int(np.shape(depth_heightmap)[-1])
+        pix = np.asarray(pixels)
+        if pix.ndim == 2:
+            pix = pix[:, None, :]
+        if pix.ndim != 3 or pix.shape[0] != n or pix.shape[1] < 1 or pix.shape[2] != 2:
+            raise ValueError("pixels must be [%d samples, K, 2] = (iy, ix), got %s" % (n, np.shape(pixels)))
+        K = pix.shape[1]
+        lab = np.asarray(labels, dtype=np.float32)
+        wgt = None if weights is None else np.asarray(weights, dtype=np.float32)
+        for name, a in (("labels", lab), ("weights", wgt)):
+            if a is not None and a.shape != (n, K) and not (K == 1 and a.shape == (n,)):
+                raise ValueError("%s must be [%d samples, %d], got %s" % (name, n, K, a.shape))
+        pix_i = pix.astype(np.int64)
+        if not np.array_equal(pix_i, pix) or pix_i.min() < 0 or pix_i.max() >= hm:
+            raise ValueError("pixels must be integer (iy, ix) inside the %d x %d heightmap" % (hm, hm))
+        num = self.model.gnum_rotations
+        rots = [0 if style == 2 else int(r) for r in flat_rots]
+        _, _, valid = self.scene_to_map(hm, np.asarray(rots).reshape(n, 1), num, pix_i)
+        if not valid.all():
+            j, k = np.argwhere(~valid)[0]
+            raise ValueError("pixel %s of sample %d has no Q window in rotation %d of %d (scene_to_map)" % (tuple(pix_i[j, k]), j, rots[j], num))
+        model = self.model
+        self.optimizer.zero_grad()
+        model._require_gpu()
+        dev = model._flat_params.device
+        hmaps, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
+        rots2 = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
+        # (uploaded BEFORE the forward is enqueued, like train_batch's labels)
+        pix_d = torch.as_tensor(np.ascontiguousarray(pix_i, dtype=np.int32), device=dev)
+        lab_d = torch.as_tensor(np.ascontiguousarray(lab.reshape(n, K)), device=dev)
+        wgt_d = None if wgt is None else torch.as_tensor(np.ascontiguousarray(wgt.reshape(n, K)), device=dev)
+        q = model.run(style, rots2, num, heightmaps=hmaps, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
+        eng, token, trunk_id, head_id = model._saved
+        assert tuple(q.shape) == (n, 1, side, side), (tuple(q.shape), n, side)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        dq = torch.empty_like(q)
+        eng.loss_scene(q.data_ptr(), [models.rotation_theta(r, num) for r in rots], hm, n, K, pix_d.data_ptr(), lab_d.data_ptr(),
+                       None if wgt_d is None else wgt_d.data_ptr(), loss.data_ptr(), dq.data_ptr(), stream)
+        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
+        return (loss, q) if return_q else loss
+
     # ---- dense class maps (reactive method on heightmaps larger than 224^2: three logits per 20x20 window of the feature plane) ---
     def _require_reactive(self, what):
         if self.method != 'reactive':
