@@ -42,7 +42,7 @@ typedef struct smg_engine smg_engine;
 const char* smg_last_error(void);
 /* ABI revision of this header: a binding must refuse a library whose smg_version() differs (stale .so) and should
  * compare its own struct sizes with smg_abi_struct_bytes(0 = smg_batch, 1 = smg_net, 2 = smg_adam) before the first call. */
-#define SMG_ABI_VERSION 7
+#define SMG_ABI_VERSION 8
 int smg_version(void);
 int smg_abi_struct_bytes(int which);
 
@@ -215,6 +215,44 @@ int smg_loss_scene(smg_engine* e, const float* q_dev, const float* affine_host, 
                    const int* pixels_dev, const float* label_dev, const float* weight_dev,
                    float* loss_dev, float* dq_dev, void* stream);
 
+/* ---- the reactive net's class maps in the scene frame --------------------------------------------------------------------------
+ * The same three services for a 3-class head (head_out != 3 returns -22 and launches nothing): q_dev is [n_maps][3][OH][OW], the
+ * head output.  The geometry is steps 1-7 above, unchanged.  At a heightmap pixel that is valid in a map's rotation, in double:
+ *     z_c = the bilinear interpolation of LOGIT plane c there (c = 0, 1, 2: the same corners and fractions for all three)
+ *     P_c = exp(z_c - m) / sum_c' exp(z_c' - m),  m = max_c z_c,  rounded to float32 once.
+ * The logits are interpolated and the softmax is taken at the scene pixel; probabilities are not interpolated.  The training loss
+ * below is the cross entropy of those same interpolated logits, whose gradient is (softmax - onehot) x the four bilinear weights
+ * (the dense-map form), so picking and training see one and the same function of the head output.  Nothing is special-cased: a
+ * NaN, or an inf that produces inf - inf, in any of the twelve corner logits makes all three probabilities NaN, as torch.softmax
+ * does in fp64.  An invalid pixel is -inf in every plane, so the argmax rules carry over unchanged.
+ * All three return -22 and launch nothing for the geometry refusals above, for n_maps < 1 / K < 1 and for cls out of range. */
+
+/* out_dev float32: cls in {0,1,2} -> [n_maps][hm][hm] = P(class cls); cls == -1 -> [n_maps][3][hm][hm], all three.
+ * q_dev is [n_maps][3][OH][OW] (the head output of a 3-class engine). */
+int smg_scene_class_maps(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size,
+                         int cls, float* out_dev, void* stream);
+
+/* Largest valid P(class cls), cls in {0,1,2}, and its flattened index into [n_maps][hm][hm], without writing the maps:
+ * idx_out_dev int32[1], val_out_dev float32[1], smg_scene_argmax's rules and bit-reproducibility.  The value comes from the
+ * expression smg_scene_class_maps stores: the result equals smg_argmax over plane cls of its output, bit for bit.  Index -1,
+ * value -inf when no pixel is valid. */
+int smg_scene_class_argmax(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size,
+                           int cls, int* idx_out_dev, float* val_out_dev, void* stream);
+
+/* Cross entropy (CrossEntropyLoss2d, class weights {1,1,0}) on K labelled heightmap pixels per pair: q and dq are
+ * [n_pairs][3][OH][OW]; pixels_dev int32 [n_pairs][K][2] = (iy, ix); label_dev float32 [n_pairs][K] class indices as in
+ * smg_loss_map_ce (0 and 1 carry weight 1, anything else is class 2, "no loss").  W_j = the number of points of pair j whose class
+ * is 0 or 1, which lie inside the heightmap and which are valid in the pair's rotation; every other point contributes nothing, is
+ * not counted, and the logits under it are not read.  With z_k the three interpolated logits of point k (double, not rounded):
+ *     nll_k   = logsumexp(z_k) - z_k[y_k]
+ *     loss[j] = (sum_k nll_k) / W_j      (0 when W_j == 0, not 0/0)
+ *     dq[j][c][oy][ox] = (1 / W_j) sum_k (softmax(z_k)[c] - [c == y_k]) * (bilinear weight of (oy, ox) at point k)
+ * summed unnormalised in double in point order, divided by W_j once and rounded once; every element of dq is written, duplicate
+ * points add up, no atomics (bit-identical between identical calls).  Also -22 when 24 OH OW bytes of accumulators exceed 48 KB
+ * of LDS (maps beyond 45 x 45).  Marks the saved forward "dense dq" exactly as smg_loss_map_ce does. */
+int smg_loss_scene_ce(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs, int K,
+                      const int* pixels_dev, const float* label_dev, float* loss_dev, float* dq_dev, void* stream);
+
 /* Backward of the last smg_forward: accumulates (+=) d(sum of losses)/d(param) into
  * net->grads for the trunk and head that forward used.  Replaces loss.backward() at
  * code/trainer.py:350-351. */
@@ -257,7 +295,7 @@ int smg_engine_set_precision(smg_engine* e, int precision);
  * output elements it feeds, skips zero dq and adds its share of the 20x20 weight gradient with fp32 atomics; right for the single
  * element smg_loss mode 0 sets.  2: the dense form - a data pass over the 400 taps and a weight pass that owns every element of
  * the weight gradient (no atomics, pairs in index order: bit-identical between identical calls); right for a whole map.
- * 0 (default): the dense form after smg_loss_map / smg_loss_map_ce / smg_loss_scene, else the per-element form.  A 3-class head follows the same
+ * 0 (default): the dense form after smg_loss_map / smg_loss_map_ce / smg_loss_scene / smg_loss_scene_ce, else the per-element form.  A 3-class head follows the same
  * rule as a one-channel head (its dense form loops over the three output channels).  smg_train_step_graph always runs the
  * per-element form (its loss is smg_loss).
  * "serialize" (0 / 1): every kernel on the caller's stream in issue order instead of two concurrent chains (profiling).

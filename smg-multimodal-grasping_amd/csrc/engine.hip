@@ -563,6 +563,78 @@ int smg_loss_scene(smg_engine* e, const float* q_dev, const float* affine_host, 
     return 0;
 }
 
+// ---- the three class planes of a 3-class head in the scene frame ---------------------
+int smg_scene_class_maps(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls, float* out_dev,
+                         void* stream) {
+    if (!e || !q_dev || !affine_host || !out_dev) return fail(-22, "NULL argument");
+    if (e->head_out != 3) return fail(-22, "smg_scene_class_maps: class probabilities need a 3-class head (head_out == 3)");
+    if (n_maps < 1) return fail(-22, "smg_scene_class_maps: n_maps < 1");
+    if (cls < -1 || cls > 2) return fail(-22, "smg_scene_class_maps: cls must be 0, 1, 2 or -1 (all three)");
+    SceneGeo g;
+    if (int rc = scene_geometry(e, hm_size, "smg_scene_class_maps", &g)) return rc;      // (its LDS bound is 12 OH OW bytes: the three float planes)
+    if (int rc = scene_affines_ok(affine_host, n_maps, "smg_scene_class_maps")) return rc;
+    HIP_OK(hipSetDevice(e->device));
+    const int64_t npix = (int64_t)hm_size * hm_size;
+    const int vec4 = npix % 4 == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 15) == 0;
+    const int tiles = (int)((npix + kSceneTile - 1) / kSceneTile);
+    for (int m0 = 0; m0 < n_maps; m0 += kSceneMaps) {
+        const int n = std::min(kSceneMaps, n_maps - m0);
+        const SceneAffine a = scene_affine(affine_host, m0, n);
+        hipLaunchKernelGGL(scene_class_map_kernel, dim3(tiles, n), dim3(256), (size_t)3 * g.OH * g.OW * sizeof(float), (hipStream_t)stream,
+                           q_dev, m0, a, g, cls, out_dev, vec4);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smg_scene_class_argmax(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                           int* idx_out_dev, float* val_out_dev, void* stream) {
+    if (!e || !q_dev || !affine_host || !idx_out_dev || !val_out_dev) return fail(-22, "NULL argument");
+    if (e->head_out != 3) return fail(-22, "smg_scene_class_argmax: class probabilities need a 3-class head (head_out == 3)");
+    if (n_maps < 1) return fail(-22, "smg_scene_class_argmax: n_maps < 1");
+    if (cls < 0 || cls > 2) return fail(-22, "smg_scene_class_argmax: cls must be 0, 1 or 2");
+    SceneGeo g;
+    if (int rc = scene_geometry(e, hm_size, "smg_scene_class_argmax", &g)) return rc;
+    const int64_t npix = (int64_t)hm_size * hm_size;
+    if ((int64_t)n_maps * npix > 0x7fffffff) return fail(-22, "smg_scene_class_argmax: the flattened index does not fit int32");
+    if (int rc = scene_affines_ok(affine_host, n_maps, "smg_scene_class_argmax")) return rc;
+    HIP_OK(hipSetDevice(e->device));
+    const int tiles = (int)((npix + kSceneTile - 1) / kSceneTile);      // <= e->scene_tiles: hm_size <= S / 2
+    for (int m0 = 0; m0 < n_maps; m0 += kSceneMaps) {      // (groups follow each other on the stream: the partials are reused)
+        const int n = std::min(kSceneMaps, n_maps - m0);
+        const SceneAffine a = scene_affine(affine_host, m0, n);
+        hipLaunchKernelGGL(scene_class_argmax_kernel, dim3(tiles, n), dim3(256), (size_t)3 * g.OH * g.OW * sizeof(float), (hipStream_t)stream,
+                           q_dev, m0, a, g, cls, e->scene_val, e->scene_idx);
+        hipLaunchKernelGGL(scene_argmax_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
+                           (const int*)e->scene_idx, tiles * n, m0 > 0 ? 1 : 0, idx_out_dev, val_out_dev);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smg_loss_scene_ce(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs, int K, const int* pixels_dev,
+                      const float* label_dev, float* loss_dev, float* dq_dev, void* stream) {
+    if (!e || !q_dev || !affine_host || !pixels_dev || !label_dev || !loss_dev || !dq_dev) return fail(-22, "NULL argument");
+    if (e->head_out != 3) return fail(-22, "smg_loss_scene_ce: the scene-pixel cross entropy needs a 3-class head (head_out == 3)");
+    if (n_pairs < 1 || n_pairs > e->max_pairs) return fail(-22, "n_pairs exceeds the engine's max_pairs");
+    if (K < 1) return fail(-22, "smg_loss_scene_ce: K < 1");
+    SceneGeo g;
+    if (int rc = scene_geometry(e, hm_size, "smg_loss_scene_ce", &g)) return rc;
+    const size_t lds = (size_t)3 * g.OH * g.OW * sizeof(double);        // + 14 KB static: under the 64 KB of a plain launch
+    if (lds > 48 * 1024) return fail(-22, "smg_loss_scene_ce: the class maps' accumulators do not fit the kernel's LDS");
+    if (int rc = scene_affines_ok(affine_host, n_pairs, "smg_loss_scene_ce")) return rc;
+    HIP_OK(hipSetDevice(e->device));
+    for (int m0 = 0; m0 < n_pairs; m0 += kSceneMaps) {
+        const int n = std::min(kSceneMaps, n_pairs - m0);
+        const SceneAffine a = scene_affine(affine_host, m0, n);
+        hipLaunchKernelGGL(loss_scene_ce_kernel, dim3(n), dim3(256), lds, (hipStream_t)stream,
+                           q_dev, m0, a, g, K, pixels_dev, label_dev, loss_dev, dq_dev);
+    }
+    HIP_OK(hipGetLastError());
+    e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0), as after smg_loss_map_ce
+    return 0;
+}
+
 int smg_backward(smg_engine* e, const smg_net* net, const float* dq_dev, void* stream) {
     if (!e || !net || !dq_dev) return fail(-22, "NULL argument");
     HIP_OK(hipSetDevice(e->device));

@@ -1,6 +1,7 @@
 // scene.cuh - dense Q maps in the SCENE frame: every rotation's [OH][OW] map rotated back and bilinearly upsampled onto the
 // heightmap's pixel grid (smg_scene_maps), the best (rotation, heightmap pixel) without materialising those maps
-// (smg_scene_argmax), and the Huber loss on labelled heightmap pixels with its gradient on the map (smg_loss_scene).
+// (smg_scene_argmax), and the Huber loss on labelled heightmap pixels with its gradient on the map (smg_loss_scene); further down
+// the same three for the class logits of a 3-class head (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce).
 //
 // Geometry (include/smg_hip.h has the derivation), all in double, coordinates (x = column, y = row):
 //   heightmap pixel (iy, ix) -> centre of its 2x2 block of the padded input   x = 2 ix + 0.5 + pad
@@ -214,6 +215,184 @@ static __global__ __launch_bounds__(256) void loss_scene_kernel(const float* q, 
     if (t == 0) loss[j] = (float)red[0];
     float* dj = dq + (int64_t)j * P;
     for (int i = t; i < P; i += 256) dj[i] = (float)sacc[i];
+}
+
+// ---- the reactive net's three class planes in the scene frame (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce) ----
+// The three LOGIT planes of a map ([3][OH][OW], `P` = OH * OW apart) are interpolated at the scene point - same corners, same
+// fractions - and the softmax is taken there, in double: z_c = bilinear(plane c), m = max z, e_c = exp(z_c - m), s = e_0 + e_1 + e_2,
+// P_c = e_c / s rounded to fp32 once.  Logits are interpolated, not probabilities: the cross entropy below is that of these very
+// z, so picking and training see one function of the head output.  Nothing is special-cased: a NaN corner, or an inf that gives
+// inf - inf, makes s NaN and with it all three probabilities, as torch.softmax does in fp64.
+struct SceneClass { double z0, z1, z2, m, e0, e1, e2, s; };
+
+template <class QPtr>
+__device__ __forceinline__ SceneClass scene_class(const ScenePoint& p, QPtr Q, int P, int OW) {
+    SceneClass c;
+    c.z0 = scene_interp(p, Q, OW); c.z1 = scene_interp(p, Q + P, OW); c.z2 = scene_interp(p, Q + 2 * P, OW);
+    c.m = fmax(c.z0, fmax(c.z1, c.z2));
+    c.e0 = exp(c.z0 - c.m); c.e1 = exp(c.z1 - c.m); c.e2 = exp(c.z2 - c.m);
+    c.s = c.e0 + c.e1 + c.e2;
+    return c;
+}
+// P(class cls) of that point: the one expression both kernels below take their values from (so the argmax is bit-equal to the maps).
+// (By value and as two flat selects: a chain of conditionals on the members of a reference became an indexed load from a copy of
+// the struct in scratch memory, 72 bytes per lane.)
+__device__ __forceinline__ float scene_class_prob(const SceneClass c, int cls) {
+    const double e01 = cls == 0 ? c.e0 : c.e1;
+    return (float)((cls == 2 ? c.e2 : e01) / c.s);
+}
+
+// scene_class_map_kernel / scene_class_argmax_kernel: scene_walk's tiling (one workgroup = kSceneTile consecutive pixels of one
+// map, blockIdx.y = map of this launch, the matrix in registers) with all three planes of the map staged in LDS (3 OH OW floats,
+// dynamic); scene_point runs once per pixel.  q is [maps][3][OH][OW].  ARGMAX == false: cls in {0, 1, 2} stores P(class cls) to
+// out [maps][hm][hm], cls == -1 all three to out [maps][3][hm][hm] - a thread's pixel group goes to three addresses hm^2 apart -
+// as 16-byte units (`vec4`) or guarded 4-byte stores; an invalid pixel is -inf in every plane.  ARGMAX == true: cls in {0, 1, 2},
+// nothing stored, the workgroup's best (P(class cls), index into [maps][hm][hm]) goes to its slot of the partial arrays exactly
+// as in scene_walk, for scene_argmax_reduce_kernel.
+template <bool ARGMAX>
+__device__ __forceinline__ void scene_class_walk(const float* q, int map0, const SceneAffine& aff, const SceneGeo& g, int cls,
+                                                 float* out, int vec4, float* part_val, int* part_idx) {
+    extern __shared__ float sq[];
+    __shared__ float bv[256];
+    __shared__ int bi[256];
+    const int t = threadIdx.x, m = blockIdx.y;
+    const int P = g.OH * g.OW;
+    const float* qm = q + (int64_t)(map0 + m) * 3 * P;
+    for (int i = t; i < 3 * P; i += 256) sq[i] = qm[i];
+    __syncthreads();
+    const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
+    const int npix = g.hm * g.hm;                       // (the host refuses maps of 2^31 pixels or more)
+    const int base = blockIdx.x * kSceneTile;
+    const int planes = cls < 0 ? 3 : 1;
+    float best = -INFINITY; int at = 0x7fffffff;
+    for (int pass = 0; pass < kSceneTile / 1024; ++pass) {
+        const int i0 = base + 4 * (pass * 256 + t);
+        if (i0 >= npix) break;
+        int iy = i0 / g.hm, ix = i0 - iy * g.hm;
+        float v[3][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k, ++ix) {
+            const int i = i0 + k;
+            if (ix == g.hm) { ix = 0; ++iy; }
+            v[0][k] = v[1][k] = v[2][k] = -INFINITY;
+            if (i < npix) {
+                const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
+                if (p.valid) {
+                    const SceneClass c = scene_class(p, sq, P, g.OW);
+                    if (cls < 0) { v[0][k] = scene_class_prob(c, 0); v[1][k] = scene_class_prob(c, 1); v[2][k] = scene_class_prob(c, 2); }
+                    else v[0][k] = scene_class_prob(c, cls);
+                    if (ARGMAX) {
+                        const int flat = (map0 + m) * npix + i;       // (< 2^31: checked by the host)
+                        if (argmax_better(v[0][k], flat, best, at)) { best = v[0][k]; at = flat; }
+                    }
+                }
+            }
+        }
+        if (!ARGMAX) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (c >= planes) break;
+                float* o = out + ((int64_t)(map0 + m) * planes + c) * npix + i0;
+                if (vec4) *reinterpret_cast<float4*>(o) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+                else
+                    for (int k = 0; k < 4; ++k) if (i0 + k < npix) o[k] = v[c][k];
+            }
+        }
+    }
+    if (ARGMAX) {
+        bv[t] = best; bi[t] = at;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (t < s) {
+                const float x = bv[t + s]; const int j = bi[t + s];
+                if (j != 0x7fffffff && argmax_better(x, j, bv[t], bi[t])) { bv[t] = x; bi[t] = j; }
+            }
+            __syncthreads();
+        }
+        if (t == 0) { const int slot = blockIdx.y * gridDim.x + blockIdx.x; part_val[slot] = bv[0]; part_idx[slot] = bi[0]; }
+    }
+}
+static __global__ __launch_bounds__(256) void scene_class_map_kernel(const float* q, int map0, const SceneAffine aff, const SceneGeo g, int cls,
+                                                                     float* out, int vec4) {
+    scene_class_walk<false>(q, map0, aff, g, cls, out, vec4, nullptr, nullptr);
+}
+static __global__ __launch_bounds__(256) void scene_class_argmax_kernel(const float* q, int map0, const SceneAffine aff, const SceneGeo g, int cls,
+                                                                        float* part_val, int* part_idx) {
+    scene_class_walk<true>(q, map0, aff, g, cls, nullptr, 0, part_val, part_idx);
+}
+
+// smg_loss_scene_ce: the cross entropy (CrossEntropyLoss2d, class weights {1, 1, 0}) of the interpolated logits at K labelled
+// heightmap pixels per pair - loss_scene_kernel's gather form on three planes.  A point COUNTS when its label is 0 or 1, it lies in
+// the heightmap and it is valid in the pair's rotation; W = the number of such points; every other point (class 2 included,
+// whatever logits lie under it) is skipped before anything is read.  Per counted point, in double:
+//     nll_k = log(s) + m - z_y        g_c = e_c / s - [c == y]
+// loss[j] = (sum nll_k) / W and dq[j][c][oy][ox] = (sum_k g_c * bilinear weight of (oy, ox) at point k) / W: summed unnormalised
+// in point order, divided once, rounded once; W == 0 gives loss 0 and dq 0.  The points are taken 256 at a time, thread t owns map
+// elements t, t + 256, ... in all three planes.  Dynamic LDS: the 3 OH OW double accumulators only - the logits are read from
+// global memory (a few corners per point of a map that sits in L2), which keeps 38 x 38 maps at 35 KB + 14 KB static.
+static __global__ __launch_bounds__(256) void loss_scene_ce_kernel(const float* q, int pair0, const SceneAffine aff, const SceneGeo g, int K,
+                                                                   const int* pixels, const float* label, float* loss, float* dq) {
+    extern __shared__ double sacc[];
+    __shared__ double red[256];
+    __shared__ int cnt[256];
+    __shared__ double p_fy[256], p_fx[256], p_g[3][256];
+    __shared__ int p_o[256];
+    const int t = threadIdx.x, m = blockIdx.x, j = pair0 + m;
+    const int P = g.OH * g.OW;
+    const float* qj = q + (int64_t)j * 3 * P;
+    for (int i = t; i < 3 * P; i += 256) sacc[i] = 0.0;
+    __syncthreads();
+    const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
+    double lsum = 0.0; int w = 0;
+    for (int k0 = 0; k0 < K; k0 += 256) {
+        const int k = k0 + t;
+        int o = -1; double fy = 0.0, fx = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+        if (k < K) {
+            const int64_t at = (int64_t)j * K + k;
+            const int iy = pixels[2 * at], ix = pixels[2 * at + 1];
+            const float lf = label[at];
+            if ((lf == 0.f || lf == 1.f) && iy >= 0 && iy < g.hm && ix >= 0 && ix < g.hm) {
+                const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
+                if (p.valid) {
+                    const SceneClass c = scene_class(p, qj, P, g.OW);
+                    lsum += (log(c.s) + c.m) - (lf == 0.f ? c.z0 : c.z1);
+                    ++w;
+                    o = p.y0 * g.OW + p.x0; fy = p.fy; fx = p.fx;
+                    g0 = c.e0 / c.s - (lf == 0.f ? 1.0 : 0.0); g1 = c.e1 / c.s - (lf == 1.f ? 1.0 : 0.0); g2 = c.e2 / c.s;
+                }
+            }
+        }
+        p_o[t] = o; p_fy[t] = fy; p_fx[t] = fx; p_g[0][t] = g0; p_g[1][t] = g1; p_g[2][t] = g2;
+        __syncthreads();
+        const int n = min(256, K - k0);
+        for (int i = t; i < P; i += 256) {
+            const int ey = i / g.OW, ex = i - ey * g.OW;
+            double acc0 = sacc[i], acc1 = sacc[P + i], acc2 = sacc[2 * P + i];
+            for (int kk = 0; kk < n; ++kk) {
+                const int oo = p_o[kk];
+                if (oo < 0) continue;
+                const int y0 = oo / g.OW, x0 = oo - y0 * g.OW;
+                const int dy = ey - y0, dx = ex - x0;
+                if ((unsigned)dy > 1u || (unsigned)dx > 1u) continue;
+                const double wy = dy ? p_fy[kk] : 1.0 - p_fy[kk], wx = dx ? p_fx[kk] : 1.0 - p_fx[kk];
+                const double wgt = wy * wx;
+                acc0 += p_g[0][kk] * wgt; acc1 += p_g[1][kk] * wgt; acc2 += p_g[2][kk] * wgt;
+            }
+            sacc[i] = acc0; sacc[P + i] = acc1; sacc[2 * P + i] = acc2;
+        }
+        __syncthreads();
+    }
+    red[t] = lsum; cnt[t] = w;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) { red[t] += red[t + s]; cnt[t] += cnt[t + s]; }
+        __syncthreads();
+    }
+    const int W = cnt[0];
+    const double dW = (double)W;
+    if (t == 0) loss[j] = W > 0 ? (float)(red[0] / dW) : 0.f;
+    float* dj = dq + (int64_t)j * 3 * P;
+    for (int i = t; i < 3 * P; i += 256) dj[i] = W > 0 ? (float)(sacc[i] / dW) : 0.f;
 }
 
 }  // namespace smg

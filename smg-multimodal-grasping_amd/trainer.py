@@ -760,6 +760,127 @@ class Trainer(object):
         label_maps[np.arange(len(lab)), pix[:, 0], pix[:, 1]] = lab
         return self.train_batch_class_maps(depth_heightmap, m_depth_heightmap, style, rotations, label_maps, grad_sync, return_q)
 
+    # ---- class maps in the scene frame (reactive method): logits rotated back and interpolated, softmax at the heightmap pixel ----------
+    def _require_scene_class(self, what, depth_heightmap):
+        self._require_reactive(what)
+        return self._scene_geometry(np.shape(depth_heightmap)[-1])
+
+    def forward_scene_class_maps(self, depth_heightmap, m_depth_heightmap, style=0, specific_rotation=-1, cls=None, logits=False,
+                                 return_device=False):
+        """forward_class_maps in the SCENE frame: every evaluated rotation's three logit maps rotated back and bilinearly
+        interpolated at the heightmap's pixels, softmax taken there (smg_scene_class_maps) - float64 [R, 3, hm, hm] class
+        probabilities, or [R, hm, hm] for one `cls` in {0, 1, 2}; the float32 device tensor if asked; -inf where no window of the
+        head is centred in that rotation.  `logits` returns the interpolated logits instead (smg_scene_maps per class plane).
+        Element [r, c, iy, ix] is P(class c) of acting at heightmap pixel (iy, ix) with rotation r: the same scene point in every
+        rotation.  Rotation choice and BN bookkeeping are forward_class_maps'.  Reactive method, heightmaps larger than 224^2."""
+        import models
+        self._require_scene_class("forward_scene_class_maps", depth_heightmap)
+        if cls is not None and cls not in (0, 1, 2):
+            raise ValueError("forward_scene_class_maps: cls must be None (all three), 0, 1 or 2")
+        model = self.model
+        q = self.forward_class_maps(depth_heightmap, m_depth_heightmap, style, specific_rotation, logits=True, return_device=True)
+        dev = q.device
+        R, _, OH, OW = q.shape
+        hm = int(np.shape(depth_heightmap)[-1])
+        aff = [models.rotation_theta(r, num) for r, num in self._scene_rotations(model, style, specific_rotation)]
+        assert len(aff) == R
+        eng = models.get_engine(dev.index or 0, self._scene_geometry(hm)[1], model.HEAD_OUT, 1, 1)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if logits:
+            planes = (0, 1, 2) if cls is None else (cls,)
+            out = torch.empty((len(planes), R, hm, hm), dtype=torch.float32, device=dev)
+            for k, c in enumerate(planes):
+                eng.scene_maps(q[:, c].data_ptr(), 3 * OH * OW, R, aff, hm, out[k].data_ptr(), stream)
+            out = out.permute(1, 0, 2, 3).contiguous() if cls is None else out[0]
+        else:
+            out = torch.empty((R, 3, hm, hm) if cls is None else (R, hm, hm), dtype=torch.float32, device=dev)
+            eng.scene_class_maps(q.data_ptr(), R, aff, hm, -1 if cls is None else cls, out.data_ptr(), stream)
+        return out if return_device else out.cpu().numpy().astype(np.float64)
+
+    def best_scene_class_action(self, depth_heightmap, m_depth_heightmap, style=0):
+        """The (rotation, heightmap pixel) of the sweep with the largest P(class 0), found on the device without materialising the
+        scene-frame maps (smg_scene_class_argmax: lowest index of the flattened [R, hm, hm] on ties like np.argmax, a NaN wins,
+        pixels without a window are never picked); the host reads back one (index, value) pair.
+        Returns {"rotation", "pixel": (iy, ix), "conf", "map_pixel": (qy, qx)} as best_scene_action does."""
+        import models
+        self._require_scene_class("best_scene_class_action", depth_heightmap)
+        model = self.model
+        q = self.forward_class_maps(depth_heightmap, m_depth_heightmap, style, logits=True, return_device=True)
+        dev = q.device
+        R = q.shape[0]
+        hm = int(np.shape(depth_heightmap)[-1])
+        rots = self._scene_rotations(model, style, -1)
+        eng = models.get_engine(dev.index or 0, self._scene_geometry(hm)[1], model.HEAD_OUT, 1, 1)
+        idx = torch.empty(1, dtype=torch.int32, device=dev)
+        val = torch.empty(1, dtype=torch.float32, device=dev)
+        eng.scene_class_argmax(q.data_ptr(), R, [models.rotation_theta(r, num) for r, num in rots], hm, 0, idx.data_ptr(), val.data_ptr(),
+                               torch.cuda.current_stream(dev).cuda_stream)
+        i = int(idx.cpu().numpy()[0])
+        row, iy, ix = i // (hm * hm), (i // hm) % hm, i % hm
+        qy, qx, _ = self.scene_to_map(hm, rots[row][0], rots[row][1], (iy, ix))
+        return {"rotation": rots[row][0], "pixel": (iy, ix), "conf": float(val.cpu().numpy().astype(np.float64)[0]),
+                "map_pixel": (float(qy), float(qx))}
+
+    def train_batch_scene_class_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, grad_sync=None,
+                                       return_q=False):
+        """train_batch_class_maps with the class labels at HEIGHTMAP pixels: sample j trains K scene pixels - `pixels`
+        [n_samples, K, 2] = (iy, ix) ([n_samples, 2] for K = 1), `labels` [n_samples, K] in {0, 1, 2} - through the bilinear
+        interpolation of its three logit maps at those points: loss_j = the mean over its class-0 / 1 points of the cross entropy
+        of the interpolated logits (smg_loss_scene_ce), whose gradient spreads over the four map elements around each point.
+        Class 2 is "no loss": padding for a ragged K, which must lie in the heightmap but needs no window.  A class-0 / 1 pixel
+        without a window of the head in its sample's rotation (scene_to_map's `valid`) raises ValueError before anything runs.
+        The gradient of the SUM of the losses goes back in one backward pass (dense head form), then ONE Adam step.  Scenes,
+        rotations and `grad_sync` as in train_batch_class_maps; host arrays.  Reactive method only.
+        Returns the loss vector (and the logits q [n_samples, 3, OH, OW] if asked)."""
+        import models
+        _, _, side = self._require_scene_class("train_batch_scene_class_pixels", depth_heightmap)
+        per_scene = np.ndim(depth_heightmap) == 3
+        flat_rots = [r for rs in rotations for r in rs] if per_scene else list(rotations)
+        n = len(flat_rots)
+        hm = int(np.shape(depth_heightmap)[-1])
+        pix = np.asarray(pixels)
+        if pix.ndim == 2:
+            pix = pix[:, None, :]
+        if pix.ndim != 3 or pix.shape[0] != n or pix.shape[1] < 1 or pix.shape[2] != 2:
+            raise ValueError("pixels must be [%d samples, K, 2] = (iy, ix), got %s" % (n, np.shape(pixels)))
+        K = pix.shape[1]
+        lab = np.asarray(labels, dtype=np.float32)
+        if lab.shape != (n, K) and not (K == 1 and lab.shape == (n,)):
+            raise ValueError("labels must be [%d samples, %d], got %s" % (n, K, lab.shape))
+        lab = lab.reshape(n, K)
+        if not np.isin(lab, (0.0, 1.0, 2.0)).all():      # (torch's nll_loss raises on a class index outside [0, 3), as in train_batch)
+            raise ValueError("labels must be class indices 0, 1 or 2")
+        pix_i = pix.astype(np.int64)
+        if not np.array_equal(pix_i, pix) or pix_i.min() < 0 or pix_i.max() >= hm:
+            raise ValueError("pixels must be integer (iy, ix) inside the %d x %d heightmap" % (hm, hm))
+        num = self.model.gnum_rotations
+        rots = [0 if style == 2 else int(r) for r in flat_rots]
+        _, _, valid = self.scene_to_map(hm, np.asarray(rots).reshape(n, 1), num, pix_i)
+        lost = ~valid & (lab != 2.0)
+        if lost.any():
+            j, k = np.argwhere(lost)[0]
+            raise ValueError("pixel %s of sample %d (class %d) has no window in rotation %d of %d (scene_to_map)"
+                             % (tuple(pix_i[j, k]), j, int(lab[j, k]), rots[j], num))
+        model = self.model
+        self.optimizer.zero_grad()
+        model._require_gpu()
+        dev = model._flat_params.device
+        hmaps, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
+        rots2 = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
+        # (uploaded BEFORE the forward is enqueued, like train_batch's labels)
+        pix_d = torch.as_tensor(np.ascontiguousarray(pix_i, dtype=np.int32), device=dev)
+        lab_d = torch.as_tensor(np.ascontiguousarray(lab), device=dev)
+        q = model.run(style, rots2, num, heightmaps=hmaps, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
+        eng, token, trunk_id, head_id = model._saved
+        assert tuple(q.shape) == (n, 3, side, side), (tuple(q.shape), n, side)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        dq = torch.empty_like(q)
+        eng.loss_scene_ce(q.data_ptr(), [models.rotation_theta(r, num) for r in rots], hm, n, K, pix_d.data_ptr(), lab_d.data_ptr(),
+                          loss.data_ptr(), dq.data_ptr(), stream)
+        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
+        return (loss, q) if return_q else loss
+
     # The single-sample step of Trainer.backprop as ONE replayed hipGraph (smg_train_step_graph): ~560 launches of 2-20 us each are
     # enqueued by one hipGraphLaunch instead of one by one (same results, bit for bit at zero learning rate).  It saves a little host time
     # (1.8 ms per step instead of 2.3) and costs latency: the graph's ~560 dependent nodes execute no faster than the same launches from
