@@ -257,11 +257,27 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         e->have_fwd = false; e->bw_phase0_done = false; e->prof_stage = -1;
         return 0;
     };
+    // pool0's backward and conv0's weight gradient at pooled resolution (elem.cuh: stem_tail_kernel; mode 0, one-channel stem) - like the
+    // partial-tile form of the 1x1 weight gradient for calls of more than four streams or under "deterministic": a call of a few
+    // streams is launch-bound on the side stream, where the moments and the combine are three launches more than the pair they
+    // replace (single-sample step 5.34-5.57 ms with the stem-resolution pair, 5.65-6.20 with the pooled tail, alternating on one box)
+    const bool pooled_tail = e->prec == 0 && e->f_stem1 && !e->stem_plane_tail && (NS > 4 || e->deterministic);
     for (int b = ph_a ? 3 : 0; b >= (ph_b ? 0 : 1); --b) {
         e->prof_stage = b;
         const Plane pl = e->p_blk[b];
         const int Ct = kBlockCtot[b];
         if (e->dbg_stop == b * 100 + 50) return debug_stop();
+        if (b == 0 && pooled_tail) {      // the image moments R_n | S_n need the image only: on the side stream, under dense block 1's kernels
+            StemMomArgs a;
+            a.img = e->img4; a.pi = e->p_img; a.ps = e->p_stem; a.part = e->mom_part;
+            a.tiles_x = stem_mom_tiles_x(e->p_stem); a.n_tiles = stem_mom_tiles(e->p_stem); a.tiles_per_wg = kMomTilesPerWg;
+            if (fork(e->ev_misc)) return -5;
+            e->prof_stage = -1;
+            launch_kernel(e, stem_moments_kernel, dim3(e->mom_groups, NS), dim3(256), 0, s2, K_OTHER, 0, 0, false, a);
+            launch_kernel(e, stem_moments_sum_kernel, dim3((kMomOut + 255) / 256, NS), dim3(256), 0, s2, K_OTHER, 0, 0, false,
+                          (const float*)e->mom_part, e->mom_groups, e->mom);
+            e->prof_stage = b;
+        }
         for (int i = (int)T.layers[b].size() - 1; i >= 0; --i) {
             const DenseLayerRef& d = T.layers[b][i];
             float* bt = el(e, e->Bt, e->bt_off[b][i]);
@@ -456,7 +472,41 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         }
     }
     e->prof_stage = -1;
-    if (ph_b) {
+    if (ph_b && pooled_tail) {   // pool0 / relu0 backward + norm0 sums + conv0 weight gradient from the pooled pixels
+        const Plane p1 = e->p_blk[0];
+        StemTailArgs a;
+        a.G1 = e->G[0]; a.X1 = e->X[0]; a.ld1 = kBlockCtot[0]; a.p1 = p1;
+        a.xsum = fsum(e, e->st_X[0]); a.xsq = fsq(e, e->st_X[0]); a.xstride = kBlockCtot[0];
+        a.SA = b1(e, e->st_X[0]); a.SB = b2(e, e->st_X[0]); a.sstride = kBlockCtot[0];
+        a.argmax = e->argmax; a.stemv = e->stemv;
+        a.ssum = fsum(e, e->st_stem); a.ssq = fsq(e, e->st_stem); a.ps = e->p_stem;
+        a.gamma = P + T.norm0.w; a.eps = kEps;
+        a.img = e->img4; a.pi = e->p_img;
+        a.o1 = b1(e, e->st_stem); a.o2 = b2(e, e->st_stem);
+        a.tiles_x = (p1.W + kTailTW - 1) / kTailTW; a.n_tiles = a.tiles_x * ((p1.H + kTailTH - 1) / kTailTH);
+        // one 64 x 64 partial tile per workgroup.  Runs of 8 tiles or more: as long as it takes for ONE round of workgroups (three are
+        // resident per CU) and for the partial tiles to fit the workspace
+        a.tiles_per_wg = 8;
+        auto groups = [&]() { return (a.n_tiles + a.tiles_per_wg - 1) / a.tiles_per_wg; };
+        while (a.tiles_per_wg < a.n_tiles && ((int64_t)groups() * NS > 3 * e->n_cu || (int64_t)groups() * NS * 64 * 64 > e->part_floats)) ++a.tiles_per_wg;
+        const int Z = groups() * NS;
+        const PartialTiles::Slot at = tiles.place_alone((int64_t)Z * 64 * 64);
+        launch_reduce2(e, s2, at.first);
+        if (at.off < 0) return fail(-12, "partial-gradient workspace too small");
+        a.part = part_at(e, at);
+        // the kernel writes the workspace on `st`: behind everything the side stream still does there
+        HIP_OK(hipEventRecord(e->ev_end, s2));
+        HIP_OK(hipStreamWaitEvent(st, e->ev_end, 0));
+        launch_kernel(e, stem_tail_kernel, dim3(groups(), NS), dim3(256), 0, st, K_SW, 2.0 * NS * p1.HW * 64 * 49,
+                      4.0 * NS * ((double)p1.HW * (3 * 64 + 16) + (double)e->p_img.HW), false, a);
+        if (fork(e->ev_misc)) return -5;
+        launch_reduce2(e, s2, tiles.launched(at, reduce_chunk_major(a.part, Z, 1, 64, 49, 64, 64, Gr + T.conv0.w, 147, C_STEM1)));
+        StemCombineArgs c;
+        c.mom = e->mom; c.w0 = P + T.conv0.w; c.ssum = a.ssum; c.ssq = a.ssq; c.s1 = a.o1; c.s2 = a.o2;
+        c.gamma = a.gamma; c.eps = kEps; c.HW = e->p_stem.HW; c.ns = NS; c.dw = Gr + T.conv0.w;
+        launch_kernel(e, stem_combine_kernel, dim3(64), dim3(256), (size_t)(NS * kMomRows + 256) * sizeof(double), s2, K_OTHER, 0, 0, false, c);
+    }
+    if (ph_b && !pooled_tail) {
     {   // pool0 / relu0 backward + norm0 sums
         Pool0BwdArgs a;
         a.G1 = e->G[0]; a.X1 = e->X[0]; a.ld1 = kBlockCtot[0]; a.p1 = e->p_blk[0];

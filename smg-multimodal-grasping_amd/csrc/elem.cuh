@@ -280,6 +280,7 @@ struct Pool0Args {
     void* x1; int ldx; Plane po;            // block-1 buffer (activation storage of the mode)
     double* dsum; double* dsq; int dstride;
     unsigned char* argmax;                  // [n][po.HWp][64]
+    float* stemv;                           // [n][po.HWp][64] the raw stem value at the argmax (stem_tail_kernel), or nullptr
 };
 
 template <int PREC>
@@ -303,18 +304,21 @@ static __global__ __launch_bounds__(256) void pool0_kernel(const Pool0Args a) {
         const int y = p / a.po.W, x = p - y * a.po.W;
         float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         int bi[4] = {0, 0, 0, 0};
+        float raw[4] = {0.f, 0.f, 0.f, 0.f};
         for (int k = 0; k < 9; ++k) {
             const int yy = 2 * y - 1 + k / 3, xx = 2 * x - 1 + k % 3;
             if ((unsigned)yy >= (unsigned)a.ps.H || (unsigned)xx >= (unsigned)a.ps.W) continue;
-            const float4 v = bnrelu4(ld4(a.stem + ((int64_t)n * a.ps.HWp + yy * a.ps.W + xx) * 64 + 4 * cq), prm + 4 * cq, 64);
-            const float vv[4] = {v.x, v.y, v.z, v.w};
+            const float4 r = ld4(a.stem + ((int64_t)n * a.ps.HWp + yy * a.ps.W + xx) * 64 + 4 * cq);
+            const float4 v = bnrelu4(r, prm + 4 * cq, 64);
+            const float vv[4] = {v.x, v.y, v.z, v.w}, rr[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                if (vv[c] > best[c]) { best[c] = vv[c]; bi[c] = k; }
+                if (vv[c] > best[c]) { best[c] = vv[c]; bi[c] = k; raw[c] = rr[c]; }
         }
         const int64_t o = (int64_t)n * a.po.HWp + p;
         stq<XT>(a.x1, o * a.ldx + 4 * cq, make_float4(best[0], best[1], best[2], best[3]));
         if (a.argmax) *reinterpret_cast<uchar4*>(a.argmax + o * 64 + 4 * cq) = make_uchar4(bi[0], bi[1], bi[2], bi[3]);
+        if (a.stemv) *reinterpret_cast<float4*>(a.stemv + o * 64 + 4 * cq) = make_float4(raw[0], raw[1], raw[2], raw[3]);
 #pragma unroll
         for (int c = 0; c < 4; ++c) { s[c] += (double)best[c]; ss[c] += (double)best[c] * (double)best[c]; }
     }
@@ -1072,6 +1076,325 @@ static __global__ __launch_bounds__(256) void pool0_bwd_kernel(const Pool0BwdArg
         atomicAdd((q ? a.o2 : a.o1) + (int64_t)n * 64 + c + stat_rep(), (double)tot);
         // (norm0's dbeta / dgamma are these sums over the streams: db_flush_kernel adds them - 3400 workgroups on one address per
         // channel here were the tail of this kernel)
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// The same tail at POOLED resolution (precision mode 0, one-channel stem): conv0's weight gradient without a pass over the stem
+// plane and without DY0.  The gradient that pool0 / relu0 route to the stem is sparse - each (pooled pixel q, channel c) sends
+// gm[q, c] to ONE stem pixel pos(q, c), the argmax of its window, and the argmax element passed the ReLU exactly when
+// X1[q, c] > 0 - and conv0 is linear without bias, so with A = a*dy + b*x + c (the BN-backward operand of BwdWeightP: a = gamma *
+// invstd, b = -a * k, c = a * (k * mean - q1)) and x[p, c] = sum_t' w[c, t'] * I[2p + t' - 3]
+//   dW0[c, t] = sum_n ( a_nc * T1_n[c, t] + b_nc * sum_t' w[c, t'] * R_n[t', t] + c_nc * S_n[t] )
+//   T1_n[c, t] = sum_q gm_n[q, c] * I_n[2 pos(q, c) + t - 3]             stem_tail_kernel (+ norm0's s1 / s2 sums, as pool0_bwd_kernel)
+//   R_n[t', t] = sum_p I_n[2p + t' - 3] * I_n[2p + t - 3],  S_n[t] = sum_p I_n[2p + t - 3]     stem_moments_kernel: the image only
+// stem_combine_kernel adds the b and c terms in fp64.  (tests/test_cpu_stem_tail_identity.py checks the identity in float64.)
+// ------------------------------------------------------------------------------------
+// stem_tail_kernel: workgroup = tiles of 16 x 4 pooled pixels x 64 channels.  Per tile the 71 x 23 image pixels its patches can
+// touch (image row of tap ty of window element ky of pooled row qy: 4 qy - 5 + 2 ky + ty) sit in LDS together with gm and each
+// (pixel, channel)'s patch origin; thread = (channel, a quarter of the 49 taps) then walks the tile's 64 pixels.  Lanes of a
+// half-wave read at most the 9 origins of one pooled pixel: pitch 75 = 11 mod 32 keeps {0, 2, 4} + {0, 2, 4} * pitch on
+// nine banks.  A workgroup leaves ONE 64 x 64 partial tile (columns 49.. zero), already scaled by a_nc: reduce_partials_kernel
+// sums them in a fixed order - no atomics on the gradient.
+constexpr int kTailTW = 16, kTailTH = 4, kTailIW = 4 * kTailTW + 7, kTailIH = 4 * kTailTH + 7, kTailPitch = 75, kTailGl = 65;
+struct StemTailArgs {
+    const float* G1; const float* X1; int ld1; Plane p1;     // block-1 buffers (fp32: mode 0)
+    const double* xsum; const double* xsq; int xstride;      // block-1 stats
+    const double* SA; const double* SB; int sstride;
+    const unsigned char* argmax; const float* stemv;         // [n][p1.HWp][64] (pool0_kernel)
+    const double* ssum; const double* ssq; Plane ps;         // stem stats [n][64]
+    const float* gamma; float eps;                           // norm0
+    const float* img; Plane pi;                              // one-channel image [n][pi.HWp]
+    double* o1; double* o2;                                  // [n][64]
+    float* part;                                             // [n][gridDim.x][64][64]
+    int tiles_x, n_tiles, tiles_per_wg;
+};
+
+template <int T0, int NT>
+__device__ __forceinline__ void stem_tail_taps(float (&acc)[13], const float* gl, const unsigned short* ol, const float* it, int c) {
+#pragma unroll 2
+    for (int q = 0; q < kTailTW * kTailTH; ++q) {
+        const float g = gl[q * kTailGl + c];
+        const float* ip = it + ol[q * 64 + c];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[j] = fmaf(g, ip[((T0 + j) / 7) * kTailPitch + (T0 + j) % 7], acc[j]);
+    }
+}
+template <int T0, int NT>
+__device__ __forceinline__ void stem_tail_put(const float (&acc)[13], float* gl, int c, float a) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) gl[c * kTailGl + T0 + j] = acc[j] * a;
+}
+
+static __global__ __launch_bounds__(256) void stem_tail_kernel(const StemTailArgs a) {
+    __shared__ float prm[7 * 64];
+    __shared__ float gl[64 * kTailGl];                       // gm [pixel][channel]; at the end the partial tile [channel][tap], then the sums
+    __shared__ unsigned short ol[64 * 64];                   // patch origin in `it`
+    __shared__ float it[kTailIH * kTailPitch];
+    static_assert(2 * 16 * 64 <= 64 * kTailGl, "the s1 / s2 reduction reuses gl");
+    const int n = blockIdx.y, t = threadIdx.x, cq = t & 15, slot = t >> 4;
+    if (t < 64) {
+        float mean, invstd;
+        bn_moments(a.ssum, a.ssq, (int64_t)n * 64 + t, 1.0 / (double)a.ps.HW, a.eps, mean, invstd);
+        prm[256 + t] = mean; prm[320 + t] = invstd; prm[384 + t] = a.gamma[t] * invstd;
+        const double inv = 1.0 / (double)a.p1.HW;
+        float m1, i1;
+        bn_moments(a.xsum, a.xsq, (int64_t)n * a.xstride + t, inv, a.eps, m1, i1);
+        const float q1 = (float)(stat_get(a.SA, (int64_t)n * a.sstride + t) * inv);
+        const float q2 = (float)(stat_get(a.SB, (int64_t)n * a.sstride + t) * inv);
+        prm[t] = i1; prm[64 + t] = q1; prm[128 + t] = m1; prm[192 + t] = i1 * q2;
+    }
+    float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+    float acc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const float* img = a.img + (int64_t)n * a.pi.HWp;
+    const int tile0 = blockIdx.x * a.tiles_per_wg, tile1 = min(tile0 + a.tiles_per_wg, a.n_tiles);
+    for (int tile = tile0; tile < tile1; ++tile) {
+        const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+        const int qy0 = ty * kTailTH, qx0 = tx * kTailTW;
+        float4 gq[4], xq[4], sq[4];
+        uchar4 aq[4];
+        bool okq[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int lp = slot + 16 * i;                       // local pixel 0..63 = 4 rows of 16
+            const int qy = qy0 + (lp >> 4), qx = qx0 + (lp & 15);
+            okq[i] = qy < a.p1.H && qx < a.p1.W;
+            const int64_t pr = (int64_t)n * a.p1.HWp + (okq[i] ? qy * a.p1.W + qx : 0);
+            gq[i] = ld4(a.G1 + pr * a.ld1 + 4 * cq);
+            xq[i] = ld4(a.X1 + pr * a.ld1 + 4 * cq);
+            sq[i] = ld4(a.stemv + pr * 64 + 4 * cq);
+            aq[i] = *reinterpret_cast<const uchar4*>(a.argmax + pr * 64 + 4 * cq);
+        }
+        constexpr int kImg = kTailIH * kTailIW, kImgLoads = (kImg + 255) / 256;
+        float iv[kImgLoads];
+        const int iy0 = 4 * qy0 - 5, ix0 = 4 * qx0 - 5;
+#pragma unroll
+        for (int j = 0; j < kImgLoads; ++j) {
+            const int idx = t + 256 * j, r = idx / kTailIW, cc = idx - r * kTailIW;
+            const int y = iy0 + r, x = ix0 + cc;
+            const bool in = idx < kImg && (unsigned)y < (unsigned)a.pi.H && (unsigned)x < (unsigned)a.pi.W;      // zero outside the image
+            iv[j] = img[in ? y * a.pi.W + x : 0];
+            if (!in) iv[j] = 0.f;
+        }
+        __syncthreads();                                        // prm ready; the previous tile's gl / ol / it consumed
+#pragma unroll
+        for (int j = 0; j < kImgLoads; ++j) {
+            const int idx = t + 256 * j, r = idx / kTailIW, cc = idx - r * kTailIW;
+            if (idx < kImg) it[r * kTailPitch + cc] = iv[j];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int lp = slot + 16 * i;
+            const float4 gv = affine2(gq[i], xq[i], prm + 4 * cq, 64);
+            const float g4[4] = {gv.x, gv.y, gv.z, gv.w}, x4[4] = {xq[i].x, xq[i].y, xq[i].z, xq[i].w}, v4[4] = {sq[i].x, sq[i].y, sq[i].z, sq[i].w};
+            const int k4[4] = {aq[i].x, aq[i].y, aq[i].z, aq[i].w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const bool on = okq[i] && x4[c] > 0.f;          // the argmax element passed the ReLU
+                const float gm = on ? g4[c] : 0.f;
+                s1[c] += gm;
+                s2[c] += gm * ((v4[c] - prm[256 + 4 * cq + c]) * prm[320 + 4 * cq + c]);
+                const int k = on ? k4[c] : 0;
+                gl[lp * kTailGl + 4 * cq + c] = gm;
+                ol[lp * 64 + 4 * cq + c] = (unsigned short)((4 * (lp >> 4) + 2 * (k / 3)) * kTailPitch + 4 * (lp & 15) + 2 * (k % 3));
+            }
+        }
+        __syncthreads();
+        switch (t >> 6) {                                       // (wave-uniform)
+            case 0: stem_tail_taps<0, 13>(acc, gl, ol, it, t & 63); break;
+            case 1: stem_tail_taps<13, 12>(acc, gl, ol, it, t & 63); break;
+            case 2: stem_tail_taps<25, 12>(acc, gl, ol, it, t & 63); break;
+            default: stem_tail_taps<37, 12>(acc, gl, ol, it, t & 63); break;
+        }
+    }
+    __syncthreads();
+    {
+        const int c = t & 63;
+        const float an = prm[384 + c];
+        switch (t >> 6) {
+            case 0: stem_tail_put<0, 13>(acc, gl, c, an); break;
+            case 1: stem_tail_put<13, 12>(acc, gl, c, an); break;
+            case 2: stem_tail_put<25, 12>(acc, gl, c, an); break;
+            default: stem_tail_put<37, 12>(acc, gl, c, an); break;
+        }
+    }
+    __syncthreads();
+    float* po = a.part + ((int64_t)n * gridDim.x + blockIdx.x) * (64 * 64);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int e = t + 256 * i, c = e >> 6, col = e & 63;
+        po[e] = col < 49 ? gl[c * kTailGl + col] : 0.f;
+    }
+    __syncthreads();
+    float* red = gl;                                            // [2][16][64]
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { red[(0 * 16 + slot) * 64 + 4 * cq + c] = s1[c]; red[(1 * 16 + slot) * 64 + 4 * cq + c] = s2[c]; }
+    __syncthreads();
+    if (t < 128) {
+        const int q = t >> 6, c = t & 63;
+        float tot = 0.f;
+        for (int k = 0; k < 16; ++k) tot += red[(q * 16 + k) * 64 + c];
+        atomicAdd((q ? a.o2 : a.o1) + (int64_t)n * 64 + c + stat_rep(), (double)tot);      // (db_flush_kernel: norm0's dbeta / dgamma)
+    }
+}
+
+// stem_moments_kernel: R_n and S_n of one stream's image over tiles of 16 x 16 stem pixels, whose 37 x 37 image pixels sit in LDS.
+// The 49 x 49 matrix R is symmetric: its tap ROWS pair up into 28 blocks (ra <= rb) of 7 x 7 products, and seven more blocks
+// (ra, a row {1, 0, ..}) carry S in their first column - thread = (one of 7 pixel slices, block), 49 fp32 accumulators, 14 LDS reads per
+// 49 multiply-adds.  A workgroup sums its slices in a fixed order and leaves 35 x 49 floats; stem_moments_sum_kernel adds the
+// workgroups of a stream in fp64.  (pitch 39 = 7 mod 32: the 7 rows x 2 slices a half-wave reads lie on 14 banks)
+constexpr int kMomT = 16, kMomI = 2 * kMomT + 5, kMomPitch = 39, kMomJobs = 35, kMomSlices = 7, kMomVals = kMomJobs * 49;
+struct StemMomArgs {
+    const float* img; Plane pi; Plane ps;                     // one-channel image [n][pi.HWp]; the stem plane
+    float* part;                                             // [n][gridDim.x][kMomVals]
+    int tiles_x, n_tiles, tiles_per_wg;
+};
+__host__ __device__ __forceinline__ int stem_mom_block(int ra, int rb) { return ra * 7 - ra * (ra - 1) / 2 + (rb - ra); }      // ra <= rb < 7
+
+static __global__ __launch_bounds__(256) void stem_moments_kernel(const StemMomArgs a) {
+    __shared__ float it[kMomI * kMomPitch + 8];
+    __shared__ float red[kMomVals];
+    const int n = blockIdx.y, t = threadIdx.x;
+    const int slice = t / kMomJobs, job = t - slice * kMomJobs;      // (threads 245..255 only load)
+    int ra = 0, rb = 7;
+    if (job >= 28) ra = job - 28;
+    else {
+        int j = job;
+        while (j >= 7 - ra) { j -= 7 - ra; ++ra; }
+        rb = ra + j;
+    }
+    float acc[7][7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i)
+#pragma unroll
+        for (int j = 0; j < 7; ++j) acc[i][j] = 0.f;
+    if (t < 8) it[kMomI * kMomPitch + t] = t == 0 ? 1.f : 0.f;
+    const float* img = a.img + (int64_t)n * a.pi.HWp;
+    const int tile0 = blockIdx.x * a.tiles_per_wg, tile1 = min(tile0 + a.tiles_per_wg, a.n_tiles);
+    for (int tile = tile0; tile < tile1; ++tile) {
+        const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+        const int y0 = ty * kMomT, x0 = tx * kMomT;
+        constexpr int kImg = kMomI * kMomI, kImgLoads = (kImg + 255) / 256;
+        float iv[kImgLoads];
+#pragma unroll
+        for (int j = 0; j < kImgLoads; ++j) {
+            const int idx = t + 256 * j, r = idx / kMomI, cc = idx - r * kMomI;
+            const int y = 2 * y0 - 3 + r, x = 2 * x0 - 3 + cc;
+            const bool in = idx < kImg && (unsigned)y < (unsigned)a.pi.H && (unsigned)x < (unsigned)a.pi.W;
+            iv[j] = img[in ? y * a.pi.W + x : 0];
+            if (!in) iv[j] = 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < kImgLoads; ++j) {
+            const int idx = t + 256 * j, r = idx / kMomI, cc = idx - r * kMomI;
+            if (idx < kImg) it[r * kMomPitch + cc] = iv[j];
+        }
+        __syncthreads();
+        if (slice < kMomSlices) {
+            for (int p = slice; p < kMomT * kMomT; p += kMomSlices) {
+                const int ly = p >> 4, lx = p & 15;
+                if (y0 + ly >= a.ps.H || x0 + lx >= a.ps.W) continue;
+                const float* pa = it + (2 * ly + ra) * kMomPitch + 2 * lx;
+                const float* pb = rb < 7 ? it + (2 * ly + rb) * kMomPitch + 2 * lx : it + kMomI * kMomPitch;
+                float av[7], bv[7];
+#pragma unroll
+                for (int i = 0; i < 7; ++i) { av[i] = pa[i]; bv[i] = pb[i]; }
+#pragma unroll
+                for (int i = 0; i < 7; ++i)
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
+            }
+        }
+    }
+    float tot[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int s = 0; s < kMomSlices; ++s) {
+        __syncthreads();
+        if (slice == s) {
+#pragma unroll
+            for (int i = 0; i < 7; ++i)
+#pragma unroll
+                for (int j = 0; j < 7; ++j) red[job * 49 + i * 7 + j] = acc[i][j];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            const int e = t + 256 * i;
+            if (e < kMomVals) tot[i] += red[e];
+        }
+    }
+    float* po = a.part + ((int64_t)n * gridDim.x + blockIdx.x) * kMomVals;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        const int e = t + 256 * i;
+        if (e < kMomVals) po[e] = tot[i];
+    }
+}
+
+// stem_moments_sum_kernel: the workgroups' partials of a stream in fp64, unfolded for the combine: mom[n] = 50 rows of 49 - row u < 49 is
+// R_n[u][.] (both triangles), row 49 is S_n.
+constexpr int kMomRows = 50, kMomOut = kMomRows * 49;
+static __global__ void stem_moments_sum_kernel(const float* part, int groups, double* mom) {      // mom [n][kMomOut]
+    const int n = blockIdx.y, o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= kMomOut) return;
+    const int u = o / 49, t = o - u * 49, uy = u / 7, ux = u - uy * 7, ty = t / 7, tx = t - ty * 7;
+    const int e = u == 49 ? (28 + ty) * 49 + tx * 7
+                          : uy <= ty ? stem_mom_block(uy, ty) * 49 + ux * 7 + tx : stem_mom_block(ty, uy) * 49 + tx * 7 + ux;
+    double s = 0.0;
+    for (int g = 0; g < groups; ++g) s += (double)part[((int64_t)n * groups + g) * kMomVals + e];
+    mom[(int64_t)n * kMomOut + o] = s;
+}
+
+// stem_combine_kernel: dW0[c, t] += sum_n ( b_nc * sum_u w[c, u] * R_n[u, t] + c_nc * S_n[t] ) in fp64, to all three input channels
+// (behind the reduce of stem_tail_kernel's partial tiles on the same stream).  a | q1 | mean | k are formed exactly as
+// BwdWeightP::init_params forms them for its operand a * ((dy - q1) - (x - mean) * k).  Workgroup = channel c: the sum over
+// (stream, row of mom) is one dot product of ns * 50 terms per tap, cut into four fixed quarters (thread = (tap, quarter)).
+struct StemCombineArgs {
+    const double* mom; const float* w0;                      // moments [n][kMomOut]; conv0's master weight [64][3][49]
+    const double* ssum; const double* ssq; const double* s1; const double* s2;      // stem stats and norm0's backward sums [n][64]
+    const float* gamma; float eps; int HW; int ns;
+    float* dw;                                               // [64][3][49]
+};
+static __global__ __launch_bounds__(256) void stem_combine_kernel(const StemCombineArgs a) {
+    extern __shared__ double cmb[];                          // coef [ns][50] | red [4][64]
+    double* coef = cmb;
+    double* red = cmb + a.ns * kMomRows;
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const double inv = 1.0 / (double)a.HW;
+    for (int n = tid; n < a.ns; n += 256) {
+        float mean, invstd;
+        bn_moments(a.ssum, a.ssq, (int64_t)n * 64 + c, inv, a.eps, mean, invstd);
+        const float q1 = (float)(stat_get(a.s1, (int64_t)n * 64 + c) * inv);
+        const float q2 = (float)(stat_get(a.s2, (int64_t)n * 64 + c) * inv);
+        const float an = a.gamma[c] * invstd, kk = invstd * q2;
+        coef[n * kMomRows + 48] = -(double)an * (double)kk;                                        // b_nc: times w[c, u] into slots 0..48 below
+        coef[n * kMomRows + 49] = (double)an * ((double)kk * (double)mean - (double)q1);           // c_nc
+    }
+    __syncthreads();
+    for (int k = tid; k < a.ns * 49; k += 256) {
+        const int n = k / 49, u = k - n * 49;
+        if (u == 48) continue;
+        coef[n * kMomRows + u] = coef[n * kMomRows + 48] * ((double)a.w0[c * 147 + u] + (double)a.w0[c * 147 + 49 + u] + (double)a.w0[c * 147 + 98 + u]);
+    }
+    __syncthreads();
+    for (int n = tid; n < a.ns; n += 256) coef[n * kMomRows + 48] *= (double)a.w0[c * 147 + 48] + (double)a.w0[c * 147 + 97] + (double)a.w0[c * 147 + 146];
+    __syncthreads();
+    const int t = tid & 63, qt = tid >> 6, K = a.ns * kMomRows;
+    const int k0 = (int)((int64_t)K * qt / 4), k1 = (int)((int64_t)K * (qt + 1) / 4);
+    double v0 = 0.0, v1 = 0.0;
+    if (t < 49) {
+        int k = k0;
+        for (; k + 1 < k1; k += 2) {
+            v0 += coef[k] * a.mom[(int64_t)k * 49 + t];
+            v1 += coef[k + 1] * a.mom[(int64_t)(k + 1) * 49 + t];
+        }
+        if (k < k1) v0 += coef[k] * a.mom[(int64_t)k * 49 + t];
+    }
+    red[qt * 64 + t] = v0 + v1;
+    __syncthreads();
+    if (tid < 49) {
+        const float v = (float)((red[tid] + red[64 + tid]) + (red[128 + tid] + red[192 + tid]));
+        for (int cc = 0; cc < 3; ++cc) a.dw[c * 147 + cc * 49 + tid] += v;
     }
 }
 

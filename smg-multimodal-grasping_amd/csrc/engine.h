@@ -166,7 +166,14 @@ struct smg_engine {
     // two kernel families for cross-checks - bit 0: dense-layer 3x3 convolutions through the generic implicit GEMM instead of the LDS-halo
     // kernels; bit 1: the 1x1 forward of the small planes through the generic kernel instead of the wave-specialised one
     // bit 2: the 1x1 weight gradient through the generic kernel instead of the wave-specialised one (wsw.cuh)
-    bool generic3x3 = false, generic_c1 = false, generic_w1 = false;
+    // bit 3 (value 8): pool0's backward and conv0's weight gradient at stem resolution (pool0_bwd_kernel + BwdWeightP over DY0) instead of the
+    // pooled-resolution tail (elem.cuh: stem_tail_kernel), which serves precision mode 0 with the one-channel stem in calls of more than
+    // four streams or under "deterministic" (backward.hip)
+    bool generic3x3 = false, generic_c1 = false, generic_w1 = false, stem_plane_tail = false;
+    // The pooled-resolution tail: the raw stem value at each argmax ([streams][p_blk[0].HWp][64], written by pool0_kernel - it lives at
+    // the start of DY0, which that tail never writes and the stem-resolution one only writes after the forward's values are of no use
+    // to it), the image moments' per-workgroup partials and their fp64 sums (R_n | S_n, [streams][kMomOut])
+    float* stemv = nullptr; float* mom_part = nullptr; double* mom = nullptr; int mom_groups = 0;
     int dbg_stop = -1;         // smg_engine_set_option("debug_stop", block * 100 + layer) (0-based): the backward returns behind that dense layer's
                                // launches (block * 100 + 50: in front of the block's first layer) - the GEMM-level tests read the ring
                                // slots, DY2 and G' at that point (smg_debug_read); -1 = off
@@ -177,6 +184,12 @@ struct smg_engine {
     double prof_ms[5][K_COUNT] = {}; int64_t prof_n[5][K_COUNT] = {}; double prof_flops[5][K_COUNT] = {}; double prof_bytes[5][K_COUNT] = {}; int prof_stage = -1;
     int launch_rc = 0;         // error code of the first launch launch_kernel refused since the last walk_status (smg_last_error() says why)
 };
+
+// stem_moments_kernel's cut of the stem plane: tiles of kMomT x kMomT pixels, runs of 8 tiles per workgroup
+constexpr int kMomTilesPerWg = 8;
+static inline int stem_mom_tiles_x(const Plane& ps) { return (ps.W + kMomT - 1) / kMomT; }
+static inline int stem_mom_tiles(const Plane& ps) { return stem_mom_tiles_x(ps) * ((ps.H + kMomT - 1) / kMomT); }
+static inline int stem_mom_groups(const Plane& ps) { return (stem_mom_tiles(ps) + kMomTilesPerWg - 1) / kMomTilesPerWg; }
 
 static Plane make_plane(int H, int W) {
     // rows per stream: a multiple of 64 (tiles and scale blocks never straddle two streams) - of 128 on the big planes, so that the

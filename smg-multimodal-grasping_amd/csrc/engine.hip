@@ -27,12 +27,16 @@ static int engine_build(smg_engine* e) {
 
     if (getenv("SMG_SERIALIZE")) e->serialize = true;        // profiling runs: serialised from the first launch (bench.py --serialize)
     const int cross = getenv("SMG_CROSSCHECK") ? atoi(getenv("SMG_CROSSCHECK")) : 0;
-    e->generic3x3 = cross & 1; e->generic_c1 = cross & 2; e->generic_w1 = cross & 4;
+    e->generic3x3 = cross & 1; e->generic_c1 = cross & 2; e->generic_w1 = cross & 4; e->stem_plane_tail = cross & 8;
 
     ALLOC(e->img4, (int64_t)NS * e->p_img.HWp * 4);
     ALLOC(e->stem, (int64_t)NS * e->p_stem.HWp * 64);
     ALLOC(e->DY0, (int64_t)NS * e->p_stem.HWp * 64);
     ALLOC(e->argmax, (int64_t)NS * e->p_blk[0].HWp * 64);
+    e->stemv = e->DY0;      // (engine.h)
+    e->mom_groups = stem_mom_groups(e->p_stem);
+    ALLOC(e->mom_part, (int64_t)NS * e->mom_groups * kMomVals);
+    ALLOC(e->mom, (int64_t)NS * kMomOut);
     int64_t bt_total = 0;
     for (int b = 0; b < 4; ++b) {
         ALLOC(e->X[b], (int64_t)NS * e->p_blk[b].HWp * kBlockCtot[b]);
@@ -390,7 +394,7 @@ void smg_engine_destroy(smg_engine* e) {
     (void)hipDeviceSynchronize();
     void* ptrs[] = {e->img4, e->stem, e->DY0, e->argmax, e->X[0], e->X[1], e->X[2], e->X[3], e->G[0], e->G[1], e->G[2], e->G[3],
                     e->Bt, e->DY2, e->part, e->F, e->DF, e->H1, e->DH1, e->fstat, e->bstat, e->dbscr, e->d_dbseg, e->asc, e->d_asc, e->gamax, e->packed_u, e->packed_f, e->stab, e->d_pack, e->d_bnupd,
-                    e->d_stage, e->scene_val, e->scene_idx};
+                    e->d_stage, e->scene_val, e->scene_idx, e->mom_part, e->mom};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->dbg_gsnap) (void)hipFree(e->dbg_gsnap);
     step_graph_drop(e);

@@ -143,6 +143,9 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
             a.x1 = xs(0); a.ldx = kBlockCtot[0]; a.po = e->p_blk[0];
             a.dsum = st_off(fsum(e, e->st_X[0]), kBlockCtot[0]); a.dsq = st_off(fsq(e, e->st_X[0]), kBlockCtot[0]); a.dstride = kBlockCtot[0];
             a.argmax = e->argmax + (int64_t)s0 * e->p_blk[0].HWp * 64;
+            // the pooled-resolution tail of the backward (one-channel stem, mode 0) reads the stem values at the argmax, not the plane
+            // (stored whatever the number of streams: "deterministic" may be set between this forward and its backward)
+            a.stemv = (stem1 && e->prec == 0 && !e->stem_plane_tail) ? e->stemv + (int64_t)s0 * e->p_blk[0].HWp * 64 : nullptr;
             PREC_DISPATCH(e, launch_kernel(e, pool0_kernel<PREC>, dim3(e->p_blk[0].HWp / 64, ns), dim3(256), 0, cs, K_OTHER, 0, 0, false, a));
         }
         for (int b = 0; b < 4; ++b) {

@@ -23,7 +23,7 @@ for e in seg:
     elif 'prep_rotate' in n: ph = 'fwd stem'
     elif 'feat_kernel' in n: ph = 'head'
     elif 'value_bwd' in n: ph = 'bwd head'
-    elif 'pool0_bwd' in n: ph = 'bwd stem'
+    elif 'pool0_bwd' in n or 'stem_tail' in n or 'stem_combine' in n: ph = 'bwd stem'
     elif 'adam' in n: ph = 'adam'
     if ph and (not marks or marks[-1][0] != ph):
         if ph not in [m[0] for m in marks]: marks.append((ph, e[0]))

@@ -36,6 +36,8 @@ def kclass(name):
     if "conv3x3_halo_fwd" in name: return "conv3x3_fwd"
     if "conv3x3_halo_dgrad" in name: return "conv3x3_dgrad"
     if "conv3x3_halo_wgrad" in name: return "conv3x3_wgrad"
+    if "stem_tail_kernel" in name: return "stem_wgrad"       # conv0's weight gradient from the pooled pixels (with pool0's backward inside)
+    if "stem_moments" in name or "stem_combine" in name: return "elementwise"      # its image moments and the fp64 combine
     if "reduce_partials" in name: return "elementwise"       # (one launch reduces a layer's 3x3 AND 1x1 partial tiles: bench.py profiles it as element-wise too)
     if "FwdConvP<" in name:
         a = targs(name, "FwdConvP")           # MODE, PREC, F32IO
