@@ -42,7 +42,7 @@ typedef struct smg_engine smg_engine;
 const char* smg_last_error(void);
 /* ABI revision of this header: a binding must refuse a library whose smg_version() differs (stale .so) and should
  * compare its own struct sizes with smg_abi_struct_bytes(0 = smg_batch, 1 = smg_net, 2 = smg_adam) before the first call. */
-#define SMG_ABI_VERSION 8
+#define SMG_ABI_VERSION 9
 int smg_version(void);
 int smg_abi_struct_bytes(int which);
 
@@ -169,7 +169,7 @@ int smg_loss_map_ce(smg_engine* e, const float* q_dev, const float* label_dev, i
                     float* loss_dev, float* dq_dev, void* stream);
 
 /* ---- dense Q maps in the scene frame ----------------------------------------------------------------------------------------
- * A dense Q map lives in the ROTATED frame of its rotation, one value per 32 input pixels.  These three entry points undo
+ * A dense Q map lives in the ROTATED frame of its rotation, one value per 32 input pixels.  These four entry points undo
  * F.affine_grid / F.grid_sample (code/models.py:372-382) and the head's 20x20 window geometry, so that a caller can read, pick and
  * train Q values at HEIGHTMAP pixels.  For a heightmap of side hm (code/trainer.py:165-173): pad = int((ceil(2 hm sqrt(2) / 32) * 32
  * - 2 hm) / 2), S = 2 hm + 2 pad (the engine's input size), OH = OW = S / 32 - 19 (the engine's).  Coordinates are (x = column,
@@ -188,8 +188,8 @@ int smg_loss_map_ce(smg_engine* e, const float* q_dev, const float* label_dev, i
  * affine_host: 6 float32 per map / pair, row-major 2x3 as in smg_batch.stream_affine; the translation column must be zero.
  * map_stride: element distance between consecutive maps in q_dev - OH * OW for the output of a one-channel head, 3 * OH * OW to
  * address one class plane of a [R][3][OH][OW] tensor.
- * All three return -22 and launch nothing when hm_size does not pad to the engine's S, when the map is 1 x 1 (S = 640: no extent
- * to interpolate over), and for n_maps < 1 / K < 1. */
+ * All four return -22 and launch nothing when hm_size does not pad to the engine's S, when the map is 1 x 1 (S = 640: no extent
+ * to interpolate over), and for n_maps < 1 / K < 1 / n_pairs < 1. */
 
 /* out_dev float32 [n_maps][hm_size][hm_size]: every map in the scene frame, -inf at invalid pixels. */
 int smg_scene_maps(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host,
@@ -214,6 +214,26 @@ int smg_scene_argmax(smg_engine* e, const float* q_dev, int64_t map_stride, int 
 int smg_loss_scene(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs, int K,
                    const int* pixels_dev, const float* label_dev, const float* weight_dev,
                    float* loss_dev, float* dq_dev, void* stream);
+
+/* smg_loss_scene with a whole label IMAGE per pair instead of K listed pixels, one-channel heads only (head_out != 1 returns -22):
+ * q and dq are [n_pairs][1][OH][OW]; label_dev, weight_dev float32 [n_pairs][hm_size][hm_size] (weight_dev NULL = all ones).
+ * Every heightmap pixel that is valid in its pair's rotation (step 6) and whose weight is not exactly 0 is a point, with v the
+ * interpolated value there (double, not rounded) and smg_loss_scene's Huber:
+ *     loss[j]       = sum over those pixels of w * huber(v - label)
+ *     dq[j][oy][ox] = sum over those pixels of w * huber'(v - label) * (bilinear weight of (oy, ox) at that pixel)
+ * A pixel that is invalid in the pair's rotation contributes nothing and is no error (a whole image always covers such pixels); a
+ * weight of exactly 0 masks its pixel; the label of a masked or invalid pixel is never read into the arithmetic (a NaN there is
+ * harmless), nor is the weight of an invalid pixel.  Like smg_loss_scene the call takes any 2x2 part (the box of an element is
+ * found with the inverse of A^T; a matrix without a usable inverse makes every workgroup walk the whole heightmap: slow, same result).
+ * Parallel over the map, not serial in the pixels: one workgroup per (pair, map
+ * element) gathers the pixels of the heightmap box around that element in a fixed order and reduces by a fixed tree; the loss is
+ * summed per element (each pixel counted at its corner element (y0, x0)) into a scratch the engine owns and reduced by a second
+ * launch in fixed order.  Accumulated in double, rounded to float32 once, every element of dq written once (zeros included), no
+ * atomics: identical calls are bit-identical, and a pair's result does not depend on the other pairs of the call.
+ * Returns -22 and launches nothing for head_out != 1, the geometry refusals above, n_pairs < 1 and an affine with a translation.
+ * Marks the saved forward "dense dq" exactly as smg_loss_scene does. */
+int smg_loss_scene_map(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs,
+                       const float* label_dev, const float* weight_dev, float* loss_dev, float* dq_dev, void* stream);
 
 /* ---- the reactive net's class maps in the scene frame --------------------------------------------------------------------------
  * The same three services for a 3-class head (head_out != 3 returns -22 and launches nothing): q_dev is [n_maps][3][OH][OW], the
@@ -295,7 +315,7 @@ int smg_engine_set_precision(smg_engine* e, int precision);
  * output elements it feeds, skips zero dq and adds its share of the 20x20 weight gradient with fp32 atomics; right for the single
  * element smg_loss mode 0 sets.  2: the dense form - a data pass over the 400 taps and a weight pass that owns every element of
  * the weight gradient (no atomics, pairs in index order: bit-identical between identical calls); right for a whole map.
- * 0 (default): the dense form after smg_loss_map / smg_loss_map_ce / smg_loss_scene / smg_loss_scene_ce, else the per-element form.  A 3-class head follows the same
+ * 0 (default): the dense form after smg_loss_map / smg_loss_map_ce / smg_loss_scene / smg_loss_scene_map / smg_loss_scene_ce, else the per-element form.  A 3-class head follows the same
  * rule as a one-channel head (its dense form loops over the three output channels).  smg_train_step_graph always runs the
  * per-element form (its loss is smg_loss).
  * "serialize" (0 / 1): every kernel on the caller's stream in issue order instead of two concurrent chains (profiling).

@@ -1,7 +1,8 @@
 // scene.cuh - dense Q maps in the SCENE frame: every rotation's [OH][OW] map rotated back and bilinearly upsampled onto the
 // heightmap's pixel grid (smg_scene_maps), the best (rotation, heightmap pixel) without materialising those maps
-// (smg_scene_argmax), and the Huber loss on labelled heightmap pixels with its gradient on the map (smg_loss_scene); further down
-// the same three for the class logits of a 3-class head (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce).
+// (smg_scene_argmax), and the Huber loss on labelled heightmap pixels with its gradient on the map (smg_loss_scene: K listed pixels;
+// smg_loss_scene_map: a whole label image and weight image); further down the first three for the class logits of a 3-class head
+// (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce).
 //
 // Geometry (include/smg_hip.h has the derivation), all in double, coordinates (x = column, y = row):
 //   heightmap pixel (iy, ix) -> centre of its 2x2 block of the padded input   x = 2 ix + 0.5 + pad
@@ -215,6 +216,96 @@ static __global__ __launch_bounds__(256) void loss_scene_kernel(const float* q, 
     if (t == 0) loss[j] = (float)red[0];
     float* dj = dq + (int64_t)j * P;
     for (int i = t; i < P; i += 256) dj[i] = (float)sacc[i];
+}
+
+// smg_loss_scene_map: loss_scene_kernel's Huber with a whole [hm][hm] label image and weight image per pair instead of K listed
+// pixels - every pixel that is valid in the pair's rotation and whose weight is not exactly 0 is a point:
+//     loss[j] = sum_pixels w huber(v - label)      dq[j][oy][ox] = sum_pixels w huber'(v - label) * (bilinear weight of (oy, ox) at the pixel)
+// Gather by map element: one workgroup owns one (pair, oy, ox) - blockIdx.x = oy * OW + ox, blockIdx.y = pair of this launch.  Only
+// pixels whose corner (y0, x0) lies in {oy - 1, oy} x {ox - 1, ox} touch that element: they lie at map coordinates
+// [ox - 1, ox + 1] x [oy - 1, oy + 1], clipped to the map.  The four corners of that square go back through the chain with the
+// inverse of A^T (u = A^-T p, whatever the 2x2 matrix is: scene_point asks for no rotation); the heightmap bounding box of the
+// four images, widened by one pixel per side and clipped to the heightmap, holds every such pixel (for a rotation about 34 x 34 at
+// a multiple of a quarter turn, 46 x 46 at 45 degrees).  A matrix without a usable inverse (determinant 0, not finite, or below
+// 1e-6 of the squared norm) maps whole lines of pixels onto one map point: the box is then the whole heightmap.  Thread t takes pixels t, t + 256, ... of the box in
+// row-major order, runs scene_point on each, keeps the valid ones that touch the element, and adds in double; a fixed tree over
+// the 256 threads follows.  The weight is read only under a valid touching pixel, the label only where the weight is not 0, the
+// map's four corners from global memory (the map sits in L2).  No atomics, every element of dq written once, rounded once:
+// identical calls are bit-identical, and a pair's results do not depend on which launch carries it.
+// The loss counts a pixel at its HOME element (y0, x0) only; the per-element sums go to `lpart` ([pairs of this launch][OH * OW]
+// doubles, every slot written) for loss_scene_map_reduce_kernel.
+static __global__ __launch_bounds__(256) void loss_scene_map_kernel(const float* q, int pair0, const SceneAffine aff, const SceneGeo g,
+                                                                    const float* label, const float* weight, double* lpart, float* dq) {
+    __shared__ double racc[256], rloss[256];
+    const int t = threadIdx.x, m = blockIdx.y, j = pair0 + m, el = blockIdx.x;
+    const int P = g.OH * g.OW;
+    const int oy = el / g.OW, ox = el - oy * g.OW;
+    const float* qj = q + (int64_t)j * P;
+    const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
+    // the box: the map square [ox - 1, ox + 1] x [oy - 1, oy + 1] (clipped) pushed back onto the heightmap
+    const double sm1 = (double)(g.S - 1);
+    const double qx0 = (double)max(ox - 1, 0), qx1 = (double)min(ox + 1, g.OW - 1), qy0 = (double)max(oy - 1, 0), qy1 = (double)min(oy + 1, g.OH - 1);
+    const double det = a00 * a11 - a10 * a01;                 // of A^T = [a00 a10; a01 a11], whose inverse is [a11 -a10; -a01 a00] / det
+    const bool inv_ok = fabs(det) > 1e-6 * (a00 * a00 + a01 * a01 + a10 * a10 + a11 * a11) && fabs(det) < INFINITY;      // (false for a NaN)
+    const double rdet = inv_ok ? 1.0 / det : 0.0;
+    double lox = INFINITY, hix = -INFINITY, loy = INFINITY, hiy = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const double qx = (c & 1) ? qx1 : qx0, qy = (c & 2) ? qy1 : qy0;
+        const double pxn = 2.0 * (32.0 * qx + 319.5) * g.inv_sm1 - 1.0, pyn = 2.0 * (32.0 * qy + 319.5) * g.inv_sm1 - 1.0;
+        const double ux = (a11 * pxn - a10 * pyn) * rdet, uy = (a00 * pyn - a01 * pxn) * rdet;            // A^-T p
+        const double fx = ((ux + 1.0) * 0.5 * sm1 - 0.5 - (double)g.pad) * 0.5, fy = ((uy + 1.0) * 0.5 * sm1 - 0.5 - (double)g.pad) * 0.5;
+        lox = fmin(lox, fx); hix = fmax(hix, fx); loy = fmin(loy, fy); hiy = fmax(hiy, fy);
+    }
+    // (clamped in double first: the conversions below stay in range whatever the matrix holds)
+    const double top = (double)g.hm;
+    if (!inv_ok) { lox = loy = 0.0; hix = hiy = top; }
+    const int bx0 = max((int)floor(fmin(fmax(lox, 0.0), top)) - 1, 0), bx1 = min((int)ceil(fmin(fmax(hix, -2.0), top)) + 1, g.hm - 1);
+    const int by0 = max((int)floor(fmin(fmax(loy, 0.0), top)) - 1, 0), by1 = min((int)ceil(fmin(fmax(hiy, -2.0), top)) + 1, g.hm - 1);
+    const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
+    const int n = bw > 0 && bh > 0 ? bw * bh : 0;             // (<= hm^2 < 2^31: checked by the host)
+    double acc = 0.0, lsum = 0.0;
+    for (int i = t; i < n; i += 256) {
+        const int ry = i / bw;
+        const int iy = by0 + ry, ix = bx0 + (i - ry * bw);
+        const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
+        if (!p.valid) continue;
+        const int dy = oy - p.y0, dx = ox - p.x0;
+        if ((unsigned)dy > 1u || (unsigned)dx > 1u) continue;
+        const int64_t at = ((int64_t)j * g.hm + iy) * g.hm + ix;
+        const double w = weight ? (double)weight[at] : 1.0;
+        if (w == 0.0) continue;
+        const double d = scene_interp(p, qj, g.OW) - (double)label[at];
+        double l, gr;
+        if (fabs(d) < 1.0) { l = 0.5 * (d * d); gr = d; }
+        else { l = fabs(d) - 0.5; gr = d > 0.0 ? 1.0 : -1.0; }
+        if (dy == 0 && dx == 0) lsum += w * l;
+        const double wy = dy ? p.fy : 1.0 - p.fy, wx = dx ? p.fx : 1.0 - p.fx;
+        acc += (w * gr) * (wy * wx);
+    }
+    racc[t] = acc; rloss[t] = lsum;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) { racc[t] += racc[t + s]; rloss[t] += rloss[t + s]; }
+        __syncthreads();
+    }
+    if (t == 0) { dq[(int64_t)j * P + el] = (float)racc[0]; lpart[(int64_t)m * P + el] = rloss[0]; }
+}
+
+// The second launch of smg_loss_scene_map: one workgroup per pair of the launch sums its P per-element loss partials - thread t
+// takes slots t, t + 256, ... in that order, then the fixed tree - and rounds to fp32 once.
+static __global__ __launch_bounds__(256) void loss_scene_map_reduce_kernel(const double* lpart, int P, int pair0, float* loss) {
+    __shared__ double red[256];
+    const int t = threadIdx.x, m = blockIdx.x;
+    double s = 0.0;
+    for (int i = t; i < P; i += 256) s += lpart[(int64_t)m * P + i];
+    red[t] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (t < k) red[t] += red[t + k];
+        __syncthreads();
+    }
+    if (t == 0) loss[pair0 + m] = (float)red[0];
 }
 
 // ---- the reactive net's three class planes in the scene frame (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce) ----

@@ -36,7 +36,7 @@ class SmgAdam(C.Structure):
                 ("step_trunk", C.c_int), ("step_head", C.c_int)]
 
 
-ABI_VERSION = 8     # SMG_ABI_VERSION of include/smg_hip.h this binding was written against
+ABI_VERSION = 9     # SMG_ABI_VERSION of include/smg_hip.h this binding was written against
 
 _lib = None
 
@@ -82,6 +82,8 @@ def lib():
     L.smg_scene_argmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smg_loss_scene_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
     L.smg_scene_class_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.smg_scene_class_argmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene_ce.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -115,7 +117,7 @@ EXPORTS = (
     "smg_last_error", "smg_version", "smg_abi_struct_bytes", "smg_engine_set_option", "smg_layout_count", "smg_layout_param_floats", "smg_layout_buffer_floats",
     "smg_layout_nbt_count", "smg_layout_entry", "smg_layout_trunk_range", "smg_layout_head_range",
     "smg_engine_create", "smg_engine_destroy", "smg_engine_workspace_bytes", "smg_engine_geometry",
-    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_argmax", "smg_loss_scene", "smg_scene_class_maps", "smg_scene_class_argmax", "smg_loss_scene_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
+    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_argmax", "smg_loss_scene", "smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_argmax", "smg_loss_scene_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
     "smg_profile_enable", "smg_profile_kinds", "smg_profile_kind_name", "smg_profile_read", "smg_profile_read_bytes",
 )
 
@@ -284,6 +286,13 @@ class Engine(object):
         `weights` None = all ones.  Marks the saved forward so that its backward runs the dense head form."""
         a, p = self._affines(affine, n_pairs)
         check(lib().smg_loss_scene(self.h, q, p, int(hm_size), int(n_pairs), int(K), pixels, labels, weights, loss_out, dq_out, stream))
+
+    def loss_scene_map(self, q, affine, hm_size, n_pairs, label_maps, weight_maps, loss_out, dq_out, stream):
+        """smg_loss_scene_map: the weighted Huber on a whole label image per pair (`label_maps` / `weight_maps` device float32
+        [n_pairs, hm_size, hm_size], `weight_maps` None = all ones), dq on the map; pixels without a window in their pair's
+        rotation contribute nothing.  Marks the saved forward so that its backward runs the dense head form."""
+        a, p = self._affines(affine, n_pairs)
+        check(lib().smg_loss_scene_map(self.h, q, p, int(hm_size), int(n_pairs), label_maps, weight_maps, loss_out, dq_out, stream))
 
     def scene_class_maps(self, q, n_maps, affine, hm_size, cls, out, stream):
         """smg_scene_class_maps: the class probabilities of the n_maps logit maps at `q` (device, [n_maps, 3, OH, OW]) in the scene

@@ -675,6 +675,48 @@ class Trainer(object):
         self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
         return (loss, q) if return_q else loss
 
+    def train_batch_scene_maps(self, depth_heightmap, m_depth_heightmap, style, rotations, label_maps, weight_maps=None, grad_sync=None,
+                               return_q=False):
+        """train_batch_scene_pixels with a whole label IMAGE per sample: `label_maps` / `weight_maps` are host arrays
+        [n_samples, hm, hm] in heightmap pixels, scene-major (`weight_maps` None = all ones, a weight of 0 masks its pixel, the label
+        under it may be anything).  loss_j = sum over the pixels that have a window of the head in sample j's rotation
+        (scene_to_map's `valid`) of w * Huber(v - label), v the bilinear interpolation of the sample's Q map there
+        (smg_loss_scene_map).  Pixels without a window contribute nothing and raise nothing: a whole image always covers such
+        pixels.  The gradient of the SUM of the losses goes back in one backward pass (dense head form), then ONE Adam step.
+        Scenes, rotations and `grad_sync` as in train_batch_scene_pixels.  Reinforcement method only.  Returns the loss vector
+        (and q [n_samples, 1, OH, OW] if asked)."""
+        import models
+        _, _, side = self._require_scene("train_batch_scene_maps", depth_heightmap)
+        per_scene = np.ndim(depth_heightmap) == 3
+        flat_rots = [r for rs in rotations for r in rs] if per_scene else list(rotations)
+        n = len(flat_rots)
+        hm = int(np.shape(depth_heightmap)[-1])
+        for name, maps in (("label_maps", label_maps), ("weight_maps", weight_maps)):
+            if (maps is not None or name == "label_maps") and (maps is None or tuple(np.shape(maps)) != (n, hm, hm)):
+                raise ValueError("%s must be [%d samples, %d, %d] for a %d^2 heightmap, got %s"
+                                 % (name, n, hm, hm, hm, None if maps is None else tuple(np.shape(maps))))
+        num = self.model.gnum_rotations
+        rots = [0 if style == 2 else int(r) for r in flat_rots]
+        model = self.model
+        self.optimizer.zero_grad()
+        model._require_gpu()
+        dev = model._flat_params.device
+        hmaps, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
+        rots2 = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
+        # (uploaded BEFORE the forward is enqueued, like train_batch_maps' maps)
+        lab_d = torch.as_tensor(np.ascontiguousarray(label_maps, dtype=np.float32), device=dev)
+        wgt_d = None if weight_maps is None else torch.as_tensor(np.ascontiguousarray(weight_maps, dtype=np.float32), device=dev)
+        q = model.run(style, rots2, num, heightmaps=hmaps, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
+        eng, token, trunk_id, head_id = model._saved
+        assert tuple(q.shape) == (n, 1, side, side), (tuple(q.shape), n, side)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        dq = torch.empty_like(q)
+        eng.loss_scene_map(q.data_ptr(), [models.rotation_theta(r, num) for r in rots], hm, n, lab_d.data_ptr(),
+                           None if wgt_d is None else wgt_d.data_ptr(), loss.data_ptr(), dq.data_ptr(), stream)
+        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
+        return (loss, q) if return_q else loss
+
     # ---- dense class maps (reactive method on heightmaps larger than 224^2: three logits per 20x20 window of the feature plane) ---
     def _require_reactive(self, what):
         if self.method != 'reactive':
