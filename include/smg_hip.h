@@ -236,7 +236,7 @@ int smg_loss_scene_map(smg_engine* e, const float* q_dev, const float* affine_ho
                        const float* label_dev, const float* weight_dev, float* loss_dev, float* dq_dev, void* stream);
 
 /* ---- the reactive net's class maps in the scene frame --------------------------------------------------------------------------
- * The same three services for a 3-class head (head_out != 3 returns -22 and launches nothing): q_dev is [n_maps][3][OH][OW], the
+ * The same services for a 3-class head (head_out != 3 returns -22 and launches nothing): q_dev is [n_maps][3][OH][OW], the
  * head output.  The geometry is steps 1-7 above, unchanged.  At a heightmap pixel that is valid in a map's rotation, in double:
  *     z_c = the bilinear interpolation of LOGIT plane c there (c = 0, 1, 2: the same corners and fractions for all three)
  *     P_c = exp(z_c - m) / sum_c' exp(z_c' - m),  m = max_c z_c,  rounded to float32 once.
@@ -245,7 +245,7 @@ int smg_loss_scene_map(smg_engine* e, const float* q_dev, const float* affine_ho
  * (the dense-map form), so picking and training see one and the same function of the head output.  Nothing is special-cased: a
  * NaN, or an inf that produces inf - inf, in any of the twelve corner logits makes all three probabilities NaN, as torch.softmax
  * does in fp64.  An invalid pixel is -inf in every plane, so the argmax rules carry over unchanged.
- * All three return -22 and launch nothing for the geometry refusals above, for n_maps < 1 / K < 1 and for cls out of range. */
+ * All four return -22 and launch nothing for the geometry refusals above, for n_maps < 1 / K < 1 / n_pairs < 1 and for cls out of range. */
 
 /* out_dev float32: cls in {0,1,2} -> [n_maps][hm][hm] = P(class cls); cls == -1 -> [n_maps][3][hm][hm], all three.
  * q_dev is [n_maps][3][OH][OW] (the head output of a 3-class engine). */
@@ -272,6 +272,29 @@ int smg_scene_class_argmax(smg_engine* e, const float* q_dev, int n_maps, const 
  * of LDS (maps beyond 45 x 45).  Marks the saved forward "dense dq" exactly as smg_loss_map_ce does. */
 int smg_loss_scene_ce(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs, int K,
                       const int* pixels_dev, const float* label_dev, float* loss_dev, float* dq_dev, void* stream);
+
+/* smg_loss_scene_ce with a whole class-label IMAGE per pair instead of K listed pixels: q and dq are [n_pairs][3][OH][OW];
+ * label_dev float32 [n_pairs][hm_size][hm_size], class indices as in smg_loss_map_ce.  A heightmap pixel is a point of pair j when
+ * it is valid in the pair's rotation (step 6) and its label is exactly 0 or 1; W_j = the number of points.  Every other pixel -
+ * class 2, NaN, any other value - is "no loss": skipped before a logit is read, whatever the logits under it hold.  A pixel that
+ * is invalid in the pair's rotation contributes nothing and is no error (a whole image always covers such pixels), and its label
+ * is never read into the arithmetic.  With z the three interpolated logits of a point (double, not rounded), m = max z,
+ * e_c = exp(z_c - m), s = e_0 + e_1 + e_2:
+ *     nll     = (log(s) + m) - z_y
+ *     loss[j] = (sum over the points of nll) / W_j      (0 when W_j == 0, not 0/0)
+ *     dq[j][c][oy][ox] = (1 / W_j) sum over the points of (e_c / s - [c == y]) * (bilinear weight of (oy, ox) at the pixel)
+ * summed unnormalised in double, divided by W_j once and rounded to float32 once; W_j == 0 gives dq exactly 0 everywhere.
+ * Parallel over the map like smg_loss_scene_map, whose walk it shares: one workgroup per (pair, map element) gathers the pixels of
+ * the heightmap box around that element in a fixed order (any 2x2 part; a matrix without a usable inverse walks the whole
+ * heightmap) and reduces by a fixed tree; a pixel's nll and count go to its corner element (y0, x0) alone, its gradient share to
+ * every element it touches.  The unnormalised per-element partials (three gradient sums, the loss sum, the count) go to a scratch
+ * the engine owns; a second launch sums loss and count per pair in fixed order and writes loss and all of dq, every element once
+ * (zeros included).  No atomics: identical calls are bit-identical, and a pair's result does not depend on the other pairs of the
+ * call.  No accumulator of the map's size in LDS, so smg_loss_scene_ce's 45 x 45 limit does not apply.
+ * Returns -22 and launches nothing for head_out != 3, the geometry refusals above, n_pairs < 1, n_pairs beyond the engine's
+ * max_pairs and an affine with a translation.  Marks the saved forward "dense dq" exactly as smg_loss_scene_ce does. */
+int smg_loss_scene_map_ce(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs,
+                          const float* label_dev, float* loss_dev, float* dq_dev, void* stream);
 
 /* Backward of the last smg_forward: accumulates (+=) d(sum of losses)/d(param) into
  * net->grads for the trunk and head that forward used.  Replaces loss.backward() at
@@ -315,7 +338,7 @@ int smg_engine_set_precision(smg_engine* e, int precision);
  * output elements it feeds, skips zero dq and adds its share of the 20x20 weight gradient with fp32 atomics; right for the single
  * element smg_loss mode 0 sets.  2: the dense form - a data pass over the 400 taps and a weight pass that owns every element of
  * the weight gradient (no atomics, pairs in index order: bit-identical between identical calls); right for a whole map.
- * 0 (default): the dense form after smg_loss_map / smg_loss_map_ce / smg_loss_scene / smg_loss_scene_map / smg_loss_scene_ce, else the per-element form.  A 3-class head follows the same
+ * 0 (default): the dense form after smg_loss_map / smg_loss_map_ce / smg_loss_scene / smg_loss_scene_map / smg_loss_scene_ce / smg_loss_scene_map_ce, else the per-element form.  A 3-class head follows the same
  * rule as a one-channel head (its dense form loops over the three output channels).  smg_train_step_graph always runs the
  * per-element form (its loss is smg_loss).
  * "serialize" (0 / 1): every kernel on the caller's stream in issue order instead of two concurrent chains (profiling).

@@ -147,8 +147,11 @@ struct smg_engine {
     float* d_affine = nullptr;
     // smg_scene_argmax: one (value, index) partial per workgroup of a launch (kSceneMaps maps x scene_tiles tiles of the largest heightmap this S serves)
     float* scene_val = nullptr; int* scene_idx = nullptr; int scene_tiles = 0;
-    // smg_loss_scene_map: one loss partial per map element of a launch (kSceneMaps pairs x OH x OW doubles)
+    // smg_loss_scene_map / smg_loss_scene_map_ce: one loss partial per map element of a launch (kSceneMaps pairs x OH x OW doubles)
     double* scene_lpart = nullptr;
+    // smg_loss_scene_map_ce on top of scene_lpart: the unnormalised gradient partials ([kSceneMaps pairs][3][OH * OW] doubles) and the point
+    // counts ([kSceneMaps pairs][OH * OW] ints) per map element of a launch
+    double* scene_gpart = nullptr; int* scene_cnt = nullptr;
     // batch description staging: one pinned ping-pong host block -> one device block per forward
     int* d_stage = nullptr; int* h_stage[2] = {}; hipEvent_t ev_stage[2] = {}; int stage_ints = 0, stage_turn = 0;
     int so_image = 0, so_rot = 0, so_pa = 0, so_pb = 0, so_seq_t = 0, so_seq_h = 0, so_uptr = 0, so_upair = 0, so_uslot = 0, so_aff = 0, so_ma = 0, so_mb = 0, so_adam = 0;

@@ -60,6 +60,8 @@ static int engine_build(smg_engine* e) {
     ALLOC(e->scene_val, (int64_t)kSceneMaps * e->scene_tiles);
     ALLOC(e->scene_idx, (int64_t)kSceneMaps * e->scene_tiles);
     ALLOC(e->scene_lpart, (int64_t)kSceneMaps * e->OH * e->OW);
+    ALLOC(e->scene_gpart, (int64_t)kSceneMaps * e->OH * e->OW * 3);
+    ALLOC(e->scene_cnt, (int64_t)kSceneMaps * e->OH * e->OW);
     HIP_OK(hipEventCreateWithFlags(&e->ev_misc, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&e->ev_end, hipEventDisableTiming));
     HIP_OK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
@@ -395,7 +397,7 @@ void smg_engine_destroy(smg_engine* e) {
     (void)hipDeviceSynchronize();
     void* ptrs[] = {e->img4, e->stem, e->DY0, e->argmax, e->X[0], e->X[1], e->X[2], e->X[3], e->G[0], e->G[1], e->G[2], e->G[3],
                     e->Bt, e->DY2, e->part, e->F, e->DF, e->H1, e->DH1, e->fstat, e->bstat, e->dbscr, e->d_dbseg, e->asc, e->d_asc, e->gamax, e->packed_u, e->packed_f, e->stab, e->d_pack, e->d_bnupd,
-                    e->d_stage, e->scene_val, e->scene_idx, e->scene_lpart, e->mom_part, e->mom};
+                    e->d_stage, e->scene_val, e->scene_idx, e->scene_lpart, e->scene_gpart, e->scene_cnt, e->mom_part, e->mom};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->dbg_gsnap) (void)hipFree(e->dbg_gsnap);
     step_graph_drop(e);
@@ -660,6 +662,30 @@ int smg_loss_scene_ce(smg_engine* e, const float* q_dev, const float* affine_hos
     }
     HIP_OK(hipGetLastError());
     e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0), as after smg_loss_map_ce
+    return 0;
+}
+
+int smg_loss_scene_map_ce(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs,
+                          const float* label_dev, float* loss_dev, float* dq_dev, void* stream) {
+    if (!e || !q_dev || !affine_host || !label_dev || !loss_dev || !dq_dev) return fail(-22, "smg_loss_scene_map_ce: NULL argument");
+    if (e->head_out != 3) return fail(-22, "smg_loss_scene_map_ce: the scene-frame label-map cross entropy needs a 3-class head (head_out == 3)");
+    if (n_pairs < 1) return fail(-22, "smg_loss_scene_map_ce: n_pairs < 1");
+    if (n_pairs > e->max_pairs) return fail(-22, "smg_loss_scene_map_ce: n_pairs exceeds the engine's max_pairs");
+    SceneGeo g;
+    if (int rc = scene_geometry(e, hm_size, "smg_loss_scene_map_ce", &g)) return rc;
+    if (int rc = scene_affines_ok(affine_host, n_pairs, "smg_loss_scene_map_ce")) return rc;
+    HIP_OK(hipSetDevice(e->device));
+    const int P = g.OH * g.OW;
+    for (int m0 = 0; m0 < n_pairs; m0 += kSceneMaps) {      // (groups follow each other on the stream: the partials are reused)
+        const int n = std::min(kSceneMaps, n_pairs - m0);
+        const SceneAffine a = scene_affine(affine_host, m0, n);
+        hipLaunchKernelGGL(loss_scene_map_ce_kernel, dim3(P, n), dim3(256), 0, (hipStream_t)stream,
+                           q_dev, m0, a, g, label_dev, e->scene_gpart, e->scene_lpart, e->scene_cnt);
+        hipLaunchKernelGGL(loss_scene_map_ce_finish_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (const double*)e->scene_gpart,
+                           (const double*)e->scene_lpart, (const int*)e->scene_cnt, P, m0, loss_dev, dq_dev);
+    }
+    HIP_OK(hipGetLastError());
+    e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0), as after smg_loss_scene_ce
     return 0;
 }
 

@@ -1,8 +1,9 @@
 // scene.cuh - dense Q maps in the SCENE frame: every rotation's [OH][OW] map rotated back and bilinearly upsampled onto the
 // heightmap's pixel grid (smg_scene_maps), the best (rotation, heightmap pixel) without materialising those maps
 // (smg_scene_argmax), and the Huber loss on labelled heightmap pixels with its gradient on the map (smg_loss_scene: K listed pixels;
-// smg_loss_scene_map: a whole label image and weight image); further down the first three for the class logits of a 3-class head
-// (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce).
+// smg_loss_scene_map: a whole label image and weight image); further down the same four for the class logits of a 3-class head
+// (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce: K listed pixels / smg_loss_scene_map_ce: a whole class-label
+// image, the cross entropy).
 //
 // Geometry (include/smg_hip.h has the derivation), all in double, coordinates (x = column, y = row):
 //   heightmap pixel (iy, ix) -> centre of its 2x2 block of the padded input   x = 2 ix + 0.5 + pad
@@ -218,6 +219,38 @@ static __global__ __launch_bounds__(256) void loss_scene_kernel(const float* q, 
     for (int i = t; i < P; i += 256) dj[i] = (float)sacc[i];
 }
 
+// The heightmap box of map element (oy, ox), shared by the two label-map kernels (loss_scene_map_kernel, loss_scene_map_ce_kernel):
+// pixels bx0 .. bx0 + bw - 1 of rows by0 .., n = bw * rows of them in row-major order (0 when the box is empty).  The kernels' comment
+// below has the construction.
+struct SceneBox { int bx0, by0, bw, n; };
+__device__ __forceinline__ SceneBox scene_element_box(const SceneGeo& g, double a00, double a01, double a10, double a11, int oy, int ox) {
+    // the box: the map square [ox - 1, ox + 1] x [oy - 1, oy + 1] (clipped) pushed back onto the heightmap
+    const double sm1 = (double)(g.S - 1);
+    const double qx0 = (double)max(ox - 1, 0), qx1 = (double)min(ox + 1, g.OW - 1), qy0 = (double)max(oy - 1, 0), qy1 = (double)min(oy + 1, g.OH - 1);
+    const double det = a00 * a11 - a10 * a01;                 // of A^T = [a00 a10; a01 a11], whose inverse is [a11 -a10; -a01 a00] / det
+    const bool inv_ok = fabs(det) > 1e-6 * (a00 * a00 + a01 * a01 + a10 * a10 + a11 * a11) && fabs(det) < INFINITY;      // (false for a NaN)
+    const double rdet = inv_ok ? 1.0 / det : 0.0;
+    double lox = INFINITY, hix = -INFINITY, loy = INFINITY, hiy = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const double qx = (c & 1) ? qx1 : qx0, qy = (c & 2) ? qy1 : qy0;
+        const double pxn = 2.0 * (32.0 * qx + 319.5) * g.inv_sm1 - 1.0, pyn = 2.0 * (32.0 * qy + 319.5) * g.inv_sm1 - 1.0;
+        const double ux = (a11 * pxn - a10 * pyn) * rdet, uy = (a00 * pyn - a01 * pxn) * rdet;            // A^-T p
+        const double fx = ((ux + 1.0) * 0.5 * sm1 - 0.5 - (double)g.pad) * 0.5, fy = ((uy + 1.0) * 0.5 * sm1 - 0.5 - (double)g.pad) * 0.5;
+        lox = fmin(lox, fx); hix = fmax(hix, fx); loy = fmin(loy, fy); hiy = fmax(hiy, fy);
+    }
+    // (clamped in double first: the conversions below stay in range whatever the matrix holds)
+    const double top = (double)g.hm;
+    if (!inv_ok) { lox = loy = 0.0; hix = hiy = top; }
+    const int bx0 = max((int)floor(fmin(fmax(lox, 0.0), top)) - 1, 0), bx1 = min((int)ceil(fmin(fmax(hix, -2.0), top)) + 1, g.hm - 1);
+    const int by0 = max((int)floor(fmin(fmax(loy, 0.0), top)) - 1, 0), by1 = min((int)ceil(fmin(fmax(hiy, -2.0), top)) + 1, g.hm - 1);
+    const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
+    const int n = bw > 0 && bh > 0 ? bw * bh : 0;             // (<= hm^2 < 2^31: checked by the host)
+    SceneBox b;
+    b.bx0 = bx0; b.by0 = by0; b.bw = bw; b.n = n;
+    return b;
+}
+
 // smg_loss_scene_map: loss_scene_kernel's Huber with a whole [hm][hm] label image and weight image per pair instead of K listed
 // pixels - every pixel that is valid in the pair's rotation and whose weight is not exactly 0 is a point:
 //     loss[j] = sum_pixels w huber(v - label)      dq[j][oy][ox] = sum_pixels w huber'(v - label) * (bilinear weight of (oy, ox) at the pixel)
@@ -242,28 +275,8 @@ static __global__ __launch_bounds__(256) void loss_scene_map_kernel(const float*
     const int oy = el / g.OW, ox = el - oy * g.OW;
     const float* qj = q + (int64_t)j * P;
     const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
-    // the box: the map square [ox - 1, ox + 1] x [oy - 1, oy + 1] (clipped) pushed back onto the heightmap
-    const double sm1 = (double)(g.S - 1);
-    const double qx0 = (double)max(ox - 1, 0), qx1 = (double)min(ox + 1, g.OW - 1), qy0 = (double)max(oy - 1, 0), qy1 = (double)min(oy + 1, g.OH - 1);
-    const double det = a00 * a11 - a10 * a01;                 // of A^T = [a00 a10; a01 a11], whose inverse is [a11 -a10; -a01 a00] / det
-    const bool inv_ok = fabs(det) > 1e-6 * (a00 * a00 + a01 * a01 + a10 * a10 + a11 * a11) && fabs(det) < INFINITY;      // (false for a NaN)
-    const double rdet = inv_ok ? 1.0 / det : 0.0;
-    double lox = INFINITY, hix = -INFINITY, loy = INFINITY, hiy = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const double qx = (c & 1) ? qx1 : qx0, qy = (c & 2) ? qy1 : qy0;
-        const double pxn = 2.0 * (32.0 * qx + 319.5) * g.inv_sm1 - 1.0, pyn = 2.0 * (32.0 * qy + 319.5) * g.inv_sm1 - 1.0;
-        const double ux = (a11 * pxn - a10 * pyn) * rdet, uy = (a00 * pyn - a01 * pxn) * rdet;            // A^-T p
-        const double fx = ((ux + 1.0) * 0.5 * sm1 - 0.5 - (double)g.pad) * 0.5, fy = ((uy + 1.0) * 0.5 * sm1 - 0.5 - (double)g.pad) * 0.5;
-        lox = fmin(lox, fx); hix = fmax(hix, fx); loy = fmin(loy, fy); hiy = fmax(hiy, fy);
-    }
-    // (clamped in double first: the conversions below stay in range whatever the matrix holds)
-    const double top = (double)g.hm;
-    if (!inv_ok) { lox = loy = 0.0; hix = hiy = top; }
-    const int bx0 = max((int)floor(fmin(fmax(lox, 0.0), top)) - 1, 0), bx1 = min((int)ceil(fmin(fmax(hix, -2.0), top)) + 1, g.hm - 1);
-    const int by0 = max((int)floor(fmin(fmax(loy, 0.0), top)) - 1, 0), by1 = min((int)ceil(fmin(fmax(hiy, -2.0), top)) + 1, g.hm - 1);
-    const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
-    const int n = bw > 0 && bh > 0 ? bw * bh : 0;             // (<= hm^2 < 2^31: checked by the host)
+    const SceneBox box = scene_element_box(g, a00, a01, a10, a11, oy, ox);
+    const int bx0 = box.bx0, by0 = box.by0, bw = box.bw, n = box.n;
     double acc = 0.0, lsum = 0.0;
     for (int i = t; i < n; i += 256) {
         const int ry = i / bw;
@@ -308,7 +321,7 @@ static __global__ __launch_bounds__(256) void loss_scene_map_reduce_kernel(const
     if (t == 0) loss[pair0 + m] = (float)red[0];
 }
 
-// ---- the reactive net's three class planes in the scene frame (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce) ----
+// ---- the reactive net's three class planes in the scene frame (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce / smg_loss_scene_map_ce) ----
 // The three LOGIT planes of a map ([3][OH][OW], `P` = OH * OW apart) are interpolated at the scene point - same corners, same
 // fractions - and the softmax is taken there, in double: z_c = bilinear(plane c), m = max z, e_c = exp(z_c - m), s = e_0 + e_1 + e_2,
 // P_c = e_c / s rounded to fp32 once.  Logits are interpolated, not probabilities: the cross entropy below is that of these very
@@ -484,6 +497,87 @@ static __global__ __launch_bounds__(256) void loss_scene_ce_kernel(const float* 
     if (t == 0) loss[j] = W > 0 ? (float)(red[0] / dW) : 0.f;
     float* dj = dq + (int64_t)j * 3 * P;
     for (int i = t; i < 3 * P; i += 256) dj[i] = W > 0 ? (float)(sacc[i] / dW) : 0.f;
+}
+
+// smg_loss_scene_map_ce: loss_scene_ce_kernel's cross entropy with a whole [hm][hm] class-label image per pair instead of K listed
+// pixels - loss_scene_map_kernel's structure on three planes.  A heightmap pixel is a POINT of pair j when it is valid in the pair's
+// rotation and its label is exactly 0.f or 1.f; every other pixel (class 2, NaN, any other value) is skipped before a logit is
+// read, and the label of an invalid pixel is never read.  W = the number of points.  Per point, in double (scene_class as it stands):
+//     nll = (log(s) + m) - z_y        g_c = e_c / s - [c == y]
+//     loss[j] = (sum nll) / W         dq[j][c][oy][ox] = (sum g_c * bilinear weight of (oy, ox) at the pixel) / W
+// Gather by map element exactly as in loss_scene_map_kernel: one workgroup owns one (pair, oy, ox) - blockIdx.x = oy * OW + ox,
+// blockIdx.y = pair of this launch - and walks scene_element_box's pixels t, t + 256, ... in row-major order; a pixel adds its nll
+// and its count at its HOME element (y0, x0) only (the logarithm is taken there alone) and its gradient share at every element it
+// touches, so a point's softmax is evaluated by up to four workgroups: the price of a form without atomics.  The twelve corner
+// logits of a pixel come from global memory (three [OH][OW] planes that sit in L2; staging the 27 logits around the element in LDS
+// measured 0.755 against 0.776 ms at S = 1824, inside the spread between repeats, and was not kept).
+// W is known only when all elements of a pair are done, so this launch writes UNNORMALISED partials into scratch the engine owns,
+// every slot written: gpart [pairs of this launch][3][OH * OW] doubles, lpart [pairs][OH * OW] doubles, cpart [pairs][OH * OW]
+// ints.  No accumulator of the map's size in LDS (4 x 256 doubles + 256 ints of reduction arrays), hence no limit on the map's size
+// beyond scene_geometry's.
+static __global__ __launch_bounds__(256) void loss_scene_map_ce_kernel(const float* q, int pair0, const SceneAffine aff, const SceneGeo g,
+                                                                       const float* label, double* gpart, double* lpart, int* cpart) {
+    __shared__ double racc[3][256], rloss[256];
+    __shared__ int rcnt[256];
+    const int t = threadIdx.x, m = blockIdx.y, j = pair0 + m, el = blockIdx.x;
+    const int P = g.OH * g.OW;
+    const int oy = el / g.OW, ox = el - oy * g.OW;
+    const float* qj = q + (int64_t)j * 3 * P;
+    const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
+    const SceneBox box = scene_element_box(g, a00, a01, a10, a11, oy, ox);
+    const int bx0 = box.bx0, by0 = box.by0, bw = box.bw, n = box.n;
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, lsum = 0.0; int w = 0;
+    for (int i = t; i < n; i += 256) {
+        const int ry = i / bw;
+        const int iy = by0 + ry, ix = bx0 + (i - ry * bw);
+        const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
+        if (!p.valid) continue;
+        const int dy = oy - p.y0, dx = ox - p.x0;
+        if ((unsigned)dy > 1u || (unsigned)dx > 1u) continue;
+        const float lf = label[((int64_t)j * g.hm + iy) * g.hm + ix];
+        if (!(lf == 0.f || lf == 1.f)) continue;
+        const SceneClass c = scene_class(p, qj, P, g.OW);
+        if (dy == 0 && dx == 0) { lsum += (log(c.s) + c.m) - (lf == 0.f ? c.z0 : c.z1); ++w; }
+        const double wy = dy ? p.fy : 1.0 - p.fy, wx = dx ? p.fx : 1.0 - p.fx;
+        const double wgt = wy * wx;
+        acc0 += (c.e0 / c.s - (lf == 0.f ? 1.0 : 0.0)) * wgt; acc1 += (c.e1 / c.s - (lf == 1.f ? 1.0 : 0.0)) * wgt; acc2 += (c.e2 / c.s) * wgt;
+    }
+    racc[0][t] = acc0; racc[1][t] = acc1; racc[2][t] = acc2; rloss[t] = lsum; rcnt[t] = w;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+            racc[0][t] += racc[0][t + s]; racc[1][t] += racc[1][t + s]; racc[2][t] += racc[2][t + s];
+            rloss[t] += rloss[t + s]; rcnt[t] += rcnt[t + s];
+        }
+        __syncthreads();
+    }
+    if (t < 3) gpart[((int64_t)m * 3 + t) * P + el] = racc[t][0];
+    if (t == 0) { lpart[(int64_t)m * P + el] = rloss[0]; cpart[(int64_t)m * P + el] = rcnt[0]; }
+}
+
+// The second launch of smg_loss_scene_map_ce: one workgroup per pair of the launch sums its P loss partials and counts - thread t
+// takes slots t, t + 256, ... in that order, then the fixed tree - which gives W, then writes loss = (float)(sum / W) and
+// dq = (float)(partial / W) for all 3 P elements: divided once, rounded once, every element written once.  W == 0: loss 0.f and dq
+// exactly 0.f everywhere.
+static __global__ __launch_bounds__(256) void loss_scene_map_ce_finish_kernel(const double* gpart, const double* lpart, const int* cpart,
+                                                                              int P, int pair0, float* loss, float* dq) {
+    __shared__ double red[256];
+    __shared__ int cnt[256];
+    const int t = threadIdx.x, m = blockIdx.x, j = pair0 + m;
+    double s = 0.0; int w = 0;
+    for (int i = t; i < P; i += 256) { s += lpart[(int64_t)m * P + i]; w += cpart[(int64_t)m * P + i]; }
+    red[t] = s; cnt[t] = w;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (t < k) { red[t] += red[t + k]; cnt[t] += cnt[t + k]; }
+        __syncthreads();
+    }
+    const int W = cnt[0];
+    const double dW = (double)W;
+    if (t == 0) loss[j] = W > 0 ? (float)(red[0] / dW) : 0.f;
+    const double* gm = gpart + (int64_t)m * 3 * P;
+    float* dj = dq + (int64_t)j * 3 * P;
+    for (int i = t; i < 3 * P; i += 256) dj[i] = W > 0 ? (float)(gm[i] / dW) : 0.f;
 }
 
 }  // namespace smg

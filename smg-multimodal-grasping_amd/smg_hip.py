@@ -56,6 +56,8 @@ def lib():
     L.smg_version.restype = C.c_int
     if not hasattr(L, "smg_abi_struct_bytes") or L.smg_version() != ABI_VERSION:
         raise SmgError("%s is ABI version %d, this binding needs %d: rebuild it (make -C csrc)" % (LIB_PATH, L.smg_version(), ABI_VERSION))
+    if not hasattr(L, "smg_loss_scene_map_ce"):       # (added without a version step: a version-9 library built before it lacks the symbol)
+        raise SmgError("%s is ABI version %d but lacks smg_loss_scene_map_ce, a stale build: rebuild it (make -C csrc)" % (LIB_PATH, ABI_VERSION))
     L.smg_abi_struct_bytes.argtypes = [C.c_int]
     for which, ty in ((0, SmgBatch), (1, SmgNet), (2, SmgAdam)):
         if L.smg_abi_struct_bytes(which) != C.sizeof(ty):
@@ -88,6 +90,7 @@ def lib():
     L.smg_scene_class_argmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene_ce.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
+    L.smg_loss_scene_map_ce.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_backward.argtypes = [C.c_void_p, C.POINTER(SmgNet), C.c_void_p, C.c_void_p]
     if hasattr(L, "smg_backward_phase"):          # (absent from the dev builds tools/ab_kernels.sh compares against)
         L.smg_backward_phase.argtypes = [C.c_void_p, C.POINTER(SmgNet), C.c_void_p, C.c_void_p, C.c_int]
@@ -117,7 +120,7 @@ EXPORTS = (
     "smg_last_error", "smg_version", "smg_abi_struct_bytes", "smg_engine_set_option", "smg_layout_count", "smg_layout_param_floats", "smg_layout_buffer_floats",
     "smg_layout_nbt_count", "smg_layout_entry", "smg_layout_trunk_range", "smg_layout_head_range",
     "smg_engine_create", "smg_engine_destroy", "smg_engine_workspace_bytes", "smg_engine_geometry",
-    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_argmax", "smg_loss_scene", "smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_argmax", "smg_loss_scene_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
+    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_argmax", "smg_loss_scene", "smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_argmax", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
     "smg_profile_enable", "smg_profile_kinds", "smg_profile_kind_name", "smg_profile_read", "smg_profile_read_bytes",
 )
 
@@ -312,6 +315,14 @@ class Engine(object):
         dense head form."""
         a, p = self._affines(affine, n_pairs)
         check(lib().smg_loss_scene_ce(self.h, q, p, int(hm_size), int(n_pairs), int(K), pixels, labels, loss_out, dq_out, stream))
+
+    def loss_scene_map_ce(self, q, affine, hm_size, n_pairs, label_maps, loss_out, dq_out, stream):
+        """smg_loss_scene_map_ce: the cross entropy (class weights {1, 1, 0}) on a whole class-label image per pair (`label_maps`
+        device float32 [n_pairs, hm_size, hm_size]; 0 and 1 count, anything else is "no loss"), the mean over the labelled pixels
+        that have a window in their pair's rotation, dq on the three logit maps.  Marks the saved forward so that its backward
+        runs the dense head form."""
+        a, p = self._affines(affine, n_pairs)
+        check(lib().smg_loss_scene_map_ce(self.h, q, p, int(hm_size), int(n_pairs), label_maps, loss_out, dq_out, stream))
 
     def backward(self, net, dq, stream, phase=None):
         """phase None: the whole backward; 0 / 1: its two halves (smg_backward_phase)."""

@@ -923,6 +923,50 @@ class Trainer(object):
         self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
         return (loss, q) if return_q else loss
 
+    def train_batch_scene_class_maps(self, depth_heightmap, m_depth_heightmap, style, rotations, label_maps, grad_sync=None,
+                                     return_q=False):
+        """train_batch_scene_class_pixels with a whole class-label IMAGE per sample: `label_maps` is a host array [n_samples, hm, hm]
+        in heightmap pixels, scene-major, of class indices 0, 1 or 2 (anything else, NaN included, raises ValueError as in
+        train_batch_class_maps).  loss_j = the mean over the class-0 / 1 pixels that have a window of the head in sample j's
+        rotation (scene_to_map's `valid`) of the cross entropy of the interpolated logits (smg_loss_scene_map_ce); class 2 is "no
+        loss".  A class-0 / 1 pixel WITHOUT a window is skipped silently - a whole image always covers such pixels - where
+        train_batch_scene_class_pixels raises; a sample without a counted pixel gives loss 0 and no gradient.  The gradient of
+        the SUM of the losses goes back in one backward pass (dense head form), then ONE Adam step.  Scenes, rotations and
+        `grad_sync` as in train_batch_scene_class_pixels.  Reactive method only.
+        Returns the loss vector (and the logits q [n_samples, 3, OH, OW] if asked)."""
+        import models
+        _, _, side = self._require_scene_class("train_batch_scene_class_maps", depth_heightmap)
+        per_scene = np.ndim(depth_heightmap) == 3
+        flat_rots = [r for rs in rotations for r in rs] if per_scene else list(rotations)
+        n = len(flat_rots)
+        hm = int(np.shape(depth_heightmap)[-1])
+        if label_maps is None or tuple(np.shape(label_maps)) != (n, hm, hm):
+            raise ValueError("label_maps must be [%d samples, %d, %d] for a %d^2 heightmap, got %s"
+                             % (n, hm, hm, hm, None if label_maps is None else tuple(np.shape(label_maps))))
+        lab_h = np.ascontiguousarray(label_maps, dtype=np.float32)
+        if not np.isin(lab_h, (0.0, 1.0, 2.0)).all():      # (torch's nll_loss raises on a class index outside [0, 3), as in train_batch)
+            raise ValueError("label maps must hold class indices 0, 1 or 2")
+        num = self.model.gnum_rotations
+        rots = [0 if style == 2 else int(r) for r in flat_rots]
+        model = self.model
+        self.optimizer.zero_grad()
+        model._require_gpu()
+        dev = model._flat_params.device
+        hmaps, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
+        rots2 = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
+        # (uploaded BEFORE the forward is enqueued, like train_batch's labels)
+        lab_d = torch.as_tensor(lab_h, device=dev)
+        q = model.run(style, rots2, num, heightmaps=hmaps, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
+        eng, token, trunk_id, head_id = model._saved
+        assert tuple(q.shape) == (n, 3, side, side), (tuple(q.shape), n, side)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        dq = torch.empty_like(q)
+        eng.loss_scene_map_ce(q.data_ptr(), [models.rotation_theta(r, num) for r in rots], hm, n, lab_d.data_ptr(), loss.data_ptr(),
+                              dq.data_ptr(), stream)
+        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
+        return (loss, q) if return_q else loss
+
     # The single-sample step of Trainer.backprop as ONE replayed hipGraph (smg_train_step_graph): ~560 launches of 2-20 us each are
     # enqueued by one hipGraphLaunch instead of one by one (same results, bit for bit at zero learning rate).  It saves a little host time
     # (1.8 ms per step instead of 2.3) and costs latency: the graph's ~560 dependent nodes execute no faster than the same launches from

@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""Timing of smg_loss_scene_map_ce (a whole class-label image per pair, parallel over the map) against the only other way to the
+same loss: smg_loss_scene_ce fed EVERY heightmap pixel as a list (serial in the pixels, one workgroup per pair).
+
+Config-5 geometry: a 640^2 heightmap (S = 1824, 38 x 38 class maps), 32 pairs = rotations 0 .. 31 of 32, seeded random logits
+[32, 3, 38, 38], full label images of the class mix of tests/scene_class_label_ref.py (0 and 1 at 35 % each; 2, NaN, 7, -1 and 0.5
+are "no loss").  The protocol is tools/scene_label_maps_bench.py's: events on the launch stream around each window, the sides
+alternating inside one process, 2 warm-ups of each, 7 repeats; median, range and spread (max - min) per side, ms per call.  Sides:
+    label_map     smg_loss_scene_map_ce on the [32, 640, 640] label images (52.4 MB)
+    pixel_list    smg_loss_scene_ce with K = 409 600 = every pixel, the (iy, ix) list and the labels PREBUILT on the device
+                  (12 bytes per pixel: 157 MB for 32 pairs; building and uploading them is not timed) - the comparator
+Before anything is timed the two sides' loss and dq must agree to 2^-22 of the loss and of max|dq| (each rounds an fp64 sum of
+the same terms, divided by the same W, once).
+A window holds --calls calls of label_map; one call of pixel_list is long, so its calls per window are lowered to what fits
+--side-b-window-ms (at least 1) from the time of a first single call, and the count used is written out.
+
+    python tools/scene_class_label_maps_bench.py --probe        # the agreement check and one timed call of pixel_list: sizes the timeout
+    python tools/scene_class_label_maps_bench.py [--repeats 7] [--warmup 2] > profiles/scene_class_label_maps.txt
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "smg-multimodal-grasping_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--calls", type=int, default=20, help="calls of label_map per timed window (pixel_list: at most this many)")
+    ap.add_argument("--side-b-window-ms", type=float, default=1000.0, help="longest pixel_list window: its calls per window are lowered to fit")
+    ap.add_argument("--size", type=int, default=640, help="heightmap side (640 -> S = 1824)")
+    ap.add_argument("--pairs", type=int, default=32, help="pairs = rotations 0 .. pairs - 1 of that many")
+    ap.add_argument("--probe", action="store_true", help="check the agreement, time one call of pixel_list, print it and stop")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("scene_class_label_maps_bench: no GPU visible (a timing needs the MI355X)")
+    import models
+    from trainer import Trainer
+
+    hm, R = args.size, args.pairs
+    pad, S, side = Trainer._scene_geometry(hm)
+    dev = torch.device("cuda:0")
+    eng = models.get_engine(0, S, 3, 2, R)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    aff = np.stack([models.rotation_theta(r, R) for r in range(R)])
+    rng = np.random.default_rng(0)
+    q = torch.from_numpy(rng.standard_normal((R, 3, side, side)).astype(np.float32)).to(dev)
+    lab = torch.from_numpy(rng.choice(np.asarray([0, 1, 2, np.nan, 7, -1, 0.5]), size=(R, hm, hm),
+                                      p=[.35, .35, .1, .05, .05, .05, .05]).astype(np.float32)).to(dev)
+    K = hm * hm
+    iy, ix = torch.meshgrid(torch.arange(hm, dtype=torch.int32, device=dev), torch.arange(hm, dtype=torch.int32, device=dev), indexing="ij")
+    pix = torch.stack((iy, ix), dim=-1).reshape(1, K, 2).expand(R, K, 2).contiguous()                  # every pixel, row-major, per pair
+    lab_k = lab.reshape(R, K)
+    loss_a, dq_a = torch.empty(R, device=dev), torch.empty_like(q)
+    loss_b, dq_b = torch.empty(R, device=dev), torch.empty_like(q)
+
+    def label_map():
+        eng.loss_scene_map_ce(q.data_ptr(), aff, hm, R, lab.data_ptr(), loss_a.data_ptr(), dq_a.data_ptr(), stream)
+
+    def pixel_list():
+        eng.loss_scene_ce(q.data_ptr(), aff, hm, R, K, pix.data_ptr(), lab_k.data_ptr(), loss_b.data_ptr(), dq_b.data_ptr(), stream)
+
+    def window(fn, calls):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        t0.record()
+        for _ in range(calls):
+            fn()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) / calls
+
+    print("# %d^2 heightmap, S = %d, %d pairs, %d x %d class maps; label images %.1f MB, pixel list + labels %.1f MB; ms per call"
+          % (hm, S, R, side, side, lab.numel() * 4 / 1e6, (pix.numel() + R * K) * 4 / 1e6))
+    first_b = window(pixel_list, 1)              # the first single call of the comparator (cold: an upper bound of a warm one)
+    label_map()
+    torch.cuda.synchronize(dev)
+    la, lb = loss_a.double().cpu().numpy(), loss_b.double().cpu().numpy()
+    da, db = dq_a.double().cpu().numpy(), dq_b.double().cpu().numpy()
+    loss_err = float(np.max(np.abs(la - lb) / np.abs(lb)))
+    dq_err = float(np.abs(da - db).max() / np.abs(db).max())
+    print("agreement: max |loss_a - loss_b| / loss_b = %.3e, max |dq_a - dq_b| / max|dq_b| = %.3e (gate 2^-22 = %.3e); first single call of pixel_list %.3f ms"
+          % (loss_err, dq_err, 2.0 ** -22, first_b), flush=True)
+    if not (np.isfinite(la).all() and np.isfinite(da).all() and loss_err <= 2.0 ** -22 and dq_err <= 2.0 ** -22):
+        sys.exit("scene_class_label_maps_bench: the two sides disagree; nothing timed")
+    if args.probe:
+        print(json.dumps({"tool": "scene_class_label_maps_bench", "probe_pixel_list_ms": first_b}))
+        return
+    calls_b = int(max(1, min(args.calls, args.side_b_window_ms // max(first_b, 1e-3))))
+    sides = (("label_map", label_map, args.calls), ("pixel_list", pixel_list, calls_b))
+    print("# calls per window: label_map %d, pixel_list %d" % (args.calls, calls_b))
+    times = {name: [] for name, _, _ in sides}
+    for _ in range(args.warmup):
+        for name, fn, calls in sides:
+            window(fn, calls)
+    for rep in range(args.repeats):
+        for name, fn, calls in (sides if rep % 2 == 0 else sides[::-1]):
+            ms = window(fn, calls)
+            times[name].append(ms)
+            print("repeat %d %-10s %.4f ms" % (rep, name, ms), flush=True)
+    summary = {"tool": "scene_class_label_maps_bench", "input_size": S, "heightmap": hm, "pairs": R, "map": [side, side], "repeats": args.repeats,
+               "warmup": args.warmup, "calls_per_window": {"label_map": args.calls, "pixel_list": calls_b},
+               "first_single_call_pixel_list_ms": first_b, "loss_rel_diff": loss_err, "dq_rel_diff": dq_err}
+    for name, _, _ in sides:
+        t = times[name]
+        summary[name + "_ms"] = {"median": float(np.median(t)), "min": min(t), "max": max(t), "spread": max(t) - min(t)}
+    a, b = summary["label_map_ms"], summary["pixel_list_ms"]
+    summary["larger_spread_ms"] = max(a["spread"], b["spread"])
+    summary["label_map_below_pixel_list_by_more_than_the_larger_spread"] = bool(b["median"] - a["median"] > summary["larger_spread_ms"])
+    summary["pixel_list_over_label_map"] = b["median"] / a["median"]
+    print(json.dumps(summary))
+
+
+if __name__ == "__main__":
+    main()
