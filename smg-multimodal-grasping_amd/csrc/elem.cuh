@@ -1763,6 +1763,18 @@ __device__ __forceinline__ bool argmax_better(float x, int i, float bx, int bi) 
     if (xn) return i < bi;
     return x > bx || (x == bx && i < bi);
 }
+// The tree over a workgroup's 256 (value, index) slots, thread t's own in bv[t], bi[t] (LDS): the best by argmax_better's rules ends
+// in slot 0.  A slot with index 0x7fffffff is empty and never wins.
+__device__ __forceinline__ void block_argmax(float* bv, int* bi, int t) {
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+            const float x = bv[t + s]; const int j = bi[t + s];
+            if (j != 0x7fffffff && argmax_better(x, j, bv[t], bi[t])) { bv[t] = x; bi[t] = j; }
+        }
+        __syncthreads();
+    }
+}
 static __global__ __launch_bounds__(256) void argmax_kernel(const float* v, int n, int* idx_out, float* val_out) {
     __shared__ float bv[256];
     __shared__ int bi[256];
@@ -1773,14 +1785,7 @@ static __global__ __launch_bounds__(256) void argmax_kernel(const float* v, int 
         if (argmax_better(x, i, best, at)) { best = x; at = i; }
     }
     bv[t] = best; bi[t] = at;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) {
-            const float x = bv[t + s]; const int j = bi[t + s];
-            if (j != 0x7fffffff && argmax_better(x, j, bv[t], bi[t])) { bv[t] = x; bi[t] = j; }
-        }
-        __syncthreads();
-    }
+    block_argmax(bv, bi, t);
     if (t == 0) { *idx_out = bi[0] == 0x7fffffff ? 0 : bi[0]; *val_out = bv[0]; }
 }
 

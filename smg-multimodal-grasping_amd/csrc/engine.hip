@@ -505,90 +505,98 @@ static SceneAffine scene_affine(const float* affine_host, int m0, int n) {
     return a;
 }
 
-int smg_scene_maps(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
-                   float* out_dev, void* stream) {
-    if (!e || !q_dev || !affine_host || !out_dev) return fail(-22, "NULL argument");
-    if (n_maps < 1 || map_stride < 0) return fail(-22, "smg_scene_maps: n_maps < 1 or a negative map_stride");
-    SceneGeo g;
-    if (int rc = scene_geometry(e, hm_size, "smg_scene_maps", &g)) return rc;
-    if (int rc = scene_affines_ok(affine_host, n_maps, "smg_scene_maps")) return rc;
+// What the eight scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
+// evaluates them and passes each one's text, or nullptr where it does not apply; the first that applies is reported as
+// "<who>: <text>"), the geometry, the one refusal that stands behind it (`after`), the n affines.  Then the device is selected and g
+// is valid.  Nothing has been launched when this returns non-zero.
+static int scene_prelude(const smg_engine* e, const char* who, std::initializer_list<const char*> before, int hm_size, const char* after,
+                         const float* affine_host, int n, SceneGeo* g) {
+    for (const char* text : before)
+        if (text) return fail(-22, std::string(who) + ": " + text);
+    if (int rc = scene_geometry(e, hm_size, who, g)) return rc;
+    if (after) return fail(-22, std::string(who) + ": " + after);
+    if (int rc = scene_affines_ok(affine_host, n, who)) return rc;
     HIP_OK(hipSetDevice(e->device));
-    const int64_t npix = (int64_t)hm_size * hm_size;
-    const int vec4 = npix % 4 == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 15) == 0;
-    const int tiles = (int)((npix + kSceneTile - 1) / kSceneTile);
-    for (int m0 = 0; m0 < n_maps; m0 += kSceneMaps) {
-        const int n = std::min(kSceneMaps, n_maps - m0);
-        const SceneAffine a = scene_affine(affine_host, m0, n);
-        hipLaunchKernelGGL(scene_map_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
-                           q_dev, map_stride, m0, a, g, out_dev, vec4);
+    return 0;
+}
+// The launches of an entry point: launch(m0, n, affines) for maps (pairs) [m0, m0 + n) of n_all, kSceneMaps at a time.  The groups
+// follow each other on the stream, so scratch of the engine that a group's launches pass on to each other is reused by the next.
+extern "C++" template <class F>
+static int scene_groups(const float* affine_host, int n_all, F launch) {
+    for (int m0 = 0; m0 < n_all; m0 += kSceneMaps) {
+        const int n = std::min(kSceneMaps, n_all - m0);
+        launch(m0, n, scene_affine(affine_host, m0, n));
     }
     HIP_OK(hipGetLastError());
     return 0;
+}
+static int scene_tiles(int hm_size) { return (int)(((int64_t)hm_size * hm_size + kSceneTile - 1) / kSceneTile); }      // <= e->scene_tiles: hm_size <= S / 2
+// whole 16-byte stores: hm^2 a multiple of 4 and an aligned output
+static int scene_vec4(int hm_size, const float* out_dev) { return (int64_t)hm_size * hm_size % 4 == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 15) == 0; }
+static const char* scene_index_fits(int n_maps, int hm_size) {
+    return (int64_t)n_maps * hm_size * hm_size > 0x7fffffff ? "the flattened index does not fit int32" : nullptr;
+}
+
+int smg_scene_maps(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
+                   float* out_dev, void* stream) {
+    if (!e || !q_dev || !affine_host || !out_dev) return fail(-22, "smg_scene_maps: NULL argument");
+    SceneGeo g;
+    if (int rc = scene_prelude(e, "smg_scene_maps", {n_maps < 1 || map_stride < 0 ? "n_maps < 1 or a negative map_stride" : nullptr},
+                               hm_size, nullptr, affine_host, n_maps, &g)) return rc;
+    const int vec4 = scene_vec4(hm_size, out_dev), tiles = scene_tiles(hm_size);
+    return scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
+        hipLaunchKernelGGL(scene_map_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
+                           q_dev, map_stride, m0, a, g, out_dev, vec4);
+    });
 }
 
 int smg_scene_argmax(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
                      int* idx_out_dev, float* val_out_dev, void* stream) {
-    if (!e || !q_dev || !affine_host || !idx_out_dev || !val_out_dev) return fail(-22, "NULL argument");
-    if (n_maps < 1 || map_stride < 0) return fail(-22, "smg_scene_argmax: n_maps < 1 or a negative map_stride");
+    if (!e || !q_dev || !affine_host || !idx_out_dev || !val_out_dev) return fail(-22, "smg_scene_argmax: NULL argument");
     SceneGeo g;
-    if (int rc = scene_geometry(e, hm_size, "smg_scene_argmax", &g)) return rc;
-    const int64_t npix = (int64_t)hm_size * hm_size;
-    if ((int64_t)n_maps * npix > 0x7fffffff) return fail(-22, "smg_scene_argmax: the flattened index does not fit int32");
-    if (int rc = scene_affines_ok(affine_host, n_maps, "smg_scene_argmax")) return rc;
-    HIP_OK(hipSetDevice(e->device));
-    const int tiles = (int)((npix + kSceneTile - 1) / kSceneTile);      // <= e->scene_tiles: hm_size <= S / 2
-    for (int m0 = 0; m0 < n_maps; m0 += kSceneMaps) {      // (groups follow each other on the stream: the partials are reused)
-        const int n = std::min(kSceneMaps, n_maps - m0);
-        const SceneAffine a = scene_affine(affine_host, m0, n);
+    if (int rc = scene_prelude(e, "smg_scene_argmax", {n_maps < 1 || map_stride < 0 ? "n_maps < 1 or a negative map_stride" : nullptr},
+                               hm_size, scene_index_fits(n_maps, hm_size), affine_host, n_maps, &g)) return rc;
+    const int tiles = scene_tiles(hm_size);
+    return scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
         hipLaunchKernelGGL(scene_argmax_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
                            q_dev, map_stride, m0, a, g, e->scene_val, e->scene_idx);
         hipLaunchKernelGGL(scene_argmax_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
                            (const int*)e->scene_idx, tiles * n, m0 > 0 ? 1 : 0, idx_out_dev, val_out_dev);
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
+    });
 }
 
 int smg_loss_scene(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs, int K, const int* pixels_dev,
                    const float* label_dev, const float* weight_dev, float* loss_dev, float* dq_dev, void* stream) {
-    if (!e || !q_dev || !affine_host || !pixels_dev || !label_dev || !loss_dev || !dq_dev) return fail(-22, "NULL argument");
-    if (e->head_out != 1) return fail(-22, "smg_loss_scene: the scene-pixel Huber needs a one-channel head (head_out == 1)");
-    if (n_pairs < 1 || n_pairs > e->max_pairs) return fail(-22, "n_pairs exceeds the engine's max_pairs");
-    if (K < 1) return fail(-22, "smg_loss_scene: K < 1");
+    if (!e || !q_dev || !affine_host || !pixels_dev || !label_dev || !loss_dev || !dq_dev) return fail(-22, "smg_loss_scene: NULL argument");
     SceneGeo g;
-    if (int rc = scene_geometry(e, hm_size, "smg_loss_scene", &g)) return rc;
-    if (int rc = scene_affines_ok(affine_host, n_pairs, "smg_loss_scene")) return rc;
-    HIP_OK(hipSetDevice(e->device));
-    for (int m0 = 0; m0 < n_pairs; m0 += kSceneMaps) {
-        const int n = std::min(kSceneMaps, n_pairs - m0);
-        const SceneAffine a = scene_affine(affine_host, m0, n);
-        hipLaunchKernelGGL(loss_scene_kernel, dim3(n), dim3(256), (size_t)g.OH * g.OW * (sizeof(double) + sizeof(float)), (hipStream_t)stream,
-                           q_dev, m0, a, g, K, pixels_dev, label_dev, weight_dev, loss_dev, dq_dev);
-    }
-    HIP_OK(hipGetLastError());
+    if (int rc = scene_prelude(e, "smg_loss_scene",
+                               {e->head_out != 1 ? "the scene-pixel Huber needs a one-channel head (head_out == 1)" : nullptr,
+                                n_pairs < 1 || n_pairs > e->max_pairs ? "n_pairs exceeds the engine's max_pairs" : nullptr,
+                                K < 1 ? "K < 1" : nullptr},
+                               hm_size, nullptr, affine_host, n_pairs, &g)) return rc;
+    if (int rc = scene_groups(affine_host, n_pairs, [&](int m0, int n, const SceneAffine& a) {
+            hipLaunchKernelGGL(loss_scene_kernel, dim3(n), dim3(256), (size_t)g.OH * g.OW * (sizeof(double) + sizeof(float)), (hipStream_t)stream,
+                               q_dev, m0, a, g, K, pixels_dev, label_dev, weight_dev, loss_dev, dq_dev);
+        })) return rc;
     e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0), as after smg_loss_map
     return 0;
 }
 
 int smg_loss_scene_map(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs,
                        const float* label_dev, const float* weight_dev, float* loss_dev, float* dq_dev, void* stream) {
-    if (!e || !q_dev || !affine_host || !label_dev || !loss_dev || !dq_dev) return fail(-22, "NULL argument");
-    if (e->head_out != 1) return fail(-22, "smg_loss_scene_map: the scene-frame label-map Huber needs a one-channel head (head_out == 1)");
-    if (n_pairs < 1) return fail(-22, "smg_loss_scene_map: n_pairs < 1");
-    if (n_pairs > e->max_pairs) return fail(-22, "smg_loss_scene_map: n_pairs exceeds the engine's max_pairs");
+    if (!e || !q_dev || !affine_host || !label_dev || !loss_dev || !dq_dev) return fail(-22, "smg_loss_scene_map: NULL argument");
     SceneGeo g;
-    if (int rc = scene_geometry(e, hm_size, "smg_loss_scene_map", &g)) return rc;
-    if (int rc = scene_affines_ok(affine_host, n_pairs, "smg_loss_scene_map")) return rc;
-    HIP_OK(hipSetDevice(e->device));
+    if (int rc = scene_prelude(e, "smg_loss_scene_map",
+                               {e->head_out != 1 ? "the scene-frame label-map Huber needs a one-channel head (head_out == 1)" : nullptr,
+                                n_pairs < 1 ? "n_pairs < 1" : nullptr,
+                                n_pairs > e->max_pairs ? "n_pairs exceeds the engine's max_pairs" : nullptr},
+                               hm_size, nullptr, affine_host, n_pairs, &g)) return rc;
     const int P = g.OH * g.OW;
-    for (int m0 = 0; m0 < n_pairs; m0 += kSceneMaps) {      // (groups follow each other on the stream: the partials are reused)
-        const int n = std::min(kSceneMaps, n_pairs - m0);
-        const SceneAffine a = scene_affine(affine_host, m0, n);
-        hipLaunchKernelGGL(loss_scene_map_kernel, dim3(P, n), dim3(256), 0, (hipStream_t)stream,
-                           q_dev, m0, a, g, label_dev, weight_dev, e->scene_lpart, dq_dev);
-        hipLaunchKernelGGL(loss_scene_map_reduce_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (const double*)e->scene_lpart, P, m0, loss_dev);
-    }
-    HIP_OK(hipGetLastError());
+    if (int rc = scene_groups(affine_host, n_pairs, [&](int m0, int n, const SceneAffine& a) {
+            hipLaunchKernelGGL(loss_scene_map_kernel, dim3(P, n), dim3(256), 0, (hipStream_t)stream,
+                               q_dev, m0, a, g, label_dev, weight_dev, e->scene_lpart, dq_dev);
+            hipLaunchKernelGGL(loss_scene_map_reduce_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (const double*)e->scene_lpart, P, m0, loss_dev);
+        })) return rc;
     e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0), as after smg_loss_scene
     return 0;
 }
@@ -596,71 +604,55 @@ int smg_loss_scene_map(smg_engine* e, const float* q_dev, const float* affine_ho
 // ---- the three class planes of a 3-class head in the scene frame ---------------------
 int smg_scene_class_maps(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls, float* out_dev,
                          void* stream) {
-    if (!e || !q_dev || !affine_host || !out_dev) return fail(-22, "NULL argument");
-    if (e->head_out != 3) return fail(-22, "smg_scene_class_maps: class probabilities need a 3-class head (head_out == 3)");
-    if (n_maps < 1) return fail(-22, "smg_scene_class_maps: n_maps < 1");
-    if (cls < -1 || cls > 2) return fail(-22, "smg_scene_class_maps: cls must be 0, 1, 2 or -1 (all three)");
-    SceneGeo g;
-    if (int rc = scene_geometry(e, hm_size, "smg_scene_class_maps", &g)) return rc;      // (its LDS bound is 12 OH OW bytes: the three float planes)
-    if (int rc = scene_affines_ok(affine_host, n_maps, "smg_scene_class_maps")) return rc;
-    HIP_OK(hipSetDevice(e->device));
-    const int64_t npix = (int64_t)hm_size * hm_size;
-    const int vec4 = npix % 4 == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 15) == 0;
-    const int tiles = (int)((npix + kSceneTile - 1) / kSceneTile);
-    for (int m0 = 0; m0 < n_maps; m0 += kSceneMaps) {
-        const int n = std::min(kSceneMaps, n_maps - m0);
-        const SceneAffine a = scene_affine(affine_host, m0, n);
-        hipLaunchKernelGGL(scene_class_map_kernel, dim3(tiles, n), dim3(256), (size_t)3 * g.OH * g.OW * sizeof(float), (hipStream_t)stream,
-                           q_dev, m0, a, g, cls, out_dev, vec4);
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
+    if (!e || !q_dev || !affine_host || !out_dev) return fail(-22, "smg_scene_class_maps: NULL argument");
+    SceneGeo g;      // (the LDS bound of the geometry is 12 OH OW bytes: the three float planes)
+    if (int rc = scene_prelude(e, "smg_scene_class_maps",
+                               {e->head_out != 3 ? "class probabilities need a 3-class head (head_out == 3)" : nullptr,
+                                n_maps < 1 ? "n_maps < 1" : nullptr,
+                                cls < -1 || cls > 2 ? "cls must be 0, 1, 2 or -1 (all three)" : nullptr},
+                               hm_size, nullptr, affine_host, n_maps, &g)) return rc;
+    const int vec4 = scene_vec4(hm_size, out_dev), tiles = scene_tiles(hm_size);
+    const int64_t P3 = (int64_t)3 * g.OH * g.OW;
+    return scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
+        hipLaunchKernelGGL(scene_class_map_kernel, dim3(tiles, n), dim3(256), (size_t)P3 * sizeof(float), (hipStream_t)stream,
+                           q_dev, P3, m0, a, g, cls, out_dev, vec4);
+    });
 }
 
 int smg_scene_class_argmax(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
                            int* idx_out_dev, float* val_out_dev, void* stream) {
-    if (!e || !q_dev || !affine_host || !idx_out_dev || !val_out_dev) return fail(-22, "NULL argument");
-    if (e->head_out != 3) return fail(-22, "smg_scene_class_argmax: class probabilities need a 3-class head (head_out == 3)");
-    if (n_maps < 1) return fail(-22, "smg_scene_class_argmax: n_maps < 1");
-    if (cls < 0 || cls > 2) return fail(-22, "smg_scene_class_argmax: cls must be 0, 1 or 2");
+    if (!e || !q_dev || !affine_host || !idx_out_dev || !val_out_dev) return fail(-22, "smg_scene_class_argmax: NULL argument");
     SceneGeo g;
-    if (int rc = scene_geometry(e, hm_size, "smg_scene_class_argmax", &g)) return rc;
-    const int64_t npix = (int64_t)hm_size * hm_size;
-    if ((int64_t)n_maps * npix > 0x7fffffff) return fail(-22, "smg_scene_class_argmax: the flattened index does not fit int32");
-    if (int rc = scene_affines_ok(affine_host, n_maps, "smg_scene_class_argmax")) return rc;
-    HIP_OK(hipSetDevice(e->device));
-    const int tiles = (int)((npix + kSceneTile - 1) / kSceneTile);      // <= e->scene_tiles: hm_size <= S / 2
-    for (int m0 = 0; m0 < n_maps; m0 += kSceneMaps) {      // (groups follow each other on the stream: the partials are reused)
-        const int n = std::min(kSceneMaps, n_maps - m0);
-        const SceneAffine a = scene_affine(affine_host, m0, n);
-        hipLaunchKernelGGL(scene_class_argmax_kernel, dim3(tiles, n), dim3(256), (size_t)3 * g.OH * g.OW * sizeof(float), (hipStream_t)stream,
-                           q_dev, m0, a, g, cls, e->scene_val, e->scene_idx);
+    if (int rc = scene_prelude(e, "smg_scene_class_argmax",
+                               {e->head_out != 3 ? "class probabilities need a 3-class head (head_out == 3)" : nullptr,
+                                n_maps < 1 ? "n_maps < 1" : nullptr,
+                                cls < 0 || cls > 2 ? "cls must be 0, 1 or 2" : nullptr},
+                               hm_size, scene_index_fits(n_maps, hm_size), affine_host, n_maps, &g)) return rc;
+    const int tiles = scene_tiles(hm_size);
+    const int64_t P3 = (int64_t)3 * g.OH * g.OW;
+    return scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
+        hipLaunchKernelGGL(scene_class_argmax_kernel, dim3(tiles, n), dim3(256), (size_t)P3 * sizeof(float), (hipStream_t)stream,
+                           q_dev, P3, m0, a, g, cls, e->scene_val, e->scene_idx);
         hipLaunchKernelGGL(scene_argmax_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
                            (const int*)e->scene_idx, tiles * n, m0 > 0 ? 1 : 0, idx_out_dev, val_out_dev);
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
+    });
 }
 
 int smg_loss_scene_ce(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs, int K, const int* pixels_dev,
                       const float* label_dev, float* loss_dev, float* dq_dev, void* stream) {
-    if (!e || !q_dev || !affine_host || !pixels_dev || !label_dev || !loss_dev || !dq_dev) return fail(-22, "NULL argument");
-    if (e->head_out != 3) return fail(-22, "smg_loss_scene_ce: the scene-pixel cross entropy needs a 3-class head (head_out == 3)");
-    if (n_pairs < 1 || n_pairs > e->max_pairs) return fail(-22, "n_pairs exceeds the engine's max_pairs");
-    if (K < 1) return fail(-22, "smg_loss_scene_ce: K < 1");
+    if (!e || !q_dev || !affine_host || !pixels_dev || !label_dev || !loss_dev || !dq_dev) return fail(-22, "smg_loss_scene_ce: NULL argument");
+    const size_t lds = (size_t)3 * e->OH * e->OW * sizeof(double);        // + 14 KB static: under the 64 KB of a plain launch
     SceneGeo g;
-    if (int rc = scene_geometry(e, hm_size, "smg_loss_scene_ce", &g)) return rc;
-    const size_t lds = (size_t)3 * g.OH * g.OW * sizeof(double);        // + 14 KB static: under the 64 KB of a plain launch
-    if (lds > 48 * 1024) return fail(-22, "smg_loss_scene_ce: the class maps' accumulators do not fit the kernel's LDS");
-    if (int rc = scene_affines_ok(affine_host, n_pairs, "smg_loss_scene_ce")) return rc;
-    HIP_OK(hipSetDevice(e->device));
-    for (int m0 = 0; m0 < n_pairs; m0 += kSceneMaps) {
-        const int n = std::min(kSceneMaps, n_pairs - m0);
-        const SceneAffine a = scene_affine(affine_host, m0, n);
-        hipLaunchKernelGGL(loss_scene_ce_kernel, dim3(n), dim3(256), lds, (hipStream_t)stream,
-                           q_dev, m0, a, g, K, pixels_dev, label_dev, loss_dev, dq_dev);
-    }
-    HIP_OK(hipGetLastError());
+    if (int rc = scene_prelude(e, "smg_loss_scene_ce",
+                               {e->head_out != 3 ? "the scene-pixel cross entropy needs a 3-class head (head_out == 3)" : nullptr,
+                                n_pairs < 1 || n_pairs > e->max_pairs ? "n_pairs exceeds the engine's max_pairs" : nullptr,
+                                K < 1 ? "K < 1" : nullptr},
+                               hm_size, lds > 48 * 1024 ? "the class maps' accumulators do not fit the kernel's LDS" : nullptr,
+                               affine_host, n_pairs, &g)) return rc;
+    if (int rc = scene_groups(affine_host, n_pairs, [&](int m0, int n, const SceneAffine& a) {
+            hipLaunchKernelGGL(loss_scene_ce_kernel, dim3(n), dim3(256), lds, (hipStream_t)stream,
+                               q_dev, m0, a, g, K, pixels_dev, label_dev, loss_dev, dq_dev);
+        })) return rc;
     e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0), as after smg_loss_map_ce
     return 0;
 }
@@ -668,23 +660,19 @@ int smg_loss_scene_ce(smg_engine* e, const float* q_dev, const float* affine_hos
 int smg_loss_scene_map_ce(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs,
                           const float* label_dev, float* loss_dev, float* dq_dev, void* stream) {
     if (!e || !q_dev || !affine_host || !label_dev || !loss_dev || !dq_dev) return fail(-22, "smg_loss_scene_map_ce: NULL argument");
-    if (e->head_out != 3) return fail(-22, "smg_loss_scene_map_ce: the scene-frame label-map cross entropy needs a 3-class head (head_out == 3)");
-    if (n_pairs < 1) return fail(-22, "smg_loss_scene_map_ce: n_pairs < 1");
-    if (n_pairs > e->max_pairs) return fail(-22, "smg_loss_scene_map_ce: n_pairs exceeds the engine's max_pairs");
     SceneGeo g;
-    if (int rc = scene_geometry(e, hm_size, "smg_loss_scene_map_ce", &g)) return rc;
-    if (int rc = scene_affines_ok(affine_host, n_pairs, "smg_loss_scene_map_ce")) return rc;
-    HIP_OK(hipSetDevice(e->device));
+    if (int rc = scene_prelude(e, "smg_loss_scene_map_ce",
+                               {e->head_out != 3 ? "the scene-frame label-map cross entropy needs a 3-class head (head_out == 3)" : nullptr,
+                                n_pairs < 1 ? "n_pairs < 1" : nullptr,
+                                n_pairs > e->max_pairs ? "n_pairs exceeds the engine's max_pairs" : nullptr},
+                               hm_size, nullptr, affine_host, n_pairs, &g)) return rc;
     const int P = g.OH * g.OW;
-    for (int m0 = 0; m0 < n_pairs; m0 += kSceneMaps) {      // (groups follow each other on the stream: the partials are reused)
-        const int n = std::min(kSceneMaps, n_pairs - m0);
-        const SceneAffine a = scene_affine(affine_host, m0, n);
-        hipLaunchKernelGGL(loss_scene_map_ce_kernel, dim3(P, n), dim3(256), 0, (hipStream_t)stream,
-                           q_dev, m0, a, g, label_dev, e->scene_gpart, e->scene_lpart, e->scene_cnt);
-        hipLaunchKernelGGL(loss_scene_map_ce_finish_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (const double*)e->scene_gpart,
-                           (const double*)e->scene_lpart, (const int*)e->scene_cnt, P, m0, loss_dev, dq_dev);
-    }
-    HIP_OK(hipGetLastError());
+    if (int rc = scene_groups(affine_host, n_pairs, [&](int m0, int n, const SceneAffine& a) {
+            hipLaunchKernelGGL(loss_scene_map_ce_kernel, dim3(P, n), dim3(256), 0, (hipStream_t)stream,
+                               q_dev, m0, a, g, label_dev, e->scene_gpart, e->scene_lpart, e->scene_cnt);
+            hipLaunchKernelGGL(loss_scene_map_ce_finish_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (const double*)e->scene_gpart,
+                               (const double*)e->scene_lpart, (const int*)e->scene_cnt, P, m0, loss_dev, dq_dev);
+        })) return rc;
     e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0), as after smg_loss_scene_ce
     return 0;
 }

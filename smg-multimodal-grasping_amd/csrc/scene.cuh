@@ -1,9 +1,14 @@
-// scene.cuh - dense Q maps in the SCENE frame: every rotation's [OH][OW] map rotated back and bilinearly upsampled onto the
-// heightmap's pixel grid (smg_scene_maps), the best (rotation, heightmap pixel) without materialising those maps
-// (smg_scene_argmax), and the Huber loss on labelled heightmap pixels with its gradient on the map (smg_loss_scene: K listed pixels;
-// smg_loss_scene_map: a whole label image and weight image); further down the same four for the class logits of a 3-class head
-// (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce: K listed pixels / smg_loss_scene_map_ce: a whole class-label
-// image, the cross entropy).
+// scene.cuh - the head's maps in the SCENE frame: every rotation's [OH][OW] map rotated back and bilinearly interpolated on the
+// heightmap's pixel grid.  In the order of the file:
+//   scene_point / scene_interp / scene_class   the coordinate chain of one heightmap pixel and the value(s) of the map there: one Q
+//                                  value, or the softmax of the three interpolated logits of a 3-class head
+//   scene_walk<PLANES, ARGMAX>     the one tiling behind smg_scene_maps / smg_scene_class_maps (ARGMAX false: the maps are stored)
+//                                  and smg_scene_argmax / smg_scene_class_argmax (true: the best (rotation, pixel), nothing stored)
+//   SceneHuber / SceneCe           the per-point terms of the two losses, each written once
+//   scene_list_walk                the loss on K LISTED pixels per pair (smg_loss_scene_ce; smg_loss_scene's kernel keeps the same
+//                                  loop in a copy of its own, for the reason its comment gives)
+//   scene_box_walk                 the loss on a whole label IMAGE per pair (smg_loss_scene_map, smg_loss_scene_map_ce)
+// The __global__ kernels are thin instantiations of these; the block trees they end in are block_argmax (elem.cuh) and block_sum.
 //
 // Geometry (include/smg_hip.h has the derivation), all in double, coordinates (x = column, y = row):
 //   heightmap pixel (iy, ix) -> centre of its 2x2 block of the padded input   x = 2 ix + 0.5 + pad
@@ -50,80 +55,132 @@ __device__ __forceinline__ double scene_interp(const ScenePoint& p, QPtr Q, int 
     return (1.0 - p.fy) * ((1.0 - p.fx) * q00 + p.fx * q01) + p.fy * ((1.0 - p.fx) * q10 + p.fx * q11);
 }
 
-// scene_map_kernel / scene_argmax_kernel.  One workgroup = one tile of kSceneTile consecutive pixels of one scene-frame map (blockIdx.y = map of this launch).  The map is
-// staged in LDS (OH x OW floats, dynamic), the matrix sits in registers.  ARGMAX == false: thread t of pass i owns pixels
-// 4 (256 i + t) .. + 3 of the tile and stores them as one 16-byte unit (`vec4`: hm^2 a multiple of 4 and `out` 16-byte aligned;
-// else four guarded 4-byte stores).  ARGMAX == true: nothing is stored; the workgroup's best (value, index into [maps][hm][hm]) by
-// argmax_better's rules - invalid pixels are skipped, not compared - goes to slot blockIdx.y * gridDim.x + blockIdx.x of the
-// partial arrays.
-template <bool ARGMAX>
-__device__ __forceinline__ void scene_walk(const float* q, int64_t map_stride, int map0, const SceneAffine& aff,
-                                           const SceneGeo& g, float* out, int vec4, float* part_val, int* part_idx) {
+// The fixed sum tree over a workgroup's 256 slots of one or more LDS arrays (thread t's own in r[t]): the sums end in slot 0 of
+// each.  The pairing order is part of the results (double sums, bit for bit).
+template <class... T>
+__device__ __forceinline__ void block_sum(int t, T*... r) {
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) { ((r[t] += r[t + s]), ...); }
+        __syncthreads();
+    }
+}
+
+// The reactive net's three class planes at a scene point (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce /
+// smg_loss_scene_map_ce).  The three LOGIT planes of a map ([3][OH][OW], `P` = OH * OW apart) are interpolated at the scene point - same corners, same
+// fractions - and the softmax is taken there, in double: z_c = bilinear(plane c), m = max z, e_c = exp(z_c - m), s = e_0 + e_1 + e_2,
+// P_c = e_c / s rounded to fp32 once.  Logits are interpolated, not probabilities: the cross entropy (SceneCe) is that of these very
+// z, so picking and training see one function of the head output.  Nothing is special-cased: a NaN corner, or an inf that gives
+// inf - inf, makes s NaN and with it all three probabilities, as torch.softmax does in fp64.
+struct SceneClass { double z0, z1, z2, m, e0, e1, e2, s; };
+
+template <class QPtr>
+__device__ __forceinline__ SceneClass scene_class(const ScenePoint& p, QPtr Q, int P, int OW) {
+    SceneClass c;
+    c.z0 = scene_interp(p, Q, OW); c.z1 = scene_interp(p, Q + P, OW); c.z2 = scene_interp(p, Q + 2 * P, OW);
+    c.m = fmax(c.z0, fmax(c.z1, c.z2));
+    c.e0 = exp(c.z0 - c.m); c.e1 = exp(c.z1 - c.m); c.e2 = exp(c.z2 - c.m);
+    c.s = c.e0 + c.e1 + c.e2;
+    return c;
+}
+// P(class cls) of that point: the one expression the map and the argmax kernel take their values from (so the argmax is bit-equal to the maps).
+// (By value and as two flat selects: a chain of conditionals on the members of a reference became an indexed load from a copy of
+// the struct in scratch memory, 72 bytes per lane.)
+__device__ __forceinline__ float scene_class_prob(const SceneClass c, int cls) {
+    const double e01 = cls == 0 ? c.e0 : c.e1;
+    return (float)((cls == 2 ? c.e2 : e01) / c.s);
+}
+
+// The four map / argmax kernels.  One workgroup = one tile of kSceneTile consecutive pixels of one scene-frame map (blockIdx.y = map
+// of this launch, `map_stride` floats apart in q).  The map's PLANES planes are staged in LDS (PLANES x OH x OW floats, dynamic; the
+// three logit planes of a class map lie OH * OW apart, so its map_stride is 3 OH OW), the matrix sits in registers, scene_point runs
+// once per pixel.  PLANES == 1: the value is the interpolated Q value, `cls` is not read.  PLANES == 3: P(class cls) of the softmax,
+// or with cls == -1 all three.
+// ARGMAX == false: thread t of pass i owns pixels 4 (256 i + t) .. + 3 of the tile and stores them as one 16-byte unit (`vec4`: hm^2
+// a multiple of 4 and `out` 16-byte aligned; else four guarded 4-byte stores) to out [maps][hm][hm], or with cls == -1 to out
+// [maps][3][hm][hm] - a thread's pixel group goes to three addresses hm^2 apart; an invalid pixel is -inf in every plane.
+// ARGMAX == true (cls in {0, 1, 2}): nothing is stored; the workgroup's best (value, index into [maps][hm][hm]) by argmax_better's
+// rules - invalid pixels are skipped, not compared - goes to slot blockIdx.y * gridDim.x + blockIdx.x of the partial arrays.
+template <int PLANES, bool ARGMAX>
+__device__ __forceinline__ void scene_walk(const float* q, int64_t map_stride, int map0, const SceneAffine& aff, const SceneGeo& g, int cls,
+                                           float* out, int vec4, float* part_val, int* part_idx) {
     extern __shared__ float sq[];
     __shared__ float bv[256];
     __shared__ int bi[256];
     const int t = threadIdx.x, m = blockIdx.y;
     const int P = g.OH * g.OW;
     const float* qm = q + (int64_t)(map0 + m) * map_stride;
-    for (int i = t; i < P; i += 256) sq[i] = qm[i];
+    for (int i = t; i < PLANES * P; i += 256) sq[i] = qm[i];
     __syncthreads();
     const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
     const int npix = g.hm * g.hm;                       // (the host refuses maps of 2^31 pixels or more)
     const int base = blockIdx.x * kSceneTile;
+    const int planes = PLANES == 3 && cls < 0 ? 3 : 1;  // planes stored per map
     float best = -INFINITY; int at = 0x7fffffff;
     for (int pass = 0; pass < kSceneTile / 1024; ++pass) {
         const int i0 = base + 4 * (pass * 256 + t);
         if (i0 >= npix) break;
         int iy = i0 / g.hm, ix = i0 - iy * g.hm;
-        float v[4];
+        float v[PLANES][4];
 #pragma unroll
         for (int k = 0; k < 4; ++k, ++ix) {
             const int i = i0 + k;
             if (ix == g.hm) { ix = 0; ++iy; }
-            v[k] = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < PLANES; ++c) v[c][k] = -INFINITY;
             if (i < npix) {
                 const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
                 if (p.valid) {
-                    v[k] = (float)scene_interp(p, sq, g.OW);
+                    if constexpr (PLANES == 1) v[0][k] = (float)scene_interp(p, sq, g.OW);
+                    else {
+                        const SceneClass c = scene_class(p, sq, P, g.OW);
+                        if (cls < 0) { v[0][k] = scene_class_prob(c, 0); v[1][k] = scene_class_prob(c, 1); v[2][k] = scene_class_prob(c, 2); }
+                        else v[0][k] = scene_class_prob(c, cls);
+                    }
                     if (ARGMAX) {
                         const int flat = (map0 + m) * npix + i;       // (< 2^31: checked by the host)
-                        if (argmax_better(v[k], flat, best, at)) { best = v[k]; at = flat; }
+                        if (argmax_better(v[0][k], flat, best, at)) { best = v[0][k]; at = flat; }
                     }
                 }
             }
         }
         if (!ARGMAX) {
-            float* o = out + (int64_t)(map0 + m) * npix + i0;
-            if (vec4) *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-            else
-                for (int k = 0; k < 4; ++k) if (i0 + k < npix) o[k] = v[k];
+#pragma unroll
+            for (int c = 0; c < PLANES; ++c) {
+                if (c >= planes) break;
+                float* o = out + ((int64_t)(map0 + m) * planes + c) * npix + i0;
+                if (vec4) *reinterpret_cast<float4*>(o) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+                else
+                    for (int k = 0; k < 4; ++k) if (i0 + k < npix) o[k] = v[c][k];
+            }
         }
     }
     if (ARGMAX) {
         bv[t] = best; bi[t] = at;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (t < s) {
-                const float x = bv[t + s]; const int j = bi[t + s];
-                if (j != 0x7fffffff && argmax_better(x, j, bv[t], bi[t])) { bv[t] = x; bi[t] = j; }
-            }
-            __syncthreads();
-        }
+        block_argmax(bv, bi, t);
         if (t == 0) { const int slot = blockIdx.y * gridDim.x + blockIdx.x; part_val[slot] = bv[0]; part_idx[slot] = bi[0]; }
     }
 }
 static __global__ __launch_bounds__(256) void scene_map_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
                                                                const SceneGeo g, float* out, int vec4) {
-    scene_walk<false>(q, map_stride, map0, aff, g, out, vec4, nullptr, nullptr);
+    scene_walk<1, false>(q, map_stride, map0, aff, g, 0, out, vec4, nullptr, nullptr);
 }
 static __global__ __launch_bounds__(256) void scene_argmax_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
                                                                   const SceneGeo g, float* part_val, int* part_idx) {
-    scene_walk<true>(q, map_stride, map0, aff, g, nullptr, 0, part_val, part_idx);
+    scene_walk<1, true>(q, map_stride, map0, aff, g, 0, nullptr, 0, part_val, part_idx);
+}
+static __global__ __launch_bounds__(256) void scene_class_map_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                     const SceneGeo g, int cls, float* out, int vec4) {
+    scene_walk<3, false>(q, map_stride, map0, aff, g, cls, out, vec4, nullptr, nullptr);
+}
+static __global__ __launch_bounds__(256) void scene_class_argmax_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                        const SceneGeo g, int cls, float* part_val, int* part_idx) {
+    scene_walk<3, true>(q, map_stride, map0, aff, g, cls, nullptr, 0, part_val, part_idx);
 }
 
-// The second launch of smg_scene_argmax: one workgroup reduces the n partials (thread t takes slots t, t + 256, ... in that
-// order) and, with `carry`, the result a previous group of maps left in the outputs.  Empty slots hold index 0x7fffffff; when
-// nothing at all was valid the result is index -1, value -inf.
+// The second launch of smg_scene_argmax / smg_scene_class_argmax: one workgroup reduces the n partials (thread t takes slots t,
+// t + 256, ... in that order) and, with `carry`, the result a previous group of maps left in the outputs.  Empty slots hold index
+// 0x7fffffff; when nothing at all was valid the result is index -1, value -inf.
 static __global__ __launch_bounds__(256) void scene_argmax_reduce_kernel(const float* part_val, const int* part_idx, int n, int carry,
                                                                          int* idx_out, float* val_out) {
     __shared__ float bv[256];
@@ -136,25 +193,126 @@ static __global__ __launch_bounds__(256) void scene_argmax_reduce_kernel(const f
         if (j != 0x7fffffff && argmax_better(x, j, best, at)) { best = x; at = j; }
     }
     bv[t] = best; bi[t] = at;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) {
-            const float x = bv[t + s]; const int j = bi[t + s];
-            if (j != 0x7fffffff && argmax_better(x, j, bv[t], bi[t])) { bv[t] = x; bi[t] = j; }
-        }
-        __syncthreads();
-    }
+    block_argmax(bv, bi, t);
     if (t == 0) { *idx_out = bi[0] == 0x7fffffff ? -1 : bi[0]; *val_out = bv[0]; }
 }
 
-// smg_loss_scene: K labelled heightmap pixels per pair (one workgroup per pair, blockIdx.x = pair of this launch).  With v_k the
-// interpolated value of point k (double, not rounded), d = v_k - label_k and the Huber of code/trainer.py:345-348:
-//     loss[j] = sum_k w_k huber(d)          dq[j][oy][ox] = sum_k w_k huber'(d) * (bilinear weight of (oy, ox) at point k)
-// Gather form: the points are taken 256 at a time - thread t works point t of the group out into LDS (corner, fractions, w huber')
-// - then every thread walks the group in index order for the map elements it owns (t, t + 256, ...), adding in double to its own
-// LDS accumulators.  No atomics: duplicate points simply add twice, and every element of dq is written once, zeros included,
-// rounded once.  A point that is invalid in the pair's rotation, or outside the heightmap, contributes nothing; a weight of
-// exactly 0 masks its point.  Dynamic LDS: OH * OW doubles (accumulators) + OH * OW floats (the map).
+// ---- the two losses: what one labelled point contributes, each written once ----
+// A loss has three members.  mask(at) reads what decides whether the point whose label (and weight) sit at index `at` counts -
+// apart from the geometry, so the list form issues this load beside the one of its pixel; counts(m) decides, before the map is
+// read; terms(g, p, m, at, home, l, gk) on a valid counted point p gives l = its loss term (needed where `home` is set only) and
+// gk[c] = the derivative of the pair's unnormalised loss by the interpolated value of plane c.  kPlanes planes, Q = the pair's
+// map(s), in LDS or global.  (l by reference and gk as a pointer to the caller's array: both stay in registers, scratch is 0.)
+//
+// The Huber of code/trainer.py:345-348 on one Q plane, weighted: d = v - label in double (v not rounded), l = w huber(d),
+// gk = w huber'(d).  weight == nullptr is all ones; a weight of exactly 0 masks its point (the label under it is not read).
+struct HuberTerm { double l, gr; };
+__device__ __forceinline__ HuberTerm scene_huber(double d) {
+    HuberTerm h;
+    if (fabs(d) < 1.0) { h.l = 0.5 * (d * d); h.gr = d; }
+    else { h.l = fabs(d) - 0.5; h.gr = d > 0.0 ? 1.0 : -1.0; }
+    return h;
+}
+struct SceneHuber {
+    static constexpr int kPlanes = 1;
+    const float *Q, *label, *weight;
+    __device__ __forceinline__ double mask(int64_t at) const { return weight ? (double)weight[at] : 1.0; }
+    __device__ __forceinline__ bool counts(double w) const { return w != 0.0; }
+    __device__ __forceinline__ void terms(const SceneGeo& g, const ScenePoint& p, double w, int64_t at, bool home, double& l, double* gk) const {
+        const HuberTerm h = scene_huber(scene_interp(p, Q, g.OW) - (double)label[at]);
+        l = w * h.l; gk[0] = w * h.gr;
+    }
+};
+// The cross entropy (CrossEntropyLoss2d, class weights {1, 1, 0}) of the three interpolated logits: a point COUNTS when its label
+// is exactly 0.f or 1.f; every other label (class 2, NaN, any other value) masks it, whatever logits lie under it.  Per counted
+// point, in double:     nll = (log(s) + m) - z_y        g_c = e_c / s - [c == y]
+// (the logarithm is taken under `home` alone).  The caller counts the points and divides by their number W.
+struct CeTerm { double nll, g0, g1, g2; };
+__device__ __forceinline__ CeTerm scene_ce(const SceneClass c, float lf, bool home) {       // (by value: see scene_class_prob)
+    CeTerm r;
+    r.nll = 0.0;
+    if (home) r.nll = (log(c.s) + c.m) - (lf == 0.f ? c.z0 : c.z1);
+    r.g0 = c.e0 / c.s - (lf == 0.f ? 1.0 : 0.0); r.g1 = c.e1 / c.s - (lf == 1.f ? 1.0 : 0.0); r.g2 = c.e2 / c.s;
+    return r;
+}
+struct SceneCe {
+    static constexpr int kPlanes = 3;
+    const float *Q, *label;
+    __device__ __forceinline__ float mask(int64_t at) const { return label[at]; }
+    __device__ __forceinline__ bool counts(float lf) const { return lf == 0.f || lf == 1.f; }
+    __device__ __forceinline__ void terms(const SceneGeo& g, const ScenePoint& p, float lf, int64_t at, bool home, double& l, double* gk) const {
+        const CeTerm r = scene_ce(scene_class(p, Q, g.OH * g.OW, g.OW), lf, home);
+        l = r.nll; gk[0] = r.g0; gk[1] = r.g1; gk[2] = r.g2;
+    }
+};
+
+// ---- the list form: K labelled heightmap pixels per pair (smg_loss_scene_ce, and in its own copy smg_loss_scene) ----
+// One workgroup per pair (blockIdx.x = pair of this launch); `sacc` = kPlanes x OH x OW double accumulators in dynamic LDS, zeroed
+// by the caller.  Gather form: the points are taken 256 at a time - thread t works point t of the group out into LDS (corner,
+// fractions, gk) - then every thread walks the group in index order for the map elements it owns (t, t + 256, ... in every plane),
+// adding gk[c] * (bilinear weight of the element at the point) in double to its own accumulators.  No atomics: duplicate points
+// simply add twice, and every element is written once.  A point outside the heightmap, invalid in the pair's rotation or masked by
+// the loss contributes nothing; the others add their loss term to the thread's `lsum` and 1 to its `cnt`.
+template <class Loss>
+__device__ __forceinline__ void scene_list_walk(const SceneGeo& g, double a00, double a01, double a10, double a11, int j, int K, const int* pixels,
+                                                const Loss& L, double* sacc, double& lsum, int& cnt) {
+    constexpr int C = Loss::kPlanes;
+    __shared__ double p_fy[256], p_fx[256], p_g[C][256];
+    __shared__ int p_o[256];
+    const int t = threadIdx.x;
+    const int P = g.OH * g.OW;
+    for (int k0 = 0; k0 < K; k0 += 256) {
+        const int k = k0 + t;
+        int o = -1; double fy = 0.0, fx = 0.0, gk[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) gk[c] = 0.0;
+        if (k < K) {
+            const int64_t at = (int64_t)j * K + k;
+            const int iy = pixels[2 * at], ix = pixels[2 * at + 1];
+            const auto m = L.mask(at);
+            if (L.counts(m) && iy >= 0 && iy < g.hm && ix >= 0 && ix < g.hm) {
+                const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
+                if (p.valid) {
+                    double l;
+                    L.terms(g, p, m, at, true, l, gk);
+                    lsum += l; ++cnt;
+                    o = p.y0 * g.OW + p.x0; fy = p.fy; fx = p.fx;
+                }
+            }
+        }
+        p_o[t] = o; p_fy[t] = fy; p_fx[t] = fx;
+#pragma unroll
+        for (int c = 0; c < C; ++c) p_g[c][t] = gk[c];
+        __syncthreads();
+        const int n = min(256, K - k0);
+        for (int i = t; i < P; i += 256) {
+            const int ey = i / g.OW, ex = i - ey * g.OW;
+            double acc[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = sacc[c * P + i];
+            for (int kk = 0; kk < n; ++kk) {
+                const int oo = p_o[kk];
+                if (oo < 0) continue;
+                const int y0 = oo / g.OW, x0 = oo - y0 * g.OW;
+                const int dy = ey - y0, dx = ex - x0;
+                if ((unsigned)dy > 1u || (unsigned)dx > 1u) continue;
+                const double wy = dy ? p_fy[kk] : 1.0 - p_fy[kk], wx = dx ? p_fx[kk] : 1.0 - p_fx[kk];
+                const double wgt = wy * wx;
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[c] += p_g[c][kk] * wgt;
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) sacc[c * P + i] = acc[c];
+        }
+        __syncthreads();
+    }
+}
+
+// smg_loss_scene: the list form with the Huber - loss[j] = sum_k w_k huber(d_k), dq[j][oy][ox] = the accumulator, unnormalised,
+// every element written once, zeros included, rounded once.  The map is staged in LDS behind the accumulators: dynamic LDS OH * OW
+// doubles + OH * OW floats.  This kernel keeps a loop of its own, the same as scene_list_walk's on one plane: as an instantiation
+// of scene_list_walk it ran 0.5 to 1.8 % slower at K = 409 600 (291.3 to 293.8 ms against 288.4 to 289.8, repeats 0.3 to 2 ms
+// apart) with the same instructions in the inner loop.
 static __global__ __launch_bounds__(256) void loss_scene_kernel(const float* q, int pair0, const SceneAffine aff, const SceneGeo g, int K,
                                                                 const int* pixels, const float* label, const float* weight,
                                                                 float* loss, float* dq) {
@@ -181,11 +339,9 @@ static __global__ __launch_bounds__(256) void loss_scene_kernel(const float* q, 
                 const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
                 if (p.valid) {
                     const double d = scene_interp(p, sq, g.OW) - (double)label[at];
-                    double l, gr;
-                    if (fabs(d) < 1.0) { l = 0.5 * (d * d); gr = d; }
-                    else { l = fabs(d) - 0.5; gr = d > 0.0 ? 1.0 : -1.0; }
-                    lsum += w * l;
-                    o = p.y0 * g.OW + p.x0; fy = p.fy; fx = p.fx; gk = w * gr;
+                    const HuberTerm h = scene_huber(d);
+                    lsum += w * h.l;
+                    o = p.y0 * g.OW + p.x0; fy = p.fy; fx = p.fx; gk = w * h.gr;
                 }
             }
         }
@@ -209,19 +365,40 @@ static __global__ __launch_bounds__(256) void loss_scene_kernel(const float* q, 
         __syncthreads();
     }
     red[t] = lsum;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
+    block_sum(t, red);
     if (t == 0) loss[j] = (float)red[0];
     float* dj = dq + (int64_t)j * P;
     for (int i = t; i < P; i += 256) dj[i] = (float)sacc[i];
 }
 
-// The heightmap box of map element (oy, ox), shared by the two label-map kernels (loss_scene_map_kernel, loss_scene_map_ce_kernel):
-// pixels bx0 .. bx0 + bw - 1 of rows by0 .., n = bw * rows of them in row-major order (0 when the box is empty).  The kernels' comment
-// below has the construction.
+// smg_loss_scene_ce: W = the number of counted points; loss[j] = (sum nll_k) / W and dq[j][c][oy][ox] = accumulator / W: summed
+// unnormalised in point order, divided once, rounded once; W == 0 gives loss 0 and dq 0.  Dynamic LDS: the 3 OH OW double
+// accumulators only - the logits are read from global memory (a few corners per point of a map that sits in L2), which keeps
+// 38 x 38 maps at 35 KB + 14 KB static.
+static __global__ __launch_bounds__(256) void loss_scene_ce_kernel(const float* q, int pair0, const SceneAffine aff, const SceneGeo g, int K,
+                                                                   const int* pixels, const float* label, float* loss, float* dq) {
+    extern __shared__ double sacc[];
+    __shared__ double red[256];
+    __shared__ int rcnt[256];
+    const int t = threadIdx.x, m = blockIdx.x, j = pair0 + m;
+    const int P = g.OH * g.OW;
+    for (int i = t; i < 3 * P; i += 256) sacc[i] = 0.0;
+    __syncthreads();
+    double lsum = 0.0; int cnt = 0;
+    scene_list_walk(g, (double)aff.a[m][0], (double)aff.a[m][1], (double)aff.a[m][2], (double)aff.a[m][3], j, K, pixels,
+                    SceneCe{q + (int64_t)j * 3 * P, label}, sacc, lsum, cnt);
+    red[t] = lsum; rcnt[t] = cnt;
+    block_sum(t, red, rcnt);
+    const int W = rcnt[0];
+    const double dW = (double)W;
+    if (t == 0) loss[j] = W > 0 ? (float)(red[0] / dW) : 0.f;
+    float* dj = dq + (int64_t)j * 3 * P;
+    for (int i = t; i < 3 * P; i += 256) dj[i] = W > 0 ? (float)(sacc[i] / dW) : 0.f;
+}
+
+// ---- the image form: a whole [hm][hm] label image per pair (smg_loss_scene_map, smg_loss_scene_map_ce) ----
+// The heightmap box of map element (oy, ox): pixels bx0 .. bx0 + bw - 1 of rows by0 .., n = bw * rows of them in row-major order
+// (0 when the box is empty).  scene_box_walk's comment below has the construction.
 struct SceneBox { int bx0, by0, bw, n; };
 __device__ __forceinline__ SceneBox scene_element_box(const SceneGeo& g, double a00, double a01, double a10, double a11, int oy, int ox) {
     // the box: the map square [ox - 1, ox + 1] x [oy - 1, oy + 1] (clipped) pushed back onto the heightmap
@@ -251,57 +428,61 @@ __device__ __forceinline__ SceneBox scene_element_box(const SceneGeo& g, double 
     return b;
 }
 
-// smg_loss_scene_map: loss_scene_kernel's Huber with a whole [hm][hm] label image and weight image per pair instead of K listed
-// pixels - every pixel that is valid in the pair's rotation and whose weight is not exactly 0 is a point:
-//     loss[j] = sum_pixels w huber(v - label)      dq[j][oy][ox] = sum_pixels w huber'(v - label) * (bilinear weight of (oy, ox) at the pixel)
-// Gather by map element: one workgroup owns one (pair, oy, ox) - blockIdx.x = oy * OW + ox, blockIdx.y = pair of this launch.  Only
+// Every pixel of the image that is valid in the pair's rotation and not masked by the loss is a point.  Gather by map element: one
+// workgroup owns one (pair, oy, ox) - blockIdx.x = oy * OW + ox, blockIdx.y = pair of this launch.  Only
 // pixels whose corner (y0, x0) lies in {oy - 1, oy} x {ox - 1, ox} touch that element: they lie at map coordinates
 // [ox - 1, ox + 1] x [oy - 1, oy + 1], clipped to the map.  The four corners of that square go back through the chain with the
 // inverse of A^T (u = A^-T p, whatever the 2x2 matrix is: scene_point asks for no rotation); the heightmap bounding box of the
 // four images, widened by one pixel per side and clipped to the heightmap, holds every such pixel (for a rotation about 34 x 34 at
 // a multiple of a quarter turn, 46 x 46 at 45 degrees).  A matrix without a usable inverse (determinant 0, not finite, or below
-// 1e-6 of the squared norm) maps whole lines of pixels onto one map point: the box is then the whole heightmap.  Thread t takes pixels t, t + 256, ... of the box in
-// row-major order, runs scene_point on each, keeps the valid ones that touch the element, and adds in double; a fixed tree over
-// the 256 threads follows.  The weight is read only under a valid touching pixel, the label only where the weight is not 0, the
-// map's four corners from global memory (the map sits in L2).  No atomics, every element of dq written once, rounded once:
-// identical calls are bit-identical, and a pair's results do not depend on which launch carries it.
-// The loss counts a pixel at its HOME element (y0, x0) only; the per-element sums go to `lpart` ([pairs of this launch][OH * OW]
-// doubles, every slot written) for loss_scene_map_reduce_kernel.
-static __global__ __launch_bounds__(256) void loss_scene_map_kernel(const float* q, int pair0, const SceneAffine aff, const SceneGeo g,
-                                                                    const float* label, const float* weight, double* lpart, float* dq) {
-    __shared__ double racc[256], rloss[256];
-    const int t = threadIdx.x, m = blockIdx.y, j = pair0 + m, el = blockIdx.x;
-    const int P = g.OH * g.OW;
-    const int oy = el / g.OW, ox = el - oy * g.OW;
-    const float* qj = q + (int64_t)j * P;
-    const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
+// 1e-6 of the squared norm) maps whole lines of pixels onto one map point: the box is then the whole heightmap.  Thread t takes
+// pixels t, t + 256, ... of the box in row-major order, runs scene_point on each, keeps the valid ones that touch the element, and
+// adds gk[c] * (bilinear weight of the element at the pixel) in double to its acc[c]; the caller's fixed tree over the 256 threads
+// follows.  Label and weight are read only under a valid touching pixel, the map's corners only under an unmasked one and from global
+// memory (the map sits in L2; for the twelve corner logits of the cross entropy, staging the 27 logits around the element in LDS
+// measured 0.755 against 0.776 ms at S = 1824, inside the spread between repeats, and was not kept).  A pixel's gradient share goes to
+// every element it touches, so its terms are evaluated by up to four workgroups: the price of a form without atomics, in which
+// identical calls are bit-identical and a pair's results do not depend on which launch carries it.  Its loss term and its count go to
+// its HOME element (y0, x0) only.
+template <class Loss>
+__device__ __forceinline__ void scene_box_walk(const SceneGeo& g, double a00, double a01, double a10, double a11, int j, int oy, int ox,
+                                               const Loss& L, double (&acc)[Loss::kPlanes], double& lsum, int& cnt) {
     const SceneBox box = scene_element_box(g, a00, a01, a10, a11, oy, ox);
     const int bx0 = box.bx0, by0 = box.by0, bw = box.bw, n = box.n;
-    double acc = 0.0, lsum = 0.0;
-    for (int i = t; i < n; i += 256) {
+    for (int i = threadIdx.x; i < n; i += 256) {
         const int ry = i / bw;
         const int iy = by0 + ry, ix = bx0 + (i - ry * bw);
         const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
         if (!p.valid) continue;
         const int dy = oy - p.y0, dx = ox - p.x0;
         if ((unsigned)dy > 1u || (unsigned)dx > 1u) continue;
+        const bool home = dy == 0 && dx == 0;
         const int64_t at = ((int64_t)j * g.hm + iy) * g.hm + ix;
-        const double w = weight ? (double)weight[at] : 1.0;
-        if (w == 0.0) continue;
-        const double d = scene_interp(p, qj, g.OW) - (double)label[at];
-        double l, gr;
-        if (fabs(d) < 1.0) { l = 0.5 * (d * d); gr = d; }
-        else { l = fabs(d) - 0.5; gr = d > 0.0 ? 1.0 : -1.0; }
-        if (dy == 0 && dx == 0) lsum += w * l;
+        const auto m = L.mask(at);
+        if (!L.counts(m)) continue;
+        double l, gk[Loss::kPlanes];
+        L.terms(g, p, m, at, home, l, gk);
+        if (home) { lsum += l; ++cnt; }
         const double wy = dy ? p.fy : 1.0 - p.fy, wx = dx ? p.fx : 1.0 - p.fx;
-        acc += (w * gr) * (wy * wx);
+        const double wgt = wy * wx;
+#pragma unroll
+        for (int c = 0; c < Loss::kPlanes; ++c) acc[c] += gk[c] * wgt;
     }
-    racc[t] = acc; rloss[t] = lsum;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) { racc[t] += racc[t + s]; rloss[t] += rloss[t + s]; }
-        __syncthreads();
-    }
+}
+
+// smg_loss_scene_map: loss_scene_kernel's Huber on the image - loss[j] = sum_pixels w huber(v - label), dq[j][oy][ox] = the
+// element's sum, written once, rounded once.  The per-element loss sums go to `lpart` ([pairs of this launch][OH * OW] doubles,
+// every slot written) for loss_scene_map_reduce_kernel.
+static __global__ __launch_bounds__(256) void loss_scene_map_kernel(const float* q, int pair0, const SceneAffine aff, const SceneGeo g,
+                                                                    const float* label, const float* weight, double* lpart, float* dq) {
+    __shared__ double racc[256], rloss[256];
+    const int t = threadIdx.x, m = blockIdx.y, j = pair0 + m, el = blockIdx.x;
+    const int P = g.OH * g.OW;
+    double acc[1] = {0.0}, lsum = 0.0; int cnt = 0;
+    scene_box_walk(g, (double)aff.a[m][0], (double)aff.a[m][1], (double)aff.a[m][2], (double)aff.a[m][3], j, el / g.OW, el % g.OW,
+                   SceneHuber{q + (int64_t)j * P, label, weight}, acc, lsum, cnt);
+    racc[t] = acc[0]; rloss[t] = lsum;
+    block_sum(t, racc, rloss);
     if (t == 0) { dq[(int64_t)j * P + el] = (float)racc[0]; lpart[(int64_t)m * P + el] = rloss[0]; }
 }
 
@@ -313,244 +494,26 @@ static __global__ __launch_bounds__(256) void loss_scene_map_reduce_kernel(const
     double s = 0.0;
     for (int i = t; i < P; i += 256) s += lpart[(int64_t)m * P + i];
     red[t] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (t < k) red[t] += red[t + k];
-        __syncthreads();
-    }
+    block_sum(t, red);
     if (t == 0) loss[pair0 + m] = (float)red[0];
 }
 
-// ---- the reactive net's three class planes in the scene frame (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce / smg_loss_scene_map_ce) ----
-// The three LOGIT planes of a map ([3][OH][OW], `P` = OH * OW apart) are interpolated at the scene point - same corners, same
-// fractions - and the softmax is taken there, in double: z_c = bilinear(plane c), m = max z, e_c = exp(z_c - m), s = e_0 + e_1 + e_2,
-// P_c = e_c / s rounded to fp32 once.  Logits are interpolated, not probabilities: the cross entropy below is that of these very
-// z, so picking and training see one function of the head output.  Nothing is special-cased: a NaN corner, or an inf that gives
-// inf - inf, makes s NaN and with it all three probabilities, as torch.softmax does in fp64.
-struct SceneClass { double z0, z1, z2, m, e0, e1, e2, s; };
-
-template <class QPtr>
-__device__ __forceinline__ SceneClass scene_class(const ScenePoint& p, QPtr Q, int P, int OW) {
-    SceneClass c;
-    c.z0 = scene_interp(p, Q, OW); c.z1 = scene_interp(p, Q + P, OW); c.z2 = scene_interp(p, Q + 2 * P, OW);
-    c.m = fmax(c.z0, fmax(c.z1, c.z2));
-    c.e0 = exp(c.z0 - c.m); c.e1 = exp(c.z1 - c.m); c.e2 = exp(c.z2 - c.m);
-    c.s = c.e0 + c.e1 + c.e2;
-    return c;
-}
-// P(class cls) of that point: the one expression both kernels below take their values from (so the argmax is bit-equal to the maps).
-// (By value and as two flat selects: a chain of conditionals on the members of a reference became an indexed load from a copy of
-// the struct in scratch memory, 72 bytes per lane.)
-__device__ __forceinline__ float scene_class_prob(const SceneClass c, int cls) {
-    const double e01 = cls == 0 ? c.e0 : c.e1;
-    return (float)((cls == 2 ? c.e2 : e01) / c.s);
-}
-
-// scene_class_map_kernel / scene_class_argmax_kernel: scene_walk's tiling (one workgroup = kSceneTile consecutive pixels of one
-// map, blockIdx.y = map of this launch, the matrix in registers) with all three planes of the map staged in LDS (3 OH OW floats,
-// dynamic); scene_point runs once per pixel.  q is [maps][3][OH][OW].  ARGMAX == false: cls in {0, 1, 2} stores P(class cls) to
-// out [maps][hm][hm], cls == -1 all three to out [maps][3][hm][hm] - a thread's pixel group goes to three addresses hm^2 apart -
-// as 16-byte units (`vec4`) or guarded 4-byte stores; an invalid pixel is -inf in every plane.  ARGMAX == true: cls in {0, 1, 2},
-// nothing stored, the workgroup's best (P(class cls), index into [maps][hm][hm]) goes to its slot of the partial arrays exactly
-// as in scene_walk, for scene_argmax_reduce_kernel.
-template <bool ARGMAX>
-__device__ __forceinline__ void scene_class_walk(const float* q, int map0, const SceneAffine& aff, const SceneGeo& g, int cls,
-                                                 float* out, int vec4, float* part_val, int* part_idx) {
-    extern __shared__ float sq[];
-    __shared__ float bv[256];
-    __shared__ int bi[256];
-    const int t = threadIdx.x, m = blockIdx.y;
-    const int P = g.OH * g.OW;
-    const float* qm = q + (int64_t)(map0 + m) * 3 * P;
-    for (int i = t; i < 3 * P; i += 256) sq[i] = qm[i];
-    __syncthreads();
-    const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
-    const int npix = g.hm * g.hm;                       // (the host refuses maps of 2^31 pixels or more)
-    const int base = blockIdx.x * kSceneTile;
-    const int planes = cls < 0 ? 3 : 1;
-    float best = -INFINITY; int at = 0x7fffffff;
-    for (int pass = 0; pass < kSceneTile / 1024; ++pass) {
-        const int i0 = base + 4 * (pass * 256 + t);
-        if (i0 >= npix) break;
-        int iy = i0 / g.hm, ix = i0 - iy * g.hm;
-        float v[3][4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k, ++ix) {
-            const int i = i0 + k;
-            if (ix == g.hm) { ix = 0; ++iy; }
-            v[0][k] = v[1][k] = v[2][k] = -INFINITY;
-            if (i < npix) {
-                const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
-                if (p.valid) {
-                    const SceneClass c = scene_class(p, sq, P, g.OW);
-                    if (cls < 0) { v[0][k] = scene_class_prob(c, 0); v[1][k] = scene_class_prob(c, 1); v[2][k] = scene_class_prob(c, 2); }
-                    else v[0][k] = scene_class_prob(c, cls);
-                    if (ARGMAX) {
-                        const int flat = (map0 + m) * npix + i;       // (< 2^31: checked by the host)
-                        if (argmax_better(v[0][k], flat, best, at)) { best = v[0][k]; at = flat; }
-                    }
-                }
-            }
-        }
-        if (!ARGMAX) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                if (c >= planes) break;
-                float* o = out + ((int64_t)(map0 + m) * planes + c) * npix + i0;
-                if (vec4) *reinterpret_cast<float4*>(o) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
-                else
-                    for (int k = 0; k < 4; ++k) if (i0 + k < npix) o[k] = v[c][k];
-            }
-        }
-    }
-    if (ARGMAX) {
-        bv[t] = best; bi[t] = at;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (t < s) {
-                const float x = bv[t + s]; const int j = bi[t + s];
-                if (j != 0x7fffffff && argmax_better(x, j, bv[t], bi[t])) { bv[t] = x; bi[t] = j; }
-            }
-            __syncthreads();
-        }
-        if (t == 0) { const int slot = blockIdx.y * gridDim.x + blockIdx.x; part_val[slot] = bv[0]; part_idx[slot] = bi[0]; }
-    }
-}
-static __global__ __launch_bounds__(256) void scene_class_map_kernel(const float* q, int map0, const SceneAffine aff, const SceneGeo g, int cls,
-                                                                     float* out, int vec4) {
-    scene_class_walk<false>(q, map0, aff, g, cls, out, vec4, nullptr, nullptr);
-}
-static __global__ __launch_bounds__(256) void scene_class_argmax_kernel(const float* q, int map0, const SceneAffine aff, const SceneGeo g, int cls,
-                                                                        float* part_val, int* part_idx) {
-    scene_class_walk<true>(q, map0, aff, g, cls, nullptr, 0, part_val, part_idx);
-}
-
-// smg_loss_scene_ce: the cross entropy (CrossEntropyLoss2d, class weights {1, 1, 0}) of the interpolated logits at K labelled
-// heightmap pixels per pair - loss_scene_kernel's gather form on three planes.  A point COUNTS when its label is 0 or 1, it lies in
-// the heightmap and it is valid in the pair's rotation; W = the number of such points; every other point (class 2 included,
-// whatever logits lie under it) is skipped before anything is read.  Per counted point, in double:
-//     nll_k = log(s) + m - z_y        g_c = e_c / s - [c == y]
-// loss[j] = (sum nll_k) / W and dq[j][c][oy][ox] = (sum_k g_c * bilinear weight of (oy, ox) at point k) / W: summed unnormalised
-// in point order, divided once, rounded once; W == 0 gives loss 0 and dq 0.  The points are taken 256 at a time, thread t owns map
-// elements t, t + 256, ... in all three planes.  Dynamic LDS: the 3 OH OW double accumulators only - the logits are read from
-// global memory (a few corners per point of a map that sits in L2), which keeps 38 x 38 maps at 35 KB + 14 KB static.
-static __global__ __launch_bounds__(256) void loss_scene_ce_kernel(const float* q, int pair0, const SceneAffine aff, const SceneGeo g, int K,
-                                                                   const int* pixels, const float* label, float* loss, float* dq) {
-    extern __shared__ double sacc[];
-    __shared__ double red[256];
-    __shared__ int cnt[256];
-    __shared__ double p_fy[256], p_fx[256], p_g[3][256];
-    __shared__ int p_o[256];
-    const int t = threadIdx.x, m = blockIdx.x, j = pair0 + m;
-    const int P = g.OH * g.OW;
-    const float* qj = q + (int64_t)j * 3 * P;
-    for (int i = t; i < 3 * P; i += 256) sacc[i] = 0.0;
-    __syncthreads();
-    const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
-    double lsum = 0.0; int w = 0;
-    for (int k0 = 0; k0 < K; k0 += 256) {
-        const int k = k0 + t;
-        int o = -1; double fy = 0.0, fx = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
-        if (k < K) {
-            const int64_t at = (int64_t)j * K + k;
-            const int iy = pixels[2 * at], ix = pixels[2 * at + 1];
-            const float lf = label[at];
-            if ((lf == 0.f || lf == 1.f) && iy >= 0 && iy < g.hm && ix >= 0 && ix < g.hm) {
-                const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
-                if (p.valid) {
-                    const SceneClass c = scene_class(p, qj, P, g.OW);
-                    lsum += (log(c.s) + c.m) - (lf == 0.f ? c.z0 : c.z1);
-                    ++w;
-                    o = p.y0 * g.OW + p.x0; fy = p.fy; fx = p.fx;
-                    g0 = c.e0 / c.s - (lf == 0.f ? 1.0 : 0.0); g1 = c.e1 / c.s - (lf == 1.f ? 1.0 : 0.0); g2 = c.e2 / c.s;
-                }
-            }
-        }
-        p_o[t] = o; p_fy[t] = fy; p_fx[t] = fx; p_g[0][t] = g0; p_g[1][t] = g1; p_g[2][t] = g2;
-        __syncthreads();
-        const int n = min(256, K - k0);
-        for (int i = t; i < P; i += 256) {
-            const int ey = i / g.OW, ex = i - ey * g.OW;
-            double acc0 = sacc[i], acc1 = sacc[P + i], acc2 = sacc[2 * P + i];
-            for (int kk = 0; kk < n; ++kk) {
-                const int oo = p_o[kk];
-                if (oo < 0) continue;
-                const int y0 = oo / g.OW, x0 = oo - y0 * g.OW;
-                const int dy = ey - y0, dx = ex - x0;
-                if ((unsigned)dy > 1u || (unsigned)dx > 1u) continue;
-                const double wy = dy ? p_fy[kk] : 1.0 - p_fy[kk], wx = dx ? p_fx[kk] : 1.0 - p_fx[kk];
-                const double wgt = wy * wx;
-                acc0 += p_g[0][kk] * wgt; acc1 += p_g[1][kk] * wgt; acc2 += p_g[2][kk] * wgt;
-            }
-            sacc[i] = acc0; sacc[P + i] = acc1; sacc[2 * P + i] = acc2;
-        }
-        __syncthreads();
-    }
-    red[t] = lsum; cnt[t] = w;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) { red[t] += red[t + s]; cnt[t] += cnt[t + s]; }
-        __syncthreads();
-    }
-    const int W = cnt[0];
-    const double dW = (double)W;
-    if (t == 0) loss[j] = W > 0 ? (float)(red[0] / dW) : 0.f;
-    float* dj = dq + (int64_t)j * 3 * P;
-    for (int i = t; i < 3 * P; i += 256) dj[i] = W > 0 ? (float)(sacc[i] / dW) : 0.f;
-}
-
-// smg_loss_scene_map_ce: loss_scene_ce_kernel's cross entropy with a whole [hm][hm] class-label image per pair instead of K listed
-// pixels - loss_scene_map_kernel's structure on three planes.  A heightmap pixel is a POINT of pair j when it is valid in the pair's
-// rotation and its label is exactly 0.f or 1.f; every other pixel (class 2, NaN, any other value) is skipped before a logit is
-// read, and the label of an invalid pixel is never read.  W = the number of points.  Per point, in double (scene_class as it stands):
-//     nll = (log(s) + m) - z_y        g_c = e_c / s - [c == y]
-//     loss[j] = (sum nll) / W         dq[j][c][oy][ox] = (sum g_c * bilinear weight of (oy, ox) at the pixel) / W
-// Gather by map element exactly as in loss_scene_map_kernel: one workgroup owns one (pair, oy, ox) - blockIdx.x = oy * OW + ox,
-// blockIdx.y = pair of this launch - and walks scene_element_box's pixels t, t + 256, ... in row-major order; a pixel adds its nll
-// and its count at its HOME element (y0, x0) only (the logarithm is taken there alone) and its gradient share at every element it
-// touches, so a point's softmax is evaluated by up to four workgroups: the price of a form without atomics.  The twelve corner
-// logits of a pixel come from global memory (three [OH][OW] planes that sit in L2; staging the 27 logits around the element in LDS
-// measured 0.755 against 0.776 ms at S = 1824, inside the spread between repeats, and was not kept).
-// W is known only when all elements of a pair are done, so this launch writes UNNORMALISED partials into scratch the engine owns,
-// every slot written: gpart [pairs of this launch][3][OH * OW] doubles, lpart [pairs][OH * OW] doubles, cpart [pairs][OH * OW]
-// ints.  No accumulator of the map's size in LDS (4 x 256 doubles + 256 ints of reduction arrays), hence no limit on the map's size
-// beyond scene_geometry's.
+// smg_loss_scene_map_ce: loss_scene_ce_kernel's cross entropy on the image - loss[j] = (sum nll) / W, dq[j][c][oy][ox] = (the
+// element's sum) / W, W = the number of counted pixels.  W is known only when all elements of a pair are done, so this launch writes
+// UNNORMALISED partials into scratch the engine owns, every slot written: gpart [pairs of this launch][3][OH * OW] doubles, lpart
+// [pairs][OH * OW] doubles, cpart [pairs][OH * OW] ints.  No accumulator of the map's size in LDS (4 x 256 doubles + 256 ints of
+// reduction arrays), hence no limit on the map's size beyond scene_geometry's.
 static __global__ __launch_bounds__(256) void loss_scene_map_ce_kernel(const float* q, int pair0, const SceneAffine aff, const SceneGeo g,
                                                                        const float* label, double* gpart, double* lpart, int* cpart) {
     __shared__ double racc[3][256], rloss[256];
     __shared__ int rcnt[256];
     const int t = threadIdx.x, m = blockIdx.y, j = pair0 + m, el = blockIdx.x;
     const int P = g.OH * g.OW;
-    const int oy = el / g.OW, ox = el - oy * g.OW;
-    const float* qj = q + (int64_t)j * 3 * P;
-    const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
-    const SceneBox box = scene_element_box(g, a00, a01, a10, a11, oy, ox);
-    const int bx0 = box.bx0, by0 = box.by0, bw = box.bw, n = box.n;
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, lsum = 0.0; int w = 0;
-    for (int i = t; i < n; i += 256) {
-        const int ry = i / bw;
-        const int iy = by0 + ry, ix = bx0 + (i - ry * bw);
-        const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
-        if (!p.valid) continue;
-        const int dy = oy - p.y0, dx = ox - p.x0;
-        if ((unsigned)dy > 1u || (unsigned)dx > 1u) continue;
-        const float lf = label[((int64_t)j * g.hm + iy) * g.hm + ix];
-        if (!(lf == 0.f || lf == 1.f)) continue;
-        const SceneClass c = scene_class(p, qj, P, g.OW);
-        if (dy == 0 && dx == 0) { lsum += (log(c.s) + c.m) - (lf == 0.f ? c.z0 : c.z1); ++w; }
-        const double wy = dy ? p.fy : 1.0 - p.fy, wx = dx ? p.fx : 1.0 - p.fx;
-        const double wgt = wy * wx;
-        acc0 += (c.e0 / c.s - (lf == 0.f ? 1.0 : 0.0)) * wgt; acc1 += (c.e1 / c.s - (lf == 1.f ? 1.0 : 0.0)) * wgt; acc2 += (c.e2 / c.s) * wgt;
-    }
-    racc[0][t] = acc0; racc[1][t] = acc1; racc[2][t] = acc2; rloss[t] = lsum; rcnt[t] = w;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) {
-            racc[0][t] += racc[0][t + s]; racc[1][t] += racc[1][t + s]; racc[2][t] += racc[2][t + s];
-            rloss[t] += rloss[t + s]; rcnt[t] += rcnt[t + s];
-        }
-        __syncthreads();
-    }
+    double acc[3] = {0.0, 0.0, 0.0}, lsum = 0.0; int cnt = 0;
+    scene_box_walk(g, (double)aff.a[m][0], (double)aff.a[m][1], (double)aff.a[m][2], (double)aff.a[m][3], j, el / g.OW, el % g.OW,
+                   SceneCe{q + (int64_t)j * 3 * P, label}, acc, lsum, cnt);
+    racc[0][t] = acc[0]; racc[1][t] = acc[1]; racc[2][t] = acc[2]; rloss[t] = lsum; rcnt[t] = cnt;
+    block_sum(t, racc[0], racc[1], racc[2], rloss, rcnt);
     if (t < 3) gpart[((int64_t)m * 3 + t) * P + el] = racc[t][0];
     if (t == 0) { lpart[(int64_t)m * P + el] = rloss[0]; cpart[(int64_t)m * P + el] = rcnt[0]; }
 }
@@ -567,11 +530,7 @@ static __global__ __launch_bounds__(256) void loss_scene_map_ce_finish_kernel(co
     double s = 0.0; int w = 0;
     for (int i = t; i < P; i += 256) { s += lpart[(int64_t)m * P + i]; w += cpart[(int64_t)m * P + i]; }
     red[t] = s; cnt[t] = w;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (t < k) { red[t] += red[t + k]; cnt[t] += cnt[t + k]; }
-        __syncthreads();
-    }
+    block_sum(t, red, cnt);
     const int W = cnt[0];
     const double dW = (double)W;
     if (t == 0) loss[j] = W > 0 ? (float)(red[0] / dW) : 0.f;

@@ -26,6 +26,23 @@ from models import STYLE_HEAD, STYLE_TRUNK, reactive_net, reinforcement_net
 _ACTION_STYLE = {"grasp": 0, "suction": 1, "grasp_then_suction": 2}
 
 
+def _f32_on(dev, a):
+    """A host array or a tensor as a contiguous float32 tensor on `dev` (None stays None)."""
+    if a is None:
+        return None
+    if torch.is_tensor(a):
+        return a.to(device=dev, dtype=torch.float32).contiguous()
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=dev)
+
+
+def _i32_on(dev, a):
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=dev)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 class FusedAdam(object):
     """torch.optim.Adam(lr=1e-4, betas=(0.9,0.999), eps=1e-8, weight_decay=0)
     (code/trainer.py:99) over the model's flat parameter buffer.  Like torch >= 2
@@ -475,33 +492,47 @@ class Trainer(object):
         Returns the loss vector (and q [n_samples, 1, OH, OW] if asked)."""
         if self.method != 'reinforcement':
             raise ValueError("train_batch_maps: reinforcement method only (a map of Q values; the reactive head is a classifier)")
-        per_scene = np.ndim(depth_heightmap) == 3
-        n = sum(len(r) for r in rotations) if per_scene else len(rotations)
+        n = len(self._flat_rotations(depth_heightmap, style, rotations))
         side = self.dense_map_size(np.shape(depth_heightmap)[-1])
         for name, maps in (("label_maps", label_maps), ("weight_maps", weight_maps)):
             if maps is not None and tuple(maps.shape if torch.is_tensor(maps) else np.shape(maps)) != (n, side, side):
                 raise ValueError("%s must be [%d samples, %d, %d] for a %d^2 heightmap, got %s"
                                  % (name, n, side, side, np.shape(depth_heightmap)[-1], tuple(np.shape(maps))))
+
+        def loss_call(eng, q, tensors, n, loss, dq, stream):
+            eng.loss_map(q.data_ptr(), _ptr(tensors[0]), _ptr(tensors[1]), n, loss.data_ptr(), dq.data_ptr(), stream)
+        return self._train_maps(depth_heightmap, m_depth_heightmap, style, rotations, (1, side),
+                                lambda dev: (_f32_on(dev, label_maps), _f32_on(dev, weight_maps)), loss_call, grad_sync, return_q)
+
+    @staticmethod
+    def _flat_rotations(depth_heightmap, style, rotations):
+        """The rotation of every sample as one flat list, scene-major (`rotations` is a list per scene where the heightmaps are
+        [n_scenes, H, H]); style 2 is rotation 0."""
+        flat = [r for rs in rotations for r in rs] if np.ndim(depth_heightmap) == 3 else list(rotations)
+        return [0 if style == 2 else int(r) for r in flat]
+
+    def _train_maps(self, depth_heightmap, m_depth_heightmap, style, rotations, q_shape, upload, loss_call, grad_sync, return_q):
+        """The step that train_batch_maps, train_batch_class_maps and the four train_batch_scene_* methods share, entered once their
+        own arguments are checked: the forward of every (scene, rotation) sample kept for the backward, ONE engine loss call on its
+        q [n, channels, side, side] (`q_shape` = the expected (channels, side)), one backward pass, ONE Adam step.
+        `upload(dev)` returns the device tensors of the labels and is called BEFORE the forward is enqueued (behind it, a pageable
+        copy would hold the host until the forward has run); `loss_call(eng, q, tensors, n, loss, dq, stream)` enqueues the loss
+        that fills loss [n] and dq (shaped like q).  Returns the loss vector (and q if asked)."""
         model = self.model
         self.optimizer.zero_grad()
         model._require_gpu()
         dev = model._flat_params.device
         hm, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
         rots = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
-
-        def to_dev(maps):      # (uploaded BEFORE the forward is enqueued, like train_batch's labels)
-            if torch.is_tensor(maps):
-                return maps.to(device=dev, dtype=torch.float32).contiguous()
-            return torch.as_tensor(np.ascontiguousarray(maps, dtype=np.float32), device=dev)
-        lab = to_dev(label_maps)
-        wgt = None if weight_maps is None else to_dev(weight_maps)
+        n = sum(len(rs) for rs in rots)
+        tensors = upload(dev)
         q = model.run(style, rots, model.gnum_rotations, heightmaps=hm, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
         eng, token, trunk_id, head_id = model._saved
-        assert tuple(q.shape) == (n, 1, side, side), (tuple(q.shape), n, side)
+        assert tuple(q.shape) == (n, q_shape[0], q_shape[1], q_shape[1]), (tuple(q.shape), n, q_shape)
         stream = torch.cuda.current_stream(dev).cuda_stream
         loss = torch.empty(n, dtype=torch.float32, device=dev)
         dq = torch.empty_like(q)
-        eng.loss_map(q.data_ptr(), lab.data_ptr(), None if wgt is None else wgt.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
+        loss_call(eng, q, tensors, n, loss, dq, stream)
         self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
         return (loss, q) if return_q else loss
 
@@ -580,19 +611,34 @@ class Trainer(object):
         the head is centred in that rotation.  Element [r, iy, ix] is the Q value of acting at heightmap pixel (iy, ix) with
         rotation r: the same scene point in every rotation.  Rotation choice and BN bookkeeping are forward's (style 2 is
         rotation 0).  Reinforcement method, heightmaps larger than 224^2."""
-        import models
         self._require_scene("forward_scene", depth_heightmap)
         model = self.model_target if is_target else self.model
         q = self.forward_dense(depth_heightmap, m_depth_heightmap, style, is_target, specific_rotation, return_device=True)
-        dev = q.device
         R, OH, OW = q.shape
-        hm = int(np.shape(depth_heightmap)[-1])
-        aff = [models.rotation_theta(r, num) for r, num in self._scene_rotations(model, style, specific_rotation)]
-        assert len(aff) == R
-        eng = models.get_engine(dev.index or 0, self._scene_geometry(hm)[1], model.HEAD_OUT, 1, 1)
-        out = torch.empty((R, hm, hm), dtype=torch.float32, device=dev)
-        eng.scene_maps(q.data_ptr(), OH * OW, R, aff, hm, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        eng, aff, hm, stream = self._scene_call(model, q, depth_heightmap, self._scene_rotations(model, style, specific_rotation))
+        out = torch.empty((R, hm, hm), dtype=torch.float32, device=q.device)
+        eng.scene_maps(q.data_ptr(), OH * OW, R, aff, hm, out.data_ptr(), stream)
         return out if return_device else out.cpu().numpy().astype(np.float64)
+
+    def _scene_call(self, model, q, depth_heightmap, rots):
+        """(engine, affine matrices, hm, stream) of a scene-frame call on the maps q of the `rots` = [(rotation, num_rotations)]."""
+        import models
+        assert len(rots) == q.shape[0]
+        hm = int(np.shape(depth_heightmap)[-1])
+        eng = models.get_engine(q.device.index or 0, self._scene_geometry(hm)[1], model.HEAD_OUT, 1, 1)
+        return eng, [models.rotation_theta(r, num) for r, num in rots], hm, torch.cuda.current_stream(q.device).cuda_stream
+
+    def _best_scene(self, q, hm, rots, argmax):
+        """`argmax(idx_ptr, val_ptr)` enqueues a scene argmax over the flattened [R, hm, hm]; the host reads back its one
+        (index, value) pair.  Returns {"rotation", "pixel": (iy, ix), "conf", "map_pixel": (qy, qx)}."""
+        idx = torch.empty(1, dtype=torch.int32, device=q.device)
+        val = torch.empty(1, dtype=torch.float32, device=q.device)
+        argmax(idx.data_ptr(), val.data_ptr())
+        i = int(idx.cpu().numpy()[0])
+        row, iy, ix = i // (hm * hm), (i // hm) % hm, i % hm
+        qy, qx, _ = self.scene_to_map(hm, rots[row][0], rots[row][1], (iy, ix))
+        return {"rotation": rots[row][0], "pixel": (iy, ix), "conf": float(val.cpu().numpy().astype(np.float64)[0]),
+                "map_pixel": (float(qy), float(qx))}
 
     def best_scene_action(self, depth_heightmap, m_depth_heightmap, style=0, is_target=False):
         """The best (rotation, heightmap pixel) of the sweep, found on the device without materialising the scene-frame maps
@@ -600,40 +646,20 @@ class Trainer(object):
         are never picked); the host reads back one (index, value) pair.
         Returns {"rotation", "pixel": (iy, ix), "conf", "map_pixel": (qy, qx)} - `pixel` in heightmap pixels, `map_pixel` its
         float position on that rotation's Q map (scene_to_map)."""
-        import models
         self._require_scene("best_scene_action", depth_heightmap)
         model = self.model_target if is_target else self.model
         q = self.forward_dense(depth_heightmap, m_depth_heightmap, style, is_target, return_device=True)
-        dev = q.device
         R, OH, OW = q.shape
-        hm = int(np.shape(depth_heightmap)[-1])
         rots = self._scene_rotations(model, style, -1)
-        eng = models.get_engine(dev.index or 0, self._scene_geometry(hm)[1], model.HEAD_OUT, 1, 1)
-        idx = torch.empty(1, dtype=torch.int32, device=dev)
-        val = torch.empty(1, dtype=torch.float32, device=dev)
-        eng.scene_argmax(q.data_ptr(), OH * OW, R, [models.rotation_theta(r, num) for r, num in rots], hm, idx.data_ptr(), val.data_ptr(),
-                         torch.cuda.current_stream(dev).cuda_stream)
-        i = int(idx.cpu().numpy()[0])
-        row, iy, ix = i // (hm * hm), (i // hm) % hm, i % hm
-        qy, qx, _ = self.scene_to_map(hm, rots[row][0], rots[row][1], (iy, ix))
-        return {"rotation": rots[row][0], "pixel": (iy, ix), "conf": float(val.cpu().numpy().astype(np.float64)[0]),
-                "map_pixel": (float(qy), float(qx))}
+        eng, aff, hm, stream = self._scene_call(model, q, depth_heightmap, rots)
+        return self._best_scene(q, hm, rots, lambda idx, val: eng.scene_argmax(q.data_ptr(), OH * OW, R, aff, hm, idx, val, stream))
 
-    def train_batch_scene_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, weights=None, grad_sync=None,
-                                 return_q=False):
-        """train_batch_maps with the labels at HEIGHTMAP pixels: sample j trains K scene pixels - `pixels` [n_samples, K, 2] =
-        (iy, ix) ([n_samples, 2] for K = 1), `labels` / `weights` [n_samples, K] (weights None = all ones) - through the bilinear
-        interpolation of its Q map at those points: loss_j = sum_k w * Huber(v_k - label_k) (smg_loss_scene), whose gradient
-        spreads over the four map elements around each point.  A pixel without a window of the head in its sample's rotation
-        (scene_to_map's `valid`) raises ValueError before anything runs.  The gradient of the SUM of the losses goes back in one
-        backward pass (dense head form), then ONE Adam step.  Scenes, rotations and `grad_sync` as in train_batch_maps; host
-        arrays.  Reinforcement method only.  Returns the loss vector (and q [n_samples, 1, OH, OW] if asked)."""
-        import models
-        _, _, side = self._require_scene("train_batch_scene_pixels", depth_heightmap)
-        per_scene = np.ndim(depth_heightmap) == 3
-        flat_rots = [r for rs in rotations for r in rs] if per_scene else list(rotations)
-        n = len(flat_rots)
-        hm = int(np.shape(depth_heightmap)[-1])
+    @staticmethod
+    def _scene_pixel_args(pixels, n, hm, labels, weights=None, class_labels=False):
+        """What train_batch_scene_pixels and train_batch_scene_class_pixels check of their lists, in this order: `pixels` [n, K, 2]
+        ([n, 2] is K = 1); `labels` and, unless None, `weights` [n, K] ([n] for K = 1); with `class_labels`, labels that are class
+        indices 0, 1 or 2; integer (iy, ix) inside the hm x hm heightmap.
+        Returns the pixels as int64 [n, K, 2], K, and labels and weights as float32 [n, K] (weights None stays None)."""
         pix = np.asarray(pixels)
         if pix.ndim == 2:
             pix = pix[:, None, :]
@@ -645,35 +671,42 @@ class Trainer(object):
         for name, a in (("labels", lab), ("weights", wgt)):
             if a is not None and a.shape != (n, K) and not (K == 1 and a.shape == (n,)):
                 raise ValueError("%s must be [%d samples, %d], got %s" % (name, n, K, a.shape))
+        lab, wgt = lab.reshape(n, K), None if wgt is None else wgt.reshape(n, K)
+        if class_labels and not np.isin(lab, (0.0, 1.0, 2.0)).all():      # (torch's nll_loss raises on a class index outside [0, 3), as in train_batch)
+            raise ValueError("labels must be class indices 0, 1 or 2")
         pix_i = pix.astype(np.int64)
         if not np.array_equal(pix_i, pix) or pix_i.min() < 0 or pix_i.max() >= hm:
             raise ValueError("pixels must be integer (iy, ix) inside the %d x %d heightmap" % (hm, hm))
-        num = self.model.gnum_rotations
-        rots = [0 if style == 2 else int(r) for r in flat_rots]
+        return pix_i, K, lab, wgt
+
+    @staticmethod
+    def _scene_affines(rots, num):
+        import models
+        return [models.rotation_theta(r, num) for r in rots]
+
+    def train_batch_scene_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, weights=None, grad_sync=None,
+                                 return_q=False):
+        """train_batch_maps with the labels at HEIGHTMAP pixels: sample j trains K scene pixels - `pixels` [n_samples, K, 2] =
+        (iy, ix) ([n_samples, 2] for K = 1), `labels` / `weights` [n_samples, K] (weights None = all ones) - through the bilinear
+        interpolation of its Q map at those points: loss_j = sum_k w * Huber(v_k - label_k) (smg_loss_scene), whose gradient
+        spreads over the four map elements around each point.  A pixel without a window of the head in its sample's rotation
+        (scene_to_map's `valid`) raises ValueError before anything runs.  The gradient of the SUM of the losses goes back in one
+        backward pass (dense head form), then ONE Adam step.  Scenes, rotations and `grad_sync` as in train_batch_maps; host
+        arrays.  Reinforcement method only.  Returns the loss vector (and q [n_samples, 1, OH, OW] if asked)."""
+        _, _, side = self._require_scene("train_batch_scene_pixels", depth_heightmap)
+        rots = self._flat_rotations(depth_heightmap, style, rotations)
+        n, num, hm = len(rots), self.model.gnum_rotations, int(np.shape(depth_heightmap)[-1])
+        pix_i, K, lab, wgt = self._scene_pixel_args(pixels, n, hm, labels, weights)
         _, _, valid = self.scene_to_map(hm, np.asarray(rots).reshape(n, 1), num, pix_i)
         if not valid.all():
             j, k = np.argwhere(~valid)[0]
             raise ValueError("pixel %s of sample %d has no Q window in rotation %d of %d (scene_to_map)" % (tuple(pix_i[j, k]), j, rots[j], num))
-        model = self.model
-        self.optimizer.zero_grad()
-        model._require_gpu()
-        dev = model._flat_params.device
-        hmaps, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
-        rots2 = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
-        # (uploaded BEFORE the forward is enqueued, like train_batch's labels)
-        pix_d = torch.as_tensor(np.ascontiguousarray(pix_i, dtype=np.int32), device=dev)
-        lab_d = torch.as_tensor(np.ascontiguousarray(lab.reshape(n, K)), device=dev)
-        wgt_d = None if wgt is None else torch.as_tensor(np.ascontiguousarray(wgt.reshape(n, K)), device=dev)
-        q = model.run(style, rots2, num, heightmaps=hmaps, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
-        eng, token, trunk_id, head_id = model._saved
-        assert tuple(q.shape) == (n, 1, side, side), (tuple(q.shape), n, side)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        loss = torch.empty(n, dtype=torch.float32, device=dev)
-        dq = torch.empty_like(q)
-        eng.loss_scene(q.data_ptr(), [models.rotation_theta(r, num) for r in rots], hm, n, K, pix_d.data_ptr(), lab_d.data_ptr(),
-                       None if wgt_d is None else wgt_d.data_ptr(), loss.data_ptr(), dq.data_ptr(), stream)
-        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
-        return (loss, q) if return_q else loss
+
+        def loss_call(eng, q, tensors, n, loss, dq, stream):
+            eng.loss_scene(q.data_ptr(), self._scene_affines(rots, num), hm, n, K, _ptr(tensors[0]), _ptr(tensors[1]), _ptr(tensors[2]),
+                           loss.data_ptr(), dq.data_ptr(), stream)
+        return self._train_maps(depth_heightmap, m_depth_heightmap, style, rotations, (1, side),
+                                lambda dev: (_i32_on(dev, pix_i), _f32_on(dev, lab), _f32_on(dev, wgt)), loss_call, grad_sync, return_q)
 
     def train_batch_scene_maps(self, depth_heightmap, m_depth_heightmap, style, rotations, label_maps, weight_maps=None, grad_sync=None,
                                return_q=False):
@@ -685,37 +718,19 @@ class Trainer(object):
         pixels.  The gradient of the SUM of the losses goes back in one backward pass (dense head form), then ONE Adam step.
         Scenes, rotations and `grad_sync` as in train_batch_scene_pixels.  Reinforcement method only.  Returns the loss vector
         (and q [n_samples, 1, OH, OW] if asked)."""
-        import models
         _, _, side = self._require_scene("train_batch_scene_maps", depth_heightmap)
-        per_scene = np.ndim(depth_heightmap) == 3
-        flat_rots = [r for rs in rotations for r in rs] if per_scene else list(rotations)
-        n = len(flat_rots)
-        hm = int(np.shape(depth_heightmap)[-1])
+        rots = self._flat_rotations(depth_heightmap, style, rotations)
+        n, num, hm = len(rots), self.model.gnum_rotations, int(np.shape(depth_heightmap)[-1])
         for name, maps in (("label_maps", label_maps), ("weight_maps", weight_maps)):
             if (maps is not None or name == "label_maps") and (maps is None or tuple(np.shape(maps)) != (n, hm, hm)):
                 raise ValueError("%s must be [%d samples, %d, %d] for a %d^2 heightmap, got %s"
                                  % (name, n, hm, hm, hm, None if maps is None else tuple(np.shape(maps))))
-        num = self.model.gnum_rotations
-        rots = [0 if style == 2 else int(r) for r in flat_rots]
-        model = self.model
-        self.optimizer.zero_grad()
-        model._require_gpu()
-        dev = model._flat_params.device
-        hmaps, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
-        rots2 = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
-        # (uploaded BEFORE the forward is enqueued, like train_batch_maps' maps)
-        lab_d = torch.as_tensor(np.ascontiguousarray(label_maps, dtype=np.float32), device=dev)
-        wgt_d = None if weight_maps is None else torch.as_tensor(np.ascontiguousarray(weight_maps, dtype=np.float32), device=dev)
-        q = model.run(style, rots2, num, heightmaps=hmaps, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
-        eng, token, trunk_id, head_id = model._saved
-        assert tuple(q.shape) == (n, 1, side, side), (tuple(q.shape), n, side)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        loss = torch.empty(n, dtype=torch.float32, device=dev)
-        dq = torch.empty_like(q)
-        eng.loss_scene_map(q.data_ptr(), [models.rotation_theta(r, num) for r in rots], hm, n, lab_d.data_ptr(),
-                           None if wgt_d is None else wgt_d.data_ptr(), loss.data_ptr(), dq.data_ptr(), stream)
-        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
-        return (loss, q) if return_q else loss
+
+        def loss_call(eng, q, tensors, n, loss, dq, stream):
+            eng.loss_scene_map(q.data_ptr(), self._scene_affines(rots, num), hm, n, _ptr(tensors[0]), _ptr(tensors[1]),
+                               loss.data_ptr(), dq.data_ptr(), stream)
+        return self._train_maps(depth_heightmap, m_depth_heightmap, style, rotations, (1, side),
+                                lambda dev: (_f32_on(dev, label_maps), _f32_on(dev, weight_maps)), loss_call, grad_sync, return_q)
 
     # ---- dense class maps (reactive method on heightmaps larger than 224^2: three logits per 20x20 window of the feature plane) ---
     def _require_reactive(self, what):
@@ -759,34 +774,20 @@ class Trainer(object):
         outside {0, 1, 2}, device tensors are not read back.  Reactive method only.
         Returns the loss vector (and the logits q [n_samples, 3, OH, OW] if asked)."""
         self._require_reactive("train_batch_class_maps")
-        per_scene = np.ndim(depth_heightmap) == 3
-        n = sum(len(r) for r in rotations) if per_scene else len(rotations)
+        n = len(self._flat_rotations(depth_heightmap, style, rotations))
         side = self.dense_map_size(np.shape(depth_heightmap)[-1])
         if tuple(label_maps.shape if torch.is_tensor(label_maps) else np.shape(label_maps)) != (n, side, side):
             raise ValueError("label_maps must be [%d samples, %d, %d] for a %d^2 heightmap, got %s"
                              % (n, side, side, np.shape(depth_heightmap)[-1], tuple(np.shape(label_maps))))
-        lab_h = None
         if not torch.is_tensor(label_maps):
-            lab_h = np.ascontiguousarray(label_maps, dtype=np.float32)
-            if not np.isin(lab_h, (0.0, 1.0, 2.0)).all():      # (torch's nll_loss raises on a class index outside [0, 3), as in train_batch)
+            label_maps = np.ascontiguousarray(label_maps, dtype=np.float32)
+            if not np.isin(label_maps, (0.0, 1.0, 2.0)).all():      # (torch's nll_loss raises on a class index outside [0, 3), as in train_batch)
                 raise ValueError("label maps must hold class indices 0, 1 or 2")
-        model = self.model
-        self.optimizer.zero_grad()
-        model._require_gpu()
-        dev = model._flat_params.device
-        hm, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
-        rots = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
-        # (uploaded BEFORE the forward is enqueued, like train_batch's labels)
-        lab = label_maps.to(device=dev, dtype=torch.float32).contiguous() if lab_h is None else torch.as_tensor(lab_h, device=dev)
-        q = model.run(style, rots, model.gnum_rotations, heightmaps=hm, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
-        eng, token, trunk_id, head_id = model._saved
-        assert tuple(q.shape) == (n, 3, side, side), (tuple(q.shape), n, side)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        loss = torch.empty(n, dtype=torch.float32, device=dev)
-        dq = torch.empty_like(q)
-        eng.loss_map_ce(q.data_ptr(), lab.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
-        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
-        return (loss, q) if return_q else loss
+
+        def loss_call(eng, q, lab, n, loss, dq, stream):
+            eng.loss_map_ce(q.data_ptr(), lab.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
+        return self._train_maps(depth_heightmap, m_depth_heightmap, style, rotations, (3, side),
+                                lambda dev: _f32_on(dev, label_maps), loss_call, grad_sync, return_q)
 
     def train_batch_class_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, grad_sync=None, return_q=False):
         """train_batch_class_maps with ONE labelled pixel per sample: `pixels` holds an (oy, ox) per sample, `labels` its class -
@@ -815,19 +816,13 @@ class Trainer(object):
         head is centred in that rotation.  `logits` returns the interpolated logits instead (smg_scene_maps per class plane).
         Element [r, c, iy, ix] is P(class c) of acting at heightmap pixel (iy, ix) with rotation r: the same scene point in every
         rotation.  Rotation choice and BN bookkeeping are forward_class_maps'.  Reactive method, heightmaps larger than 224^2."""
-        import models
         self._require_scene_class("forward_scene_class_maps", depth_heightmap)
         if cls is not None and cls not in (0, 1, 2):
             raise ValueError("forward_scene_class_maps: cls must be None (all three), 0, 1 or 2")
-        model = self.model
         q = self.forward_class_maps(depth_heightmap, m_depth_heightmap, style, specific_rotation, logits=True, return_device=True)
         dev = q.device
         R, _, OH, OW = q.shape
-        hm = int(np.shape(depth_heightmap)[-1])
-        aff = [models.rotation_theta(r, num) for r, num in self._scene_rotations(model, style, specific_rotation)]
-        assert len(aff) == R
-        eng = models.get_engine(dev.index or 0, self._scene_geometry(hm)[1], model.HEAD_OUT, 1, 1)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        eng, aff, hm, stream = self._scene_call(self.model, q, depth_heightmap, self._scene_rotations(self.model, style, specific_rotation))
         if logits:
             planes = (0, 1, 2) if cls is None else (cls,)
             out = torch.empty((len(planes), R, hm, hm), dtype=torch.float32, device=dev)
@@ -844,24 +839,11 @@ class Trainer(object):
         scene-frame maps (smg_scene_class_argmax: lowest index of the flattened [R, hm, hm] on ties like np.argmax, a NaN wins,
         pixels without a window are never picked); the host reads back one (index, value) pair.
         Returns {"rotation", "pixel": (iy, ix), "conf", "map_pixel": (qy, qx)} as best_scene_action does."""
-        import models
         self._require_scene_class("best_scene_class_action", depth_heightmap)
-        model = self.model
         q = self.forward_class_maps(depth_heightmap, m_depth_heightmap, style, logits=True, return_device=True)
-        dev = q.device
-        R = q.shape[0]
-        hm = int(np.shape(depth_heightmap)[-1])
-        rots = self._scene_rotations(model, style, -1)
-        eng = models.get_engine(dev.index or 0, self._scene_geometry(hm)[1], model.HEAD_OUT, 1, 1)
-        idx = torch.empty(1, dtype=torch.int32, device=dev)
-        val = torch.empty(1, dtype=torch.float32, device=dev)
-        eng.scene_class_argmax(q.data_ptr(), R, [models.rotation_theta(r, num) for r, num in rots], hm, 0, idx.data_ptr(), val.data_ptr(),
-                               torch.cuda.current_stream(dev).cuda_stream)
-        i = int(idx.cpu().numpy()[0])
-        row, iy, ix = i // (hm * hm), (i // hm) % hm, i % hm
-        qy, qx, _ = self.scene_to_map(hm, rots[row][0], rots[row][1], (iy, ix))
-        return {"rotation": rots[row][0], "pixel": (iy, ix), "conf": float(val.cpu().numpy().astype(np.float64)[0]),
-                "map_pixel": (float(qy), float(qx))}
+        rots = self._scene_rotations(self.model, style, -1)
+        eng, aff, hm, stream = self._scene_call(self.model, q, depth_heightmap, rots)
+        return self._best_scene(q, hm, rots, lambda idx, val: eng.scene_class_argmax(q.data_ptr(), q.shape[0], aff, hm, 0, idx, val, stream))
 
     def train_batch_scene_class_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, grad_sync=None,
                                        return_q=False):
@@ -874,54 +856,22 @@ class Trainer(object):
         The gradient of the SUM of the losses goes back in one backward pass (dense head form), then ONE Adam step.  Scenes,
         rotations and `grad_sync` as in train_batch_class_maps; host arrays.  Reactive method only.
         Returns the loss vector (and the logits q [n_samples, 3, OH, OW] if asked)."""
-        import models
         _, _, side = self._require_scene_class("train_batch_scene_class_pixels", depth_heightmap)
-        per_scene = np.ndim(depth_heightmap) == 3
-        flat_rots = [r for rs in rotations for r in rs] if per_scene else list(rotations)
-        n = len(flat_rots)
-        hm = int(np.shape(depth_heightmap)[-1])
-        pix = np.asarray(pixels)
-        if pix.ndim == 2:
-            pix = pix[:, None, :]
-        if pix.ndim != 3 or pix.shape[0] != n or pix.shape[1] < 1 or pix.shape[2] != 2:
-            raise ValueError("pixels must be [%d samples, K, 2] = (iy, ix), got %s" % (n, np.shape(pixels)))
-        K = pix.shape[1]
-        lab = np.asarray(labels, dtype=np.float32)
-        if lab.shape != (n, K) and not (K == 1 and lab.shape == (n,)):
-            raise ValueError("labels must be [%d samples, %d], got %s" % (n, K, lab.shape))
-        lab = lab.reshape(n, K)
-        if not np.isin(lab, (0.0, 1.0, 2.0)).all():      # (torch's nll_loss raises on a class index outside [0, 3), as in train_batch)
-            raise ValueError("labels must be class indices 0, 1 or 2")
-        pix_i = pix.astype(np.int64)
-        if not np.array_equal(pix_i, pix) or pix_i.min() < 0 or pix_i.max() >= hm:
-            raise ValueError("pixels must be integer (iy, ix) inside the %d x %d heightmap" % (hm, hm))
-        num = self.model.gnum_rotations
-        rots = [0 if style == 2 else int(r) for r in flat_rots]
+        rots = self._flat_rotations(depth_heightmap, style, rotations)
+        n, num, hm = len(rots), self.model.gnum_rotations, int(np.shape(depth_heightmap)[-1])
+        pix_i, K, lab, _ = self._scene_pixel_args(pixels, n, hm, labels, class_labels=True)
         _, _, valid = self.scene_to_map(hm, np.asarray(rots).reshape(n, 1), num, pix_i)
         lost = ~valid & (lab != 2.0)
         if lost.any():
             j, k = np.argwhere(lost)[0]
             raise ValueError("pixel %s of sample %d (class %d) has no window in rotation %d of %d (scene_to_map)"
                              % (tuple(pix_i[j, k]), j, int(lab[j, k]), rots[j], num))
-        model = self.model
-        self.optimizer.zero_grad()
-        model._require_gpu()
-        dev = model._flat_params.device
-        hmaps, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
-        rots2 = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
-        # (uploaded BEFORE the forward is enqueued, like train_batch's labels)
-        pix_d = torch.as_tensor(np.ascontiguousarray(pix_i, dtype=np.int32), device=dev)
-        lab_d = torch.as_tensor(np.ascontiguousarray(lab), device=dev)
-        q = model.run(style, rots2, num, heightmaps=hmaps, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
-        eng, token, trunk_id, head_id = model._saved
-        assert tuple(q.shape) == (n, 3, side, side), (tuple(q.shape), n, side)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        loss = torch.empty(n, dtype=torch.float32, device=dev)
-        dq = torch.empty_like(q)
-        eng.loss_scene_ce(q.data_ptr(), [models.rotation_theta(r, num) for r in rots], hm, n, K, pix_d.data_ptr(), lab_d.data_ptr(),
-                          loss.data_ptr(), dq.data_ptr(), stream)
-        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
-        return (loss, q) if return_q else loss
+
+        def loss_call(eng, q, tensors, n, loss, dq, stream):
+            eng.loss_scene_ce(q.data_ptr(), self._scene_affines(rots, num), hm, n, K, _ptr(tensors[0]), _ptr(tensors[1]),
+                              loss.data_ptr(), dq.data_ptr(), stream)
+        return self._train_maps(depth_heightmap, m_depth_heightmap, style, rotations, (3, side),
+                                lambda dev: (_i32_on(dev, pix_i), _f32_on(dev, lab)), loss_call, grad_sync, return_q)
 
     def train_batch_scene_class_maps(self, depth_heightmap, m_depth_heightmap, style, rotations, label_maps, grad_sync=None,
                                      return_q=False):
@@ -934,38 +884,20 @@ class Trainer(object):
         the SUM of the losses goes back in one backward pass (dense head form), then ONE Adam step.  Scenes, rotations and
         `grad_sync` as in train_batch_scene_class_pixels.  Reactive method only.
         Returns the loss vector (and the logits q [n_samples, 3, OH, OW] if asked)."""
-        import models
         _, _, side = self._require_scene_class("train_batch_scene_class_maps", depth_heightmap)
-        per_scene = np.ndim(depth_heightmap) == 3
-        flat_rots = [r for rs in rotations for r in rs] if per_scene else list(rotations)
-        n = len(flat_rots)
-        hm = int(np.shape(depth_heightmap)[-1])
+        rots = self._flat_rotations(depth_heightmap, style, rotations)
+        n, num, hm = len(rots), self.model.gnum_rotations, int(np.shape(depth_heightmap)[-1])
         if label_maps is None or tuple(np.shape(label_maps)) != (n, hm, hm):
             raise ValueError("label_maps must be [%d samples, %d, %d] for a %d^2 heightmap, got %s"
                              % (n, hm, hm, hm, None if label_maps is None else tuple(np.shape(label_maps))))
         lab_h = np.ascontiguousarray(label_maps, dtype=np.float32)
         if not np.isin(lab_h, (0.0, 1.0, 2.0)).all():      # (torch's nll_loss raises on a class index outside [0, 3), as in train_batch)
             raise ValueError("label maps must hold class indices 0, 1 or 2")
-        num = self.model.gnum_rotations
-        rots = [0 if style == 2 else int(r) for r in flat_rots]
-        model = self.model
-        self.optimizer.zero_grad()
-        model._require_gpu()
-        dev = model._flat_params.device
-        hmaps, rotations = self._scenes_to_device(depth_heightmap, m_depth_heightmap, rotations)
-        rots2 = [[0 if style == 2 else int(r) for r in rs] for rs in rotations]
-        # (uploaded BEFORE the forward is enqueued, like train_batch's labels)
-        lab_d = torch.as_tensor(lab_h, device=dev)
-        q = model.run(style, rots2, num, heightmaps=hmaps, mean=self.image_mean, std=self.image_std, keep_for_backward=True)
-        eng, token, trunk_id, head_id = model._saved
-        assert tuple(q.shape) == (n, 3, side, side), (tuple(q.shape), n, side)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        loss = torch.empty(n, dtype=torch.float32, device=dev)
-        dq = torch.empty_like(q)
-        eng.loss_scene_map_ce(q.data_ptr(), [models.rotation_theta(r, num) for r in rots], hm, n, lab_d.data_ptr(), loss.data_ptr(),
-                              dq.data_ptr(), stream)
-        self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
-        return (loss, q) if return_q else loss
+
+        def loss_call(eng, q, lab, n, loss, dq, stream):
+            eng.loss_scene_map_ce(q.data_ptr(), self._scene_affines(rots, num), hm, n, lab.data_ptr(), loss.data_ptr(), dq.data_ptr(), stream)
+        return self._train_maps(depth_heightmap, m_depth_heightmap, style, rotations, (3, side),
+                                lambda dev: _f32_on(dev, lab_h), loss_call, grad_sync, return_q)
 
     # The single-sample step of Trainer.backprop as ONE replayed hipGraph (smg_train_step_graph): ~560 launches of 2-20 us each are
     # enqueued by one hipGraphLaunch instead of one by one (same results, bit for bit at zero learning rate).  It saves a little host time
