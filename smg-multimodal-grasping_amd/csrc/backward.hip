@@ -83,15 +83,14 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             w.h1 = a.h1; w.p4 = p4; w.hsum = a.hsum; w.hsq = a.hsq; w.gamma = a.gamma; w.beta = a.beta; w.eps = kEps;
             w.dq = dq; w.OH = e->OH; w.OW = e->OW; w.n_pairs = NP; w.dw2 = a.dw2;
             w.RC = std::min(e->OH, 64); w.OWp = (e->OW + 3) / 4 * 4; w.Wp = w.OWp + kVFrame;
-            const dim3 dgrid((p4.HW + 63) / 64, NP);
-            if (e->head_out == 1) {
-                launch_kernel(e, value_bwd_dense_kernel, dgrid, dim3(256), value_bwd_dense_lds(e->OH, e->OW), st, K_OTHER, 0, 0, false, a);
-                launch_kernel(e, value_wgrad_dense_kernel, dim3(20, kHeadMid / 4), dim3(256), value_wgrad_dense_lds(w), st, K_OTHER, 0, 0, false, w);
-            } else {
-                // (38 x 38 maps: 78 528 B of dynamic LDS - launch_kernel raises the kernel's limit)
-                launch_kernel(e, value_bwd_dense3_kernel, dgrid, dim3(256), value_bwd_dense3_lds(e->OH, e->OW), st, K_OTHER, 0, 0, false, a);
-                launch_kernel(e, value_wgrad_dense3_kernel, dim3(20, kHeadMid / 4, 3), dim3(256), value_wgrad_dense_lds(w), st, K_OTHER, 0, 0, false, w);
-            }
+            auto go = [&](auto oc) {
+                constexpr int OC = decltype(oc)::value;
+                // (3 classes on 38 x 38 maps: 78 528 B of dynamic LDS - launch_kernel raises the kernel's limit)
+                launch_kernel(e, value_bwd_dense_kernel<OC>, dim3((p4.HW + 63) / 64, NP), dim3(256), value_bwd_dense_lds(OC, e->OH, e->OW), st, K_OTHER, 0, 0, false, a);
+                launch_kernel(e, value_wgrad_dense_kernel<OC>, dim3(20, kHeadMid / 4, OC), dim3(256), value_wgrad_dense_lds(w), st, K_OTHER, 0, 0, false, w);
+            };
+            if (e->head_out == 1) go(std::integral_constant<int, 1>{});
+            else go(std::integral_constant<int, 3>{});
         }
     }
     int chunk4, cps4;

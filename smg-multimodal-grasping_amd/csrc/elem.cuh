@@ -420,7 +420,7 @@ static __global__ __launch_bounds__(256) void value_conv_kernel(const ValueArgs 
     }
     red[t] = acc;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
+    for (int s = 128; s > 0; s >>= 1) {     // (block_sum's tree, written out: through the function this kernel's listing grows by two instructions)
         if (t < s) red[t] += red[t + s];
         __syncthreads();
     }
@@ -443,15 +443,33 @@ struct ValueBwdArgs {
     float* dw2;                               // native [out][64][20][20]
 };
 
-static __global__ __launch_bounds__(256) void value_bwd_kernel(const ValueBwdArgs a) {
-    __shared__ float prm[256];
-    __shared__ float red[2][16][64];
-    const int j = blockIdx.y, t = threadIdx.x, cq = t & 15, slot = t >> 4;
+// The two ends the backward kernels below share.  Front: norm1's per-channel parameters of pair j,
+// prm[t] = gamma * invstd | beta | mean | invstd (the caller's barrier publishes them).  Back: the threads' sums of dy and dy * xhat
+// have met in red[2][16][64] (written and published by the caller: a barrier inside the inlined function leaves a dead exec-mask
+// instruction behind in the dense kernels); per channel a 16-way sum in slot order, one double atomic to o1 / o2 and one float
+// atomic to dbeta / dgamma per workgroup.
+__device__ __forceinline__ void value_bwd_params(const ValueBwdArgs& a, int j, int t, float* prm) {
     if (t < 64) {
         float mean, invstd;
         bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
         prm[t] = a.gamma[t] * invstd; prm[64 + t] = a.beta[t]; prm[128 + t] = mean; prm[192 + t] = invstd;
     }
+}
+__device__ __forceinline__ void value_bwd_sums(const ValueBwdArgs& a, int j, int t, const float (*red)[16][64]) {
+    if (t < 128) {
+        const int q = t >> 6, c = t & 63;
+        float tot = 0.f;
+        for (int k = 0; k < 16; ++k) tot += red[q][k][c];
+        atomicAdd((q ? a.o2 : a.o1) + (int64_t)j * 64 + c + stat_rep(), (double)tot);
+        atomicAdd((q ? a.dgamma : a.dbeta) + c, tot);
+    }
+}
+
+static __global__ __launch_bounds__(256) void value_bwd_kernel(const ValueBwdArgs a) {
+    __shared__ float prm[256];
+    __shared__ float red[2][16][64];
+    const int j = blockIdx.y, t = threadIdx.x, cq = t & 15, slot = t >> 4;
+    value_bwd_params(a, j, t, prm);
     __syncthreads();
     float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
     for (int i = 0; i < 4; ++i) {
@@ -489,18 +507,11 @@ static __global__ __launch_bounds__(256) void value_bwd_kernel(const ValueBwdArg
 #pragma unroll
     for (int c = 0; c < 4; ++c) { red[0][slot][4 * cq + c] = s1[c]; red[1][slot][4 * cq + c] = s2[c]; }
     __syncthreads();
-    if (t < 128) {
-        const int q = t >> 6, c = t & 63;
-        float tot = 0.f;
-        for (int k = 0; k < 16; ++k) tot += red[q][k][c];
-        atomicAdd((q ? a.o2 : a.o1) + (int64_t)j * 64 + c + stat_rep(), (double)tot);
-        atomicAdd((q ? a.dgamma : a.dbeta) + c, tot);
-    }
+    value_bwd_sums(a, j, t, red);
 }
 
 // The same backward for a DENSE dq (a whole weighted map per pair: smg_loss_map on a one-channel head, smg_loss_map_ce on a
-// 3-class one, whose two kernels follow their one-channel originals below).  value_bwd_kernel above
-// walks the output elements a pixel feeds and adds four fp32 atomics per non-zero dq and tap: fine for the one element the Huber
+// 3-class one).  value_bwd_kernel above walks the output elements a pixel feeds and adds four fp32 atomics per non-zero dq and tap: fine for the one element the Huber
 // of code/trainer.py:345 reads, 1444 x 400 x 64 = 37 M atomics per pair and output channel onto 25 600 addresses for a full
 // 38 x 38 map.  Here the work is split by what it reuses:
 //   value_bwd_dense_kernel   (data pass)   dact, DH1, the norm1 sums - per workgroup 64 pixels of one pair, looping over the 400
@@ -509,106 +520,42 @@ static __global__ __launch_bounds__(256) void value_bwd_kernel(const ValueBwdArg
 //   value_wgrad_dense_kernel (weight pass) dW - per workgroup one tap row and channel quad (and output channel), pairs in index
 //                                          order, every element of dW written by exactly one thread: a fixed summation order
 //                                          and no atomic at all.
+// Both are templates on the head's OC output channels (1, or the 3 classes).  The data pass's frame holds the OC dq maps,
+// [OC][OH + 38][OW + 38], and every tap reads OC float4 of packed weights and 4 OC frame values.  With three maps the frame is
+// 69 312 B at 38 x 38, above the 64 KB default: the launch path raises the kernel's limit, and the raised limit of 160 KiB is the
+// whole CU's, so a kernel that takes it must not hold static LDS beside it (the raise is refused and the launch fails) - for
+// OC > 1 the parameter and reduction arrays follow the frame in the DYNAMIC area.
 constexpr int kVFrame = 19;     // the 20 x 20 window reaches 19 outputs up / left of a pixel
-static inline size_t value_bwd_dense_lds(int OH, int OW) { return (size_t)(OH + 2 * kVFrame) * (OW + 2 * kVFrame) * sizeof(float); }
-
-static __global__ __launch_bounds__(256) void value_bwd_dense_kernel(const ValueBwdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];    // dq of the pair in a frame of zeros: [OH + 38][OW + 38]
-    __shared__ float prm[256];
-    __shared__ float red[2][16][64];
-    const int j = blockIdx.y, t = threadIdx.x, cq = t & 15, slot = t >> 4;
-    const int PW = a.OW + 2 * kVFrame, PH = a.OH + 2 * kVFrame;
-    if (t < 64) {
-        float mean, invstd;
-        bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
-        prm[t] = a.gamma[t] * invstd; prm[64 + t] = a.beta[t]; prm[128 + t] = mean; prm[192 + t] = invstd;
-    }
-    for (int i = t; i < PH * PW; i += 256) {
-        const int y = i / PW - kVFrame, x = i % PW - kVFrame;
-        smem[i] = (y >= 0 && y < a.OH && x >= 0 && x < a.OW) ? a.dq[((int64_t)j * a.OH + y) * a.OW + x] : 0.f;
-    }
-    __syncthreads();
-    // frame position of output (py, px) for each of the thread's four pixels; output (py - ty, px - tx) lies ty rows and tx columns
-    // in front of it (rows -19 .. OH + 18 of the frame: always inside)
-    int base[4]; bool live[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int p = blockIdx.x * 64 + slot + 16 * i;
-        live[i] = p < a.p4.HW;
-        const int py = live[i] ? p / a.p4.W : 0, px = live[i] ? p - py * a.p4.W : 0;
-        base[i] = (py + kVFrame) * PW + px + kVFrame;
-    }
-    float dact[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) dact[i][c] = 0.f;
-    const float* wq = a.w2p + 4 * cq;
-    for (int ty = 0; ty < 20; ++ty) {
-#pragma unroll 5
-        for (int tx = 0; tx < 20; ++tx) {
-            const float4 w = ld4(wq + (ty * 20 + tx) * 64);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float g = smem[base[i] - ty * PW - tx];
-                dact[i][0] = fmaf(g, w.x, dact[i][0]); dact[i][1] = fmaf(g, w.y, dact[i][1]);
-                dact[i][2] = fmaf(g, w.z, dact[i][2]); dact[i][3] = fmaf(g, w.w, dact[i][3]);
-            }
-        }
-    }
-    float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (!live[i]) continue;
-        const int64_t row = (int64_t)j * a.p4.HWp + blockIdx.x * 64 + slot + 16 * i;
-        const float4 hv = ld4(a.h1 + row * 64 + 4 * cq);
-        const float h[4] = {hv.x, hv.y, hv.z, hv.w};
-        float dy[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float act = fmaxf(bn1(h[c], prm[128 + 4 * cq + c], prm[4 * cq + c], prm[64 + 4 * cq + c]), 0.f);
-            dy[c] = act > 0.f ? dact[i][c] : 0.f;
-            s1[c] += dy[c];
-            s2[c] += dy[c] * ((h[c] - prm[128 + 4 * cq + c]) * prm[192 + 4 * cq + c]);
-        }
-        *reinterpret_cast<float4*>(a.dh1 + row * 64 + 4 * cq) = make_float4(dy[0], dy[1], dy[2], dy[3]);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { red[0][slot][4 * cq + c] = s1[c]; red[1][slot][4 * cq + c] = s2[c]; }
-    __syncthreads();
-    if (t < 128) {     // (the per-channel norm1 sums keep their one atomic per workgroup, as in value_bwd_kernel)
-        const int q = t >> 6, c = t & 63;
-        float tot = 0.f;
-        for (int k = 0; k < 16; ++k) tot += red[q][k][c];
-        atomicAdd((q ? a.o2 : a.o1) + (int64_t)j * 64 + c + stat_rep(), (double)tot);
-        atomicAdd((q ? a.dgamma : a.dbeta) + c, tot);
-    }
+static inline size_t value_bwd_dense_lds(int OC, int OH, int OW) {
+    return ((size_t)OC * (OH + 2 * kVFrame) * (OW + 2 * kVFrame) + (OC == 1 ? 0 : 256 + 2 * 16 * 64)) * sizeof(float);
 }
 
-// The data pass of a 3-class head: the frame holds the three dq maps, [3][OH + 38][OW + 38] (69 312 B at 38 x 38: above the
-// 64 KB default, the launch path raises the kernel's limit), and every tap reads three float4 of packed weights and twelve frame
-// values.  The parameter and reduction arrays follow the frame in the DYNAMIC area: the raised limit of 160 KiB is the whole CU's, so a
-// kernel that takes it must not hold static LDS beside it (the raise is refused and the launch fails).  A kernel of its own, not a template shared with the one above: sharing the body moved the one-channel kernel's register
-// allocation and instruction order, and its code object is pinned by the bit-identity tests of the one-channel path.
-static inline size_t value_bwd_dense3_lds(int OH, int OW) { return 3 * value_bwd_dense_lds(OH, OW) + (256 + 2 * 16 * 64) * sizeof(float); }
-static __global__ __launch_bounds__(256) void value_bwd_dense3_kernel(const ValueBwdArgs a) {
-    constexpr int OC = 3;
+template <int OC>
+static __global__ __launch_bounds__(256) void value_bwd_dense_kernel(const ValueBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];    // dq of the pair in a frame of zeros: [OC][OH + 38][OW + 38]
     const int j = blockIdx.y, t = threadIdx.x, cq = t & 15, slot = t >> 4;
     const int PW = a.OW + 2 * kVFrame, PH = a.OH + 2 * kVFrame;
-    float* prm = smem + OC * PH * PW;                                                  // [256]
-    float (*red)[16][64] = reinterpret_cast<float (*)[16][64]>(prm + 256);             // [2][16][64]
-    if (t < 64) {
-        float mean, invstd;
-        bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
-        prm[t] = a.gamma[t] * invstd; prm[64 + t] = a.beta[t]; prm[128 + t] = mean; prm[192 + t] = invstd;
+    float* prm;                      // [256]
+    float (*red)[16][64];            // [2][16][64]
+    if constexpr (OC == 1) {
+        __shared__ float prm1[256];
+        __shared__ float red1[2][16][64];
+        prm = prm1; red = red1;
+    } else {
+        prm = smem + OC * PH * PW;
+        red = reinterpret_cast<float (*)[16][64]>(prm + 256);
     }
+    value_bwd_params(a, j, t, prm);
+    // (the two loops over the output channels are do-whiles: written as `for`, their single trip at OC == 1 lives long enough to
+    // move what the compiler hoists out of the fill loop and to flip the tap loop's exit compare)
+    int o = 0;
 #pragma unroll
-    for (int o = 0; o < OC; ++o)
+    do {
         for (int i = t; i < PH * PW; i += 256) {
             const int y = i / PW - kVFrame, x = i % PW - kVFrame;
             smem[o * PH * PW + i] = (y >= 0 && y < a.OH && x >= 0 && x < a.OW) ? a.dq[(((int64_t)j * OC + o) * a.OH + y) * a.OW + x] : 0.f;
         }
+    } while (++o < OC);
     __syncthreads();
     // frame position of output (py, px) for each of the thread's four pixels; output (py - ty, px - tx) lies ty rows and tx columns
     // in front of it (rows -19 .. OH + 18 of the frame: always inside)
@@ -629,8 +576,9 @@ static __global__ __launch_bounds__(256) void value_bwd_dense3_kernel(const Valu
     for (int ty = 0; ty < 20; ++ty) {
 #pragma unroll 5
         for (int tx = 0; tx < 20; ++tx) {
+            o = 0;
 #pragma unroll
-            for (int o = 0; o < OC; ++o) {
+            do {
                 const float4 w = ld4(wq + (o * 400 + ty * 20 + tx) * 64);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -638,7 +586,7 @@ static __global__ __launch_bounds__(256) void value_bwd_dense3_kernel(const Valu
                     dact[i][0] = fmaf(g, w.x, dact[i][0]); dact[i][1] = fmaf(g, w.y, dact[i][1]);
                     dact[i][2] = fmaf(g, w.z, dact[i][2]); dact[i][3] = fmaf(g, w.w, dact[i][3]);
                 }
-            }
+            } while (++o < OC);
         }
     }
     float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
@@ -661,13 +609,7 @@ static __global__ __launch_bounds__(256) void value_bwd_dense3_kernel(const Valu
 #pragma unroll
     for (int c = 0; c < 4; ++c) { red[0][slot][4 * cq + c] = s1[c]; red[1][slot][4 * cq + c] = s2[c]; }
     __syncthreads();
-    if (t < 128) {     // (the per-channel norm1 sums keep their one atomic per workgroup, as in value_bwd_kernel)
-        const int q = t >> 6, c = t & 63;
-        float tot = 0.f;
-        for (int k = 0; k < 16; ++k) tot += red[q][k][c];
-        atomicAdd((q ? a.o2 : a.o1) + (int64_t)j * 64 + c + stat_rep(), (double)tot);
-        atomicAdd((q ? a.dgamma : a.dbeta) + c, tot);
-    }
+    value_bwd_sums(a, j, t, red);
 }
 
 // dW[c][ty][tx] += sum over pairs, oy, ox of dq[j][oy][ox] * act[j][oy + ty][ox + tx][c].
@@ -677,6 +619,9 @@ static __global__ __launch_bounds__(256) void value_bwd_dense3_kernel(const Valu
 // outputs at a time: 4 dq values and 23 activations feed 80 multiply-adds into its 20 per-tap-column accumulators (fp32 along a
 // row, carried in fp64 from row chunk to row chunk and pair to pair).  The rows meet in LDS (fp64, over the staging area) in row
 // order, and one thread per element adds the rounded total to the gradient array.
+// OC output channels (dq [pair][OC][OH][OW], dW [OC][64][20][20]): the output channel is the third grid dimension, 20 x 16 x OC
+// workgroups that each stage the activations for themselves (the 60 per-tap-column accumulators of a 3-class head, in fp32 and fp64,
+// would not fit one thread's registers without scratch), same order of summation per element.
 struct ValueWgradDenseArgs {
     const float* h1; Plane p4;
     const double* hsum; const double* hsq;
@@ -690,6 +635,7 @@ static inline size_t value_wgrad_dense_lds(const ValueWgradDenseArgs& a) {
     return std::max(stage, meet) + 16 * sizeof(float);
 }
 
+template <int OC>
 static __global__ __launch_bounds__(256) void value_wgrad_dense_kernel(const ValueWgradDenseArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* acts = smem;                                   // [RC][Wp] float4
@@ -697,78 +643,7 @@ static __global__ __launch_bounds__(256) void value_wgrad_dense_kernel(const Val
     double* red = reinterpret_cast<double*>(smem);        // [64][20][4], once the last chunk has been read
     float* prm = smem + max(a.RC * (a.Wp * 4 + a.OWp), 64 * 80 * 2);      // mean[4], scale[4], beta[4]
     const int ty = blockIdx.x, cq = blockIdx.y, t = threadIdx.x, c = t & 3, g = t >> 2;
-    const int W = a.p4.W;
-    double tot[20];
-#pragma unroll
-    for (int k = 0; k < 20; ++k) tot[k] = 0.0;
-    for (int j = 0; j < a.n_pairs; ++j) {
-        if (t < 4) {
-            float mean, invstd;
-            bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + 4 * cq + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
-            prm[t] = mean; prm[4 + t] = a.gamma[4 * cq + t] * invstd; prm[8 + t] = a.beta[4 * cq + t];
-        }
-        for (int r0 = 0; r0 < a.OH; r0 += a.RC) {
-            const int nr = min(a.RC, a.OH - r0);
-            __syncthreads();        // the parameters are written; the previous chunk has been read
-            for (int i = t; i < nr * a.Wp; i += 256) {
-                const int row = i / a.Wp, x = i - row * a.Wp;
-                float4 v = zero4();
-                if (x < W) v = bnrelu4(ld4(a.h1 + ((int64_t)j * a.p4.HWp + (r0 + row + ty) * W + x) * 64 + 4 * cq), prm, 4);
-                *reinterpret_cast<float4*>(acts + (size_t)i * 4) = v;
-            }
-            for (int i = t; i < nr * a.OWp; i += 256) {
-                const int row = i / a.OWp, x = i - row * a.OWp;
-                dqs[i] = x < a.OW ? a.dq[((int64_t)j * a.OH + r0 + row) * a.OW + x] : 0.f;
-            }
-            __syncthreads();
-            if (g < nr) {
-                float acc[20];
-#pragma unroll
-                for (int k = 0; k < 20; ++k) acc[k] = 0.f;
-                const float* ar = acts + (size_t)g * a.Wp * 4 + c;
-                const float* dr = dqs + g * a.OWp;
-                for (int ox = 0; ox < a.OWp; ox += 4) {
-                    const float4 d4 = ld4(dr + ox);
-                    const float d[4] = {d4.x, d4.y, d4.z, d4.w};
-                    float av[23];
-#pragma unroll
-                    for (int k = 0; k < 23; ++k) av[k] = ar[(ox + k) * 4];
-#pragma unroll
-                    for (int b = 0; b < 4; ++b)
-#pragma unroll
-                        for (int tx = 0; tx < 20; ++tx) acc[tx] = fmaf(d[b], av[b + tx], acc[tx]);
-                }
-#pragma unroll
-                for (int k = 0; k < 20; ++k) tot[k] += (double)acc[k];
-            }
-        }
-    }
-    __syncthreads();             // the staging area becomes the meeting place
-#pragma unroll
-    for (int tx = 0; tx < 20; ++tx) red[g * 80 + tx * 4 + c] = tot[tx];
-    __syncthreads();
-    if (t < 80) {
-        double sum = 0.0;
-        for (int k = 0; k < 64; ++k) sum += red[k * 80 + t];
-        const int tx = t >> 2, ch = 4 * cq + (t & 3);
-        float* dst = a.dw2 + (int64_t)ch * 400 + ty * 20 + tx;
-        *dst = *dst + (float)sum;       // one writer per element
-    }
-}
-
-// The weight pass of a 3-class head, dW [3][64][20][20]: the output channel is the third grid dimension - 20 x 16 x 3 workgroups, the
-// activations staged once per output channel (60 per-tap-column accumulators in fp32 and fp64 per thread would not fit the
-// register file without scratch).  Same order of summation per element as the kernel above; a kernel of its own for the same reason
-// as value_bwd_dense3_kernel.
-static __global__ __launch_bounds__(256) void value_wgrad_dense3_kernel(const ValueWgradDenseArgs a) {
-    constexpr int OC = 3;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* acts = smem;                                   // [RC][Wp] float4
-    float* dqs = acts + (size_t)a.RC * a.Wp * 4;          // [RC][OWp]
-    double* red = reinterpret_cast<double*>(smem);        // [64][20][4], once the last chunk has been read
-    float* prm = smem + max(a.RC * (a.Wp * 4 + a.OWp), 64 * 80 * 2);      // mean[4], scale[4], beta[4]
-    const int ty = blockIdx.x, cq = blockIdx.y, t = threadIdx.x, c = t & 3, g = t >> 2;
-    const int o = blockIdx.z;
+    const int o = OC == 1 ? 0 : blockIdx.z;
     const int W = a.p4.W;
     double tot[20];
 #pragma unroll
@@ -1606,6 +1481,41 @@ static __global__ void zero_uncovered_kernel(void* G, int ld, Plane p, int Hc, i
 }
 
 // ------------------------------------------------------------------------------------
+// The two trees a workgroup's 256 threads end in: the best (value, index) and the sum.
+// ------------------------------------------------------------------------------------
+// Largest value and its index, exactly like np.argmax: lowest index on ties, and a NaN beats every number (the FIRST NaN
+// wins) - a diverged network surfaces as a NaN best value instead of an arbitrary but valid-looking action.
+__device__ __forceinline__ bool argmax_better(float x, int i, float bx, int bi) {
+    if (bi == 0x7fffffff) return true;                  // nothing held yet
+    const bool xn = x != x, bn = bx != bx;
+    if (xn != bn) return xn;
+    if (xn) return i < bi;
+    return x > bx || (x == bx && i < bi);
+}
+// The tree over a workgroup's 256 (value, index) slots, thread t's own in bv[t], bi[t] (LDS): the best by argmax_better's rules ends
+// in slot 0.  A slot with index 0x7fffffff is empty and never wins.
+__device__ __forceinline__ void block_argmax(float* bv, int* bi, int t) {
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+            const float x = bv[t + s]; const int j = bi[t + s];
+            if (j != 0x7fffffff && argmax_better(x, j, bv[t], bi[t])) { bv[t] = x; bi[t] = j; }
+        }
+        __syncthreads();
+    }
+}
+// The fixed sum tree over a workgroup's 256 slots of one or more LDS arrays (thread t's own in r[t]): the sums end in slot 0 of
+// each.  The pairing order is part of the results (double sums, bit for bit).
+template <class... T>
+__device__ __forceinline__ void block_sum(int t, T*... r) {
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) { ((r[t] += r[t + s]), ...); }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // Losses (code/trainer.py:345-348 Huber on element [0,0,0,0]; :296-299 +
 // code/utils.py:306-313 class-weighted cross entropy, weights {1,1,0}).
 // ------------------------------------------------------------------------------------
@@ -1659,11 +1569,7 @@ static __global__ __launch_bounds__(256) void loss_map_kernel(const float* q, co
         dq[o + i] = w == 0.f ? 0.f : w * g;
     }
     red[t] = sum;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
+    block_sum(t, red);
     if (t == 0) loss[j] = red[0];
 }
 
@@ -1693,11 +1599,7 @@ static __global__ __launch_bounds__(256) void loss_map_ce_kernel(const float* q,
         cnt += 1.f;
     }
     red[0][t] = sum; red[1][t] = cnt;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) { red[0][t] += red[0][t + s]; red[1][t] += red[1][t + s]; }
-        __syncthreads();
-    }
+    block_sum(t, red[0], red[1]);
     const float W = red[1][0];
     if (t == 0) loss[j] = W > 0.f ? red[0][0] / W : 0.f;
     const float scale = 1.f / W;                 // (unused when W == 0: every pixel is masked then)
@@ -1754,27 +1656,7 @@ static __global__ void heightmap_warp_kernel(const HeightmapArgs a) {
                                    tap(y0 + 1, x0 + 1) * (double)w11;
 }
 
-// Largest value and its index, exactly like np.argmax: lowest index on ties, and a NaN beats every number (the FIRST NaN
-// wins) - a diverged network surfaces as a NaN best value instead of an arbitrary but valid-looking action.  One workgroup.
-__device__ __forceinline__ bool argmax_better(float x, int i, float bx, int bi) {
-    if (bi == 0x7fffffff) return true;                  // nothing held yet
-    const bool xn = x != x, bn = bx != bx;
-    if (xn != bn) return xn;
-    if (xn) return i < bi;
-    return x > bx || (x == bx && i < bi);
-}
-// The tree over a workgroup's 256 (value, index) slots, thread t's own in bv[t], bi[t] (LDS): the best by argmax_better's rules ends
-// in slot 0.  A slot with index 0x7fffffff is empty and never wins.
-__device__ __forceinline__ void block_argmax(float* bv, int* bi, int t) {
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) {
-            const float x = bv[t + s]; const int j = bi[t + s];
-            if (j != 0x7fffffff && argmax_better(x, j, bv[t], bi[t])) { bv[t] = x; bi[t] = j; }
-        }
-        __syncthreads();
-    }
-}
+// np.argmax of an array by argmax_better's rules (smg_argmax).  One workgroup.
 static __global__ __launch_bounds__(256) void argmax_kernel(const float* v, int n, int* idx_out, float* val_out) {
     __shared__ float bv[256];
     __shared__ int bi[256];
@@ -1839,32 +1721,28 @@ static __global__ void bn_update_kernel(const BnUpdDesc* descs, const double* st
 // ------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam, no amsgrad, no weight decay).
 // ------------------------------------------------------------------------------------
-static __global__ void adam_kernel(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
-                            float eps, float bc1, float bc2_sqrt) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float gi = g[i];
-        const float mi = m[i] + (gi - m[i]) * (1.f - b1);           // torch: exp_avg.lerp_(grad, 1-beta1)
-        const float vi = v[i] * b2 + (1.f - b2) * gi * gi;           // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] - (lr / bc1) * (mi / denom);
-    }
+// one element's step; the two step-dependent scalars are lr / (1 - beta1^t) and sqrt(1 - beta2^t)
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float lr_over_bc1, float b1, float b2, float eps, float bc2_sqrt) {
+    const float mi = m + (g - m) * (1.f - b1);           // torch: exp_avg.lerp_(grad, 1-beta1)
+    const float vi = v * b2 + (1.f - b2) * g * g;        // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
+    m = mi;
+    v = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p = p - lr_over_bc1 * (mi / denom);
 }
 
-// The same step with its two step-dependent scalars (lr / (1 - beta1^t), sqrt(1 - beta2^t)) read from device memory: the form
-// a captured training step replays (smg_train_step_graph) - the host refreshes the scalars, the graph's kernel arguments stay.
+static __global__ void adam_kernel(float* p, const float* g, float* m, float* v, int64_t n, float lr_over_bc1, float b1, float b2,
+                            float eps, float bc2_sqrt) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        adam_update(p[i], g[i], m[i], v[i], lr_over_bc1, b1, b2, eps, bc2_sqrt);
+}
+
+// The same step with its two scalars read from device memory: the form a captured training step replays (smg_train_step_graph) -
+// the host refreshes the scalars, the graph's kernel arguments stay.
 static __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, int64_t n, const float* sc, float b1, float b2, float eps) {
-    const float lr = sc[0], bc2_sqrt = sc[1];
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float gi = g[i];
-        const float mi = m[i] + (gi - m[i]) * (1.f - b1);
-        const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] - (lr / 1.f) * (mi / denom);
-    }
+    const float lr_over_bc1 = sc[0], bc2_sqrt = sc[1];
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        adam_update(p[i], g[i], m[i], v[i], lr_over_bc1, b1, b2, eps, bc2_sqrt);
 }
 
 }  // namespace smg

@@ -827,7 +827,7 @@ int smg_adam_step(float* params, const float* grads, float* m, float* v, int64_t
     int blocks = (int)((count + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params + offset, grads + offset, m + offset, v + offset,
-                       count, step_size, beta1, beta2, eps, 1.0f, bc2_sqrt);
+                       count, step_size, beta1, beta2, eps, bc2_sqrt);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -8,7 +8,7 @@
 //   scene_list_walk                the loss on K LISTED pixels per pair (smg_loss_scene_ce; smg_loss_scene's kernel keeps the same
 //                                  loop in a copy of its own, for the reason its comment gives)
 //   scene_box_walk                 the loss on a whole label IMAGE per pair (smg_loss_scene_map, smg_loss_scene_map_ce)
-// The __global__ kernels are thin instantiations of these; the block trees they end in are block_argmax (elem.cuh) and block_sum.
+// The __global__ kernels are thin instantiations of these; the block trees they end in are block_argmax and block_sum (elem.cuh).
 //
 // Geometry (include/smg_hip.h has the derivation), all in double, coordinates (x = column, y = row):
 //   heightmap pixel (iy, ix) -> centre of its 2x2 block of the padded input   x = 2 ix + 0.5 + pad
@@ -53,17 +53,6 @@ __device__ __forceinline__ double scene_interp(const ScenePoint& p, QPtr Q, int 
     const int o = p.y0 * OW + p.x0;
     const double q00 = (double)Q[o], q01 = (double)Q[o + 1], q10 = (double)Q[o + OW], q11 = (double)Q[o + OW + 1];
     return (1.0 - p.fy) * ((1.0 - p.fx) * q00 + p.fx * q01) + p.fy * ((1.0 - p.fx) * q10 + p.fx * q11);
-}
-
-// The fixed sum tree over a workgroup's 256 slots of one or more LDS arrays (thread t's own in r[t]): the sums end in slot 0 of
-// each.  The pairing order is part of the results (double sums, bit for bit).
-template <class... T>
-__device__ __forceinline__ void block_sum(int t, T*... r) {
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) { ((r[t] += r[t + s]), ...); }
-        __syncthreads();
-    }
 }
 
 // The reactive net's three class planes at a scene point (smg_scene_class_maps / smg_scene_class_argmax / smg_loss_scene_ce /
