@@ -1,36 +1,20 @@
 """CPU-side checks of the dense class-map interface of the reactive method (no GPU): the C ABI declares and exports
 smg_loss_map_ce, the four Trainer entry points exist, refuse a reinforcement trainer, refuse to run without the GPU instead of
 falling back to anything, and reject wrong shapes, class indices and pixels before they touch the engine."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
-from helpers import REPO
-
-import smg_hip
-
-
-def _cpu_trainer(method='reactive'):
-    from trainer import Trainer
-    return Trainer(method, 0.5, False, None, True)       # force_cpu: no engine can exist behind it
+from map_harness import assert_declared_exported_and_bound, cpu_trainer
 
 
 def test_loss_map_ce_is_declared_exported_and_bound():
-    hdr = open(os.path.join(REPO, "include", "smg_hip.h")).read()
-    assert re.search(r"\bint\s+smg_loss_map_ce\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*label_dev,\s*"
-                     r"int n_pairs,\s*float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*void\*\s*stream\)", hdr)
-    assert int(re.search(r"#define\s+SMG_ABI_VERSION\s+(\d+)", hdr).group(1)) == smg_hip.ABI_VERSION >= 6
-    assert hasattr(ctypes.CDLL(smg_hip.LIB_PATH), "smg_loss_map_ce")
-    assert "smg_loss_map_ce" in smg_hip.EXPORTS
-    assert len(smg_hip.lib().smg_loss_map_ce.argtypes) == 7
-    assert callable(smg_hip.Engine.loss_map_ce)
+    assert_declared_exported_and_bound(
+        "smg_loss_map_ce", r"\bint\s+smg_loss_map_ce\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*label_dev,\s*"
+        r"int n_pairs,\s*float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*void\*\s*stream\)", 7, "loss_map_ce")
 
 
 def test_class_map_entry_points_have_no_cpu_fallback():
-    tr = _cpu_trainer()
+    tr = cpu_trainer('reactive')
     d = np.zeros((240, 240))
     with pytest.raises(RuntimeError):
         tr.forward_class_maps(d, d, 0)
@@ -43,7 +27,7 @@ def test_class_map_entry_points_have_no_cpu_fallback():
 
 
 def test_class_map_entry_points_are_for_the_reactive_method():
-    tr = _cpu_trainer('reinforcement')
+    tr = cpu_trainer('reinforcement')
     d = np.zeros((240, 240))
     with pytest.raises(ValueError):
         tr.forward_class_maps(d, d, 0)
@@ -58,7 +42,7 @@ def test_class_map_entry_points_are_for_the_reactive_method():
 def test_train_batch_class_maps_rejects_bad_input_before_the_engine():
     from trainer import Trainer
     assert Trainer.dense_map_size(240) == 3
-    tr = _cpu_trainer()
+    tr = cpu_trainer('reactive')
     d = np.zeros((240, 240))                 # S = 704: 3 x 3 maps
     # (on this trainer anything that reaches the engine raises RuntimeError: a ValueError proves the check came first)
     with pytest.raises(ValueError):

@@ -1,32 +1,16 @@
 """CPU-side checks of the dense-Q-map interface (no GPU): the C ABI declares and exports smg_loss_map, the Python entry
 points exist and - like every other entry point - refuse to run without the GPU instead of falling back to anything, and
 train_batch_maps rejects label / weight maps of the wrong shape before it touches the engine."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
-from helpers import REPO
-
-import smg_hip
-
-
-def _cpu_trainer(method='reinforcement'):
-    from trainer import Trainer
-    return Trainer(method, 0.5, False, None, True)       # force_cpu: no engine can exist behind it
+from map_harness import assert_declared_exported_and_bound, cpu_trainer
 
 
 def test_loss_map_is_declared_exported_and_bound():
-    hdr = open(os.path.join(REPO, "include", "smg_hip.h")).read()
-    assert re.search(r"\bint\s+smg_loss_map\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*label_dev,\s*"
-                     r"const float\*\s*weight_dev,\s*int n_pairs,\s*float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*void\*\s*stream\)", hdr)
-    assert int(re.search(r"#define\s+SMG_ABI_VERSION\s+(\d+)", hdr).group(1)) == smg_hip.ABI_VERSION >= 5
-    assert hasattr(ctypes.CDLL(smg_hip.LIB_PATH), "smg_loss_map")
-    assert "smg_loss_map" in smg_hip.EXPORTS
-    assert len(smg_hip.lib().smg_loss_map.argtypes) == 8
-    assert callable(smg_hip.Engine.loss_map)
+    hdr = assert_declared_exported_and_bound(
+        "smg_loss_map", r"\bint\s+smg_loss_map\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*label_dev,\s*"
+        r"const float\*\s*weight_dev,\s*int n_pairs,\s*float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*void\*\s*stream\)", 8, "loss_map")
     assert '"head_bwd"' in hdr
 
 
@@ -37,7 +21,7 @@ def test_dense_map_size_follows_the_network_strides():
 
 
 def test_dense_entry_points_have_no_cpu_fallback():
-    tr = _cpu_trainer()
+    tr = cpu_trainer('reinforcement')
     d = np.zeros((240, 240))
     with pytest.raises(RuntimeError):
         tr.forward_dense(d, d, 0)
@@ -50,7 +34,7 @@ def test_dense_entry_points_have_no_cpu_fallback():
 
 
 def test_train_batch_maps_rejects_wrong_shapes_before_the_engine():
-    tr = _cpu_trainer()
+    tr = cpu_trainer('reinforcement')
     d = np.zeros((240, 240))                 # S = 704: 3 x 3 maps
     # (on this trainer anything that reaches the engine raises RuntimeError: a ValueError proves the check came first)
     with pytest.raises(ValueError):
@@ -68,7 +52,7 @@ def test_train_batch_maps_rejects_wrong_shapes_before_the_engine():
 
 
 def test_dense_training_is_for_the_reinforcement_method():
-    tr = _cpu_trainer('reactive')
+    tr = cpu_trainer('reactive')
     d = np.zeros((240, 240))
     with pytest.raises(ValueError):
         tr.train_batch_maps(d, d, 0, [1], np.zeros((1, 3, 3)))

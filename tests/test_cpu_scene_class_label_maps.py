@@ -3,14 +3,12 @@ the binding carries it, the fp64 restatement of tests/scene_class_label_ref.py -
 element - agree with each other and with scene_class_ref.scene_class_loss, and Trainer.train_batch_scene_class_maps refuses
 before it touches the engine."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import REPO
+from map_harness import assert_declared_exported_and_bound, cpu_trainer
 
 import scene_class_label_ref
 import scene_class_ref
@@ -20,25 +18,11 @@ import smg_hip
 ROTS = (0, 3, 8, 13)
 
 
-def _cpu_trainer(method='reactive'):
-    from trainer import Trainer
-    tr = Trainer(method, 0.5, False, None, True)       # force_cpu: no engine can exist behind it
-    tr.model.gnum_rotations = tr.model.snum_rotations = 16
-    return tr
-
-
 def test_loss_scene_map_ce_is_declared_exported_and_bound():
-    hdr = open(os.path.join(REPO, "include", "smg_hip.h")).read()
-    assert re.search(r"\bint\s+smg_loss_scene_map_ce\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*affine_host,\s*int hm_size,\s*"
-                     r"int n_pairs,\s*const float\*\s*label_dev,\s*float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*void\*\s*stream\)", hdr)
-    assert int(re.search(r"#define\s+SMG_ABI_VERSION\s+(\d+)", hdr).group(1)) == smg_hip.ABI_VERSION
-    so = ctypes.CDLL(smg_hip.LIB_PATH)
-    assert hasattr(so, "smg_loss_scene_map_ce")
-    assert "smg_loss_scene_map_ce" in smg_hip.EXPORTS
-    assert len(smg_hip.lib().smg_loss_scene_map_ce.argtypes) == 9
-    assert callable(smg_hip.Engine.loss_scene_map_ce)
-    from trainer import Trainer
-    assert callable(Trainer.train_batch_scene_class_maps)
+    assert_declared_exported_and_bound(
+        "smg_loss_scene_map_ce", r"\bint\s+smg_loss_scene_map_ce\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*affine_host,\s*int hm_size,\s*"
+        r"int n_pairs,\s*const float\*\s*label_dev,\s*float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*void\*\s*stream\)", 9, "loss_scene_map_ce",
+        ["train_batch_scene_class_maps"])
 
 
 def test_a_library_without_the_symbol_is_reported_as_a_stale_build(monkeypatch):
@@ -117,7 +101,7 @@ def test_an_image_without_a_labelled_pixel_gives_zero():
 def test_train_batch_scene_class_maps_has_no_cpu_fallback():
     """A whole image - labelled pixels without a window among them: nothing is raised for those - passes every check and reaches
     the engine, which a CPU trainer does not have."""
-    tr = _cpu_trainer()
+    tr = cpu_trainer('reactive')
     d = np.zeros((240, 240))
     lab = np.full((2, 240, 240), 2.0)
     lab[:, 118:123, 118:123] = 1.0
@@ -133,8 +117,8 @@ def test_train_batch_scene_class_maps_refuses_before_the_engine():
     d = np.zeros((240, 240))
     ok = np.full((1, 240, 240), 2.0)
     with pytest.raises(ValueError):
-        _cpu_trainer('reinforcement').train_batch_scene_class_maps(d, d, 0, [1], ok)
-    tr = _cpu_trainer()
+        cpu_trainer('reinforcement').train_batch_scene_class_maps(d, d, 0, [1], ok)
+    tr = cpu_trainer('reactive')
     d224 = np.zeros((224, 224))              # S = 640: a 1 x 1 map has no extent
     with pytest.raises(ValueError):
         tr.train_batch_scene_class_maps(d224, d224, 0, [1], np.full((1, 224, 224), 2.0))

@@ -3,46 +3,28 @@ smg_scene_class_argmax / smg_loss_scene_ce (ABI version 8), the fp64 restatement
 over torch's own bilinear grid_sample of the logits, its point form is torch's weighted nll_loss, and the Python entry points
 refuse - a reinforcement trainer, a 224^2 heightmap, bad labels, shapes and pixels - before they touch the engine, while the
 reinforcement scene-frame entry points keep refusing a reactive trainer."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import REPO
+from map_harness import assert_declared_exported_and_bound, cpu_trainer
 
 import scene_class_ref
 import scene_ref
-import smg_hip
-
-
-def _cpu_trainer(method='reactive'):
-    from trainer import Trainer
-    tr = Trainer(method, 0.5, False, None, True)       # force_cpu: no engine can exist behind it
-    tr.model.gnum_rotations = tr.model.snum_rotations = 16
-    return tr
 
 
 def test_scene_class_entry_points_are_declared_exported_and_bound():
-    hdr = open(os.path.join(REPO, "include", "smg_hip.h")).read()
-    assert re.search(r"\bint\s+smg_scene_class_maps\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*int n_maps,\s*const float\*\s*affine_host,\s*"
-                     r"int hm_size,\s*int cls,\s*float\*\s*out_dev,\s*void\*\s*stream\)", hdr)
-    assert re.search(r"\bint\s+smg_scene_class_argmax\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*int n_maps,\s*const float\*\s*affine_host,\s*"
-                     r"int hm_size,\s*int cls,\s*int\*\s*idx_out_dev,\s*float\*\s*val_out_dev,\s*void\*\s*stream\)", hdr)
-    assert re.search(r"\bint\s+smg_loss_scene_ce\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*affine_host,\s*int hm_size,\s*"
-                     r"int n_pairs,\s*int K,\s*const int\*\s*pixels_dev,\s*const float\*\s*label_dev,\s*float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*"
-                     r"void\*\s*stream\)", hdr)
-    assert int(re.search(r"#define\s+SMG_ABI_VERSION\s+(\d+)", hdr).group(1)) == smg_hip.ABI_VERSION >= 8
-    so = ctypes.CDLL(smg_hip.LIB_PATH)
-    for name, nargs, method in (("smg_scene_class_maps", 8, "scene_class_maps"), ("smg_scene_class_argmax", 9, "scene_class_argmax"),
-                                ("smg_loss_scene_ce", 11, "loss_scene_ce")):
-        assert hasattr(so, name)
-        assert name in smg_hip.EXPORTS
-        assert len(getattr(smg_hip.lib(), name).argtypes) == nargs
-        assert callable(getattr(smg_hip.Engine, method))
+    assert_declared_exported_and_bound(
+        "smg_scene_class_maps", r"\bint\s+smg_scene_class_maps\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*int n_maps,\s*const float\*\s*affine_host,\s*"
+        r"int hm_size,\s*int cls,\s*float\*\s*out_dev,\s*void\*\s*stream\)", 8, "scene_class_maps")
+    assert_declared_exported_and_bound(
+        "smg_scene_class_argmax", r"\bint\s+smg_scene_class_argmax\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*int n_maps,\s*const float\*\s*affine_host,\s*"
+        r"int hm_size,\s*int cls,\s*int\*\s*idx_out_dev,\s*float\*\s*val_out_dev,\s*void\*\s*stream\)", 9, "scene_class_argmax")
+    assert_declared_exported_and_bound(
+        "smg_loss_scene_ce", r"\bint\s+smg_loss_scene_ce\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*affine_host,\s*int hm_size,\s*"
+        r"int n_pairs,\s*int K,\s*const int\*\s*pixels_dev,\s*const float\*\s*label_dev,\s*float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*"
+        r"void\*\s*stream\)", 11, "loss_scene_ce")
 
 
 @pytest.mark.parametrize("hm,R", [(240, 16), (320, 16)])
@@ -106,7 +88,7 @@ def test_scene_class_ref_point_form_is_the_weighted_nll_loss():
 
 
 def test_scene_class_entry_points_have_no_cpu_fallback():
-    tr = _cpu_trainer()
+    tr = cpu_trainer('reactive')
     d = np.zeros((240, 240))
     with pytest.raises(RuntimeError):
         tr.forward_scene_class_maps(d, d, 0)
@@ -123,7 +105,7 @@ def test_scene_class_entry_points_have_no_cpu_fallback():
 
 
 def test_scene_class_entry_points_are_for_the_reactive_method():
-    tr = _cpu_trainer('reinforcement')
+    tr = cpu_trainer('reinforcement')
     d = np.zeros((240, 240))
     with pytest.raises(ValueError):
         tr.forward_scene_class_maps(d, d, 0)
@@ -134,7 +116,7 @@ def test_scene_class_entry_points_are_for_the_reactive_method():
 
 
 def test_reinforcement_scene_entry_points_still_refuse_a_reactive_trainer():
-    tr = _cpu_trainer('reactive')
+    tr = cpu_trainer('reactive')
     d = np.zeros((240, 240))
     with pytest.raises(ValueError):
         tr.forward_scene(d, d, 0)
@@ -145,7 +127,7 @@ def test_reinforcement_scene_entry_points_still_refuse_a_reactive_trainer():
 
 
 def test_scene_class_entry_points_refuse_before_the_engine():
-    tr = _cpu_trainer()
+    tr = cpu_trainer('reactive')
     d = np.zeros((240, 240))                 # S = 704: 3 x 3 maps, valid pixels around the centre only
     # (on this trainer anything that reaches the engine raises RuntimeError: a ValueError proves the check came first)
     from trainer import Trainer

@@ -1,41 +1,20 @@
 """CPU-side checks of the scene-frame label-map interface (no GPU): the C ABI declares and exports smg_loss_scene_map and the
 binding carries it, the fp64 restatement of tests/scene_label_ref.py - map form and gather by map element - agrees with
 scene_ref.scene_points + torch autograd, and Trainer.train_batch_scene_maps refuses before it touches the engine."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
-from helpers import REPO
+from map_harness import assert_declared_exported_and_bound, cpu_trainer
 
 import scene_label_ref
 import scene_ref
-import smg_hip
-
-
-def _cpu_trainer(method='reinforcement'):
-    from trainer import Trainer
-    tr = Trainer(method, 0.5, False, None, True)       # force_cpu: no engine can exist behind it
-    tr.model.gnum_rotations = tr.model.snum_rotations = 16
-    return tr
 
 
 def test_loss_scene_map_is_declared_exported_and_bound():
-    hdr = open(os.path.join(REPO, "include", "smg_hip.h")).read()
-    assert re.search(r"\bint\s+smg_loss_scene_map\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*affine_host,\s*int hm_size,\s*"
-                     r"int n_pairs,\s*const float\*\s*label_dev,\s*const float\*\s*weight_dev,\s*float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*"
-                     r"void\*\s*stream\)", hdr)
-    assert int(re.search(r"#define\s+SMG_ABI_VERSION\s+(\d+)", hdr).group(1)) == smg_hip.ABI_VERSION == 9
-    so = ctypes.CDLL(smg_hip.LIB_PATH)
-    assert hasattr(so, "smg_loss_scene_map")
-    assert "smg_loss_scene_map" in smg_hip.EXPORTS
-    assert smg_hip.lib().smg_version() == 9
-    assert len(smg_hip.lib().smg_loss_scene_map.argtypes) == 10
-    assert callable(smg_hip.Engine.loss_scene_map)
-    from trainer import Trainer
-    assert callable(Trainer.train_batch_scene_maps)
+    assert_declared_exported_and_bound(
+        "smg_loss_scene_map", r"\bint\s+smg_loss_scene_map\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*affine_host,\s*int hm_size,\s*"
+        r"int n_pairs,\s*const float\*\s*label_dev,\s*const float\*\s*weight_dev,\s*float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*"
+        r"void\*\s*stream\)", 10, "loss_scene_map", ["train_batch_scene_maps"])
 
 
 @pytest.mark.parametrize("hm", [240, 320])
@@ -102,7 +81,7 @@ def test_boxes_hold_every_touching_pixel_for_matrices_that_are_no_rotation():
 def test_train_batch_scene_maps_has_no_cpu_fallback():
     """Whole images with invalid pixels under them pass every check (nothing is raised for pixels without a window) and reach the
     engine, which a CPU trainer does not have."""
-    tr = _cpu_trainer()
+    tr = cpu_trainer('reinforcement')
     d = np.zeros((240, 240))
     with pytest.raises(RuntimeError):
         tr.train_batch_scene_maps(d, d, 0, [1, 2], np.zeros((2, 240, 240)), np.ones((2, 240, 240)))
@@ -114,8 +93,8 @@ def test_train_batch_scene_maps_refuses_before_the_engine():
     # (on a CPU trainer anything that reaches the engine raises RuntimeError: a ValueError proves the check came first)
     d = np.zeros((240, 240))
     with pytest.raises(ValueError):
-        _cpu_trainer('reactive').train_batch_scene_maps(d, d, 0, [1], np.zeros((1, 240, 240)))
-    tr = _cpu_trainer()
+        cpu_trainer('reactive').train_batch_scene_maps(d, d, 0, [1], np.zeros((1, 240, 240)))
+    tr = cpu_trainer('reinforcement')
     d224 = np.zeros((224, 224))              # S = 640: a 1 x 1 map has no extent
     with pytest.raises(ValueError):
         tr.train_batch_scene_maps(d224, d224, 0, [1], np.zeros((1, 224, 224)))

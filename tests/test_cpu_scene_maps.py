@@ -2,44 +2,27 @@
 smg_loss_scene, the fp64 restatement of the geometry (tests/scene_ref.py) agrees with torch's own bilinear grid_sample and with
 Trainer.scene_to_map, known answers pin the window geometry and the rotation, and the Python entry points refuse - without a
 GPU, for a reactive trainer, for invalid pixels, wrong shapes and a 224^2 heightmap - before they touch the engine."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import REPO
+from map_harness import assert_declared_exported_and_bound, cpu_trainer
 
 import scene_ref
-import smg_hip
-
-
-def _cpu_trainer(method='reinforcement'):
-    from trainer import Trainer
-    tr = Trainer(method, 0.5, False, None, True)       # force_cpu: no engine can exist behind it
-    tr.model.gnum_rotations = tr.model.snum_rotations = 16
-    return tr
 
 
 def test_scene_entry_points_are_declared_exported_and_bound():
-    hdr = open(os.path.join(REPO, "include", "smg_hip.h")).read()
-    assert re.search(r"\bint\s+smg_scene_maps\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*int64_t map_stride,\s*int n_maps,\s*"
-                     r"const float\*\s*affine_host,\s*int hm_size,\s*float\*\s*out_dev,\s*void\*\s*stream\)", hdr)
-    assert re.search(r"\bint\s+smg_scene_argmax\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*int64_t map_stride,\s*int n_maps,\s*"
-                     r"const float\*\s*affine_host,\s*int hm_size,\s*int\*\s*idx_out_dev,\s*float\*\s*val_out_dev,\s*void\*\s*stream\)", hdr)
-    assert re.search(r"\bint\s+smg_loss_scene\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*affine_host,\s*int hm_size,\s*"
-                     r"int n_pairs,\s*int K,\s*const int\*\s*pixels_dev,\s*const float\*\s*label_dev,\s*const float\*\s*weight_dev,\s*"
-                     r"float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*void\*\s*stream\)", hdr)
-    assert int(re.search(r"#define\s+SMG_ABI_VERSION\s+(\d+)", hdr).group(1)) == smg_hip.ABI_VERSION >= 7
-    so = ctypes.CDLL(smg_hip.LIB_PATH)
-    for name, nargs, method in (("smg_scene_maps", 8, "scene_maps"), ("smg_scene_argmax", 9, "scene_argmax"), ("smg_loss_scene", 12, "loss_scene")):
-        assert hasattr(so, name)
-        assert name in smg_hip.EXPORTS
-        assert len(getattr(smg_hip.lib(), name).argtypes) == nargs
-        assert callable(getattr(smg_hip.Engine, method))
+    assert_declared_exported_and_bound(
+        "smg_scene_maps", r"\bint\s+smg_scene_maps\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*int64_t map_stride,\s*int n_maps,\s*"
+        r"const float\*\s*affine_host,\s*int hm_size,\s*float\*\s*out_dev,\s*void\*\s*stream\)", 8, "scene_maps")
+    assert_declared_exported_and_bound(
+        "smg_scene_argmax", r"\bint\s+smg_scene_argmax\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*int64_t map_stride,\s*int n_maps,\s*"
+        r"const float\*\s*affine_host,\s*int hm_size,\s*int\*\s*idx_out_dev,\s*float\*\s*val_out_dev,\s*void\*\s*stream\)", 9, "scene_argmax")
+    assert_declared_exported_and_bound(
+        "smg_loss_scene", r"\bint\s+smg_loss_scene\s*\(\s*smg_engine\*\s*e,\s*const float\*\s*q_dev,\s*const float\*\s*affine_host,\s*int hm_size,\s*"
+        r"int n_pairs,\s*int K,\s*const int\*\s*pixels_dev,\s*const float\*\s*label_dev,\s*const float\*\s*weight_dev,\s*"
+        r"float\*\s*loss_dev,\s*float\*\s*dq_dev,\s*void\*\s*stream\)", 12, "loss_scene")
 
 
 @pytest.mark.parametrize("hm,R", [(240, 16), (320, 16)])
@@ -145,7 +128,7 @@ def test_rotation_sense_against_the_forward_own_rotation():
 
 
 def test_scene_entry_points_have_no_cpu_fallback():
-    tr = _cpu_trainer()
+    tr = cpu_trainer('reinforcement')
     d = np.zeros((240, 240))
     with pytest.raises(RuntimeError):
         tr.forward_scene(d, d, 0)
@@ -158,7 +141,7 @@ def test_scene_entry_points_have_no_cpu_fallback():
 
 
 def test_scene_entry_points_are_for_the_reinforcement_method():
-    tr = _cpu_trainer('reactive')
+    tr = cpu_trainer('reactive')
     d = np.zeros((240, 240))
     with pytest.raises(ValueError):
         tr.forward_scene(d, d, 0)
@@ -169,7 +152,7 @@ def test_scene_entry_points_are_for_the_reinforcement_method():
 
 
 def test_train_batch_scene_pixels_refuses_before_the_engine():
-    tr = _cpu_trainer()
+    tr = cpu_trainer('reinforcement')
     d = np.zeros((240, 240))                 # S = 704: 3 x 3 maps, valid pixels around the centre only
     # (on this trainer anything that reaches the engine raises RuntimeError: a ValueError proves the check came first)
     from trainer import Trainer

@@ -17,39 +17,11 @@ import torch
 import torch.nn.functional as F
 
 from helpers import grads_within_fp32_class, MEAN, STD, oracle_net, orc, q_close
+from map_harness import assert_bit_identical, cached_engine, filled, gpu, HEAD, make_trainer, stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-HEAD = "graspnet_val.grasp-val-"        # style 0's head (oracle.affordance.STYLE_HEAD)
 U = 2.0 ** -24                          # one fp32 rounding, relative
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()
-    return torch.device("cuda:0")
-
-
-def make_trainer(seed, R=16, out_ch=3):
-    import synthetic
-    from trainer import Trainer
-    tr = Trainer('reinforcement' if out_ch == 1 else 'reactive', 0.5, False, None, False)
-    sd = synthetic.make_state_dict(orc.state_layout(out_ch), seed)
-    tr.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-    tr.model.gnum_rotations = tr.model.snum_rotations = R
-    if out_ch == 1:
-        tr.model_target.load_state_dict(tr.model.state_dict())
-        tr.model_target.gnum_rotations = tr.model_target.snum_rotations = R
-    tr.optimizer.lr = 0.0
-    return tr
-
-
-def engine(S, out_ch=3):
-    import models
-    return models.get_engine(0, S, out_ch, 2, 1)
 
 
 def ce_map(q, y):
@@ -86,7 +58,7 @@ def test_loss_map_ce_kernel_vs_torch_fp64(gpu):
     dq: q - max and expf (3; the error of q - max moves an exponential e^-x by x e^-x u <= u / e), the sum (3 + 2 = 5), their
     quotient (3 + 5 + 1 = 9), - [c == y] (10), 1 / W (11), the product (12): gate 16 x 2^-24 / W per element (softmax and
     softmax - onehot are at most 1 in magnitude)."""
-    eng = engine(928)
+    eng = cached_engine(928, 3)
     assert (eng.OH, eng.OW) == (10, 10)
     g = torch.Generator().manual_seed(11)
     q = (2.0 * torch.randn((3, 3, 10, 10), generator=g)).float()
@@ -94,12 +66,11 @@ def test_loss_map_ce_kernel_vs_torch_fp64(gpu):
     y[0] = torch.randint(0, 3, (10, 10), generator=g)
     y[1, 6, 3] = 1
     assert sorted(np.unique(y[0].numpy())) == [0, 1, 2]
-    stream = torch.cuda.current_stream().cuda_stream
 
     def run(qh):
         qd, lab = qh.cuda(), y.float().reshape(3, 1, 10, 10).cuda()
-        loss, dq = torch.full((3,), -7.0, device="cuda"), torch.full_like(qd, -7.0)
-        eng.loss_map_ce(qd.data_ptr(), lab.data_ptr(), 3, loss.data_ptr(), dq.data_ptr(), stream)
+        loss, dq = filled((3,)), filled(qd.shape)
+        eng.loss_map_ce(qd.data_ptr(), lab.data_ptr(), 3, loss.data_ptr(), dq.data_ptr(), stream())
         torch.cuda.synchronize()
         return loss.cpu(), dq.cpu()
 
@@ -126,29 +97,28 @@ def test_loss_map_ce_kernel_vs_torch_fp64(gpu):
     p2 = torch.nonzero(y[0] == 2)[0]
     q_inf[0, 0, p2[0], p2[1]], q_inf[0, 1, p2[0], p2[1]], q_inf[0, 2, p2[0], p2[1]] = float("inf"), float("nan"), -float("inf")
     loss_i, dq_i = run(q_inf)
-    assert torch.equal(loss_i.view(torch.int32), loss.view(torch.int32))
-    assert torch.equal(dq_i.view(torch.int32), dq.view(torch.int32))
+    assert_bit_identical(loss_i, loss)
+    assert_bit_identical(dq_i, dq)
 
 
 def test_one_weighted_pixel_equals_smg_loss_mode_1(gpu):
     """At S = 640 the map is one pixel: smg_loss_map_ce's loss and dq on labels 0 and 1 are bit-identical to smg_loss mode 1's
     (W = 1: x / 1 and 1 * x are exact, the per-pixel arithmetic is the same operation for operation)."""
-    eng = engine(640)
+    eng = cached_engine(640, 3)
     assert (eng.OH, eng.OW) == (1, 1)
     g = torch.Generator().manual_seed(12)
     q = (2.0 * torch.randn((2, 3, 1, 1), generator=g)).float().cuda()
     lab = torch.tensor([0.0, 1.0], device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
     out = []
     for use_map in (False, True):
-        loss, dq = torch.full((2,), -1.0, device="cuda"), torch.full_like(q, -1.0)
+        loss, dq = filled((2,), -1.0), filled(q.shape, -1.0)
         if use_map:
-            eng.loss_map_ce(q.data_ptr(), lab.reshape(2, 1, 1, 1).data_ptr(), 2, loss.data_ptr(), dq.data_ptr(), stream)
+            eng.loss_map_ce(q.data_ptr(), lab.reshape(2, 1, 1, 1).data_ptr(), 2, loss.data_ptr(), dq.data_ptr(), stream())
         else:
-            eng.loss(1, q.data_ptr(), lab.data_ptr(), 2, loss.data_ptr(), dq.data_ptr(), stream)
+            eng.loss(1, q.data_ptr(), lab.data_ptr(), 2, loss.data_ptr(), dq.data_ptr(), stream())
         out.append((loss, dq))
-    assert torch.equal(out[0][0].view(torch.int32), out[1][0].view(torch.int32))
-    assert torch.equal(out[0][1].view(torch.int32), out[1][1].view(torch.int32))
+    assert_bit_identical(out[0][0], out[1][0])
+    assert_bit_identical(out[0][1], out[1][1])
     assert bool((out[1][0] > 0).all()) and bool((out[1][1] != 0).all())
 
 
@@ -187,8 +157,8 @@ def test_whole_class_map_training_vs_fp64_oracle_s928(gpu):
           % (float(qo.detach().min()), float(qo.detach().max()), float(torch.softmax(qo.detach(), 1).max()), float(loss32.detach()), float(loss64.detach())))
     loss32.backward()
 
-    tr = make_trainer(1)
-    eng = engine(928)
+    tr = make_trainer('reactive', 1)
+    eng = cached_engine(928, 3)
     head_names = [HEAD + "conv1.weight", HEAD + "norm1.weight", HEAD + "norm1.bias"]
     got = {}
     try:
@@ -223,14 +193,14 @@ def test_config5_geometry_three_class_head_alone_vs_fp64(gpu):
     -> map cross entropy is rebuilt with torch in fp64 (the truth) and in fp32, and the engine's dh1 and its gradients of
     conv1.weight [3, 64, 20, 20], norm1.weight and norm1.bias must lie within 3x the fp32 evaluation's own error."""
     import synthetic
-    tr = make_trainer(0, R=32)
+    tr = make_trainer('reactive', 0, R=32)
     depth, masks = synthetic.heightmap_scene(4, size=640, n_boxes=8)
     md = depth * masks[0]
     rots = [5, 6]
     n, side, HW, HWp = len(rots), 38, 57 * 57, 3264
     lab = np.minimum(np.floor(synthetic.uniform(5, "cls5/lab", n * side * side, 0, 3)), 2).astype(np.int64).reshape(n, side, side)
     assert all((lab[j] == c).any() for j in range(n) for c in range(3))
-    eng = engine(1824)
+    eng = cached_engine(1824, 3)
     eng.set_option("head_bwd", 2)
     try:
         loss, q = tr.train_batch_class_maps(depth, md, 0, rots, lab, return_q=True)
@@ -284,12 +254,12 @@ def test_class_map_training_is_bit_reproducible(gpu):
     value-convolution weight gradient [3, 64, 20, 20] - every element written by one thread, pairs in index order - bit for bit
     equal and not zero, dh1 too."""
     import synthetic
-    tr = make_trainer(3)
+    tr = make_trainer('reactive', 3)
     depth, masks = synthetic.heightmap_scene(6, size=320)
     md = depth * masks[1]
     rots = [1, 6, 11]
     lab = np.minimum(np.floor(synthetic.uniform(7, "clsdet/lab", 300, 0, 3)), 2).reshape(3, 10, 10)
-    eng = engine(928)
+    eng = cached_engine(928, 3)
     HWp = eng.HWp[5]
     runs = []
     for it in range(2):
@@ -298,15 +268,15 @@ def test_class_map_training_is_bit_reproducible(gpu):
         runs.append((g.clone(), eng.debug_read("dh1", count=3 * HWp * 64).copy()))
     assert tuple(runs[0][0].shape) == (3, 64, 20, 20)
     assert all(float(runs[0][0][o].abs().max()) > 0 for o in range(3))
-    assert torch.equal(runs[0][0].view(torch.int32), runs[1][0].view(torch.int32)), int((runs[0][0] != runs[1][0]).sum())
-    assert np.array_equal(runs[0][1].view(np.uint32), runs[1][1].view(np.uint32))
+    assert_bit_identical(runs[0][0], runs[1][0])
+    assert_bit_identical(runs[0][1], runs[1][1])
 
 
 def test_train_batch_class_pixels_equals_train_batch_class_maps(gpu):
     """One labelled pixel per sample is a label map of class 2 with that one entry: loss and logits bit-identical (240^2 heightmap,
     3 x 3 maps, two samples, one per class)."""
     import synthetic
-    tr = make_trainer(2)
+    tr = make_trainer('reactive', 2)
     depth, masks = synthetic.heightmap_scene(8, size=240, n_boxes=8)
     md = depth * masks[0]
     rots, pixels, labels = [5, 9], [(2, 1), (0, 2)], [0, 1]
@@ -316,8 +286,8 @@ def test_train_batch_class_pixels_equals_train_batch_class_maps(gpu):
     loss_a, q_a = tr.train_batch_class_maps(depth, md, 0, rots, maps, return_q=True)
     loss_b, q_b = tr.train_batch_class_pixels(depth, md, 0, rots, pixels, labels, return_q=True)
     assert tuple(q_a.shape) == (2, 3, 3, 3)
-    assert torch.equal(q_a.view(torch.int32), q_b.view(torch.int32))
-    assert torch.equal(loss_a.view(torch.int32), loss_b.view(torch.int32))
+    assert_bit_identical(q_a, q_b)
+    assert_bit_identical(loss_a, loss_b)
     assert bool((loss_a > 0).all())
     # ... and the value is the cross entropy of that one pixel
     for k, ((oy, ox), c) in enumerate(zip(pixels, labels)):
@@ -327,7 +297,7 @@ def test_train_batch_class_pixels_equals_train_batch_class_maps(gpu):
 
 def test_forward_class_maps_and_best_class_map_action(gpu):
     import synthetic
-    tr = make_trainer(4)
+    tr = make_trainer('reactive', 4)
     depth, masks = synthetic.heightmap_scene(0)
     md = depth * masks[0]
     p = tr.forward_class_maps(depth, md)
@@ -354,9 +324,9 @@ def test_forward_class_maps_and_best_class_map_action(gpu):
 def test_loss_map_ce_refuses_a_one_channel_head(gpu):
     """smg_loss_map_ce on an engine with head_out == 1: -22, nothing launched (the outputs keep their fill)."""
     import smg_hip
-    eng = engine(640, out_ch=1)
+    eng = cached_engine(640, 1)
     q = torch.zeros((1, 1, 1, 1), device="cuda")
-    lab, loss, dq = torch.zeros((1, 1, 1, 1), device="cuda"), torch.full((1,), -7.0, device="cuda"), torch.full((1, 3, 1, 1), -7.0, device="cuda")
+    lab, loss, dq = torch.zeros((1, 1, 1, 1), device="cuda"), filled((1,)), filled((1, 3, 1, 1))
     rc = smg_hip.lib().smg_loss_map_ce(eng.h, q.data_ptr(), lab.data_ptr(), 1, loss.data_ptr(), dq.data_ptr(), C.c_void_p(0))
     assert rc == -22
     assert b"head_out" in smg_hip.lib().smg_last_error()

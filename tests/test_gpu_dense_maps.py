@@ -13,40 +13,10 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import grads_within_fp32_class, MEAN, STD, oracle_net, orc, product_net, q_close
+from helpers import grads_within_fp32_class, MEAN, STD, oracle_net, orc, q_close
+from map_harness import assert_bit_identical, cached_engine, filled, gpu, HEAD, make_trainer, stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-HEAD = "graspnet_val.grasp-val-"        # style 0's head (oracle.affordance.STYLE_HEAD)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()
-    return torch.device("cuda:0")
-
-
-def make_trainer(seed, R=16, out_ch=1):
-    import synthetic
-    from trainer import Trainer
-    tr = Trainer('reinforcement' if out_ch == 1 else 'reactive', 0.5, False, None, False)
-    sd = synthetic.make_state_dict(orc.state_layout(out_ch), seed)
-    tr.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-    tr.model.gnum_rotations = tr.model.snum_rotations = R
-    if out_ch == 1:
-        tr.model_target.load_state_dict(tr.model.state_dict())
-        tr.model_target.gnum_rotations = tr.model_target.snum_rotations = R
-    tr.optimizer.lr = 0.0
-    return tr
-
-
-def engine(S, out_ch=1):
-    import models
-    return models.get_engine(0, S, out_ch, 2, 1)
-
 
 def huber_map(q, lab, w):
     """sum over the map of w * Huber(q - label), code/trainer.py:345-348 per element (torch, any dtype)."""
@@ -94,8 +64,8 @@ def test_whole_map_training_vs_fp64_oracle_s928(gpu):
           % (float(qo.detach().min()), float(qo.detach().max()), 100.0 * (d >= 1).mean(), int((wgt == 0).sum())))
     huber_map(qo, lab_t, wgt_t).backward()
 
-    tr = make_trainer(1)
-    eng = engine(928)
+    tr = make_trainer('reinforcement', 1)
+    eng = cached_engine(928, 1)
     head_names = [HEAD + "conv1.weight", HEAD + "norm1.weight", HEAD + "norm1.bias"]
     got = {}
     try:
@@ -130,17 +100,16 @@ def test_train_batch_pixels_at_origin_equals_train_batch(gpu):
     """One trained pixel per sample at (0, 0) is what train_batch trains (the Huber on element [0,0,0,0], code/trainer.py:345):
     loss and q bit-identical, and smg_loss_map's dq on the one-hot maps bit-identical to smg_loss's."""
     import synthetic
-    tr = make_trainer(2)
+    tr = make_trainer('reinforcement', 2)
     depth, masks = synthetic.heightmap_scene(8, size=240, n_boxes=8)
     md = depth * masks[0]
     rots, labels = [5, 9], [0.4, 7.5]                 # one sample per Huber branch
     loss_a, q_a = tr.train_batch(depth, md, 0, rots, labels, return_q=True)
     loss_b, q_b = tr.train_batch_pixels(depth, md, 0, rots, [(0, 0), (0, 0)], labels, return_q=True)
     assert tuple(q_a.shape) == (2, 1, 3, 3)
-    assert torch.equal(q_a.view(torch.int32), q_b.view(torch.int32))
-    assert torch.equal(loss_a.view(torch.int32), loss_b.view(torch.int32))
-    eng = engine(704)
-    stream = torch.cuda.current_stream().cuda_stream
+    assert_bit_identical(q_a, q_b)
+    assert_bit_identical(loss_a, loss_b)
+    eng = cached_engine(704, 1)
     lab = torch.tensor(labels, dtype=torch.float32, device="cuda")
     lab_maps = torch.zeros_like(q_a)
     lab_maps[:, 0, 0, 0] = lab
@@ -148,18 +117,18 @@ def test_train_batch_pixels_at_origin_equals_train_batch(gpu):
     w_maps[:, 0, 0, 0] = 1.0
     out = []
     for use_map in (False, True):
-        loss, dq = torch.full((2,), -1.0, device="cuda"), torch.full_like(q_a, -1.0)
+        loss, dq = filled((2,), -1.0), filled(q_a.shape, -1.0)
         if use_map:
-            eng.loss_map(q_a.data_ptr(), lab_maps.data_ptr(), w_maps.data_ptr(), 2, loss.data_ptr(), dq.data_ptr(), stream)
+            eng.loss_map(q_a.data_ptr(), lab_maps.data_ptr(), w_maps.data_ptr(), 2, loss.data_ptr(), dq.data_ptr(), stream())
         else:
-            eng.loss(0, q_a.data_ptr(), lab.data_ptr(), 2, loss.data_ptr(), dq.data_ptr(), stream)
+            eng.loss(0, q_a.data_ptr(), lab.data_ptr(), 2, loss.data_ptr(), dq.data_ptr(), stream())
         out.append((loss, dq))
-    assert torch.equal(out[0][1].view(torch.int32), out[1][1].view(torch.int32))
-    assert torch.equal(out[0][0].view(torch.int32), out[1][0].view(torch.int32))
+    assert_bit_identical(out[0][1], out[1][1])
+    assert_bit_identical(out[0][0], out[1][0])
     assert int((out[1][1] != 0).sum()) == 2
     # NULL weights: every element counts
     loss, dq = torch.empty(2, device="cuda"), torch.empty_like(q_a)
-    eng.loss_map(q_a.data_ptr(), lab_maps.data_ptr(), None, 2, loss.data_ptr(), dq.data_ptr(), stream)
+    eng.loss_map(q_a.data_ptr(), lab_maps.data_ptr(), None, 2, loss.data_ptr(), dq.data_ptr(), stream())
     ref = torch.stack([huber_map(q_a[k].double(), lab_maps[k].double(), 1.0) for k in range(2)])
     assert torch.allclose(loss.double(), ref, rtol=1e-6, atol=0)      # (nine positive terms: 3 roundings each + 4 tree levels = 7 x 2^-24)
 
@@ -171,14 +140,14 @@ def test_config5_geometry_head_alone_vs_fp64(gpu):
     of conv1.weight, norm1.weight and norm1.bias must lie within 3x the fp32 evaluation's own error.  (The whole network at this
     size against the oracle is test_large_input_backward_config5_share's.)"""
     import synthetic
-    tr = make_trainer(0, R=32)
+    tr = make_trainer('reinforcement', 0, R=32)
     depth, masks = synthetic.heightmap_scene(4, size=640, n_boxes=8)
     md = depth * masks[0]
     rots = [5, 6]
     n, side, HW, HWp = len(rots), 38, 57 * 57, 3264
     lab = synthetic.uniform(5, "dense5/lab", n * side * side, -1.5, 2.5).astype(np.float32).reshape(n, side, side)
     wgt = synthetic.uniform(5, "dense5/w", n * side * side, 0.05, 1.0).astype(np.float32).reshape(n, side, side)
-    eng = engine(1824)
+    eng = cached_engine(1824, 1)
     eng.set_option("head_bwd", 2)
     try:
         loss, q = tr.train_batch_maps(depth, md, 0, rots, lab, wgt, return_q=True)
@@ -230,12 +199,12 @@ def test_dense_head_backward_is_bit_reproducible(gpu):
     """Two identical train_batch_maps calls (zero learning rate, dense form): the value-convolution weight gradient - every element
     written by one thread, pairs in index order - bit for bit equal, dh1 too."""
     import synthetic
-    tr = make_trainer(3)
+    tr = make_trainer('reinforcement', 3)
     depth, masks = synthetic.heightmap_scene(6, size=320)
     md = depth * masks[1]
     rots = [1, 6, 11]
     lab = synthetic.uniform(7, "det/lab", 300, -1.5, 2.5).reshape(3, 10, 10)
-    eng = engine(928)
+    eng = cached_engine(928, 1)
     HWp = eng.HWp[5]
     runs = []
     for it in range(2):
@@ -243,13 +212,13 @@ def test_dense_head_backward_is_bit_reproducible(gpu):
         g = dict(tr.model.named_parameters())[HEAD + "conv1.weight"].grad
         runs.append((g.clone(), eng.debug_read("dh1", count=3 * HWp * 64).copy()))
     assert float(runs[0][0].abs().max()) > 0
-    assert torch.equal(runs[0][0].view(torch.int32), runs[1][0].view(torch.int32)), int((runs[0][0] != runs[1][0]).sum())
-    assert np.array_equal(runs[0][1].view(np.uint32), runs[1][1].view(np.uint32))
+    assert_bit_identical(runs[0][0], runs[1][0])
+    assert_bit_identical(runs[0][1], runs[1][1])
 
 
 def test_forward_dense_and_best_dense_action(gpu):
     import synthetic
-    tr = make_trainer(4)
+    tr = make_trainer('reinforcement', 4)
     depth, masks = synthetic.heightmap_scene(0)
     md = depth * masks[0]
     for kw in (dict(), dict(specific_rotation=7), dict(style=2), dict(style=1, is_target=True)):
@@ -278,9 +247,9 @@ def test_forward_dense_and_best_dense_action(gpu):
 def test_loss_map_refuses_a_three_class_head(gpu):
     """smg_loss_map on an engine with head_out == 3: -22, nothing launched (the outputs keep their fill)."""
     import smg_hip
-    eng = engine(640, out_ch=3)
+    eng = cached_engine(640, 3)
     q = torch.zeros((1, 3, 1, 1), device="cuda")
-    lab, loss, dq = torch.zeros((1, 1, 1, 1), device="cuda"), torch.full((1,), -7.0, device="cuda"), torch.full((1, 3, 1, 1), -7.0, device="cuda")
+    lab, loss, dq = torch.zeros((1, 1, 1, 1), device="cuda"), filled((1,)), filled((1, 3, 1, 1))
     rc = smg_hip.lib().smg_loss_map(eng.h, q.data_ptr(), lab.data_ptr(), None, 1, loss.data_ptr(), dq.data_ptr(), C.c_void_p(0))
     assert rc == -22
     assert b"head_out" in smg_hip.lib().smg_last_error()

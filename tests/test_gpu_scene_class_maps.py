@@ -3,52 +3,22 @@ smg_loss_scene_ce on an engine alone with synthetic logits N(0, std 2) against t
 (probabilities to one fp32 rounding, the validity mask, np.argmax over the kernel's own maps, torch fp64 autograd for the loss),
 their refusals, then train_batch_scene_class_pixels against the fp64 PyTorch-CPU oracle and forward_scene_class_maps /
 best_scene_class_action against the trainer's own logits pushed through scene_class_ref."""
-import copy
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import grads_within_fp32_class, MEAN, STD, oracle_net, orc
+from helpers import orc
+from map_harness import assert_bit_identical, assert_train_batch_runs, cached_engine, filled, gpu, HEAD, make_trainer, s704_scene, stream  # noqa: F401
 
 import scene_class_ref
 import scene_ref
 
 pytestmark = pytest.mark.gpu
 
-HEAD = "graspnet_val.grasp-val-"        # style 0's head (oracle.affordance.STYLE_HEAD)
 SHAPES = ((240, 704, 3), (320, 928, 10))
 FILL = 7.0
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()
-    return torch.device("cuda:0")
-
-
-def make_trainer(seed, R=16):
-    import synthetic
-    from trainer import Trainer
-    tr = Trainer('reactive', 0.5, False, None, False)
-    sd = synthetic.make_state_dict(orc.state_layout(3), seed)
-    tr.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-    tr.model.gnum_rotations = tr.model.snum_rotations = R
-    tr.optimizer.lr = 0.0
-    return tr
-
-
-def engine(S, out_ch=3):
-    import models
-    return models.get_engine(0, S, out_ch, 2, 1)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def affines(R=16, rots=None):
@@ -61,14 +31,14 @@ def logits(seed, n, side):
 
 def gpu_class_maps(eng, q, aff, hm, cls):
     n = len(aff)
-    out = torch.full((n, 3, hm, hm) if cls < 0 else (n, hm, hm), FILL, dtype=torch.float32, device="cuda")
+    out = filled((n, 3, hm, hm) if cls < 0 else (n, hm, hm), FILL)
     eng.scene_class_maps(q.data_ptr(), n, aff, hm, cls, out.data_ptr(), stream())
     return out.cpu().numpy()
 
 
 def gpu_class_argmax(eng, q, aff, hm, cls):
     idx = torch.full((1,), -5, dtype=torch.int32, device="cuda")
-    val = torch.full((1,), -5.0, dtype=torch.float32, device="cuda")
+    val = filled((1,), -5.0)
     eng.scene_class_argmax(q.data_ptr(), len(aff), aff, hm, cls, idx.data_ptr(), val.data_ptr(), stream())
     return int(idx.cpu().numpy()[0]), val.cpu().numpy()[0]
 
@@ -98,7 +68,7 @@ def check_class_maps(got, q_host, aff, hm, what):
 @pytest.mark.parametrize("hm,S,side", SHAPES)
 def test_scene_class_maps_against_fp64(gpu, hm, S, side):
     assert scene_ref.geometry(hm)[1:] == (S, side)
-    eng = engine(S)
+    eng = cached_engine(S, 3)
     aff = affines()
     qh = logits(S, 16, side)
     q = torch.from_numpy(qh).cuda()
@@ -113,19 +83,19 @@ def test_scene_class_maps_with_an_odd_group_of_maps_and_an_unaligned_output(gpu)
     """More maps than one launch carries (33 > 32, the second launch starts at map 32) written to outputs that are 4 bytes off
     16-byte alignment: the guarded 4-byte stores instead of the 16-byte ones, the same values; the floats before and after stay."""
     hm, S, side = 240, 704, 3
-    eng = engine(S)
+    eng = cached_engine(S, 3)
     aff = affines(33)
     qh = logits(5, 33, side)
     q = torch.from_numpy(qh).cuda()
     n = 33 * 3 * hm * hm
-    buf = torch.full((n + 2,), FILL, dtype=torch.float32, device="cuda")
+    buf = filled((n + 2,), FILL)
     out = buf[1:1 + n]
     assert out.data_ptr() % 16 == 4
     eng.scene_class_maps(q.data_ptr(), 33, aff, hm, -1, out.data_ptr(), stream())
     got = out.cpu().numpy().reshape(33, 3, hm, hm)
     check_class_maps(got, qh, aff, hm, "33 maps, unaligned")
     assert float(buf[0]) == FILL and float(buf[-1]) == FILL
-    buf1 = torch.full((n // 3 + 2,), FILL, dtype=torch.float32, device="cuda")
+    buf1 = filled((n // 3 + 2,), FILL)
     out1 = buf1[1:1 + n // 3]
     assert out1.data_ptr() % 16 == 4
     eng.scene_class_maps(q.data_ptr(), 33, aff, hm, 1, out1.data_ptr(), stream())
@@ -148,7 +118,7 @@ def gpu_loss(eng, qh, aff, hm, pix, lab):
     n, K = lab.shape
     q = torch.from_numpy(qh).cuda()
     pix_d, lab_d = torch.from_numpy(pix.astype(np.int32)).cuda(), torch.from_numpy(lab.astype(np.float32)).cuda()
-    loss, dq = torch.full((n,), -FILL, device="cuda"), torch.full_like(q, -FILL)
+    loss, dq = filled((n,), -FILL), filled(q.shape, -FILL)
     eng.loss_scene_ce(q.data_ptr(), aff, hm, n, K, pix_d.data_ptr(), lab_d.data_ptr(), loss.data_ptr(), dq.data_ptr(), stream())
     return loss.cpu().numpy(), dq.cpu().numpy()
 
@@ -188,7 +158,7 @@ def test_config5_geometry_maps_and_loss(gpu):
     double accumulators press on the LDS) - classes 0 / 1 / 2 mixed, duplicates, some points without a window."""
     hm, S, side = 640, 1824, 38
     assert scene_ref.geometry(hm)[1:] == (S, side)
-    eng = engine(S)
+    eng = cached_engine(S, 3)
     aff = affines(32, (3, 20))
     qh = logits(S, 2, side)
     got = gpu_class_maps(eng, torch.from_numpy(qh).cuda(), aff, hm, -1)
@@ -206,13 +176,14 @@ def test_config5_geometry_maps_and_loss(gpu):
     assert int((ref[1] != 0).sum()) > 3 * 300
     runs = [gpu_loss(eng, qh, aff, hm, pix, lab) for _ in range(2)]
     check_loss(runs[0], ref, "S=1824 K=300")
-    assert np.array_equal(runs[0][0].view(np.uint32), runs[1][0].view(np.uint32)) and np.array_equal(runs[0][1].view(np.uint32), runs[1][1].view(np.uint32))
+    assert_bit_identical(runs[0][0], runs[1][0])
+    assert_bit_identical(runs[0][1], runs[1][1])
 
 
 def test_scene_class_argmax(gpu):
     """33 maps (the second launch group carries the first's result) at hm 240."""
     hm, S, side = 240, 704, 3
-    eng = engine(S)
+    eng = cached_engine(S, 3)
     aff = affines(33)
     qh = logits(S + 7, 33, side)
     q = torch.from_numpy(qh).cuda()
@@ -245,7 +216,7 @@ def test_loss_scene_ce_against_torch_fp64_autograd(gpu):
     neither contribute nor count (W = 4).  Then: a pair whose points are all class 2 gives loss 0 and dq 0; inf / NaN in the
     corner logits under a class-2 point change nothing, bit for bit."""
     hm, S, side = 320, 928, 10
-    eng = engine(S)
+    eng = cached_engine(S, 3)
     rots = [0, 3, 8, 13]
     aff = affines(16, rots)
     rng = np.random.default_rng(11)
@@ -266,7 +237,8 @@ def test_loss_scene_ce_against_torch_fp64_autograd(gpu):
     # (W = 4, not 5: the corner point does not count.  With it counted the loss would be 4/5 of the reference.)
     runs = [gpu_loss(eng, qh, aff, hm, pix, lab) for _ in range(2)]
     check_loss(runs[0], ref, "S=928 K=6")
-    assert np.array_equal(runs[0][0].view(np.uint32), runs[1][0].view(np.uint32)) and np.array_equal(runs[0][1].view(np.uint32), runs[1][1].view(np.uint32))
+    assert_bit_identical(runs[0][0], runs[1][0])
+    assert_bit_identical(runs[0][1], runs[1][1])
     # pair 2 all class 2: loss 0, dq 0; the other pairs as before
     lab2 = lab.copy()
     lab2[2] = 2
@@ -292,10 +264,10 @@ def test_scene_class_entry_points_refuse(gpu):
     aff = affines()
     ap = aff.ctypes.data_as(C.POINTER(C.c_float))
     q = torch.zeros((16, 3, 3, 3), device="cuda")
-    out = torch.full((16, 3, 240, 240), FILL, device="cuda")
-    idx, val = torch.full((1,), -5, dtype=torch.int32, device="cuda"), torch.full((1,), -5.0, device="cuda")
+    out = filled((16, 3, 240, 240), FILL)
+    idx, val = torch.full((1,), -5, dtype=torch.int32, device="cuda"), filled((1,), -5.0)
     pix = torch.full((1, 1, 2), 120, dtype=torch.int32, device="cuda")
-    lab, loss, dq = torch.zeros((1, 1), device="cuda"), torch.full((1,), -FILL, device="cuda"), torch.full((1, 3, 3, 3), -FILL, device="cuda")
+    lab, loss, dq = torch.zeros((1, 1), device="cuda"), filled((1,), -FILL), filled((1, 3, 3, 3), -FILL)
 
     def maps(e, n, a, hm, cls):
         return L.smg_scene_class_maps(e.h, q.data_ptr(), n, a, hm, cls, out.data_ptr(), None)
@@ -306,10 +278,10 @@ def test_scene_class_entry_points_refuse(gpu):
     def ce(e, a, hm, n, K):
         return L.smg_loss_scene_ce(e.h, q.data_ptr(), a, hm, n, K, pix.data_ptr(), lab.data_ptr(), loss.data_ptr(), dq.data_ptr(), None)
 
-    eng1 = engine(704, out_ch=1)
+    eng1 = cached_engine(704, 1)
     for rc in (maps(eng1, 16, ap, 240, 0), argmax(eng1, 16, ap, 240, 0), ce(eng1, ap, 240, 1, 1)):
         assert rc == -22 and b"head_out" in L.smg_last_error()
-    eng = engine(704)
+    eng = cached_engine(704, 3)
     assert maps(eng, 16, ap, 240, 0) == 0 and argmax(eng, 16, ap, 240, 0) == 0 and ce(eng, ap, 240, 1, 1) == 0      # (the calls are well-formed)
     torch.cuda.synchronize()
     out.fill_(FILL); idx.fill_(-5); val.fill_(-5.0); loss.fill_(-FILL); dq.fill_(-FILL)
@@ -324,7 +296,7 @@ def test_scene_class_entry_points_refuse(gpu):
     shifted0 = aff.copy()
     shifted0[0, 5] = -0.5
     assert ce(eng, shifted0.ctypes.data_as(C.POINTER(C.c_float)), 240, 1, 1) == -22
-    eng640 = engine(640)
+    eng640 = cached_engine(640, 3)
     for rc in (maps(eng640, 16, ap, 224, 0), argmax(eng640, 16, ap, 224, 0), ce(eng640, ap, 224, 1, 1)):
         assert rc == -22
     with pytest.raises(smg_hip.SmgError):
@@ -342,35 +314,22 @@ def test_train_batch_scene_class_pixels_vs_fp64_oracle_s704(gpu):
     mean over its points: 2 x 1e-3 x scale per sample.  All 368 gradient tensors within 3x the fp32 oracle's own error against
     fp64 (test_train_batch_scene_pixels_vs_fp64_oracle_s704's yardstick), and - the head backward took its dense form - the value
     convolution's weight gradient identical between two runs."""
-    import synthetic
-    hm, style, rots = 240, 0, [1, 6]
+    sc = s704_scene(3)
+    hm, style, rots, aff, depth, md, x, mx, on, q64 = (sc[k] for k in ("hm", "style", "rots", "aff", "depth", "md", "x", "mx", "on", "q64"))
     pix = np.asarray([[(118, 123), (124, 116), (0, 0)], [(121, 119), (115, 126), (0, 0)]])
     lab = np.asarray([[0, 1, 2], [1, 0, 2]])
-    aff = [scene_ref.theta(r, 16) for r in rots]
     for j in range(2):
         assert scene_ref.map_coords(hm, aff[j], pix[j, :, 0], pix[j, :, 1])[2].tolist() == [True, True, False]
-    depth, masks = synthetic.heightmap_scene(8, size=hm, n_boxes=8)
-    md = depth * masks[0]
-    x = orc.preprocess(depth, [MEAN] * 3, [STD] * 3)
-    mx = orc.preprocess(md, [MEAN] * 3, [STD] * 3)
-    assert x.shape[-1] == 704
-
-    on = oracle_net(1, out_ch=3)
-    o64 = copy.deepcopy(on).double()
-    trunk, head = getattr(o64, orc.STYLE_TRUNK[style]).features, getattr(o64, orc.STYLE_HEAD[style])
-    fm = trunk(mx.double())
-    q64 = [head(torch.cat((trunk(orc.rotate(x, r, 16).double()), fm), 1)) for r in rots]
-    assert tuple(q64[0].shape) == (1, 3, 3, 3)
 
     def total(qs):
         return sum(scene_class_ref.scene_class_loss(qs[j][0], aff[j], hm, pix[j], lab[j]) for j in range(2))
     loss64 = total(q64)
     loss64.backward()
-    g64 = {n: p.grad for n, p in o64.named_parameters() if p.grad is not None}
+    g64 = {n: p.grad for n, p in sc["o64"].named_parameters() if p.grad is not None}
     on.zero_grad()
     total([orc.forward(on, x, mx, style, False, r) for r in rots]).backward()
 
-    tr = make_trainer(1)
+    tr = make_trainer('reactive', 1)
     runs = []
     for it in range(2):
         loss, q = tr.train_batch_scene_class_pixels(depth, md, style, rots, pix, lab, return_q=True)
@@ -390,23 +349,19 @@ def test_train_batch_scene_class_pixels_vs_fp64_oracle_s704(gpu):
     gate = 2 * 1e-3 * scale * 2
     print("loss sum %.7f, fp64 oracle %.7f, |d| %.2e (gate %.2e)" % (float(loss.double().sum()), float(loss64.detach()), abs(float(loss.double().sum()) - float(loss64.detach())), gate))
     assert abs(float(loss.double().sum()) - float(loss64.detach())) <= gate
-    rel_p, _, _ = grads_within_fp32_class(tr.model.named_parameters(), on.named_parameters(), g64, 3.0, "S=704 scene class pixels",
-                                          max_outliers=3, outlier_cap=0.05)
-    print("%d gradient tensors compared, %d in the fp64 oracle" % (len(rel_p), len(g64)))
-    assert len(rel_p) == len(g64) == 368
-    assert float(runs[0].abs().max()) > 0
-    assert torch.equal(runs[0].view(torch.int32), runs[1].view(torch.int32)), int((runs[0] != runs[1]).sum())
+    n_compared = assert_train_batch_runs(tr, runs, on, g64, "S=704 scene class pixels")
+    print("%d gradient tensors compared, %d in the fp64 oracle" % (n_compared, len(g64)))
 
 
 def test_forward_scene_class_maps_and_best_scene_class_action(gpu):
     import synthetic
     from trainer import Trainer
     hm, side = 240, 3
-    tr = make_trainer(4)
+    tr = make_trainer('reactive', 4)
     depth, masks = synthetic.heightmap_scene(8, size=hm, n_boxes=8)
     md = depth * masks[0]
     aff = affines()
-    eng = engine(704)
+    eng = cached_engine(704, 3)
     for style in (0, 1):
         ps = tr.forward_scene_class_maps(depth, md, style)
         qd = tr._last_q.cpu().numpy()                        # the logits of that very call
@@ -435,7 +390,7 @@ def test_forward_scene_class_maps_and_best_scene_class_action(gpu):
     assert tuple(z.shape) == (16, 3, hm, hm)
     q = tr._last_q
     for c in range(3):
-        out = torch.full((16, hm, hm), FILL, dtype=torch.float32, device="cuda")
+        out = filled((16, hm, hm), FILL)
         eng.scene_maps(q[:, c].data_ptr(), 3 * side * side, 16, aff, hm, out.data_ptr(), stream())
         assert torch.equal(out.view(torch.int32), z[:, c].contiguous().view(torch.int32)), c
     z1 = tr.forward_scene_class_maps(depth, md, 0, cls=1, logits=True)

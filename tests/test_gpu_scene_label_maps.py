@@ -2,32 +2,23 @@
 fp64 autograd through tests/scene_ref.py (tests/scene_label_ref.py builds the cases), against smg_loss_scene fed the same pixels
 as a list, its masks, groups of more than 32 pairs and refusals, then train_batch_scene_maps against the fp64 PyTorch-CPU oracle
 and against train_batch_scene_pixels."""
-import copy
-import ctypes as C
+import contextlib
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import grads_within_fp32_class, MEAN, STD, oracle_net, orc
+from helpers import orc
+from map_harness import (assert_bit_identical, assert_scene_loss_refusals, assert_train_batch_runs, assert_written_and_finite, bits,  # noqa: F401
+                         border_pixels, cached_engine, filled, gpu, HEAD, make_trainer, s704_scene, stream)
 
 import scene_label_ref
 import scene_ref
 
 pytestmark = pytest.mark.gpu
 
-HEAD = "graspnet_val.grasp-val-"        # style 0's head (oracle.affordance.STYLE_HEAD)
 ROTS = (0, 3, 8, 13)
 _CASES = {}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()
-    return torch.device("cuda:0")
 
 
 def case(hm, rots=ROTS):
@@ -38,56 +29,30 @@ def case(hm, rots=ROTS):
     return _CASES[key]
 
 
-def make_trainer(seed, R=16):
-    import synthetic
-    from trainer import Trainer
-    tr = Trainer('reinforcement', 0.5, False, None, False)
-    sd = synthetic.make_state_dict(orc.state_layout(1), seed)
-    tr.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-    tr.model.gnum_rotations = tr.model.snum_rotations = R
-    tr.model_target.load_state_dict(tr.model.state_dict())
-    tr.model_target.gnum_rotations = tr.model_target.snum_rotations = R
-    tr.optimizer.lr = 0.0
-    return tr
-
-
-def engine(S, out_ch=1, pairs=1):
-    import models
-    return models.get_engine(0, S, out_ch, 2, pairs)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def run(eng, q, aff, hm, label, weight):
     """One smg_loss_scene_map call on device tensors, outputs pre-filled with -7 -> (loss [n], dq [n, side, side]) on the host."""
     n = q.shape[0]
-    loss, dq = torch.full((n,), -7.0, device="cuda"), torch.full_like(q, -7.0)
+    loss, dq = filled((n,)), filled(q.shape)
     eng.loss_scene_map(q.data_ptr(), aff, hm, n, label.data_ptr(), None if weight is None else weight.data_ptr(), loss.data_ptr(),
                        dq.data_ptr(), stream())
     return loss.cpu().numpy(), dq.cpu().numpy()[:, 0]
 
 
 def check_against_fp64(c, what):
-    eng = engine(c["S"])
+    eng = cached_engine(c["S"], 1)
     q, lab, wgt = (torch.from_numpy(c[k]).cuda() for k in ("q", "label", "weight"))
     loss, dq = run(eng, q, c["aff"], c["hm"], lab, wgt)
     for j in range(len(loss)):
         print("%s pair %d: loss %.7f ref %.7f |d| %.2e (gate %.2e); max |ddq| %.2e (gate %.2e); quadratic share %.2f" % (
             what, j, loss[j], c["loss"][j], abs(loss[j] - c["loss"][j]), 2.0 ** -23 * c["abs_terms"][j],
             np.abs(dq[j] - c["dq"][j]).max(), 2.0 ** -23 * np.abs(c["dq"][j]).max(), c["quad"]))
-    assert np.isfinite(loss).all() and np.isfinite(dq).all()
-    assert not (loss == -7.0).any() and not (dq == -7.0).any()
+    assert_written_and_finite(-7.0, loss, dq)
     assert (np.abs(loss - c["loss"]) <= 2.0 ** -23 * c["abs_terms"]).all()
     for j in range(len(loss)):
         assert np.abs(dq[j] - c["dq"][j]).max() <= 2.0 ** -23 * np.abs(c["dq"][j]).max()
     loss2, dq2 = run(eng, q, c["aff"], c["hm"], lab, wgt)            # a second call: bit-identical
-    assert np.array_equal(bits(loss), bits(loss2)) and np.array_equal(bits(dq), bits(dq2))
+    assert_bit_identical(loss, loss2)
+    assert_bit_identical(dq, dq2)
     return loss, dq
 
 
@@ -108,8 +73,7 @@ def test_loss_scene_map_where_the_heightmap_border_clips_the_boxes(gpu):
     by the heightmap edge (at 240 and 320 the valid area stays inside).  Same gates."""
     c = case(448, (2, 5))
     assert (c["S"], c["side"]) == (1280, 21)
-    v = c["valid"][0]
-    border = int(v[0].sum() + v[-1].sum() + v[1:-1, 0].sum() + v[1:-1, -1].sum())
+    border = border_pixels(c["valid"][0])
     print("rotation 2: %d valid pixels on the image border" % border)
     assert border > 0
     check_against_fp64(c, "hm=448")
@@ -118,7 +82,7 @@ def test_loss_scene_map_where_the_heightmap_border_clips_the_boxes(gpu):
 def test_loss_scene_map_groups_of_pairs(gpu):
     """33 pairs at hm = 240 (the second launch carries pair 32 alone), pair 32 with pair 0's inputs: bit-equal results."""
     hm, S, side = 240, 704, 3
-    eng = engine(S, pairs=33)
+    eng = cached_engine(S, 1, pairs=33)
     rng = np.random.default_rng(33)
     rots = list(range(32)) + [0]
     aff = np.stack([scene_ref.theta(r, 32) for r in rots])
@@ -127,9 +91,10 @@ def test_loss_scene_map_groups_of_pairs(gpu):
     wgt = rng.uniform(0.2, 1.0, size=(33, hm, hm)).astype(np.float32)
     q[32], lab[32], wgt[32] = q[0], lab[0], wgt[0]
     loss, dq = run(eng, torch.from_numpy(q).cuda(), aff, hm, torch.from_numpy(lab).cuda(), torch.from_numpy(wgt).cuda())
-    assert not (loss == -7.0).any() and not (dq == -7.0).any() and np.isfinite(loss).all() and np.isfinite(dq).all()
+    assert_written_and_finite(-7.0, loss, dq)
     assert loss[0] > 0 and np.abs(dq[0]).max() > 0
-    assert bits(loss[32:33])[0] == bits(loss[0:1])[0] and np.array_equal(bits(dq[32]), bits(dq[0]))
+    assert_bit_identical(loss[32:33], loss[0:1])
+    assert_bit_identical(dq[32], dq[0])
     assert not np.array_equal(dq[31], dq[0])
     l0, g0, terms, _ = scene_label_ref.autograd(q[5, 0], aff[5], hm, lab[5], wgt[5])           # one pair of the first launch against fp64
     assert abs(loss[5] - l0) <= 2.0 ** -23 * np.abs(terms).sum() and np.abs(dq[5] - g0).max() <= 2.0 ** -23 * np.abs(g0).max()
@@ -140,7 +105,7 @@ def test_loss_scene_map_with_matrices_that_are_no_rotation(gpu):
     as wide) and the zero matrix (no inverse: every workgroup walks the whole heightmap, every pixel lands on the map's centre)
     against torch fp64 autograd with the gates above."""
     hm, S, side = 240, 704, 3
-    eng = engine(S)
+    eng = cached_engine(S, 1)
     aff = scene_label_ref.odd_affines()
     n = len(aff)
     rng = np.random.default_rng(77)
@@ -163,7 +128,7 @@ def test_loss_scene_map_against_loss_scene_on_the_same_pixels(gpu):
     round an fp64 sum of the same terms once, so loss and dq agree to 2^-22 of sum|terms| and max|dq|."""
     c = case(320)
     hm = c["hm"]
-    eng = engine(c["S"])
+    eng = cached_engine(c["S"], 1)
     q, lab, wgt = (torch.from_numpy(c[k]).cuda() for k in ("q", "label", "weight"))
     loss, dq = run(eng, q, c["aff"], hm, lab, wgt)
     for j in range(4):
@@ -172,7 +137,7 @@ def test_loss_scene_map_against_loss_scene_on_the_same_pixels(gpu):
         assert K > 10000
         pix_d = torch.from_numpy(np.ascontiguousarray(pix, dtype=np.int32)).cuda()
         lab_d, wgt_d = torch.from_numpy(c["label"][j][keep]).cuda(), torch.from_numpy(c["weight"][j][keep]).cuda()
-        lj, dj = torch.full((1,), -7.0, device="cuda"), torch.full((1, 1, c["side"], c["side"]), -7.0, device="cuda")
+        lj, dj = filled((1,)), filled((1, 1, c["side"], c["side"]))
         eng.loss_scene(q[j:j + 1].data_ptr(), c["aff"][j:j + 1], hm, 1, K, pix_d.data_ptr(), lab_d.data_ptr(), wgt_d.data_ptr(), lj.data_ptr(),
                        dj.data_ptr(), stream())
         lj, dj = float(lj.cpu()[0]), dj.cpu().numpy()[0, 0]
@@ -185,7 +150,7 @@ def test_loss_scene_map_masks(gpu):
     """All-zero weights: loss 0 and dq exactly 0 everywhere, whatever the labels hold.  NULL weights = explicit ones, bit for bit."""
     c = case(240)
     hm = c["hm"]
-    eng = engine(c["S"])
+    eng = cached_engine(c["S"], 1)
     q = torch.from_numpy(c["q"]).cuda()
     nan_lab = torch.full((4, hm, hm), float("nan"), device="cuda")
     loss, dq = run(eng, q, c["aff"], hm, nan_lab, torch.zeros((4, hm, hm), device="cuda"))
@@ -194,7 +159,8 @@ def test_loss_scene_map_masks(gpu):
     loss_null, dq_null = run(eng, q, c["aff"], hm, lab, None)
     loss_ones, dq_ones = run(eng, q, c["aff"], hm, lab, torch.ones((4, hm, hm), device="cuda"))
     assert (loss_null > 0).all() and np.abs(dq_null).max() > 0
-    assert np.array_equal(bits(loss_null), bits(loss_ones)) and np.array_equal(bits(dq_null), bits(dq_ones))
+    assert_bit_identical(loss_null, loss_ones)
+    assert_bit_identical(dq_null, dq_ones)
 
 
 def test_loss_scene_map_refusals(gpu):
@@ -202,30 +168,17 @@ def test_loss_scene_map_refusals(gpu):
     a 1 x 1 map, n_pairs < 1, an affine matrix with a translation."""
     import smg_hip
     L = smg_hip.lib()
-    hm = 240
-    aff = np.stack([scene_ref.theta(r, 16) for r in range(4)])
-    ap = aff.ctypes.data_as(C.POINTER(C.c_float))
     q = torch.zeros((4, 1, 3, 3), device="cuda")
     lab = torch.zeros((4, 320, 320), device="cuda")
-    loss, dq = torch.full((4,), -7.0, device="cuda"), torch.full((4, 3, 3, 3), -7.0, device="cuda")
+    loss, dq = filled((4,)), filled((4, 3, 3, 3))
 
-    def refused(eng, affine, size, n, word):
-        rc = L.smg_loss_scene_map(eng.h, q.data_ptr(), affine, size, n, lab.data_ptr(), None, loss.data_ptr(), dq.data_ptr(), None)
-        msg = L.smg_last_error()
-        assert rc == -22 and b"smg_loss_scene_map" in msg and word in msg, (rc, msg)
-    eng = engine(704)
-    refused(engine(704, out_ch=3), ap, hm, 4, b"head_out")
-    refused(eng, ap, 320, 4, b"does not pad")
-    refused(eng, ap, 224, 4, b"does not pad")
-    refused(engine(640), ap, 224, 4, b"1 x 1")
-    refused(eng, ap, hm, 0, b"n_pairs < 1")
-    shifted = aff.copy()
-    shifted[3, 5] = 0.25
-    refused(eng, shifted.ctypes.data_as(C.POINTER(C.c_float)), hm, 4, b"translation")
-    with pytest.raises(smg_hip.SmgError):
-        eng.loss_scene_map(q.data_ptr(), shifted, hm, 4, lab.data_ptr(), None, loss.data_ptr(), dq.data_ptr(), None)
-    torch.cuda.synchronize()
-    assert bool((loss == -7.0).all()) and bool((dq == -7.0).all())
+    def call(eng, affine, size, n):
+        return L.smg_loss_scene_map(eng.h, q.data_ptr(), affine, size, n, lab.data_ptr(), None, loss.data_ptr(), dq.data_ptr(), None)
+
+    def method(eng, affine, size, n):
+        eng.loss_scene_map(q.data_ptr(), affine, size, n, lab.data_ptr(), None, loss.data_ptr(), dq.data_ptr(), None)
+    assert_scene_loss_refusals(call, method, b"smg_loss_scene_map", 1, 3, lambda S, out_ch: contextlib.nullcontext(cached_engine(S, out_ch)),
+                               loss, dq, name_leads=False)
 
 
 def test_train_batch_scene_maps_vs_fp64_oracle_s704(gpu):
@@ -234,24 +187,8 @@ def test_train_batch_scene_maps_vs_fp64_oracle_s704(gpu):
     Huber branches.  The loss against fp64 over the product's own q (2^-23 of the terms) and against the fp64 oracle (that test's
     gate), all 368 gradient tensors within 3x the fp32 oracle's own error, the head's conv1 weight gradient identical between two
     runs, and train_batch_scene_pixels on the same 81 pixels gives the same losses to 2^-22."""
-    import synthetic
-    hm, style, rots = 240, 0, [1, 6]
-    by, bx = np.meshgrid(np.arange(116, 125), np.arange(116, 125), indexing="ij")
-    block = np.stack([by.ravel(), bx.ravel()], axis=-1)                        # 81 pixels, row-major
-    aff = [scene_ref.theta(r, 16) for r in rots]
-    for j in range(2):
-        assert scene_ref.map_coords(hm, aff[j], block[:, 0], block[:, 1])[2].all()
-    depth, masks = synthetic.heightmap_scene(8, size=hm, n_boxes=8)
-    md = depth * masks[0]
-    x = orc.preprocess(depth, [MEAN] * 3, [STD] * 3)
-    mx = orc.preprocess(md, [MEAN] * 3, [STD] * 3)
-    assert x.shape[-1] == 704
-
-    on = oracle_net(1)
-    o64 = copy.deepcopy(on).double()
-    trunk, head = getattr(o64, orc.STYLE_TRUNK[style]).features, getattr(o64, orc.STYLE_HEAD[style])
-    fm = trunk(mx.double())
-    q64 = [head(torch.cat((trunk(orc.rotate(x, r, 16).double()), fm), 1)) for r in rots]
+    sc = s704_scene(1)
+    hm, style, rots, block, aff, depth, md, x, mx, on, q64 = (sc[k] for k in ("hm", "style", "rots", "block", "aff", "depth", "md", "x", "mx", "on", "q64"))
     v64 = [scene_ref.scene_points(q64[j][0, 0], aff[j], hm, block) for j in range(2)]
     rng = np.random.default_rng(3)
     wk = rng.uniform(0.25, 1.0, size=(2, 81)).astype(np.float32)
@@ -268,12 +205,12 @@ def test_train_batch_scene_maps_vs_fp64_oracle_s704(gpu):
         return sum((torch.from_numpy(wk[j]).to(dtype) * scene_ref.huber(vs[j] - torch.from_numpy(lk[j]).to(dtype))).sum() for j in range(2))
     loss64 = total(v64, torch.float64)
     loss64.backward()
-    g64 = {n: p.grad for n, p in o64.named_parameters() if p.grad is not None}
+    g64 = {n: p.grad for n, p in sc["o64"].named_parameters() if p.grad is not None}
     on.zero_grad()
     qo = [orc.forward(on, x, mx, style, False, r) for r in rots]
     total([scene_ref.scene_points(qo[j][0, 0], aff[j], hm, block) for j in range(2)], torch.float32).backward()
 
-    tr = make_trainer(1)
+    tr = make_trainer('reinforcement', 1)
     runs = []
     for it in range(2):
         loss, q = tr.train_batch_scene_maps(depth, md, style, rots, lab, wgt, return_q=True)
@@ -294,11 +231,7 @@ def test_train_batch_scene_maps_vs_fp64_oracle_s704(gpu):
     gate = 1e-3 * scale * float(wk.sum())       # huber' <= 1, each v a convex combination of q: |d loss| <= sum_k w_k max|dq|
     print("loss sum %.7f, fp64 oracle %.7f, |d| %.2e (gate %.2e)" % (own, float(loss64), abs(own - float(loss64)), gate))
     assert abs(float(loss.double().sum()) - float(loss64)) <= gate
-    rel_p, _, _ = grads_within_fp32_class(tr.model.named_parameters(), on.named_parameters(), g64, 3.0, "S=704 scene label maps",
-                                          max_outliers=3, outlier_cap=0.05)
-    assert len(rel_p) == 368
-    assert float(runs[0].abs().max()) > 0
-    assert torch.equal(runs[0].view(torch.int32), runs[1].view(torch.int32)), int((runs[0] != runs[1]).sum())
+    assert_train_batch_runs(tr, runs, on, g64, "S=704 scene label maps")
     # the same 81 pixels as a list
     loss_p = tr.train_batch_scene_pixels(depth, md, style, rots, np.stack([block, block]), np.nan_to_num(lk), wk)
     a, b = loss.cpu().numpy().astype(np.float64), loss_p.cpu().numpy().astype(np.float64)

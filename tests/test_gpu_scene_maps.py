@@ -2,52 +2,20 @@
 synthetic maps against the fp64 restatement of tests/scene_ref.py (values to one fp32 rounding, the validity mask, the sense of
 the rotation, np.argmax over the kernel's own maps, torch fp64 autograd for the loss), then train_batch_scene_pixels against the
 fp64 PyTorch-CPU oracle and forward_scene / best_scene_action against forward_dense pushed through scene_ref."""
-import copy
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import grads_within_fp32_class, MEAN, STD, oracle_net, orc
+from helpers import orc
+from map_harness import assert_bit_identical, assert_train_batch_runs, cached_engine, filled, gpu, HEAD, make_trainer, s704_scene, stream  # noqa: F401
 
 import scene_ref
 
 pytestmark = pytest.mark.gpu
 
-HEAD = "graspnet_val.grasp-val-"        # style 0's head (oracle.affordance.STYLE_HEAD)
 SHAPES = ((240, 704, 3), (320, 928, 10))
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()
-    return torch.device("cuda:0")
-
-
-def make_trainer(seed, R=16):
-    import synthetic
-    from trainer import Trainer
-    tr = Trainer('reinforcement', 0.5, False, None, False)
-    sd = synthetic.make_state_dict(orc.state_layout(1), seed)
-    tr.model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-    tr.model.gnum_rotations = tr.model.snum_rotations = R
-    tr.model_target.load_state_dict(tr.model.state_dict())
-    tr.model_target.gnum_rotations = tr.model_target.snum_rotations = R
-    tr.optimizer.lr = 0.0
-    return tr
-
-
-def engine(S, out_ch=1):
-    import models
-    return models.get_engine(0, S, out_ch, 2, 1)
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def affines(R=16):
@@ -56,14 +24,14 @@ def affines(R=16):
 
 def gpu_scene_maps(eng, q, aff, hm, map_stride=None):
     n = len(aff)
-    out = torch.full((n, hm, hm), 7.0, dtype=torch.float32, device="cuda")
+    out = filled((n, hm, hm), 7.0)
     eng.scene_maps(q.data_ptr(), q[0].numel() if map_stride is None else map_stride, n, aff, hm, out.data_ptr(), stream())
     return out.cpu().numpy()
 
 
 def gpu_scene_argmax(eng, q, aff, hm):
     idx = torch.full((1,), -5, dtype=torch.int32, device="cuda")
-    val = torch.full((1,), -5.0, dtype=torch.float32, device="cuda")
+    val = filled((1,), -5.0)
     eng.scene_argmax(q.data_ptr(), q[0].numel(), len(aff), aff, hm, idx.data_ptr(), val.data_ptr(), stream())
     return int(idx.cpu().numpy()[0]), val.cpu().numpy()[0]
 
@@ -88,7 +56,7 @@ def check_maps(got, q_host, aff, hm, what):
 @pytest.mark.parametrize("hm,S,side", SHAPES)
 def test_scene_maps_against_fp64(gpu, hm, S, side):
     assert scene_ref.geometry(hm)[1:] == (S, side)
-    eng = engine(S)
+    eng = cached_engine(S, 1)
     aff = affines()
     q = torch.from_numpy(np.random.default_rng(S).standard_normal((16, side, side)).astype(np.float32)).cuda()
     got = gpu_scene_maps(eng, q, aff, hm)
@@ -103,10 +71,10 @@ def test_scene_maps_with_an_odd_group_of_maps_and_an_unaligned_output(gpu):
     """More maps than one launch carries (33 > 32, the second launch starts at map 32) written to an output that is 4 bytes off
     16-byte alignment: the guarded 4-byte stores instead of the 16-byte ones, the same values."""
     hm, S, side = 240, 704, 3
-    eng = engine(S)
+    eng = cached_engine(S, 1)
     aff = np.stack([scene_ref.theta(r, 33) for r in range(33)])
     q = torch.from_numpy(np.random.default_rng(5).standard_normal((33, side, side)).astype(np.float32)).cuda()
-    buf = torch.full((33 * hm * hm + 2,), 7.0, dtype=torch.float32, device="cuda")
+    buf = filled((33 * hm * hm + 2,), 7.0)
     out = buf[1:1 + 33 * hm * hm]
     assert out.data_ptr() % 16 == 4
     eng.scene_maps(q.data_ptr(), side * side, 33, aff, hm, out.data_ptr(), stream())
@@ -122,7 +90,7 @@ def test_rotation_sense_on_a_plane_of_scene_coordinates(gpu, hm, S, side):
     """Q_r = f(u) = 0.7 u_x - 1.3 u_y + 0.2 at the SCENE coordinates u = A p of each window centre p: bilinear interpolation
     reproduces a plane, so every rotation's scene-frame map must be f at the heightmap pixels, to 2^-23 max|f| (fp32 map elements
     and output) + 2^-22 (0.7 + 1.3) (A is fp32: A^T A != I)."""
-    eng = engine(S)
+    eng = cached_engine(S, 1)
     aff = affines()
     c = 2.0 * (32.0 * np.arange(side) + 319.5) / (S - 1) - 1.0         # window centres, normalised, rotated frame
     py, px = np.meshgrid(c, c, indexing="ij")
@@ -145,7 +113,7 @@ def test_rotation_sense_on_a_plane_of_scene_coordinates(gpu, hm, S, side):
 
 @pytest.mark.parametrize("hm,S,side", SHAPES)
 def test_scene_argmax(gpu, hm, S, side):
-    eng = engine(S)
+    eng = cached_engine(S, 1)
     aff = affines()
     qh = np.random.default_rng(S + 7).standard_normal((16, side, side)).astype(np.float32)
     q = torch.from_numpy(qh).cuda()
@@ -176,7 +144,7 @@ def test_loss_scene_against_torch_fp64_autograd(gpu):
     the touched corners, two calls bit-identical."""
     import smg_hip
     hm, S, side = 320, 928, 10
-    eng = engine(S)
+    eng = cached_engine(S, 1)
     rots = [0, 3, 8, 13]
     aff = np.stack([scene_ref.theta(r, 16) for r in rots])
     rng = np.random.default_rng(11)
@@ -209,7 +177,7 @@ def test_loss_scene_against_torch_fp64_autograd(gpu):
     pix_d, lab_d, wgt_d = torch.from_numpy(pix).cuda(), torch.from_numpy(lab).cuda(), torch.from_numpy(wgt).cuda()
     runs = []
     for _ in range(2):
-        loss, dq = torch.full((4,), -7.0, device="cuda"), torch.full_like(q, -7.0)
+        loss, dq = filled((4,)), filled(q.shape)
         eng.loss_scene(q.data_ptr(), aff, hm, 4, 5, pix_d.data_ptr(), lab_d.data_ptr(), wgt_d.data_ptr(), loss.data_ptr(), dq.data_ptr(), stream())
         runs.append((loss.cpu().numpy(), dq.cpu().numpy()[:, 0]))
     loss, dq = runs[0]
@@ -217,7 +185,8 @@ def test_loss_scene_against_torch_fp64_autograd(gpu):
     assert (np.abs(loss - ref_loss) <= 2.0 ** -23 * np.abs(ref_loss)).all()
     assert np.abs(dq - ref_dq).max() <= 2.0 ** -23 * np.abs(ref_dq).max()
     assert (dq[ref_dq == 0] == 0).all() and int((ref_dq != 0).sum()) <= 4 * 4 * 4
-    assert np.array_equal(runs[0][0].view(np.uint32), runs[1][0].view(np.uint32)) and np.array_equal(runs[0][1].view(np.uint32), runs[1][1].view(np.uint32))
+    assert_bit_identical(runs[0][0], runs[1][0])
+    assert_bit_identical(runs[0][1], runs[1][1])
     # NULL weights = all ones
     loss1, dq1 = torch.empty(4, device="cuda"), torch.empty_like(q)
     eng.loss_scene(q.data_ptr(), aff, hm, 4, 5, pix_d.data_ptr(), lab_d.data_ptr(), None, loss1.data_ptr(), dq1.data_ptr(), stream())
@@ -227,8 +196,8 @@ def test_loss_scene_against_torch_fp64_autograd(gpu):
         ones.append(float(scene_ref.huber(d).sum()))
     assert (np.abs(loss1.cpu().numpy() - np.asarray(ones)) <= 2.0 ** -23 * np.abs(ones)).all()
     # a 3-class engine refuses: -22, nothing launched
-    eng3 = engine(704, out_ch=3)
-    loss3, dq3 = torch.full((1,), -7.0, device="cuda"), torch.full((1, 3, 3, 3), -7.0, device="cuda")
+    eng3 = cached_engine(704, 3)
+    loss3, dq3 = filled((1,)), filled((1, 3, 3, 3))
     rc = smg_hip.lib().smg_loss_scene(eng3.h, dq3.data_ptr(), aff.ctypes.data_as(C.POINTER(C.c_float)), 240, 1, 5, pix_d.data_ptr(), lab_d.data_ptr(), None,
                                       loss3.data_ptr(), dq3.data_ptr(), C.c_void_p(0))
     assert rc == -22 and b"head_out" in smg_hip.lib().smg_last_error()
@@ -241,14 +210,14 @@ def test_scene_entry_points_refuse_bad_geometry(gpu):
     matrix with a translation (the chain is p = A^T u: rotations about the centre)."""
     import smg_hip
     L = smg_hip.lib()
-    eng = engine(704)
+    eng = cached_engine(704, 1)
     aff = affines()
     ap = aff.ctypes.data_as(C.POINTER(C.c_float))
     q = torch.zeros((16, 3, 3), device="cuda")
-    out = torch.full((16, 240, 240), 7.0, device="cuda")
-    idx, val = torch.full((1,), -5, dtype=torch.int32, device="cuda"), torch.full((1,), -5.0, device="cuda")
+    out = filled((16, 240, 240), 7.0)
+    idx, val = torch.full((1,), -5, dtype=torch.int32, device="cuda"), filled((1,), -5.0)
     pix = torch.full((1, 1, 2), 120, dtype=torch.int32, device="cuda")
-    lab, loss, dq = torch.zeros((1, 1), device="cuda"), torch.full((1,), -7.0, device="cuda"), torch.full((1, 1, 3, 3), -7.0, device="cuda")
+    lab, loss, dq = torch.zeros((1, 1), device="cuda"), filled((1,)), filled((1, 1, 3, 3))
     assert L.smg_scene_maps(eng.h, q.data_ptr(), 9, 16, ap, 320, out.data_ptr(), None) == -22
     assert L.smg_scene_maps(eng.h, q.data_ptr(), 9, 0, ap, 240, out.data_ptr(), None) == -22
     assert L.smg_scene_argmax(eng.h, q.data_ptr(), 9, 16, ap, 224, idx.data_ptr(), val.data_ptr(), None) == -22
@@ -258,7 +227,7 @@ def test_scene_entry_points_refuse_bad_geometry(gpu):
     shifted = aff.copy()
     shifted[15, 2] = 0.25
     assert L.smg_scene_maps(eng.h, q.data_ptr(), 9, 16, shifted.ctypes.data_as(C.POINTER(C.c_float)), 240, out.data_ptr(), None) == -22
-    eng640 = engine(640)
+    eng640 = cached_engine(640, 1)
     assert L.smg_scene_maps(eng640.h, q.data_ptr(), 1, 16, ap, 224, out.data_ptr(), None) == -22
     with pytest.raises(smg_hip.SmgError):
         eng640.scene_argmax(q.data_ptr(), 1, 16, aff, 224, idx.data_ptr(), val.data_ptr(), None)
@@ -272,23 +241,11 @@ def test_train_batch_scene_pixels_vs_fp64_oracle_s704(gpu):
     rounding: 2^-23 of the terms) and against the fp64 oracle's (|dv| <= max|dq|: q_close's 1e-3 of the map's scale per point),
     all 368 gradient tensors within 3x the fp32 oracle's own error against fp64 (test_whole_map_training_vs_fp64_oracle_s928's
     yardstick), and - the head backward took its dense form - the value convolution's weight gradient identical between two runs."""
-    import synthetic
-    hm, style, rots = 240, 0, [1, 6]
+    sc = s704_scene(1)
+    hm, style, rots, aff, depth, md, x, mx, on, q64 = (sc[k] for k in ("hm", "style", "rots", "aff", "depth", "md", "x", "mx", "on", "q64"))
     pix = np.asarray([[(118, 123), (124, 116)], [(121, 119), (115, 126)]])
-    aff = [scene_ref.theta(r, 16) for r in rots]
     for j in range(2):
         assert scene_ref.map_coords(hm, aff[j], pix[j, :, 0], pix[j, :, 1])[2].all()
-    depth, masks = synthetic.heightmap_scene(8, size=hm, n_boxes=8)
-    md = depth * masks[0]
-    x = orc.preprocess(depth, [MEAN] * 3, [STD] * 3)
-    mx = orc.preprocess(md, [MEAN] * 3, [STD] * 3)
-    assert x.shape[-1] == 704
-
-    on = oracle_net(1)
-    o64 = copy.deepcopy(on).double()
-    trunk, head = getattr(o64, orc.STYLE_TRUNK[style]).features, getattr(o64, orc.STYLE_HEAD[style])
-    fm = trunk(mx.double())
-    q64 = [head(torch.cat((trunk(orc.rotate(x, r, 16).double()), fm), 1)) for r in rots]
     v64 = [scene_ref.scene_points(q64[j][0, 0], aff[j], hm, pix[j]) for j in range(2)]
     lab = np.stack([v.detach().numpy() + np.asarray([0.4, -1.6]) for v in v64]).astype(np.float32)       # |d| = 0.4 and 1.6
     wgt = np.asarray([[1.0, 0.5], [0.75, 1.0]], dtype=np.float32)
@@ -297,12 +254,12 @@ def test_train_batch_scene_pixels_vs_fp64_oracle_s704(gpu):
         return sum((torch.from_numpy(wgt[j]).to(dtype) * scene_ref.huber(vs[j] - torch.from_numpy(lab[j]).to(dtype))).sum() for j in range(2))
     loss64 = total(v64, torch.float64)
     loss64.backward()
-    g64 = {n: p.grad for n, p in o64.named_parameters() if p.grad is not None}
+    g64 = {n: p.grad for n, p in sc["o64"].named_parameters() if p.grad is not None}
     on.zero_grad()
     qo = [orc.forward(on, x, mx, style, False, r) for r in rots]
     total([scene_ref.scene_points(qo[j][0, 0], aff[j], hm, pix[j]) for j in range(2)], torch.float32).backward()
 
-    tr = make_trainer(1)
+    tr = make_trainer('reinforcement', 1)
     runs = []
     for it in range(2):
         loss, q = tr.train_batch_scene_pixels(depth, md, style, rots, pix, lab, wgt, return_q=True)
@@ -321,18 +278,14 @@ def test_train_batch_scene_pixels_vs_fp64_oracle_s704(gpu):
     gate = 1e-3 * scale * float(wgt.sum())       # huber' <= 1, each v a convex combination of q: |d loss| <= sum_k w_k max|dq|
     print("loss sum %.7f, fp64 oracle %.7f, |d| %.2e (gate %.2e)" % (own, float(loss64), abs(own - float(loss64)), gate))
     assert abs(float(loss.double().sum()) - float(loss64)) <= gate
-    rel_p, _, _ = grads_within_fp32_class(tr.model.named_parameters(), on.named_parameters(), g64, 3.0, "S=704 scene pixels",
-                                          max_outliers=3, outlier_cap=0.05)
-    assert len(rel_p) == 368
-    assert float(runs[0].abs().max()) > 0
-    assert torch.equal(runs[0].view(torch.int32), runs[1].view(torch.int32)), int((runs[0] != runs[1]).sum())
+    assert_train_batch_runs(tr, runs, on, g64, "S=704 scene pixels")
 
 
 def test_forward_scene_and_best_scene_action(gpu):
     import synthetic
     from trainer import Trainer
     hm = 240
-    tr = make_trainer(4)
+    tr = make_trainer('reinforcement', 4)
     depth, masks = synthetic.heightmap_scene(8, size=hm, n_boxes=8)
     md = depth * masks[0]
     aff = affines()

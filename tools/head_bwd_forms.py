@@ -13,17 +13,16 @@ smg_loss_map_ce.
     python tools/head_bwd_forms.py --classes 3 > profiles/head_bwd_forms_3class.txt
 """
 import argparse
+import functools
 import json
-import os
 import sys
 
 import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (REPO, os.path.join(REPO, "smg-multimodal-grasping_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from bench_sides import add_repo_paths, run_sides, side_stats, window
+
+add_repo_paths()
 
 
 def main():
@@ -57,8 +56,10 @@ def main():
     loss = torch.empty(n, dtype=torch.float32, device=dev)
     head = "graspnet_val.grasp-val-conv1.weight"
 
+    grads = {}
+
     def one(form):
-        """forward + loss (untimed), then the timed backward; returns (ms, the value convolution's weight gradient)"""
+        """forward + loss (untimed), then the timed backward; returns its ms and keeps the value convolution's weight gradient"""
         q = model.run(0, rots, 32, heightmaps=hm, mean=tr.image_mean, std=tr.image_std, keep_for_backward=True, update_bn=False)
         eng = model._saved[0]
         eng.set_option("head_bwd", form)
@@ -69,37 +70,25 @@ def main():
             eng.loss_map_ce(q.data_ptr(), lab.data_ptr(), n, loss.data_ptr(), dq.data_ptr(), stream)
         model.flat_grads().zero_()
         net = model._net_struct(True)
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(dev)
-        t0.record()
-        eng.backward(net, dq.data_ptr(), stream)
-        t1.record()
-        t1.synchronize()
+        ms = window(lambda: eng.backward(net, dq.data_ptr(), stream), 1, dev)
         eng.set_option("head_bwd", 0)
         off, cnt = next((o, int(np.prod(s))) for nm, k, o, s in model._layout if nm == head and k == 0)
-        return t0.elapsed_time(t1), model.flat_grads()[off:off + cnt].clone()
+        grads[form] = model.flat_grads()[off:off + cnt].clone()
+        return ms
 
     print("# %d^2 heightmap, %d rotations (%d streams), %d x %d maps, %s; the backward call only, ms"
           % (args.size, n, n + 1, side, side, "full weight maps" if args.classes == 1 else "3 classes, every pixel labelled 0 / 1"))
-    times, grads = {1: [], 2: []}, {}
-    for _ in range(args.warmup):
-        for form in (1, 2):
-            one(form)
-    for rep in range(args.repeats):
-        for form in ((1, 2) if rep % 2 == 0 else (2, 1)):
-            ms, g = one(form)
-            times[form].append(ms)
-            grads[form] = g
-            print("repeat %d head_bwd=%d backward %.3f ms" % (rep, form, ms), flush=True)
+    sides = tuple(("head_bwd=%d backward" % form, functools.partial(one, form)) for form in (1, 2))
+    times = run_sides(sides, args.warmup, args.repeats, 0, line="repeat %d %-*s %.3f ms")
+    per_element, dense = (side_stats(times[label]) for label, _ in sides)
     eng = model._saved[0]
-    med = {f: float(np.median(times[f])) for f in times}
     d = float((grads[1].double() - grads[2].double()).norm() / grads[1].double().norm())
     print(json.dumps({
         "tool": "head_bwd_forms", **({} if args.classes == 1 else {"classes": args.classes}), "input_size": eng.S, "samples": n, "streams": n + 1, "map": [side, side], "repeats": args.repeats,
-        "per_element_ms": {"median": med[1], "min": min(times[1]), "max": max(times[1])},
-        "dense_ms": {"median": med[2], "min": min(times[2]), "max": max(times[2])},
-        "baseline_spread_ms": max(times[1]) - min(times[1]),
-        "dense_over_per_element": med[2] / med[1],
+        "per_element_ms": per_element,
+        "dense_ms": dense,
+        "baseline_spread_ms": per_element["max"] - per_element["min"],
+        "dense_over_per_element": dense["median"] / per_element["median"],
         "value_conv_wgrad_rel_distance": d,
     }))
 

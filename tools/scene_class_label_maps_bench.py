@@ -18,17 +18,16 @@ A window holds --calls calls of label_map; one call of pixel_list is long, so it
     python tools/scene_class_label_maps_bench.py [--repeats 7] [--warmup 2] > profiles/scene_class_label_maps.txt
 """
 import argparse
+import functools
 import json
-import os
 import sys
 
 import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (REPO, os.path.join(REPO, "smg-multimodal-grasping_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from bench_sides import add_repo_paths, run_sides, side_stats, window
+
+add_repo_paths()
 
 
 def main():
@@ -69,19 +68,9 @@ def main():
     def pixel_list():
         eng.loss_scene_ce(q.data_ptr(), aff, hm, R, K, pix.data_ptr(), lab_k.data_ptr(), loss_b.data_ptr(), dq_b.data_ptr(), stream)
 
-    def window(fn, calls):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(dev)
-        t0.record()
-        for _ in range(calls):
-            fn()
-        t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) / calls
-
     print("# %d^2 heightmap, S = %d, %d pairs, %d x %d class maps; label images %.1f MB, pixel list + labels %.1f MB; ms per call"
           % (hm, S, R, side, side, lab.numel() * 4 / 1e6, (pix.numel() + R * K) * 4 / 1e6))
-    first_b = window(pixel_list, 1)              # the first single call of the comparator (cold: an upper bound of a warm one)
+    first_b = window(pixel_list, 1, dev)              # the first single call of the comparator (cold: an upper bound of a warm one)
     label_map()
     torch.cuda.synchronize(dev)
     la, lb = loss_a.double().cpu().numpy(), loss_b.double().cpu().numpy()
@@ -96,23 +85,14 @@ def main():
         print(json.dumps({"tool": "scene_class_label_maps_bench", "probe_pixel_list_ms": first_b}))
         return
     calls_b = int(max(1, min(args.calls, args.side_b_window_ms // max(first_b, 1e-3))))
-    sides = (("label_map", label_map, args.calls), ("pixel_list", pixel_list, calls_b))
+    sides = (("label_map", functools.partial(window, label_map, args.calls, dev)), ("pixel_list", functools.partial(window, pixel_list, calls_b, dev)))
     print("# calls per window: label_map %d, pixel_list %d" % (args.calls, calls_b))
-    times = {name: [] for name, _, _ in sides}
-    for _ in range(args.warmup):
-        for name, fn, calls in sides:
-            window(fn, calls)
-    for rep in range(args.repeats):
-        for name, fn, calls in (sides if rep % 2 == 0 else sides[::-1]):
-            ms = window(fn, calls)
-            times[name].append(ms)
-            print("repeat %d %-10s %.4f ms" % (rep, name, ms), flush=True)
+    times = run_sides(sides, args.warmup, args.repeats, 10)
     summary = {"tool": "scene_class_label_maps_bench", "input_size": S, "heightmap": hm, "pairs": R, "map": [side, side], "repeats": args.repeats,
                "warmup": args.warmup, "calls_per_window": {"label_map": args.calls, "pixel_list": calls_b},
                "first_single_call_pixel_list_ms": first_b, "loss_rel_diff": loss_err, "dq_rel_diff": dq_err}
-    for name, _, _ in sides:
-        t = times[name]
-        summary[name + "_ms"] = {"median": float(np.median(t)), "min": min(t), "max": max(t), "spread": max(t) - min(t)}
+    for name, _ in sides:
+        summary[name + "_ms"] = side_stats(times[name], spread=True)
     a, b = summary["label_map_ms"], summary["pixel_list_ms"]
     summary["larger_spread_ms"] = max(a["spread"], b["spread"])
     summary["label_map_below_pixel_list_by_more_than_the_larger_spread"] = bool(b["median"] - a["median"] > summary["larger_spread_ms"])

@@ -18,18 +18,17 @@ The logits are synthetic (seeded normal, std 2): the kernels' time does not depe
     python tools/scene_class_maps_bench.py [--repeats 7] [--warmup 2] > profiles/scene_class_maps.txt
 """
 import argparse
+import functools
 import json
-import os
 import sys
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (REPO, os.path.join(REPO, "smg-multimodal-grasping_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from bench_sides import add_repo_paths, run_sides, side_stats, window
+
+add_repo_paths()
 
 
 def main():
@@ -84,30 +83,13 @@ def main():
         z = F.grid_sample(q, grid_d, mode="bilinear", padding_mode="border", align_corners=True)
         return torch.where(mask_d, torch.softmax(z, dim=1), ninf)
 
-    sides = (("class_maps_0", class_maps_0), ("class_maps_all", class_maps_all), ("class_argmax", class_argmax), ("maps+argmax", maps_argmax),
-             ("grid_sample", grid_sample))
-
-    def one(fn):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(dev)
-        t0.record()
-        for _ in range(args.calls):
-            fn()
-        t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) / args.calls
+    sides = tuple((name, functools.partial(window, fn, args.calls, dev)) for name, fn in (
+        ("class_maps_0", class_maps_0), ("class_maps_all", class_maps_all), ("class_argmax", class_argmax), ("maps+argmax", maps_argmax),
+        ("grid_sample", grid_sample)))
 
     print("# %d^2 heightmap, S = %d, %d rotations, %d x %d x 3 logits -> [%d, %d, %d] fp32 = %.1f MB per class plane, %.1f MB for all three; "
           "%d calls between two events, ms per call" % (hm, S, R, side, side, R, hm, hm, out1.numel() * 4 / 1e6, out3.numel() * 4 / 1e6, args.calls))
-    times = {name: [] for name, _ in sides}
-    for _ in range(args.warmup):
-        for name, fn in sides:
-            one(fn)
-    for rep in range(args.repeats):
-        for name, fn in (sides if rep % 2 == 0 else sides[::-1]):
-            ms = one(fn)
-            times[name].append(ms)
-            print("repeat %d %-14s %.4f ms" % (rep, name, ms), flush=True)
+    times = run_sides(sides, args.warmup, args.repeats, 14)
     # agreement of the two sides (fp32 grid and fp32 softmax on the comparator's side: not bit-equal) and of the two argmax routes
     ref = grid_sample()
     both = torch.isfinite(ref) & torch.isfinite(out3)
@@ -119,8 +101,7 @@ def main():
                "one_class_equals_its_plane_of_all": bool(torch.equal(out1.view(torch.int32), out3[:, 0].contiguous().view(torch.int32))),
                "argmax_routes_agree": bool(i[0] == i[1])}
     for name, _ in sides:
-        t = times[name]
-        summary[name + "_ms"] = {"median": float(np.median(t)), "min": min(t), "max": max(t)}
+        summary[name + "_ms"] = side_stats(times[name])
     summary["class_maps_0_write_gb_per_s"] = out1.numel() * 4 / 1e9 / (summary["class_maps_0_ms"]["median"] * 1e-3)
     summary["class_maps_all_write_gb_per_s"] = out3.numel() * 4 / 1e9 / (summary["class_maps_all_ms"]["median"] * 1e-3)
     cmp_, all_ = summary["grid_sample_ms"], summary["class_maps_all_ms"]

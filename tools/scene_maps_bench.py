@@ -16,18 +16,17 @@ The maps are synthetic (seeded normal): the kernels' time does not depend on the
     python tools/scene_maps_bench.py [--repeats 7] [--warmup 2] > profiles/scene_maps.txt
 """
 import argparse
+import functools
 import json
-import os
 import sys
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (REPO, os.path.join(REPO, "smg-multimodal-grasping_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from bench_sides import add_repo_paths, run_sides, side_stats, window
+
+add_repo_paths()
 
 
 def main():
@@ -77,29 +76,12 @@ def main():
     def grid_sample():
         return torch.where(mask_d, F.grid_sample(q[:, None], grid_d, mode="bilinear", padding_mode="border", align_corners=True)[:, 0], ninf)
 
-    sides = (("scene_maps", scene_maps), ("scene_argmax", scene_argmax), ("maps+argmax", maps_argmax), ("grid_sample", grid_sample))
-
-    def one(fn):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(dev)
-        t0.record()
-        for _ in range(args.calls):
-            fn()
-        t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) / args.calls
+    sides = tuple((name, functools.partial(window, fn, args.calls, dev)) for name, fn in (
+        ("scene_maps", scene_maps), ("scene_argmax", scene_argmax), ("maps+argmax", maps_argmax), ("grid_sample", grid_sample)))
 
     print("# %d^2 heightmap, S = %d, %d rotations, %d x %d maps -> [%d, %d, %d] fp32 = %.1f MB; %d calls between two events, ms per call"
           % (hm, S, R, side, side, R, hm, hm, out.numel() * 4 / 1e6, args.calls))
-    times = {name: [] for name, _ in sides}
-    for _ in range(args.warmup):
-        for name, fn in sides:
-            one(fn)
-    for rep in range(args.repeats):
-        for name, fn in (sides if rep % 2 == 0 else sides[::-1]):
-            ms = one(fn)
-            times[name].append(ms)
-            print("repeat %d %-12s %.4f ms" % (rep, name, ms), flush=True)
+    times = run_sides(sides, args.warmup, args.repeats, 12)
     # agreement of the two sides (fp32 grid on the comparator's side: not bit-equal) and of the two argmax routes
     ref = grid_sample()
     both = torch.isfinite(ref) & torch.isfinite(out)
@@ -110,8 +92,7 @@ def main():
                "mask_mismatches_vs_grid_sample": int((torch.isfinite(ref) != torch.isfinite(out)).sum()),
                "argmax_routes_agree": bool(i[0] == i[1])}
     for name, _ in sides:
-        t = times[name]
-        summary[name + "_ms"] = {"median": float(np.median(t)), "min": min(t), "max": max(t)}
+        summary[name + "_ms"] = side_stats(times[name])
     med = summary["scene_maps_ms"]["median"]
     summary["scene_maps_write_gb_per_s"] = out.numel() * 4 / 1e9 / (med * 1e-3)
     cmp_ = summary["grid_sample_ms"]
