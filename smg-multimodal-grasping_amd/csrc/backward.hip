@@ -177,7 +177,8 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         else gsrc = fused_gsrc(b, d);
         if (!e->generic3x3) {
             // conv2 weight gradient with the activation halo resident in LDS (halo.cuh)
-            const PartialTiles::Slot at = tiles.place_halo3x3(w.w3.groups);
+            const bool w1_partial = w1_partial_tiles(pl, NS, e->deterministic);
+            const PartialTiles::Slot at = tiles.place_halo3x3(w.w3.groups, w1_partial);
             if (at.refused) return fail(-12, tiles.refusal());
             launch_reduce2(e, s2, at.first);
             Halo3x3WgradArgs a;
@@ -218,7 +219,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             a.btab = stat_table(e, e->sx_tab[b], e->max_streams, Ct); a.bgamma = P + d.n1.w; a.bbeta = P + d.n1.b; a.basc = asc_n1(e, b, i);
             a.chunk = w.chunk; a.chunks_per_stream = w.cps; a.n_chunks = NS * w.cps;
             a.dw = Gr + d.c1.w; a.ldw_out = d.cin; a.ldp = w.nt * G::BN;
-            const PartialTiles::Slot at = tiles.place_behind3x3((int64_t)a.n_chunks * G::BM * a.ldp);
+            const PartialTiles::Slot at = tiles.place_behind3x3((int64_t)a.n_chunks * G::BM * a.ldp, true);
             launch_reduce2(e, s2, at.first);
             if (at.refused) return fail(-12, tiles.refusal());
             a.part = part_at(e, at);
@@ -241,7 +242,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 p.dw = Gr + d.c1.w; p.ldw_out = d.cin;
                 const dim3 grid(1, w.nt, NS * w.cps);
                 return launch_wgrad(e, s2, p, grid, K_W1, 2.0 * NS * pl.HW * d.cin * kBottleneck,
-                                    ESZ(e) * NS * pl.HW * (kBottleneck + d.cin), 1, C_IDENT, tiles, tiles.place_behind3x3(wgrad_partial_floats(p, grid)));
+                                    ESZ(e) * NS * pl.HW * (kBottleneck + d.cin), 1, C_IDENT, tiles, tiles.place_behind3x3(wgrad_partial_floats(p, grid), w1_partial_tiles(pl, NS, e->deterministic)));
             };
             PREC_DISPATCH(e, if (int rc = go(PTAG)) return rc);
         }
@@ -252,6 +253,9 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         launch_reduce2(e, s2, tiles.drain());
         HIP_OK(hipEventRecord(e->ev_end, s2));
         HIP_OK(hipStreamWaitEvent(st, e->ev_end, 0));
+        // the walk leaves in front of db_flush_kernel: drop what the layers so far left in the dbeta / dgamma scratch, or the next
+        // backward's flush adds it to ITS norm1 / transition-norm gradients (the scratch is zero between calls: engine.h)
+        HIP_OK(hipMemsetAsync(e->dbscr, 0, (size_t)kDbRep * e->db_total * sizeof(float), st));
         if (int rc = walk_status(e)) return rc;
         e->have_fwd = false; e->bw_phase0_done = false; e->prof_stage = -1;
         return 0;

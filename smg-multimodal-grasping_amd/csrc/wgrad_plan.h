@@ -115,6 +115,14 @@ struct WgradPlan {
     // conv1 (1x1): wave-specialised (128-column tiles) or generic (64-column tiles); nt column tiles, cps chunks of `chunk` pixels per stream
     bool w1_ws; int nt, chunk, cps;
 };
+// Does a dense layer's 1x1 weight gradient leave partial tiles (summed by reduce_partials_kernel in a fixed order) or add with fp32 atomics?
+// Atomics save a few-stream call - which is host-launch-bound - the reduce launches, but each workgroup then sums its whole pixel chunk in
+// ONE set of fp32 accumulators before it adds: on planes of more than 1600 pixels that is a chain of 800 - 2600 pixels per workgroup and
+// 16 - 63 atomics per element, measured at 3.0 - 7.3x the error of a blocked fp32 reduction (S = 672, 3 streams, 168^2 / 84^2; the
+// partial-tile form: 1.3 - 2.4x).  So few-stream calls keep the atomics on the small planes only - the ones whose GS the side stream
+// materialises as well (backward.hip gs_on_side).
+static inline bool w1_partial_tiles(const Plane& pl, int NS, bool deterministic) { return deterministic || NS > 4 || pl.HW > 1600; }
+
 // split16: the walk's operand form of the dense layers (fp16-split units in D2), which the wave-specialised 1x1 kernel reads.
 static inline WgradPlan plan_layer_wgrads(const Plane& pl, int cin, int NS, int prec, bool split16, bool deterministic, int64_t part_floats,
                                           bool generic3x3, bool generic_w1) {
@@ -124,9 +132,10 @@ static inline WgradPlan plan_layer_wgrads(const Plane& pl, int cin, int NS, int 
         w.w3_grid = (unsigned)(((w.w3.groups * NS + 7) / 8) * 8 * (kBottleneck / 32));      // (see the kernel: channel groups of a tile group share an XCD)
     }
     // conv1 weight gradient, wave-specialised (wsw.cuh): 128 x 128 tiles, 32-pixel k-tiles, loader + matrix waves - for the partial-tile
-    // form (more than four streams, or "deterministic") on layers of more than 64 input channels (a half-empty 128-column tile
+    // form (w1_partial_tiles) on layers of more than 64 input channels (a half-empty 128-column tile
     // costs block 1's first layer 77 -> 107 us; few-stream calls keep the generic kernel's 128 x 64 atomics: 7.3 -> 7.5 ms per single-sample step)
-    w.w1_ws = split16 && !generic_w1 && cin > 64 && (deterministic || NS > 4);
+    const bool partial = w1_partial_tiles(pl, NS, deterministic);
+    w.w1_ws = split16 && !generic_w1 && cin > 64 && partial;
     if (w.w1_ws) {
         w.nt = (cin + kW1WsTileN - 1) / kW1WsTileN;
         pick_chunk(pl, NS, w.nt, w.chunk, w.cps, 320);      // (256 / 512 / 768 workgroups: 16.45-16.62 / 16.64-16.67 / 16.73-16.82 ms per step against 16.47-16.53)
@@ -137,7 +146,7 @@ static inline WgradPlan plan_layer_wgrads(const Plane& pl, int cin, int NS, int 
         // on many-stream batches (config 3: 28.9 -> 28.5 ms at 160; 120 / 80: 28.6 / 28.8; S = 1824 with 5 streams: 320 stays)
         // few-stream calls on the atomics form: 128 (every workgroup adds a 128 x 64 tile with fp32 atomics; single-sample step 5.9 -> 5.65 ms;
         // 64 / 192 / 320: 6.0 / 5.7 / 5.9)
-        pick_chunk(pl, NS, w.nt, w.chunk, w.cps, (prec && NS >= 16) ? 160 : (NS <= 4 && !deterministic) ? 128 : 320);
+        pick_chunk(pl, NS, w.nt, w.chunk, w.cps, (prec && NS >= 16) ? 160 : !partial ? 128 : 320);
     }
     return w;
 }
@@ -152,9 +161,9 @@ static inline WgradPlan plan_layer_wgrads(const Plane& pl, int cin, int NS, int 
 //  * A dense layer's halo 3x3 tiles start at offset 0 and its 1x1 tiles go behind them, so that ONE reduce launch serves both (if the
 //    1x1 tiles do not fit behind, or the 1x1 takes atomics, the 3x3 reduction runs first and the 1x1 starts over at offset 0).
 //    The 1x1 leaves partial tiles (reproducible; since reduce_partials splits the partials over four waves the fixed-order reduce
-//    beats 128 x 64 fp32 atomics per workgroup) with more than four streams or under "deterministic"; a few streams are
-//    host-launch-bound, atomics save the reduce launches.
-//  * Few-stream calls without "deterministic" (only the 3x3 leaves partial tiles): the reduce of layer l waits for layer l - 1's and
+//    beats 128 x 64 fp32 atomics per workgroup) with more than four streams, under "deterministic" and on planes of more than 1600
+//    pixels (w1_partial_tiles); a few streams are host-launch-bound, on the small planes atomics save the reduce launches.
+//  * Layers whose 1x1 takes atomics (only the 3x3 leaves partial tiles): the reduce of layer l waits for layer l - 1's and
 //    ONE launch serves both - the tiles alternate between the two halves of the workspace.  (The side stream is the longer one
 //    in a single-sample step: 29 reduce launches of ~7.5 us less on it.)
 //  * drain() before the side stream is joined.
@@ -175,17 +184,17 @@ public:
         if (s.off < 0 && deterministic) s.refused = refuse(need, floats);
         return s;
     }
-    Slot place_halo3x3(int groups) {
+    // w1_partial: this layer's 1x1 leaves partial tiles behind the 3x3's (w1_partial_tiles)
+    Slot place_halo3x3(int groups, bool w1_partial) {
         Slot s{HALO3, 0, w3_partial_floats(groups, NS), ReducePair{}, false};
         if (s.size > floats) { s.refused = refuse(-1, floats); return s; }
-        if (!deterministic && NS <= 4 && s.size * 2 <= floats) s.kind = HALO3_PAIRED;
+        if (!w1_partial && s.size * 2 <= floats) s.kind = HALO3_PAIRED;
         if (s.kind == HALO3) s.first = drain();
         else if (half) s.off = floats / 2;
         return s;
     }
-    Slot place_behind3x3(int64_t need) {
+    Slot place_behind3x3(int64_t need, bool partial) {
         Slot s{BEHIND3, cursor, need, ReducePair{}, false};
-        const bool partial = deterministic || NS > 4;
         if (held.Z && (!partial || s.off + need > floats)) { s.first.a = held; held.Z = 0; s.off = 0; }
         const int64_t have = floats - s.off;
         if (!partial || need > have) s.off = -1;

@@ -21,7 +21,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import _bn_stats64, _fp32_blocked, _fp32_chain, _WGRAD_BLK, _WGRAD_GATE, grads_within_fp32_class, MEAN, STD, nhwc_plane, oracle_net, orc, probe_idx, q_close, scene, scene_tensors
+import dense_ref as dr
+from helpers import _fp32_chain, _WGRAD_BLK, _WGRAD_GATE, grads_within_fp32_class, MEAN, STD, nhwc_plane, oracle_net, orc, probe_idx, q_close, scene, scene_tensors
 
 pytestmark = pytest.mark.gpu
 
@@ -1260,58 +1261,38 @@ def test_debug_read_of_bottlenecks_in_16bit_storage(gpu):
 def test_layer_products_within_fp32_chain_error(gpu, block, layer):
     """GEMM-level gate on the PRODUCT's kernels at real layer shapes (K = 64 / 480 / 992 for the 1x1, K = 1152 for the 3x3):
     the raw output of one dense layer's conv1 (BN + ReLU + scaled two-piece fp16 split + three MFMA terms, operand kind 3) and
-    conv2, read back from the engine, against the same layer evaluated in fp64 from the engine's own input buffer.  The error must stay within 2x
-    that of a plain fp32 multiply-add chain over the same operands - i.e. the split products are fp32-class arithmetic,
-    independent of how the gradient gates of the end-to-end tests are set."""
+    conv2, read back from the engine, against the same layer evaluated in fp64 from the engine's own input buffer (tests/dense_ref.py).
+    The error must stay within 2x that of a plain fp32 multiply-add chain over the same operands - i.e. the split products are
+    fp32-class arithmetic, independent of how the gradient gates of the end-to-end tests are set.  (Stream 0, conv2 on a band of 48
+    rows; tests/test_gpu_dense_gates.py holds every kernel variant, the other streams and the whole planes to the same yardstick.)"""
     net = product_net(0)
     x, mx = scene_tensors(0, [0])
     net.forward(x, mx, 0, True, 3)
     eng = engine_of(net)
     NS, H, HWp = eng.max_streams, eng.H[1 + block], eng.HWp[1 + block]
-    Ct = (256, 512, 1024, 1024)[block - 1]
-    cin = (64, 128, 256, 512)[block - 1] + 32 * (layer - 1)
+    Ct, cin = dr.CT[block - 1], dr.cin_of(block, layer)
     X = eng.debug_read("x%d" % block).reshape(NS, HWp, Ct)[0, :H * H, :]
     BT = eng.debug_read("bt%d_%d" % (block, layer)).reshape(NS, HWp, 128)[0, :H * H, :]
     sd = {k: v.detach().cpu().numpy() for k, v in net.state_dict().items()}
     pre = "grasp_depth_trunk.features.denseblock%d.denselayer%d." % (block, layer)
 
-    def bn_relu(v, g, b, dt):
-        v64 = v.astype(np.float64)
-        mean, var = v64.mean(0), v64.var(0)
-        inv = 1.0 / np.sqrt(var + 1e-5)
-        if dt == np.float64:
-            return np.maximum((v64 - mean) * inv * g.astype(np.float64) + b.astype(np.float64), 0.0)
-        sc = (g.astype(np.float64) * inv).astype(np.float32)
-        return np.maximum((v - mean.astype(np.float32)) * sc + b, np.float32(0)).astype(np.float32)
-
     # conv1: 1x1, cin -> 128
-    w1 = sd[pre + "conv1.weight"].reshape(128, cin)
-    a64 = bn_relu(X[:, :cin], sd[pre + "norm1.weight"], sd[pre + "norm1.bias"], np.float64)
-    a32 = bn_relu(X[:, :cin], sd[pre + "norm1.weight"], sd[pre + "norm1.bias"], np.float32)
-    ref = a64 @ w1.astype(np.float64).T
-    mag = np.abs(a64) @ np.abs(w1.astype(np.float64)).T + 1e-30
-    e_prod = np.sqrt((((BT.astype(np.float64) - ref) / mag) ** 2).mean())
-    e_chain = np.sqrt((((_fp32_chain(a32, w1).astype(np.float64) - ref) / mag) ** 2).mean())
+    g1, b1, w1 = sd[pre + "norm1.weight"], sd[pre + "norm1.bias"], sd[pre + "conv1.weight"].reshape(128, cin)
+    ref, mag = dr.conv1_fwd(X[:, :cin], g1, b1, w1)
+    e_prod = dr.rms(BT, ref, mag)
+    e_chain = dr.rms(dr.conv1_chain(X[:, :cin], g1, b1, w1, np.arange(H * H)), ref, mag)
     print("conv1 block %d layer %d K %d: err/sum|ab| rms product %.3e, fp32 chain %.3e" % (block, layer, cin, e_prod, e_chain))
     assert e_prod <= 2.0 * e_chain, (e_prod, e_chain)
 
     # conv2: 3x3 pad 1, 128 -> 32 (the layer's slice of the block buffer), on a 48-row band (keeps the fp32 chain cheap)
-    w2 = sd[pre + "conv2.weight"]                                      # [32][128][3][3]
-    b64 = bn_relu(BT, sd[pre + "norm2.weight"], sd[pre + "norm2.bias"], np.float64).reshape(H, H, 128)
-    b32 = bn_relu(BT, sd[pre + "norm2.weight"], sd[pre + "norm2.bias"], np.float32).reshape(H, H, 128)
-    rows = min(H, 48)
-
-    def im2col(a):
-        p = np.zeros((H + 2, H + 2, 128), dtype=a.dtype)
-        p[1:-1, 1:-1] = a
-        return np.concatenate([p[dy:dy + rows, dx:dx + H].reshape(rows * H, 128) for dy in range(3) for dx in range(3)], axis=1)
-    wk = np.concatenate([w2[:, :, dy, dx] for dy in range(3) for dx in range(3)], axis=1)     # [32][9*128], tap-major like im2col
-    c64, c32 = im2col(b64), im2col(b32)
-    out = X[:, cin:cin + 32].reshape(H, H, 32)[:rows].reshape(rows * H, 32)
+    g2, b2, w2 = sd[pre + "norm2.weight"], sd[pre + "norm2.bias"], sd[pre + "conv2.weight"]      # [32][128][3][3]
+    pix = np.arange(min(H, 48) * H)
+    wk = dr.w2_fwd_mat(w2)                                              # [32][9*128], tap-major like im2col
+    c64 = dr.im2col(dr.act64(BT, g2, b2), H, H, pix)
     ref = c64 @ wk.astype(np.float64).T
     mag = np.abs(c64) @ np.abs(wk.astype(np.float64)).T + 1e-30
-    e_prod = np.sqrt((((out.astype(np.float64) - ref) / mag) ** 2).mean())
-    e_chain = np.sqrt((((_fp32_chain(c32, wk).astype(np.float64) - ref) / mag) ** 2).mean())
+    e_prod = dr.rms(X[pix, cin:cin + 32], ref, mag)
+    e_chain = dr.rms(dr.conv2_chain(BT, H, H, g2, b2, w2, pix), ref, mag)
     print("conv2 block %d layer %d K 1152: err/sum|ab| rms product %.3e, fp32 chain %.3e" % (block, layer, e_prod, e_chain))
     assert e_prod <= 2.0 * e_chain, (e_prod, e_chain)
 
@@ -1322,9 +1303,10 @@ def test_backward_layer_products_within_fp32_chain_error(gpu, block, layer):
     one dense layer (engine option debug_stop) and the test reads what that layer's kernels consumed and produced - GS and D2 from
     their ring slots (D2 rebuilt from its fp16 units and block scales: the operand the MFMAs see), the raw 3x3 data gradient, the
     block's G' in front of and behind the layer's 1x1 data gradients, the two weight gradients - and recomputes the four products
-    in fp64 from those buffers: conv2 data gradient, conv2 weight gradient, conv1 data gradient (per-layer or layer-grouped form),
-    conv1 weight gradient.  Each must stay within 2x the error of a plain fp32 multiply-add chain over the same operands.
-    Sample 3 enters with dq = 1e-6 (2^-20 of the others): its stream's gradient operands sit 20 binades below the rest."""
+    in fp64 from those buffers (tests/dense_ref.py): conv2 data gradient, conv2 weight gradient, conv1 data gradient (per-layer or
+    layer-grouped form), conv1 weight gradient.  Each must stay within 2x the error of a plain fp32 multiply-add chain over the same
+    operands.  Sample 3 enters with dq = 1e-6 (2^-20 of the others): its stream's gradient operands sit 20 binades below the rest.
+    (tests/test_gpu_dense_gates.py holds the other kernel variants, stream regimes and planes to the same yardsticks.)"""
     import synthetic
     net = product_net(0)
     depth, masks = synthetic.heightmap_scene(0)
@@ -1332,7 +1314,7 @@ def test_backward_layer_products_within_fp32_chain_error(gpu, block, layer):
     rots = [0, 3, 7, 10, 13]
     NSu = len(rots) + 1
     b, i = block - 1, layer - 1
-    L = (6, 12, 24, 16)[b]
+    L = dr.LAYERS[b]
     q = net.run(0, rots, 16, heightmaps=hm, mean=MEAN, std=STD, keep_for_backward=True)
     eng = engine_of(net)
     dq = torch.tensor([1.0, -1.0, 0.5, 1e-6, -0.25], device=gpu).view(5, 1, 1, 1)
@@ -1345,8 +1327,7 @@ def test_backward_layer_products_within_fp32_chain_error(gpu, block, layer):
     torch.cuda.synchronize()
     H, HWp = eng.H[1 + block], eng.HWp[1 + block]
     HW = H * H
-    Ct = (256, 512, 1024, 1024)[b]
-    cin = (64, 128, 256, 512)[b] + 32 * i
+    Ct, cin = dr.CT[b], dr.cin_of(block, layer)
 
     def rd(name, C):
         return eng.debug_read(name, count=NSu * HWp * C).reshape(NSu, HWp, C)[:, :HW, :]
@@ -1360,118 +1341,57 @@ def test_backward_layer_products_within_fp32_chain_error(gpu, block, layer):
 
     def check(what, got, ref, mag, chain, keep=None):
         keep = np.ones(ref.shape, dtype=bool) if keep is None else keep
-        e_prod = np.sqrt(((((got.astype(np.float64) - ref) / mag) ** 2)[keep]).mean())
-        e_chain = np.sqrt(((((chain.astype(np.float64) - ref) / mag) ** 2)[keep]).mean())
+        e_prod, e_chain = dr.rms(got, ref, mag, keep), dr.rms(chain, ref, mag, keep)
         print("%s block %d layer %d: err/sum|ab| rms product %.3e, fp32 chain %.3e (%d elements)" % (what, block, layer, e_prod, e_chain, int(keep.sum())))
         assert e_prod <= 2.0 * e_chain, (what, e_prod, e_chain)
 
-    def bn_act(v, g, bta, dt):
-        """relu(bn(v)) of one stream's plane, fp64 or the kernels' fp32 form; also the fp64 pre-activation (borderline test)"""
-        mean, inv = _bn_stats64(v)
-        pre64 = (v.astype(np.float64) - mean) * inv * g.astype(np.float64) + bta.astype(np.float64)
-        if dt == np.float64:
-            return np.maximum(pre64, 0.0), pre64
-        sc = (g.astype(np.float64) * inv).astype(np.float32)
-        return np.maximum((v - mean.astype(np.float32)) * sc + bta, np.float32(0)).astype(np.float32), pre64
-
     g2, b2 = sd[pre + "norm2.weight"], sd[pre + "norm2.bias"]
     w2 = sd[pre + "conv2.weight"]                                      # [32][128][3][3]
-    rows = min(H, 24)
+    pix = np.arange(min(H, 24) * H)
 
     # ---- conv2 data gradient on a band of rows of stream 0 and of the 2^-20 stream: dy[p][k] = mask * sum_{tap, c} gs[p - d(tap)][c] * w2[c][k][tap]
-    wk_d = np.concatenate([w2[:, :, dy, dx].T for dy in range(3) for dx in range(3)], axis=1)      # [128][9 * 32], taps in the order of the gather below
+    wk_d = dr.w2_bwd_mat(w2)                                             # [128][9 * 32], taps in the order of the gather
     for n in (0, 3):
-        gs = GS[n].reshape(H, H, 32)
-        pad = np.zeros((H + 2, H + 2, 32), dtype=np.float32)
-        pad[1:-1, 1:-1] = gs
-        col = np.concatenate([pad[2 - dy:2 - dy + rows, 2 - dx:2 - dx + H].reshape(rows * H, 32) for dy in range(3) for dx in range(3)], axis=1)
-        _, pre64 = bn_act(BT[n], g2, b2, np.float64)
-        pre_b = pre64.reshape(H, H, 128)[:rows].reshape(rows * H, 128)
-        scale_b = np.abs(BT[n].astype(np.float64) - _bn_stats64(BT[n])[0]).reshape(H, H, 128)[:rows].reshape(rows * H, 128) * np.abs(g2) * _bn_stats64(BT[n])[1] + np.abs(b2)
-        on = pre_b > 1e-5 * scale_b                                      # clearly inside the ReLU (borderline signs are the mask's business, not the GEMM's)
+        col = dr.im2col(GS[n], H, H, pix, flip=True)
+        on = dr.relu_sides(BT[n], g2, b2, rows=pix)[0]                   # clearly inside the ReLU (borderline signs are the mask's business, not the GEMM's)
         ref = col.astype(np.float64) @ wk_d.astype(np.float64).T
         mag = np.abs(col).astype(np.float64) @ np.abs(wk_d).astype(np.float64).T + 1e-300
-        got = DY[n].reshape(H, H, 128)[:rows].reshape(rows * H, 128)
-        check("conv2 dgrad (stream %d)" % n, got, ref, mag, _fp32_chain(col, wk_d), keep=on)
+        check("conv2 dgrad (stream %d)" % n, DY[n][pix], ref, mag, _fp32_chain(col, wk_d), keep=on)
 
     # ---- norm2 backward as stored for the three 1x1 consumers (units + block scales) against fp64 from the raw gradient
     for n in (0, 3):
-        mean, inv = _bn_stats64(BT[n])
-        xh = (BT[n].astype(np.float64) - mean) * inv
-        dy = DY[n].astype(np.float64)
-        ref = g2.astype(np.float64) * inv * (dy - dy.mean(0) - xh * (dy * xh).mean(0))
-        blk = np.abs(ref).reshape(-1, 64, 128).max(axis=(1, 2), keepdims=True) if HW % 64 == 0 else np.abs(ref).max()
-        err = np.abs(D2[n].astype(np.float64) - ref)
-        rel = (err.reshape(-1, 64, 128) / np.maximum(blk, 1e-300)).max() if HW % 64 == 0 else (err / blk).max()
+        rel = dr.unit_form_error(D2[n], dr.norm2_bwd(DY[n], BT[n], g2))
         print("norm2 backward in unit form, stream %d: max |err| / block max %.3e" % (n, rel))
         assert rel <= 2e-5, rel                                          # fp32 evaluation of the affine form + 22-bit pieces (2^-22 = 2.4e-7 of the block's maximum)
 
     # ---- conv2 weight gradient: dW2[c][k][tap] = sum_{stream, p} gs[p][c] * relu(bn2(bt))[p + d(tap)][k]
-    a64s, a32s = [], []
-    for n in range(NSu):
-        a64, _ = bn_act(BT[n], g2, b2, np.float64)
-        a32, _ = bn_act(BT[n], g2, b2, np.float32)
-        for a, lst in ((a64, a64s), (a32, a32s)):
-            padk = np.zeros((H + 2, H + 2, 128), dtype=a.dtype)
-            padk[1:-1, 1:-1] = a.reshape(H, H, 128)
-            lst.append(np.concatenate([padk[dy:dy + H, dx:dx + H].reshape(HW, 128) for dy in range(3) for dx in range(3)], axis=1))
-    A64, A32 = np.concatenate(a64s), np.concatenate(a32s)                # [streams * HW][9 * 128]
-    Gs = GS.reshape(NSu * HW, 32)
     # Yardstick: a BLOCKED fp32 reduction over ALL streams x pixels (64-term chains, then pairwise: _fp32_blocked) on a subset of the
     # output elements - every 9th of the 9 * 128 columns - with the product's error on the same elements within 3x it.  (Until round
     # 5 the yardstick was ONE sequential chain over a thinned reduction, scaled by sqrt(length): 50 - 130x slack on these lengths.)
-    csel = slice(0, None, 9)
-    ref = Gs.astype(np.float64).T @ A64[:, csel]
-    mag = np.abs(Gs).astype(np.float64).T @ np.abs(A64[:, csel]) + 1e-300
-    got = grads[pre + "conv2.weight"].transpose(0, 2, 3, 1).reshape(32, 9 * 128)[:, csel]      # [c][tap][k] like the im2col columns
-    e_prod = np.sqrt((((got.astype(np.float64) - ref) / mag) ** 2).mean())
-    e_blk = {bl: np.sqrt((((_fp32_blocked(Gs, np.ascontiguousarray(A32[:, csel]), bl).astype(np.float64) - ref) / mag) ** 2).mean()) for bl in (64, 512)}
+    cols = np.arange(0, 9 * 128, 9)
+    Gs, A64, A32 = dr.conv2_wgrad_ops(GS, BT, H, H, g2, b2, cols)
+    e_prod, e_blk, ref, _ = dr.wgrad_errors(dr.w2_grad_mat(grads[pre + "conv2.weight"])[:, cols], Gs, A64, A32)      # [c][tap][k] like the im2col columns
     print("conv2 wgrad block %d layer %d: err/sum|ab| rms product %.3e, blocked fp32 (chains + pairwise) 64-term %.3e / 512-term %.3e over all %d terms, %d elements: ratios %.2f / %.2f"
           % (block, layer, e_prod, e_blk[64], e_blk[512], NSu * HW, ref.size, e_prod / e_blk[64], e_prod / e_blk[512]))
     assert e_prod <= _WGRAD_GATE * e_blk[_WGRAD_BLK], ("conv2 wgrad", e_prod, e_blk)
 
     # ---- conv1 data gradient: G'[p][c] += gamma1[c] * relu'(bn1(x))[p][c] * sum_k D2[p][k] * w1[k][c]
-    g_lo = i - (0 if (L - 1 - i) % 4 == 3 else min(i, 3 - (L - 1 - i) % 4))
-    cs = (64, 128, 256, 512)[b] + 32 * g_lo
-    segs = []                                                             # (layer, column range) pairs whose contribution landed between the snapshots
-    if cin > cs:
-        segs.append(([layer], cs, cin))
-    if i == g_lo:
-        g_hi = L - 1 - ((L - 1 - g_lo) // 4) * 4
-        segs.append((list(range(g_lo + 1, g_hi + 2)), 0, cs))
-    for layers, c0, c1 in segs:
+    # (layer, column range) pairs whose contribution landed between the snapshots: dense_ref.dgrad1_segments restates backward.hip's groups
+    for layers, c0, c1 in dr.dgrad1_segments(L, i, dr.CIN0[b]):
+        prm = [(sd["grasp_depth_trunk.features.denseblock%d.denselayer%d.norm1.weight" % (block, l + 1)],
+                sd["grasp_depth_trunk.features.denseblock%d.denselayer%d.norm1.bias" % (block, l + 1)],
+                sd["grasp_depth_trunk.features.denseblock%d.denselayer%d.conv1.weight" % (block, l + 1)].reshape(128, -1)) for l in layers]
         for n in (0, 3):
             take = slice(0, min(HW, 4096))
-            ref = G0[n][take, c0:c1].astype(np.float64)
-            mag = np.abs(ref) + 1e-300
-            ch = G0[n][take, c0:c1].copy()
-            keep = np.ones(ref.shape, dtype=bool)
-            mean, inv = _bn_stats64(X[n][:, c0:c1])
-            for lyr in layers:
-                prl = "grasp_depth_trunk.features.denseblock%d.denselayer%d." % (block, lyr)
-                g1, b1_ = sd[prl + "norm1.weight"][c0:c1], sd[prl + "norm1.bias"][c0:c1]
-                w1 = sd[prl + "conv1.weight"].reshape(128, -1)[:, c0:c1]                   # [128][cols]
-                d2 = rd("d2_%d_%d" % (block, lyr), 128)[n][take]
-                pre64 = (X[n][take, c0:c1].astype(np.float64) - mean) * inv * g1 + b1_
-                sc = np.abs(X[n][take, c0:c1].astype(np.float64) - mean) * inv * np.abs(g1) + np.abs(b1_)
-                keep &= np.abs(pre64) > 1e-5 * sc
-                m = pre64 > 0
-                ref = ref + g1.astype(np.float64) * m * (d2.astype(np.float64) @ w1.astype(np.float64))
-                mag = mag + np.abs(g1).astype(np.float64) * m * (np.abs(d2).astype(np.float64) @ np.abs(w1).astype(np.float64))
-                ch = (ch + (g1 * m).astype(np.float32) * _fp32_chain(d2, np.ascontiguousarray(w1.T))).astype(np.float32)
-            check("conv1 dgrad (stream %d, layers %s, columns %d..%d)" % (n, layers, c0, c1), G1[n][take, c0:c1], ref, mag, ch, keep=keep)
+            d2s = [rd("d2_%d_%d" % (block, l + 1), 128)[n] for l in layers]
+            ref, mag, ch, keep = dr.conv1_dgrad(G0[n], X[n], prm, d2s, c0, c1, take=take)
+            check("conv1 dgrad (stream %d, layers %s, columns %d..%d)" % (n, [l + 1 for l in layers], c0, c1), G1[n][take, c0:c1], ref, mag, ch, keep=keep)
 
     # ---- conv1 weight gradient: dW1[k][c] = sum_{stream, p} D2[p][k] * relu(bn1(x))[p][c]
     g1, b1_ = sd[pre + "norm1.weight"], sd[pre + "norm1.bias"]
-    a64 = np.concatenate([bn_act(X[n][:, :cin], g1, b1_, np.float64)[0] for n in range(NSu)])
-    a32 = np.concatenate([bn_act(X[n][:, :cin], g1, b1_, np.float32)[0] for n in range(NSu)])
-    D2f = D2.reshape(NSu * HW, 128)
-    rsel, csel = slice(0, None, 8), slice(0, None, max(1, cin // 128))      # 16 of the 128 rows x <= 128 columns, the whole reduction
-    ref = D2f[:, rsel].astype(np.float64).T @ a64[:, csel]
-    mag = np.abs(D2f[:, rsel]).astype(np.float64).T @ np.abs(a64[:, csel]) + 1e-300
-    got = grads[pre + "conv1.weight"].reshape(128, cin)[rsel, csel]
-    e_prod = np.sqrt((((got.astype(np.float64) - ref) / mag) ** 2).mean())
-    e_blk = {bl: np.sqrt((((_fp32_blocked(np.ascontiguousarray(D2f[:, rsel]), np.ascontiguousarray(a32[:, csel]), bl).astype(np.float64) - ref) / mag) ** 2).mean()) for bl in (64, 512)}
+    rows, cols = np.arange(0, 128, 8), np.arange(0, cin, max(1, cin // 128))      # 16 of the 128 rows x <= 128 columns, the whole reduction
+    D, A64, A32 = dr.conv1_wgrad_ops(D2, X, g1, b1_, rows, cols)
+    e_prod, e_blk, ref, _ = dr.wgrad_errors(grads[pre + "conv1.weight"].reshape(128, cin)[np.ix_(rows, cols)], D, A64, A32)
     print("conv1 wgrad block %d layer %d K %d: err/sum|ab| rms product %.3e, blocked fp32 (chains + pairwise) 64-term %.3e / 512-term %.3e over all %d terms, %d elements: ratios %.2f / %.2f"
           % (block, layer, cin, e_prod, e_blk[64], e_blk[512], NSu * HW, ref.size, e_prod / e_blk[64], e_prod / e_blk[512]))
     assert e_prod <= _WGRAD_GATE * e_blk[_WGRAD_BLK], ("conv1 wgrad", e_prod, e_blk)
