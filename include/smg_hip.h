@@ -202,6 +202,26 @@ int smg_scene_maps(smg_engine* e, const float* q_dev, int64_t map_stride, int n_
 int smg_scene_argmax(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host,
                      int hm_size, int* idx_out_dev, float* val_out_dev, void* stream);
 
+/* smg_scene_argmax per OBJECT: every map restricted to the heightmap pixels its masks select, one result per group of maps, the
+ * scene-frame maps never written.  Geometry, validity and values are steps 1-7 above, exactly smg_scene_maps' (a value rounded to
+ * float32 once).
+ * masks_dev float64 [n_masks][hm_size][hm_size] - the very tensor smg_batch.masks_dev was given for the forward: no second upload,
+ * no conversion.  map_mask_a / map_mask_b (host, n_maps each): a pixel is SELECTED for map m when mask[map_mask_a[m]] or
+ * mask[map_mask_b[m]] is not exactly 0 there; index -1 = no such term, both -1 = every pixel.  -0.0 does not select, a NaN does;
+ * the values are never used arithmetically.  map_group (host, n_maps): map m competes for the result of group map_group[m]; the
+ * maps of a group need not be contiguous.
+ * idx_out_dev int32[n_groups], val_out_dev float32[n_groups]: per group the best selected valid pixel over the group's maps - the
+ * flattened index into [n_maps][hm_size][hm_size] of the WHOLE call - by smg_argmax's rules (lowest index on ties, a NaN wins).  A
+ * group with no map, or with no selected valid pixel, gets index -1, value -inf; every group's pair is written by every successful
+ * call.  Per-workgroup partials in a scratch the engine owns, reduced by one workgroup per group; no atomics: two identical calls
+ * are bit-identical, and a group's result equals smg_argmax over smg_scene_maps' output with the unselected pixels set to -inf.
+ * Returns -22 and launches nothing for a NULL pointer, n_maps < 1, n_masks < 1, n_groups < 1, a negative map_stride, a mask index
+ * outside [-1, n_masks), a group outside [0, n_groups), a flattened index that does not fit int32, and the geometry refusals above
+ * (hm_size, a 1 x 1 map, an affine with a translation). */
+int smg_scene_argmax_objects(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host,
+                             int hm_size, const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
+                             const int* map_group, int n_groups, int* idx_out_dev, float* val_out_dev, void* stream);
+
 /* Huber loss on K labelled heightmap pixels per pair, one-channel heads only (head_out != 1 returns -22): q and dq are
  * [n_pairs][1][OH][OW]; pixels_dev int32 [n_pairs][K][2] = (iy, ix); label_dev, weight_dev float32 [n_pairs][K] (weight_dev NULL =
  * all ones, a weight of exactly 0 masks its point).  With v_k the interpolated value of point k in its pair's rotation (double,

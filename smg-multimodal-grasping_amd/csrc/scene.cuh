@@ -2,8 +2,10 @@
 // heightmap's pixel grid.  In the order of the file:
 //   scene_point / scene_interp / scene_class   the coordinate chain of one heightmap pixel and the value(s) of the map there: one Q
 //                                  value, or the softmax of the three interpolated logits of a 3-class head
-//   scene_walk<PLANES, ARGMAX>     the one tiling behind smg_scene_maps / smg_scene_class_maps (ARGMAX false: the maps are stored)
-//                                  and smg_scene_argmax / smg_scene_class_argmax (true: the best (rotation, pixel), nothing stored)
+//   scene_walk<PLANES, ARGMAX, SELECT>  the one tiling behind smg_scene_maps / smg_scene_class_maps (ARGMAX false: the maps are
+//                                  stored), smg_scene_argmax / smg_scene_class_argmax (true: the best (rotation, pixel), nothing
+//                                  stored) and smg_scene_argmax_objects (SELECT: every map on the pixels its masks select, one
+//                                  result per group of maps)
 //   SceneHuber / SceneCe           the per-point terms of the two losses, each written once
 //   scene_list_walk                the loss on K LISTED pixels per pair (smg_loss_scene_ce; smg_loss_scene's kernel keeps the same
 //                                  loop in a copy of its own, for the reason its comment gives)
@@ -80,7 +82,31 @@ __device__ __forceinline__ float scene_class_prob(const SceneClass c, int cls) {
     return (float)((cls == 2 ? c.e2 : e01) / c.s);
 }
 
-// The four map / argmax kernels.  One workgroup = one tile of kSceneTile consecutive pixels of one scene-frame map (blockIdx.y = map
+// Per map of a launch of smg_scene_argmax_objects, as kernel arguments beside SceneAffine: the two mask terms that select the map's
+// heightmap pixels (an index into masks [n_masks][hm][hm] float64, -1 = no such term, both -1 = every pixel) and the group whose
+// result the map competes for.
+struct SceneSelect { int a[kSceneMaps], b[kSceneMaps], group[kSceneMaps]; };
+
+// Which of the 4 consecutive pixels i0 .. i0 + 3 mask `term` selects, OR-ed into s: a pixel is selected when its double is not
+// exactly 0 - the bit pattern without its sign is tested, so -0.0 does not select, a NaN does, and the value never enters any
+// arithmetic.  vec: two 16-byte loads (masks 16-byte aligned and hm^2 a multiple of 4, so the thread's 32 bytes are aligned and
+// inside the mask); else guarded 8-byte loads.
+__device__ __forceinline__ void scene_select4(const double* masks, int term, int npix, int i0, int vec, bool (&s)[4]) {
+    if (term < 0) return;
+    const unsigned long long* p = reinterpret_cast<const unsigned long long*>(masks) + (int64_t)term * npix + i0;
+    unsigned long long w[4] = {0ull, 0ull, 0ull, 0ull};
+    if (vec) {
+        const ulonglong2 lo = *reinterpret_cast<const ulonglong2*>(p), hi = *reinterpret_cast<const ulonglong2*>(p + 2);
+        w[0] = lo.x; w[1] = lo.y; w[2] = hi.x; w[3] = hi.y;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (i0 + k < npix) w[k] = p[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = s[k] || (w[k] << 1) != 0ull;
+}
+
+// The map / argmax kernels.  One workgroup = one tile of kSceneTile consecutive pixels of one scene-frame map (blockIdx.y = map
 // of this launch, `map_stride` floats apart in q).  The map's PLANES planes are staged in LDS (PLANES x OH x OW floats, dynamic; the
 // three logit planes of a class map lie OH * OW apart, so its map_stride is 3 OH OW), the matrix sits in registers, scene_point runs
 // once per pixel.  PLANES == 1: the value is the interpolated Q value, `cls` is not read.  PLANES == 3: P(class cls) of the softmax,
@@ -90,9 +116,15 @@ __device__ __forceinline__ float scene_class_prob(const SceneClass c, int cls) {
 // [maps][3][hm][hm] - a thread's pixel group goes to three addresses hm^2 apart; an invalid pixel is -inf in every plane.
 // ARGMAX == true (cls in {0, 1, 2}): nothing is stored; the workgroup's best (value, index into [maps][hm][hm]) by argmax_better's
 // rules - invalid pixels are skipped, not compared - goes to slot blockIdx.y * gridDim.x + blockIdx.x of the partial arrays.
-template <int PLANES, bool ARGMAX>
+// SELECT (with ARGMAX; smg_scene_argmax_objects): the map only sees the pixels its two mask terms sel->a[m] / sel->b[m] select
+// (scene_select4, `mvec` = its 16-byte loads).  The masks are read BEFORE the geometry: a pixel that is not selected is skipped like
+// an invalid one and never enters the double-precision chain - objects are compact, so whole waves skip it.  A workgroup without a
+// selected valid pixel leaves an empty slot (index 0x7fffffff).
+template <int PLANES, bool ARGMAX, bool SELECT = false>
 __device__ __forceinline__ void scene_walk(const float* q, int64_t map_stride, int map0, const SceneAffine& aff, const SceneGeo& g, int cls,
-                                           float* out, int vec4, float* part_val, int* part_idx) {
+                                           float* out, int vec4, float* part_val, int* part_idx,
+                                           const SceneSelect* sel = nullptr, const double* masks = nullptr, int mvec = 0) {
+    static_assert(ARGMAX || !SELECT, "the selected walk is an argmax");
     extern __shared__ float sq[];
     __shared__ float bv[256];
     __shared__ int bi[256];
@@ -111,13 +143,22 @@ __device__ __forceinline__ void scene_walk(const float* q, int64_t map_stride, i
         if (i0 >= npix) break;
         int iy = i0 / g.hm, ix = i0 - iy * g.hm;
         float v[PLANES][4];
+        bool s[4] = {true, true, true, true};
+        if constexpr (SELECT) {
+            const int ta = sel->a[m], tb = sel->b[m];
+            if (ta >= 0 || tb >= 0) {
+                s[0] = s[1] = s[2] = s[3] = false;
+                scene_select4(masks, ta, npix, i0, mvec, s);
+                scene_select4(masks, tb, npix, i0, mvec, s);
+            }
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k, ++ix) {
             const int i = i0 + k;
             if (ix == g.hm) { ix = 0; ++iy; }
 #pragma unroll
             for (int c = 0; c < PLANES; ++c) v[c][k] = -INFINITY;
-            if (i < npix) {
+            if (i < npix && (!SELECT || s[k])) {
                 const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
                 if (p.valid) {
                     if constexpr (PLANES == 1) v[0][k] = (float)scene_interp(p, sq, g.OW);
@@ -167,6 +208,12 @@ static __global__ __launch_bounds__(256) void scene_class_argmax_kernel(const fl
     scene_walk<3, true>(q, map_stride, map0, aff, g, cls, nullptr, 0, part_val, part_idx);
 }
 
+static __global__ __launch_bounds__(256) void scene_argmax_objects_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                          const SceneSelect sel, const SceneGeo g, const double* masks, int mvec,
+                                                                          float* part_val, int* part_idx) {
+    scene_walk<1, true, true>(q, map_stride, map0, aff, g, 0, nullptr, 0, part_val, part_idx, &sel, masks, mvec);
+}
+
 // The second launch of smg_scene_argmax / smg_scene_class_argmax: one workgroup reduces the n partials (thread t takes slots t,
 // t + 256, ... in that order) and, with `carry`, the result a previous group of maps left in the outputs.  Empty slots hold index
 // 0x7fffffff; when nothing at all was valid the result is index -1, value -inf.
@@ -184,6 +231,27 @@ static __global__ __launch_bounds__(256) void scene_argmax_reduce_kernel(const f
     bv[t] = best; bi[t] = at;
     block_argmax(bv, bi, t);
     if (t == 0) { *idx_out = bi[0] == 0x7fffffff ? -1 : bi[0]; *val_out = bv[0]; }
+}
+
+// The grouped form, the second launch of smg_scene_argmax_objects: one workgroup per group (blockIdx.x) scans the slots of this
+// launch's `n_maps` maps (`tiles` slots each, map-major) whose map belongs to its group - thread t takes slots t, t + 256, ... in that
+// order - and, with `carry`, the result an earlier launch of maps left in the group's outputs.  Every group's pair is written: a
+// group without a map in any launch, or without a selected valid pixel, ends at index -1, value -inf.
+static __global__ __launch_bounds__(256) void scene_argmax_group_reduce_kernel(const float* part_val, const int* part_idx, int tiles, int n_maps,
+                                                                               const SceneSelect sel, int carry, int* idx_out, float* val_out) {
+    __shared__ float bv[256];
+    __shared__ int bi[256];
+    const int t = threadIdx.x, grp = blockIdx.x;
+    float best = -INFINITY; int at = 0x7fffffff;
+    if (t == 0 && carry && idx_out[grp] >= 0) { best = val_out[grp]; at = idx_out[grp]; }
+    for (int i = t; i < tiles * n_maps; i += 256) {
+        if (sel.group[i / tiles] != grp) continue;
+        const float x = part_val[i]; const int j = part_idx[i];
+        if (j != 0x7fffffff && argmax_better(x, j, best, at)) { best = x; at = j; }
+    }
+    bv[t] = best; bi[t] = at;
+    block_argmax(bv, bi, t);
+    if (t == 0) { idx_out[grp] = bi[0] == 0x7fffffff ? -1 : bi[0]; val_out[grp] = bv[0]; }
 }
 
 // ---- the two losses: what one labelled point contributes, each written once ----

@@ -56,8 +56,9 @@ def lib():
     L.smg_version.restype = C.c_int
     if not hasattr(L, "smg_abi_struct_bytes") or L.smg_version() != ABI_VERSION:
         raise SmgError("%s is ABI version %d, this binding needs %d: rebuild it (make -C csrc)" % (LIB_PATH, L.smg_version(), ABI_VERSION))
-    if not hasattr(L, "smg_loss_scene_map_ce"):       # (added without a version step: a version-9 library built before it lacks the symbol)
-        raise SmgError("%s is ABI version %d but lacks smg_loss_scene_map_ce, a stale build: rebuild it (make -C csrc)" % (LIB_PATH, ABI_VERSION))
+    for added in ("smg_loss_scene_map_ce", "smg_scene_argmax_objects"):       # (added without a version step: a version-9 library built before them lacks the symbol)
+        if not hasattr(L, added):
+            raise SmgError("%s is ABI version %d but lacks %s, a stale build: rebuild it (make -C csrc)" % (LIB_PATH, ABI_VERSION, added))
     L.smg_abi_struct_bytes.argtypes = [C.c_int]
     for which, ty in ((0, SmgBatch), (1, SmgNet), (2, SmgAdam)):
         if L.smg_abi_struct_bytes(which) != C.sizeof(ty):
@@ -82,6 +83,8 @@ def lib():
     L.smg_loss_map_ce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_scene_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]
     L.smg_scene_argmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smg_scene_argmax_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -120,7 +123,7 @@ EXPORTS = (
     "smg_last_error", "smg_version", "smg_abi_struct_bytes", "smg_engine_set_option", "smg_layout_count", "smg_layout_param_floats", "smg_layout_buffer_floats",
     "smg_layout_nbt_count", "smg_layout_entry", "smg_layout_trunk_range", "smg_layout_head_range",
     "smg_engine_create", "smg_engine_destroy", "smg_engine_workspace_bytes", "smg_engine_geometry",
-    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_argmax", "smg_loss_scene", "smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_argmax", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
+    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_loss_scene","smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_argmax", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
     "smg_profile_enable", "smg_profile_kinds", "smg_profile_kind_name", "smg_profile_read", "smg_profile_read_bytes",
 )
 
@@ -283,6 +286,23 @@ class Engine(object):
         """smg_scene_argmax: the best valid (map, iy, ix) of those scene-frame maps as a flattened index, without writing them."""
         a, p = self._affines(affine, n_maps)
         check(lib().smg_scene_argmax(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), idx_out, val_out, stream))
+
+    def scene_argmax_objects(self, q, map_stride, n_maps, affine, hm_size, masks, n_masks, mask_a, mask_b, groups, n_groups,
+                             idx_out, val_out, stream):
+        """smg_scene_argmax_objects: scene_argmax per group of maps, every map on the heightmap pixels its masks select - `masks`
+        the device float64 [n_masks, hm_size, hm_size] tensor of the forward, `mask_a` / `mask_b` / `groups` host sequences of
+        n_maps ints (mask index or -1; group in [0, n_groups)).  idx_out int32[n_groups] = flattened index into [n_maps, hm, hm]
+        or -1, val_out float32[n_groups]."""
+        a, p = self._affines(affine, n_maps)
+        sel = []
+        for name, seq in (("mask_a", mask_a), ("mask_b", mask_b), ("groups", groups)):
+            arr = np.ascontiguousarray(seq, dtype=np.int32).reshape(-1)
+            if arr.size != n_maps:
+                raise ValueError("%s: need one int per map, got %d for %d maps" % (name, arr.size, n_maps))
+            sel.append(arr)
+        ma, mb, gr = (s.ctypes.data_as(C.POINTER(C.c_int)) for s in sel)
+        check(lib().smg_scene_argmax_objects(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), masks, int(n_masks), ma, mb, gr,
+                                             int(n_groups), idx_out, val_out, stream))
 
     def loss_scene(self, q, affine, hm_size, n_pairs, K, pixels, labels, weights, loss_out, dq_out, stream):
         """smg_loss_scene: the weighted Huber on K heightmap pixels (int32 [n_pairs, K, 2] = iy, ix) per pair, dq on the map;

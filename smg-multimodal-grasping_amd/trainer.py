@@ -218,6 +218,22 @@ class Trainer(object):
             raise ValueError("mask_depth must be [n_objects, H, H] like the heightmap")
         return d, m
 
+    def _object_maps(self, what, depth_heightmap, mask_depth, style, is_target):
+        """The one engine call behind forward_objects and forward_objects_dense, with its BN sequence:
+        -> (model, q [n * R, 1, OH, OW] object-major, the masks on the device, n, R)."""
+        if self.method != 'reinforcement' or style not in (0, 1):
+            raise ValueError("%s: reinforcement styles 0 (grasp) and 1 (suction)" % what)
+        model = self.model_target if is_target else self.model
+        d, m = self._objects_on_device(model, depth_heightmap, mask_depth)
+        n = int(m.shape[0])
+        R = model.gnum_rotations if style == 0 else model.snum_rotations
+        pairs = [(r, k) for k in range(n) for r in range(R)]
+        seq_t = [v for k in range(n) for r in range(R) for v in (r, R + k)]       # trunk(rot r), trunk(mask k) per sample
+        q = model.run_pairs(style, R, d, list(range(R)), [0] * n, pairs, self.image_mean, self.image_std,
+                            bn_seq_trunk=seq_t, bn_seq_head=list(range(len(pairs))),
+                            masks=m, mask_a=list(range(n)), mask_b=[-1] * n)
+        return model, q, m, n, R
+
     def forward_objects(self, depth_heightmap, mask_depth, style=0, is_target=False, return_device=False):
         """All objects of one scene in ONE engine call - the loop of code/main.py:158-166:
 
@@ -229,40 +245,40 @@ class Trainer(object):
         on the device by the input kernel (the host ships the heightmap and the masks once).  BN
         running statistics are updated in the reference's order and count.
         Returns conf[n_objects, R] float64 (styles 0 / 1), or the device tensor [n*R] if asked."""
-        if self.method != 'reinforcement' or style not in (0, 1):
-            raise ValueError("forward_objects: reinforcement styles 0 (grasp) and 1 (suction)")
-        model = self.model_target if is_target else self.model
-        d, m = self._objects_on_device(model, depth_heightmap, mask_depth)
-        n = int(m.shape[0])
-        R = model.gnum_rotations if style == 0 else model.snum_rotations
-        pairs = [(r, k) for k in range(n) for r in range(R)]
-        seq_t = [v for k in range(n) for r in range(R) for v in (r, R + k)]       # trunk(rot r), trunk(mask k) per sample
-        q = model.run_pairs(style, R, d, list(range(R)), [0] * n, pairs, self.image_mean, self.image_std,
-                            bn_seq_trunk=seq_t, bn_seq_head=list(range(len(pairs))),
-                            masks=m, mask_a=list(range(n)), mask_b=[-1] * n)
+        _, q, _, n, R = self._object_maps("forward_objects", depth_heightmap, mask_depth, style, is_target)
         if q.shape[2] * q.shape[3] != 1:
             raise NotImplementedError("dense Q maps")
         if return_device:
             return q.reshape(-1)
         return q.reshape(n, R).cpu().numpy().astype(np.float64)
 
-    def forward_object_pairs(self, depth_heightmap, mask_depth, is_target=False, return_device=False):
-        """The enveloping-then-sucking loop of code/main.py:183-192 in one engine call: for every
-        unordered object pair (g < s) the mask is mask[g] + mask[s] (summed and applied on the device),
-        style 2, rotation 0.  Returns gs_conf[n, n] with -100 where the reference leaves its fill value
-        (main.py:184), or (device tensor of the pair values, [(g, s)]) if asked."""
+    def _object_pair_maps(self, depth_heightmap, mask_depth, is_target):
+        """The one engine call behind forward_object_pairs and forward_object_pairs_dense, with its BN sequence: style 2, rotation
+        0, the mask of pair (g < s) = mask[g] + mask[s] -> (model, q [n_pairs, 1, OH, OW], the masks on the device, [(g, s)]); q
+        and the masks are None without a pair (nothing runs)."""
         model = self.model_target if is_target else self.model
         n = int(np.asarray(mask_depth).shape[0])
-        gs = np.full((n, n), -100.0)
         idx = [(g, s) for g in range(n) for s in range(g + 1, n)]
         if not idx:
-            return (None, idx) if return_device else gs
+            return model, None, None, idx
         d, m = self._objects_on_device(model, depth_heightmap, mask_depth)
         pairs = [(0, k) for k in range(len(idx))]
         seq_t = [v for k in range(len(idx)) for v in (0, 1 + k)]
         q = model.run_pairs(2, model.gnum_rotations, d, [0], [0] * len(idx), pairs, self.image_mean, self.image_std,
                             bn_seq_trunk=seq_t, bn_seq_head=list(range(len(idx))),
                             masks=m, mask_a=[g for g, _ in idx], mask_b=[s_ for _, s_ in idx])
+        return model, q, m, idx
+
+    def forward_object_pairs(self, depth_heightmap, mask_depth, is_target=False, return_device=False):
+        """The enveloping-then-sucking loop of code/main.py:183-192 in one engine call: for every
+        unordered object pair (g < s) the mask is mask[g] + mask[s] (summed and applied on the device),
+        style 2, rotation 0.  Returns gs_conf[n, n] with -100 where the reference leaves its fill value
+        (main.py:184), or (device tensor of the pair values, [(g, s)]) if asked."""
+        n = int(np.asarray(mask_depth).shape[0])
+        gs = np.full((n, n), -100.0)
+        _, q, _, idx = self._object_pair_maps(depth_heightmap, mask_depth, is_target)
+        if not idx:
+            return (None, idx) if return_device else gs
         if return_device:
             return q.reshape(-1), idx
         vals = q.reshape(-1).cpu().numpy().astype(np.float64)
@@ -653,6 +669,96 @@ class Trainer(object):
         rots = self._scene_rotations(model, style, -1)
         eng, aff, hm, stream = self._scene_call(model, q, depth_heightmap, rots)
         return self._best_scene(q, hm, rots, lambda idx, val: eng.scene_argmax(q.data_ptr(), OH * OW, R, aff, hm, idx, val, stream))
+
+    def forward_objects_dense(self, depth_heightmap, mask_depth, style=0, is_target=False, return_device=False):
+        """forward_objects on a heightmap larger than 224^2: its one engine call, with its BN sequence, and the whole Q map of every
+        (object, rotation) kept - float64 [n_objects, R, OH, OW], or the float32 device tensor of that shape if asked.  The maps
+        are in the rotated frame of their rotation, like forward_dense's."""
+        self._require_scene("forward_objects_dense", depth_heightmap)
+        _, q, _, n, R = self._object_maps("forward_objects_dense", depth_heightmap, mask_depth, style, is_target)
+        q = q.reshape(n, R, q.shape[2], q.shape[3])
+        return q if return_device else q.cpu().numpy().astype(np.float64)
+
+    def forward_object_pairs_dense(self, depth_heightmap, mask_depth, is_target=False, return_device=False):
+        """forward_object_pairs on a heightmap larger than 224^2: its one engine call, with its BN sequence, and the style-2 map of
+        every object pair kept.  Returns (maps float64 [n_pairs, OH, OW] - or the float32 device tensor -, [(g, s)]); with fewer
+        than two objects nothing runs and the maps are [0, OH, OW]."""
+        _, _, side = self._require_scene("forward_object_pairs_dense", depth_heightmap)
+        model, q, _, idx = self._object_pair_maps(depth_heightmap, mask_depth, is_target)
+        if q is None:
+            dev = model._flat_params.device
+            q = torch.empty((0, side, side), dtype=torch.float32, device=dev if return_device else "cpu")
+        else:
+            q = q.reshape(len(idx), q.shape[2], q.shape[3])
+        return (q if return_device else q.cpu().numpy().astype(np.float64)), idx
+
+    def best_scene_actions(self, depth_heightmap, mask_depth, is_ets=True, is_target=False):
+        """best_actions in the SCENE frame, for a heightmap larger than 224^2 - the whole per-step evaluation of code/main.py:158-195
+        with every object's Q maps rotated back onto the heightmap and read on that object's OWN pixels (mask_depth[k] != 0; for
+        the enveloping-then-sucking pair (g, s) the pixels of either object).  One engine forward per primitive and one
+        smg_scene_argmax_objects on the masks tensor that forward used: per object (per pair) the best selected pixel with a window
+        of the head over all its rotations, found on the device without writing the n * R scene-frame maps; the host reads back one
+        (index, value) pair per object and primitive.  The overall best of a primitive is np.argmax over the objects' values (the
+        first NaN wins, then the largest value, the lowest object on ties).
+        Returns bestg_id / bests_id = (object, rotation), bestg_pixel / bests_pixel = (iy, ix), bestg_conf / bests_conf - None ids
+        and pixels and -inf when no object has a selected pixel with a window -; bestgs_num = (g, s), bestgs_pixel, bestgs_conf
+        (None / None / 0 with fewer than two objects or is_ets False, as in best_actions); per_object = {"grasp": [...],
+        "suction": [...]}, one (rotation, (iy, ix), conf) per object or None.  is_target evaluates the target net (the future
+        reward of get_label_value in this frame)."""
+        self._require_scene("best_scene_actions", depth_heightmap)
+        n = int(np.asarray(mask_depth).shape[0])
+        if n < 1:
+            raise ValueError("best_scene_actions: mask_depth holds no object")
+        hm = int(np.shape(depth_heightmap)[-1])
+        n_pairs = n * (n - 1) // 2 if is_ets else 0
+        idx = val = None
+        calls, kept = [], {}              # per primitive: (offset into idx / val, groups, maps per group)
+        for style, name in ((0, "grasp"), (1, "suction"), (2, "pairs")):
+            if style == 2:
+                if not n_pairs:
+                    break
+                model, q, m, pair_list = self._object_pair_maps(depth_heightmap, mask_depth, is_target)
+                groups, per = len(pair_list), 1
+                rots = [(0, model.gnum_rotations)] * groups
+                mask_a, mask_b = [g for g, _ in pair_list], [s_ for _, s_ in pair_list]
+            else:
+                model, q, m, groups, per = self._object_maps("best_scene_actions", depth_heightmap, mask_depth, style, is_target)
+                rots = [(r, per) for k in range(groups) for r in range(per)]
+                mask_a, mask_b = [k for k in range(groups) for r in range(per)], [-1] * (groups * per)
+            if idx is None:
+                idx = torch.empty(2 * n + n_pairs, dtype=torch.int32, device=q.device)
+                val = torch.empty(2 * n + n_pairs, dtype=torch.float32, device=q.device)
+            off = sum(c[1] for c in calls)
+            eng, aff, _, stream = self._scene_call(model, q, depth_heightmap, rots)
+            eng.scene_argmax_objects(q.data_ptr(), q.shape[2] * q.shape[3], len(rots), aff, hm, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
+                                     [j // per for j in range(len(rots))], groups, idx[off:].data_ptr(), val[off:].data_ptr(), stream)
+            calls.append((off, groups, per))
+            kept[name] = q
+        self._last_object_q = kept        # the maps behind the result, object-major: "grasp" / "suction" [n * R, 1, OH, OW], "pairs" [n_pairs, 1, OH, OW]
+        i_all, v_all = idx.cpu().numpy(), val.cpu().numpy().astype(np.float64)
+
+        def decode(off, groups, per):
+            """Per group (rotation, (iy, ix), conf) or None, and the overall best group or None."""
+            entries = []
+            for k in range(groups):
+                i = int(i_all[off + k])
+                entries.append(None if i < 0 else ((i // (hm * hm)) % per, ((i // hm) % hm, i % hm), v_all[off + k]))
+            have = [k for k in range(groups) if entries[k] is not None]
+            return entries, (have[int(np.argmax([entries[k][2] for k in have]))] if have else None)
+        out = {"per_object": {}}
+        for (off, groups, per), name, key in zip(calls, ("grasp", "suction"), ("bestg", "bests")):
+            entries, best = decode(off, groups, per)
+            out["per_object"][name] = entries
+            out[key + "_id"] = None if best is None else (best, entries[best][0])
+            out[key + "_pixel"] = None if best is None else entries[best][1]
+            out[key + "_conf"] = -np.inf if best is None else entries[best][2]
+        out.update(bestgs_num=None, bestgs_pixel=None, bestgs_conf=0)
+        if len(calls) == 3:
+            entries, best = decode(*calls[2])
+            out["bestgs_conf"] = -np.inf
+            if best is not None:
+                out.update(bestgs_num=pair_list[best], bestgs_pixel=entries[best][1], bestgs_conf=entries[best][2])
+        return out
 
     @staticmethod
     def _scene_pixel_args(pixels, n, hm, labels, weights=None, class_labels=False):
