@@ -50,14 +50,16 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
     // 7.23-7.29 ms).  With 17 streams the side stream has no slack on those planes: the same move costs the headline step 0.15 ms
     // (16.44-16.50 -> 16.62-16.64 ms, alternating on one box), and on the big planes the two strided slice reads cost more than the launch.
     auto gs_on_side = [&](const Plane& pl) { return split16 && !e->generic3x3 && pl.HW <= 1600 && NS <= 4; };
-    auto launch_gs_apply = [&](int b, int i, hipStream_t cs, float* GSb) {
+    // The G' / X slices of dense layer d's 32 output channels with the BN backward applied on load: what the 3x3 kernels read in
+    // the fused form, and what launch_gs_apply materialises (that one from the forward's table instead of the fp64 sums)
+    auto fused_gsrc = [&](int b, const DenseLayerRef& d) {
+        return grad_src(e, e->G[b], kBlockCtot[b], e->X[b], kBlockCtot[b], e->st_X[b], d.cin, nullptr);
+    };
+    auto launch_gs_apply = [&](int b, int i, hipStream_t cs, float* GSb, const GradSrc& fused) {
         const Plane pl = e->p_blk[b];
-        const int Ct = kBlockCtot[b];
-        const DenseLayerRef& d = T.layers[b][i];
         BnBwdApplyArgs a{};
-        a.g = e->G[b]; a.ldg = Ct; a.gcoff = d.cin; a.x = e->X[b]; a.ldx = Ct; a.xcoff = d.cin; a.pl = pl; a.C = kGrowth;
-        a.xsum = fsum(e, e->st_X[b]); a.xsq = fsq(e, e->st_X[b]); a.xstride = Ct; a.xtab = stat_table(e, e->sx_tab[b], e->max_streams, Ct);
-        a.s1 = b1(e, e->st_X[b]); a.s2 = b2(e, e->st_X[b]); a.sstride = Ct; a.scoff = d.cin; a.gamma = nullptr; a.eps = kEps;
+        a.src = fused; a.src.xtab = stat_table(e, e->sx_tab[b], e->max_streams, kBlockCtot[b], T.layers[b][i].cin);
+        a.pl = pl; a.C = kGrowth;
         a.out = GSb; a.ldo = kGrowth; a.amax = split16 ? gamax_of(e, b, i, 0) : nullptr;
         PREC_DISPATCH(e, launch_kernel(e, bn_bwd_apply_kernel<PREC>, dim3((pl.HWp + bn_apply_rows(PREC) - 1) / bn_apply_rows(PREC), NS), dim3(256), 0, cs,
                                        K_OTHER, 0, ESZ(e) * NS * pl.HW * 3 * kGrowth, false, a));
@@ -95,12 +97,11 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
     }
     int chunk4, cps4;
     pick_chunk(p4, NP, 2 * kFeat / 64, chunk4, cps4);
+    const GradSrc dh1 = grad_src(e, e->DH1, kHeadMid, e->H1, kHeadMid, e->st_H1, 0, P + Hd.n1.w);      // dy1 through norm1: both conv0 gradients read it
     {   // head conv0 weight gradient
         auto go = [&](auto ptag) -> int {
         BwdWeightP<CfgW64x64, W_ONE, C_IDENT, kPdWgrad, true, decltype(ptag)::value, true> p{};      // fp32 head buffers in every mode
-        p.gbuf = e->DH1; p.ldg = kHeadMid; p.gcoff = 0; p.xbuf = e->H1; p.ldx = kHeadMid; p.xcoff = 0; p.pa = p4; p.MA = kHeadMid;
-        p.xsum = fsum(e, e->st_H1); p.xsq = fsq(e, e->st_H1); p.xstride = kHeadMid;
-        p.s1 = b1(e, e->st_H1); p.s2 = b2(e, e->st_H1); p.sstride = kHeadMid; p.scoff = 0; p.agamma = P + Hd.n1.w;
+        p.gs = dh1; p.pa = p4; p.MA = kHeadMid;
         p.bbuf = e->F; p.ldb = 2 * kFeat; p.pb = p4; p.NB = 2 * kFeat;
         p.bsum = fsum(e, e->st_F); p.bsq = fsq(e, e->st_F); p.bstride = 2 * kFeat; p.bgamma = P + Hd.n0.w; p.bbeta = P + Hd.n0.b;
         p.eps = kEps; p.chunk = chunk4; p.chunks_per_stream = cps4; p.n_chunks = NP * cps4;
@@ -116,9 +117,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         auto run = [&](auto tag, auto ptag) {
                 using Cfg = decltype(tag);
                 BwdDataP<Cfg, false, E_STORE, true, decltype(ptag)::value, true> p{};      // fp32 head buffers in every mode
-        p.gbuf = e->DH1; p.ldg = kHeadMid; p.gcoff = 0; p.xbuf = e->H1; p.ldx = kHeadMid; p.xcoff = 0; p.pa = p4; p.KA = kHeadMid;
-        p.xsum = fsum(e, e->st_H1); p.xsq = fsq(e, e->st_H1); p.xstride = kHeadMid;
-        p.s1 = b1(e, e->st_H1); p.s2 = b2(e, e->st_H1); p.sstride = kHeadMid; p.scoff = 0; p.agamma = P + Hd.n1.w;
+        p.gs = dh1; p.pa = p4; p.KA = kHeadMid;
         p.wp = e->packed_u + e->pk_hd0; p.K8tot = kHeadMid / 8; p.ldn = 2 * kFeat; p.wcol0 = 0; p.N = 2 * kFeat;
         p.mbuf = e->F; p.ldm = 2 * kFeat; p.mcoff = 0; p.pm = p4;
         p.msum = fsum(e, e->st_F); p.msq = fsq(e, e->st_F); p.mstride = 2 * kFeat; p.egamma = P + Hd.n0.w; p.ebeta = P + Hd.n0.b;
@@ -132,8 +131,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
     }
     {   // head norm0 backward + concat backward + norm5 backward -> G'_4
         Norm5BwdArgs a;
-        a.DF = e->DF; a.F = e->F; a.p4 = p4; a.fsum = fsum(e, e->st_F); a.fsq = fsq(e, e->st_F);
-        a.f1 = b1(e, e->st_F); a.f2 = b2(e, e->st_F); a.hgamma = P + Hd.n0.w;
+        a.df = grad_src(e, e->DF, 2 * kFeat, e->F, 2 * kFeat, e->st_F, 0, P + Hd.n0.w); a.p4 = p4;
         a.x4 = e->X[3]; a.xsum = fsum(e, e->st_X[3]); a.xsq = fsq(e, e->st_X[3]); a.gamma5 = P + T.norm5.w; a.eps = kEps;
         a.user_ptr = e->d_user_ptr; a.user_pair = e->d_user_pair; a.user_slot = e->d_user_slot;
         a.G4 = e->G[3]; a.SA = b1(e, e->st_X[3]); a.SB = b2(e, e->st_X[3]);
@@ -153,15 +151,6 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         const int r = ring_pos(b, i);
         return LayerBuf{e->GS[r % kRing], e->D2[r % kRing], e->D2S[r % kRing], r};
     };
-    // The form that applies the BN backward while loading the G' / X slices of dense layer d's 32 output channels
-    auto fused_gsrc = [&](int b, const DenseLayerRef& d) {
-        const int Ct = kBlockCtot[b];
-        GradSrc g{};
-        g.g = el(e, e->G[b], d.cin); g.ldg = Ct; g.x = el(e, e->X[b], d.cin); g.ldx = Ct;
-        g.xsum = fsum(e, e->st_X[b]) + d.cin; g.xsq = fsq(e, e->st_X[b]) + d.cin;
-        g.s1 = b1(e, e->st_X[b]) + d.cin; g.s2 = b2(e, e->st_X[b]) + d.cin; g.sstride = Ct; g.eps = kEps;
-        return g;
-    };
     // The two weight gradients of dense layer (b, i) and their reduce launches, on the side stream (which must already wait for the
     // layer's D2 / GS).
     auto issue_wgrads = [&](int b, int i) -> int {
@@ -171,10 +160,9 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         float* bt = el(e, e->Bt, e->bt_off[b][i]);
         const LayerBuf lb = buf_of(b, i);
         const WgradPlan w = plan_layer_wgrads(pl, d.cin, NS, e->prec, split16, e->deterministic, e->part_floats, e->generic3x3, e->generic_w1);
-        GradSrc gsrc{};
-        if (gs_on_side(pl)) launch_gs_apply(b, i, s2, lb.GS);
-        if (gs_materialised) { gsrc.g = lb.GS; gsrc.ldg = kGrowth; gsrc.amax = gamax_of(e, b, i, 0); }
-        else gsrc = fused_gsrc(b, d);
+        GradSrc gsrc = fused_gsrc(b, d);
+        if (gs_on_side(pl)) launch_gs_apply(b, i, s2, lb.GS, gsrc);
+        if (gs_materialised) gsrc = grad_done(lb.GS, kGrowth, gamax_of(e, b, i, 0));
         if (!e->generic3x3) {
             // conv2 weight gradient with the activation halo resident in LDS (halo.cuh)
             const bool w1_partial = w1_partial_tiles(pl, NS, e->deterministic);
@@ -201,7 +189,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             int chunk, cps;
             pick_chunk(pl, NS, 9, chunk, cps);      // (9 workgroups per chunk: one per tap)
             BwdWeightP<CfgW32x128, W_THREE, C_3x3, kPdWgrad, false> p{};
-            p.gbuf = lb.GS; p.ldg = kGrowth; p.gcoff = 0; p.xbuf = nullptr; p.pa = pl; p.MA = kGrowth;
+            p.gs = grad_done(lb.GS, kGrowth); p.pa = pl; p.MA = kGrowth;
             p.bbuf = bt; p.ldb = kBottleneck; p.pb = pl; p.NB = kBottleneck;
             p.bsum = fsum(e, e->st_Bt[b][i]); p.bsq = fsq(e, e->st_Bt[b][i]); p.bstride = kBottleneck;
             p.bgamma = P + d.n2.w; p.bbeta = P + d.n2.b; p.eps = kEps;
@@ -234,7 +222,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             static_assert(Cfg::BN == kW1TileN, "plan_layer_wgrads counts this kernel's column tiles");
             auto go = [&](auto ptag) -> int {
                 BwdWeightP<MC<Cfg, decltype(ptag)::value>, W_ONE, C_IDENT, kPdWgrad, false, decltype(ptag)::value> p{};
-                p.gbuf = lb.D2; p.ldg = kBottleneck; p.gcoff = 0; p.xbuf = nullptr; p.pa = pl; p.MA = kBottleneck; p.binv = lb.D2S; p.basc = asc_n1(e, b, i);
+                p.gs = grad_done(lb.D2, kBottleneck); p.pa = pl; p.MA = kBottleneck; p.binv = lb.D2S; p.basc = asc_n1(e, b, i);
                 p.bbuf = e->X[b]; p.ldb = Ct; p.pb = pl; p.NB = d.cin;
                 p.bsum = fsum(e, e->st_X[b]); p.bsq = fsq(e, e->st_X[b]); p.bstride = Ct; p.btab = stat_table(e, e->sx_tab[b], e->max_streams, Ct);
                 p.bgamma = P + d.n1.w; p.bbeta = P + d.n1.b; p.eps = kEps;
@@ -297,8 +285,8 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             // many-stream batches - two strided 128-B-per-pixel reads replace one dense one in both consumers.
             GradSrc gsrc = fused_gsrc(b, d);
             if (e->generic3x3 || (gs_materialised && !gs_on_side(pl))) {
-                launch_gs_apply(b, i, st, GSb);
-                if (gs_materialised) { gsrc = GradSrc{}; gsrc.g = GSb; gsrc.ldg = kGrowth; gsrc.amax = gamax_of(e, b, i, 0); }
+                launch_gs_apply(b, i, st, GSb, gsrc);
+                if (gs_materialised) gsrc = grad_done(GSb, kGrowth, gamax_of(e, b, i, 0));
             }
             if (!e->generic3x3) {
                 // conv2 (3x3) data gradient with the gradient halo resident in LDS (halo.cuh)
@@ -328,7 +316,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 auto run = [&](auto tag) {
                     using Cfg = decltype(tag);
                     BwdDataP<Cfg, true, E_STORE, false> p{};
-                    p.gbuf = GSb; p.ldg = kGrowth; p.gcoff = 0; p.xbuf = nullptr; p.pa = pl; p.KA = kGrowth;
+                    p.gs = grad_done(GSb, kGrowth); p.pa = pl; p.KA = kGrowth;
                     p.wp = e->packed_u + e->pk_g3d[b][i]; p.K8tot = 9 * kGrowth / 8; p.ldn = kBottleneck; p.wcol0 = 0; p.N = kBottleneck;
                     p.mbuf = bt; p.ldm = kBottleneck; p.mcoff = 0; p.pm = pl;
                     p.msum = fsum(e, e->st_Bt[b][i]); p.msq = fsq(e, e->st_Bt[b][i]); p.mstride = kBottleneck;
@@ -341,20 +329,17 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 };
                 if (pl.HWp % 128 == 0) run(CfgP128x128{}); else run(CfgP64x128{});
             }
+            // dy through norm2 (the generic 3x3 path leaves no table of the bottleneck: the fp64 sums)
+            const GradSrc dy2 = grad_src(e, split16 ? e->DY2 : D2b, kBottleneck, bt, kBottleneck, e->st_Bt[b][i], 0, P + d.n2.w,
+                                         !e->generic3x3 ? stat_table(e, e->sb_tab[b][i], e->max_streams, kBottleneck) : StatTab{});
             if (split16) {   // norm2 backward applied once: D2 (unit form, per-block scales) <- gamma2*invstd*(dy - s1/n - xhat*s2/n)
                 BnBwdApplySplitArgs a{};
-                a.g = e->DY2; a.x = bt; a.pl = pl;
-                a.xsum = fsum(e, e->st_Bt[b][i]); a.xsq = fsq(e, e->st_Bt[b][i]); a.xstride = kBottleneck; a.xtab = !e->generic3x3 ? stat_table(e, e->sb_tab[b][i], e->max_streams, kBottleneck) : StatTab{};
-                a.s1 = b1(e, e->st_Bt[b][i]); a.s2 = b2(e, e->st_Bt[b][i]); a.sstride = kBottleneck;
-                a.gamma = P + d.n2.w; a.eps = kEps; a.out = reinterpret_cast<u32x4*>(D2b); a.binv = lb.D2S;
+                a.src = dy2; a.pl = pl; a.out = reinterpret_cast<u32x4*>(D2b); a.binv = lb.D2S;
                 if (!e->generic3x3) { a.dbeta = Gr + d.n2.b; a.dgamma = Gr + d.n2.w; }   // the halo dgrad leaves these to us
                 launch_kernel(e, bn_bwd_apply_split_kernel, dim3(pl.HWp / kScaleBlock, NS), dim3(256), 0, st, K_OTHER, 0, 4.0 * NS * pl.HW * 3 * kBottleneck, false, a);
             } else {   // 16-bit modes: norm2 backward applied once, in place: D2 <- gamma2*invstd*(dy - s1/n - xhat*s2/n)
                 BnBwdApplyArgs a{};
-                a.g = D2b; a.ldg = kBottleneck; a.gcoff = 0; a.x = bt; a.ldx = kBottleneck; a.xcoff = 0; a.pl = pl; a.C = kBottleneck;
-                a.xsum = fsum(e, e->st_Bt[b][i]); a.xsq = fsq(e, e->st_Bt[b][i]); a.xstride = kBottleneck; a.xtab = !e->generic3x3 ? stat_table(e, e->sb_tab[b][i], e->max_streams, kBottleneck) : StatTab{};
-                a.s1 = b1(e, e->st_Bt[b][i]); a.s2 = b2(e, e->st_Bt[b][i]); a.sstride = kBottleneck; a.scoff = 0;
-                a.gamma = P + d.n2.w; a.eps = kEps; a.out = D2b; a.ldo = kBottleneck; a.amax = nullptr;
+                a.src = dy2; a.pl = pl; a.C = kBottleneck; a.out = D2b; a.ldo = kBottleneck;
                 if (!e->generic3x3) { a.dbeta = Gr + d.n2.b; a.dgamma = Gr + d.n2.w; }   // the halo dgrad leaves these to us
                 PREC_DISPATCH(e, launch_kernel(e, bn_bwd_apply_kernel<PREC>, dim3((pl.HWp + bn_apply_rows(PREC) - 1) / bn_apply_rows(PREC), NS), dim3(256), 0, st,
                                                K_OTHER, 0, ESZ(e) * NS * pl.HW * 3 * kBottleneck, false, a));
@@ -385,7 +370,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 auto run = [&](auto tag, auto ptag) {
                     using Cfg = MC<decltype(tag), decltype(ptag)::value>;
                     BwdDataP<Cfg, false, E_ACCUM, false, decltype(ptag)::value> p{};
-                    p.gbuf = D2b; p.ldg = kBottleneck; p.gcoff = 0; p.xbuf = nullptr; p.pa = pl; p.KA = kBottleneck; p.binv = lb.D2S;
+                    p.gs = grad_done(D2b, kBottleneck); p.pa = pl; p.KA = kBottleneck; p.binv = lb.D2S;
                     p.wp = e->packed_u + e->pk_d1[b][i]; p.K8tot = kBottleneck / 8; p.ldn = d.cin; p.wcol0 = cs; p.N = d.cin - cs;
                     p.mbuf = e->X[b]; p.ldm = Ct; p.mcoff = cs; p.pm = pl;
                     p.msum = fsum(e, e->st_X[b]); p.msq = fsq(e, e->st_X[b]); p.mstride = Ct; p.mtab = stat_table(e, e->sx_tab[b], e->max_streams, Ct);
@@ -429,14 +414,13 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         if (b > 0) {   // transition b-1: X[b-1] (all channels) -> X[b][:, 0:C0]
             const Plane pp = e->p_blk[b - 1];
             const int Cp = kBlockCtot[b - 1], C0 = kBlockCin[b];
+            const GradSrc gx = grad_src(e, e->G[b], Ct, e->X[b], Ct, e->st_X[b], 0, nullptr);      // the block's first C0 channels: both transition gradients read them
             {
                 int chunk, cps;
                 pick_chunk(pl, NS, (C0 / 128) * (Cp / 128), chunk, cps);
                 auto go = [&](auto ptag) -> int {
                 BwdWeightP<MC<CfgW128x128, decltype(ptag)::value>, W_POOL, C_IDENT, 1, true, decltype(ptag)::value> p{};      // (one k-tile in flight: the pooling fetch holds 4 float4 per slot, three tiles of them leave one workgroup per CU)
-                p.gbuf = e->G[b]; p.ldg = Ct; p.gcoff = 0; p.xbuf = e->X[b]; p.ldx = Ct; p.xcoff = 0; p.pa = pl; p.MA = C0;
-                p.xsum = fsum(e, e->st_X[b]); p.xsq = fsq(e, e->st_X[b]); p.xstride = Ct;
-                p.s1 = b1(e, e->st_X[b]); p.s2 = b2(e, e->st_X[b]); p.sstride = Ct; p.scoff = 0; p.agamma = nullptr;
+                p.gs = gx; p.pa = pl; p.MA = C0;
                 p.bbuf = e->X[b - 1]; p.ldb = Cp; p.pb = pp; p.NB = Cp;
                 p.bsum = fsum(e, e->st_X[b - 1]); p.bsq = fsq(e, e->st_X[b - 1]); p.bstride = Cp;
                 p.bgamma = P + T.tnorm[b - 1].w; p.bbeta = P + T.tnorm[b - 1].b; p.eps = kEps;
@@ -457,9 +441,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 auto run = [&](auto tag, auto ptag) {
                 using Cfg = MC<decltype(tag), decltype(ptag)::value>;
                 BwdDataP<Cfg, false, E_UNPOOL, true, decltype(ptag)::value> p{};
-                p.gbuf = e->G[b]; p.ldg = Ct; p.gcoff = 0; p.xbuf = e->X[b]; p.ldx = Ct; p.xcoff = 0; p.pa = pl; p.KA = C0;
-                p.xsum = fsum(e, e->st_X[b]); p.xsq = fsq(e, e->st_X[b]); p.xstride = Ct;
-                p.s1 = b1(e, e->st_X[b]); p.s2 = b2(e, e->st_X[b]); p.sstride = Ct; p.scoff = 0; p.agamma = nullptr;
+                p.gs = gx; p.pa = pl; p.KA = C0;
                 p.wp = e->packed_u + e->pk_td[b - 1]; p.K8tot = C0 / 8; p.ldn = Cp; p.wcol0 = 0; p.N = Cp;
                 p.mbuf = e->X[b - 1]; p.ldm = Cp; p.mcoff = 0; p.pm = pp;
                 p.msum = fsum(e, e->st_X[b - 1]); p.msq = fsq(e, e->st_X[b - 1]); p.mstride = Cp;
@@ -478,9 +460,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
     if (ph_b && pooled_tail) {   // pool0 / relu0 backward + norm0 sums + conv0 weight gradient from the pooled pixels
         const Plane p1 = e->p_blk[0];
         StemTailArgs a;
-        a.G1 = e->G[0]; a.X1 = e->X[0]; a.ld1 = kBlockCtot[0]; a.p1 = p1;
-        a.xsum = fsum(e, e->st_X[0]); a.xsq = fsq(e, e->st_X[0]); a.xstride = kBlockCtot[0];
-        a.SA = b1(e, e->st_X[0]); a.SB = b2(e, e->st_X[0]); a.sstride = kBlockCtot[0];
+        a.g1 = grad_src(e, e->G[0], kBlockCtot[0], e->X[0], kBlockCtot[0], e->st_X[0], 0, nullptr); a.p1 = p1;
         a.argmax = e->argmax; a.stemv = e->stemv;
         a.ssum = fsum(e, e->st_stem); a.ssq = fsq(e, e->st_stem); a.ps = e->p_stem;
         a.gamma = P + T.norm0.w; a.eps = kEps;
@@ -505,16 +485,14 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         if (fork(e->ev_misc)) return -5;
         launch_reduce2(e, s2, tiles.launched(at, reduce_chunk_major(a.part, Z, 1, 64, 49, 64, 64, Gr + T.conv0.w, 147, C_STEM1)));
         StemCombineArgs c;
-        c.mom = e->mom; c.w0 = P + T.conv0.w; c.ssum = a.ssum; c.ssq = a.ssq; c.s1 = a.o1; c.s2 = a.o2;
-        c.gamma = a.gamma; c.eps = kEps; c.HW = e->p_stem.HW; c.ns = NS; c.dw = Gr + T.conv0.w;
+        c.mom = e->mom; c.w0 = P + T.conv0.w; c.dy = grad_src(e, nullptr, 64, nullptr, 64, e->st_stem, 0, a.gamma);      // (neither dy0 nor the stem plane exists here)
+        c.HW = e->p_stem.HW; c.ns = NS; c.dw = Gr + T.conv0.w;
         launch_kernel(e, stem_combine_kernel, dim3(64), dim3(256), (size_t)(NS * kMomRows + 256) * sizeof(double), s2, K_OTHER, 0, 0, false, c);
     }
     if (ph_b && !pooled_tail) {
     {   // pool0 / relu0 backward + norm0 sums
         Pool0BwdArgs a;
-        a.G1 = e->G[0]; a.X1 = e->X[0]; a.ld1 = kBlockCtot[0]; a.p1 = e->p_blk[0];
-        a.xsum = fsum(e, e->st_X[0]); a.xsq = fsq(e, e->st_X[0]); a.xstride = kBlockCtot[0];
-        a.SA = b1(e, e->st_X[0]); a.SB = b2(e, e->st_X[0]); a.sstride = kBlockCtot[0];
+        a.g1 = grad_src(e, e->G[0], kBlockCtot[0], e->X[0], kBlockCtot[0], e->st_X[0], 0, nullptr); a.p1 = e->p_blk[0];
         a.argmax = e->argmax; a.stem = e->stem; a.ps = e->p_stem;
         a.ssum = fsum(e, e->st_stem); a.ssq = fsq(e, e->st_stem);
         a.gamma = P + T.norm0.w; a.beta = P + T.norm0.b; a.eps = kEps;
@@ -533,9 +511,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         constexpr int SM = decltype(mtag)::value;      // W_STEM (3-channel image, 196 columns) or W_STEM1 (one channel, 49 taps, replicated x3 at the flush)
         using WCfg = typename std::conditional<SM == W_STEM1, CfgW64x64, CfgW64x256>::type;
         BwdWeightP<WCfg, SM, SM == W_STEM1 ? C_STEM1 : C_STEM, kPdWgrad, true, decltype(ptag)::value> p{};      // (fp32 image / stem plane in every mode)
-        p.gbuf = e->DY0; p.ldg = 64; p.gcoff = 0; p.xbuf = e->stem; p.ldx = 64; p.xcoff = 0; p.pa = ps_; p.MA = 64;
-        p.xsum = fsum(e, e->st_stem); p.xsq = fsq(e, e->st_stem); p.xstride = 64;
-        p.s1 = b1(e, e->st_stem); p.s2 = b2(e, e->st_stem); p.sstride = 64; p.scoff = 0; p.agamma = P + T.norm0.w;
+        p.gs = grad_src(e, e->DY0, 64, e->stem, 64, e->st_stem, 0, P + T.norm0.w); p.pa = ps_; p.MA = 64;
         p.bbuf = e->img4; p.ldb = 4; p.pb = e->p_img; p.NB = SM == W_STEM1 ? 64 : 196;
         p.eps = kEps; p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
         p.dw = Gr + T.conv0.w; p.ldw_out = 147;

@@ -710,10 +710,7 @@ static __global__ __launch_bounds__(256) void value_wgrad_dense_kernel(const Val
 //   G'_4[s] = gamma5 * dy5,  SA/SB += gamma5 * sums,  dbeta5/dgamma5 += sums.
 // ------------------------------------------------------------------------------------
 struct Norm5BwdArgs {
-    const float* DF; const float* F; Plane p4;      // [pair][HWp][2048]
-    const double* fsum; const double* fsq;          // F statistics [pair][2048]
-    const double* f1; const double* f2;             // sums of dy0, dy0*xhat [pair][2048]
-    const float* hgamma;                            // head norm0 gamma [2048]
+    GradSrc df; Plane p4;                           // the head's gradient of F through norm0: fp32 [pair][HWp][2048], statistics [pair][2048]
     const void* x4; const double* xsum; const double* xsq;    // [n][HWp][1024] (activation storage), [n][1024]
     const float* gamma5; float eps;
     const int* user_ptr; const int* user_pair; const int* user_slot;  // CSR over streams
@@ -765,20 +762,18 @@ static __global__ __launch_bounds__(256) void norm5_bwd_kernel(const Norm5BwdArg
         float cf[16];   // a[4], q1[4], mean[4], k[4]
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            float mean, invstd;
-            bn_moments(a.fsum, a.fsq, (int64_t)j * 2048 + ch + c, inv, a.eps, mean, invstd);
-            const float q2 = (float)(stat_get(a.f2, (int64_t)j * 2048 + ch + c) * inv);
-            cf[c] = a.hgamma[ch + c] * invstd;
-            cf[4 + c] = (float)(stat_get(a.f1, (int64_t)j * 2048 + ch + c) * inv);
-            cf[8 + c] = mean;
-            cf[12 + c] = invstd * q2;
+            const GradCoef f = grad_src_coef(a.df, j, ch + c, inv);
+            cf[c] = f.a;
+            cf[4 + c] = f.q1;
+            cf[8 + c] = f.mean;
+            cf[12 + c] = f.k;
         }
 #pragma unroll
         for (int q = 0; q < CH; ++q) {
             const int p = p0 + q;
             if (p < p1) {
                 const int64_t fr = ((int64_t)j * a.p4.HWp + p) * 2048 + ch;
-                const float4 d = affine2(ld4(a.DF + fr), ld4(a.F + fr), cf, 4);
+                const float4 d = affine2(ld4(static_cast<const float*>(a.df.g) + fr), ld4(static_cast<const float*>(a.df.x) + fr), cf, 4);
                 const int64_t xr = ((int64_t)s * a.p4.HWp + p) * 1024 + c5;
                 const float4 xv = ldq<XT>(a.x4, xr);
                 const float dd[4] = {d.x, d.y, d.z, d.w}, xx[4] = {xv.x, xv.y, xv.z, xv.w};
@@ -833,9 +828,7 @@ static __global__ __launch_bounds__(256) void norm5_bwd_kernel(const Norm5BwdArg
 // the <= 4 pooled windows covering it and takes those whose argmax points at it.
 // ------------------------------------------------------------------------------------
 struct Pool0BwdArgs {
-    const void* G1; const void* X1; int ld1; Plane p1;       // block-1 buffers (gradient / activation storage of the mode)
-    const double* xsum; const double* xsq; int xstride;      // block-1 stats
-    const double* SA; const double* SB; int sstride;
+    GradSrc g1; Plane p1;                                    // block 1's G' / X, channels 0..63 (gradient / activation storage of the mode)
     const unsigned char* argmax;                             // [n][p1.HWp][64]
     const float* stem; Plane ps;                             // raw stem output [n][HWp][64]
     const double* ssum; const double* ssq;                   // [n][64]
@@ -867,11 +860,8 @@ static __global__ __launch_bounds__(256) void pool0_bwd_kernel(const Pool0BwdArg
         bn_moments(a.ssum, a.ssq, (int64_t)n * 64 + t, 1.0 / (double)a.ps.HW, a.eps, mean, invstd);
         prm[t] = a.gamma[t] * invstd; prm[64 + t] = a.beta[t]; prm[128 + t] = mean; prm[192 + t] = invstd;
         const double inv = 1.0 / (double)a.p1.HW;
-        float m1, i1;
-        bn_moments(a.xsum, a.xsq, (int64_t)n * a.xstride + t, inv, a.eps, m1, i1);
-        const float q1 = (float)(stat_get(a.SA, (int64_t)n * a.sstride + t) * inv);
-        const float q2 = (float)(stat_get(a.SB, (int64_t)n * a.sstride + t) * inv);
-        prm[256 + t] = i1; prm[320 + t] = q1; prm[384 + t] = m1; prm[448 + t] = i1 * q2;
+        const GradCoef f = grad_src_coef(a.g1, n, t, inv);
+        prm[256 + t] = f.a; prm[320 + t] = f.q1; prm[384 + t] = f.mean; prm[448 + t] = f.k;
     }
     float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
     const int tile0 = blockIdx.x * a.tiles_per_wg, tile1 = min(tile0 + a.tiles_per_wg, n_tiles);
@@ -899,8 +889,8 @@ static __global__ __launch_bounds__(256) void pool0_bwd_kernel(const Pool0BwdArg
         const int wy = wy0 + pp / 5, wx = wx0 + pp % 5;
         okq[k] = item < 400 && wy < a.p1.H && wx < a.p1.W;
         const int64_t pr = (int64_t)n * a.p1.HWp + (okq[k] ? wy * a.p1.W + wx : 0);
-        gq[k] = ldq<GT>(a.G1, pr * a.ld1 + 4 * q);
-        xq[k] = ldq<XT>(a.X1, pr * a.ld1 + 4 * q);
+        gq[k] = ldq<GT>(a.g1.g, pr * a.g1.ldg + 4 * q);
+        xq[k] = ldq<XT>(a.g1.x, pr * a.g1.ldx + 4 * q);
         aq[k] = *reinterpret_cast<const uchar4*>(a.argmax + pr * 64 + 4 * q);
     }
     __syncthreads();                                        // prm ready; previous tile's gl / al consumed
@@ -973,9 +963,7 @@ static __global__ __launch_bounds__(256) void pool0_bwd_kernel(const Pool0BwdArg
 // sums them in a fixed order - no atomics on the gradient.
 constexpr int kTailTW = 16, kTailTH = 4, kTailIW = 4 * kTailTW + 7, kTailIH = 4 * kTailTH + 7, kTailPitch = 75, kTailGl = 65;
 struct StemTailArgs {
-    const float* G1; const float* X1; int ld1; Plane p1;     // block-1 buffers (fp32: mode 0)
-    const double* xsum; const double* xsq; int xstride;      // block-1 stats
-    const double* SA; const double* SB; int sstride;
+    GradSrc g1; Plane p1;                                    // block 1's G' / X, channels 0..63 (fp32: mode 0)
     const unsigned char* argmax; const float* stemv;         // [n][p1.HWp][64] (pool0_kernel)
     const double* ssum; const double* ssq; Plane ps;         // stem stats [n][64]
     const float* gamma; float eps;                           // norm0
@@ -1013,11 +1001,8 @@ static __global__ __launch_bounds__(256) void stem_tail_kernel(const StemTailArg
         bn_moments(a.ssum, a.ssq, (int64_t)n * 64 + t, 1.0 / (double)a.ps.HW, a.eps, mean, invstd);
         prm[256 + t] = mean; prm[320 + t] = invstd; prm[384 + t] = a.gamma[t] * invstd;
         const double inv = 1.0 / (double)a.p1.HW;
-        float m1, i1;
-        bn_moments(a.xsum, a.xsq, (int64_t)n * a.xstride + t, inv, a.eps, m1, i1);
-        const float q1 = (float)(stat_get(a.SA, (int64_t)n * a.sstride + t) * inv);
-        const float q2 = (float)(stat_get(a.SB, (int64_t)n * a.sstride + t) * inv);
-        prm[t] = i1; prm[64 + t] = q1; prm[128 + t] = m1; prm[192 + t] = i1 * q2;
+        const GradCoef f = grad_src_coef(a.g1, n, t, inv);
+        prm[t] = f.a; prm[64 + t] = f.q1; prm[128 + t] = f.mean; prm[192 + t] = f.k;
     }
     float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
     float acc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1035,8 +1020,8 @@ static __global__ __launch_bounds__(256) void stem_tail_kernel(const StemTailArg
             const int qy = qy0 + (lp >> 4), qx = qx0 + (lp & 15);
             okq[i] = qy < a.p1.H && qx < a.p1.W;
             const int64_t pr = (int64_t)n * a.p1.HWp + (okq[i] ? qy * a.p1.W + qx : 0);
-            gq[i] = ld4(a.G1 + pr * a.ld1 + 4 * cq);
-            xq[i] = ld4(a.X1 + pr * a.ld1 + 4 * cq);
+            gq[i] = ld4(static_cast<const float*>(a.g1.g) + pr * a.g1.ldg + 4 * cq);
+            xq[i] = ld4(static_cast<const float*>(a.g1.x) + pr * a.g1.ldx + 4 * cq);
             sq[i] = ld4(a.stemv + pr * 64 + 4 * cq);
             aq[i] = *reinterpret_cast<const uchar4*>(a.argmax + pr * 64 + 4 * cq);
         }
@@ -1221,13 +1206,13 @@ static __global__ void stem_moments_sum_kernel(const float* part, int groups, do
 }
 
 // stem_combine_kernel: dW0[c, t] += sum_n ( b_nc * sum_u w[c, u] * R_n[u, t] + c_nc * S_n[t] ) in fp64, to all three input channels
-// (behind the reduce of stem_tail_kernel's partial tiles on the same stream).  a | q1 | mean | k are formed exactly as
-// BwdWeightP::init_params forms them for its operand a * ((dy - q1) - (x - mean) * k).  Workgroup = channel c: the sum over
+// (behind the reduce of stem_tail_kernel's partial tiles on the same stream).  a | q1 | mean | k are those of the operand
+// a * ((dy - q1) - (x - mean) * k) that BwdWeightP forms from the same descriptor (grad_src_coef).  Workgroup = channel c: the sum over
 // (stream, row of mom) is one dot product of ns * 50 terms per tap, cut into four fixed quarters (thread = (tap, quarter)).
 struct StemCombineArgs {
     const double* mom; const float* w0;                      // moments [n][kMomOut]; conv0's master weight [64][3][49]
-    const double* ssum; const double* ssq; const double* s1; const double* s2;      // stem stats and norm0's backward sums [n][64]
-    const float* gamma; float eps; int HW; int ns;
+    GradSrc dy;                                              // dy0 through norm0 - its statistics only: stem stats, norm0's backward sums [n][64], gamma
+    int HW; int ns;
     float* dw;                                               // [64][3][49]
 };
 static __global__ __launch_bounds__(256) void stem_combine_kernel(const StemCombineArgs a) {
@@ -1237,13 +1222,9 @@ static __global__ __launch_bounds__(256) void stem_combine_kernel(const StemComb
     const int c = blockIdx.x, tid = threadIdx.x;
     const double inv = 1.0 / (double)a.HW;
     for (int n = tid; n < a.ns; n += 256) {
-        float mean, invstd;
-        bn_moments(a.ssum, a.ssq, (int64_t)n * 64 + c, inv, a.eps, mean, invstd);
-        const float q1 = (float)(stat_get(a.s1, (int64_t)n * 64 + c) * inv);
-        const float q2 = (float)(stat_get(a.s2, (int64_t)n * 64 + c) * inv);
-        const float an = a.gamma[c] * invstd, kk = invstd * q2;
-        coef[n * kMomRows + 48] = -(double)an * (double)kk;                                        // b_nc: times w[c, u] into slots 0..48 below
-        coef[n * kMomRows + 49] = (double)an * ((double)kk * (double)mean - (double)q1);           // c_nc
+        const GradCoef f = grad_src_coef(a.dy, n, c, inv);
+        coef[n * kMomRows + 48] = -(double)f.a * (double)f.k;                                      // b_nc: times w[c, u] into slots 0..48 below
+        coef[n * kMomRows + 49] = (double)f.a * ((double)f.k * (double)f.mean - (double)f.q1);     // c_nc
     }
     __syncthreads();
     for (int k = tid; k < a.ns * 49; k += 256) {
@@ -1280,12 +1261,8 @@ static __global__ __launch_bounds__(256) void stem_combine_kernel(const StemComb
 // weight-gradient GEMMs that follow then stream ONE array instead of two.
 // ------------------------------------------------------------------------------------
 struct BnBwdApplyArgs {
-    const void* g; int ldg, gcoff;                // gradient storage of the mode
-    const void* x; int ldx, xcoff;                // activation storage of the mode
+    GradSrc src;                                  // G' and x of the C channels, gradient / activation storage of the mode
     Plane pl; int C;
-    const double* xsum; const double* xsq; int xstride; StatTab xtab;      // xtab: table of the same activation (columns as xcoff + t), or none
-    const double* s1; const double* s2; int sstride, scoff;
-    const float* gamma; float eps;
     void* out; int ldo;
     float* dbeta; float* dgamma;                  // if set: the affine gradients, dbeta += sum_n s1[n], dgamma += sum_n s2[n]
                                                   // (one fp32 atomic per stream and channel instead of one per producer tile)
@@ -1317,21 +1294,18 @@ static __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdApp
         const int r = r0 + k * rows_per_pass;
         if (k * rows_per_pass >= RPW) break;           // (workgroup-uniform: C = 32 uses two slots, C = 128 eight)
         const int64_t pix = (int64_t)n * a.pl.HWp + (r < a.pl.HW ? r : 0);
-        gv[k] = ld16(a.g, (int64_t)GT::size * (pix * a.ldg + a.gcoff + E * cs));
-        xv[k] = ld16(a.x, (int64_t)XT::size * (pix * a.ldx + a.xcoff + E * cs));
+        gv[k] = ld16(a.src.g, (int64_t)GT::size * (pix * a.src.ldg + E * cs));
+        xv[k] = ld16(a.src.x, (int64_t)XT::size * (pix * a.src.ldx + E * cs));
     }
     if (t < a.C) {
-        const double inv = 1.0 / (double)a.pl.HW;
-        float mean, invstd;
-        tab_or_moments(a.xtab, n, a.xcoff + t, a.xsum, a.xsq, (int64_t)n * a.xstride + a.xcoff + t, inv, a.eps, mean, invstd);
-        const float q2 = (float)(stat_get(a.s2, (int64_t)n * a.sstride + a.scoff + t) * inv);
-        prm[t] = (a.gamma ? a.gamma[t] : 1.f) * invstd;
-        prm[a.C + t] = (float)(stat_get(a.s1, (int64_t)n * a.sstride + a.scoff + t) * inv);
-        prm[2 * a.C + t] = mean;
-        prm[3 * a.C + t] = invstd * q2;
-        if (a.dbeta && blockIdx.x == 0) {
-            atomicAdd(a.dbeta + t, (float)stat_get(a.s1, (int64_t)n * a.sstride + a.scoff + t));
-            atomicAdd(a.dgamma + t, (float)stat_get(a.s2, (int64_t)n * a.sstride + a.scoff + t));
+        const GradCoef f = grad_src_coef(a.src, n, t, 1.0 / (double)a.pl.HW);
+        prm[t] = f.a;
+        prm[a.C + t] = f.q1;
+        prm[2 * a.C + t] = f.mean;
+        prm[3 * a.C + t] = f.k;
+        if (a.dbeta && blockIdx.x == 0) {         // (the whole sums, not coefficients)
+            atomicAdd(a.dbeta + t, (float)stat_get(a.src.s1, (int64_t)n * a.src.sstride + t));
+            atomicAdd(a.dgamma + t, (float)stat_get(a.src.s2, (int64_t)n * a.src.sstride + t));
         }
     }
     __syncthreads();
@@ -1376,12 +1350,8 @@ static __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdApp
 // eight consecutive pixels of one quad side by side, so loads and stores both move 128-byte runs.
 // ------------------------------------------------------------------------------------
 struct BnBwdApplySplitArgs {
-    const float* g;                               // raw 3x3 data gradient dy [n][HWp][128]
-    const float* x;                               // the bottleneck activation norm2 normalised [n][HWp][128]
+    GradSrc src;                                  // raw 3x3 data gradient dy and the bottleneck activation norm2 normalised: fp32 [n][HWp][128]
     Plane pl;
-    const double* xsum; const double* xsq; int xstride; StatTab xtab;
-    const double* s1; const double* s2; int sstride;
-    const float* gamma; float eps;
     u32x4* out;                                   // units of this ring slot
     float* binv;                                  // [streams][HWp / 64] inverse block scales
     float* dbeta; float* dgamma;                  // norm2's affine gradients (one fp32 atomic per stream and channel)
@@ -1398,15 +1368,17 @@ static __global__ __launch_bounds__(256) void bn_bwd_apply_split_kernel(const Bn
     for (int k = 0; k < 8; ++k) {                 // the data loads first: one memory round trip with the parameter prologue
         const int r = r0 + 8 * k;
         const int64_t pix = (int64_t)n * a.pl.HWp + (r < a.pl.HW ? r : 0);
-        gv[k] = ld4(a.g + pix * C + 4 * cs);
-        xv[k] = ld4(a.x + pix * C + 4 * cs);
+        gv[k] = ld4(static_cast<const float*>(a.src.g) + pix * C + 4 * cs);
+        xv[k] = ld4(static_cast<const float*>(a.src.x) + pix * C + 4 * cs);
     }
     if (t < C) {
         const double inv = 1.0 / (double)a.pl.HW;
         float mean, invstd;
-        tab_or_moments(a.xtab, n, t, a.xsum, a.xsq, (int64_t)n * a.xstride + t, inv, a.eps, mean, invstd);
-        const double s1 = stat_get(a.s1, (int64_t)n * a.sstride + t), s2 = stat_get(a.s2, (int64_t)n * a.sstride + t);
-        prm[t] = a.gamma[t] * invstd;
+        // (not grad_src_coef: s1 / s2 stay doubles here, for the coefficients AND the affine gradients below)
+        const GradSrc& g = a.src;
+        tab_or_moments(g.xtab, n, t, g.xsum, g.xsq, (int64_t)n * g.sstride + t, inv, g.eps, mean, invstd);
+        const double s1 = stat_get(g.s1, (int64_t)n * g.sstride + t), s2 = stat_get(g.s2, (int64_t)n * g.sstride + t);
+        prm[t] = g.gamma[t] * invstd;
         prm[C + t] = (float)(s1 * inv);
         prm[2 * C + t] = mean;
         prm[3 * C + t] = invstd * (float)(s2 * inv);

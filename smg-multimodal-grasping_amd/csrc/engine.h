@@ -396,6 +396,24 @@ static inline double* b2(smg_engine* e, const StatArr& s) { return e->bstat + e-
 
 static const float kEps = 1e-5f;
 
+// The gradient operand (GradSrc, gemm.cuh) that reads G' from `g` and the activation its BN normalised from `x`, channels c0 on:
+// every pointer at that channel, both arenas through the one handle `s` (and its one stride).  Buffers with c0 != 0 are mode-typed
+// (el); `gamma` (at channel c0) and `tab` (stat_table(.., c0)) are optional.  g = x = nullptr: the statistics side alone.
+static inline GradSrc grad_src(smg_engine* e, float* g, int ldg, float* x, int ldx, const StatArr& s, int c0, const float* gamma,
+                               StatTab tab = StatTab{}) {
+    GradSrc r{};
+    r.g = g ? el(e, g, c0) : nullptr; r.ldg = ldg; r.x = x ? el(e, x, c0) : nullptr; r.ldx = ldx;
+    r.xsum = fsum(e, s) + c0; r.xsq = fsq(e, s) + c0; r.s1 = b1(e, s) + c0; r.s2 = b2(e, s) + c0; r.sstride = s.stride;
+    r.xtab = tab; r.gamma = gamma; r.eps = kEps;
+    return r;
+}
+// ... and a finished gradient: nothing applied on load (amax: its recorded maxima, operand kind 3)
+static inline GradSrc grad_done(const float* g, int ldg, const unsigned* amax = nullptr) {
+    GradSrc r{};
+    r.g = g; r.ldg = ldg; r.amax = amax;
+    return r;
+}
+
 // position of dense layer (block b, layer i; 0-based) in the backward's ring sequence of GS / D2 / D2S slots (slot = position % kRing)
 static inline int ring_pos(int b, int i) {
     int r = kBlockLayers[b] - 1 - i;
@@ -417,8 +435,8 @@ static inline unsigned* gamax_of(const smg_engine* e, int b, int i, int kind) {
 
 // BN statistics table at float offset `at` of the table arena ([rows_max][C] mean, then invstd), from row r0 on, with the
 // affine parameters of the consuming BatchNorm
-static StatTab stat_table(smg_engine* e, int64_t at, int rows_max, int C) {      // the same table, read-only view for the backward
-    StatTab t; t.mean = e->stab + at; t.invstd = t.mean + (int64_t)rows_max * C; t.ld = C; return t;
+static StatTab stat_table(smg_engine* e, int64_t at, int rows_max, int C, int c0 = 0) {      // the same table from channel c0 on, read-only view for the backward
+    StatTab t; t.mean = e->stab + at + c0; t.invstd = t.mean + (int64_t)rows_max * C; t.ld = C; return t;
 }
 static BnTab bn_table(smg_engine* e, int64_t at, int rows_max, int r0, int C, const float* gamma, const float* beta) {
     BnTab t;

@@ -542,6 +542,30 @@ __device__ __forceinline__ float4 affine2(float4 g, float4 x, const float* prm, 
     r.w = bnb1(g.w, x.w, prm[3], q1[3], mu[3], k[3]);
     return r;
 }
+// A gradient operand with the deferred BN backward optionally applied on load: the raw gradient G' and the activation x that the BN
+// normalised (x == nullptr: the gradient is finished, nothing is applied).  THE descriptor of that operand - the data- and
+// weight-gradient GEMMs, the 3x3 halo kernels and the apply kernels all take it, and the host builds it in one place (engine.h:
+// grad_src).  Every pointer is at the operand's first channel (the host folds channel offsets in); sstride = doubles per stream of
+// the forward AND the backward statistic arena, which are carved alike.  Element sizes are the reader's business (GT / XT).
+struct GradSrc {
+    const unsigned* amax;           // operand kind 3 (x == nullptr only): [streams][kAmaxRep] recorded maxima of g (bn_bwd_apply_kernel)
+    const void* g; int ldg;         // gradient storage
+    const void* x; int ldx;         // activation storage
+    const double* xsum; const double* xsq; const double* s1; const double* s2; int sstride;
+    StatTab xtab;                   // fp32 (mean, invstd) table of the same activation, or none: the fp64 sums
+    const float* gamma;             // the BN's weight, or nullptr: 1
+    float eps;
+};
+// a | q1 | mean | k of affine2() for channel ch of stream n; inv = 1 / pixels per plane
+struct GradCoef { float a, q1, mean, k; };
+__device__ __forceinline__ GradCoef grad_src_coef(const GradSrc& s, int n, int ch, double inv) {
+    const int64_t idx = (int64_t)n * s.sstride + ch;
+    float mean, invstd;
+    tab_or_moments(s.xtab, n, ch, s.xsum, s.xsq, idx, inv, s.eps, mean, invstd);
+    const float q1 = (float)(stat_get(s.s1, idx) * inv);
+    const float q2 = (float)(stat_get(s.s2, idx) * inv);
+    return GradCoef{(s.gamma ? s.gamma[ch] : 1.f) * invstd, q1, mean, invstd * q2};
+}
 
 // XCD-aware tile order.  Workgroup b is observed to run on XCD b % 8 (MI355X_MICROARCH.md, used for
 // speed only): sibling tiles that re-read the same A operand (the N-tiles of one M-tile, or of one
@@ -1483,21 +1507,17 @@ template <class Cfg_, bool SHIFT3, int EMODE, bool AFF = true, int PREC = 0, boo
 struct BwdDataP {
     using Cfg = Cfg_;
     static_assert(Cfg::AT, "data-gradient form");
-    using GT = typename std::conditional<F32IO, e_f32, grd_t<PREC>>::type;      // gradients in (gbuf) and out (dst)
-    using XT = typename std::conditional<F32IO, e_f32, act_t<PREC>>::type;      // activations (xbuf, mbuf)
+    using GT = typename std::conditional<F32IO, e_f32, grd_t<PREC>>::type;      // gradients in (gs.g) and out (dst)
+    using XT = typename std::conditional<F32IO, e_f32, act_t<PREC>>::type;      // activations (gs.x, mbuf)
     static_assert(GT::size == XT::size, "one slot geometry for the gradient and its activation");
     // operand kind 3 needs the gradient operand's recorded maximum: the pointwise form on a FINISHED gradient only
     static constexpr int kOp = (AFF || SHIFT3) ? bwd_op_plain(PREC) : bwd_op(PREC), kAE = 16 / GT::size, kBE = 4, GSZ = GT::size, XSZ = XT::size;
     static constexpr bool kARawCopy = !AFF && !SHIFT3 && kAE == 8;              // finished bf16 gradient: copied to LDS as it is
-    static constexpr bool kAUnit = !AFF && !SHIFT3 && kOp == 3;                 // finished gradient in unit form (kD2K8): gbuf = units, ldg unused
-    const float* binv;              // operand kind 3: [streams][HWp / 64] inverse block scales of gbuf (bn_bwd_apply_split_kernel)
-    const void* gbuf; int ldg; int gcoff;
-    const void* xbuf; int ldx; int xcoff;
+    static constexpr bool kAUnit = !AFF && !SHIFT3 && kOp == 3;                 // finished gradient in unit form (kD2K8): gs.g = units, gs.ldg unused
+    const float* binv;              // operand kind 3: [streams][HWp / 64] inverse block scales of gs.g (bn_bwd_apply_split_kernel)
+    GradSrc gs;                     // the gradient operand (KA channels)
     Plane pa;
     int KA;
-    const double* xsum; const double* xsq; int xstride;
-    const double* s1; const double* s2; int sstride; int scoff;
-    const float* agamma;
     const u32x4* wp; int K8tot; int ldn; int wcol0;    // packed weight units [piece][K8tot][ldn], first output column wcol0
     int N;
     const void* mbuf; int ldm; int mcoff; Plane pm;
@@ -1517,7 +1537,7 @@ struct BwdDataP {
     // the transitions' un-pooling data gradient held to 3 waves per SIMD: 172 -> 152 registers without scratch, 169 -> 163 us per launch
     static constexpr int kMinWaves = (PREC == 0 && EMODE == E_UNPOOL) ? 3 : 1;       // (3 waves per SIMD for the 128 x 64 accumulate form: 168 VGPRs + 88 bytes of scratch, serialised total 19.0 -> 19.4 ms)
 
-    // AFF = false: the gradient operand is finished (xbuf unused).  Pointwise and finished -> descriptor loads, rows outside
+    // AFF = false: the gradient operand is finished (gs.x unset).  Pointwise and finished -> descriptor loads, rows outside
     // the plane carry the out-of-range offset and read as zero (no mask, no address arithmetic in the k-loop).
     static constexpr bool kFast = !SHIFT3 && !AFF;
     // Whole tiles inside the plane fetch the epilogue's operands (the mask source x and, for E_ACCUM, the old G') at the START
@@ -1572,7 +1592,7 @@ struct BwdDataP {
     }
     // unit (piece, k8 of this k-tile, tile row) of the finished gradient: plane-major units, consecutive rows consecutive
     __device__ UnitSrc a_unit_src(const Ctx& c, int kt, int piece, int k8, int row) const {
-        return UnitSrc{static_cast<const u32x4*>(gbuf) + d2_stream_units(c.n, pa.HWp), kWholeBuf,
+        return UnitSrc{static_cast<const u32x4*>(gs.g) + d2_stream_units(c.n, pa.HWp), kWholeBuf,
                        16u * (unsigned)((piece * kD2K8 + k8) * pa.HWp + row), 16u * (unsigned)(kt * Cfg::K8 * pa.HWp + (c.m0 - c.n * pa.HWp))};
     }
     __device__ u32x4 a_unit(const Ctx& c, int kt, int piece, int k8, int row) const {
@@ -1625,16 +1645,12 @@ struct BwdDataP {
     }
     __device__ void init_params(const Ctx& c, float* sp) const {
         const double inv = 1.0 / (double)pa.HW;
-        for (int k = threadIdx.x; xbuf && k < KA; k += 256) {
-            float mean, invstd;
-            bn_moments(xsum, xsq, (int64_t)c.n * xstride + xcoff + k, inv, eps, mean, invstd);
-            const float g = agamma ? agamma[k] : 1.f;
-            const float q1 = (float)(stat_get(s1, (int64_t)c.n * sstride + scoff + k) * inv);
-            const float q2 = (float)(stat_get(s2, (int64_t)c.n * sstride + scoff + k) * inv);
-            sp[k] = g * invstd;
-            sp[KA + k] = q1;
-            sp[2 * KA + k] = mean;
-            sp[3 * KA + k] = invstd * q2;
+        for (int k = threadIdx.x; gs.x && k < KA; k += 256) {
+            const GradCoef f = grad_src_coef(gs, c.n, k, inv);
+            sp[k] = f.a;
+            sp[KA + k] = f.q1;
+            sp[2 * KA + k] = f.mean;
+            sp[3 * KA + k] = f.k;
         }
         float* ep = sp + 4 * KA;
         const double minv = 1.0 / (double)pm.HW;
@@ -1659,9 +1675,9 @@ struct BwdDataP {
         r.valid = p < pa.HW;
         r.y = p / pa.W;
         r.x = p - r.y * pa.W;
-        r.off = r.valid ? (unsigned)GSZ * (unsigned)(p * ldg) : kOOB;
+        r.off = r.valid ? (unsigned)GSZ * (unsigned)(p * gs.ldg) : kOOB;
     }
-    using ARaw = RawT<2>;       // gradient + (when xbuf is set) the raw activation its BN normalised
+    using ARaw = RawT<2>;       // gradient + (when gs.x is set) the raw activation its BN normalised
     using BRaw = u32x4;
     __device__ int a_chan0(int kt) const {
         if constexpr (SHIFT3) { const int kpt = KA / Cfg::BK; return (kt % kpt) * Cfg::BK; }
@@ -1678,7 +1694,7 @@ struct BwdDataP {
         ARaw o;
         if constexpr (kFast) {
             o.ok = true;
-            o.v[0] = bload4(static_cast<const char*>(gbuf) + (int64_t)GSZ * ((int64_t)c.n * pa.HWp * ldg + gcoff), kWholeBuf, r.off + 16u * (unsigned)q,
+            o.v[0] = bload4(static_cast<const char*>(gs.g) + (int64_t)GSZ * ((int64_t)c.n * pa.HWp * gs.ldg), kWholeBuf, r.off + 16u * (unsigned)q,
                             (unsigned)GSZ * (unsigned)(kt * Cfg::BK));
             return o;
         }
@@ -1692,14 +1708,14 @@ struct BwdDataP {
         }
         const int ch = a_chan0(kt) + kAE * q;                                         // first channel of staging slot q
         const int64_t pix = (int64_t)c.n * pa.HWp + (o.ok ? yy * pa.W + xx : 0);      // unconditional loads, clamped address
-        o.v[0] = ld16(gbuf, (int64_t)GSZ * (pix * ldg + gcoff + ch));
-        if (xbuf) o.v[1] = ld16(xbuf, (int64_t)XSZ * (pix * ldx + xcoff + ch));      // (launch-uniform)
+        o.v[0] = ld16(gs.g, (int64_t)GSZ * (pix * gs.ldg + ch));
+        if (gs.x) o.v[1] = ld16(gs.x, (int64_t)XSZ * (pix * gs.ldx + ch));      // (launch-uniform)
         return o;
     }
     __device__ float4 a_xform(const Ctx& c, const ARaw& o, const KPrm&, int kt, int q, const float* sp) const {
         if constexpr (kFast) return o.v[0];            // (operand kind 3 takes the unit path: a_unit)
         if (!o.ok) return zero4();
-        if (!xbuf) return o.v[0];                      // gradient already BN-corrected (bn_bwd_apply_kernel)
+        if (!gs.x) return o.v[0];                      // gradient already BN-corrected (bn_bwd_apply_kernel)
         return affine2(o.v[0], o.v[1], sp + a_chan(kt, q), KA);
     }
     __device__ ARaw a_fetch_d(const Ctx&, const DRow&, int, int, int) const { return ARaw{}; }
@@ -2338,22 +2354,18 @@ struct BwdWeightP {
     using Cfg = Cfg_;
     static_assert(!Cfg::AT, "weight-gradient form");
     static constexpr bool F32IO = F32IO_ || BMODE == 3 || BMODE == 4;      // W_STEM, W_STEM1
-    using GT = typename std::conditional<F32IO, e_f32, grd_t<PREC>>::type;      // output gradient (gbuf)
-    using XT = typename std::conditional<F32IO, e_f32, act_t<PREC>>::type;      // activations (xbuf, bbuf)
+    using GT = typename std::conditional<F32IO, e_f32, grd_t<PREC>>::type;      // output gradient (gs.g)
+    using XT = typename std::conditional<F32IO, e_f32, act_t<PREC>>::type;      // activations (gs.x, bbuf)
     static_assert(GT::size == XT::size, "one slot geometry");
     // operand kind 3: the dense layers' 1x1 weight gradient (finished gradient with a recorded maximum x BN + ReLU activation)
     static constexpr int kOp = (!AFF && BMODE == 0) ? bwd_op(PREC) : bwd_op_plain(PREC), kAE = 16 / GT::size, kBE = 16 / XT::size, GSZ = GT::size, XSZ = XT::size;
     static constexpr bool kARawCopy = !AFF && kAE == 8;      // finished bf16 gradient: copied to LDS as it is
-    static constexpr bool kAUnit = !AFF && BMODE == 0 && kOp == 3;      // the gradient operand arrives in unit form (kD2K8): gbuf = units
+    static constexpr bool kAUnit = !AFF && BMODE == 0 && kOp == 3;      // the gradient operand arrives in unit form (kD2K8): gs.g = units
     static constexpr bool kH = kOp == 3;      // the BN + ReLU operand B becomes fp16 (the gradient side of modes 1 / 2 is bf16): clamped (bnrelu4)
-    const float* binv;              // operand kind 3: [streams][HWp / 64] inverse block scales of gbuf (bn_bwd_apply_split_kernel)
+    const float* binv;              // operand kind 3: [streams][HWp / 64] inverse block scales of gs.g (bn_bwd_apply_split_kernel)
     const float* basc;              // operand kind 3: {s, 1 / s} of the BN + ReLU operand B (scale_kernel)
-    const void* gbuf; int ldg; int gcoff;
-    const void* xbuf; int ldx; int xcoff;
+    GradSrc gs;                     // the gradient operand A (MA channels)
     Plane pa; int MA;
-    const double* xsum; const double* xsq; int xstride;
-    const double* s1; const double* s2; int sstride; int scoff;
-    const float* agamma;
     const void* bbuf; int ldb; Plane pb; int NB;
     const double* bsum; const double* bsq; int bstride; StatTab btab;
     const float* bgamma; const float* bbeta;
@@ -2424,7 +2436,7 @@ struct BwdWeightP {
     }
     // unit (piece, channel group k8, pixel kr of k-tile kt) of the gradient operand: plane-major units, consecutive pixels consecutive
     __device__ u32x4 a_unit_d(const Ctx& c, int kt, int piece, int k8, int kr) const {
-        return bload_u4(static_cast<const u32x4*>(gbuf) + d2_stream_units(c.n, pa.HWp), 16u * (unsigned)(2 * kD2K8 * pa.HWp),
+        return bload_u4(static_cast<const u32x4*>(gs.g) + d2_stream_units(c.n, pa.HWp), 16u * (unsigned)(2 * kD2K8 * pa.HWp),
                         16u * (unsigned)((piece * kD2K8 + k8) * pa.HWp + kr), 16u * (unsigned)(c.p0 + kt * Cfg::BK));
     }
     __device__ u32x4 a_unit(const Ctx&, int, int, int, int) const { return u32x4{}; }
@@ -2449,22 +2461,14 @@ struct BwdWeightP {
     }
     __device__ void init_params(const Ctx& c, float* sp) const {
         const double inv = 1.0 / (double)pa.HW;
-        for (int k = threadIdx.x; xbuf && k < Cfg::BM; k += 256) {
+        for (int k = threadIdx.x; gs.x && k < Cfg::BM; k += 256) {
             const int ch = c.m0 + k;
-            float a = 0.f, q1 = 0.f, mean = 0.f, kk = 0.f;
-            if (ch < MA) {
-                float invstd;
-                bn_moments(xsum, xsq, (int64_t)c.n * xstride + xcoff + ch, inv, eps, mean, invstd);
-                const float g = agamma ? agamma[ch] : 1.f;
-                q1 = (float)(stat_get(s1, (int64_t)c.n * sstride + scoff + ch) * inv);
-                const float q2 = (float)(stat_get(s2, (int64_t)c.n * sstride + scoff + ch) * inv);
-                a = g * invstd;
-                kk = invstd * q2;
-            }
-            sp[k] = a;
-            sp[Cfg::BM + k] = q1;
-            sp[2 * Cfg::BM + k] = mean;
-            sp[3 * Cfg::BM + k] = kk;
+            GradCoef f{0.f, 0.f, 0.f, 0.f};
+            if (ch < MA) f = grad_src_coef(gs, c.n, ch, inv);
+            sp[k] = f.a;
+            sp[Cfg::BM + k] = f.q1;
+            sp[2 * Cfg::BM + k] = f.mean;
+            sp[3 * Cfg::BM + k] = f.k;
         }
         if constexpr (BMODE != W_STEM && BMODE != W_STEM1) {
             float* bp = sp + 4 * Cfg::BM;
@@ -2503,15 +2507,15 @@ struct BwdWeightP {
         const int ch = c.m0 + kAE * q;                                    // first channel of staging slot q
         if constexpr (!AFF) {
             o.ok = true;
-            o.v[0] = bload4(static_cast<const char*>(gbuf) + (int64_t)GSZ * ((int64_t)c.n * pa.HWp * ldg + gcoff), (unsigned)GSZ * (unsigned)(pa.HW * ldg - gcoff),
-                            ch < MA ? (unsigned)GSZ * (unsigned)(kr * ldg + ch) : kOOB, (unsigned)GSZ * (unsigned)((c.p0 + kt * Cfg::BK) * ldg));
+            o.v[0] = bload4(static_cast<const char*>(gs.g) + (int64_t)GSZ * ((int64_t)c.n * pa.HWp * gs.ldg), (unsigned)GSZ * (unsigned)(pa.HW * gs.ldg),
+                            ch < MA ? (unsigned)GSZ * (unsigned)(kr * gs.ldg + ch) : kOOB, (unsigned)GSZ * (unsigned)((c.p0 + kt * Cfg::BK) * gs.ldg));
             return o;
         }
         o.ok = r.p < pa.HW && ch < MA;
         const int64_t pix = (int64_t)c.n * pa.HWp + (o.ok ? r.p : 0);
         const int chc = o.ok ? ch : 0;
-        o.v[0] = ld16(gbuf, (int64_t)GSZ * (pix * ldg + gcoff + chc));
-        if (xbuf) o.v[1] = ld16(xbuf, (int64_t)XSZ * (pix * ldx + xcoff + chc));          // (launch-uniform)
+        o.v[0] = ld16(gs.g, (int64_t)GSZ * (pix * gs.ldg + chc));
+        if (gs.x) o.v[1] = ld16(gs.x, (int64_t)XSZ * (pix * gs.ldx + chc));          // (launch-uniform)
         return o;
     }
     __device__ ARaw a_quad(const ARaw& o, int h) const {
@@ -2529,7 +2533,7 @@ struct BwdWeightP {
     __device__ float4 a_xform(const Ctx& c, const ARaw& o, const KPrm&, int, int q, const float* sp) const {
         if constexpr (!AFF) return o.v[0];             // (operand kind 3 takes the unit path: a_unit_d)
         if (!o.ok) return zero4();
-        if (!xbuf) return o.v[0];
+        if (!gs.x) return o.v[0];
         return affine2(o.v[0], o.v[1], sp + 4 * q, Cfg::BM);
     }
     __device__ BRaw b_fetch(const Ctx& c, const DRow& r, int kt, int kr, int q) const {

@@ -472,29 +472,19 @@ static __global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : kHaloFwdWaves) void
 }
 
 
-// The finished gradient of a layer's 32 output channels, as the 3x3 backward kernels read it: either a dense
+// The finished gradient of a layer's 32 output channels, as the 3x3 backward kernels read it (GradSrc, gemm.cuh): either a dense
 // [n][HWp][32] array (x == nullptr), or the G' and X slices of the block buffers with the deferred BN backward
 // applied on load (what bn_bwd_apply_kernel would have written):
 //   g = invstd * ((G' - SA/n) - (x - mean) * invstd * SB/n)
-// Statistics pointers are already offset to the slice's first channel; sstride = floats per stream.
-struct GradSrc {
-    const unsigned* amax;           // operand kind 3 (x == nullptr only): [streams][kAmaxRep] recorded maxima of g (bn_bwd_apply_kernel)
-    const void* g; int ldg;         // gradient storage: fp32 / bf16 by mode
-    const void* x; int ldx;         // activation storage: fp32 / bf16 / fp16 by mode
-    const double* xsum; const double* xsq; const double* s1; const double* s2; int sstride;
-    float eps;
-};
 // parameters a | q1 | mean | k of affine2() for the 32 channels -> gp[4][32]  (threads 0..31)
 __device__ __forceinline__ void grad_src_params(const GradSrc& s, int n, int hw, float* gp) {
     const int t = threadIdx.x;
     if (s.x && t < 32) {
-        const double inv = 1.0 / (double)hw;
-        float mean, invstd;
-        bn_moments(s.xsum, s.xsq, (int64_t)n * s.sstride + t, inv, s.eps, mean, invstd);
-        gp[t] = invstd;
-        gp[32 + t] = (float)(stat_get(s.s1, (int64_t)n * s.sstride + t) * inv);
-        gp[64 + t] = mean;
-        gp[96 + t] = invstd * (float)(stat_get(s.s2, (int64_t)n * s.sstride + t) * inv);
+        const GradCoef f = grad_src_coef(s, n, t, 1.0 / (double)hw);
+        gp[t] = f.a;
+        gp[32 + t] = f.q1;
+        gp[64 + t] = f.mean;
+        gp[96 + t] = f.k;
     }
 }
 
