@@ -265,7 +265,7 @@ int smg_loss_scene_map(smg_engine* e, const float* q_dev, const float* affine_ho
  * (the dense-map form), so picking and training see one and the same function of the head output.  Nothing is special-cased: a
  * NaN, or an inf that produces inf - inf, in any of the twelve corner logits makes all three probabilities NaN, as torch.softmax
  * does in fp64.  An invalid pixel is -inf in every plane, so the argmax rules carry over unchanged.
- * All four return -22 and launch nothing for the geometry refusals above, for n_maps < 1 / K < 1 / n_pairs < 1 and for cls out of range. */
+ * All five return -22 and launch nothing for the geometry refusals above, for n_maps < 1 / K < 1 / n_pairs < 1 and for cls out of range. */
 
 /* out_dev float32: cls in {0,1,2} -> [n_maps][hm][hm] = P(class cls); cls == -1 -> [n_maps][3][hm][hm], all three.
  * q_dev is [n_maps][3][OH][OW] (the head output of a 3-class engine). */
@@ -278,6 +278,24 @@ int smg_scene_class_maps(smg_engine* e, const float* q_dev, int n_maps, const fl
  * value -inf when no pixel is valid. */
 int smg_scene_class_argmax(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size,
                            int cls, int* idx_out_dev, float* val_out_dev, void* stream);
+
+/* smg_scene_class_argmax per OBJECT - smg_scene_argmax_objects for the 3-class head: every map restricted to the heightmap pixels
+ * its masks select, one result per group of maps, the value P(class cls) of the interpolated logits, cls in {0,1,2}; neither the
+ * scene-frame maps nor the masked copies are written.  q_dev is [n_maps][3][OH][OW].  masks_dev, n_masks, map_mask_a, map_mask_b,
+ * map_group, n_groups, idx_out_dev int32[n_groups] and val_out_dev float32[n_groups] mean what they mean for
+ * smg_scene_argmax_objects, word for word: selection by "not exactly 0" on the float64 masks tensor of the forward (-0.0 does not
+ * select, a NaN does), the union of the two terms, groups that need not be contiguous, every group's pair written, index -1 / value
+ * -inf for a group with no map or no selected valid pixel, the flattened index into [n_maps][hm][hm] of the whole call, smg_argmax's
+ * tie and NaN rules (a NaN in any corner logit of any plane makes the pixel's value NaN, and it wins its group).  The masks are
+ * read before the geometry: an unselected pixel costs no double-precision arithmetic and no exponential.  No atomics: two identical
+ * calls are bit-identical, the value comes from the expression smg_scene_class_maps stores, and a group's result equals smg_argmax
+ * over plane cls of smg_scene_class_maps' output with the unselected pixels set to -inf, bit for bit.
+ * Returns -22 and launches nothing for a NULL pointer, head_out != 3, cls outside {0,1,2}, n_maps < 1, n_masks < 1, n_groups < 1,
+ * a mask index outside [-1, n_masks), a group outside [0, n_groups), a flattened index that does not fit int32, and the geometry
+ * refusals above (hm_size, a 1 x 1 map, an affine with a translation). */
+int smg_scene_class_argmax_objects(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                                   const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
+                                   const int* map_group, int n_groups, int* idx_out_dev, float* val_out_dev, void* stream);
 
 /* Cross entropy (CrossEntropyLoss2d, class weights {1,1,0}) on K labelled heightmap pixels per pair: q and dq are
  * [n_pairs][3][OH][OW]; pixels_dev int32 [n_pairs][K][2] = (iy, ix); label_dev float32 [n_pairs][K] class indices as in

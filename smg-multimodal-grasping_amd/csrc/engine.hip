@@ -505,7 +505,7 @@ static SceneAffine scene_affine(const float* affine_host, int m0, int n) {
     return a;
 }
 
-// What the nine scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
+// What the ten scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
 // evaluates them and passes each one's text, or nullptr where it does not apply; the first that applies is reported as
 // "<who>: <text>"), the geometry, the one refusal that stands behind it (`after`), the n affines.  Then the device is selected and g
 // is valid.  Nothing has been launched when this returns non-zero.
@@ -568,34 +568,48 @@ int smg_scene_argmax(smg_engine* e, const float* q_dev, int64_t map_stride, int 
 // smg_scene_argmax with every map restricted to the pixels its masks select and one result per group of maps: the selected walk
 // fills the same per-workgroup slots, the grouped reduce (one workgroup per group) carries each group's result from one launch of
 // kSceneMaps maps to the next.  The per-map mask indices and group ids travel as kernel arguments, like the matrices.
-int smg_scene_argmax_objects(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
-                             const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
-                             int n_groups, int* idx_out_dev, float* val_out_dev, void* stream) {
-    if (!e || !q_dev || !affine_host || !masks_dev || !map_mask_a || !map_mask_b || !map_group || !idx_out_dev || !val_out_dev)
-        return fail(-22, "smg_scene_argmax_objects: NULL argument");
-    const bool counts_ok = n_maps >= 1 && n_masks >= 1 && n_groups >= 1;
+// One body for the one-plane form and the class form (smg_scene_class_argmax_objects): `own` = the refusals of the entry point's
+// own arguments (head, n_maps, map_stride, cls), reported first; walk(tiles, n, m0, affines, select, g, mvec) launches the form's
+// selected walk for maps [m0, m0 + n).
+struct SceneObjectArgs { const double* masks_dev; int n_masks; const int *map_mask_a, *map_mask_b, *map_group; int n_groups; int* idx_out_dev; float* val_out_dev; };
+extern "C++" template <class F>
+static int scene_argmax_objects(smg_engine* e, const char* who, const void* q_dev, std::initializer_list<const char*> own, int n_maps,
+                                const float* affine_host, int hm_size, const SceneObjectArgs& o, void* stream, F walk) {
+    if (!e || !q_dev || !affine_host || !o.masks_dev || !o.map_mask_a || !o.map_mask_b || !o.map_group || !o.idx_out_dev || !o.val_out_dev)
+        return fail(-22, std::string(who) + ": NULL argument");
+    for (const char* text : own)
+        if (text) return fail(-22, std::string(who) + ": " + text);
+    const bool counts_ok = n_maps >= 1 && o.n_masks >= 1 && o.n_groups >= 1;
     const char *bad_mask = nullptr, *bad_group = nullptr;
     for (int m = 0; counts_ok && m < n_maps; ++m) {
-        if (map_mask_a[m] < -1 || map_mask_a[m] >= n_masks || map_mask_b[m] < -1 || map_mask_b[m] >= n_masks) bad_mask = "a mask index outside [-1, n_masks)";
-        if (map_group[m] < 0 || map_group[m] >= n_groups) bad_group = "a group outside [0, n_groups)";
+        if (o.map_mask_a[m] < -1 || o.map_mask_a[m] >= o.n_masks || o.map_mask_b[m] < -1 || o.map_mask_b[m] >= o.n_masks) bad_mask = "a mask index outside [-1, n_masks)";
+        if (o.map_group[m] < 0 || o.map_group[m] >= o.n_groups) bad_group = "a group outside [0, n_groups)";
     }
     SceneGeo g;
-    if (int rc = scene_prelude(e, "smg_scene_argmax_objects",
-                               {n_maps < 1 || map_stride < 0 ? "n_maps < 1 or a negative map_stride" : nullptr,
-                                n_masks < 1 ? "n_masks < 1" : nullptr, n_groups < 1 ? "n_groups < 1" : nullptr, bad_mask, bad_group},
+    if (int rc = scene_prelude(e, who, {o.n_masks < 1 ? "n_masks < 1" : nullptr, o.n_groups < 1 ? "n_groups < 1" : nullptr, bad_mask, bad_group},
                                hm_size, scene_index_fits(n_maps, hm_size), affine_host, n_maps, &g)) return rc;
     const int tiles = scene_tiles(hm_size);
-    const int mvec = (int64_t)hm_size * hm_size % 4 == 0 && (reinterpret_cast<uintptr_t>(masks_dev) & 15) == 0;       // scene_vec4's split, on the masks
+    const int mvec = (int64_t)hm_size * hm_size % 4 == 0 && (reinterpret_cast<uintptr_t>(o.masks_dev) & 15) == 0;       // scene_vec4's split, on the masks
     return scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
         SceneSelect sel;
         for (int m = 0; m < kSceneMaps; ++m) {
             const bool in = m < n;
-            sel.a[m] = in ? map_mask_a[m0 + m] : -1; sel.b[m] = in ? map_mask_b[m0 + m] : -1; sel.group[m] = in ? map_group[m0 + m] : -1;
+            sel.a[m] = in ? o.map_mask_a[m0 + m] : -1; sel.b[m] = in ? o.map_mask_b[m0 + m] : -1; sel.group[m] = in ? o.map_group[m0 + m] : -1;
         }
+        walk(tiles, n, m0, a, sel, g, mvec);
+        hipLaunchKernelGGL(scene_argmax_group_reduce_kernel, dim3(o.n_groups), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
+                           (const int*)e->scene_idx, tiles, n, sel, m0 > 0 ? 1 : 0, o.idx_out_dev, o.val_out_dev);
+    });
+}
+
+int smg_scene_argmax_objects(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
+                             const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
+                             int n_groups, int* idx_out_dev, float* val_out_dev, void* stream) {
+    return scene_argmax_objects(e, "smg_scene_argmax_objects", q_dev, {n_maps < 1 || map_stride < 0 ? "n_maps < 1 or a negative map_stride" : nullptr},
+                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, stream,
+                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec) {
         hipLaunchKernelGGL(scene_argmax_objects_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
                            q_dev, map_stride, m0, a, sel, g, masks_dev, mvec, e->scene_val, e->scene_idx);
-        hipLaunchKernelGGL(scene_argmax_group_reduce_kernel, dim3(n_groups), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
-                           (const int*)e->scene_idx, tiles, n, sel, m0 > 0 ? 1 : 0, idx_out_dev, val_out_dev);
     });
 }
 
@@ -669,6 +683,22 @@ int smg_scene_class_argmax(smg_engine* e, const float* q_dev, int n_maps, const 
                            q_dev, P3, m0, a, g, cls, e->scene_val, e->scene_idx);
         hipLaunchKernelGGL(scene_argmax_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
                            (const int*)e->scene_idx, tiles * n, m0 > 0 ? 1 : 0, idx_out_dev, val_out_dev);
+    });
+}
+
+// smg_scene_class_argmax with every map restricted to the pixels its masks select, one result per group: scene_argmax_objects'
+// body with the selected walk on the three logit planes.
+int smg_scene_class_argmax_objects(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                                   const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
+                                   int n_groups, int* idx_out_dev, float* val_out_dev, void* stream) {
+    return scene_argmax_objects(e, "smg_scene_class_argmax_objects", q_dev,
+                                {e && e->head_out != 3 ? "class probabilities need a 3-class head (head_out == 3)" : nullptr,
+                                 n_maps < 1 ? "n_maps < 1" : nullptr, cls < 0 || cls > 2 ? "cls must be 0, 1 or 2" : nullptr},
+                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, stream,
+                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec) {
+        const int64_t P3 = (int64_t)3 * g.OH * g.OW;
+        hipLaunchKernelGGL(scene_class_argmax_objects_kernel, dim3(tiles, n), dim3(256), (size_t)P3 * sizeof(float), (hipStream_t)stream,
+                           q_dev, P3, m0, a, sel, g, cls, masks_dev, mvec, e->scene_val, e->scene_idx);
     });
 }
 

@@ -4,8 +4,8 @@
 //                                  value, or the softmax of the three interpolated logits of a 3-class head
 //   scene_walk<PLANES, ARGMAX, SELECT>  the one tiling behind smg_scene_maps / smg_scene_class_maps (ARGMAX false: the maps are
 //                                  stored), smg_scene_argmax / smg_scene_class_argmax (true: the best (rotation, pixel), nothing
-//                                  stored) and smg_scene_argmax_objects (SELECT: every map on the pixels its masks select, one
-//                                  result per group of maps)
+//                                  stored) and smg_scene_argmax_objects / smg_scene_class_argmax_objects (SELECT: every map on the
+//                                  pixels its masks select, one result per group of maps)
 //   SceneHuber / SceneCe           the per-point terms of the two losses, each written once
 //   scene_list_walk                the loss on K LISTED pixels per pair (smg_loss_scene_ce; smg_loss_scene's kernel keeps the same
 //                                  loop in a copy of its own, for the reason its comment gives)
@@ -82,7 +82,7 @@ __device__ __forceinline__ float scene_class_prob(const SceneClass c, int cls) {
     return (float)((cls == 2 ? c.e2 : e01) / c.s);
 }
 
-// Per map of a launch of smg_scene_argmax_objects, as kernel arguments beside SceneAffine: the two mask terms that select the map's
+// Per map of a launch of smg_scene_argmax_objects / smg_scene_class_argmax_objects, as kernel arguments beside SceneAffine: the two mask terms that select the map's
 // heightmap pixels (an index into masks [n_masks][hm][hm] float64, -1 = no such term, both -1 = every pixel) and the group whose
 // result the map competes for.
 struct SceneSelect { int a[kSceneMaps], b[kSceneMaps], group[kSceneMaps]; };
@@ -116,7 +116,7 @@ __device__ __forceinline__ void scene_select4(const double* masks, int term, int
 // [maps][3][hm][hm] - a thread's pixel group goes to three addresses hm^2 apart; an invalid pixel is -inf in every plane.
 // ARGMAX == true (cls in {0, 1, 2}): nothing is stored; the workgroup's best (value, index into [maps][hm][hm]) by argmax_better's
 // rules - invalid pixels are skipped, not compared - goes to slot blockIdx.y * gridDim.x + blockIdx.x of the partial arrays.
-// SELECT (with ARGMAX; smg_scene_argmax_objects): the map only sees the pixels its two mask terms sel->a[m] / sel->b[m] select
+// SELECT (with ARGMAX; smg_scene_argmax_objects, smg_scene_class_argmax_objects): the map only sees the pixels its two mask terms sel->a[m] / sel->b[m] select
 // (scene_select4, `mvec` = its 16-byte loads).  The masks are read BEFORE the geometry: a pixel that is not selected is skipped like
 // an invalid one and never enters the double-precision chain - objects are compact, so whole waves skip it.  A workgroup without a
 // selected valid pixel leaves an empty slot (index 0x7fffffff).
@@ -213,6 +213,13 @@ static __global__ __launch_bounds__(256) void scene_argmax_objects_kernel(const 
                                                                           float* part_val, int* part_idx) {
     scene_walk<1, true, true>(q, map_stride, map0, aff, g, 0, nullptr, 0, part_val, part_idx, &sel, masks, mvec);
 }
+// smg_scene_class_argmax_objects: the selected walk on the three logit planes (dynamic LDS 3 x OH x OW floats, as
+// scene_class_argmax_kernel's).  An unselected pixel never reaches scene_class and its three double exponentials.
+static __global__ __launch_bounds__(256) void scene_class_argmax_objects_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                                const SceneSelect sel, const SceneGeo g, int cls, const double* masks,
+                                                                                int mvec, float* part_val, int* part_idx) {
+    scene_walk<3, true, true>(q, map_stride, map0, aff, g, cls, nullptr, 0, part_val, part_idx, &sel, masks, mvec);
+}
 
 // The second launch of smg_scene_argmax / smg_scene_class_argmax: one workgroup reduces the n partials (thread t takes slots t,
 // t + 256, ... in that order) and, with `carry`, the result a previous group of maps left in the outputs.  Empty slots hold index
@@ -233,7 +240,7 @@ static __global__ __launch_bounds__(256) void scene_argmax_reduce_kernel(const f
     if (t == 0) { *idx_out = bi[0] == 0x7fffffff ? -1 : bi[0]; *val_out = bv[0]; }
 }
 
-// The grouped form, the second launch of smg_scene_argmax_objects: one workgroup per group (blockIdx.x) scans the slots of this
+// The grouped form, the second launch of smg_scene_argmax_objects / smg_scene_class_argmax_objects: one workgroup per group (blockIdx.x) scans the slots of this
 // launch's `n_maps` maps (`tiles` slots each, map-major) whose map belongs to its group - thread t takes slots t, t + 256, ... in that
 // order - and, with `carry`, the result an earlier launch of maps left in the group's outputs.  Every group's pair is written: a
 // group without a map in any launch, or without a selected valid pixel, ends at index -1, value -inf.

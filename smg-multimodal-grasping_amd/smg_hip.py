@@ -56,7 +56,7 @@ def lib():
     L.smg_version.restype = C.c_int
     if not hasattr(L, "smg_abi_struct_bytes") or L.smg_version() != ABI_VERSION:
         raise SmgError("%s is ABI version %d, this binding needs %d: rebuild it (make -C csrc)" % (LIB_PATH, L.smg_version(), ABI_VERSION))
-    for added in ("smg_loss_scene_map_ce", "smg_scene_argmax_objects"):       # (added without a version step: a version-9 library built before them lacks the symbol)
+    for added in ("smg_loss_scene_map_ce", "smg_scene_argmax_objects", "smg_scene_class_argmax_objects"):       # (added without a version step: a version-9 library built before them lacks the symbol)
         if not hasattr(L, added):
             raise SmgError("%s is ABI version %d but lacks %s, a stale build: rebuild it (make -C csrc)" % (LIB_PATH, ABI_VERSION, added))
     L.smg_abi_struct_bytes.argtypes = [C.c_int]
@@ -91,6 +91,8 @@ def lib():
                                      C.c_void_p]
     L.smg_scene_class_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.smg_scene_class_argmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smg_scene_class_argmax_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene_ce.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
     L.smg_loss_scene_map_ce.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -123,7 +125,7 @@ EXPORTS = (
     "smg_last_error", "smg_version", "smg_abi_struct_bytes", "smg_engine_set_option", "smg_layout_count", "smg_layout_param_floats", "smg_layout_buffer_floats",
     "smg_layout_nbt_count", "smg_layout_entry", "smg_layout_trunk_range", "smg_layout_head_range",
     "smg_engine_create", "smg_engine_destroy", "smg_engine_workspace_bytes", "smg_engine_geometry",
-    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_loss_scene","smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_argmax", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
+    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_loss_scene","smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_argmax", "smg_scene_class_argmax_objects", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
     "smg_profile_enable", "smg_profile_kinds", "smg_profile_kind_name", "smg_profile_read", "smg_profile_read_bytes",
 )
 
@@ -287,6 +289,17 @@ class Engine(object):
         a, p = self._affines(affine, n_maps)
         check(lib().smg_scene_argmax(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), idx_out, val_out, stream))
 
+    @staticmethod
+    def _selects(n_maps, mask_a, mask_b, groups):
+        """the per-map mask indices and group ids of the *_argmax_objects calls as int32 arrays (kept alive by the caller) and pointers"""
+        sel = []
+        for name, seq in (("mask_a", mask_a), ("mask_b", mask_b), ("groups", groups)):
+            arr = np.ascontiguousarray(seq, dtype=np.int32).reshape(-1)
+            if arr.size != n_maps:
+                raise ValueError("%s: need one int per map, got %d for %d maps" % (name, arr.size, n_maps))
+            sel.append(arr)
+        return sel, [s.ctypes.data_as(C.POINTER(C.c_int)) for s in sel]
+
     def scene_argmax_objects(self, q, map_stride, n_maps, affine, hm_size, masks, n_masks, mask_a, mask_b, groups, n_groups,
                              idx_out, val_out, stream):
         """smg_scene_argmax_objects: scene_argmax per group of maps, every map on the heightmap pixels its masks select - `masks`
@@ -294,13 +307,7 @@ class Engine(object):
         n_maps ints (mask index or -1; group in [0, n_groups)).  idx_out int32[n_groups] = flattened index into [n_maps, hm, hm]
         or -1, val_out float32[n_groups]."""
         a, p = self._affines(affine, n_maps)
-        sel = []
-        for name, seq in (("mask_a", mask_a), ("mask_b", mask_b), ("groups", groups)):
-            arr = np.ascontiguousarray(seq, dtype=np.int32).reshape(-1)
-            if arr.size != n_maps:
-                raise ValueError("%s: need one int per map, got %d for %d maps" % (name, arr.size, n_maps))
-            sel.append(arr)
-        ma, mb, gr = (s.ctypes.data_as(C.POINTER(C.c_int)) for s in sel)
+        sel, (ma, mb, gr) = self._selects(n_maps, mask_a, mask_b, groups)
         check(lib().smg_scene_argmax_objects(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), masks, int(n_masks), ma, mb, gr,
                                              int(n_groups), idx_out, val_out, stream))
 
@@ -328,6 +335,15 @@ class Engine(object):
         """smg_scene_class_argmax: the valid (map, iy, ix) with the largest P(class cls) as a flattened index, without writing the maps."""
         a, p = self._affines(affine, n_maps)
         check(lib().smg_scene_class_argmax(self.h, q, int(n_maps), p, int(hm_size), int(cls), idx_out, val_out, stream))
+
+    def scene_class_argmax_objects(self, q, n_maps, affine, hm_size, cls, masks, n_masks, mask_a, mask_b, groups, n_groups,
+                                   idx_out, val_out, stream):
+        """smg_scene_class_argmax_objects: scene_class_argmax per group of maps, every map on the heightmap pixels its masks select
+        - scene_argmax_objects' arguments on the logit maps `q` [n_maps, 3, OH, OW]; the value is P(class cls), cls 0 / 1 / 2."""
+        a, p = self._affines(affine, n_maps)
+        sel, (ma, mb, gr) = self._selects(n_maps, mask_a, mask_b, groups)
+        check(lib().smg_scene_class_argmax_objects(self.h, q, int(n_maps), p, int(hm_size), int(cls), masks, int(n_masks), ma, mb, gr,
+                                                   int(n_groups), idx_out, val_out, stream))
 
     def loss_scene_ce(self, q, affine, hm_size, n_pairs, K, pixels, labels, loss_out, dq_out, stream):
         """smg_loss_scene_ce: the cross entropy (class weights {1, 1, 0}) on K heightmap pixels (int32 [n_pairs, K, 2] = iy, ix) per

@@ -219,10 +219,10 @@ class Trainer(object):
         return d, m
 
     def _object_maps(self, what, depth_heightmap, mask_depth, style, is_target):
-        """The one engine call behind forward_objects and forward_objects_dense, with its BN sequence:
-        -> (model, q [n * R, 1, OH, OW] object-major, the masks on the device, n, R)."""
-        if self.method != 'reinforcement' or style not in (0, 1):
-            raise ValueError("%s: reinforcement styles 0 (grasp) and 1 (suction)" % what)
+        """The one engine call behind forward_objects, forward_objects_dense and forward_class_objects, with its BN sequence:
+        -> (model, q [n * R, HEAD_OUT, OH, OW] object-major, the masks on the device, n, R).  The caller checks the method."""
+        if style not in (0, 1):
+            raise ValueError("%s: styles 0 (grasp) and 1 (suction)" % what)
         model = self.model_target if is_target else self.model
         d, m = self._objects_on_device(model, depth_heightmap, mask_depth)
         n = int(m.shape[0])
@@ -245,6 +245,8 @@ class Trainer(object):
         on the device by the input kernel (the host ships the heightmap and the masks once).  BN
         running statistics are updated in the reference's order and count.
         Returns conf[n_objects, R] float64 (styles 0 / 1), or the device tensor [n*R] if asked."""
+        if self.method != 'reinforcement':
+            raise ValueError("forward_objects: reinforcement method only (the reactive net's form is forward_class_objects)")
         _, q, _, n, R = self._object_maps("forward_objects", depth_heightmap, mask_depth, style, is_target)
         if q.shape[2] * q.shape[3] != 1:
             raise NotImplementedError("dense Q maps")
@@ -253,8 +255,8 @@ class Trainer(object):
         return q.reshape(n, R).cpu().numpy().astype(np.float64)
 
     def _object_pair_maps(self, depth_heightmap, mask_depth, is_target):
-        """The one engine call behind forward_object_pairs and forward_object_pairs_dense, with its BN sequence: style 2, rotation
-        0, the mask of pair (g < s) = mask[g] + mask[s] -> (model, q [n_pairs, 1, OH, OW], the masks on the device, [(g, s)]); q
+        """The one engine call behind forward_object_pairs, forward_object_pairs_dense and forward_class_object_pairs, with its BN
+        sequence: style 2, rotation 0, the mask of pair (g < s) = mask[g] + mask[s] -> (model, q [n_pairs, HEAD_OUT, OH, OW], the masks on the device, [(g, s)]); q
         and the masks are None without a pair (nothing runs)."""
         model = self.model_target if is_target else self.model
         n = int(np.asarray(mask_depth).shape[0])
@@ -706,9 +708,19 @@ class Trainer(object):
         "suction": [...]}, one (rotation, (iy, ix), conf) per object or None.  is_target evaluates the target net (the future
         reward of get_label_value in this frame)."""
         self._require_scene("best_scene_actions", depth_heightmap)
+
+        def argmax(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream):
+            eng.scene_argmax_objects(q.data_ptr(), q.shape[2] * q.shape[3], n_maps, aff, hm, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
+                                     group_of, groups, idx, val, stream)
+        return self._best_scene_objects("best_scene_actions", depth_heightmap, mask_depth, is_ets, is_target, argmax)
+
+    def _best_scene_objects(self, what, depth_heightmap, mask_depth, is_ets, is_target, argmax):
+        """The body of best_scene_actions and best_scene_class_actions (the caller has checked method and geometry): one forward per
+        primitive, one argmax(engine, q, n_maps, affines, hm, masks, mask_a, mask_b, group of every map, n_groups, idx pointer, val
+        pointer, stream) on its maps, one read-back, and the host decode of index -> (object, rotation, pixel)."""
         n = int(np.asarray(mask_depth).shape[0])
         if n < 1:
-            raise ValueError("best_scene_actions: mask_depth holds no object")
+            raise ValueError("%s: mask_depth holds no object" % what)
         hm = int(np.shape(depth_heightmap)[-1])
         n_pairs = n * (n - 1) // 2 if is_ets else 0
         idx = val = None
@@ -722,7 +734,7 @@ class Trainer(object):
                 rots = [(0, model.gnum_rotations)] * groups
                 mask_a, mask_b = [g for g, _ in pair_list], [s_ for _, s_ in pair_list]
             else:
-                model, q, m, groups, per = self._object_maps("best_scene_actions", depth_heightmap, mask_depth, style, is_target)
+                model, q, m, groups, per = self._object_maps(what, depth_heightmap, mask_depth, style, is_target)
                 rots = [(r, per) for k in range(groups) for r in range(per)]
                 mask_a, mask_b = [k for k in range(groups) for r in range(per)], [-1] * (groups * per)
             if idx is None:
@@ -730,11 +742,11 @@ class Trainer(object):
                 val = torch.empty(2 * n + n_pairs, dtype=torch.float32, device=q.device)
             off = sum(c[1] for c in calls)
             eng, aff, _, stream = self._scene_call(model, q, depth_heightmap, rots)
-            eng.scene_argmax_objects(q.data_ptr(), q.shape[2] * q.shape[3], len(rots), aff, hm, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
-                                     [j // per for j in range(len(rots))], groups, idx[off:].data_ptr(), val[off:].data_ptr(), stream)
+            argmax(eng, q, len(rots), aff, hm, m, mask_a, mask_b, [j // per for j in range(len(rots))], groups,
+                   idx[off:].data_ptr(), val[off:].data_ptr(), stream)
             calls.append((off, groups, per))
             kept[name] = q
-        self._last_object_q = kept        # the maps behind the result, object-major: "grasp" / "suction" [n * R, 1, OH, OW], "pairs" [n_pairs, 1, OH, OW]
+        self._last_object_q = kept        # the maps behind the result, object-major: "grasp" / "suction" [n * R, HEAD_OUT, OH, OW], "pairs" [n_pairs, HEAD_OUT, OH, OW]
         i_all, v_all = idx.cpu().numpy(), val.cpu().numpy().astype(np.float64)
 
         def decode(off, groups, per):
@@ -950,6 +962,68 @@ class Trainer(object):
         rots = self._scene_rotations(self.model, style, -1)
         eng, aff, hm, stream = self._scene_call(self.model, q, depth_heightmap, rots)
         return self._best_scene(q, hm, rots, lambda idx, val: eng.scene_class_argmax(q.data_ptr(), q.shape[0], aff, hm, 0, idx, val, stream))
+
+    # ---- the reactive net per object: the loops of code/main.py:158-195, which run for both methods --------------------------------
+    def _require_class_objects(self, what, depth_heightmap, mask_depth):
+        """Reactive method, masks [n_objects >= 1, H, H] like the heightmap: checked before anything reaches an engine."""
+        self._require_reactive(what)
+        shape = tuple(np.shape(mask_depth))
+        if len(shape) != 3 or shape[1:] != tuple(np.shape(depth_heightmap)) or shape[1] != shape[2]:
+            raise ValueError("%s: mask_depth must be [n_objects, H, H] like the square heightmap, got %s" % (what, shape))
+        if shape[0] < 1:
+            raise ValueError("%s: mask_depth holds no object" % what)
+
+    def _class_maps_out(self, q, logits, return_device):
+        p = q if logits else torch.softmax(q, dim=-3)
+        return p if return_device else p.cpu().numpy().astype(np.float64)
+
+    def forward_class_objects(self, depth_heightmap, mask_depth, style=0, logits=False, return_device=False):
+        """forward_objects for the reactive net, on any heightmap from 224^2 up - the loop of code/main.py:158-166 with
+        forward_class_maps(depth, depth * mask_depth[k], style) in place of the scalar forward: ONE engine call, R + n trunk
+        passes, the products formed on the device, BN running statistics updated in the order and count of the reference's loop.
+        Returns float64 [n_objects, R, 3, OH, OW] class probabilities (softmax over the class axis on the device, as
+        forward_class_maps'; `logits` = the raw head output instead), or the float32 device tensor of that shape if asked.  The
+        maps are in the rotated frame of their rotation; OH = OW = 1 at 224^2, where [k, r, 0, 0, 0] is the reactive
+        Trainer.forward's P(success).  Styles 0 / 1, reactive method only."""
+        self._require_class_objects("forward_class_objects", depth_heightmap, mask_depth)
+        _, q, _, n, R = self._object_maps("forward_class_objects", depth_heightmap, mask_depth, style, False)
+        return self._class_maps_out(q.reshape(n, R, 3, q.shape[2], q.shape[3]), logits, return_device)
+
+    def forward_class_object_pairs(self, depth_heightmap, mask_depth, logits=False, return_device=False):
+        """forward_object_pairs for the reactive net (code/main.py:183-192): style 2, rotation 0, the mask of pair (g < s) is
+        mask[g] + mask[s], one engine call with the reference's BN sequence.  Returns (float64 [n_pairs, 3, OH, OW] class
+        probabilities - `logits` = the raw head output; the float32 device tensor if asked -, [(g, s)]); with fewer than two objects
+        nothing runs and the maps are [0, 3, OH, OW].  Reactive method only."""
+        self._require_class_objects("forward_class_object_pairs", depth_heightmap, mask_depth)
+        model, q, _, idx = self._object_pair_maps(depth_heightmap, mask_depth, False)
+        if q is None:
+            side = self.dense_map_size(np.shape(depth_heightmap)[-1])
+            q = torch.empty((0, 3, side, side), dtype=torch.float32, device=model._flat_params.device if return_device else "cpu")
+        return self._class_maps_out(q, logits, return_device), idx
+
+    def best_scene_class_actions(self, depth_heightmap, mask_depth, is_ets=True, cls=0):
+        """best_scene_actions for the reactive net, for a heightmap larger than 224^2: the per-step evaluation of
+        code/main.py:158-195 - which the reference runs for both methods - with every object's three logit maps rotated back onto
+        the heightmap, the softmax taken at the pixel, and P(class `cls`) read on that object's OWN pixels (mask_depth[k] != 0; for a
+        pair (g, s) the pixels of either object).  One engine forward per primitive and one smg_scene_class_argmax_objects on the
+        logits and the masks tensor that forward used; neither the n * R scene-frame maps nor masked copies are written, an
+        unselected pixel costs no exponential, and the host reads back one (index, value) pair per object and primitive.
+        Returns best_scene_actions' dict with its conventions: bestg_id / bests_id = (object, rotation), bestg_pixel / bests_pixel
+        = (iy, ix), bestg_conf / bests_conf = P(class cls) there - None, None and -inf when no object has a selected pixel with a
+        window -; bestgs_num = (g, s), bestgs_pixel, bestgs_conf (None / None / 0 with fewer than two objects or is_ets False);
+        per_object = {"grasp": [...], "suction": [...]}, one (rotation, (iy, ix), conf) per object or None.  The logits behind the
+        result stay in self._last_object_q.  There is no is_target: the reactive method has no target net.
+        Which primitive to execute is the caller's business: code/main.py:221-226 compares bestg_conf, bests_conf and
+        2 * bestgs_conf (the pair's confidence counts twice, for both methods) and takes the largest."""
+        self._require_class_objects("best_scene_class_actions", depth_heightmap, mask_depth)
+        if cls not in (0, 1, 2):
+            raise ValueError("best_scene_class_actions: cls must be 0, 1 or 2")
+        self._scene_geometry(np.shape(depth_heightmap)[-1])
+
+        def argmax(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream):
+            eng.scene_class_argmax_objects(q.data_ptr(), n_maps, aff, hm, cls, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
+                                           group_of, groups, idx, val, stream)
+        return self._best_scene_objects("best_scene_class_actions", depth_heightmap, mask_depth, is_ets, False, argmax)
 
     def train_batch_scene_class_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, grad_sync=None,
                                        return_q=False):
