@@ -362,7 +362,9 @@ int smg_layout_trunk_split(int head_out, int trunk_id, int64_t* offset);
  *   2  fp16 storage of activations with fp16 forward products; gradients stored and multiplied in bf16 (fp32 exponent range:
  *      no loss scaling).
  * In every mode parameters, their gradients, Adam, BN statistics, every accumulation, the input image, the stem plane and the
- * head's feature buffers stay fp32.  Takes effect with the next smg_forward (a saved forward of another mode is dropped). */
+ * head's feature buffers stay fp32.  Takes effect with the next smg_forward (a saved forward of another mode is dropped).
+ * A CHANGE of mode waits for the device and zeroes the mode-typed buffers: their padding rows are read as they lie and must not
+ * hold the other storage type's words. */
 int smg_engine_set_precision(smg_engine* e, int precision);
 
 /* Engine switches by name.  "deterministic" (0 / 1): the 1x1-convolution weight gradients (conv1 of every dense layer,

@@ -96,7 +96,7 @@ struct smg_engine {
     // activations
     // (X, Bt, G, GS, D2 hold fp32 elements in mode 0 and 16-bit elements in modes 1 / 2: they are allocated for fp32 and
     // addressed through el(); everything else is fp32 in every mode)
-    float* img4 = nullptr; float* stem = nullptr; float* X[4] = {}; float* Bt = nullptr;
+    float* img4 = nullptr; float* stem = nullptr; float* X[4] = {}; float* Bt = nullptr; int64_t bt_floats = 0;
     std::vector<int64_t> bt_off[4];          // ELEMENT offset of each layer's bottleneck buffer
     unsigned char* argmax = nullptr;
     float* F = nullptr; float* H1 = nullptr;

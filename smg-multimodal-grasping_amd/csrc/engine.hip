@@ -13,6 +13,28 @@ int smg_fail(int code, const std::string& msg) { g_err = msg; return code; }
 // ------------------------------------------------------------------------------------
 // creation
 // ------------------------------------------------------------------------------------
+// The mode-typed buffers (X, Bt, G', GS, D2: fp32 in mode 0, 16-bit in modes 1 / 2) all zero: +0 in every storage type.  No kernel of
+// the forward stores the padding rows [HW, HWp) of a block buffer, and the 1x1 kernels read them as they lie - in the 16-bit modes without
+// a clamp in the weight gradient (BwdWeightP: kH is operand kind 3 only), whose other operand is zero on those rows.  Those rows must
+// therefore never hold another storage type's bit patterns (an fp32 plane read as bf16 pairs holds inf and NaN patterns: inf * 0 = NaN
+// in a column of dW) nor what hipMalloc handed out: zeroed at creation and at every change of the precision mode.
+static int zero_typed_buffers(smg_engine* e) {
+    const int NS = e->max_streams;
+    for (int b = 0; b < 4; ++b) {
+        const size_t n = (size_t)NS * e->p_blk[b].HWp * kBlockCtot[b] * sizeof(float);
+        HIP_OK(hipMemset(e->X[b], 0, n));
+        HIP_OK(hipMemset(e->G[b], 0, n));
+    }
+    HIP_OK(hipMemset(e->Bt, 0, (size_t)e->bt_floats * sizeof(float)));
+    for (int k = 0; k < kRing; ++k) {
+        HIP_OK(hipMemset(e->D2[k], 0, (size_t)NS * e->p_blk[0].HWp * kBottleneck * sizeof(float)));
+        HIP_OK(hipMemset(e->GS[k], 0, (size_t)NS * e->p_blk[0].HWp * kGrowth * sizeof(float)));
+    }
+    HIP_OK(hipMemset(e->DY2, 0, (size_t)NS * e->p_blk[0].HWp * kBottleneck * sizeof(float)));
+    HIP_OK(hipDeviceSynchronize());      // (the engine's streams do not order themselves behind the null stream)
+    return 0;
+}
+
 static int engine_build(smg_engine* e) {
     const Layout& L = *e->L;
     const int NS = e->max_streams, NP = e->max_pairs;
@@ -56,6 +78,8 @@ static int engine_build(smg_engine* e) {
         HIP_OK(hipEventCreateWithFlags(&e->ev_side[k], hipEventDisableTiming));
     }
     ALLOC(e->DY2, (int64_t)NS * e->p_blk[0].HWp * kBottleneck);
+    e->bt_floats = bt_total;
+    if (int rc = zero_typed_buffers(e)) return rc;
     e->scene_tiles = (int)(((int64_t)(S / 2) * (S / 2) + kSceneTile - 1) / kSceneTile);      // (a heightmap of side hm pads to S >= 2 hm)
     ALLOC(e->scene_val, (int64_t)kSceneMaps * e->scene_tiles);
     ALLOC(e->scene_idx, (int64_t)kSceneMaps * e->scene_tiles);
@@ -828,6 +852,11 @@ int smg_engine_set_precision(smg_engine* e, int precision) {
     if (!e) return fail(-22, "engine is NULL");
     if (precision < 0 || precision > 2) return fail(-22, "precision must be 0 (fp32 storage, fp32-class split products), 1 (bf16 storage) or 2 (fp16 activations, bf16 gradients)");
     if (precision && e->generic3x3) return fail(-22, "SMG_CROSSCHECK=1 (the generic implicit-GEMM 3x3 path) exists in the fp32-class mode only");
+    if (precision != e->prec) {      // the buffers change their storage type: nothing of the old one may be read in the new (zero_typed_buffers)
+        HIP_OK(hipSetDevice(e->device));
+        HIP_OK(hipDeviceSynchronize());      // (a rare call: whatever still reads or writes the buffers finishes first)
+        if (int rc = zero_typed_buffers(e)) return rc;
+    }
     e->prec = precision;
     step_graph_drop(e);
     e->have_fwd = false;        // activations saved by a forward of another precision are not backward-compatible

@@ -1,0 +1,241 @@
+"""The 16-bit yardstick of the storage-mode gates (tests/test_gpu_storage_gates.py): numpy models of what precision modes 1 ('bf16':
+bf16 storage of activations and gradients, one bf16 MFMA term per product) and 2 ('fp16': fp16 activations and forward products,
+bf16 gradients and backward products) round, and where.  tests/test_cpu_storage_ref.py proves them on the CPU (rounding against
+torch bit for bit, the storage chain against a torch 16-bit matmul, what each gate still catches, the keep-mask shares).
+
+Every rounding point below was read out of the kernel source; the citation stands next to the code that models it:
+  * every fp32 -> 16-bit conversion of the library is round-to-nearest-even: gemm.cuh pack_bf16 / pack_f16 are
+    __builtin_convertvector of a float pair (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32), st1 casts through them or through (_Float16),
+    stq / store_acc_rows / pack_unit / split4<1 | 2> go through pack2.  No store truncates (there is no round-toward-zero pack in csrc/).
+  * the A operand: the kernel forms it in fp32 - BN + ReLU of the stored input (bnrelu4, for fp16 operands clamped to 65504:
+    bnrelu4<H = true>, gemm.cuh kH), the 2 x 2 average of four of them (F_POOL / W_POOL), or the BN-corrected gradient (affine2) - and
+    rounds it ONCE to the operand type when it stages it (pack_unit<OP> / split4<OP>, OP = fwd_op / bwd_op_plain of the mode);
+  * the weights: pack_weights_kernel (elem.cuh) rounds each fp32 weight once, to `prec` for the forward packs and to bf16 for the
+    data-gradient packs; PK_STEM1 first rounds the fp64 sum of the three channel weights to fp32;
+  * the accumulator is fp32 (v_mfma_f32_32x32x16_bf16 / _f16); the epilogue rounds it once to the destination's storage type
+    (FwdConvP::epilogue st1 / store_acc_rows<DstT>, the halo forward's stq<ST>, BwdDataP::epilogue stq<GT> / st1<GT>).  The
+    destinations stem, feat, h1, df and dh1 are fp32 buffers in every mode (F32IO policies; smg_debug_read converts only x*, g*, bt*).
+
+The statistics trap.  Every producer of a 16-bit plane sums its BatchNorm statistics from the fp32 values BEFORE the 16-bit store:
+  * FwdConvP::epilogue (gemm.cuh): whole tiles sum dx = acc - s and dx^2 from the accumulator registers, partial tiles (double)acc;
+    the store of the same registers rounds afterwards (conv1 -> bt, the transitions -> x<t+1>[:, :C0]);
+  * conv3x3_halo_fwd_kernel (halo.cuh): `xd = (double)v[k]` of the accumulator, then stq<ST> (conv2 -> x<b>[:, cin:cin+32]);
+  * pool0_kernel (elem.cuh): `s[c] += (double)best[c]` of the fp32 maximum, after stq<XT> of the same values (x1[:, :64]);
+  * bn_stat_kernel only turns the fp64 sums into mean / invstd: it inherits its producer's form.
+  feat_kernel writes fp32 and sums what it wrote: the head's statistics are those of the stored values in every mode.
+The gates recompute each stage from the buffer the kernel read, with fp64 statistics over the STORED values, so the engine's mean
+and invstd differ from the reference's by what rounding did to the plane.  store_stat_slack bounds that: |x_stored - x| <= h, half a
+storage ulp per element, hence |delta mean| <= mean(h) and |delta var| <= 2 mean(|x - mean| h) + mean(h^2).  The element-wise gates
+add it to their bound (bn_store_slack, xhat_sum_slack), the keep-mask widens by it (keep16 / keep_s); no factor is widened.  Where the
+values before the store follow from an fp32 buffer - pool0's channels of x1, from the stem plane - the engine's statistics are
+recomputed instead of bounded (plane_stats / x1_stats): the product gates then need no slack."""
+import numpy as np
+
+import dense_ref as dr
+import stage_ref as sr
+from helpers import _fp32_blocked, _fp32_chain
+
+f32 = np.float32
+F16_MAX = 65504.0            # gemm.cuh kF16Max
+# per mode (models.set_precision name): storage of activations / of gradients, operand type of the forward / backward products
+MODES = {"bf16": dict(act="bf16", grd="bf16", fwd="bf16", bwd="bf16"),       # engine.h prec 1: ActT<1> / GrdT<1> = e_bf16, fwd_op(1) = bwd_op(1) = 1
+         "fp16": dict(act="fp16", grd="bf16", fwd="fp16", bwd="bf16")}       # prec 2: ActT<2> = e_f16, GrdT<2> = e_bf16, fwd_op(2) = 2, bwd_op(2) = 1
+MANT = {"bf16": 8, "fp16": 11}      # significand bits, the hidden one included
+
+
+# ---- rounding ----------------------------------------------------------------------------------------------------------------------------
+def round_bf16(x):
+    """fp32 -> bf16 -> fp32, round-to-nearest-even on the bits (v_cvt_pk_bf16_f32): add 0x7FFF + the lowest kept bit, cut 16 bits; NaN
+    stays NaN (quiet), inf stays inf, the largest finite values round up to inf"""
+    u = np.ascontiguousarray(x, dtype=f32).view(np.uint32)
+    r = ((u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) & np.uint32(0xFFFF0000))
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, (u | np.uint32(0x00400000)) & np.uint32(0xFFFF0000), r).astype(np.uint32).view(f32)
+
+
+def round_fp16(x):
+    """fp32 -> fp16 -> fp32, round-to-nearest-even on the bits (v_cvt_pk_f16_f32): subnormals below 2^-14 in steps of 2^-24, everything
+    from 65520 up becomes inf"""
+    u = np.ascontiguousarray(x, dtype=f32).view(np.uint32)
+    sign = u & np.uint32(0x80000000)
+    a = (u & np.uint32(0x7FFFFFFF)).view(f32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        # subnormal range (|x| < 2^-14): |x| * 2^24 < 2^10 is exact, and adding 2^23 - where fp32's ulp is 1 - rounds it to the nearest
+        # integer, ties to even, in fp32's own arithmetic; the subtraction and the scaling back are exact
+        sub = (((a * f32(2.0 ** 24)) + f32(2.0 ** 23)) - f32(2.0 ** 23)) * f32(2.0 ** -24)
+        au = a.view(np.uint32)
+        nrm = ((au + (np.uint32(0xFFF) + ((au >> np.uint32(13)) & np.uint32(1)))) & np.uint32(0xFFFFE000)).view(f32)
+        nrm = np.where(nrm >= f32(65520.0), f32(np.inf), nrm)
+    out = np.where(a < f32(2.0 ** -14), sub, nrm)
+    out = np.where(np.isnan(a), f32(np.nan), out).astype(f32)
+    return (out.view(np.uint32) | sign).view(f32)
+
+
+def rnd(x, kind):
+    """round an fp32 array once to `kind` ('bf16' / 'fp16'; None or 'fp32': left as it is)"""
+    x = np.asarray(x, dtype=f32)
+    return round_bf16(x) if kind == "bf16" else round_fp16(x) if kind == "fp16" else x
+
+
+def half_ulp(v, kind):
+    """half a unit in the last place of `kind` at |v| (fp64 in, fp64 out): what one rounding to storage can move a value of that size;
+    below fp16's normal range the ulp is the subnormal step 2^-24"""
+    v = np.abs(np.asarray(v, dtype=np.float64))
+    e = np.frexp(np.maximum(v, 1e-300))[1] - 1                      # floor(log2 |v|)
+    e = np.maximum(e, -14 if kind == "fp16" else -126)
+    return np.ldexp(0.5, e - (MANT[kind] - 1))
+
+
+# ---- operands and products -------------------------------------------------------------------------------------------------------------------
+def operand(a32, kind):
+    """the A operand as the kernel stages it: the fp32 value, clamped to fp16's largest finite value where it becomes an fp16 operand
+    (bnrelu4<H>: v_med3_f32(., 0, 65504) - in-range values untouched), rounded once (pack_unit<OP>)"""
+    a32 = np.asarray(a32, dtype=f32)
+    return rnd(np.minimum(a32, f32(F16_MAX)) if kind == "fp16" else a32, kind)
+
+
+def storage_chain(a32, w32, op, dst=None):
+    """out[m][n] = sum_k a[m][k] * w[n][k]: operands rounded once to `op` (the A operand handed in is the fp32 value the kernel forms;
+    the weight as pack_weights_kernel packs it), accumulated as helpers._fp32_chain does, the result rounded once to the destination's
+    storage type `dst` (None: an fp32 buffer)"""
+    return rnd(_fp32_chain(operand(a32, op), rnd(w32, op)), dst)
+
+
+def storage_blocked(a32, w32, op_a, op_w, blk=64):
+    """out[m][n] = sum_k a[k][m] * w[k][n] over a long k (the weight gradients): both operands rounded once to their operand types,
+    reduced as helpers._fp32_blocked does; the weight gradient itself is fp32 in every mode"""
+    return _fp32_blocked(np.ascontiguousarray(operand(a32, op_a)), np.ascontiguousarray(operand(w32, op_w)), blk)
+
+
+def conv2_chain(bt, H, W, g2, b2, w2, pix, op, dst):
+    """the storage chain of a dense layer's 3x3: BN + ReLU of the stored bottleneck rounded once per element (the halo kernel packs the
+    halo once: conv3x3_halo_fwd_kernel s_store -> pack_unit<OP>; zero padding applies after it), the PK_HF weights rounded to `op`"""
+    return storage_chain(dr.im2col(dr.act32(bt, g2, b2), H, W, pix), dr.w2_fwd_mat(w2).astype(f32), op, dst)
+
+
+def stored_bound(ref, k, mag, kind, slack=0.0):
+    """bound of an element-wise stage whose result is stored in `kind`: the mode-0 bound k * 2^-24 * mag (+ slack, absolute) on the fp32
+    value, plus half a storage ulp at the largest value that bound allows"""
+    b32 = k * sr.U * np.asarray(mag, dtype=np.float64) + slack
+    return b32 + half_ulp(np.abs(ref) + b32, kind)
+
+
+# ---- statistics summed before the 16-bit store -----------------------------------------------------------------------------------------------
+def store_stat_slack(v, kind):
+    """v [pixels][C]: a plane as STORED in `kind`, whose producer summed the unrounded fp32 values.  Per channel (M, R) with
+    |mean_engine - mean(v)| <= M  and  |invstd_engine / invstd(v) - 1| <= R  (derivation in the module docstring; R from
+    invstd' / invstd = 1 / sqrt(1 - delta_var * invstd^2) at the largest delta_var)."""
+    v = np.asarray(v, dtype=np.float64)
+    mean, inv = sr.bn_stats(v)
+    h = half_ulp(v, kind)
+    M = h.mean(0)
+    dvar = 2.0 * (np.abs(v - mean) * h).mean(0) + (h * h).mean(0)
+    t = np.minimum(dvar * inv * inv, 0.75)
+    return M, 1.0 / np.sqrt(1.0 - t) - 1.0
+
+
+def bn_store_slack(v, g, kind):
+    """what store_stat_slack moves gamma * (x - mean) * invstd + beta by, per element, in absolute units"""
+    v = np.asarray(v, dtype=np.float64)
+    mean, inv = sr.bn_stats(v)
+    M, R = store_stat_slack(v, kind)
+    return np.abs(np.asarray(g, dtype=np.float64) * inv) * (M * (1.0 + R) + np.abs(v - mean) * R)
+
+
+def xhat_sum_slack(dy, v, S):
+    """What the statistics' slack moves sum_p dy[p] * xhat[p] by (a BatchNorm weight gradient over a 16-bit plane v), per channel.  With
+    the engine's mean_e = mean - d and invstd_e = (1 + r) invstd:  xhat_e = (1 + r) (xhat + d * invstd), so the sum moves by EXACTLY
+    r * sum(dy * xhat) + (1 + r) d invstd sum(dy):  <= R |sum dy xhat| + (1 + R) M invstd |sum dy|  - the two sums as they cancel, not
+    their terms' magnitudes (behind a BatchNorm both are what eps leaves of them)."""
+    dy, v = np.asarray(dy, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    xh = (v - S.mean) * S.inv
+    return S.R * np.abs((dy * xh).sum(0)) + (1.0 + S.R) * S.M * S.inv * np.abs(dy.sum(0))
+
+
+def keep16(v, g, b, kind):
+    """the borderline-ReLU rule of the data-gradient gates for a 16-bit plane: stage_ref.bn_keep's threshold plus bn_store_slack - an
+    element whose pre-activation the engine's statistics can carry across zero is the mask's business, not the product's"""
+    mean, inv = sr.bn_stats(v)
+    pre = sr.bn_pre(v, g, b)
+    sc = np.abs(np.asarray(v, dtype=np.float64) - mean) * inv * np.abs(g) + np.abs(b)
+    return np.abs(pre) > 1e-5 * sc + bn_store_slack(v, g, kind)
+
+
+# ---- BN + ReLU of a 16-bit plane with the statistics the ENGINE holds, as far as they can be known ------------------------------------------
+class PlaneStats:
+    """per channel: mean, invstd (fp64) and the slack (M, R) of store_stat_slack - zero where the engine's statistics are known"""
+    def __init__(self, mean, inv, M, R):
+        self.mean, self.inv, self.M, self.R = mean, inv, M, R
+
+    def cols(self, c):
+        return PlaneStats(self.mean[c], self.inv[c], self.M[c], self.R[c])
+
+
+def plane_stats(v, kind, known=None):
+    """Statistics of the stored plane v [pixels][C] with their slack.  known = (channel slice, the plane's values BEFORE the store on
+    those channels, recomputed to fp32 accuracy from an fp32 buffer): there the engine's statistics are those of that plane, no slack.
+    The one such case is x1[:, :64]: pool0_kernel's fp32 maxima follow from the fp32 stem plane (x1_stats).  It matters: a rotated or
+    masked heightmap is mostly one background value, which rounds ONE way on thousands of pixels - the engine's mean sits up to half a
+    storage ulp off the stored plane's, and (x - mean) * invstd of exactly those background pixels is the small difference of the two."""
+    mean, inv = sr.bn_stats(v)
+    M, R = store_stat_slack(v, kind)
+    if known is not None:
+        c, pre = known
+        mean, inv, M, R = mean.copy(), inv.copy(), M.copy(), R.copy()
+        mean[c], inv[c] = sr.bn_stats(pre)
+        M[c] = R[c] = 0.0
+    return PlaneStats(mean, inv, M, R)
+
+
+def x1_stats(x1, stem, Hs, g0, b0, kind):
+    """x1 [HW1][256] as stored, stem [Hs * Hs][64] the fp32 stem plane of the same stream: channels 0..63 are pool0's, whose fp32 values
+    before the store are stage_ref.pool0_32 of the stem (K_BN fp32 roundings from the kernel's: nothing at 16-bit resolution)"""
+    pre = sr.pool0_32(stem, Hs, Hs, g0, b0)
+    assert pre.shape == (len(x1), 64)
+    return plane_stats(x1, kind, known=(slice(0, 64), pre))
+
+
+def bn_pre_s(v, g, b, S):
+    """gamma * (x - mean) * invstd + beta in fp64 with the statistics S"""
+    return (np.asarray(v, dtype=np.float64) - S.mean) * (S.inv * np.asarray(g, dtype=np.float64)) + np.asarray(b, dtype=np.float64)
+
+
+def act64_s(v, g, b, S):
+    return np.maximum(bn_pre_s(v, g, b, S), 0.0)
+
+
+def act32_s(v, g, b, S):
+    """stage_ref.bn32 with the statistics S: mean and gamma * invstd rounded once, (x - mean) * sc + beta, ReLU"""
+    sc = (np.asarray(g, dtype=np.float64) * S.inv).astype(f32)
+    return np.maximum(((np.asarray(v, dtype=f32) - S.mean.astype(f32)) * sc + np.asarray(b, dtype=f32)).astype(f32), f32(0))
+
+
+def slack_s(v, g, S):
+    """bn_store_slack with the statistics S (zero on the channels whose statistics are known)"""
+    return np.abs(np.asarray(g, dtype=np.float64) * S.inv) * (S.M * (1.0 + S.R) + np.abs(np.asarray(v, dtype=np.float64) - S.mean) * S.R)
+
+
+def keep_s(v, g, b, S):
+    """keep16 with the statistics S"""
+    sc = np.abs(np.asarray(v, dtype=np.float64) - S.mean) * S.inv * np.abs(g) + np.abs(b)
+    return np.abs(bn_pre_s(v, g, b, S)) > 1e-5 * sc + slack_s(v, g, S)
+
+
+# ---- the variant table of modes 1 / 2 (forward.hip) --------------------------------------------------------------------------------------------
+def conv1_fwd_cfg16(HWp, ns):
+    """forward conv1 in modes 1 / 2: the wave-specialised kernel is `e->prec == 0` only, so the choice is between the three generic
+    configurations (small_wgs = 320)"""
+    wg128, wg64 = ns * HWp // 128, ns * HWp // 64 * 2
+    return "P128x128" if HWp % 128 == 0 and wg128 >= 320 else ("P32x64" if wg64 < 320 else "P64x64")
+
+
+def halo_tile(H, ns):
+    return 16 if ((H + 15) // 16) ** 2 * ns >= 200 else 8                     # wgrad_plan.h halo_tile (no precision in it)
+
+
+def transition_cfg(HWp_next):
+    return "P128x128" if HWp_next % 128 == 0 else "P64x128"                   # forward.hip: by the OUTPUT plane's padding
+
+
+def forward_chains(NS, H1):
+    return [NS // 2, NS - NS // 2] if NS >= 2 and NS * H1 * H1 >= 200000 else [NS]      # forward.hip two_chains
