@@ -3,6 +3,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,6 +16,16 @@ import synthetic  # noqa: E402
 from oracle import affordance as orc  # noqa: E402
 
 MEAN, STD = 0.01, 0.03
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    """the device of the gpu-marked tests; a test module takes the fixture by importing it by name"""
+    if not torch.cuda.is_available():
+        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
+    import smg_hip
+    smg_hip.lib()   # raises if libsmg_hip.so is missing
+    return torch.device("cuda:0")
 
 
 def probe_idx(n, k, tag):

@@ -11,21 +11,12 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import grads_within_fp32_class, MEAN, STD, oracle_net, orc, REPO
+from helpers import gpu, grads_within_fp32_class, MEAN, STD, oracle_net, orc, REPO  # noqa: F401  (gpu: the fixture, for the map modules to import by name)
 
 import scene_ref
 
 HEAD = "graspnet_val.grasp-val-"        # style 0's head (oracle.affordance.STYLE_HEAD)
 HEAD_OUT = {'reinforcement': 1, 'reactive': 3}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()
-    return torch.device("cuda:0")
 
 
 def make_trainer(method, seed, R=16):

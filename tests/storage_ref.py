@@ -219,23 +219,3 @@ def keep_s(v, g, b, S):
     """keep16 with the statistics S"""
     sc = np.abs(np.asarray(v, dtype=np.float64) - S.mean) * S.inv * np.abs(g) + np.abs(b)
     return np.abs(bn_pre_s(v, g, b, S)) > 1e-5 * sc + slack_s(v, g, S)
-
-
-# ---- the variant table of modes 1 / 2 (forward.hip) --------------------------------------------------------------------------------------------
-def conv1_fwd_cfg16(HWp, ns):
-    """forward conv1 in modes 1 / 2: the wave-specialised kernel is `e->prec == 0` only, so the choice is between the three generic
-    configurations (small_wgs = 320)"""
-    wg128, wg64 = ns * HWp // 128, ns * HWp // 64 * 2
-    return "P128x128" if HWp % 128 == 0 and wg128 >= 320 else ("P32x64" if wg64 < 320 else "P64x64")
-
-
-def halo_tile(H, ns):
-    return 16 if ((H + 15) // 16) ** 2 * ns >= 200 else 8                     # wgrad_plan.h halo_tile (no precision in it)
-
-
-def transition_cfg(HWp_next):
-    return "P128x128" if HWp_next % 128 == 0 else "P64x128"                   # forward.hip: by the OUTPUT plane's padding
-
-
-def forward_chains(NS, H1):
-    return [NS // 2, NS - NS // 2] if NS >= 2 and NS * H1 * H1 >= 200000 else [NS]      # forward.hip two_chains

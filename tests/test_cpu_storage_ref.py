@@ -26,6 +26,7 @@ import torch
 import dense_ref as dr
 import stage_ref as sr
 import storage_ref as st
+from gate_harness import conv1_fwd_cfg, forward_chains, halo_tile, transition_cfg
 from helpers import _WGRAD_GATE, MEAN, STD, orc
 from test_cpu_stage_ref import SCENES, _hp, _oracle_planes, _tiny_head, _tp
 
@@ -132,13 +133,13 @@ def test_store_stat_slack_bounds_what_rounding_does_to_the_statistics(kind):
 def test_variant_rules_of_the_16_bit_modes():
     """forward.hip, modes 1 / 2: conv1 never goes wave-specialised (`e->prec == 0`), so 80^2 with 6 streams (wg128 = 300 < 320 <= wg64 =
     1200) and 84^2 with 3 (HWp % 128 = 64, wg64 = 666) take CfgP64x64 - a configuration the mode-0 table selects in neither scene"""
-    S640 = [st.conv1_fwd_cfg16(h, 6) for h in (25600, 6400, 1600, 448)]
-    S672 = [st.conv1_fwd_cfg16(h, 3) for h in (28288, 7104, 1792, 448)]
+    S640 = [conv1_fwd_cfg(h, 6, False) for h in (25600, 6400, 1600, 448)]
+    S672 = [conv1_fwd_cfg(h, 3, False) for h in (28288, 7104, 1792, 448)]
     assert S640 == ["P128x128", "P64x64", "P32x64", "P32x64"] and S672 == ["P128x128", "P64x64", "P32x64", "P32x64"]
-    assert [st.halo_tile(h, 6) for h in (160, 80, 40, 20)] == [16, 8, 8, 8] and [st.halo_tile(h, 3) for h in (168, 84, 42, 21)] == [16, 8, 8, 8]
-    assert [st.transition_cfg(h) for h in (6400, 1600, 448)] == ["P128x128", "P64x128", "P64x128"]
-    assert [st.transition_cfg(h) for h in (7104, 1792, 448)] == ["P64x128", "P128x128", "P64x128"]
-    assert st.forward_chains(6, 160) == [6] and st.forward_chains(3, 168) == [3] and st.forward_chains(17, 160) == [8, 9]
+    assert [halo_tile(h, 6) for h in (160, 80, 40, 20)] == [16, 8, 8, 8] and [halo_tile(h, 3) for h in (168, 84, 42, 21)] == [16, 8, 8, 8]
+    assert [transition_cfg(h) for h in (6400, 1600, 448)] == ["P128x128", "P64x128", "P64x128"]
+    assert [transition_cfg(h) for h in (7104, 1792, 448)] == ["P64x128", "P128x128", "P64x128"]
+    assert forward_chains(6, 160) == [6] and forward_chains(3, 168) == [3] and forward_chains(17, 160) == [8, 9]
 
 
 # ---- what the gates still catch at 16-bit resolution ---------------------------------------------------------------------------------------------

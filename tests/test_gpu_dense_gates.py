@@ -6,8 +6,8 @@ dense layers have theirs in tests/test_gpu_stage_gates.py.
 Four cases; the walk picks the kernel instantiation from the plane, the number of streams of the call (of the forward CHAIN: calls of
 8 streams and more run as two chains of NS / 2 and NS - NS / 2 streams, forward.hip) and the layer's place in its group.  VARIANTS
 below is that choice per case and block, test_geometry_selects_the_variants_of_the_table derives it from eng.H / eng.HWp with the
-rules of the source - halo_tile (wgrad_plan.h: 16 x 16 tiles from 200 tiles per launch), HWp % 128 and the small_wgs = 320 rule of
-the forward conv1 (forward.hip), w1_partial_tiles / plan_layer_wgrads (wgrad_plan.h: the 1x1 weight gradient adds with fp32 atomics
+rules of the source (tests/gate_harness.py) - halo_tile (wgrad_plan.h: 16 x 16 tiles from 200 tiles per launch), HWp % 128 and the
+small_wgs = 320 rule of the forward conv1 (forward.hip), w1_partial_tiles / plan_layer_wgrads (wgrad_plan.h: the 1x1 weight gradient adds with fp32 atomics
 only in calls of <= 4 streams on planes of <= 1600 pixels) and gs_on_side (backward.hip):
 
  case  call                          plane (HWp / HW)       conv1 forward   3x3 tile, fwd / bwd        1x1 wgrad        GS / reduces
@@ -60,17 +60,12 @@ import torch
 
 import dense_ref as dr
 import stage_ref as sr
-from helpers import _WGRAD_BLK, _WGRAD_GATE, MEAN, STD, product_net
+from gate_harness import SCENES, TRUNK, GateCtx, conv1_fwd_cfg, forward_chains, gate, gpu, halo_tile, wgrad_gate  # noqa: F401  (gpu: the fixture)
+from helpers import _WGRAD_BLK, _WGRAD_GATE, _fp32_blocked, product_net
 
 pytestmark = pytest.mark.gpu
 
-_DQ = [1.0, -1.0, 0.5, 1e-6, -0.25, 0.75, -0.5, 0.3]
-CASES = {"A": dict(seed=0, size=224, S=640, rots=[0, 3, 7, 10, 13], dq=[[1.0], [-1.0], [0.5], [1e-6], [-0.25]]),
-         "B": dict(seed=8, size=236, S=672, rots=[2, 11], dq=[[1.0, -0.5, 0.25, -2.0], [-0.75, 1.5, -1e-3, 0.4]]),
-         "C": dict(seed=0, size=224, S=640, rots=[3], dq=[[1.0]]),
-         "D": dict(seed=0, size=224, S=640, rots=list(range(16)), dq=[[_DQ[j % 8]] for j in range(16)])}
-# H and HWp of blocks 1-4 (eng.H[2:6] / eng.HWp[2:6])
-GEOMETRY = {640: ([160, 80, 40, 20], [25600, 6400, 1600, 448]), 672: ([168, 84, 42, 21], [28288, 7104, 1792, 448])}
+CASES = {"A": SCENES["S640x6"], "B": SCENES["S672x3"], "C": SCENES["S640x2"], "D": SCENES["S640x17"]}
 # per block: (conv1 forward, 3x3 tile forward, 3x3 tile backward, bounds-checked 16 x 16, gs_on_side); per case: the 1x1 weight gradient of blocks 1-4
 VARIANTS = {"A": ([("P128x128", 16, 16, False, False), ("ws", 8, 8, False, False), ("P32x64", 8, 8, False, False), ("P32x64", 8, 8, False, False)], ["ws"] * 4),
             "B": ([("P128x128", 16, 16, True, False), ("ws", 8, 8, False, False), ("P32x64", 8, 8, False, False), ("P32x64", 8, 8, False, True)], ["ws", "ws", "ws", "atomics"]),
@@ -81,21 +76,7 @@ BWD_LAYERS = {"A": [(1, 3), (1, 6), (2, 5), (2, 6), (3, 21), (4, 1), (4, 14), (4
               "B": [(1, 3), (1, 6), (2, 9), (3, 21), (3, 24), (4, 13), (4, 16)],
               "C": [(2, 12), (3, 21), (3, 24), (4, 13), (4, 16)],
               "D": [(2, 9), (2, 12)]}
-TRUNK = "grasp_depth_trunk.features."
 _STATE, _FWD = {}, {}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()   # raises if libsmg_hip.so is missing
-    return torch.device("cuda:0")
-
-
-class _Ctx:
-    pass
 
 
 def _ctx(gpu, case):
@@ -104,76 +85,29 @@ def _ctx(gpu, case):
         _STATE["net"] = product_net(0)
         _STATE["sd"] = {k: v.detach().cpu().numpy() for k, v in _STATE["net"].state_dict().items()}
     if case not in _STATE:
-        import synthetic
-        c = CASES[case]
-        x = _Ctx()
-        x.case, x.S, x.rots, x.net, x.sd = case, c["S"], c["rots"], _STATE["net"], _STATE["sd"]
-        depth, masks = synthetic.heightmap_scene(c["seed"], size=c["size"], n_boxes=8)
-        x.hm = torch.from_numpy(np.stack([depth, depth * masks[0]])).to(gpu)
-        x.NS = len(x.rots) + 1
-        x.streams = sorted({0, x.NS // 2, x.NS - 1})          # the first, a middle one, the last (masked) stream
-        _STATE[case] = x
+        _STATE[case] = GateCtx(_STATE["net"], _STATE["sd"], CASES[case], gpu)
     return _STATE[case]
 
 
-def _forward(x):
-    import models
-    q = x.net.run(0, x.rots, 16, heightmaps=x.hm, mean=MEAN, std=STD, keep_for_backward=True)
-    torch.cuda.synchronize()
-    x.eng = models._ENGINES[(0, x.S, x.net.HEAD_OUT)]
-    H, HWp = GEOMETRY[x.S]
-    assert list(x.eng.H[2:6]) == H and list(x.eng.HWp[2:6]) == HWp, (x.eng.H, x.eng.HWp)
-    x.H, x.HWp = H, HWp
-    return q
+def _streams(x):
+    return sorted({0, x.NS // 2, x.NS - 1})          # the first, a middle one, the last (masked) stream
 
-
-def _rd(x, name, block, C, streams=None, pad=False):
-    """[streams][HW][C] of a [NS][HWp][C] buffer of `block`'s plane (pad: all HWp rows); streams None: all NS of the call"""
-    HW, HWp = x.H[block - 1] ** 2, x.HWp[block - 1]
-    a = x.eng.debug_read(name, count=x.NS * HWp * C).reshape(x.NS, HWp, C)
-    a = a if streams is None else a[streams]
-    return a if pad else np.ascontiguousarray(a[:, :HW])
-
-
-def _lp(x, block, layer, name):
-    return x.sd[TRUNK + "denseblock%d.denselayer%d.%s" % (block, layer, name)]
-
-
-def _gate(what, e_prod, e_yard, factor, e_whole=None, n=0):
-    msg = "%s: err/sum|ab| rms product %.3e, fp32 yardstick %.3e: ratio %.2f" % (what, e_prod, e_yard, e_prod / e_yard)
-    if e_whole is not None:
-        msg += "; whole plane %.3e: ratio %.2f" % (e_whole, e_whole / e_yard)
-    print(msg + (" (%d elements)" % n if n else ""))
-    assert e_prod <= factor * e_yard, (what, e_prod, e_yard)
-    if e_whole is not None:
-        assert e_whole <= factor * e_yard, (what, "whole plane", e_whole, e_yard)
 
 # ---- the variant table ---------------------------------------------------------------------------------------------------------------------
-def _halo_tile(H, ns):
-    return 16 if ((H + 15) // 16) ** 2 * ns >= 200 else 8                     # wgrad_plan.h halo_tile
-
-
-def _conv1_fwd_cfg(HWp, ns):
-    wg128, wg64 = ns * HWp // 128, ns * HWp // 64 * 2                            # forward.hip, small_wgs = 320
-    if not (HWp % 128 == 0 and wg128 >= 320) and wg64 >= 320 and HWp % 64 == 0:
-        return "ws"
-    return "P128x128" if HWp % 128 == 0 and wg128 >= 320 else ("P32x64" if wg64 < 320 else "P64x64")
-
-
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_geometry_selects_the_variants_of_the_table(gpu, case):
     x = _ctx(gpu, case)
-    _forward(x)
+    x.forward()
     NS = x.NS
-    chains = [NS // 2, NS - NS // 2] if NS >= 2 and NS * x.H[0] ** 2 >= 200000 else [NS]      # forward.hip two_chains
+    chains = forward_chains(NS, x.H[2])
     got = []
     for b in range(4):
-        H, HWp = x.H[b], x.HWp[b]
-        c1, t_f = {_conv1_fwd_cfg(HWp, ns) for ns in chains}, {_halo_tile(H, ns) for ns in chains}
+        H, HWp = x.H[2 + b], x.HWp[2 + b]
+        c1, t_f = {conv1_fwd_cfg(HWp, ns, True) for ns in chains}, {halo_tile(H, ns) for ns in chains}
         assert len(c1) == 1 and len(t_f) == 1, (case, b, c1, t_f)              # both chains take the same instantiations
-        t_b = _halo_tile(H, NS)
+        t_b = halo_tile(H, NS)
         got.append((c1.pop(), t_f.pop(), t_b, t_b == 16 and H % 16 != 0, NS <= 4 and H * H <= 1600))
-    w1 = ["ws" if NS > 4 or H * H > 1600 else "atomics" for H in x.H]           # w1_partial_tiles (cin > 64: every gated layer)
+    w1 = ["ws" if NS > 4 or H * H > 1600 else "atomics" for H in x.H[2:]]           # w1_partial_tiles (cin > 64: every gated layer)
     print("case %s: %d streams, forward chains %s: %s, 1x1 weight gradient %s" % (case, NS, chains, got, w1))
     assert (got, w1) == VARIANTS[case]
 
@@ -184,18 +118,18 @@ def _fwd(gpu, case):
     if case not in _FWD:
         _FWD.clear()                                                            # one case's buffers at a time
         x = _ctx(gpu, case)
-        _forward(x)
+        x.forward()
         B = {}
         for b in range(1, 5):
-            full = _rd(x, "x%d" % b, b, dr.CT[b - 1], pad=True)
-            HW = x.H[b - 1] ** 2
+            full = x.rd("x%d" % b, x.NS, 1 + b, dr.CT[b - 1], pad=True)
+            HW = x.H[1 + b] ** 2
             padrows = full[:, HW:]
             # the forward stores no row >= HW of x<b> (module docstring): whatever lies there is read by the 1x1 kernels, which clamp
             print("case %s x%d: %d padding rows per stream, largest |value| %.3e" % (case, b, padrows.shape[1], np.abs(padrows).max() if padrows.size else 0.0))
             assert np.isfinite(padrows).all()
-            B["x%d" % b] = full[x.streams][:, :HW].copy()
+            B["x%d" % b] = full[_streams(x)][:, :HW].copy()
         for b, l in FWD_LAYERS:
-            B["bt%d_%d" % (b, l)] = _rd(x, "bt%d_%d" % (b, l), b, 128, x.streams)
+            B["bt%d_%d" % (b, l)] = x.rd("bt%d_%d" % (b, l), x.NS, 1 + b, 128, _streams(x))
         _FWD[case] = B
     return _ctx(gpu, case), _FWD[case]
 
@@ -205,38 +139,24 @@ def _fwd(gpu, case):
 def test_forward_layer(gpu, case, block, layer):
     """norm1 + ReLU + conv1 from x<b>[:, :cin] and norm2 + ReLU + conv2 from the bottleneck, on three streams, whole planes"""
     x, B = _fwd(gpu, case)
-    H, cin = x.H[block - 1], dr.cin_of(block, layer)
-    g1, b1, w1 = _lp(x, block, layer, "norm1.weight"), _lp(x, block, layer, "norm1.bias"), _lp(x, block, layer, "conv1.weight").reshape(128, cin)
-    g2, b2, w2 = _lp(x, block, layer, "norm2.weight"), _lp(x, block, layer, "norm2.bias"), _lp(x, block, layer, "conv2.weight")
+    H, cin = x.H[1 + block], dr.cin_of(block, layer)
+    g1, b1, w1 = x.lp(block, layer, "norm1.weight"), x.lp(block, layer, "norm1.bias"), x.lp(block, layer, "conv1.weight").reshape(128, cin)
+    g2, b2, w2 = x.lp(block, layer, "norm2.weight"), x.lp(block, layer, "norm2.bias"), x.lp(block, layer, "conv2.weight")
     pix = dr.sample(H * H)
-    for k, n in enumerate(x.streams):
+    for k, n in enumerate(_streams(x)):
         X, BT = B["x%d" % block][k], B["bt%d_%d" % (block, layer)][k]
         ref, mag = dr.conv1_fwd(X[:, :cin], g1, b1, w1)
         chain = dr.conv1_chain(X[:, :cin], g1, b1, w1, pix)
-        _gate("case %s conv1 (%d,%d) K %d stream %d" % (case, block, layer, cin, n), dr.rms(BT[pix], ref[pix], mag[pix]), dr.rms(chain, ref[pix], mag[pix]), 2.0,
-              e_whole=dr.rms(BT, ref, mag), n=chain.size)
+        gate("case %s conv1 (%d,%d) K %d stream %d" % (case, block, layer, cin, n), dr.rms(BT[pix], ref[pix], mag[pix]), dr.rms(chain, ref[pix], mag[pix]), 2.0,
+             e_whole=dr.rms(BT, ref, mag), n=chain.size)
         ref, mag = dr.conv2_fwd(BT, H, H, g2, b2, w2)
         chain = dr.conv2_chain(BT, H, H, g2, b2, w2, pix)
         got = X[:, cin:cin + 32]
-        _gate("case %s conv2 (%d,%d) stream %d" % (case, block, layer, n), dr.rms(got[pix], ref[pix], mag[pix]), dr.rms(chain, ref[pix], mag[pix]), 2.0,
-              e_whole=dr.rms(got, ref, mag), n=chain.size)
+        gate("case %s conv2 (%d,%d) stream %d" % (case, block, layer, n), dr.rms(got[pix], ref[pix], mag[pix]), dr.rms(chain, ref[pix], mag[pix]), 2.0,
+             e_whole=dr.rms(got, ref, mag), n=chain.size)
 
 
 # ---- backward ----------------------------------------------------------------------------------------------------------------------------
-def _backward_to(gpu, x, stop):
-    """a fresh forward, then the backward up to `stop`; returns the gradients the walk has finished"""
-    q = _forward(x)
-    dq = torch.tensor(CASES[x.case]["dq"], dtype=torch.float32, device=gpu).view(q.shape)
-    x.net.zero_grad()
-    x.eng.set_option("debug_stop", stop)
-    try:
-        x.net._engine_backward(x.net._saved[1], dq)
-    finally:
-        x.eng.set_option("debug_stop", -1)
-    torch.cuda.synchronize()
-    return {n: p.grad.detach().cpu().numpy() for n, p in x.net.named_parameters() if p.grad is not None}
-
-
 def test_a_stopped_backward_leaves_nothing_in_the_affine_gradient_scratch(gpu):
     """The norm1 / transition-norm dbeta and dgamma go through a scratch that db_flush_kernel adds to the gradients - and zeroes - at
     the END of the walk.  A backward that leaves at a debug_stop must not hand its share to the next call: with this module in front
@@ -247,14 +167,14 @@ def test_a_stopped_backward_leaves_nothing_in_the_affine_gradient_scratch(gpu):
     names = [TRUNK + "denseblock%d.denselayer%d.norm1.%s" % (b, l, p) for b, l in ((4, 16), (4, 1), (3, 24), (1, 1)) for p in ("weight", "bias")]
 
     def step():
-        q = _forward(x)
+        q = x.forward()
         x.net.zero_grad()
         x.net._engine_backward(x.net._saved[1], torch.tensor(CASES["C"]["dq"], dtype=torch.float32, device=gpu).view(q.shape))
         torch.cuda.synchronize()
         g = dict(x.net.named_parameters())
         return {n: g[n].grad.detach().cpu().numpy().astype(np.float64) for n in names}
     before = step()
-    _backward_to(gpu, x, 300)
+    x.backward_to(300)
     after = step()
     for n in names:
         rel = np.abs(after[n] - before[n]).max() / np.abs(before[n]).max()
@@ -263,10 +183,9 @@ def test_a_stopped_backward_leaves_nothing_in_the_affine_gradient_scratch(gpu):
 
 
 def _wgrad_gate(what, got, a32, w64, w32):
-    e_prod, e_blk, ref, _ = dr.wgrad_errors(got, a32, w64, w32, blks=(_WGRAD_BLK,))
-    print("%s: err/sum|ab| rms product %.3e, blocked fp32 (chains + pairwise) %d-term %.3e over all %d terms, %d elements: ratio %.2f"
-          % (what, e_prod, _WGRAD_BLK, e_blk[_WGRAD_BLK], len(a32), ref.size, e_prod / e_blk[_WGRAD_BLK]))
-    assert e_prod <= _WGRAD_GATE * e_blk[_WGRAD_BLK], (what, e_prod, e_blk)
+    """(a is an fp32 buffer on both sides; only the gated 64-term reduction is evaluated: the whole reduction runs over up to 10^5 pixels)"""
+    a32, w32 = np.ascontiguousarray(a32), np.ascontiguousarray(w32)
+    wgrad_gate(what, got, a32.astype(np.float64), w64, lambda blk: _fp32_blocked(a32, w32, blk), (_WGRAD_BLK,))
 
 
 @pytest.mark.parametrize("case,block,layer", [(c, b, l) for c in sorted(BWD_LAYERS) for b, l in BWD_LAYERS[c]])
@@ -293,19 +212,19 @@ def test_backward_layer(gpu, case, block, layer):
     x = _ctx(gpu, case)
     _FWD.clear()
     b, i = block - 1, layer - 1
-    grads = _backward_to(gpu, x, b * 100 + i)
-    H, HW, HWp, Ct, cin, Lb = x.H[b], x.H[b] ** 2, x.HWp[b], dr.CT[b], dr.cin_of(block, layer), dr.LAYERS[b]
+    grads = x.backward_to(b * 100 + i)
+    H, HW, HWp, Ct, cin, Lb = x.H[1 + block], x.H[1 + block] ** 2, x.HWp[1 + block], dr.CT[b], dr.cin_of(block, layer), dr.LAYERS[b]
     tag = "case %s (%d,%d)" % (case, block, layer)
     on_side = x.NS <= 4 and HW <= 1600
     assert on_side == VARIANTS[case][0][b][4]
-    S3 = x.streams
-    X, BT = _rd(x, "x%d" % block, block, Ct), _rd(x, "bt%d_%d" % (block, layer), block, 128)
-    GS, DY = _rd(x, "gs_%d_%d" % (block, layer), block, 32), _rd(x, "dy2", block, 128)
-    D2p = _rd(x, "d2_%d_%d" % (block, layer), block, 128, pad=True)
+    S3 = _streams(x)
+    X, BT = x.rd("x%d" % block, x.NS, 1 + block, Ct), x.rd("bt%d_%d" % (block, layer), x.NS, 1 + block, 128)
+    GS, DY = x.rd("gs_%d_%d" % (block, layer), x.NS, 1 + block, 32), x.rd("dy2", x.NS, 1 + block, 128)
+    D2p = x.rd("d2_%d_%d" % (block, layer), x.NS, 1 + block, 128, pad=True)
     D2 = D2p[:, :HW]
-    G0, G1 = _rd(x, "gsnap", block, Ct, S3), _rd(x, "g%d" % block, block, Ct, S3)
-    g1, b1, w1 = _lp(x, block, layer, "norm1.weight"), _lp(x, block, layer, "norm1.bias"), _lp(x, block, layer, "conv1.weight").reshape(128, cin)
-    g2, b2, w2 = _lp(x, block, layer, "norm2.weight"), _lp(x, block, layer, "norm2.bias"), _lp(x, block, layer, "conv2.weight")
+    G0, G1 = x.rd("gsnap", x.NS, 1 + block, Ct, S3), x.rd("g%d" % block, x.NS, 1 + block, Ct, S3)
+    g1, b1, w1 = x.lp(block, layer, "norm1.weight"), x.lp(block, layer, "norm1.bias"), x.lp(block, layer, "conv1.weight").reshape(128, cin)
+    g2, b2, w2 = x.lp(block, layer, "norm2.weight"), x.lp(block, layer, "norm2.bias"), x.lp(block, layer, "conv2.weight")
     pix = dr.sample(HW)
 
     # ---- padding rows of D2: zeros, exactly (bn_bwd_apply_split_kernel stores them)
@@ -327,8 +246,8 @@ def test_backward_layer(gpu, case, block, layer):
             gs32 = GS[n]
             ref, mag = dr.conv2_dgrad(gs32, H, H, w2)
         chain = dr.conv2_dgrad_chain(gs32, H, H, w2, pix)
-        _gate("%s conv2 dgrad stream %d%s" % (tag, n, " (BN backward on load)" if on_side else ""), dr.rms(DY[n][pix], ref[pix], mag[pix], on[pix]),
-              dr.rms(chain, ref[pix], mag[pix], on[pix]), 2.0, e_whole=dr.rms(DY[n], ref, mag, on), n=int(on[pix].sum()))
+        gate("%s conv2 dgrad stream %d%s" % (tag, n, " (BN backward on load)" if on_side else ""), dr.rms(DY[n][pix], ref[pix], mag[pix], on[pix]),
+             dr.rms(chain, ref[pix], mag[pix], on[pix]), 2.0, e_whole=dr.rms(DY[n], ref, mag, on), n=int(on[pix].sum()))
         assert not DY[n][off].any(), "conv2 dgrad: non-zero where the ReLU is clearly off"
 
         # ---- norm2 backward as stored for the three 1x1 consumers (units + block scales), padding rows included
@@ -338,13 +257,13 @@ def test_backward_layer(gpu, case, block, layer):
 
         # ---- conv1 data gradient: per-layer form on [cs, cin), grouped form on [0, cs) at the bottom of a group
         for layers, c0, c1 in dr.dgrad1_segments(Lb, i, dr.CIN0[b]):
-            prm = [(_lp(x, block, l + 1, "norm1.weight"), _lp(x, block, l + 1, "norm1.bias"), _lp(x, block, l + 1, "conv1.weight").reshape(128, -1)) for l in layers]
-            d2s = [D2[n] if l == i else _rd(x, "d2_%d_%d" % (block, l + 1), block, 128, [n])[0] for l in layers]
+            prm = [(x.lp(block, l + 1, "norm1.weight"), x.lp(block, l + 1, "norm1.bias"), x.lp(block, l + 1, "conv1.weight").reshape(128, -1)) for l in layers]
+            d2s = [D2[n] if l == i else x.rd("d2_%d_%d" % (block, l + 1), x.NS, 1 + block, 128, [n])[0] for l in layers]
             ref, mag, _, keep = dr.conv1_dgrad(G0[k], X[n], prm, d2s, c0, c1, chain=False)
             assert 1 - keep.mean() <= 0.01, ("borderline ReLU signs", 1 - keep.mean())
             rs, ms, ch, ks = dr.conv1_dgrad(G0[k], X[n], prm, d2s, c0, c1, take=pix)
-            _gate("%s conv1 dgrad stream %d, %s form, layers %s, columns %d..%d" % (tag, n, "grouped" if len(layers) > 1 or c0 == 0 else "per-layer", [l + 1 for l in layers], c0, c1),
-                  dr.rms(G1[k][pix, c0:c1], rs, ms, ks), dr.rms(ch, rs, ms, ks), 2.0, e_whole=dr.rms(G1[k][:, c0:c1], ref, mag, keep), n=int(ks.sum()))
+            gate("%s conv1 dgrad stream %d, %s form, layers %s, columns %d..%d" % (tag, n, "grouped" if len(layers) > 1 or c0 == 0 else "per-layer", [l + 1 for l in layers], c0, c1),
+                 dr.rms(G1[k][pix, c0:c1], rs, ms, ks), dr.rms(ch, rs, ms, ks), 2.0, e_whole=dr.rms(G1[k][:, c0:c1], ref, mag, keep), n=int(ks.sum()))
 
     # ---- norm2's affine gradients: sums over ALL streams and pixels
     aff = dr.norm2_affine(DY, BT)

@@ -22,27 +22,14 @@ import pytest
 import torch
 
 import dense_ref as dr
-from helpers import _fp32_chain, _WGRAD_BLK, _WGRAD_GATE, grads_within_fp32_class, MEAN, STD, nhwc_plane, oracle_net, orc, probe_idx, q_close, scene, scene_tensors
+from helpers import (_fp32_chain, _WGRAD_BLK, _WGRAD_GATE, gpu, grads_within_fp32_class, MEAN, STD, nhwc_plane, oracle_net, orc, probe_idx,  # noqa: F401  (gpu: the fixture)
+                     product_net, q_close, scene, scene_tensors)
 
 pytestmark = pytest.mark.gpu
 
 
 def crc(a):
     return np.uint32(zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()   # raises if libsmg_hip.so is missing
-    return torch.device("cuda:0")
-
-
-def product_net(seed, out_ch=1, R=16):
-    from helpers import product_net as pn
-    return pn(seed, out_ch, R)
 
 
 def engine_of(net, S=640):

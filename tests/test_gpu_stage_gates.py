@@ -1,4 +1,5 @@
-"""Operator-level gates on the stages AROUND the dense layers (the dense layers have theirs in test_gpu_parity.py): every stage's
+"""Operator-level gates on the stages AROUND the dense layers (the dense layers have theirs in test_gpu_dense_gates.py; what the gate
+modules share is tests/gate_harness.py): every stage's
 input and output are read back from the engine and the stage is recomputed in fp64 from its OWN input buffer with its own fp64
 batch statistics over [:HW] of each stream or pair (tests/stage_ref.py, proved against torch in tests/test_cpu_stage_ref.py).
 
@@ -8,7 +9,7 @@ Backward (one debug_stop each, inputs and outputs read after that ONE stop): at 
 norm5_bwd_kernel on every single-user stream and on the shared masked stream, norm5's affine gradients; at 250 / 150 / 50 transition
 3 / 2 / 1's E_UNPOOL data gradient and W_POOL weight gradient.
 
-Two geometries, for the tile variants and padded rows they select (asserted from eng.H / eng.HWp, GEOMETRY below):
+Two geometries, for the tile variants and padded rows they select (asserted from eng.H / eng.HWp, gate_harness.GEOMETRY):
   S = 640: planes 320^2, 160^2 (128-row, no padding), 80^2 (128-row), 40^2 (64-row), 20^2 (448 rows for 400 pixels); 6 streams, 5 pairs:
            the masked stream has 5 users, more than norm5_bwd_kernel's 4 phases; sample 3 enters with dq = 1e-6, 20 binades low.
   S = 672: planes 336^2, 168^2 (28288 rows for 28224), 84^2 (64-row, 7104 for 7056), 42^2 (128-row, 1792 for 1764), 21^2 (448 for 441,
@@ -45,122 +46,37 @@ import numpy as np
 import pytest
 import torch
 
+import dense_ref as dr
 import stage_ref as sr
-from helpers import _WGRAD_BLK, _WGRAD_GATE, _fp32_blocked, _fp32_chain, MEAN, STD, product_net
+from gate_harness import CT, HEAD, SCENES, TRUNK, GateCtx, elementwise, gate, gpu, wgrad_gate  # noqa: F401  (gpu: the fixture)
+from helpers import _fp32_blocked, _fp32_chain, product_net
 
 pytestmark = pytest.mark.gpu
 
-CASES = {"S640": dict(seed=0, size=224, rots=[0, 3, 7, 10, 13], S=640, dq=[[1.0], [-1.0], [0.5], [1e-6], [-0.25]]),
-         "S672": dict(seed=8, size=236, rots=[2, 11], S=672, dq=[[1.0, -0.5, 0.25, -2.0], [-0.75, 1.5, -1e-3, 0.4]])}
-# H and HWp of the stem plane and of blocks 1-4 (eng.H[1:6] / eng.HWp[1:6]); HWp % 128 picks the 128-row or the 64-row configuration
-GEOMETRY = {"S640": ([320, 160, 80, 40, 20], [102400, 25600, 6400, 1600, 448]),
-            "S672": ([336, 168, 84, 42, 21], [112896, 28288, 7104, 1792, 448])}
-CT = (256, 512, 1024, 1024)
-TRUNK, HEAD = "grasp_depth_trunk.features.", "graspnet_val.grasp-val-"
+CASES = {"S640": SCENES["S640x6"], "S672": SCENES["S672x3"]}
 _NETS, _FWD = {}, {}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()   # raises if libsmg_hip.so is missing
-    return torch.device("cuda:0")
-
-
-class _Ctx:
-    pass
 
 
 def _ctx(gpu, case):
     """net, heightmaps and stream / pair layout of one geometry (built once per module)"""
     if case not in _NETS:
-        import synthetic
-        c = CASES[case]
-        x = _Ctx()
-        x.case, x.S, x.rots = case, c["S"], c["rots"]
-        x.net = product_net(0)
-        depth, masks = synthetic.heightmap_scene(c["seed"], size=c["size"], n_boxes=8)
-        x.hm = torch.from_numpy(np.stack([depth, depth * masks[0]])).to(gpu)
-        x.NS, x.NP = len(x.rots) + 1, len(x.rots)
-        x.pa, x.pb = list(range(x.NP)), [x.NS - 1] * x.NP
-        x.sd = {k: v.detach().cpu().numpy() for k, v in x.net.state_dict().items()}
-        _NETS[case] = x
+        net = product_net(0)
+        _NETS[case] = GateCtx(net, {k: v.detach().cpu().numpy() for k, v in net.state_dict().items()}, CASES[case], gpu)
     return _NETS[case]
-
-
-def _forward(x):
-    import models
-    q = x.net.run(0, x.rots, 16, heightmaps=x.hm, mean=MEAN, std=STD, keep_for_backward=True)
-    torch.cuda.synchronize()
-    x.eng = models._ENGINES[(0, x.S, x.net.HEAD_OUT)]
-    H, HWp = GEOMETRY[x.case]
-    assert list(x.eng.H[1:6]) == H and list(x.eng.HWp[1:6]) == HWp, (x.eng.H, x.eng.HWp)
-    x.H, x.HWp = [x.S] + H, [int(x.eng.HWp[0])] + HWp
-    return q
-
-
-def _rd(x, name, rows, plane, C):
-    """the first `rows` streams / pairs of a [rows][HWp][C] buffer, cut to the plane's pixels"""
-    HW, HWp = x.H[plane] ** 2, x.HWp[plane]
-    return x.eng.debug_read(name, count=rows * HWp * C).reshape(rows, HWp, C)[:, :HW, :]
 
 
 def _fwd(gpu, case):
     """ONE heightmap-form forward per geometry; every buffer the forward gates compare is read after that one run"""
     if case not in _FWD:
         x = _ctx(gpu, case)
-        _forward(x)
+        x.forward()
         B = {"img": x.eng.debug_read("img").reshape(-1, x.HWp[0], 4)[:x.NS, :x.S * x.S, 0].copy(),
-             "stem": _rd(x, "stem", x.NS, 1, 64), "stemv": _rd(x, "dy0", x.NS, 2, 64),
-             "feat": _rd(x, "feat", x.NP, 5, 2048), "h1": _rd(x, "h1", x.NP, 5, 64)}
+             "stem": x.rd("stem", x.NS, 1, 64), "stemv": x.rd("dy0", x.NS, 2, 64),
+             "feat": x.rd("feat", x.NP, 5, 2048), "h1": x.rd("h1", x.NP, 5, 64)}
         for b in range(4):
-            B["x%d" % (b + 1)] = _rd(x, "x%d" % (b + 1), x.NS, 2 + b, CT[b])
+            B["x%d" % (b + 1)] = x.rd("x%d" % (b + 1), x.NS, 2 + b, CT[b])
         _FWD[case] = B
     return _ctx(gpu, case), _FWD[case]
-
-
-def _sample(n, k=256):
-    """pixel sample of a plane of n pixels: the first k, the last k and 2 k strided through it (<= 4 k, sorted, unique)"""
-    if n <= 4 * k:
-        return np.arange(n)
-    return np.unique(np.concatenate([np.arange(k), np.arange(n - k, n), np.arange(0, n, max(1, n // (2 * k)))[:2 * k]]))
-
-
-def _rms(got, ref, mag, keep=None):
-    r = ((np.asarray(got, dtype=np.float64) - ref) / mag) ** 2
-    return float(np.sqrt((r if keep is None else r[keep]).mean()))
-
-
-def _gate(what, e_prod, e_yard, factor, e_whole=None, n=0):
-    msg = "%s: err/sum|ab| rms product %.3e, fp32 yardstick %.3e: ratio %.2f" % (what, e_prod, e_yard, e_prod / e_yard)
-    if e_whole is not None:
-        msg += "; whole plane %.3e: ratio %.2f" % (e_whole, e_whole / e_yard)
-    print(msg + (" (%d elements)" % n if n else ""))
-    assert e_prod <= factor * e_yard, (what, e_prod, e_yard)
-    if e_whole is not None:
-        assert e_whole <= factor * e_yard, (what, "whole plane", e_whole, e_yard)
-
-
-def _elementwise(what, got, ref, mag, k, slack=None):
-    """max |err| against (k * mag + slack) * 2^-24: k = the fp32 roundings on the kernel's path, slack = what the fp32 strip sums of the
-    forward statistics add (stage_ref.bn_stat_slack; None where the statistics are fp64 sums of the elements).  An element whose bound
-    is 0 must be exact.  Prints the error in roundings of mag as well."""
-    err = np.abs(np.asarray(got, dtype=np.float64) - ref)
-    bound = k * mag if slack is None else k * mag + slack
-    r = float((err / (bound + 1e-300)).max())
-    print("%s: max |err| / mag = %.2f x 2^-24; at %.2f of the bound (%d roundings of mag%s)"
-          % (what, float((err / (mag + 1e-300)).max() / sr.U), r / sr.U, k, "" if slack is None else " + the statistics' strip sums"))
-    assert r <= sr.U, (what, r / sr.U, k)
-
-
-def _tp(x, name):
-    return x.sd[TRUNK + name]
-
-
-def _hp(x, name):
-    return x.sd[HEAD + name]
 
 
 # ---- forward -----------------------------------------------------------------------------------------------------------------------------
@@ -175,7 +91,7 @@ def test_stem_conv0_heightmap_form(gpu, case):
     pack_weights_kernel stores (PK_STEM1).  sum |a||w| is taken over all 147 products."""
     x, B = _fwd(gpu, case)
     S, Hs = x.S, x.H[1]
-    w = _tp(x, "conv0.weight")
+    w = x.tp("conv0.weight")
     w1 = w.astype(np.float64).sum(1, keepdims=True)
     rows = _stem_rows(Hs)
     pix = (rows[:, None] * Hs + np.arange(Hs)[None, :]).ravel()
@@ -184,7 +100,7 @@ def test_stem_conv0_heightmap_form(gpu, case):
         ref, _ = sr.stem_conv(img, w1, rows)
         mag = np.abs(sr.stem_cols(img.astype(np.float64), rows)) @ sr.stem_wmat(np.abs(w.astype(np.float64)).sum(1, keepdims=True)).T + 1e-300
         chain = _fp32_chain(sr.stem_cols(img, rows), sr.stem_wmat(w1.astype(np.float32)))
-        _gate("%s stem conv0, heightmap form, stream %d" % (case, n), _rms(B["stem"][n][pix], ref, mag), _rms(chain, ref, mag), 2.0, n=ref.size)
+        gate("%s stem conv0, heightmap form, stream %d" % (case, n), dr.rms(B["stem"][n][pix], ref, mag), dr.rms(chain, ref, mag), 2.0, n=ref.size)
 
 
 def test_stem_conv0_image_form(gpu):
@@ -207,7 +123,7 @@ def test_stem_conv0_image_form(gpu):
         im = img[n, :, :3].reshape(640, 640, 3)
         ref, mag = sr.stem_conv(im, w, rows)
         chain = _fp32_chain(sr.stem_cols(im, rows), sr.stem_wmat(w))
-        _gate("S640 stem conv0, image form, stream %d" % n, _rms(stem[n][pix], ref, mag + 1e-300), _rms(chain, ref, mag + 1e-300), 2.0, n=ref.size)
+        gate("S640 stem conv0, image form, stream %d" % n, dr.rms(stem[n][pix], ref, mag + 1e-300), dr.rms(chain, ref, mag + 1e-300), 2.0, n=ref.size)
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
@@ -218,7 +134,7 @@ def test_pool0_and_raw_stem_value_at_the_argmax(gpu, case):
     BN + ReLU equals the window's fp64 maximum within the same bound."""
     x, B = _fwd(gpu, case)
     Hs = x.H[1]
-    g, b = _tp(x, "norm0.weight"), _tp(x, "norm0.bias")
+    g, b = x.tp("norm0.weight"), x.tp("norm0.bias")
     for n in range(x.NS):
         stem = B["stem"][n]
         ref, mag = sr.pool0(stem, Hs, Hs, g, b)
@@ -226,13 +142,13 @@ def test_pool0_and_raw_stem_value_at_the_argmax(gpu, case):
         # rounding of either where a channel's mean is small against its spread (measured without the term: 20.7 roundings of mag on the
         # masked stream of S = 640, 2.5 - 3.5 on the others)
         slack = sr.maxpool3s2(sr.bn_stat_slack(stem, g, (Hs * Hs // 128) * 128), Hs, Hs)
-        _elementwise("%s pool0 stream %d" % (case, n), B["x1"][n][:, :64], ref, mag, sr.K_BN, slack)
+        elementwise("%s pool0 stream %d" % (case, n), B["x1"][n][:, :64], ref, mag, sr.K_BN, slack)
         sv = B["stemv"][n]
         win = sr.pool_windows(stem, Hs, Hs, np.float32(np.nan))
         assert (win == sv[None]).any(0).all(), "a kept stem value is none of its window's"
         mean, inv = sr.bn_stats(stem)
-        _elementwise("%s BN + ReLU of the kept raw stem value, stream %d" % (case, n),
-                     np.maximum((sv.astype(np.float64) - mean) * (inv * g) + b, 0.0), ref, mag, sr.K_BN)      # (fp64 on both sides: 0)
+        elementwise("%s BN + ReLU of the kept raw stem value, stream %d" % (case, n),
+                    np.maximum((sv.astype(np.float64) - mean) * (inv * g) + b, 0.0), ref, mag, sr.K_BN)      # (fp64 on both sides: 0)
 
 
 @pytest.mark.parametrize("t", [1, 2, 3])
@@ -243,9 +159,9 @@ def test_transition_forward(gpu, case, t):
     x, B = _fwd(gpu, case)
     H, Cp = x.H[1 + t], CT[t - 1]
     C0 = Cp // 2
-    g, b = _tp(x, "transition%d.norm.weight" % t), _tp(x, "transition%d.norm.bias" % t)
-    w = _tp(x, "transition%d.conv.weight" % t).reshape(C0, Cp)
-    pix = _sample((H // 2) ** 2)
+    g, b = x.tp("transition%d.norm.weight" % t), x.tp("transition%d.norm.bias" % t)
+    w = x.tp("transition%d.conv.weight" % t).reshape(C0, Cp)
+    pix = dr.sample((H // 2) ** 2)
     cols = np.arange(0, C0, max(1, C0 // 128))
     for n in range(x.NS):
         X = B["x%d" % t][n]
@@ -255,61 +171,42 @@ def test_transition_forward(gpu, case, t):
         a32 = sr.pooled_act32(X, H, H, g, b)[pix]
         chain = _fp32_chain(a32, np.ascontiguousarray(w[cols]))
         sel = np.ix_(pix, cols)
-        _gate("%s transition %d stream %d" % (case, t, n), _rms(got[sel], ref[sel], mag[sel]), _rms(chain, ref[sel], mag[sel]), 2.0,
-              e_whole=_rms(got, ref, mag), n=chain.size)
+        gate("%s transition %d stream %d" % (case, t, n), dr.rms(got[sel], ref[sel], mag[sel]), dr.rms(chain, ref[sel], mag[sel]), 2.0,
+             e_whole=dr.rms(got, ref, mag), n=chain.size)
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_norm5_concat(gpu, case):
     """feat_kernel: F[pair] = norm5(x4[rotation stream]) | norm5(x4[masked stream]), no ReLU; K_BN roundings of bn_mag, whole planes"""
     x, B = _fwd(gpu, case)
-    g5 = _tp(x, "norm5.weight")
-    ref, mag = sr.feat(list(B["x4"]), g5, _tp(x, "norm5.bias"), x.pa, x.pb)
+    g5 = x.tp("norm5.weight")
+    ref, mag = sr.feat(list(B["x4"]), g5, x.tp("norm5.bias"), x.pa, x.pb)
     # x4's first 512 channels leave transition 3 through 64-row tiles: the whole ones (384 of the 400 / 441 pixels) sum their statistics
     # in fp32 strips, the last one and the 3x3 kernels' channels per element in fp64 (measured without the term: 9.5 / 8.0 roundings)
     HW = x.H[5] ** 2
     sl = [np.concatenate([sr.bn_stat_slack(v[:, :512], g5[:512], (HW // 64) * 64), np.zeros((HW, 512))], axis=1) for v in B["x4"]]
     for j in range(x.NP):
         for half, name, s in ((slice(0, 1024), "rotation", x.pa[j]), (slice(1024, 2048), "masked", x.pb[j])):
-            _elementwise("%s feat pair %d, %s half" % (case, j, name), B["feat"][j][:, half], ref[j][:, half], mag[j][:, half], sr.K_BN, sl[s])
+            elementwise("%s feat pair %d, %s half" % (case, j, name), B["feat"][j][:, half], ref[j][:, half], mag[j][:, half], sr.K_BN, sl[s])
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_head_conv0_forward(gpu, case):
     """head norm0 + ReLU + conv0 (2048 -> 64): statistics PER PAIR, K = 2048, every pixel of every pair"""
     x, B = _fwd(gpu, case)
-    g, b, w = _hp(x, "norm0.weight"), _hp(x, "norm0.bias"), _hp(x, "conv0.weight").reshape(64, 2048)
+    g, b, w = x.hp("norm0.weight"), x.hp("norm0.bias"), x.hp("conv0.weight").reshape(64, 2048)
     for j in range(x.NP):
         ref, a64 = sr.head_conv0(B["feat"][j], g, b, w)
         mag = a64 @ np.abs(w.astype(np.float64)).T + 1e-300
         chain = _fp32_chain(sr.bn32(B["feat"][j], g, b), w)
-        _gate("%s head conv0 pair %d" % (case, j), _rms(B["h1"][j], ref, mag), _rms(chain, ref, mag), 2.0, n=ref.size)
+        gate("%s head conv0 pair %d" % (case, j), dr.rms(B["h1"][j], ref, mag), dr.rms(chain, ref, mag), 2.0, n=ref.size)
 
 
 # ---- backward ----------------------------------------------------------------------------------------------------------------------------
-def _backward_to(gpu, x, stop):
-    """a fresh forward, then the backward up to `stop`; returns the gradients the walk has finished"""
-    q = _forward(x)
-    dq = torch.tensor(CASES[x.case]["dq"], dtype=torch.float32, device=gpu).view(q.shape)
-    x.net.zero_grad()
-    x.eng.set_option("debug_stop", stop)
-    try:
-        x.net._engine_backward(x.net._saved[1], dq)
-    finally:
-        x.eng.set_option("debug_stop", -1)
-    torch.cuda.synchronize()
-    return {n: p.grad.detach().cpu().numpy() for n, p in x.net.named_parameters() if p.grad is not None}
-
-
 def _wgrad_gate(what, got, a64, w64, a32, w32):
-    """got [M][N] = sum_k a[k][m] * w[k][n] over ALL streams x pixels, on the rows / columns handed in"""
-    ref = a64.T @ w64
-    mag = np.abs(a64).T @ np.abs(w64) + 1e-300
-    e_blk = {bl: _rms(_fp32_blocked(np.ascontiguousarray(a32), np.ascontiguousarray(w32), bl), ref, mag) for bl in (64, 512)}
-    e_prod = _rms(got, ref, mag)
-    print("%s: err/sum|ab| rms product %.3e, blocked fp32 (chains + pairwise) 64-term %.3e / 512-term %.3e over all %d terms, %d elements: ratios %.2f / %.2f"
-          % (what, e_prod, e_blk[64], e_blk[512], a64.shape[0], ref.size, e_prod / e_blk[64], e_prod / e_blk[512]))
-    assert e_prod <= _WGRAD_GATE * e_blk[_WGRAD_BLK], (what, e_prod, e_blk)
+    """the project's weight-gradient gate against the blocked fp32 reduction, its 512-term form printed beside the gated 64-term one"""
+    a32, w32 = np.ascontiguousarray(a32), np.ascontiguousarray(w32)
+    wgrad_gate(what, got, a64, w64, lambda blk: _fp32_blocked(a32, w32, blk), (64, 512))
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
@@ -322,12 +219,12 @@ def test_head_conv0_and_norm5_backward(gpu, case):
       * norm5.bias / norm5.weight: the sums of dy5 and dy5 * xhat5 over all streams (final here: the kernel adds them itself).
         norm5 feeds the head's BatchNorm directly, so both cancel to (nearly) nothing: they are held to their sum |term|."""
     x = _ctx(gpu, case)
-    grads = _backward_to(gpu, x, 350)
-    h1, dh1 = _rd(x, "h1", x.NP, 5, 64), _rd(x, "dh1", x.NP, 5, 64)
-    Fm, DF = _rd(x, "feat", x.NP, 5, 2048), _rd(x, "df", x.NP, 5, 2048)
-    x4, g4 = _rd(x, "x4", x.NS, 5, 1024), _rd(x, "g4", x.NS, 5, 1024)
-    g0, b0, g1 = _hp(x, "norm0.weight"), _hp(x, "norm0.bias"), _hp(x, "norm1.weight")
-    w0 = _hp(x, "conv0.weight").reshape(64, 2048)
+    grads = x.backward_to(350)
+    h1, dh1 = x.rd("h1", x.NP, 5, 64), x.rd("dh1", x.NP, 5, 64)
+    Fm, DF = x.rd("feat", x.NP, 5, 2048), x.rd("df", x.NP, 5, 2048)
+    x4, g4 = x.rd("x4", x.NS, 5, 1024), x.rd("g4", x.NS, 5, 1024)
+    g0, b0, g1 = x.hp("norm0.weight"), x.hp("norm0.bias"), x.hp("norm1.weight")
+    w0 = x.hp("conv0.weight").reshape(64, 2048)
     A64s, A32s, P64s, P32s = [], [], [], []
     for j in range(x.NP):
         ref, A64, on, _ = sr.head_conv0_bwd(h1[j], dh1[j], Fm[j], g1, g0, b0, w0)
@@ -336,25 +233,25 @@ def test_head_conv0_and_norm5_backward(gpu, case):
         chain = (on * _fp32_chain(A32, np.ascontiguousarray(w0.T))).astype(np.float32)
         keep = sr.bn_keep(Fm[j], g0, b0)
         assert 1 - keep.mean() <= 0.01, ("borderline ReLU signs", 1 - keep.mean())
-        _gate("%s head conv0 dgrad pair %d" % (case, j), _rms(DF[j], ref, mag, keep), _rms(chain, ref, mag, keep), 2.0, n=int(keep.sum()))
+        gate("%s head conv0 dgrad pair %d" % (case, j), dr.rms(DF[j], ref, mag, keep), dr.rms(chain, ref, mag, keep), 2.0, n=int(keep.sum()))
         A64s.append(A64); A32s.append(A32)
         P64s.append(np.maximum(sr.bn_pre(Fm[j], g0, b0), 0.0)[:, ::8]); P32s.append(sr.bn32(Fm[j], g0, b0)[:, ::8])
     # measured on the MI355X: 1.46 (S = 640, 2000 terms) and 1.21 (S = 672, 882 terms) of the 64-term blocked reduction; gate 3.0
     _wgrad_gate("%s head conv0 wgrad" % case, grads[HEAD + "conv0.weight"].reshape(64, 2048)[::8, ::8],
                 np.concatenate(A64s)[:, ::8], np.concatenate(P64s), np.concatenate(A32s)[:, ::8], np.concatenate(P32s))
 
-    g5 = _tp(x, "norm5.weight")
+    g5 = x.tp("norm5.weight")
     G4, dy5, mag, db, dg, dbm, dgm = sr.norm5_bwd(list(x4), Fm, DF, g0, g5, x.pa, x.pb)
     for s in range(x.NS):
         users = x.NP if s == x.NS - 1 else 1
         # k_g4: one user's path (a, q1 and k from the fp32 tile sums of the head's data gradient, x - mean, the fused multiply-add,
         # the product with a: K_DY5_USER = 142), the product with gamma5, one add per user and the phase tree (stage_ref.k_g4)
-        _elementwise("%s norm5 backward stream %d (%d user%s)" % (case, s, users, "s" if users > 1 else ""),
-                     g4[s], G4[s], np.abs(g5) * mag[s], sr.k_g4(users))
+        elementwise("%s norm5 backward stream %d (%d user%s)" % (case, s, users, "s" if users > 1 else ""),
+                    g4[s], G4[s], np.abs(g5) * mag[s], sr.k_g4(users))
     # k_sums5: a term's own path, xhat5 and the product, <= 80 fp32 adds per thread, one fp32 atomic per (stream, workgroup)
     k = sr.k_sums5(x.H[5] ** 2, x.NS - 1, True)
-    _elementwise("%s norm5.bias gradient" % case, grads[TRUNK + "norm5.bias"], db, dbm, k)
-    _elementwise("%s norm5.weight gradient" % case, grads[TRUNK + "norm5.weight"], dg, dgm, k)
+    elementwise("%s norm5.bias gradient" % case, grads[TRUNK + "norm5.bias"], db, dbm, k)
+    elementwise("%s norm5.weight gradient" % case, grads[TRUNK + "norm5.weight"], dg, dgm, k)
 
 
 @pytest.mark.parametrize("t", [3, 2, 1])
@@ -373,14 +270,14 @@ def test_transition_backward(gpu, case, t):
     G', and against a reference built on them the same gradients were at 2.76e-8 / 1.63e-8: the products were never off, the yardstick
     left out a rounding the kernels legitimately make."""
     x = _ctx(gpu, case)
-    grads = _backward_to(gpu, x, (t - 1) * 100 + 50)
+    grads = x.backward_to((t - 1) * 100 + 50)
     H, Cp = x.H[1 + t], CT[t - 1]
     C0, Hn = Cp // 2, H // 2
-    X, Gt = _rd(x, "x%d" % t, x.NS, 1 + t, Cp), _rd(x, "g%d" % t, x.NS, 1 + t, Cp)
-    Xn, Gn = _rd(x, "x%d" % (t + 1), x.NS, 2 + t, CT[t])[:, :, :C0], _rd(x, "g%d" % (t + 1), x.NS, 2 + t, CT[t])[:, :, :C0]
-    g, b = _tp(x, "transition%d.norm.weight" % t), _tp(x, "transition%d.norm.bias" % t)
-    w = _tp(x, "transition%d.conv.weight" % t).reshape(C0, Cp)
-    q = _sample(Hn * Hn)
+    X, Gt = x.rd("x%d" % t, x.NS, 1 + t, Cp), x.rd("g%d" % t, x.NS, 1 + t, Cp)
+    Xn, Gn = x.rd("x%d" % (t + 1), x.NS, 2 + t, CT[t])[:, :, :C0], x.rd("g%d" % (t + 1), x.NS, 2 + t, CT[t])[:, :, :C0]
+    g, b = x.tp("transition%d.norm.weight" % t), x.tp("transition%d.norm.bias" % t)
+    w = x.tp("transition%d.conv.weight" % t).reshape(C0, Cp)
+    q = dr.sample(Hn * Hn)
     qy, qx = q // Hn, q % Hn
     pix = np.stack([(2 * qy + dy) * H + 2 * qx + dx for dy in (0, 1) for dx in (0, 1)], axis=1).ravel()      # the 4 pixels of each pooled pixel
     cols = np.arange(0, Cp, max(1, Cp // 128))
@@ -398,8 +295,8 @@ def test_transition_backward(gpu, case, t):
         # / 1.63 (whole plane); gate 2.0.  That stream is mostly background: on its few object pixels |xhat| is large, the term
         # (x - mean) * k carries the gradient, and k = invstd * mean(G' * xhat) is a sum that cancels to 2 % of its terms' size - the
         # engine's sum sat 0.25 roundings (rms, 1.3 at most) of those terms from the fp64 sum of the stored G'.
-        _gate("%s transition %d dgrad stream %d" % (case, t, n), _rms(Gt[n][sel], ref[sel], mag[sel], keep[sel]),
-              _rms(chain, ref[sel], mag[sel], keep[sel]), 2.0, e_whole=_rms(Gt[n], ref, mag, keep), n=int(keep[sel].sum()))
+        gate("%s transition %d dgrad stream %d" % (case, t, n), dr.rms(Gt[n][sel], ref[sel], mag[sel], keep[sel]),
+             dr.rms(chain, ref[sel], mag[sel], keep[sel]), 2.0, e_whole=dr.rms(Gt[n], ref, mag, keep), n=int(keep[sel].sum()))
         dX64s.append(dX); dX32s.append(dX32)
     P64 = np.concatenate([sr.pooled_act(X[n], H, H, g, b)[:, ::8] for n in range(x.NS)])
     P32 = np.concatenate([sr.pooled_act32(X[n], H, H, g, b)[:, ::8] for n in range(x.NS)])

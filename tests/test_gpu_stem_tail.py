@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import MEAN, STD, oracle_net, orc
+from helpers import gpu, MEAN, STD, oracle_net, orc  # noqa: F401  (gpu: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -52,15 +52,6 @@ print("CHILD OK")
 CONV0, NORM0W, NORM0B = ("g:grasp_depth_trunk.features.conv0.weight", "g:grasp_depth_trunk.features.norm0.weight",
                          "g:grasp_depth_trunk.features.norm0.bias")
 _RUNS = {}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()   # raises if libsmg_hip.so is missing
-    return torch.device("cuda:0")
 
 
 def _run(case, tag, env, tmp):

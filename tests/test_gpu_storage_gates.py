@@ -37,13 +37,13 @@ Two geometries, one forward per (mode, geometry), every buffer read after it:
   S = 672, 3 streams (seed 8, size 236): padded planes 28288 / 7104 / 1792 / 448, ragged 3x3 tiles, bounds-checked 16 x 16 tiles;
   S = 640, 6 streams (seed 0, rotations 0 3 7 10 13): exact tiles, and CfgP64x64 for conv1 at 80^2, where mode 0 goes wave-specialised.
 VARIANTS16 is the choice of the walk in modes 1 / 2 (forward.hip: the wave-specialised conv1 and the split scales are `e->prec == 0`
-only), asserted from eng.H / eng.HWp; the rules are restated on the CPU in test_cpu_storage_ref.
+only), asserted from eng.H / eng.HWp; the rules (tests/gate_harness.py) are checked on the CPU in test_cpu_storage_ref.
 
 Forward: dense layers (1,1) (1,6) (2,1) (2,12) (3,24) (4,1) (4,16) on the first and the masked stream - conv1 from x<b>[:, :cin] into
 bt<b>_<l>, conv2 from the bottleneck into x<b>[:, cin:cin+32]; stem conv0 in the heightmap form (operands rounded to the mode's forward
 operand type - FwdConvP's kOp = fwd_op_plain(PREC) - into the fp32 stem plane); pool0 into the 16-bit x1; the three transitions;
 feat_kernel from the 16-bit x4 into fp32; the head's norm0 + ReLU + conv0 (fp32 in and out, 16-bit operands); x<b>'s padding rows finite.
-Backward, the dq of test_gpu_stage_gates.CASES, one debug_stop per gate: at 350 the head conv0 data and weight gradients (bf16
+Backward, the dq of the stage gates (gate_harness.SCENES), one debug_stop per gate: at 350 the head conv0 data and weight gradients (bf16
 operands, fp32 buffers), norm5_bwd_kernel into the bf16 g4 on every stream, norm5's affine gradients; at 250 / 150 / 50 the E_UNPOOL
 data gradient into g<t> and the W_POOL weight gradient of transitions 3 / 2 / 1.
 
@@ -59,11 +59,13 @@ import torch
 import dense_ref as dr
 import stage_ref as sr
 import storage_ref as st
-from helpers import _WGRAD_BLK, _WGRAD_GATE, MEAN, STD, product_net
-from test_gpu_stage_gates import CASES, CT, GEOMETRY, HEAD, TRUNK
+from gate_harness import (CT, HEAD, SCENES, TRUNK, GateCtx, bounded, conv1_fwd_cfg, forward_chains, gate, gpu, halo_tile,  # noqa: F401  (gpu: the fixture)
+                          transition_cfg, wgrad_gate)
+from helpers import MEAN, STD, product_net
 
 pytestmark = pytest.mark.gpu
 
+CASES = {"S640": SCENES["S640x6"], "S672": SCENES["S672x3"]}          # the stage gates' two geometries, and their dq
 # per block: (conv1 forward, 3x3 tile, bounds-checked 16 x 16); then the three transitions, the stem, the head conv0
 VARIANTS16 = {"S640": ([("P128x128", 16, False), ("P64x64", 8, False), ("P32x64", 8, False), ("P32x64", 8, False)], ["P128x128", "P64x128", "P64x128"], "P128x64", "P64x64"),
               "S672": ([("P128x128", 16, True), ("P64x64", 8, False), ("P32x64", 8, False), ("P32x64", 8, False)], ["P64x128", "P128x128", "P64x128"], "P128x64", "P64x64")}
@@ -79,38 +81,25 @@ DGRAD_OVER_THE_CAP = {("bf16", "S640", 1): (0,)}
 _STATE = {}
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: the gpu-marked tests must run on the MI355X box")
-    import smg_hip
-    smg_hip.lib()   # raises if libsmg_hip.so is missing
-    return torch.device("cuda:0")
+class _ModeCtx(GateCtx):
+    """GateCtx of one (mode, geometry): the mode's storage and operand types, the two streams of the dense-layer gates, the buffers of
+    the one forward (_fwd)"""
 
-
-class _Ctx:
-    pass
+    def __init__(self, net, sd, case, gpu, mode):
+        super().__init__(net, sd, CASES[case], gpu, mode)
+        self.case, self.dense_streams, self.B = case, [0, self.NS - 1], None
+        self.act, self.grd, self.fwd, self.bwd = (st.MODES[mode][k] for k in ("act", "grd", "fwd", "bwd"))
 
 
 @pytest.fixture(scope="module", params=[(m, c) for m in sorted(st.MODES) for c in sorted(CASES)], ids=lambda p: "%s-%s" % p)
 def mc(gpu, request):
     """one (mode, geometry) at a time (pytest groups the tests by this module-scoped parameter): the net in that precision mode, the
     scene, the stream / pair layout; the default mode is restored whatever happens"""
-    import synthetic
     mode, case = request.param
     if "net" not in _STATE:
         _STATE["net"] = product_net(0)
         _STATE["sd"] = {k: v.detach().cpu().numpy() for k, v in _STATE["net"].state_dict().items()}
-    c = CASES[case]
-    x = _Ctx()
-    x.mode, x.case, x.S, x.rots, x.net, x.sd, x.gpu = mode, case, c["S"], c["rots"], _STATE["net"], _STATE["sd"], gpu
-    x.act, x.grd, x.fwd, x.bwd = (st.MODES[mode][k] for k in ("act", "grd", "fwd", "bwd"))
-    depth, masks = synthetic.heightmap_scene(c["seed"], size=c["size"], n_boxes=8)
-    x.hm = torch.from_numpy(np.stack([depth, depth * masks[0]])).to(gpu)
-    x.NS, x.NP = len(x.rots) + 1, len(x.rots)
-    x.pa, x.pb = list(range(x.NP)), [x.NS - 1] * x.NP
-    x.dense_streams = [0, x.NS - 1]
-    x.B = None
+    x = _ModeCtx(_STATE["net"], _STATE["sd"], case, gpu, mode)
     try:
         # a default-mode forward first: the engine's buffers then hold fp32 planes when the mode changes, whatever ran before this file -
         # what the padding-row assertion of _fwd needs to mean something (see there)
@@ -124,33 +113,14 @@ def mc(gpu, request):
         x.B = None
 
 
-def _forward(x):
-    import models
-    q = x.net.run(0, x.rots, 16, heightmaps=x.hm, mean=MEAN, std=STD, keep_for_backward=True)
-    torch.cuda.synchronize()
-    x.eng = models._ENGINES[(0, x.S, x.net.HEAD_OUT)]
-    assert x.eng.precision == x.mode
-    H, HWp = GEOMETRY[x.case]
-    assert list(x.eng.H[1:6]) == H and list(x.eng.HWp[1:6]) == HWp, (x.eng.H, x.eng.HWp)
-    x.H, x.HWp = [x.S] + H, [int(x.eng.HWp[0])] + HWp
-    return q
-
-
-def _rd(x, name, rows, plane, C, pad=False):
-    """the first `rows` streams / pairs of a [rows][HWp][C] buffer (16-bit buffers arrive widened to fp32), cut to the plane's pixels"""
-    HW, HWp = x.H[plane] ** 2, x.HWp[plane]
-    a = x.eng.debug_read(name, count=rows * HWp * C).reshape(rows, HWp, C)
-    return a if pad else a[:, :HW, :]
-
-
 def _fwd(x):
     """ONE forward per (mode, geometry); every buffer the forward gates compare is read after that one run"""
     if x.B is None:
-        _forward(x)
+        x.forward()
         B = {"img": x.eng.debug_read("img").reshape(-1, x.HWp[0], 4)[:x.NS, :x.S * x.S, 0].copy(),
-             "stem": _rd(x, "stem", x.NS, 1, 64), "feat": _rd(x, "feat", x.NP, 5, 2048), "h1": _rd(x, "h1", x.NP, 5, 64)}
+             "stem": x.rd("stem", x.NS, 1, 64), "feat": x.rd("feat", x.NP, 5, 2048), "h1": x.rd("h1", x.NP, 5, 64)}
         for b in range(4):
-            full = _rd(x, "x%d" % (b + 1), x.NS, 2 + b, CT[b], pad=True)
+            full = x.rd("x%d" % (b + 1), x.NS, 2 + b, CT[b], pad=True)
             HW = x.H[2 + b] ** 2
             padrows = full[:, HW:]
             # No kernel of the forward stores rows >= HW of x<b> (test_gpu_dense_gates.py) and the 1x1 kernels read them as they lie - the
@@ -162,7 +132,7 @@ def _fwd(x):
             B["x%d" % (b + 1)] = full[:, :HW]
             assert np.array_equal(st.rnd(B["x%d" % (b + 1)], x.act), B["x%d" % (b + 1)])          # every stored value is a value of the storage type
         for b, l in FWD_LAYERS:
-            B["bt%d_%d" % (b, l)] = _rd(x, "bt%d_%d" % (b, l), x.NS, 1 + b, 128)[x.dense_streams].copy()
+            B["bt%d_%d" % (b, l)] = x.rd("bt%d_%d" % (b, l), x.NS, 1 + b, 128)[x.dense_streams].copy()
             fs = x.eng.debug_read("fs_bt%d_%d" % (b, l)).view(np.float64).reshape(2, -1, 128)
             B["fs%d_%d" % (b, l)] = fs[:, x.dense_streams].copy()
         x.B = B
@@ -174,18 +144,8 @@ def _xstats(x, B, block, n):
     channels of x1 from the fp32 stem plane, every other channel from the stored plane with its slack"""
     X = B["x%d" % block][n]
     if block == 1:
-        return st.x1_stats(X, B["stem"][n], x.H[1], _tp(x, "norm0.weight"), _tp(x, "norm0.bias"), x.act)
+        return st.x1_stats(X, B["stem"][n], x.H[1], x.tp("norm0.weight"), x.tp("norm0.bias"), x.act)
     return st.plane_stats(X, x.act)
-
-
-def _gate(what, e_prod, e_yard, factor, e_whole=None, n=0):
-    msg = "%s: err/sum|ab| rms product %.3e, storage chain %.3e: ratio %.2f" % (what, e_prod, e_yard, e_prod / e_yard)
-    if e_whole is not None:
-        msg += "; whole plane %.3e: ratio %.2f" % (e_whole, e_whole / e_yard)
-    print(msg + (" (%d elements)" % n if n else ""))
-    assert e_prod <= factor * e_yard, (what, e_prod, e_yard)
-    if e_whole is not None:
-        assert e_whole <= factor * e_yard, (what, "whole plane", e_whole, e_yard)
 
 
 def _rms(got, ref, mag, keep):
@@ -193,39 +153,19 @@ def _rms(got, ref, mag, keep):
     return dr.rms(np.asarray(got)[keep], np.asarray(ref)[keep], np.asarray(mag)[keep])
 
 
-def _bounded(what, got, ref, bound):
-    """max |err| / bound <= 1 (an element whose bound is 0 must be exact)"""
-    err = np.abs(np.asarray(got, dtype=np.float64) - ref)
-    r = float((err / (bound + 1e-300)).max())
-    print("%s: max |err| at %.3f of the bound" % (what, r))
-    assert r <= 1.0, (what, r)
-
-
-def _tp(x, name):
-    return x.sd[TRUNK + name]
-
-
-def _hp(x, name):
-    return x.sd[HEAD + name]
-
-
-def _lp(x, block, layer, name):
-    return x.sd[TRUNK + "denseblock%d.denselayer%d.%s" % (block, layer, name)]
-
-
 # ---- the variant table ---------------------------------------------------------------------------------------------------------------------
 def test_geometry_selects_the_variants_of_the_16_bit_table(mc):
     x = mc
     _fwd(x)
-    chains = st.forward_chains(x.NS, x.H[2])
+    chains = forward_chains(x.NS, x.H[2])
     blocks = []
     for b in range(4):
         H, HWp = x.H[2 + b], x.HWp[2 + b]
-        c1, ts = {st.conv1_fwd_cfg16(HWp, ns) for ns in chains}, {st.halo_tile(H, ns) for ns in chains}
+        c1, ts = {conv1_fwd_cfg(HWp, ns, False) for ns in chains}, {halo_tile(H, ns) for ns in chains}
         assert len(c1) == 1 and len(ts) == 1, (x.case, b, c1, ts)
         t = ts.pop()
         blocks.append((c1.pop(), t, t == 16 and H % 16 != 0))
-    got = (blocks, [st.transition_cfg(x.HWp[3 + b]) for b in range(3)], "P128x64" if x.HWp[1] % 128 == 0 else "P64x64", "P128x64" if x.HWp[5] % 128 == 0 else "P64x64")
+    got = (blocks, [transition_cfg(x.HWp[3 + b]) for b in range(3)], "P128x64" if x.HWp[1] % 128 == 0 else "P64x64", "P128x64" if x.HWp[5] % 128 == 0 else "P64x64")
     print("%s %s: %d streams, forward chains %s: %s" % (x.mode, x.case, x.NS, chains, got))
     assert got == VARIANTS16[x.case]
 
@@ -239,8 +179,8 @@ def test_forward_layer(mc, block, layer):
     x = mc
     B = _fwd(x)
     H, cin = x.H[1 + block], dr.cin_of(block, layer)
-    g1, b1, w1 = _lp(x, block, layer, "norm1.weight"), _lp(x, block, layer, "norm1.bias"), _lp(x, block, layer, "conv1.weight").reshape(128, cin)
-    g2, b2, w2 = _lp(x, block, layer, "norm2.weight"), _lp(x, block, layer, "norm2.bias"), _lp(x, block, layer, "conv2.weight")
+    g1, b1, w1 = x.lp(block, layer, "norm1.weight"), x.lp(block, layer, "norm1.bias"), x.lp(block, layer, "conv1.weight").reshape(128, cin)
+    g2, b2, w2 = x.lp(block, layer, "norm2.weight"), x.lp(block, layer, "norm2.bias"), x.lp(block, layer, "conv2.weight")
     pix = dr.sample(H * H)
     for k, n in enumerate(x.dense_streams):
         X, BT = B["x%d" % block][n], B["bt%d_%d" % (block, layer)][k]
@@ -249,13 +189,13 @@ def test_forward_layer(mc, block, layer):
         a64 = st.act64_s(X[:, :cin], g1, b1, S)
         ref, mag = a64 @ w1.astype(np.float64).T, a64 @ np.abs(w1.astype(np.float64)).T + 1e-300
         chain = st.storage_chain(st.act32_s(X[:, :cin], g1, b1, S)[pix], w1, x.fwd, x.act)
-        _gate("%s %s conv1 (%d,%d) K %d stream %d" % (x.mode, x.case, block, layer, cin, n), dr.rms(BT[pix], ref[pix], mag[pix]), dr.rms(chain, ref[pix], mag[pix]), 2.0,
-              e_whole=dr.rms(BT, ref, mag), n=chain.size)
+        gate("%s %s conv1 (%d,%d) K %d stream %d" % (x.mode, x.case, block, layer, cin, n), dr.rms(BT[pix], ref[pix], mag[pix]), dr.rms(chain, ref[pix], mag[pix]), 2.0,
+             e_whole=dr.rms(BT, ref, mag), n=chain.size, yard="storage chain")
         ref, mag = dr.conv2_fwd(BT, H, H, g2, b2, w2)
         chain = st.conv2_chain(BT, H, H, g2, b2, w2, pix, x.fwd, x.act)
         got = X[:, cin:cin + 32]
-        _gate("%s %s conv2 (%d,%d) stream %d" % (x.mode, x.case, block, layer, n), dr.rms(got[pix], ref[pix], mag[pix]), dr.rms(chain, ref[pix], mag[pix]), 2.0,
-              e_whole=dr.rms(got, ref, mag), n=chain.size)
+        gate("%s %s conv2 (%d,%d) stream %d" % (x.mode, x.case, block, layer, n), dr.rms(got[pix], ref[pix], mag[pix]), dr.rms(chain, ref[pix], mag[pix]), 2.0,
+             e_whole=dr.rms(got, ref, mag), n=chain.size, yard="storage chain")
 
 
 @pytest.mark.parametrize("block,layer", FWD_LAYERS)
@@ -288,7 +228,7 @@ def test_stem_conv0_heightmap_form(mc):
     x = mc
     B = _fwd(x)
     S, Hs = x.S, x.H[1]
-    w = _tp(x, "conv0.weight")
+    w = x.tp("conv0.weight")
     w1 = w.astype(np.float64).sum(1, keepdims=True)
     rows = np.concatenate([np.arange(24), np.arange(Hs - 24, Hs)])
     pix = (rows[:, None] * Hs + np.arange(Hs)[None, :]).ravel()
@@ -297,7 +237,7 @@ def test_stem_conv0_heightmap_form(mc):
         ref, _ = sr.stem_conv(img, w1, rows)
         mag = np.abs(sr.stem_cols(img.astype(np.float64), rows)) @ sr.stem_wmat(np.abs(w.astype(np.float64)).sum(1, keepdims=True)).T + 1e-300
         chain = st.storage_chain(sr.stem_cols(img, rows), sr.stem_wmat(w1.astype(np.float32)), x.fwd)
-        _gate("%s %s stem conv0, heightmap form, stream %d" % (x.mode, x.case, n), dr.rms(B["stem"][n][pix], ref, mag), dr.rms(chain, ref, mag), 2.0, n=ref.size)
+        gate("%s %s stem conv0, heightmap form, stream %d" % (x.mode, x.case, n), dr.rms(B["stem"][n][pix], ref, mag), dr.rms(chain, ref, mag), 2.0, n=ref.size, yard="storage chain")
 
 
 def test_pool0_into_16_bit_x1(mc):
@@ -305,12 +245,12 @@ def test_pool0_into_16_bit_x1(mc):
     x = mc
     B = _fwd(x)
     Hs = x.H[1]
-    g, b = _tp(x, "norm0.weight"), _tp(x, "norm0.bias")
+    g, b = x.tp("norm0.weight"), x.tp("norm0.bias")
     for n in range(x.NS):
         stem = B["stem"][n]
         ref, mag = sr.pool0(stem, Hs, Hs, g, b)
         slack = sr.maxpool3s2(sr.bn_stat_slack(stem, g, (Hs * Hs // 128) * 128), Hs, Hs) * sr.U
-        _bounded("%s %s pool0 stream %d" % (x.mode, x.case, n), B["x1"][n][:, :64], ref, st.stored_bound(ref, sr.K_BN, mag, x.act, slack))
+        bounded("%s %s pool0 stream %d" % (x.mode, x.case, n), B["x1"][n][:, :64], ref, st.stored_bound(ref, sr.K_BN, mag, x.act, slack))
 
 
 @pytest.mark.parametrize("t", [1, 2, 3])
@@ -321,8 +261,8 @@ def test_transition_forward(mc, t):
     B = _fwd(x)
     H, Cp = x.H[1 + t], CT[t - 1]
     C0 = Cp // 2
-    g, b = _tp(x, "transition%d.norm.weight" % t), _tp(x, "transition%d.norm.bias" % t)
-    w = _tp(x, "transition%d.conv.weight" % t).reshape(C0, Cp)
+    g, b = x.tp("transition%d.norm.weight" % t), x.tp("transition%d.norm.bias" % t)
+    w = x.tp("transition%d.conv.weight" % t).reshape(C0, Cp)
     pix = dr.sample((H // 2) ** 2)
     cols = np.arange(0, C0, max(1, C0 // 128))
     for n in range(x.NS):
@@ -334,8 +274,8 @@ def test_transition_forward(mc, t):
         mag = sr.avgpool2(a64, H, H) @ np.abs(w.astype(np.float64)).T + 1e-300
         chain = st.storage_chain(sr.avgpool2(st.act32_s(X, g, b, S), H, H)[pix], np.ascontiguousarray(w[cols]), x.fwd, x.act)
         sel = np.ix_(pix, cols)
-        _gate("%s %s transition %d stream %d" % (x.mode, x.case, t, n), dr.rms(got[sel], ref[sel], mag[sel]), dr.rms(chain, ref[sel], mag[sel]), 2.0,
-              e_whole=dr.rms(got, ref, mag), n=chain.size)
+        gate("%s %s transition %d stream %d" % (x.mode, x.case, t, n), dr.rms(got[sel], ref[sel], mag[sel]), dr.rms(chain, ref[sel], mag[sel]), 2.0,
+             e_whole=dr.rms(got, ref, mag), n=chain.size, yard="storage chain")
 
 
 def test_norm5_concat_from_16_bit_x4(mc):
@@ -344,8 +284,8 @@ def test_norm5_concat_from_16_bit_x4(mc):
     them before the store)"""
     x = mc
     B = _fwd(x)
-    g5 = _tp(x, "norm5.weight")
-    ref, mag = sr.feat(list(B["x4"]), g5, _tp(x, "norm5.bias"), x.pa, x.pb)
+    g5 = x.tp("norm5.weight")
+    ref, mag = sr.feat(list(B["x4"]), g5, x.tp("norm5.bias"), x.pa, x.pb)
     HW = x.H[5] ** 2
     sl = [np.concatenate([sr.bn_stat_slack(v[:, :512], g5[:512], (HW // 64) * 64), np.zeros((HW, 512))], axis=1) * sr.U + st.bn_store_slack(v, g5, x.act) for v in B["x4"]]
     for j in range(x.NP):
@@ -362,39 +302,19 @@ def test_head_conv0_forward(mc):
     operand type; statistics PER PAIR, of the stored fp32 features (feat_kernel sums what it stores)"""
     x = mc
     B = _fwd(x)
-    g, b, w = _hp(x, "norm0.weight"), _hp(x, "norm0.bias"), _hp(x, "conv0.weight").reshape(64, 2048)
+    g, b, w = x.hp("norm0.weight"), x.hp("norm0.bias"), x.hp("conv0.weight").reshape(64, 2048)
     for j in range(x.NP):
         ref, a64 = sr.head_conv0(B["feat"][j], g, b, w)
         mag = a64 @ np.abs(w.astype(np.float64)).T + 1e-300
         chain = st.storage_chain(sr.bn32(B["feat"][j], g, b), w, x.fwd)
-        _gate("%s %s head conv0 pair %d" % (x.mode, x.case, j), dr.rms(B["h1"][j], ref, mag), dr.rms(chain, ref, mag), 2.0, n=ref.size)
+        gate("%s %s head conv0 pair %d" % (x.mode, x.case, j), dr.rms(B["h1"][j], ref, mag), dr.rms(chain, ref, mag), 2.0, n=ref.size, yard="storage chain")
 
 
 # ---- backward ----------------------------------------------------------------------------------------------------------------------------
-def _backward_to(x, stop):
-    """a fresh forward, then the backward up to `stop` (the stops are honoured in every mode); returns the finished gradients"""
-    q = _forward(x)
-    dq = torch.tensor(CASES[x.case]["dq"], dtype=torch.float32, device=x.gpu).view(q.shape)
-    x.net.zero_grad()
-    x.eng.set_option("debug_stop", stop)
-    try:
-        x.net._engine_backward(x.net._saved[1], dq)
-    finally:
-        x.eng.set_option("debug_stop", -1)
-    torch.cuda.synchronize()
-    return {n: p.grad.detach().cpu().numpy() for n, p in x.net.named_parameters() if p.grad is not None}
-
-
 def _wgrad_gate(what, got, a64, w64, a32, w32, op):
     """got [M][N] = sum_k a[k][m] * w[k][n] over ALL streams x pixels; the yardstick: the blocked fp32 reduction over both operands
     rounded once to `op`"""
-    ref = a64.T @ w64
-    mag = np.abs(a64).T @ np.abs(w64) + 1e-300
-    e_blk = {bl: dr.rms(st.storage_blocked(a32, w32, op, op, bl), ref, mag) for bl in (64, 512)}
-    e_prod = dr.rms(got, ref, mag)
-    print("%s: err/sum|ab| rms product %.3e, blocked reduction over the %s operands 64-term %.3e / 512-term %.3e over all %d terms, %d elements: ratios %.2f / %.2f"
-          % (what, e_prod, op, e_blk[64], e_blk[512], a64.shape[0], ref.size, e_prod / e_blk[64], e_prod / e_blk[512]))
-    assert e_prod <= _WGRAD_GATE * e_blk[_WGRAD_BLK], (what, e_prod, e_blk)
+    wgrad_gate(what, got, a64, w64, lambda blk: st.storage_blocked(a32, w32, op, op, blk), (64, 512), yard="blocked reduction over the %s operands" % op)
 
 
 def test_head_conv0_and_norm5_backward(mc):
@@ -403,13 +323,13 @@ def test_head_conv0_and_norm5_backward(mc):
     relu(bn0(feat)) for the weight gradient.  norm5_bwd_kernel forms g4 in fp32 from the fp32 df / feat exactly as in mode 0 and rounds
     it once to bf16 (stq<GT>); dgamma5 multiplies by xhat5 of the 16-bit x4, whose statistics were summed before the store."""
     x = mc
-    grads = _backward_to(x, 350)
-    h1, dh1 = _rd(x, "h1", x.NP, 5, 64), _rd(x, "dh1", x.NP, 5, 64)
-    Fm, DF = _rd(x, "feat", x.NP, 5, 2048), _rd(x, "df", x.NP, 5, 2048)
-    x4, g4 = _rd(x, "x4", x.NS, 5, 1024), _rd(x, "g4", x.NS, 5, 1024)
+    grads = x.backward_to(350)
+    h1, dh1 = x.rd("h1", x.NP, 5, 64), x.rd("dh1", x.NP, 5, 64)
+    Fm, DF = x.rd("feat", x.NP, 5, 2048), x.rd("df", x.NP, 5, 2048)
+    x4, g4 = x.rd("x4", x.NS, 5, 1024), x.rd("g4", x.NS, 5, 1024)
     assert np.array_equal(st.rnd(g4, x.grd), g4)
-    g0, b0, g1 = _hp(x, "norm0.weight"), _hp(x, "norm0.bias"), _hp(x, "norm1.weight")
-    w0 = _hp(x, "conv0.weight").reshape(64, 2048)
+    g0, b0, g1 = x.hp("norm0.weight"), x.hp("norm0.bias"), x.hp("norm1.weight")
+    w0 = x.hp("conv0.weight").reshape(64, 2048)
     A64s, A32s, P64s, P32s = [], [], [], []
     for j in range(x.NP):
         ref, A64, on, _ = sr.head_conv0_bwd(h1[j], dh1[j], Fm[j], g1, g0, b0, w0)
@@ -418,25 +338,25 @@ def test_head_conv0_and_norm5_backward(mc):
         chain = (on * st.storage_chain(A32, np.ascontiguousarray(w0.T), x.bwd)).astype(np.float32)
         keep = sr.bn_keep(Fm[j], g0, b0)          # (feat is fp32 and its statistics are those of the stored values: mode 0's rule)
         assert 1 - keep.mean() <= 0.01, ("borderline ReLU signs", 1 - keep.mean())
-        _gate("%s %s head conv0 dgrad pair %d" % (x.mode, x.case, j), _rms(DF[j], ref, mag, keep), _rms(chain, ref, mag, keep), 2.0, n=int(keep.sum()))
+        gate("%s %s head conv0 dgrad pair %d" % (x.mode, x.case, j), _rms(DF[j], ref, mag, keep), _rms(chain, ref, mag, keep), 2.0, n=int(keep.sum()), yard="storage chain")
         A64s.append(A64); A32s.append(A32)
         P64s.append(np.maximum(sr.bn_pre(Fm[j], g0, b0), 0.0)[:, ::8]); P32s.append(sr.bn32(Fm[j], g0, b0)[:, ::8])
     _wgrad_gate("%s %s head conv0 wgrad" % (x.mode, x.case), grads[HEAD + "conv0.weight"].reshape(64, 2048)[::8, ::8],
                 np.concatenate(A64s)[:, ::8], np.concatenate(P64s), np.concatenate(A32s)[:, ::8], np.concatenate(P32s), x.bwd)
 
-    g5 = _tp(x, "norm5.weight")
+    g5 = x.tp("norm5.weight")
     G4, dy5, mag, db, dg, dbm, dgm = sr.norm5_bwd(list(x4), Fm, DF, g0, g5, x.pa, x.pb)
     for s in range(x.NS):
         users = x.NP if s == x.NS - 1 else 1
-        _bounded("%s %s norm5 backward stream %d (%d user%s)" % (x.mode, x.case, s, users, "s" if users > 1 else ""),
-                 g4[s], G4[s], st.stored_bound(G4[s], sr.k_g4(users), np.abs(g5) * mag[s], x.grd))
+        bounded("%s %s norm5 backward stream %d (%d user%s)" % (x.mode, x.case, s, users, "s" if users > 1 else ""),
+                g4[s], G4[s], st.stored_bound(G4[s], sr.k_g4(users), np.abs(g5) * mag[s], x.grd))
     k = sr.k_sums5(x.H[5] ** 2, x.NS - 1, True)
-    _bounded("%s %s norm5.bias gradient" % (x.mode, x.case), grads[TRUNK + "norm5.bias"], db, k * sr.U * dbm)
+    bounded("%s %s norm5.bias gradient" % (x.mode, x.case), grads[TRUNK + "norm5.bias"], db, k * sr.U * dbm)
     # xhat5 = (x - mean5) * inv5 with the engine's mean5 / inv5, summed before x4's store: storage_ref.xhat_sum_slack, per stream
     slack = sum(st.xhat_sum_slack(dy5[s], x4[s], st.plane_stats(x4[s], x.act)) for s in range(x.NS))
     print("%s %s norm5.weight gradient: max |err| at %.2f of the fp32 bound alone (%d roundings of sum |term|)"
           % (x.mode, x.case, float((np.abs(grads[TRUNK + "norm5.weight"] - dg) / (k * sr.U * dgm)).max()), k))
-    _bounded("%s %s norm5.weight gradient" % (x.mode, x.case), grads[TRUNK + "norm5.weight"], dg, k * sr.U * dgm + slack)
+    bounded("%s %s norm5.weight gradient" % (x.mode, x.case), grads[TRUNK + "norm5.weight"], dg, k * sr.U * dgm + slack)
 
 
 @pytest.mark.parametrize("t", [3, 2, 1])
@@ -446,22 +366,22 @@ def test_transition_backward(mc, t):
     fp32 accumulation, 1/4 and gamma_t and the ReLU mask in fp32, one rounding to the bf16 g<t> (stq<GT>).  W_POOL: dX and the 2 x 2
     average of relu(bn_t(x<t>)) both rounded to bf16 (bwd_op_plain), reduced in fp32."""
     x = mc
-    grads = _backward_to(x, (t - 1) * 100 + 50)
+    grads = x.backward_to((t - 1) * 100 + 50)
     H, Cp = x.H[1 + t], CT[t - 1]
     C0, Hn = Cp // 2, H // 2
-    X, Gt = _rd(x, "x%d" % t, x.NS, 1 + t, Cp), _rd(x, "g%d" % t, x.NS, 1 + t, Cp)
-    Xn, Gn = _rd(x, "x%d" % (t + 1), x.NS, 2 + t, CT[t])[:, :, :C0], _rd(x, "g%d" % (t + 1), x.NS, 2 + t, CT[t])[:, :, :C0]
+    X, Gt = x.rd("x%d" % t, x.NS, 1 + t, Cp), x.rd("g%d" % t, x.NS, 1 + t, Cp)
+    Xn, Gn = x.rd("x%d" % (t + 1), x.NS, 2 + t, CT[t])[:, :, :C0], x.rd("g%d" % (t + 1), x.NS, 2 + t, CT[t])[:, :, :C0]
     assert np.array_equal(st.rnd(Gt, x.grd), Gt)
-    g, b = _tp(x, "transition%d.norm.weight" % t), _tp(x, "transition%d.norm.bias" % t)
-    w = _tp(x, "transition%d.conv.weight" % t).reshape(C0, Cp)
+    g, b = x.tp("transition%d.norm.weight" % t), x.tp("transition%d.norm.bias" % t)
+    w = x.tp("transition%d.conv.weight" % t).reshape(C0, Cp)
     q = dr.sample(Hn * Hn)
     qy, qx = q // Hn, q % Hn
     pix = np.stack([(2 * qy + dy) * H + 2 * qx + dx for dy in (0, 1) for dx in (0, 1)], axis=1).ravel()
     cols = np.arange(0, Cp, max(1, Cp // 128))
-    stem = _rd(x, "stem", x.NS, 1, 64) if t == 1 else None          # (untouched at stop 50: the stem's backward has not run)
+    stem = x.rd("stem", x.NS, 1, 64) if t == 1 else None          # (untouched at stop 50: the stem's backward has not run)
     dX64s, dX32s, stats, over = [], [], [], []
     for n in range(x.NS):
-        S = st.x1_stats(X[n], stem[n], x.H[1], _tp(x, "norm0.weight"), _tp(x, "norm0.bias"), x.act) if t == 1 else st.plane_stats(X[n], x.act)
+        S = st.x1_stats(X[n], stem[n], x.H[1], x.tp("norm0.weight"), x.tp("norm0.bias"), x.act) if t == 1 else st.plane_stats(X[n], x.act)
         stats.append(S)
         dX = sr.bn_bwd(Gn[n], Xn[n])
         on = st.bn_pre_s(X[n], g, b, S) > 0
@@ -478,8 +398,8 @@ def test_transition_backward(mc, t):
         up = (np.float32(0.25) * st.storage_chain(dX32[q], np.ascontiguousarray(w.T[cols]), x.bwd)).astype(np.float32)
         sel = np.ix_(pix, cols)
         chain = st.rnd((g[cols] * (on[sel] * np.repeat(up, 4, axis=0)).astype(np.float32)).astype(np.float32), x.grd)
-        _gate("%s %s transition %d dgrad stream %d" % (x.mode, x.case, t, n), _rms(Gt[n][sel], ref[sel], mag[sel], keep[sel]),
-              _rms(chain, ref[sel], mag[sel], keep[sel]), 2.0, e_whole=_rms(Gt[n], ref, mag, keep), n=int(keep[sel].sum()))
+        gate("%s %s transition %d dgrad stream %d" % (x.mode, x.case, t, n), _rms(Gt[n][sel], ref[sel], mag[sel], keep[sel]),
+             _rms(chain, ref[sel], mag[sel], keep[sel]), 2.0, e_whole=_rms(Gt[n], ref, mag, keep), n=int(keep[sel].sum()), yard="storage chain")
     assert tuple(over) == DGRAD_OVER_THE_CAP.get((x.mode, x.case, t), ()), ("borderline ReLU signs over the 1 % cap on streams", over)
     c8 = slice(0, Cp, 8)
     P64 = np.concatenate([sr.avgpool2(st.act64_s(X[n][:, c8], g[c8], b[c8], stats[n].cols(c8)), H, H) for n in range(x.NS)])
