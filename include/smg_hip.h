@@ -169,7 +169,7 @@ int smg_loss_map_ce(smg_engine* e, const float* q_dev, const float* label_dev, i
                     float* loss_dev, float* dq_dev, void* stream);
 
 /* ---- dense Q maps in the scene frame ----------------------------------------------------------------------------------------
- * A dense Q map lives in the ROTATED frame of its rotation, one value per 32 input pixels.  These four entry points undo
+ * A dense Q map lives in the ROTATED frame of its rotation, one value per 32 input pixels.  These entry points undo
  * F.affine_grid / F.grid_sample (code/models.py:372-382) and the head's 20x20 window geometry, so that a caller can read, pick and
  * train Q values at HEIGHTMAP pixels.  For a heightmap of side hm (code/trainer.py:165-173): pad = int((ceil(2 hm sqrt(2) / 32) * 32
  * - 2 hm) / 2), S = 2 hm + 2 pad (the engine's input size), OH = OW = S / 32 - 19 (the engine's).  Coordinates are (x = column,
@@ -188,12 +188,24 @@ int smg_loss_map_ce(smg_engine* e, const float* q_dev, const float* label_dev, i
  * affine_host: 6 float32 per map / pair, row-major 2x3 as in smg_batch.stream_affine; the translation column must be zero.
  * map_stride: element distance between consecutive maps in q_dev - OH * OW for the output of a one-channel head, 3 * OH * OW to
  * address one class plane of a [R][3][OH][OW] tensor.
- * All four return -22 and launch nothing when hm_size does not pad to the engine's S, when the map is 1 x 1 (S = 640: no extent
+ * All of them return -22 and launch nothing when hm_size does not pad to the engine's S, when the map is 1 x 1 (S = 640: no extent
  * to interpolate over), and for n_maps < 1 / K < 1 / n_pairs < 1. */
 
 /* out_dev float32 [n_maps][hm_size][hm_size]: every map in the scene frame, -inf at invalid pixels. */
 int smg_scene_maps(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host,
                    int hm_size, float* out_dev, void* stream);
+
+/* The value of those scene-frame maps at K LISTED heightmap pixels per map, without writing the maps: pixels_dev int32
+ * [n_maps][K][2] = (iy, ix), K points per map (only 4-byte alignment is assumed); out_dev float32 [n_maps][K].  out[m][k] is the
+ * float smg_scene_maps stores at [m][iy][ix], bit for bit: steps 1-7 above in double, rounded to float32 once, -inf where no window
+ * of the head is centred, NaN where a corner is NaN.  A point outside [0, hm_size)^2 is -inf; that is decided before the geometry
+ * and no address is formed from it, so any int32 is legal there.  Any head width is accepted (map_stride = 3 OH OW addresses one
+ * logit plane).  One thread per point, the four corners read from global memory; every element of out is written by every
+ * successful call; no atomics, no scratch of the engine: two identical calls are bit-identical.
+ * Returns -22 and launches nothing for a NULL pointer, n_maps < 1, K < 1, a negative map_stride, n_maps * K beyond int32 and the
+ * geometry refusals above (hm_size, a 1 x 1 map, an affine with a translation). */
+int smg_scene_values(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host,
+                     int hm_size, int K, const int* pixels_dev, float* out_dev, void* stream);
 
 /* The largest valid value of those scene-frame maps and its flattened index into [n_maps][hm_size][hm_size], without writing the
  * maps: idx_out_dev int32[1], val_out_dev float32[1].  The rules are smg_argmax's (lowest index on ties, a NaN wins) with invalid
@@ -265,12 +277,22 @@ int smg_loss_scene_map(smg_engine* e, const float* q_dev, const float* affine_ho
  * (the dense-map form), so picking and training see one and the same function of the head output.  Nothing is special-cased: a
  * NaN, or an inf that produces inf - inf, in any of the twelve corner logits makes all three probabilities NaN, as torch.softmax
  * does in fp64.  An invalid pixel is -inf in every plane, so the argmax rules carry over unchanged.
- * All five return -22 and launch nothing for the geometry refusals above, for n_maps < 1 / K < 1 / n_pairs < 1 and for cls out of range. */
+ * All of them return -22 and launch nothing for the geometry refusals above, for n_maps < 1 / K < 1 / n_pairs < 1 and for cls out of range. */
 
 /* out_dev float32: cls in {0,1,2} -> [n_maps][hm][hm] = P(class cls); cls == -1 -> [n_maps][3][hm][hm], all three.
  * q_dev is [n_maps][3][OH][OW] (the head output of a 3-class engine). */
 int smg_scene_class_maps(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size,
                          int cls, float* out_dev, void* stream);
+
+/* smg_scene_values for the 3-class head: the class probabilities at K listed heightmap pixels per map, without writing the maps.
+ * q_dev is [n_maps][3][OH][OW]; pixels_dev int32 [n_maps][K][2] = (iy, ix) as for smg_scene_values.  out_dev float32: cls in
+ * {0,1,2} -> [n_maps][K] = P(class cls); cls == -1 -> [n_maps][3][K], all three.  Each value is the float smg_scene_class_maps
+ * stores at that pixel, bit for bit (a NaN in any of the twelve corner logits makes it NaN); a point outside the heightmap or
+ * invalid in the map's rotation is -inf in every plane.  Every element of out is written, no atomics, no scratch of the engine.
+ * Returns -22 and launches nothing for a NULL pointer, head_out != 3, n_maps < 1, cls outside {-1,0,1,2}, K < 1, n_maps * K beyond
+ * int32 and the geometry refusals above. */
+int smg_scene_class_values(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                           int K, const int* pixels_dev, float* out_dev, void* stream);
 
 /* Largest valid P(class cls), cls in {0,1,2}, and its flattened index into [n_maps][hm][hm], without writing the maps:
  * idx_out_dev int32[1], val_out_dev float32[1], smg_scene_argmax's rules and bit-reproducibility.  The value comes from the

@@ -529,7 +529,7 @@ static SceneAffine scene_affine(const float* affine_host, int m0, int n) {
     return a;
 }
 
-// What the ten scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
+// What the twelve scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
 // evaluates them and passes each one's text, or nullptr where it does not apply; the first that applies is reported as
 // "<who>: <text>"), the geometry, the one refusal that stands behind it (`after`), the n affines.  Then the device is selected and g
 // is valid.  Nothing has been launched when this returns non-zero.
@@ -571,6 +571,26 @@ int smg_scene_maps(smg_engine* e, const float* q_dev, int64_t map_stride, int n_
     return scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
         hipLaunchKernelGGL(scene_map_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
                            q_dev, map_stride, m0, a, g, out_dev, vec4);
+    });
+}
+
+// smg_scene_values / smg_scene_class_values: K listed pixels per map, one thread per point, nothing of the engine's scratch used.
+static const char* scene_values_fit(int n_maps, int K) {
+    return (int64_t)n_maps * K > 0x7fffffff ? "n_maps * K does not fit int32" : nullptr;
+}
+static int scene_value_blocks(int K) { return (int)(((int64_t)K + 255) / 256); }
+int smg_scene_values(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size, int K,
+                     const int* pixels_dev, float* out_dev, void* stream) {
+    if (!e || !q_dev || !affine_host || !pixels_dev || !out_dev) return fail(-22, "smg_scene_values: NULL argument");
+    SceneGeo g;
+    if (int rc = scene_prelude(e, "smg_scene_values",
+                               {n_maps < 1 || map_stride < 0 ? "n_maps < 1 or a negative map_stride" : nullptr,
+                                K < 1 ? "K < 1" : nullptr,
+                                n_maps >= 1 && K >= 1 ? scene_values_fit(n_maps, K) : nullptr},
+                               hm_size, nullptr, affine_host, n_maps, &g)) return rc;
+    return scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
+        hipLaunchKernelGGL(scene_values_kernel<1>, dim3(scene_value_blocks(K), n), dim3(256), 0, (hipStream_t)stream,
+                           q_dev, map_stride, m0, a, g, 0, K, pixels_dev, out_dev);
     });
 }
 
@@ -688,6 +708,24 @@ int smg_scene_class_maps(smg_engine* e, const float* q_dev, int n_maps, const fl
     return scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
         hipLaunchKernelGGL(scene_class_map_kernel, dim3(tiles, n), dim3(256), (size_t)P3 * sizeof(float), (hipStream_t)stream,
                            q_dev, P3, m0, a, g, cls, out_dev, vec4);
+    });
+}
+
+int smg_scene_class_values(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls, int K,
+                           const int* pixels_dev, float* out_dev, void* stream) {
+    if (!e || !q_dev || !affine_host || !pixels_dev || !out_dev) return fail(-22, "smg_scene_class_values: NULL argument");
+    SceneGeo g;
+    if (int rc = scene_prelude(e, "smg_scene_class_values",
+                               {e->head_out != 3 ? "class probabilities need a 3-class head (head_out == 3)" : nullptr,
+                                n_maps < 1 ? "n_maps < 1" : nullptr,
+                                cls < -1 || cls > 2 ? "cls must be 0, 1, 2 or -1 (all three)" : nullptr,
+                                K < 1 ? "K < 1" : nullptr,
+                                n_maps >= 1 && K >= 1 ? scene_values_fit(n_maps, K) : nullptr},
+                               hm_size, nullptr, affine_host, n_maps, &g)) return rc;
+    const int64_t P3 = (int64_t)3 * g.OH * g.OW;
+    return scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
+        hipLaunchKernelGGL(scene_values_kernel<3>, dim3(scene_value_blocks(K), n), dim3(256), 0, (hipStream_t)stream,
+                           q_dev, P3, m0, a, g, cls, K, pixels_dev, out_dev);
     });
 }
 

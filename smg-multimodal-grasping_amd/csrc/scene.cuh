@@ -6,6 +6,8 @@
 //                                  stored), smg_scene_argmax / smg_scene_class_argmax (true: the best (rotation, pixel), nothing
 //                                  stored) and smg_scene_argmax_objects / smg_scene_class_argmax_objects (SELECT: every map on the
 //                                  pixels its masks select, one result per group of maps)
+//   scene_values_kernel<PLANES>    smg_scene_values / smg_scene_class_values: the same value(s) at K LISTED pixels per map, the
+//                                  corners read from global memory, nothing staged
 //   SceneHuber / SceneCe           the per-point terms of the two losses, each written once
 //   scene_list_walk                the loss on K LISTED pixels per pair (smg_loss_scene_ce; smg_loss_scene's kernel keeps the same
 //                                  loop in a copy of its own, for the reason its comment gives)
@@ -259,6 +261,44 @@ static __global__ __launch_bounds__(256) void scene_argmax_group_reduce_kernel(c
     bv[t] = best; bi[t] = at;
     block_argmax(bv, bi, t);
     if (t == 0) { idx_out[grp] = bi[0] == 0x7fffffff ? -1 : bi[0]; val_out[grp] = bv[0]; }
+}
+
+// ---- the value of a map at K listed heightmap pixels (smg_scene_values, smg_scene_class_values) ----
+// blockIdx.y = map of this launch, blockIdx.x * 256 + threadIdx.x = point k of that map's K; pixels [maps][K][2] = (iy, ix), 4-byte
+// aligned only, hence two 4-byte loads.  A point outside the heightmap is -inf before the geometry: whatever int32 it holds enters
+// no arithmetic and no address.  A point inside goes through scene_point and scene_interp (PLANES == 1) or scene_class +
+// scene_class_prob (PLANES == 3; cls == -1: all three), the functions scene_walk calls, so the float stored here is the one
+// scene_walk stores at [map][iy][ix].  The corners are read from global memory: 4 (12) loads per point of a map that sits in L2,
+// against staging PLANES x OH x OW floats per workgroup for at most 256 points.  No LDS, no barrier, one 4-byte store per plane:
+// out [maps][K], or with cls == -1 [maps][3][K].
+template <int PLANES>
+static __global__ __launch_bounds__(256) void scene_values_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                  const SceneGeo g, int cls, int K, const int* pixels, float* out) {
+    const int m = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= K) return;
+    const int64_t at = (int64_t)(map0 + m) * K + k;
+    const int iy = pixels[2 * at], ix = pixels[2 * at + 1];
+    const int planes = PLANES == 3 && cls < 0 ? 3 : 1;  // planes stored per map
+    float v[PLANES];
+#pragma unroll
+    for (int c = 0; c < PLANES; ++c) v[c] = -INFINITY;
+    if (iy >= 0 && iy < g.hm && ix >= 0 && ix < g.hm) {
+        const ScenePoint p = scene_point(g, (double)aff.a[m][0], (double)aff.a[m][1], (double)aff.a[m][2], (double)aff.a[m][3], iy, ix);
+        if (p.valid) {
+            const float* qm = q + (int64_t)(map0 + m) * map_stride;
+            if constexpr (PLANES == 1) v[0] = (float)scene_interp(p, qm, g.OW);
+            else {
+                const SceneClass c = scene_class(p, qm, g.OH * g.OW, g.OW);
+                if (cls < 0) { v[0] = scene_class_prob(c, 0); v[1] = scene_class_prob(c, 1); v[2] = scene_class_prob(c, 2); }
+                else v[0] = scene_class_prob(c, cls);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < PLANES; ++c) {
+        if (c >= planes) break;
+        out[((int64_t)(map0 + m) * planes + c) * K + k] = v[c];
+    }
 }
 
 // ---- the two losses: what one labelled point contributes, each written once ----

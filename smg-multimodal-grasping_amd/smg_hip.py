@@ -56,7 +56,8 @@ def lib():
     L.smg_version.restype = C.c_int
     if not hasattr(L, "smg_abi_struct_bytes") or L.smg_version() != ABI_VERSION:
         raise SmgError("%s is ABI version %d, this binding needs %d: rebuild it (make -C csrc)" % (LIB_PATH, L.smg_version(), ABI_VERSION))
-    for added in ("smg_loss_scene_map_ce", "smg_scene_argmax_objects", "smg_scene_class_argmax_objects"):       # (added without a version step: a version-9 library built before them lacks the symbol)
+    for added in ("smg_loss_scene_map_ce", "smg_scene_argmax_objects", "smg_scene_class_argmax_objects", "smg_scene_values",
+                  "smg_scene_class_values"):       # (added without a version step: a version-9 library built before them lacks the symbol)
         if not hasattr(L, added):
             raise SmgError("%s is ABI version %d but lacks %s, a stale build: rebuild it (make -C csrc)" % (LIB_PATH, ABI_VERSION, added))
     L.smg_abi_struct_bytes.argtypes = [C.c_int]
@@ -82,6 +83,7 @@ def lib():
     L.smg_loss_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_map_ce.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_scene_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]
+    L.smg_scene_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_scene_argmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_scene_argmax_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int,
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -90,6 +92,7 @@ def lib():
     L.smg_loss_scene_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
     L.smg_scene_class_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.smg_scene_class_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_scene_class_argmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_scene_class_argmax_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -125,7 +128,7 @@ EXPORTS = (
     "smg_last_error", "smg_version", "smg_abi_struct_bytes", "smg_engine_set_option", "smg_layout_count", "smg_layout_param_floats", "smg_layout_buffer_floats",
     "smg_layout_nbt_count", "smg_layout_entry", "smg_layout_trunk_range", "smg_layout_head_range",
     "smg_engine_create", "smg_engine_destroy", "smg_engine_workspace_bytes", "smg_engine_geometry",
-    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_loss_scene","smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_argmax", "smg_scene_class_argmax_objects", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
+    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_values", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_loss_scene","smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_values", "smg_scene_class_argmax", "smg_scene_class_argmax_objects", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
     "smg_profile_enable", "smg_profile_kinds", "smg_profile_kind_name", "smg_profile_read", "smg_profile_read_bytes",
 )
 
@@ -284,6 +287,13 @@ class Engine(object):
         a, p = self._affines(affine, n_maps)
         check(lib().smg_scene_maps(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), out, stream))
 
+    def scene_values(self, q, map_stride, n_maps, affine, hm_size, K, pixels, out, stream):
+        """smg_scene_values: the value of those scene-frame maps at K listed heightmap pixels per map (`pixels` device int32
+        [n_maps, K, 2] = iy, ix) to `out` [n_maps, K], the floats scene_maps stores there, without writing the maps; -inf where
+        invalid or outside the heightmap."""
+        a, p = self._affines(affine, n_maps)
+        check(lib().smg_scene_values(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), int(K), pixels, out, stream))
+
     def scene_argmax(self, q, map_stride, n_maps, affine, hm_size, idx_out, val_out, stream):
         """smg_scene_argmax: the best valid (map, iy, ix) of those scene-frame maps as a flattened index, without writing them."""
         a, p = self._affines(affine, n_maps)
@@ -330,6 +340,13 @@ class Engine(object):
         [n_maps, 3, hm_size, hm_size] for cls -1; -inf where invalid."""
         a, p = self._affines(affine, n_maps)
         check(lib().smg_scene_class_maps(self.h, q, int(n_maps), p, int(hm_size), int(cls), out, stream))
+
+    def scene_class_values(self, q, n_maps, affine, hm_size, cls, K, pixels, out, stream):
+        """smg_scene_class_values: the class probabilities scene_class_maps stores at K listed heightmap pixels per map (`pixels`
+        device int32 [n_maps, K, 2] = iy, ix) to `out` [n_maps, K] for cls 0 / 1 / 2 or [n_maps, 3, K] for cls -1, without
+        writing the maps; -inf where invalid or outside the heightmap."""
+        a, p = self._affines(affine, n_maps)
+        check(lib().smg_scene_class_values(self.h, q, int(n_maps), p, int(hm_size), int(cls), int(K), pixels, out, stream))
 
     def scene_class_argmax(self, q, n_maps, affine, hm_size, cls, idx_out, val_out, stream):
         """smg_scene_class_argmax: the valid (map, iy, ix) with the largest P(class cls) as a flattened index, without writing the maps."""

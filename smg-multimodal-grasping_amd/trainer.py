@@ -316,28 +316,28 @@ class Trainer(object):
             out["bestgs_num"], out["bestgs_conf"] = pair_list[int(i[2])], v[2]
         return out
 
-    def get_label_value(self, primitive_action, objects_number,
-                        suction_success, grasp_success, gs_success,
-                        depth_heightmap, mask_depth, objects_mask,
-                        bestg_id, bests_id, bestgs_g_id, bestgs_s_id,
-                        exploit_action, bestg_conf, bests_conf, bestgs_conf):
-        """code/trainer.py:212-274."""
-        if self.method == 'reactive':
-            label_value = 0
-            if primitive_action == 'suction':
-                success_value = suction_success
-                if not suction_success:
-                    label_value = 1
-            elif primitive_action == 'grasp':
-                success_value = grasp_success
-                if not grasp_success:
-                    label_value = 1
-            elif primitive_action == 'grasp_then_suction':
-                success_value = gs_success
-                label_value = 0 if gs_success == 2.5 else 1
-            print('Label value: %d' % (label_value))
-            return label_value, success_value
+    @staticmethod
+    def _class_label(primitive_action, suction_success, grasp_success, gs_success):
+        """The reactive label of code/trainer.py:214-232, which needs no network: (label_value, success_value), printed."""
+        label_value = 0
+        if primitive_action == 'suction':
+            success_value = suction_success
+            if not suction_success:
+                label_value = 1
+        elif primitive_action == 'grasp':
+            success_value = grasp_success
+            if not grasp_success:
+                label_value = 1
+        elif primitive_action == 'grasp_then_suction':
+            success_value = gs_success
+            label_value = 0 if gs_success == 2.5 else 1
+        print('Label value: %d' % (label_value))
+        return label_value, success_value
 
+    @staticmethod
+    def _reward_now(primitive_action, objects_number, suction_success, grasp_success, gs_success):
+        """The part of code/trainer.py:236-253 that needs no network: (current_reward, whether the future reward is 0 - nothing
+        succeeded, or the scene is cleared)."""
         current_reward = 0
         if primitive_action == 'suction':
             current_reward = suction_success
@@ -346,9 +346,20 @@ class Trainer(object):
         elif primitive_action == 'grasp_then_suction':
             current_reward = gs_success
         if suction_success == 0 and grasp_success == 0 and gs_success == 0:
-            future_reward = 0
-        elif (objects_number == 1 and suction_success == 1) or (objects_number == 1 and grasp_success == 1) or \
-                (objects_number == 2 and gs_success == 2.5):
+            return current_reward, True
+        return current_reward, bool((objects_number == 1 and suction_success == 1) or (objects_number == 1 and grasp_success == 1) or
+                                    (objects_number == 2 and gs_success == 2.5))
+
+    def get_label_value(self, primitive_action, objects_number,
+                        suction_success, grasp_success, gs_success,
+                        depth_heightmap, mask_depth, objects_mask,
+                        bestg_id, bests_id, bestgs_g_id, bestgs_s_id,
+                        exploit_action, bestg_conf, bests_conf, bestgs_conf):
+        """code/trainer.py:212-274."""
+        if self.method == 'reactive':
+            return self._class_label(primitive_action, suction_success, grasp_success, gs_success)
+        current_reward, no_future = self._reward_now(primitive_action, objects_number, suction_success, grasp_success, gs_success)
+        if no_future:
             future_reward = 0
         else:
             if exploit_action == 'grasp':
@@ -1078,6 +1089,230 @@ class Trainer(object):
             eng.loss_scene_map_ce(q.data_ptr(), self._scene_affines(rots, num), hm, n, lab.data_ptr(), loss.data_ptr(), dq.data_ptr(), stream)
         return self._train_maps(depth_heightmap, m_depth_heightmap, style, rotations, (3, side),
                                 lambda dev: _f32_on(dev, lab_h), loss_call, grad_sync, return_q)
+
+    # ---- the value of a GIVEN action in the scene frame: maps read at listed heightmap pixels (smg_scene_values) -------------------
+    @staticmethod
+    def _scene_value_pixels(pixels, n, hm):
+        """The pixel lists of the scene_*_values methods as int64 [n, K, 2], and whether the caller gave the K axis.  n None: one
+        list for every map, [K, 2] or one (iy, ix), returned as [1, K, 2]; else [n, K, 2], or [n, 2] for K = 1.  Integer (iy, ix)
+        inside the hm x hm heightmap, as _scene_pixel_args asks; ValueError otherwise."""
+        pix = np.asarray(pixels)
+        if n is None:
+            listed, n, want = True, 1, "[K, 2] or one (iy, ix)"
+            pix = pix[None, None] if pix.ndim == 1 else pix[None]
+        else:
+            listed, want = pix.ndim != 2, "[%d, K, 2] or [%d, 2]" % (n, n)
+            if pix.ndim == 2:
+                pix = pix[:, None, :]
+        if pix.ndim != 3 or pix.shape[0] != n or pix.shape[1] < 1 or pix.shape[2] != 2:
+            raise ValueError("pixels must be %s = (iy, ix), got %s" % (want, np.shape(pixels)))
+        pix_i = pix.astype(np.int64)
+        if not np.array_equal(pix_i, pix) or pix_i.min() < 0 or pix_i.max() >= hm:
+            raise ValueError("pixels must be integer (iy, ix) inside the %d x %d heightmap" % (hm, hm))
+        return pix_i, listed
+
+    @staticmethod
+    def _read_q_values(eng, q, n_maps, aff, hm, K, pix, stream):
+        """One smg_scene_values on the one-channel maps q [n_maps, 1, OH, OW] -> float32 [n_maps, K] on the device."""
+        out = torch.empty((n_maps, K), dtype=torch.float32, device=q.device)
+        eng.scene_values(q.data_ptr(), q.shape[2] * q.shape[3], n_maps, aff, hm, K, pix.data_ptr(), out.data_ptr(), stream)
+        return out
+
+    @staticmethod
+    def _class_values_reader(what, cls, logits):
+        """read(eng, q, n_maps, aff, hm, K, pix, stream) on the logit maps q [n_maps, 3, OH, OW] -> float32 [n_maps, 3, K], or
+        [n_maps, K] for one `cls`: the probabilities by one smg_scene_class_values, or with `logits` the interpolated logits by one
+        smg_scene_values per class plane (as forward_scene_class_maps uses smg_scene_maps)."""
+        if cls is not None and cls not in (0, 1, 2):
+            raise ValueError("%s: cls must be None (all three), 0, 1 or 2" % what)
+
+        def read(eng, q, n_maps, aff, hm, K, pix, stream):
+            OH, OW = q.shape[2], q.shape[3]
+            if logits:
+                planes = (0, 1, 2) if cls is None else (cls,)
+                out = torch.empty((len(planes), n_maps, K), dtype=torch.float32, device=q.device)
+                for k, c in enumerate(planes):
+                    eng.scene_values(q[:, c].data_ptr(), 3 * OH * OW, n_maps, aff, hm, K, pix.data_ptr(), out[k].data_ptr(), stream)
+                return out.permute(1, 0, 2).contiguous() if cls is None else out[0]
+            out = torch.empty((n_maps, 3, K) if cls is None else (n_maps, K), dtype=torch.float32, device=q.device)
+            eng.scene_class_values(q.data_ptr(), n_maps, aff, hm, -1 if cls is None else cls, K, pix.data_ptr(), out.data_ptr(), stream)
+            return out
+        return read
+
+    @staticmethod
+    def _values_out(out, return_device):
+        return out if return_device else out.cpu().numpy().astype(np.float64)
+
+    def _scene_values_sweep(self, model, depth_heightmap, pixels, style, specific_rotation, forward, read, return_device):
+        """The body of scene_values and scene_class_values (the caller has checked method and geometry): the pixels checked and
+        uploaded, `forward()` - which leaves its maps in self._last_q -, one `read` of all R maps at the same K points."""
+        hm = int(np.shape(depth_heightmap)[-1])
+        pix, _ = self._scene_value_pixels(pixels, None, hm)
+        model._require_gpu()
+        rots = self._scene_rotations(model, style, specific_rotation)
+        pix_dev = _i32_on(model._flat_params.device, np.repeat(pix, len(rots), axis=0))
+        forward()
+        q = self._last_q
+        eng, aff, _, stream = self._scene_call(model, q, depth_heightmap, rots)
+        return self._values_out(read(eng, q, len(rots), aff, hm, pix.shape[1], pix_dev, stream), return_device)
+
+    def _scene_values_objects(self, what, depth_heightmap, mask_depth, pixels, style, is_target, read, return_device):
+        """The body of scene_object_values and scene_class_object_values: _object_maps' one engine call, one `read` over the n * R
+        maps with object k's points repeated for its R maps -> [n, R, ..., K], the K axis dropped where the caller gave [n, 2]."""
+        if style not in (0, 1):
+            raise ValueError("%s: styles 0 (grasp) and 1 (suction)" % what)
+        model = self.model_target if is_target else self.model
+        n, hm = int(np.shape(mask_depth)[0]), int(np.shape(depth_heightmap)[-1])
+        pix, listed = self._scene_value_pixels(pixels, n, hm)
+        model._require_gpu()
+        R = model.snum_rotations if style == 1 else model.gnum_rotations
+        pix_dev = _i32_on(model._flat_params.device, np.repeat(pix, R, axis=0))
+        model, q, _, n, R = self._object_maps(what, depth_heightmap, mask_depth, style, is_target)
+        self._keep_object_q("grasp" if style == 0 else "suction", q)
+        eng, aff, _, stream = self._scene_call(model, q, depth_heightmap, [(r, R) for k in range(n) for r in range(R)])
+        out = read(eng, q, n * R, aff, hm, pix.shape[1], pix_dev, stream)
+        out = out.reshape((n, R) + tuple(out.shape[1:]))
+        return self._values_out(out if listed else out[..., 0], return_device)
+
+    def _scene_values_pairs(self, depth_heightmap, mask_depth, pixels, is_target, read, return_device):
+        """The body of scene_object_pair_values and scene_class_object_pair_values: _object_pair_maps' one engine call (style 2,
+        rotation 0) and one `read` over the n_pairs maps -> ([n_pairs, ..., K] - the K axis dropped for [n_pairs, 2] -, [(g, s)]).
+        With fewer than two objects nothing runs and the values are empty."""
+        model = self.model_target if is_target else self.model
+        n, hm = int(np.shape(mask_depth)[0]), int(np.shape(depth_heightmap)[-1])
+        n_pairs = n * (n - 1) // 2
+        if not n_pairs:
+            dev = model._flat_params.device
+            return torch.empty(0, dtype=torch.float32, device=dev) if return_device else np.empty(0, dtype=np.float64), []
+        pix, listed = self._scene_value_pixels(pixels, n_pairs, hm)
+        model._require_gpu()
+        pix_dev = _i32_on(model._flat_params.device, pix)
+        model, q, _, idx = self._object_pair_maps(depth_heightmap, mask_depth, is_target)
+        self._keep_object_q("pairs", q)
+        eng, aff, _, stream = self._scene_call(model, q, depth_heightmap, [(0, model.gnum_rotations)] * n_pairs)
+        out = read(eng, q, n_pairs, aff, hm, pix.shape[1], pix_dev, stream)
+        return self._values_out(out if listed else out[..., 0], return_device), idx
+
+    def _keep_object_q(self, name, q):
+        """self._last_object_q[name] = q, beside what best_scene_actions / best_scene_class_actions left there."""
+        kept = dict(getattr(self, "_last_object_q", None) or {})
+        kept[name] = q
+        self._last_object_q = kept
+
+    def scene_values(self, depth_heightmap, m_depth_heightmap, pixels, style=0, is_target=False, specific_rotation=-1, return_device=False):
+        """forward_scene read at LISTED heightmap pixels: `pixels` [K, 2] = (iy, ix), or one (iy, ix) -> float64 [R, K] (or the
+        float32 device tensor), equal to forward_scene(...)[:, iy, ix] bit for bit - forward_dense's engine call, rotation choice
+        and BN bookkeeping, then one smg_scene_values: R * K floats are written instead of R * hm * hm.  A pixel without a window
+        of the head in a rotation is -inf there and raises nothing.  The maps stay in self._last_q.  With is_target and a specific
+        rotation this is the reference's target forward of code/trainer.py:255-270 plus one point.  Reinforcement method,
+        heightmaps larger than 224^2."""
+        self._require_scene("scene_values", depth_heightmap)
+        return self._scene_values_sweep(
+            self.model_target if is_target else self.model, depth_heightmap, pixels, style, specific_rotation,
+            lambda: self.forward_dense(depth_heightmap, m_depth_heightmap, style, is_target, specific_rotation, return_device=True),
+            self._read_q_values, return_device)
+
+    def scene_object_values(self, depth_heightmap, mask_depth, pixels, style=0, is_target=False, return_device=False):
+        """gra_conf / suc_conf of code/main.py:165-166 on a heightmap larger than 224^2, read at the caller's action points
+        (masks_cter): `pixels` [n, 2] = object k's own (iy, ix), or [n, K, 2] -> float64 [n, R] or [n, R, K] (or the float32 device
+        tensor).  forward_objects' one engine call (R + n trunk passes, the reference's BN sequence) and one smg_scene_values over
+        the n * R maps, which stay in self._last_object_q["grasp" / "suction"].  -inf where a pixel has no window in a rotation.
+        Styles 0 / 1, reinforcement method."""
+        self._require_scene("scene_object_values", depth_heightmap)
+        return self._scene_values_objects("scene_object_values", depth_heightmap, mask_depth, pixels, style, is_target,
+                                          self._read_q_values, return_device)
+
+    def scene_object_pair_values(self, depth_heightmap, mask_depth, pixels, is_target=False, return_device=False):
+        """gs_conf of code/main.py:183-192 at given points: `pixels` [n_pairs, 2] or [n_pairs, K, 2] in forward_object_pairs' pair
+        order -> (float64 [n_pairs] or [n_pairs, K] - or the float32 device tensor -, [(g, s)]); the maps stay in
+        self._last_object_q["pairs"].  With fewer than two objects nothing runs.  Reinforcement method."""
+        self._require_scene("scene_object_pair_values", depth_heightmap)
+        return self._scene_values_pairs(depth_heightmap, mask_depth, pixels, is_target, self._read_q_values, return_device)
+
+    def scene_class_values(self, depth_heightmap, m_depth_heightmap, pixels, style=0, specific_rotation=-1, cls=None, logits=False,
+                           return_device=False):
+        """forward_scene_class_maps read at LISTED heightmap pixels: `pixels` [K, 2] or one (iy, ix) -> float64 [R, 3, K] class
+        probabilities, or [R, K] for one `cls` (or the float32 device tensor), bit for bit what forward_scene_class_maps gives at
+        those pixels - one smg_scene_class_values, or with `logits` one smg_scene_values per class plane.  -inf where a pixel has
+        no window in a rotation.  The logits stay in self._last_q.  Reactive method, heightmaps larger than 224^2."""
+        self._require_scene_class("scene_class_values", depth_heightmap)
+        return self._scene_values_sweep(
+            self.model, depth_heightmap, pixels, style, specific_rotation,
+            lambda: self.forward_class_maps(depth_heightmap, m_depth_heightmap, style, specific_rotation, logits=True, return_device=True),
+            self._class_values_reader("scene_class_values", cls, logits), return_device)
+
+    def scene_class_object_values(self, depth_heightmap, mask_depth, pixels, style=0, cls=0, logits=False, return_device=False):
+        """scene_object_values for the reactive net: P(class `cls`) - or with `logits` the interpolated logit - of every (object,
+        rotation) at object k's own points, `pixels` [n, 2] or [n, K, 2] -> [n, R] or [n, R, K] ([n, R, 3(, K)] for cls None).  The
+        logits stay in self._last_object_q["grasp" / "suction"]."""
+        self._require_class_objects("scene_class_object_values", depth_heightmap, mask_depth)
+        self._scene_geometry(np.shape(depth_heightmap)[-1])
+        return self._scene_values_objects("scene_class_object_values", depth_heightmap, mask_depth, pixels, style, False,
+                                          self._class_values_reader("scene_class_object_values", cls, logits), return_device)
+
+    def scene_class_object_pair_values(self, depth_heightmap, mask_depth, pixels, cls=0, logits=False, return_device=False):
+        """scene_object_pair_values for the reactive net: (P(class `cls`) or the logit of every pair's style-2 map at its points,
+        [(g, s)]).  The logits stay in self._last_object_q["pairs"]."""
+        self._require_class_objects("scene_class_object_pair_values", depth_heightmap, mask_depth)
+        self._scene_geometry(np.shape(depth_heightmap)[-1])
+        return self._scene_values_pairs(depth_heightmap, mask_depth, pixels, False,
+                                        self._class_values_reader("scene_class_object_pair_values", cls, logits), return_device)
+
+    # ---- the two calls that close the loop of code/main.py on a heightmap larger than 224^2 --------------------------------------
+    @staticmethod
+    def _scene_action(what, best, action, depth_heightmap, mask_depth):
+        """The action `best` (best_scene_actions' or best_scene_class_actions' dict) names for the primitive `action` ->
+        (masked heightmap, style, rotation, pixel): 'grasp' bestg_id = (k, r) and bestg_pixel on depth * mask[k]; 'suction' the
+        bests_ keys; 'grasp_then_suction' bestgs_num = (g, s) and bestgs_pixel on depth * (mask[g] + mask[s]), rotation 0."""
+        if action not in _ACTION_STYLE:
+            raise ValueError("%s: unknown primitive %r" % (what, action))
+        style = _ACTION_STYLE[action]
+        key = ("bestg_id", "bests_id", "bestgs_num")[style]
+        pixel = None if best is None else best.get(("bestg_pixel", "bests_pixel", "bestgs_pixel")[style])
+        ids = None if best is None else best.get(key)
+        if ids is None or pixel is None:
+            raise ValueError("%s: best[%r] is None - best_scene_actions found no %s action in this scene" % (what, key, action))
+        depth = np.asarray(depth_heightmap)
+        if style == 2:
+            return depth * (mask_depth[ids[0]] + mask_depth[ids[1]]), 2, 0, tuple(pixel)
+        return depth * mask_depth[ids[0]], style, int(ids[1]), tuple(pixel)
+
+    def get_label_value_scene(self, primitive_action, objects_number, suction_success, grasp_success, gs_success,
+                              depth_heightmap, mask_depth, best, exploit_action):
+        """get_label_value (code/trainer.py:212-274, code/main.py:317) on a heightmap larger than 224^2, with `best` the dict
+        best_scene_actions returned for the current scene.  Reinforcement: rewards and the two zero-future cases are
+        get_label_value's; otherwise the future reward is the TARGET net's value at the action the online net chose for
+        `exploit_action` - object(s), rotation and pixel from `best` (_scene_action), one scene_values(..., is_target=True,
+        specific_rotation=r) at that one pixel: the reference's two-stream, one-rotation target forward plus one point.  A None
+        id for the chosen primitive raises ValueError.  Prints the reference's line, returns (expected_reward, current_reward).
+        Reactive: get_label_value's (label_value, success_value); no forward runs and `best` may be None."""
+        if self.method == 'reactive':
+            return self._class_label(primitive_action, suction_success, grasp_success, gs_success)
+        current_reward, no_future = self._reward_now(primitive_action, objects_number, suction_success, grasp_success, gs_success)
+        if no_future:
+            future_reward = 0
+        else:
+            m, style, rot, pixel = self._scene_action("get_label_value_scene", best, exploit_action, depth_heightmap, mask_depth)
+            future_reward = self.scene_values(depth_heightmap, m, [pixel], style, is_target=True, specific_rotation=rot)[0, 0]
+        expected_reward = current_reward + self.future_reward_discount * future_reward
+        print('Expected reward: %f + %f x %f = %f' % (current_reward, self.future_reward_discount, future_reward, expected_reward))
+        return expected_reward, current_reward
+
+    def backprop_scene(self, depth_heightmap, primitive_action, best, label_value, objects_mask):
+        """backprop (code/trainer.py:334-384, code/main.py:338) on a heightmap larger than 224^2: the reference's one-sample step
+        on the EXECUTED action - object(s), rotation and heightmap pixel taken from `best` (_scene_action) - as one
+        train_batch_scene_pixels (reinforcement, Huber against `label_value`) or train_batch_scene_class_pixels (reactive, the
+        class label) with one sample and one pixel.  `objects_mask` is [n, H, H] or [n, H, H, 1] and is not reshaped in place.
+        Prints the reference's line and returns the loss as a 0-d array."""
+        mask_depth = np.asarray(objects_mask)
+        if mask_depth.ndim == 4:
+            mask_depth = mask_depth[..., 0]
+        m, style, rot, pixel = self._scene_action("backprop_scene", best, primitive_action, depth_heightmap, mask_depth)
+        step = self.train_batch_scene_pixels if self.method == 'reinforcement' else self.train_batch_scene_class_pixels
+        loss = step(depth_heightmap, m, style, [rot], [[pixel]], [label_value])
+        loss_value = np.asarray(loss.cpu().numpy()[0])
+        print('Training loss: %f' % (loss_value))
+        return loss_value
 
     # The single-sample step of Trainer.backprop as ONE replayed hipGraph (smg_train_step_graph): ~560 launches of 2-20 us each are
     # enqueued by one hipGraphLaunch instead of one by one (same results, bit for bit at zero learning rate).  It saves a little host time
