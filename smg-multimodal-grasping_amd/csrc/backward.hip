@@ -65,14 +65,27 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                                        K_OTHER, 0, ESZ(e) * NS * pl.HW * 3 * kGrowth, false, a));
     };
 
+    // The two activation operands of dense layer (b, i) (ActSrc): X[b] through norm1, channels c0 on, with the forward's table - the
+    // 1x1 weight gradient in both its forms (c0 = 0) and the per-layer 1x1 data gradient's mask (c0 = the group's lowest channel) read
+    // it; Bt through norm2 - the 3x3 data gradient's mask and the 3x3 weight gradient (the generic 3x3 path leaves no table of the
+    // bottleneck: the fp64 sums).  The transition kernels read no table: their operand takes the sums.
+    auto norm1_src = [&](int b, int i, int c0) {
+        const DenseLayerRef& d = T.layers[b][i];
+        return act_src(e, e->X[b], kBlockCtot[b], e->st_X[b], c0, P + d.n1.w, P + d.n1.b, stat_table(e, e->sx_tab[b], e->max_streams, kBlockCtot[b]), asc_n1(e, b, i));
+    };
+    auto norm2_src = [&](int b, int i) {
+        const DenseLayerRef& d = T.layers[b][i];
+        return act_src(e, el(e, e->Bt, e->bt_off[b][i]), kBottleneck, e->st_Bt[b][i], 0, P + d.n2.w, P + d.n2.b,
+                       !e->generic3x3 ? stat_table(e, e->sb_tab[b][i], e->max_streams, kBottleneck) : StatTab{}, asc_n2(e, b, i));
+    };
+
     // the partial-tile workspace of this call and its pending reductions (wgrad_plan.h has the rules)
     PartialTiles tiles(e->part_floats, NS, e->deterministic);
 
     if (ph_a) {
     {   // value conv backward + relu1 + norm1 sums
         ValueBwdArgs a;
-        a.h1 = e->H1; a.p4 = p4; a.hsum = fsum(e, e->st_H1); a.hsq = fsq(e, e->st_H1);
-        a.gamma = P + Hd.n1.w; a.beta = P + Hd.n1.b; a.eps = kEps; a.w2p = e->packed_f + e->pk_head1;
+        a.h1 = head_norm1_src(e, Hd, P); a.p4 = p4; a.w2p = e->packed_f + e->pk_head1;
         a.dq = dq; a.out_ch = e->head_out; a.OH = e->OH; a.OW = e->OW; a.dh1 = e->DH1;
         a.o1 = b1(e, e->st_H1); a.o2 = b2(e, e->st_H1); a.dbeta = Gr + Hd.n1.b; a.dgamma = Gr + Hd.n1.w; a.dw2 = Gr + Hd.c1.w;
         // a dense dq (the mark of smg_loss_map / smg_loss_map_ce, or "head_bwd" = 2) takes the two-pass form without atomics on the weight
@@ -82,7 +95,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             launch_kernel(e, value_bwd_kernel, dim3((p4.HW + 63) / 64, NP), dim3(256), 0, st, K_OTHER, 0, 0, false, a);
         } else {
             ValueWgradDenseArgs w;
-            w.h1 = a.h1; w.p4 = p4; w.hsum = a.hsum; w.hsq = a.hsq; w.gamma = a.gamma; w.beta = a.beta; w.eps = kEps;
+            w.h1 = a.h1; w.p4 = p4;
             w.dq = dq; w.OH = e->OH; w.OW = e->OW; w.n_pairs = NP; w.dw2 = a.dw2;
             w.RC = std::min(e->OH, 64); w.OWp = (e->OW + 3) / 4 * 4; w.Wp = w.OWp + kVFrame;
             auto go = [&](auto oc) {
@@ -98,13 +111,13 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
     int chunk4, cps4;
     pick_chunk(p4, NP, 2 * kFeat / 64, chunk4, cps4);
     const GradSrc dh1 = grad_src(e, e->DH1, kHeadMid, e->H1, kHeadMid, e->st_H1, 0, P + Hd.n1.w);      // dy1 through norm1: both conv0 gradients read it
+    const ActSrc f0 = act_src(e, e->F, 2 * kFeat, e->st_F, 0, P + Hd.n0.w, P + Hd.n0.b);                // F through the head's norm0: likewise
     {   // head conv0 weight gradient
         auto go = [&](auto ptag) -> int {
         BwdWeightP<CfgW64x64, W_ONE, C_IDENT, kPdWgrad, true, decltype(ptag)::value, true> p{};      // fp32 head buffers in every mode
         p.gs = dh1; p.pa = p4; p.MA = kHeadMid;
-        p.bbuf = e->F; p.ldb = 2 * kFeat; p.pb = p4; p.NB = 2 * kFeat;
-        p.bsum = fsum(e, e->st_F); p.bsq = fsq(e, e->st_F); p.bstride = 2 * kFeat; p.bgamma = P + Hd.n0.w; p.bbeta = P + Hd.n0.b;
-        p.eps = kEps; p.chunk = chunk4; p.chunks_per_stream = cps4; p.n_chunks = NP * cps4;
+        p.bsrc = f0; p.pb = p4; p.NB = 2 * kFeat;
+        p.chunk = chunk4; p.chunks_per_stream = cps4; p.n_chunks = NP * cps4;
         p.dw = Gr + Hd.c0.w; p.ldw_out = 2 * kFeat;
         if (fork(e->ev_misc)) return -5;
         const dim3 grid(1, 2 * kFeat / 64, NP * cps4);
@@ -119,11 +132,10 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 BwdDataP<Cfg, false, E_STORE, true, decltype(ptag)::value, true> p{};      // fp32 head buffers in every mode
         p.gs = dh1; p.pa = p4; p.KA = kHeadMid;
         p.wp = e->packed_u + e->pk_hd0; p.K8tot = kHeadMid / 8; p.ldn = 2 * kFeat; p.wcol0 = 0; p.N = 2 * kFeat;
-        p.mbuf = e->F; p.ldm = 2 * kFeat; p.mcoff = 0; p.pm = p4;
-        p.msum = fsum(e, e->st_F); p.msq = fsq(e, e->st_F); p.mstride = 2 * kFeat; p.egamma = P + Hd.n0.w; p.ebeta = P + Hd.n0.b;
+        p.m = f0; p.pm = p4;
         p.dst = e->DF; p.ldd = 2 * kFeat; p.dcoff = 0;
         p.o1 = b1(e, e->st_F); p.o2 = b2(e, e->st_F); p.ostride = 2 * kFeat; p.ocoff = 0;
-        p.dbeta = Gr + Hd.n0.b; p.dgamma = Gr + Hd.n0.w; p.rep_stride = 0; p.eps = kEps;
+        p.dbeta = Gr + Hd.n0.b; p.dgamma = Gr + Hd.n0.w; p.rep_stride = 0;
         launch_gemm(e, st, p, dim3(NP * p4.HWp / Cfg::BM, 2 * kFeat / Cfg::BN), K_HD0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid,
                     4.0 * NP * p4.HW * (2 * kHeadMid + 2 * 2 * kFeat));
             };
@@ -132,7 +144,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
     {   // head norm0 backward + concat backward + norm5 backward -> G'_4
         Norm5BwdArgs a;
         a.df = grad_src(e, e->DF, 2 * kFeat, e->F, 2 * kFeat, e->st_F, 0, P + Hd.n0.w); a.p4 = p4;
-        a.x4 = e->X[3]; a.xsum = fsum(e, e->st_X[3]); a.xsq = fsq(e, e->st_X[3]); a.gamma5 = P + T.norm5.w; a.eps = kEps;
+        a.x4 = norm5_src(e, T, P);
         a.user_ptr = e->d_user_ptr; a.user_pair = e->d_user_pair; a.user_slot = e->d_user_slot;
         a.G4 = e->G[3]; a.SA = b1(e, e->st_X[3]); a.SB = b2(e, e->st_X[3]);
         a.dbeta5 = Gr + T.norm5.b; a.dgamma5 = Gr + T.norm5.w; a.chunk = 16;
@@ -155,9 +167,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
     // layer's D2 / GS).
     auto issue_wgrads = [&](int b, int i) -> int {
         const Plane pl = e->p_blk[b];
-        const int Ct = kBlockCtot[b];
         const DenseLayerRef& d = T.layers[b][i];
-        float* bt = el(e, e->Bt, e->bt_off[b][i]);
         const LayerBuf lb = buf_of(b, i);
         const WgradPlan w = plan_layer_wgrads(pl, d.cin, NS, e->prec, split16, e->deterministic, e->part_floats, e->generic3x3, e->generic_w1);
         GradSrc gsrc = fused_gsrc(b, d);
@@ -170,9 +180,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             if (at.refused) return fail(-12, tiles.refusal());
             launch_reduce2(e, s2, at.first);
             Halo3x3WgradArgs a;
-            a.g = gsrc; a.pl = pl; a.src = bt; a.C = kBottleneck;
-            a.bt = bn_table(e, e->sb_tab[b][i], e->max_streams, 0, kBottleneck, P + d.n2.w, P + d.n2.b);
-            a.asc = asc_n2(e, b, i);
+            a.g = gsrc; a.pl = pl; a.b = norm2_src(b, i); a.C = kBottleneck;
             a.tiles_x = w.w3.tiles_x; a.n_tiles = w.w3.n_tiles; a.tiles_per_wg = w.w3.tiles_per_wg;
             a.part = part_at(e, at);
             a.groups = w.w3.groups; a.streams = NS;
@@ -190,9 +198,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             pick_chunk(pl, NS, 9, chunk, cps);      // (9 workgroups per chunk: one per tap)
             BwdWeightP<CfgW32x128, W_THREE, C_3x3, kPdWgrad, false> p{};
             p.gs = grad_done(lb.GS, kGrowth); p.pa = pl; p.MA = kGrowth;
-            p.bbuf = bt; p.ldb = kBottleneck; p.pb = pl; p.NB = kBottleneck;
-            p.bsum = fsum(e, e->st_Bt[b][i]); p.bsq = fsq(e, e->st_Bt[b][i]); p.bstride = kBottleneck;
-            p.bgamma = P + d.n2.w; p.bbeta = P + d.n2.b; p.eps = kEps;
+            p.bsrc = norm2_src(b, i); p.pb = pl; p.NB = kBottleneck;
             p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
             p.dw = Gr + d.c2.w; p.ldw_out = kBottleneck * 9;
             const dim3 grid(1, 1, 9 * NS * cps);
@@ -203,8 +209,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             using G = WswGeo;
             static_assert(G::BN == kW1WsTileN, "plan_layer_wgrads counts this kernel's column tiles");
             Wgrad1x1WsArgs a{};
-            a.d2 = reinterpret_cast<const u32x4*>(lb.D2); a.binv = lb.D2S; a.x = e->X[b]; a.ldb = Ct; a.pl = pl; a.NB = d.cin;
-            a.btab = stat_table(e, e->sx_tab[b], e->max_streams, Ct); a.bgamma = P + d.n1.w; a.bbeta = P + d.n1.b; a.basc = asc_n1(e, b, i);
+            a.d2 = reinterpret_cast<const u32x4*>(lb.D2); a.binv = lb.D2S; a.b = norm1_src(b, i, 0); a.pl = pl; a.NB = d.cin;
             a.chunk = w.chunk; a.chunks_per_stream = w.cps; a.n_chunks = NS * w.cps;
             a.dw = Gr + d.c1.w; a.ldw_out = d.cin; a.ldp = w.nt * G::BN;
             const PartialTiles::Slot at = tiles.place_behind3x3((int64_t)a.n_chunks * G::BM * a.ldp, true);
@@ -222,10 +227,8 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             static_assert(Cfg::BN == kW1TileN, "plan_layer_wgrads counts this kernel's column tiles");
             auto go = [&](auto ptag) -> int {
                 BwdWeightP<MC<Cfg, decltype(ptag)::value>, W_ONE, C_IDENT, kPdWgrad, false, decltype(ptag)::value> p{};
-                p.gs = grad_done(lb.D2, kBottleneck); p.pa = pl; p.MA = kBottleneck; p.binv = lb.D2S; p.basc = asc_n1(e, b, i);
-                p.bbuf = e->X[b]; p.ldb = Ct; p.pb = pl; p.NB = d.cin;
-                p.bsum = fsum(e, e->st_X[b]); p.bsq = fsq(e, e->st_X[b]); p.bstride = Ct; p.btab = stat_table(e, e->sx_tab[b], e->max_streams, Ct);
-                p.bgamma = P + d.n1.w; p.bbeta = P + d.n1.b; p.eps = kEps;
+                p.gs = grad_done(lb.D2, kBottleneck); p.pa = pl; p.MA = kBottleneck; p.binv = lb.D2S;
+                p.bsrc = norm1_src(b, i, 0); p.pb = pl; p.NB = d.cin;
                 p.chunk = w.chunk; p.chunks_per_stream = w.cps; p.n_chunks = NS * w.cps;
                 p.dw = Gr + d.c1.w; p.ldw_out = d.cin;
                 const dim3 grid(1, w.nt, NS * w.cps);
@@ -272,6 +275,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         for (int i = (int)T.layers[b].size() - 1; i >= 0; --i) {
             const DenseLayerRef& d = T.layers[b][i];
             float* bt = el(e, e->Bt, e->bt_off[b][i]);
+            const ActSrc n2 = norm2_src(b, i);      // Bt through norm2: the 3x3 data gradient's mask (its weight gradient builds the same on the side stream)
             const LayerBuf lb = buf_of(b, i);
             float* GSb = lb.GS;
             float* D2b = lb.D2;
@@ -291,10 +295,9 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             if (!e->generic3x3) {
                 // conv2 (3x3) data gradient with the gradient halo resident in LDS (halo.cuh)
                 Halo3x3DgradArgs a;
-                a.g = gsrc; a.pl = pl; a.C = kBottleneck;
-                a.mbuf = bt;
+                a.g = gsrc; a.pl = pl; a.C = kBottleneck; a.m = n2;
                 a.dst = split16 ? e->DY2 : D2b; a.o1 = b1(e, e->st_Bt[b][i]); a.o2 = b2(e, e->st_Bt[b][i]); a.ostride = kBottleneck;
-                a.wu = e->packed_u + e->pk_hd[b][i]; a.bt = bn_table(e, e->sb_tab[b][i], e->max_streams, 0, kBottleneck, P + d.n2.w, P + d.n2.b);
+                a.wu = e->packed_u + e->pk_hd[b][i];
                 // (traced launches: dev stamps with SMG_TRACE_KIND=5)
                 const double flops = 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth;
                 const double bytes = ESZ(e) * NS * pl.HW * (kGrowth + 2 * kBottleneck);      // gradient in, mask source in, dy out
@@ -318,12 +321,10 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                     BwdDataP<Cfg, true, E_STORE, false> p{};
                     p.gs = grad_done(GSb, kGrowth); p.pa = pl; p.KA = kGrowth;
                     p.wp = e->packed_u + e->pk_g3d[b][i]; p.K8tot = 9 * kGrowth / 8; p.ldn = kBottleneck; p.wcol0 = 0; p.N = kBottleneck;
-                    p.mbuf = bt; p.ldm = kBottleneck; p.mcoff = 0; p.pm = pl;
-                    p.msum = fsum(e, e->st_Bt[b][i]); p.msq = fsq(e, e->st_Bt[b][i]); p.mstride = kBottleneck;
-                    p.egamma = P + d.n2.w; p.ebeta = P + d.n2.b;
+                    p.m = n2; p.pm = pl;
                     p.dst = split16 ? e->DY2 : D2b; p.ldd = kBottleneck; p.dcoff = 0;
                     p.o1 = b1(e, e->st_Bt[b][i]); p.o2 = b2(e, e->st_Bt[b][i]); p.ostride = kBottleneck; p.ocoff = 0;
-                    p.dbeta = Gr + d.n2.b; p.dgamma = Gr + d.n2.w; p.eps = kEps;
+                    p.dbeta = Gr + d.n2.b; p.dgamma = Gr + d.n2.w;
                     launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, kBottleneck / Cfg::BN), K_D3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth,
                                 ESZ(e) * NS * pl.HW * (kGrowth + 2 * kBottleneck));
                 };
@@ -372,12 +373,10 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                     BwdDataP<Cfg, false, E_ACCUM, false, decltype(ptag)::value> p{};
                     p.gs = grad_done(D2b, kBottleneck); p.pa = pl; p.KA = kBottleneck; p.binv = lb.D2S;
                     p.wp = e->packed_u + e->pk_d1[b][i]; p.K8tot = kBottleneck / 8; p.ldn = d.cin; p.wcol0 = cs; p.N = d.cin - cs;
-                    p.mbuf = e->X[b]; p.ldm = Ct; p.mcoff = cs; p.pm = pl;
-                    p.msum = fsum(e, e->st_X[b]); p.msq = fsq(e, e->st_X[b]); p.mstride = Ct; p.mtab = stat_table(e, e->sx_tab[b], e->max_streams, Ct);
-                    p.egamma = P + d.n1.w + cs; p.ebeta = P + d.n1.b + cs;
+                    p.m = norm1_src(b, i, cs); p.pm = pl;
                     p.dst = e->G[b]; p.ldd = Ct; p.dcoff = cs;
                     p.o1 = b1(e, e->st_X[b]); p.o2 = b2(e, e->st_X[b]); p.ostride = Ct; p.ocoff = cs;
-                    p.dbeta = e->dbscr + e->db_off[b][i] + cs; p.dgamma = e->dbscr + e->db_off[b][i] + d.cin + cs; p.rep_stride = e->db_total; p.eps = kEps;
+                    p.dbeta = e->dbscr + e->db_off[b][i] + cs; p.dgamma = e->dbscr + e->db_off[b][i] + d.cin + cs; p.rep_stride = e->db_total;
                     launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, (p.N + Cfg::BN - 1) / Cfg::BN), K_D1, 2.0 * NS * pl.HW * p.N * kBottleneck,
                                 ESZ(e) * NS * pl.HW * (kBottleneck + 3.0 * p.N));          // dy in; x in, G' read + written
                 };
@@ -397,10 +396,9 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                         p.seg[k].dbeta = e->dbscr + e->db_off[b][g_lo + k]; p.seg[k].dgamma = e->dbscr + e->db_off[b][g_lo + k] + dk.cin;
                     }
                     p.ldg = kBottleneck; p.pa = pl; p.KA = kBottleneck; p.N = cs;
-                    p.mbuf = e->X[b]; p.ldm = Ct;
-                    p.msum = fsum(e, e->st_X[b]); p.msq = fsq(e, e->st_X[b]); p.mstride = Ct; p.mtab = stat_table(e, e->sx_tab[b], e->max_streams, Ct);
+                    p.m = act_src(e, e->X[b], Ct, e->st_X[b], 0, nullptr, nullptr, stat_table(e, e->sx_tab[b], e->max_streams, Ct));      // (gamma / beta: per segment)
                     p.dst = e->G[b]; p.ldd = Ct;
-                    p.o1 = b1(e, e->st_X[b]); p.o2 = b2(e, e->st_X[b]); p.ostride = Ct; p.rep_stride = e->db_total; p.eps = kEps;
+                    p.o1 = b1(e, e->st_X[b]); p.o2 = b2(e, e->st_X[b]); p.ostride = Ct; p.rep_stride = e->db_total;
                     launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, (cs + Cfg::BN - 1) / Cfg::BN), K_D1, 2.0 * NS * pl.HW * cs * kBottleneck * p.nseg,
                                 ESZ(e) * NS * pl.HW * ((double)p.nseg * kBottleneck + 3.0 * cs));
                 };
@@ -415,15 +413,14 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             const Plane pp = e->p_blk[b - 1];
             const int Cp = kBlockCtot[b - 1], C0 = kBlockCin[b];
             const GradSrc gx = grad_src(e, e->G[b], Ct, e->X[b], Ct, e->st_X[b], 0, nullptr);      // the block's first C0 channels: both transition gradients read them
+            const ActSrc xt = act_src(e, e->X[b - 1], Cp, e->st_X[b - 1], 0, P + T.tnorm[b - 1].w, P + T.tnorm[b - 1].b, StatTab{}, asc_trans(e, b - 1));      // X[b-1] through the transition norm: likewise
             {
                 int chunk, cps;
                 pick_chunk(pl, NS, (C0 / 128) * (Cp / 128), chunk, cps);
                 auto go = [&](auto ptag) -> int {
                 BwdWeightP<MC<CfgW128x128, decltype(ptag)::value>, W_POOL, C_IDENT, 1, true, decltype(ptag)::value> p{};      // (one k-tile in flight: the pooling fetch holds 4 float4 per slot, three tiles of them leave one workgroup per CU)
                 p.gs = gx; p.pa = pl; p.MA = C0;
-                p.bbuf = e->X[b - 1]; p.ldb = Cp; p.pb = pp; p.NB = Cp;
-                p.bsum = fsum(e, e->st_X[b - 1]); p.bsq = fsq(e, e->st_X[b - 1]); p.bstride = Cp;
-                p.bgamma = P + T.tnorm[b - 1].w; p.bbeta = P + T.tnorm[b - 1].b; p.eps = kEps;
+                p.bsrc = xt; p.pb = pp; p.NB = Cp;
                 p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
                 p.dw = Gr + T.tconv[b - 1].w; p.ldw_out = Cp;
                 if (fork(e->ev_misc)) return -5;
@@ -443,12 +440,10 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 BwdDataP<Cfg, false, E_UNPOOL, true, decltype(ptag)::value> p{};
                 p.gs = gx; p.pa = pl; p.KA = C0;
                 p.wp = e->packed_u + e->pk_td[b - 1]; p.K8tot = C0 / 8; p.ldn = Cp; p.wcol0 = 0; p.N = Cp;
-                p.mbuf = e->X[b - 1]; p.ldm = Cp; p.mcoff = 0; p.pm = pp;
-                p.msum = fsum(e, e->st_X[b - 1]); p.msq = fsq(e, e->st_X[b - 1]); p.mstride = Cp;
-                p.egamma = P + T.tnorm[b - 1].w; p.ebeta = P + T.tnorm[b - 1].b;
+                p.m = xt; p.pm = pp;
                 p.dst = e->G[b - 1]; p.ldd = Cp; p.dcoff = 0;
                 p.o1 = b1(e, e->st_X[b - 1]); p.o2 = b2(e, e->st_X[b - 1]); p.ostride = Cp; p.ocoff = 0;
-                p.dbeta = e->dbscr + e->db_toff[b - 1]; p.dgamma = e->dbscr + e->db_toff[b - 1] + Cp; p.rep_stride = e->db_total; p.eps = kEps;
+                p.dbeta = e->dbscr + e->db_toff[b - 1]; p.dgamma = e->dbscr + e->db_toff[b - 1] + Cp; p.rep_stride = e->db_total;
                 launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, Cp / Cfg::BN), K_TD, 2.0 * NS * pl.HW * Cp * C0,
                             ESZ(e) * NS * (2.0 * pl.HW * C0 + 2.0 * pp.HW * Cp));
             };
@@ -462,8 +457,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         StemTailArgs a;
         a.g1 = grad_src(e, e->G[0], kBlockCtot[0], e->X[0], kBlockCtot[0], e->st_X[0], 0, nullptr); a.p1 = p1;
         a.argmax = e->argmax; a.stemv = e->stemv;
-        a.ssum = fsum(e, e->st_stem); a.ssq = fsq(e, e->st_stem); a.ps = e->p_stem;
-        a.gamma = P + T.norm0.w; a.eps = kEps;
+        a.stem = act_src(e, nullptr, 64, e->st_stem, 0, P + T.norm0.w, nullptr); a.ps = e->p_stem;      // (the stem plane is not read here)
         a.img = e->img4; a.pi = e->p_img;
         a.o1 = b1(e, e->st_stem); a.o2 = b2(e, e->st_stem);
         a.tiles_x = (p1.W + kTailTW - 1) / kTailTW; a.n_tiles = a.tiles_x * ((p1.H + kTailTH - 1) / kTailTH);
@@ -485,7 +479,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         if (fork(e->ev_misc)) return -5;
         launch_reduce2(e, s2, tiles.launched(at, reduce_chunk_major(a.part, Z, 1, 64, 49, 64, 64, Gr + T.conv0.w, 147, C_STEM1)));
         StemCombineArgs c;
-        c.mom = e->mom; c.w0 = P + T.conv0.w; c.dy = grad_src(e, nullptr, 64, nullptr, 64, e->st_stem, 0, a.gamma);      // (neither dy0 nor the stem plane exists here)
+        c.mom = e->mom; c.w0 = P + T.conv0.w; c.dy = grad_src(e, nullptr, 64, nullptr, 64, e->st_stem, 0, a.stem.gamma);      // (neither dy0 nor the stem plane exists here)
         c.HW = e->p_stem.HW; c.ns = NS; c.dw = Gr + T.conv0.w;
         launch_kernel(e, stem_combine_kernel, dim3(64), dim3(256), (size_t)(NS * kMomRows + 256) * sizeof(double), s2, K_OTHER, 0, 0, false, c);
     }
@@ -493,9 +487,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
     {   // pool0 / relu0 backward + norm0 sums
         Pool0BwdArgs a;
         a.g1 = grad_src(e, e->G[0], kBlockCtot[0], e->X[0], kBlockCtot[0], e->st_X[0], 0, nullptr); a.p1 = e->p_blk[0];
-        a.argmax = e->argmax; a.stem = e->stem; a.ps = e->p_stem;
-        a.ssum = fsum(e, e->st_stem); a.ssq = fsq(e, e->st_stem);
-        a.gamma = P + T.norm0.w; a.beta = P + T.norm0.b; a.eps = kEps;
+        a.argmax = e->argmax; a.stem = act_src(e, e->stem, 64, e->st_stem, 0, P + T.norm0.w, P + T.norm0.b); a.ps = e->p_stem;
         a.DY0 = e->DY0; a.o1 = b1(e, e->st_stem); a.o2 = b2(e, e->st_stem);
         a.dbeta = Gr + T.norm0.b; a.dgamma = Gr + T.norm0.w;
         if (e->p_stem.H % 8 || e->p_stem.W % 8) return fail(-22, "stem plane must tile by 8 (input_size multiple of 16)");
@@ -512,8 +504,8 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         using WCfg = typename std::conditional<SM == W_STEM1, CfgW64x64, CfgW64x256>::type;
         BwdWeightP<WCfg, SM, SM == W_STEM1 ? C_STEM1 : C_STEM, kPdWgrad, true, decltype(ptag)::value> p{};      // (fp32 image / stem plane in every mode)
         p.gs = grad_src(e, e->DY0, 64, e->stem, 64, e->st_stem, 0, P + T.norm0.w); p.pa = ps_; p.MA = 64;
-        p.bbuf = e->img4; p.ldb = 4; p.pb = e->p_img; p.NB = SM == W_STEM1 ? 64 : 196;
-        p.eps = kEps; p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
+        p.bsrc.x = e->img4; p.bsrc.ldx = 4; p.pb = e->p_img; p.NB = SM == W_STEM1 ? 64 : 196;      // (the image: no BN in front of conv0)
+        p.chunk = chunk; p.chunks_per_stream = cps; p.n_chunks = NS * cps;
         p.dw = Gr + T.conv0.w; p.ldw_out = 147;
         if (fork(e->ev_misc)) return -5;
         const dim3 grid(1, 1, NS * cps);

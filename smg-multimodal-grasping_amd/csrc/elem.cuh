@@ -250,7 +250,7 @@ static __global__ void pack_weights_kernel(const PackDesc* descs, const float* p
 // ------------------------------------------------------------------------------------
 // BN statistics table entries for channels whose producer is not a dense layer (block inputs after pool0 / a
 // transition, the head's concatenated features): fp64 sums -> fp32 mean | invstd, once.  The channels a dense
-// layer appends are finished by their first consumer instead (BnTab, gemm.cuh) - no launch of their own.
+// layer appends are finished by their first consumer instead (ActSrc, gemm.cuh) - no launch of their own.
 // ------------------------------------------------------------------------------------
 struct BnStatArgs {
     const double* sum; const double* sq; int sstride;          // [row][sstride] statistics
@@ -274,9 +274,7 @@ static __global__ void bn_stat_kernel(const BnStatArgs a) {
 // Workgroup = 64 pooled pixels x 64 channels; thread = (channel quad, pixel slot).
 // ------------------------------------------------------------------------------------
 struct Pool0Args {
-    const float* stem; Plane ps;           // [n][HWp][64]
-    const double* ssum; const double* ssq;  // [n][64]
-    const float* gamma; const float* beta; float eps;
+    ActSrc stem; Plane ps;                 // raw stem output [n][HWp][64] (fp32), its statistics [n][64] and norm0
     void* x1; int ldx; Plane po;            // block-1 buffer (activation storage of the mode)
     double* dsum; double* dsq; int dstride;
     unsigned char* argmax;                  // [n][po.HWp][64]
@@ -290,11 +288,7 @@ static __global__ __launch_bounds__(256) void pool0_kernel(const Pool0Args a) {
     __shared__ double red[2][16][64];
     const int n = blockIdx.y, t = threadIdx.x, cq = t & 15, slot = t >> 4;
     if (t < 64) {
-        float mean, invstd;
-        bn_moments(a.ssum, a.ssq, (int64_t)n * 64 + t, 1.0 / (double)a.ps.HW, a.eps, mean, invstd);
-        prm[t] = mean;
-        prm[64 + t] = a.gamma[t] * invstd;
-        prm[128 + t] = a.beta[t];
+        act_prm_store(prm + t, 64, act_src_coef<A_SUMS>(a.stem, n, t, 1.0 / (double)a.ps.HW), 1.f);
     }
     __syncthreads();
     double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
@@ -308,7 +302,7 @@ static __global__ __launch_bounds__(256) void pool0_kernel(const Pool0Args a) {
         for (int k = 0; k < 9; ++k) {
             const int yy = 2 * y - 1 + k / 3, xx = 2 * x - 1 + k % 3;
             if ((unsigned)yy >= (unsigned)a.ps.H || (unsigned)xx >= (unsigned)a.ps.W) continue;
-            const float4 r = ld4(a.stem + ((int64_t)n * a.ps.HWp + yy * a.ps.W + xx) * 64 + 4 * cq);
+            const float4 r = ld4(static_cast<const float*>(a.stem.x) + ((int64_t)n * a.ps.HWp + yy * a.ps.W + xx) * 64 + 4 * cq);
             const float4 v = bnrelu4(r, prm + 4 * cq, 64);
             const float vv[4] = {v.x, v.y, v.z, v.w}, rr[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
@@ -339,9 +333,7 @@ static __global__ __launch_bounds__(256) void pool0_kernel(const Pool0Args a) {
 // per-(pair, channel) statistics the head's norm0 needs.
 // ------------------------------------------------------------------------------------
 struct FeatArgs {
-    const void* x4; Plane p4;               // [n][HWp][1024] (activation storage of the mode)
-    const double* xsum; const double* xsq;  // [n][1024]
-    const float* gamma; const float* beta; float eps;   // norm5
+    ActSrc x4; Plane p4;                    // [n][HWp][1024] (activation storage of the mode), its statistics [n][1024] and norm5
     const int* pair_a; const int* pair_b;
     float* F;                               // [pair][HWp][2048]
     double* fsum; double* fsq;              // [pair][2048]
@@ -357,16 +349,16 @@ static __global__ __launch_bounds__(256) void feat_kernel(const FeatArgs a) {
     float mu[4], sc[4], be[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        float invstd;
-        bn_moments(a.xsum, a.xsq, (int64_t)s * 1024 + c5 + c, 1.0 / (double)a.p4.HW, a.eps, mu[c], invstd);
-        sc[c] = a.gamma[c5 + c] * invstd;
-        be[c] = a.beta[c5 + c];
+        const ActCoef f = act_src_coef<A_SUMS>(a.x4, s, c5 + c, 1.0 / (double)a.p4.HW);
+        mu[c] = f.mean;
+        sc[c] = f.gamma * f.invstd;
+        be[c] = f.beta;
     }
     double sm[4] = {0, 0, 0, 0}, sq[4] = {0, 0, 0, 0};
     const int p0 = blockIdx.z * a.chunk;
     const int p1 = min(p0 + a.chunk, a.p4.HW);
     for (int p = p0; p < p1; ++p) {
-        const float4 v = ldq<XT>(a.x4, ((int64_t)s * a.p4.HWp + p) * 1024 + c5);
+        const float4 v = ldq<XT>(a.x4.x, ((int64_t)s * a.p4.HWp + p) * 1024 + c5);
         float4 o;
         o.x = bn1(v.x, mu[0], sc[0], be[0]); o.y = bn1(v.y, mu[1], sc[1], be[1]);
         o.z = bn1(v.z, mu[2], sc[2], be[2]); o.w = bn1(v.w, mu[3], sc[3], be[3]);
@@ -387,9 +379,7 @@ static __global__ __launch_bounds__(256) void feat_kernel(const FeatArgs a) {
 // One workgroup per output element; fixed summation order -> reproducible argmax.
 // ------------------------------------------------------------------------------------
 struct ValueArgs {
-    const float* h1; Plane p4;               // [pair][HWp][64]
-    const double* hsum; const double* hsq;   // [pair][64]
-    const float* gamma; const float* beta; float eps;
+    ActSrc h1; Plane p4;                     // [pair][HWp][64] (fp32), its statistics [pair][64] and the head's norm1
     const float* w2p;                        // packed [out][400][64]
     float* q; int out_ch, OH, OW;
 };
@@ -404,17 +394,13 @@ static __global__ __launch_bounds__(256) void value_conv_kernel(const ValueArgs 
     const int o = id % a.out_ch;
     const int j = id / a.out_ch;
     if (t < 64) {
-        float mean, invstd;
-        bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
-        prm[t] = mean;
-        prm[64 + t] = a.gamma[t] * invstd;
-        prm[128 + t] = a.beta[t];
+        act_prm_store(prm + t, 64, act_src_coef<A_SUMS>(a.h1, j, t, 1.0 / (double)a.p4.HW), 1.f);
     }
     __syncthreads();
     float acc = 0.f;
     for (int tap = slot; tap < 400; tap += 16) {
         const int pix = (oy + tap / 20) * a.p4.W + ox + tap % 20;
-        const float4 v = bnrelu4(ld4(a.h1 + ((int64_t)j * a.p4.HWp + pix) * 64 + 4 * cq), prm + 4 * cq, 64);
+        const float4 v = bnrelu4(ld4(static_cast<const float*>(a.h1.x) + ((int64_t)j * a.p4.HWp + pix) * 64 + 4 * cq), prm + 4 * cq, 64);
         const float4 w = ld4(a.w2p + ((int64_t)o * 400 + tap) * 64 + 4 * cq);
         acc = fmaf(v.x, w.x, acc); acc = fmaf(v.y, w.y, acc); acc = fmaf(v.z, w.z, acc); acc = fmaf(v.w, w.w, acc);
     }
@@ -432,9 +418,7 @@ static __global__ __launch_bounds__(256) void value_conv_kernel(const ValueArgs 
 //   dy = dact * [BN(h1) > 0] -> DH1 ; sums of dy, dy*xhat per (pair, c);
 //   dW[o][c][tap] += dq * act.
 struct ValueBwdArgs {
-    const float* h1; Plane p4;
-    const double* hsum; const double* hsq;
-    const float* gamma; const float* beta; float eps;
+    ActSrc h1; Plane p4;                      // [pair][HWp][64] (fp32), its statistics [pair][64] and the head's norm1
     const float* w2p;                         // packed [out][400][64]
     const float* dq; int out_ch, OH, OW;
     float* dh1;                               // [pair][HWp][64]
@@ -449,11 +433,7 @@ struct ValueBwdArgs {
 // instruction behind in the dense kernels); per channel a 16-way sum in slot order, one double atomic to o1 / o2 and one float
 // atomic to dbeta / dgamma per workgroup.
 __device__ __forceinline__ void value_bwd_params(const ValueBwdArgs& a, int j, int t, float* prm) {
-    if (t < 64) {
-        float mean, invstd;
-        bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
-        prm[t] = a.gamma[t] * invstd; prm[64 + t] = a.beta[t]; prm[128 + t] = mean; prm[192 + t] = invstd;
-    }
+    if (t < 64) act_mask_store(prm + t, 64, act_src_coef<A_SUMS>(a.h1, j, t, 1.0 / (double)a.p4.HW));
 }
 __device__ __forceinline__ void value_bwd_sums(const ValueBwdArgs& a, int j, int t, const float (*red)[16][64]) {
     if (t < 128) {
@@ -477,7 +457,7 @@ static __global__ __launch_bounds__(256) void value_bwd_kernel(const ValueBwdArg
         if (p >= a.p4.HW) continue;
         const int py = p / a.p4.W, px = p - py * a.p4.W;
         const int64_t row = (int64_t)j * a.p4.HWp + p;
-        const float4 hv = ld4(a.h1 + row * 64 + 4 * cq);
+        const float4 hv = ld4(static_cast<const float*>(a.h1.x) + row * 64 + 4 * cq);
         const float h[4] = {hv.x, hv.y, hv.z, hv.w};
         float act[4], dact[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -594,7 +574,7 @@ static __global__ __launch_bounds__(256) void value_bwd_dense_kernel(const Value
     for (int i = 0; i < 4; ++i) {
         if (!live[i]) continue;
         const int64_t row = (int64_t)j * a.p4.HWp + blockIdx.x * 64 + slot + 16 * i;
-        const float4 hv = ld4(a.h1 + row * 64 + 4 * cq);
+        const float4 hv = ld4(static_cast<const float*>(a.h1.x) + row * 64 + 4 * cq);
         const float h[4] = {hv.x, hv.y, hv.z, hv.w};
         float dy[4];
 #pragma unroll
@@ -623,9 +603,7 @@ static __global__ __launch_bounds__(256) void value_bwd_dense_kernel(const Value
 // workgroups that each stage the activations for themselves (the 60 per-tap-column accumulators of a 3-class head, in fp32 and fp64,
 // would not fit one thread's registers without scratch), same order of summation per element.
 struct ValueWgradDenseArgs {
-    const float* h1; Plane p4;
-    const double* hsum; const double* hsq;
-    const float* gamma; const float* beta; float eps;
+    ActSrc h1; Plane p4;                      // the descriptor ValueBwdArgs holds
     const float* dq; int OH, OW, n_pairs;
     float* dw2;                               // native [out][64][20][20]
     int RC, OWp, Wp;                          // output rows per chunk (<= 64), OW rounded up to 4, OWp + 19 staged columns
@@ -649,18 +627,14 @@ static __global__ __launch_bounds__(256) void value_wgrad_dense_kernel(const Val
 #pragma unroll
     for (int k = 0; k < 20; ++k) tot[k] = 0.0;
     for (int j = 0; j < a.n_pairs; ++j) {
-        if (t < 4) {
-            float mean, invstd;
-            bn_moments(a.hsum, a.hsq, (int64_t)j * 64 + 4 * cq + t, 1.0 / (double)a.p4.HW, a.eps, mean, invstd);
-            prm[t] = mean; prm[4 + t] = a.gamma[4 * cq + t] * invstd; prm[8 + t] = a.beta[4 * cq + t];
-        }
+        if (t < 4) act_prm_store(prm + t, 4, act_src_coef<A_SUMS>(a.h1, j, 4 * cq + t, 1.0 / (double)a.p4.HW), 1.f);
         for (int r0 = 0; r0 < a.OH; r0 += a.RC) {
             const int nr = min(a.RC, a.OH - r0);
             __syncthreads();        // the parameters are written; the previous chunk has been read
             for (int i = t; i < nr * a.Wp; i += 256) {
                 const int row = i / a.Wp, x = i - row * a.Wp;
                 float4 v = zero4();
-                if (x < W) v = bnrelu4(ld4(a.h1 + ((int64_t)j * a.p4.HWp + (r0 + row + ty) * W + x) * 64 + 4 * cq), prm, 4);
+                if (x < W) v = bnrelu4(ld4(static_cast<const float*>(a.h1.x) + ((int64_t)j * a.p4.HWp + (r0 + row + ty) * W + x) * 64 + 4 * cq), prm, 4);
                 *reinterpret_cast<float4*>(acts + (size_t)i * 4) = v;
             }
             for (int i = t; i < nr * a.OWp; i += 256) {
@@ -711,8 +685,7 @@ static __global__ __launch_bounds__(256) void value_wgrad_dense_kernel(const Val
 // ------------------------------------------------------------------------------------
 struct Norm5BwdArgs {
     GradSrc df; Plane p4;                           // the head's gradient of F through norm0: fp32 [pair][HWp][2048], statistics [pair][2048]
-    const void* x4; const double* xsum; const double* xsq;    // [n][HWp][1024] (activation storage), [n][1024]
-    const float* gamma5; float eps;
+    ActSrc x4;                                      // [n][HWp][1024] (activation storage), its statistics [n][1024] and norm5: the descriptor FeatArgs holds
     const int* user_ptr; const int* user_pair; const int* user_slot;  // CSR over streams
     void* G4;                                       // [n][HWp][1024] (gradient storage of the mode)
     double* SA; double* SB;                         // [n][1024]
@@ -745,8 +718,8 @@ static __global__ __launch_bounds__(256) void norm5_bwd_kernel(const Norm5BwdArg
     float mean5[4], inv5[4], g5[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        bn_moments(a.xsum, a.xsq, (int64_t)s * 1024 + c5 + c, inv, a.eps, mean5[c], inv5[c]);
-        g5[c] = a.gamma5[c5 + c];
+        const ActCoef f = act_src_coef<A_SUMS, 1>(a.x4, s, c5 + c, inv);
+        mean5[c] = f.mean; inv5[c] = f.invstd; g5[c] = f.gamma;
     }
     float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
     for (int sub = 0; sub < n_sub; ++sub) {
@@ -775,7 +748,7 @@ static __global__ __launch_bounds__(256) void norm5_bwd_kernel(const Norm5BwdArg
                 const int64_t fr = ((int64_t)j * a.p4.HWp + p) * 2048 + ch;
                 const float4 d = affine2(ld4(static_cast<const float*>(a.df.g) + fr), ld4(static_cast<const float*>(a.df.x) + fr), cf, 4);
                 const int64_t xr = ((int64_t)s * a.p4.HWp + p) * 1024 + c5;
-                const float4 xv = ldq<XT>(a.x4, xr);
+                const float4 xv = ldq<XT>(a.x4.x, xr);
                 const float dd[4] = {d.x, d.y, d.z, d.w}, xx[4] = {xv.x, xv.y, xv.z, xv.w};
                 gacc[q].x += g5[0] * dd[0]; gacc[q].y += g5[1] * dd[1]; gacc[q].z += g5[2] * dd[2]; gacc[q].w += g5[3] * dd[3];
 #pragma unroll
@@ -830,9 +803,7 @@ static __global__ __launch_bounds__(256) void norm5_bwd_kernel(const Norm5BwdArg
 struct Pool0BwdArgs {
     GradSrc g1; Plane p1;                                    // block 1's G' / X, channels 0..63 (gradient / activation storage of the mode)
     const unsigned char* argmax;                             // [n][p1.HWp][64]
-    const float* stem; Plane ps;                             // raw stem output [n][HWp][64]
-    const double* ssum; const double* ssq;                   // [n][64]
-    const float* gamma; const float* beta; float eps;        // norm0
+    ActSrc stem; Plane ps;                                   // raw stem output [n][HWp][64] (fp32), its statistics [n][64] and norm0
     float* DY0;                                              // [n][ps.HWp][64]
     double* o1; double* o2;                                  // [n][64]
     float* dbeta; float* dgamma;
@@ -856,9 +827,7 @@ static __global__ __launch_bounds__(256) void pool0_bwd_kernel(const Pool0BwdArg
     const int n = blockIdx.y, t = threadIdx.x, cq = t & 15, slot = t >> 4;
     const int tiles_x = a.ps.W / 8, n_tiles = tiles_x * (a.ps.H / 8);
     if (t < 64) {
-        float mean, invstd;
-        bn_moments(a.ssum, a.ssq, (int64_t)n * 64 + t, 1.0 / (double)a.ps.HW, a.eps, mean, invstd);
-        prm[t] = a.gamma[t] * invstd; prm[64 + t] = a.beta[t]; prm[128 + t] = mean; prm[192 + t] = invstd;
+        act_mask_store(prm + t, 64, act_src_coef<A_SUMS>(a.stem, n, t, 1.0 / (double)a.ps.HW));
         const double inv = 1.0 / (double)a.p1.HW;
         const GradCoef f = grad_src_coef(a.g1, n, t, inv);
         prm[256 + t] = f.a; prm[320 + t] = f.q1; prm[384 + t] = f.mean; prm[448 + t] = f.k;
@@ -875,7 +844,7 @@ static __global__ __launch_bounds__(256) void pool0_bwd_kernel(const Pool0BwdArg
     for (int i = 0; i < 4; ++i) {
         const int lp = slot + 16 * i;                       // local pixel 0..63
         srow[i] = (int64_t)n * a.ps.HWp + (y0 + (lp >> 3)) * a.ps.W + x0 + (lp & 7);
-        sv[i] = ld4(a.stem + srow[i] * 64 + 4 * cq);
+        sv[i] = ld4(static_cast<const float*>(a.stem.x) + srow[i] * 64 + 4 * cq);
     }
     // pooled pixels wy in [y0/2, y0/2 + 4], wx likewise
     const int wy0 = y0 >> 1, wx0 = x0 >> 1;
@@ -965,8 +934,7 @@ constexpr int kTailTW = 16, kTailTH = 4, kTailIW = 4 * kTailTW + 7, kTailIH = 4 
 struct StemTailArgs {
     GradSrc g1; Plane p1;                                    // block 1's G' / X, channels 0..63 (fp32: mode 0)
     const unsigned char* argmax; const float* stemv;         // [n][p1.HWp][64] (pool0_kernel)
-    const double* ssum; const double* ssq; Plane ps;         // stem stats [n][64]
-    const float* gamma; float eps;                           // norm0
+    ActSrc stem; Plane ps;                                   // stem stats [n][64] and norm0 (no plane: x unset)
     const float* img; Plane pi;                              // one-channel image [n][pi.HWp]
     double* o1; double* o2;                                  // [n][64]
     float* part;                                             // [n][gridDim.x][64][64]
@@ -997,9 +965,8 @@ static __global__ __launch_bounds__(256) void stem_tail_kernel(const StemTailArg
     static_assert(2 * 16 * 64 <= 64 * kTailGl, "the s1 / s2 reduction reuses gl");
     const int n = blockIdx.y, t = threadIdx.x, cq = t & 15, slot = t >> 4;
     if (t < 64) {
-        float mean, invstd;
-        bn_moments(a.ssum, a.ssq, (int64_t)n * 64 + t, 1.0 / (double)a.ps.HW, a.eps, mean, invstd);
-        prm[256 + t] = mean; prm[320 + t] = invstd; prm[384 + t] = a.gamma[t] * invstd;
+        const ActCoef s0 = act_src_coef<A_SUMS, 1>(a.stem, n, t, 1.0 / (double)a.ps.HW);      // (gamma alone)
+        prm[256 + t] = s0.mean; prm[320 + t] = s0.invstd; prm[384 + t] = s0.gamma * s0.invstd;
         const double inv = 1.0 / (double)a.p1.HW;
         const GradCoef f = grad_src_coef(a.g1, n, t, inv);
         prm[t] = f.a; prm[64 + t] = f.q1; prm[128 + t] = f.mean; prm[192 + t] = f.k;

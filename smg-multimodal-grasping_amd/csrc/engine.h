@@ -131,7 +131,7 @@ struct smg_engine {
     float* asc = nullptr; ActScaleDesc* d_asc = nullptr; int n_asc = 0;
     unsigned* gamax = nullptr; int64_t gamax_words = 0;
     // BN statistics as fp32 tables (mean | invstd, [rows][C] each): one per dense-block buffer, one per bottleneck, one
-    // for the head's features; written by the first consumer of a channel (BnTab, gemm.cuh), kept until the backward
+    // for the head's features; written by the first consumer of a channel (ActSrc, gemm.cuh), kept until the backward
     float* stab = nullptr; int64_t stab_floats = 0;
     int64_t sx_tab[4] = {}, sb_tab[4][24] = {}, sf_tab = 0;
     // bn update descriptors
@@ -433,17 +433,40 @@ static inline unsigned* gamax_of(const smg_engine* e, int b, int i, int kind) {
     return e->gamax + ((int64_t)(2 * layer_seq(b, i) + kind) * e->max_streams) * kAmaxRep;
 }
 
-// BN statistics table at float offset `at` of the table arena ([rows_max][C] mean, then invstd), from row r0 on, with the
-// affine parameters of the consuming BatchNorm
-static StatTab stat_table(smg_engine* e, int64_t at, int rows_max, int C, int c0 = 0) {      // the same table from channel c0 on, read-only view for the backward
+// BN statistics table at float offset `at` of the table arena ([rows_max][C] mean, then invstd), from channel c0 on
+static StatTab stat_table(smg_engine* e, int64_t at, int rows_max, int C, int c0 = 0) {
     StatTab t; t.mean = e->stab + at + c0; t.invstd = t.mean + (int64_t)rows_max * C; t.ld = C; return t;
 }
-static BnTab bn_table(smg_engine* e, int64_t at, int rows_max, int r0, int C, const float* gamma, const float* beta) {
-    BnTab t;
-    t.mean = e->stab + at + (int64_t)r0 * C; t.invstd = t.mean + (int64_t)rows_max * C; t.ld = C; t.gamma = gamma; t.beta = beta;
-    return t;
+// The activation operand (ActSrc, gemm.cuh) that reads the raw activation from `buf` (nullptr: the statistics side alone) with the
+// statistics handle `s` (and its one stride), channels c0 on: `buf`, `gamma`, `beta` and `tab` are given at channel 0 and every
+// pointer is moved to channel c0 here.  Buffers with c0 != 0 are mode-typed (el).  Affine pair, table and scale are optional.
+static inline ActSrc act_src(smg_engine* e, float* buf, int ld, const StatArr& s, int c0, const float* gamma, const float* beta,
+                             StatTab tab = StatTab{}, const float* asc = nullptr) {
+    ActSrc r{};
+    r.x = buf ? el(e, buf, c0) : nullptr; r.ldx = ld;
+    r.sum = fsum(e, s) + c0; r.sq = fsq(e, s) + c0; r.sstride = s.stride;
+    if (tab.mean) { r.tab = tab; r.tab.mean += c0; r.tab.invstd += c0; }
+    r.gamma = gamma ? gamma + c0 : nullptr; r.beta = beta ? beta + c0 : nullptr;
+    r.asc = asc; r.eps = kEps;
+    return r;
 }
-
+// ... and in the forward, for the chain that runs streams (or pairs) r0 on: `buf` is given at stream r0, the sums and the table rows
+// are moved there; the table is also writable, and channels fresh0 on have no entry in it yet.
+static inline ActSrc act_src_fwd(smg_engine* e, float* buf, int ld, const StatArr& s, int r0, const float* gamma, const float* beta,
+                                 StatTab tab = StatTab{}, int fresh0 = 0, const float* asc = nullptr) {
+    ActSrc r = act_src(e, buf, ld, s, 0, gamma, beta, tab, asc);
+    r.sum += (int64_t)r0 * s.stride; r.sq += (int64_t)r0 * s.stride;
+    if (tab.mean) { r.tab.mean += (int64_t)r0 * tab.ld; r.tab.invstd += (int64_t)r0 * tab.ld; }
+    r.tw_mean = const_cast<float*>(r.tab.mean); r.tw_invstd = const_cast<float*>(r.tab.invstd); r.fresh0 = fresh0;
+    return r;
+}
+// the operands two walks share: X[3] through norm5 (feat_kernel, norm5_bwd_kernel) and H1 through the head's norm1 (the value kernels)
+static inline ActSrc norm5_src(smg_engine* e, const TrunkRef& T, const float* P) {
+    return act_src(e, e->X[3], kBlockCtot[3], e->st_X[3], 0, P + T.norm5.w, P + T.norm5.b);
+}
+static inline ActSrc head_norm1_src(smg_engine* e, const HeadRef& Hd, const float* P) {
+    return act_src(e, e->H1, kHeadMid, e->st_H1, 0, P + Hd.n1.w, P + Hd.n1.b);
+}
 
 int validate_batch(const smg_engine* e, const smg_batch* B);
 void fill_stage(const smg_engine* e, const smg_batch* B, int* h);

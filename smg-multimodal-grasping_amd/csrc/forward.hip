@@ -92,12 +92,12 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
     // The trunk of streams [s0, s0 + ns).  Streams are independent up to the head (BN statistics are per stream), so
     // the batch is run as TWO chains on two HIP streams: the tail of one chain's kernel overlaps the other chain's
     // next kernel (two full sweeps side by side take 83 % of their serial time, tests/gpu_concurrency_probe.py).
-    // BN table of one consumer layer (rows [r0, r0 + rows) of a [max rows][C] table at float offset `at`) + the launch that fills it
-    // table entries of channels [c0, c0 + C) whose producer is not a dense layer (block inputs, head features)
-    auto bn_stat = [&](hipStream_t cs, const BnTab& t, int rows, const double* sum, const double* sq, int sstride, int c0, int C, int count) {
+    // The launch that fills the table entries of channels [c0, c0 + C) of `rows` streams of the operand `s`, for channels whose producer
+    // is not a dense layer (block inputs, head features)
+    auto bn_stat = [&](hipStream_t cs, const ActSrc& s, int rows, int c0, int C, int count) {
         BnStatArgs a;
-        a.sum = sum; a.sq = sq; a.sstride = sstride; a.eps = kEps; a.inv_count = 1.0 / (double)count;
-        a.mean = const_cast<float*>(t.mean); a.invstd = const_cast<float*>(t.invstd); a.ld = t.ld; a.c0 = c0; a.C = C; a.rows = rows;
+        a.sum = s.sum; a.sq = s.sq; a.sstride = s.sstride; a.eps = s.eps; a.inv_count = 1.0 / (double)count;
+        a.mean = s.tw_mean; a.invstd = s.tw_invstd; a.ld = s.tab.ld; a.c0 = c0; a.C = C; a.rows = rows;
         launch_kernel(e, bn_stat_kernel, dim3((rows * C + 255) / 256), dim3(256), 0, cs, K_OTHER, 0, 0, false, a);
     };
     // Units [u_lo, u_hi) of the chain: unit 0 = input preparation + stem + pool0, then one unit per dense layer and per
@@ -107,7 +107,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
         int unit = 0;
         auto on = [&]() { const bool r = unit >= u_lo && unit < u_hi; ++unit; return r; };
         auto xs = [&](int b) { return el(e, e->X[b], (int64_t)s0 * e->p_blk[b].HWp * kBlockCtot[b]); };
-        auto st_off = [&](double* base, int stride) { return base + (int64_t)s0 * stride; };
+        auto st_off = [&](double* base, int stride) { return base + (int64_t)s0 * stride; };      // (the sums a launch WRITES; what it reads: act_src_fwd)
         const bool stem1 = B->heightmaps_dev != nullptr;                      // heightmap form: the three channels are identical by construction
         float* img4 = stem1 ? e->img4 + (int64_t)s0 * e->p_img.HWp : e->img4 + (int64_t)s0 * e->p_img.HWp * 4;
         float* stem = e->stem + (int64_t)s0 * e->p_stem.HWp * 64;
@@ -126,7 +126,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                 using Cfg = decltype(tag);
                 constexpr int SM = decltype(mtag)::value;          // F_STEM (3-channel image) or F_STEM1 (one channel, 49 taps)
                 FwdConvP<Cfg, SM, decltype(ptag)::value> p{};
-                p.src = img4; p.lds_ = 4; p.ps = e->p_img; p.po = e->p_stem; p.K = 0;
+                p.act.x = img4; p.act.ldx = 4; p.ps = e->p_img; p.po = e->p_stem; p.K = 0;
                 p.wp = e->packed_u + (SM == F_STEM1 ? e->pk_conv0_1 : e->pk_conv0); p.K8tot = (SM == F_STEM1 ? 64 : 224) / 8; p.N = 64;
                 p.dst = stem; p.ldd = 64; p.dcoff = 0;
                 p.dsum = st_off(fsum(e, e->st_stem), 64); p.dsq = st_off(fsq(e, e->st_stem), 64); p.dstride = 64;
@@ -138,8 +138,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
         }
         if (head_unit) {   // norm0 + relu0 + pool0
             Pool0Args a;
-            a.stem = stem; a.ps = e->p_stem; a.ssum = st_off(fsum(e, e->st_stem), 64); a.ssq = st_off(fsq(e, e->st_stem), 64);
-            a.gamma = P + T.norm0.w; a.beta = P + T.norm0.b; a.eps = kEps;
+            a.stem = act_src_fwd(e, stem, 64, e->st_stem, s0, P + T.norm0.w, P + T.norm0.b); a.ps = e->p_stem;
             a.x1 = xs(0); a.ldx = kBlockCtot[0]; a.po = e->p_blk[0];
             a.dsum = st_off(fsum(e, e->st_X[0]), kBlockCtot[0]); a.dsq = st_off(fsq(e, e->st_X[0]), kBlockCtot[0]); a.dstride = kBlockCtot[0];
             a.argmax = e->argmax + (int64_t)s0 * e->p_blk[0].HWp * 64;
@@ -159,15 +158,15 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                 float* bt = el(e, e->Bt, e->bt_off[b][i] + (int64_t)s0 * pl.HWp * kBottleneck);
                 double* bsum = st_off(fsum(e, e->st_Bt[b][i]), kBottleneck); double* bsq = st_off(fsq(e, e->st_Bt[b][i]), kBottleneck);
                 {   // norm1 + relu + conv1 (1x1, cin -> 128)
-                    const BnTab t1 = bn_table(e, e->sx_tab[b], e->max_streams, s0, Ct, P + d.n1.w, P + d.n1.b);
-                    if (i == 0) bn_stat(cs, t1, ns, xsum, xsq, Ct, 0, d.cin, pl.HW);     // block input: from pool0 / the transition
+                    // the layer's input through norm1: the 32 channels the layer below appended are fresh (the block's first layer: none, bn_stat)
+                    const ActSrc n1 = act_src_fwd(e, xs(b), Ct, e->st_X[b], s0, P + d.n1.w, P + d.n1.b, stat_table(e, e->sx_tab[b], e->max_streams, Ct),
+                                                  i == 0 ? d.cin : d.cin - kGrowth, asc_n1(e, b, (int)i));
+                    if (i == 0) bn_stat(cs, n1, ns, 0, d.cin, pl.HW);     // block input: from pool0 / the transition
                     auto run_p = [&](auto tag, auto ptag) {
                         using Cfg0 = decltype(tag);
                         using Cfg = MC<Cfg0, decltype(ptag)::value, (Cfg0::BK < 32 ? 2 : 1)>;      // (cin is a multiple of 32 only)
                         FwdConvP<Cfg, F_ONE, decltype(ptag)::value> p{};
-                        p.src = xs(b); p.lds_ = Ct; p.ps = pl; p.po = pl; p.K = d.cin; p.asc = asc_n1(e, b, (int)i);
-                        p.bt = t1; p.fresh0 = i == 0 ? d.cin : d.cin - kGrowth; p.fsum = xsum; p.fsq = xsq; p.fstride = Ct; p.eps = kEps;
-                        p.tw_mean = const_cast<float*>(t1.mean); p.tw_invstd = const_cast<float*>(t1.invstd);
+                        p.act = n1; p.ps = pl; p.po = pl; p.K = d.cin;
                         p.wp = e->packed_u + e->pk_c1[b][i]; p.K8tot = d.cin / 8; p.N = kBottleneck;
                         p.dst = bt; p.ldd = kBottleneck; p.dcoff = 0;
                         p.dsum = bsum; p.dsq = bsq; p.dstride = kBottleneck;
@@ -183,10 +182,8 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                     if (!e->generic_c1 && e->prec == 0 && !(pl.HWp % 128 == 0 && wg128 >= small_wgs) && wg64 >= small_wgs && d.cin % 32 == 0 && pl.HWp % 64 == 0) {
                         // wave-specialised 64 x 128 x 32 (ws.cuh)
                         Fwd1x1WsArgs a{};
-                        a.src = xs(b); a.lds_ = Ct; a.pl = pl; a.K = d.cin;
-                        a.bt = t1; a.fresh0 = i == 0 ? d.cin : d.cin - kGrowth; a.fsum = xsum; a.fsq = xsq; a.fstride = Ct; a.eps = kEps;
-                        a.tw_mean = const_cast<float*>(t1.mean); a.tw_invstd = const_cast<float*>(t1.invstd);
-                        a.wp = e->packed_u + e->pk_c1[b][i]; a.N = kBottleneck; a.asc = asc_n1(e, b, (int)i);
+                        a.act = n1; a.pl = pl; a.K = d.cin;
+                        a.wp = e->packed_u + e->pk_c1[b][i]; a.N = kBottleneck;
                         a.dst = bt; a.ldd = kBottleneck; a.dsum = bsum; a.dsq = bsq; a.dstride = kBottleneck;
                         using WG_ = WsGeoT<np_of(fwd_op(0))>;                // one workgroup per 64-row tile covers all 128 output columns
                         const int nM = ns * pl.HWp / 64, nN = kBottleneck / WG_::BN;
@@ -198,17 +195,17 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                     else if (wg64 < small_wgs) run(CfgP32x64{});
                     else run(CfgP64x64{});
                 }
-                const BnTab t2 = bn_table(e, e->sb_tab[b][i], e->max_streams, s0, kBottleneck, P + d.n2.w, P + d.n2.b);
-                if (e->generic3x3) bn_stat(cs, t2, ns, bsum, bsq, kBottleneck, 0, kBottleneck, pl.HW);
+                // the bottleneck through norm2: the halo kernel derives every channel itself, the generic one reads the table bn_stat fills
+                const ActSrc n2 = act_src_fwd(e, bt, kBottleneck, e->st_Bt[b][i], s0, P + d.n2.w, P + d.n2.b, stat_table(e, e->sb_tab[b][i], e->max_streams, kBottleneck),
+                                              e->generic3x3 ? kBottleneck : 0, asc_n2(e, b, (int)i));
+                if (e->generic3x3) bn_stat(cs, n2, ns, 0, kBottleneck, pl.HW);
                 if (!e->generic3x3) {
                     // norm2 + relu + conv2 (3x3, 128 -> 32) with an LDS-resident input halo (halo.cuh)
                     Halo3x3FwdArgs a;
-                    a.src = bt; a.lds_ = kBottleneck; a.pl = pl; a.C = kBottleneck;
-                    a.ssum = bsum; a.ssq = bsq; a.sstride = kBottleneck; a.gamma = P + d.n2.w; a.beta = P + d.n2.b; a.eps = kEps;
-                    a.tw_mean = const_cast<float*>(t2.mean); a.tw_invstd = const_cast<float*>(t2.invstd);
+                    a.act = n2; a.pl = pl; a.C = kBottleneck;
                     a.dst = xs(b); a.ldd = Ct; a.dcoff = d.cin;
                     a.dsum = xsum; a.dsq = xsq; a.dstride = Ct;
-                    a.wu = e->packed_u + e->pk_hf[b][i]; a.asc = asc_n2(e, b, (int)i);
+                    a.wu = e->packed_u + e->pk_hf[b][i];
                     const double flops = 2.0 * ns * pl.HW * 9 * kBottleneck * kGrowth, bytes = ESZ(e) * ns * pl.HW * (kBottleneck + kGrowth);
                     if (halo_tile(pl, ns) == 8) {      // (traced launches, as the 16 x 16 ones: dev stamps with SMG_TRACE_KIND=2)
                         // small planes: the wave-specialised form (halo.cuh; 17.1 -> 15.2 us per launch.  At TS = 16 it measures
@@ -231,9 +228,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                     auto run = [&](auto tag) {
                         using Cfg = decltype(tag);
                         FwdConvP<Cfg, F_THREE> p{};
-                        p.src = bt; p.lds_ = kBottleneck; p.ps = pl; p.po = pl; p.K = kBottleneck; p.asc = asc_n2(e, b, (int)i);
-                        p.bt = t2; p.fresh0 = kBottleneck; p.fsum = bsum; p.fsq = bsq; p.fstride = kBottleneck; p.eps = kEps;
-                        p.tw_mean = const_cast<float*>(t2.mean); p.tw_invstd = const_cast<float*>(t2.invstd);
+                        p.act = n2; p.ps = pl; p.po = pl; p.K = kBottleneck;
                         p.wp = e->packed_u + e->pk_g3f[b][i]; p.K8tot = 9 * kBottleneck / 8; p.N = kGrowth;
                         p.dst = xs(b); p.ldd = Ct; p.dcoff = d.cin;
                         p.dsum = xsum; p.dsq = xsq; p.dstride = Ct;
@@ -245,20 +240,19 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                 if (b == 3 && i + 1 == T.layers[b].size()) {
                     // the last layer's 32 channels have no dense-layer or transition consumer to finish their table entries (norm5 reads
                     // the sums); the backward reads the table (backward.hip: use_tabs), so finish them here
-                    const BnTab t5 = bn_table(e, e->sx_tab[b], e->max_streams, s0, Ct, nullptr, nullptr);
-                    bn_stat(cs, t5, ns, xsum, xsq, Ct, Ct - kGrowth, kGrowth, pl.HW);
+                    const ActSrc t5 = act_src_fwd(e, nullptr, Ct, e->st_X[b], s0, nullptr, nullptr, stat_table(e, e->sx_tab[b], e->max_streams, Ct));
+                    bn_stat(cs, t5, ns, Ct - kGrowth, kGrowth, pl.HW);
                 }
             }
             if (b < 3 && on()) {   // transition: norm + relu + (avgpool2 commuted in front of) conv 1x1
                 const Plane pn = e->p_blk[b + 1];
                 const int Cn = kBlockCtot[b + 1];
-                const BnTab tt = bn_table(e, e->sx_tab[b], e->max_streams, s0, Ct, P + T.tnorm[b].w, P + T.tnorm[b].b);
+                const ActSrc tt = act_src_fwd(e, xs(b), Ct, e->st_X[b], s0, P + T.tnorm[b].w, P + T.tnorm[b].b, stat_table(e, e->sx_tab[b], e->max_streams, Ct),
+                                              Ct - kGrowth, asc_trans(e, b));      // fresh: the block's last layer
                 auto run = [&](auto tag, auto ptag) {
                     using Cfg = MC<decltype(tag), decltype(ptag)::value>;
                     FwdConvP<Cfg, F_POOL, decltype(ptag)::value> p{};
-                    p.src = xs(b); p.lds_ = Ct; p.ps = pl; p.po = pn; p.K = Ct; p.asc = asc_trans(e, b);
-                    p.bt = tt; p.fresh0 = Ct - kGrowth; p.fsum = xsum; p.fsq = xsq; p.fstride = Ct; p.eps = kEps;     // the block's last layer
-                    p.tw_mean = const_cast<float*>(tt.mean); p.tw_invstd = const_cast<float*>(tt.invstd);
+                    p.act = tt; p.ps = pl; p.po = pn; p.K = Ct;
                     p.wp = e->packed_u + e->pk_t[b]; p.K8tot = Ct / 8; p.N = Ct / 2;
                     p.dst = xs(b + 1); p.ldd = Cn; p.dcoff = 0;
                     p.dsum = st_off(fsum(e, e->st_X[b + 1]), Cn); p.dsq = st_off(fsq(e, e->st_X[b + 1]), Cn); p.dstride = Cn;
@@ -293,21 +287,19 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
     const Plane p4 = e->p_blk[3];
     {   // norm5 + two-stream concat
         FeatArgs a;
-        a.x4 = e->X[3]; a.p4 = p4; a.xsum = fsum(e, e->st_X[3]); a.xsq = fsq(e, e->st_X[3]);
-        a.gamma = P + T.norm5.w; a.beta = P + T.norm5.b; a.eps = kEps;
+        a.x4 = norm5_src(e, T, P); a.p4 = p4;
         a.pair_a = e->d_pair_a; a.pair_b = e->d_pair_b; a.F = e->F;
         a.fsum = fsum(e, e->st_F); a.fsq = fsq(e, e->st_F); a.chunk = 64;
         PREC_DISPATCH(e, launch_kernel(e, feat_kernel<PREC>, dim3(2, NP, (p4.HW + 63) / 64), dim3(256), 0, st, K_OTHER, 0, 0, false, a));
     }
     {   // head norm0 + relu + conv0 (1x1, 2048 -> 64)
-        const BnTab th = bn_table(e, e->sf_tab, e->max_pairs, 0, 2 * kFeat, P + Hd.n0.w, P + Hd.n0.b);
-        bn_stat(st, th, NP, fsum(e, e->st_F), fsq(e, e->st_F), 2 * kFeat, 0, 2 * kFeat, p4.HW);
+        const ActSrc th = act_src_fwd(e, e->F, 2 * kFeat, e->st_F, 0, P + Hd.n0.w, P + Hd.n0.b, stat_table(e, e->sf_tab, e->max_pairs, 2 * kFeat),
+                                      2 * kFeat, asc_head0(e));
+        bn_stat(st, th, NP, 0, 2 * kFeat, p4.HW);
         auto run = [&](auto tag, auto ptag) {
                 using Cfg = decltype(tag);
                 FwdConvP<Cfg, F_ONE, decltype(ptag)::value, true> p{};      // fp32 feature buffers in every mode
-        p.src = e->F; p.lds_ = 2 * kFeat; p.ps = p4; p.po = p4; p.K = 2 * kFeat; p.asc = asc_head0(e);
-        p.bt = th; p.fresh0 = 2 * kFeat; p.fsum = fsum(e, e->st_F); p.fsq = fsq(e, e->st_F); p.fstride = 2 * kFeat; p.eps = kEps;
-        p.tw_mean = const_cast<float*>(th.mean); p.tw_invstd = const_cast<float*>(th.invstd);
+        p.act = th; p.ps = p4; p.po = p4; p.K = 2 * kFeat;
         p.wp = e->packed_u + e->pk_head0; p.K8tot = 2 * kFeat / 8; p.N = kHeadMid;
         p.dst = e->H1; p.ldd = kHeadMid; p.dcoff = 0;
         p.dsum = fsum(e, e->st_H1); p.dsq = fsq(e, e->st_H1); p.dstride = kHeadMid;
@@ -317,8 +309,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
     }
     {   // head norm1 + relu + conv1 (20x20 valid)
         ValueArgs a;
-        a.h1 = e->H1; a.p4 = p4; a.hsum = fsum(e, e->st_H1); a.hsq = fsq(e, e->st_H1);
-        a.gamma = P + Hd.n1.w; a.beta = P + Hd.n1.b; a.eps = kEps;
+        a.h1 = head_norm1_src(e, Hd, P); a.p4 = p4;
         a.w2p = e->packed_f + e->pk_head1; a.q = q_out; a.out_ch = e->head_out; a.OH = e->OH; a.OW = e->OW;
         launch_kernel(e, value_conv_kernel, dim3(NP * e->head_out * e->OH * e->OW), dim3(256), 0, st, K_OTHER, 0, 0, false, a);
     }

@@ -42,7 +42,7 @@
 // its own: the producer's epilogue accumulates per-(stream, channel) sum / sum of
 // squares in fp64 (in-lane, then fp64 atomics); the first consumer of a channel turns them into
 // fp32 (mean, invstd) table entries - every workgroup for itself, one per stream for the table
-// (BnTab) - and every later consumer's staging threads read the table per k-tile and apply
+// (ActSrc) - and every later consumer's staging threads read the table per k-tile and apply
 // BN + ReLU in the centered form (x - mean)*(gamma*invstd) + beta while staging the operand:
 // a forward workgroup's parameter prologue is 32 channels, whatever K is.
 #pragma once
@@ -478,13 +478,91 @@ __device__ __forceinline__ float4 mul4(float4 v, float s) {      // two elements
     return make_float4(a.x, a.y, b.x, b.y);
 }
 
-// BatchNorm statistics of one activation buffer as fp32, finished ONCE per (stream, channel): mean | invstd tables of
-// [rows][ld] (rows = streams or pairs), plus the affine parameters of the consuming BN layer.  Who writes them: the first
-// consumer of a channel - every workgroup of that launch derives the (few) channels nobody has finished yet from the
-// fp64 sums itself, and one designated workgroup per stream stores them for all later layers and for the backward.
-struct BnTab { const float* mean; const float* invstd; int ld; const float* gamma; const float* beta; };
-__device__ __forceinline__ const float* tab_mean(const BnTab& t, int n) { return t.mean + (int64_t)n * t.ld; }
-__device__ __forceinline__ const float* tab_invstd(const BnTab& t, int n) { return t.invstd + (int64_t)n * t.ld; }
+// An activation operand that a BatchNorm + ReLU turns into a convolution's input (forward), recomputes as such (weight gradients)
+// or reads as the ReLU mask and xhat source (data gradients).  THE descriptor of that operand - the forward and backward GEMMs, the
+// wave-specialised and 3x3 halo kernels and the element-wise kernels all take it, and the host builds it in one place (engine.h:
+// act_src).  Every pointer is at the operand's first channel; sstride = doubles per stream of the forward statistic arena.
+// Element sizes are the reader's business.
+// The fp32 table holds BatchNorm statistics finished ONCE per (stream, channel): mean | invstd of [rows][ld] (rows = streams or
+// pairs).  Who writes them: the first consumer of a channel - every workgroup of that launch derives the (few) channels nobody has
+// finished yet (fresh0 on) from the fp64 sums itself, and one designated workgroup per stream stores them through the writable
+// view for all later layers and for the backward.
+struct ActSrc {
+    const float* asc;               // operand kind 3: {s, 1 / s} of the BN + ReLU operand (scale_kernel), or nullptr
+    const double* sum; const double* sq; int sstride;
+    StatTab tab;                    // fp32 (mean, invstd) table of the same activation, or none: the fp64 sums
+    float* tw_mean; float* tw_invstd; int fresh0;      // forward: the table again, writable, and the first channel without an entry yet
+    const float* gamma; const float* beta;             // the BN's affine pair; nullptr where a site reads none (act_src_coef's AFF)
+    float eps;
+    // last, and the plane first behind the descriptor in every argument block: the storage, its leading dimension and the plane are what
+    // a kernel needs in front of its first loads, and the compiler fetches kernel arguments in runs of adjacent words - apart, they
+    // cost the 3x3 forward one more round trip of scalar loads before its halo loads go out
+    const void* x; int ldx;         // raw activation storage
+};
+// (mean, invstd) and the affine pair of channel ch of stream n; inv = 1 / pixels per plane.
+// FROM: where (mean, invstd) come from - the table if the descriptor has one (A_ANY: the backward GEMMs), the fp64 sums (A_SUMS: a
+// channel without a table entry yet, and the kernels that never get a table), the table for sure (A_TAB).
+// AFF: which of the affine pair the site has - bit 0 gamma, bit 1 beta; the other reads as 1 / 0.
+// Both are compile-time choices: every site knows, and a run-time test costs every prologue branches and a round trip of scalar
+// loads in front of its wait (measured on the forward sweep: +0.07 ms of 4.4).
+enum { A_ANY = 0, A_SUMS = 1, A_TAB = 2 };
+struct ActCoef { float mean, invstd, gamma, beta; };
+template <int FROM = A_ANY, int AFF = 3>
+__device__ __forceinline__ ActCoef act_src_coef(const ActSrc& s, int n, int ch, double inv) {
+    ActCoef f;
+    if constexpr (FROM == A_SUMS) bn_moments(s.sum, s.sq, (int64_t)n * s.sstride + ch, inv, s.eps, f.mean, f.invstd);
+    else if constexpr (FROM == A_TAB) { f.mean = s.tab.mean[(int64_t)n * s.tab.ld + ch]; f.invstd = s.tab.invstd[(int64_t)n * s.tab.ld + ch]; }
+    else tab_or_moments(s.tab, n, ch, s.sum, s.sq, (int64_t)n * s.sstride + ch, inv, s.eps, f.mean, f.invstd);
+    f.gamma = (AFF & 1) ? s.gamma[ch] : 1.f;
+    f.beta = (AFF & 2) ? s.beta[ch] : 0.f;
+    return f;
+}
+// The two shapes of an LDS parameter block, one channel at p, the fields `stride` floats apart:
+//   recomputed operand   mean | gamma * invstd * sa | beta * sa          (sa: the activation scale of operand kind 3, else 1)
+//   mask operand         gamma * invstd | beta | mean | invstd (| gamma)
+__device__ __forceinline__ void act_prm_store(float* p, int stride, const ActCoef& f, float sa) {
+    p[0] = f.mean;
+    p[stride] = f.gamma * f.invstd * sa;
+    p[2 * stride] = f.beta * sa;
+}
+template <bool GAMMA = false>
+__device__ __forceinline__ void act_mask_store(float* p, int stride, const ActCoef& f) {
+    p[0] = f.gamma * f.invstd;
+    p[stride] = f.beta;
+    p[2 * stride] = f.mean;
+    p[3 * stride] = f.invstd;
+    if constexpr (GAMMA) p[4 * stride] = f.gamma;
+}
+// Forward prologue of the 1x1 / transition / generic 3x3 kernels: the recomputed block of channels [0, K) of stream n -> sp, by all
+// THREADS threads of the workgroup.  Channels below fresh0 come from the table, four per thread; the fresh ones (the growth rate's
+// 32 at most) from the fp64 sums, and the workgroup with `store` set (one per stream) enters them into the table.
+constexpr int kFresh = 32;
+template <int THREADS>
+__device__ __forceinline__ void act_params_fwd(const ActSrc& s, int n, int K, double inv, float sa, bool store, float* sp) {
+    const int t = threadIdx.x;
+    const int64_t row = (int64_t)n * s.tab.ld;
+    for (int ch = 4 * t; ch < K && ch < s.fresh0; ch += 4 * THREADS) {
+        const f32x4 m = ldv4(s.tab.mean + row + ch), iv = ldv4(s.tab.invstd + row + ch), g = ldv4(s.gamma + ch), be = ldv4(s.beta + ch);
+        *reinterpret_cast<f32x4*>(sp + ch) = m;
+        *reinterpret_cast<f32x4*>(sp + K + ch) = g * iv * sa;
+        *reinterpret_cast<f32x4*>(sp + 2 * K + ch) = be * sa;
+    }
+    if (s.fresh0 < K && t < kFresh) {
+        const int ch = s.fresh0 + t;
+        const ActCoef f = act_src_coef<A_SUMS>(s, n, ch, inv);
+        act_prm_store(sp + ch, K, f, sa);
+        if (store) { s.tw_mean[row + ch] = f.mean; s.tw_invstd[row + ch] = f.invstd; }
+    }
+}
+// Weight-gradient prologue: the recomputed block of columns [n0, n0 + BN) of stream n -> bp, zeros past NB
+template <int BN, int THREADS, int FROM = A_ANY>
+__device__ __forceinline__ void act_params_cols(const ActSrc& s, int n, int n0, int NB, double inv, float sa, float* bp) {
+    for (int j = threadIdx.x; j < BN; j += THREADS) {
+        const int ch = n0 + j;
+        if (ch < NB) act_prm_store(bp + j, BN, act_src_coef<FROM>(s, n, ch, inv), sa);
+        else bp[j] = bp[BN + j] = bp[2 * BN + j] = 0.f;
+    }
+}
 
 // BN + ReLU in the centered form (x - mean) * (gamma * invstd) + beta: no cancellation
 // between x*scale and a pre-folded shift on near-constant channels.
@@ -1196,14 +1274,11 @@ struct FwdConvP {
     static constexpr int kOp = (MODE == 3 || MODE == 4) ? fwd_op_plain(PREC) : fwd_op(PREC), kAE = 16 / SrcT::size, kBE = 4, ESZ = SrcT::size;
     static constexpr bool kARawCopy = false, kAUnit = false;
     static constexpr bool kH = kOp == 2 || kOp == 3;      // the BN + ReLU operand becomes fp16: clamped to fp16's range (bnrelu4)
-    const float* asc;               // operand kind 3: {s, 1 / s} of the BN + ReLU operand (scale_kernel)
-    const void* src; int lds_;
+    // the input and the BN in front of this conv (the stem: the image, x / ldx alone).  Channels [fresh0, K) have no table entry yet
+    // (the 32 a dense layer appended last): derived here from the fp64 sums
+    ActSrc act;
     Plane ps, po;
     int K;
-    BnTab bt;                       // statistics + affine parameters of the BN in front of this conv
-    // channels [fresh0, K) have no table entry yet (the 32 a dense layer appended last): derived here from the fp64 sums
-    int fresh0; const double* fsum; const double* fsq; int fstride; float eps;
-    float* tw_mean; float* tw_invstd;       // the table again, writable (designated workgroups store the fresh channels)
     const u32x4* wp; int K8tot;     // packed weight units [piece][K8tot][N] (pack_weights_kernel)
     int N;
     void* dst; int ldd; int dcoff;
@@ -1218,7 +1293,6 @@ struct FwdConvP {
     static constexpr bool kStem = MODE == F_STEM || MODE == F_STEM1;
     static constexpr bool kHasPrologue = !kStem;
     static constexpr bool kEarlyFetch = false;
-    static constexpr int kFresh = 32;       // growth rate: at most this many fresh channels
     // waves per SIMD the register allocator is held to: the 128x128 tile (64 accumulator registers) must stay at 3
     static constexpr int kMinWaves = (Cfg::TM * Cfg::TN == 4 && MODE != F_POOL) ? kFwdBigMinWaves : 1;    // (the pooling fetch holds 4 float4 per row)
 
@@ -1239,35 +1313,14 @@ struct FwdConvP {
         return c.m0 - c.n * po.HWp < po.HW;
     }
     // BN parameters of this stream's K channels -> LDS, once per workgroup: (mean, gamma*invstd, beta) from the fp32 tables;
-    // the fresh channels (the last kFresh) from the fp64 sums, and the first tile of every stream stores those in the table.
+    // the fresh channels (the growth rate's 32 at most) from the fp64 sums, and the first tile of every stream stores those in the
+    // table (act_params_fwd, the one body this prologue shares with the wave-specialised kernel).
     // The staging threads then read their channel quad's parameters from LDS per k-tile (reading them from the tables per
     // k-tile was 16 KB of L1 traffic per workgroup and k-tile, twice the A operand).
     __device__ void init_params(const Ctx& c, float* sp) const {
-        if constexpr (!kStem) {
-            const int t = threadIdx.x;
-            const float* tmean = tab_mean(bt, c.n);
-            const float* tinv = tab_invstd(bt, c.n);
-            // operand kind 3: relu(s * t) = s * relu(t) - the activation scale is folded into gamma * invstd and beta (no VALU in the k-loop)
-            const float sa = kOp == 3 ? asc[0] : 1.f;
-            for (int ch = 4 * t; ch < K && ch < fresh0; ch += 1024) {
-                const f32x4 m = ldv4(tmean + ch), iv = ldv4(tinv + ch), g = ldv4(bt.gamma + ch), be = ldv4(bt.beta + ch);
-                *reinterpret_cast<f32x4*>(sp + ch) = m;
-                *reinterpret_cast<f32x4*>(sp + K + ch) = g * iv * sa;
-                *reinterpret_cast<f32x4*>(sp + 2 * K + ch) = be * sa;
-            }
-            if (fresh0 < K && t < kFresh) {
-                const int ch = fresh0 + t;
-                float mean, invstd;
-                bn_moments(fsum, fsq, (int64_t)c.n * fstride + ch, 1.0 / (double)ps.HW, eps, mean, invstd);
-                sp[ch] = mean;
-                sp[K + ch] = bt.gamma[ch] * invstd * sa;
-                sp[2 * K + ch] = bt.beta[ch] * sa;
-                if (c.n0 == 0 && c.m0 == c.n * po.HWp) {
-                    tw_mean[(int64_t)c.n * bt.ld + ch] = mean;
-                    tw_invstd[(int64_t)c.n * bt.ld + ch] = invstd;
-                }
-            }
-        }
+        // operand kind 3: relu(s * t) = s * relu(t) - the activation scale is folded into gamma * invstd and beta (no VALU in the k-loop)
+        if constexpr (!kStem)
+            act_params_fwd<256>(act, c.n, K, 1.0 / (double)ps.HW, kOp == 3 ? act.asc[0] : 1.f, c.n0 == 0 && c.m0 == c.n * po.HWp, sp);
     }
     __device__ void d_init(const Ctx&, DRow&, int) const {}
     __device__ void d_next(const Ctx&, DRow&) const {}
@@ -1282,7 +1335,7 @@ struct FwdConvP {
         r.valid = p < po.HW;
         r.y = p / po.W;
         r.x = p - r.y * po.W;
-        r.off = (unsigned)ESZ * (unsigned)(p * lds_);    // byte offset of the row inside its stream
+        r.off = (unsigned)ESZ * (unsigned)(p * act.ldx);    // byte offset of the row inside its stream
     }
     struct RawTaps { float4 v[1]; bool ok; unsigned m; };      // F_STEM1: four gathered taps + which of them exist
     using ARaw = typename std::conditional<MODE == F_STEM1, RawTaps, RawT<(MODE == F_POOL) ? 4 : 1>>::type;
@@ -1322,23 +1375,23 @@ struct FwdConvP {
         if constexpr (MODE == F_ONE) {
             // rows of the plane padding are read as they are (they exist) and produce output rows nobody stores or sums
             o.ok = true;
-            o.v[0] = bload4(static_cast<const char*>(src) + (int64_t)ESZ * c.n * ps.HWp * lds_, kWholeBuf, r.off + 16u * (unsigned)q, (unsigned)ESZ * (unsigned)(kt * Cfg::BK));
+            o.v[0] = bload4(static_cast<const char*>(act.x) + (int64_t)ESZ * c.n * ps.HWp * act.ldx, kWholeBuf, r.off + 16u * (unsigned)q, (unsigned)ESZ * (unsigned)(kt * Cfg::BK));
         } else if constexpr (MODE == F_THREE) {
             const int tap = kt / (K / Cfg::BK);
             const int yy = r.y + tap / 3 - 1, xx = r.x + tap % 3 - 1;
             o.ok = r.valid && (unsigned)yy < (unsigned)ps.H && (unsigned)xx < (unsigned)ps.W;
-            o.v[0] = ld16(src, (int64_t)ESZ * (((int64_t)c.n * ps.HWp + (o.ok ? yy * ps.W + xx : 0)) * lds_ + a_slot_chan(kt, q)));
+            o.v[0] = ld16(act.x, (int64_t)ESZ * (((int64_t)c.n * ps.HWp + (o.ok ? yy * ps.W + xx : 0)) * act.ldx + a_slot_chan(kt, q)));
         } else if constexpr (MODE == F_POOL) {
             o.ok = r.valid;
-            const int64_t b = (int64_t)ESZ * (((int64_t)c.n * ps.HWp + (o.ok ? (2 * r.y) * ps.W + 2 * r.x : 0)) * lds_ + a_slot_chan(kt, q));
-            o.v[0] = ld16(src, b);
-            o.v[1] = ld16(src, b + (int64_t)ESZ * lds_);
-            o.v[2] = ld16(src, b + (int64_t)ESZ * ps.W * lds_);
-            o.v[3] = ld16(src, b + (int64_t)ESZ * (ps.W + 1) * lds_);
+            const int64_t b = (int64_t)ESZ * (((int64_t)c.n * ps.HWp + (o.ok ? (2 * r.y) * ps.W + 2 * r.x : 0)) * act.ldx + a_slot_chan(kt, q));
+            o.v[0] = ld16(act.x, b);
+            o.v[1] = ld16(act.x, b + (int64_t)ESZ * act.ldx);
+            o.v[2] = ld16(act.x, b + (int64_t)ESZ * ps.W * act.ldx);
+            o.v[3] = ld16(act.x, b + (int64_t)ESZ * (ps.W + 1) * act.ldx);
         } else if constexpr (MODE == F_STEM1) {
             // slot q of the k-tile = taps 4 q' .. 4 q' + 3 of the 7x7 window: four unconditional scalar loads from clamped
             // addresses of the one-channel plane; which taps exist (inside the window and the image) travels as a bit mask
-            const float* img = static_cast<const float*>(src) + (int64_t)c.n * ps.HWp;
+            const float* img = static_cast<const float*>(act.x) + (int64_t)c.n * ps.HWp;
             float tv[4];
             o.ok = true; o.m = 0u;
 #pragma unroll
@@ -1354,7 +1407,7 @@ struct FwdConvP {
             const int tap = kt * (Cfg::BK / 4) + q;
             const int yy = 2 * r.y + tap / 7 - 3, xx = 2 * r.x + tap % 7 - 3;
             o.ok = r.valid && tap < 49 && (unsigned)yy < (unsigned)ps.H && (unsigned)xx < (unsigned)ps.W;
-            o.v[0] = ld16(src, 16 * ((int64_t)c.n * ps.HWp + (o.ok ? yy * ps.W + xx : 0)));
+            o.v[0] = ld16(act.x, 16 * ((int64_t)c.n * ps.HWp + (o.ok ? yy * ps.W + xx : 0)));
         }
         return o;
     }
@@ -1393,7 +1446,7 @@ struct FwdConvP {
 #pragma unroll
         for (int j = 0; j < Cfg::TN; ++j) v[0][j] = v[1][j] = 0.0;
         if constexpr (kOp == 3) {          // the products were formed on scaled operands: exact power-of-two correction
-            const float inv = asc[1] * pack_inv_scale(wp);
+            const float inv = act.asc[1] * pack_inv_scale(wp);
 #pragma unroll
             for (int i = 0; i < Cfg::TM; ++i)
 #pragma unroll
@@ -1508,7 +1561,7 @@ struct BwdDataP {
     using Cfg = Cfg_;
     static_assert(Cfg::AT, "data-gradient form");
     using GT = typename std::conditional<F32IO, e_f32, grd_t<PREC>>::type;      // gradients in (gs.g) and out (dst)
-    using XT = typename std::conditional<F32IO, e_f32, act_t<PREC>>::type;      // activations (gs.x, mbuf)
+    using XT = typename std::conditional<F32IO, e_f32, act_t<PREC>>::type;      // activations (gs.x, m.x)
     static_assert(GT::size == XT::size, "one slot geometry for the gradient and its activation");
     // operand kind 3 needs the gradient operand's recorded maximum: the pointwise form on a FINISHED gradient only
     static constexpr int kOp = (AFF || SHIFT3) ? bwd_op_plain(PREC) : bwd_op(PREC), kAE = 16 / GT::size, kBE = 4, GSZ = GT::size, XSZ = XT::size;
@@ -1520,13 +1573,10 @@ struct BwdDataP {
     int KA;
     const u32x4* wp; int K8tot; int ldn; int wcol0;    // packed weight units [piece][K8tot][ldn], first output column wcol0
     int N;
-    const void* mbuf; int ldm; int mcoff; Plane pm;
-    const double* msum; const double* msq; int mstride; StatTab mtab;
-    const float* egamma; const float* ebeta;
+    ActSrc m; Plane pm;             // the mask / xhat source: the activation whose BN + ReLU feeds this convolution's input, N channels
     void* dst; int ldd; int dcoff;
     double* o1; double* o2; int ostride; int ocoff;
     float* dbeta; float* dgamma; int rep_stride;      // rep_stride != 0: kDbRep replicas of a scratch (engine.h), this workgroup's = index mod 8
-    float eps;
     TileMap tm;
     static constexpr int kSwizzle = 1;
     static constexpr int kPrefetch = (Cfg::TM * Cfg::TN <= 2) ? kPdDgrad : kPdDgradBig;
@@ -1612,16 +1662,16 @@ struct BwdDataP {
                         for (int j = 0; j < Cfg::TN; ++j) {
                             if (c.n0 + wn0 + j * 32 + 32 > N) continue;      // (wave-uniform) tile outside [0, N): never read
                             // 16 / 8-byte loads, one per four accumulator rows (fetch_acc_rows, above GemmCfg); transposed in the epilogue
-                            const int64_t ax = (int64_t)(c.m0 + wm0 + i * 32) * ldm + mcoff + c.n0 + wn0 + j * 32;
+                            const int64_t ax = (int64_t)(c.m0 + wm0 + i * 32) * m.ldx + c.n0 + wn0 + j * 32;
                             const int64_t ag = (int64_t)(c.m0 + wm0 + i * 32) * ldd + dcoff + c.n0 + wn0 + j * 32;
     #pragma unroll
                             for (int g = 0; g < 4; ++g) {
-                                c.xq[i][j][g] = fetch_acc_rows<XT>(mbuf, ax, ldm, g, half, lane);
+                                c.xq[i][j][g] = fetch_acc_rows<XT>(m.x, ax, m.ldx, g, half, lane);
                                 if constexpr (EMODE == E_ACCUM) c.gq[i][j][g] = fetch_acc_rows<GT>(dst, ag, ldd, g, half, lane);
                             }
                         }
                 } else {
-                    const char* xb = static_cast<const char*>(mbuf) + (int64_t)XSZ * ((int64_t)c.m0 * ldm + mcoff + c.n0);
+                    const char* xb = static_cast<const char*>(m.x) + (int64_t)XSZ * ((int64_t)c.m0 * m.ldx + c.n0);
                     const char* gb = static_cast<const char*>(dst) + (int64_t)GSZ * ((int64_t)c.m0 * ldd + dcoff + c.n0);
     #pragma unroll
                     for (int i = 0; i < Cfg::TM; ++i)
@@ -1629,13 +1679,13 @@ struct BwdDataP {
                         for (int j = 0; j < Cfg::TN; ++j) {
                             if (c.n0 + wn0 + j * 32 + 32 > N) continue;      // (wave-uniform) tile outside [0, N): never read
                             const int cj = wn0 + j * 32 + l31;
-                            unsigned ox = (unsigned)((wm0 + i * 32 + 4 * half) * ldm + cj);
+                            unsigned ox = (unsigned)((wm0 + i * 32 + 4 * half) * m.ldx + cj);
                             unsigned og = (unsigned)((wm0 + i * 32 + 4 * half) * ldd + cj);
     #pragma unroll
                             for (int r = 0; r < 16; ++r) {
                                 c.xv[i][j][r] = ld1<XT>(xb, ox);
                                 if constexpr (EMODE == E_ACCUM) c.gold[i][j][r] = ld1<GT>(gb, og);
-                                ox += (r & 3) == 3 ? 5u * (unsigned)ldm : (unsigned)ldm;
+                                ox += (r & 3) == 3 ? 5u * (unsigned)m.ldx : (unsigned)m.ldx;
                                 og += (r & 3) == 3 ? 5u * (unsigned)ldd : (unsigned)ldd;
                             }
                         }
@@ -1656,17 +1706,9 @@ struct BwdDataP {
         const double minv = 1.0 / (double)pm.HW;
         for (int j = threadIdx.x; j < Cfg::BN; j += 256) {
             const int col = c.n0 + j;
-            float mean = 0.f, invstd = 0.f, g = 0.f, b = 0.f;
-            if (col < N) {
-                tab_or_moments(mtab, c.n, mcoff + col, msum, msq, (int64_t)c.n * mstride + mcoff + col, minv, eps, mean, invstd);
-                g = egamma[col];
-                b = ebeta[col];
-            }
-            ep[j] = g * invstd;
-            ep[Cfg::BN + j] = b;
-            ep[2 * Cfg::BN + j] = mean;
-            ep[3 * Cfg::BN + j] = invstd;
-            ep[4 * Cfg::BN + j] = g;
+            ActCoef f{0.f, 0.f, 0.f, 0.f};
+            if (col < N) f = act_src_coef(m, c.n, col, minv);
+            act_mask_store<true>(ep + j, Cfg::BN, f);
         }
     }
     __device__ int ktiles(const Ctx&) const { return (SHIFT3 ? 9 : 1) * (KA / Cfg::BK); }
@@ -1820,7 +1862,7 @@ struct BwdDataP {
                         const int64_t pix0 = (int64_t)c.n * pm.HWp + (2 * y) * pm.W + 2 * x;
                         float4 xq[4];
 #pragma unroll
-                        for (int d = 0; d < 4; ++d) xq[d] = ldq<XT>(mbuf, (pix0 + (d >> 1) * pm.W + (d & 1)) * ldm + mcoff + c.n0 + cq0);
+                        for (int d = 0; d < 4; ++d) xq[d] = ldq<XT>(m.x, (pix0 + (d >> 1) * pm.W + (d & 1)) * m.ldx + c.n0 + cq0);
                         float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                         for (int d = 0; d < 4; ++d) {
@@ -1865,10 +1907,10 @@ struct BwdDataP {
                             pix0[q] = c.n * pm.HWp + (2 * y) * pm.W + 2 * x;
 #pragma unroll
                             for (int d = 0; d < 4; ++d)
-                                xv[q][d] = ok[q] ? ld1<XT>(mbuf, (int64_t)(pix0[q] + (d >> 1) * pm.W + (d & 1)) * ldm + mcoff + col) : 0.f;
+                                xv[q][d] = ok[q] ? ld1<XT>(m.x, (int64_t)(pix0[q] + (d >> 1) * pm.W + (d & 1)) * m.ldx + col) : 0.f;
                         } else {
                             pix0[q] = c.m0 + row;
-                            xv[q][0] = ok[q] ? ld1<XT>(mbuf, (int64_t)pix0[q] * ldm + mcoff + col) : 0.f;
+                            xv[q][0] = ok[q] ? ld1<XT>(m.x, (int64_t)pix0[q] * m.ldx + col) : 0.f;
                             if constexpr (EMODE == E_ACCUM) gold[q] = ok[q] ? ld1<GT>(dst, (int64_t)pix0[q] * ldd + dcoff + col) : 0.f;
                         }
                     }
@@ -1959,12 +2001,10 @@ struct BwdDataGroupP {
     GroupSeg seg[GROUP_MAX]; int nseg;
     int ldg; Plane pa; int KA;
     int N;                                              // output channels [0, N)
-    const void* mbuf; int ldm;                          // block buffer X (mask / xhat source)
-    const double* msum; const double* msq; int mstride; StatTab mtab;
+    ActSrc m;                                           // block buffer X (mask / xhat source) and its statistics; gamma / beta live per segment
     void* dst; int ldd;                                 // G'
     double* o1; double* o2; int ostride;                // SA / SB [n][C]
     int rep_stride;                                     // replicas of the dbeta / dgamma scratch (see BwdDataP)
-    float eps;
     TileMap tm;
     static constexpr int kSwizzle = 1;
     // deep k-tiles with ONE tile of loads in flight (the staging registers of two half-as-deep tiles, half the barriers): mode 0
@@ -2020,7 +2060,7 @@ struct BwdDataGroupP {
         }
         for (int j = threadIdx.x; j < Cfg::BN; j += 256) {
             const int col = c.n0 + j;
-            float mean = 0.f, invstd = 0.f;
+            ActCoef f{0.f, 0.f, 0.f, 0.f};
             // every segment's gamma / beta first (one memory round trip; a loop that loads and stores per segment waits per load)
             float g[GROUP_MAX], be[GROUP_MAX];
 #pragma unroll
@@ -2029,13 +2069,13 @@ struct BwdDataGroupP {
                 g[s] = on ? seg[s].gamma[col] : 0.f;
                 be[s] = on ? seg[s].beta[col] : 0.f;
             }
-            if (col < N) tab_or_moments(mtab, c.n, col, msum, msq, (int64_t)c.n * mstride + col, minv, eps, mean, invstd);
-            sp[j] = mean;
-            sp[Cfg::BN + j] = invstd;
+            if (col < N) f = act_src_coef<A_ANY, 0>(m, c.n, col, minv);
+            sp[j] = f.mean;
+            sp[Cfg::BN + j] = f.invstd;
 #pragma unroll
             for (int s = 0; s < GROUP_MAX; ++s) {
                 float* q = sp + (2 + 3 * s) * Cfg::BN;
-                q[j] = g[s] * invstd;
+                q[j] = g[s] * f.invstd;
                 q[Cfg::BN + j] = be[s];
                 q[2 * Cfg::BN + j] = g[s];
             }
@@ -2075,11 +2115,11 @@ struct BwdDataGroupP {
                 for (int j = 0; j < Cfg::TN; ++j)
     #pragma unroll
                     for (int i = 0; i < Cfg::TM; ++i) {
-                        const int64_t ax = (int64_t)(c.m0 + wm0 + i * 32) * ldm + c.n0 + wn0 + j * 32;
+                        const int64_t ax = (int64_t)(c.m0 + wm0 + i * 32) * m.ldx + c.n0 + wn0 + j * 32;
                         const int64_t ag = (int64_t)(c.m0 + wm0 + i * 32) * ldd + c.n0 + wn0 + j * 32;
     #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            const rawq_t<XT> xr = fetch_acc_rows<XT>(mbuf, ax, ldm, g, half, lane);
+                            const rawq_t<XT> xr = fetch_acc_rows<XT>(m.x, ax, m.ldx, g, half, lane);
                             if constexpr (std::is_same<XT, e_f32>::value) { c.x[i][j][4 * g] = xr.x; c.x[i][j][4 * g + 1] = xr.y; c.x[i][j][4 * g + 2] = xr.z; c.x[i][j][4 * g + 3] = xr.w; }
                             else { c.x[i][j][4 * g] = __uint_as_float(xr.x); c.x[i][j][4 * g + 1] = __uint_as_float(xr.y); }
                             c.gq[i][j][g] = fetch_acc_rows<GT>(dst, ag, ldd, g, half, lane);
@@ -2096,7 +2136,7 @@ struct BwdDataGroupP {
                             const int row = SMG_ACC_ROW(wm0, i, r, half);
                             const bool ok = pbase + row < pa.HW && col < N;
                             // unconditional load from a clamped address (a branch around it would serialise the loads)
-                            const float v = ld1<XT>(mbuf, (int64_t)(c.m0 + (ok ? row : 0)) * ldm + (ok ? col : 0));
+                            const float v = ld1<XT>(m.x, (int64_t)(c.m0 + (ok ? row : 0)) * m.ldx + (ok ? col : 0));
                             c.x[i][j][r] = ok ? v : 0.f;
                         }
                 }
@@ -2107,19 +2147,19 @@ struct BwdDataGroupP {
             const int t = threadIdx.x, lane = t & 63, wmn = (t >> 6) % (Cfg::WM * Cfg::WN), l31 = lane & 31, half = lane >> 5;
             const int wm0 = (wmn / Cfg::WN) * Cfg::TM * 32, wn0 = (wmn % Cfg::WN) * Cfg::TN * 32;
             if (c.whole) {
-                const char* xb = static_cast<const char*>(mbuf) + (int64_t)XT::size * ((int64_t)c.m0 * ldm + c.n0);
+                const char* xb = static_cast<const char*>(m.x) + (int64_t)XT::size * ((int64_t)c.m0 * m.ldx + c.n0);
                 const char* gb = static_cast<const char*>(dst) + (int64_t)GSZ * ((int64_t)c.m0 * ldd + c.n0);
     #pragma unroll
                 for (int j = 0; j < Cfg::TN; ++j)
     #pragma unroll
                     for (int i = 0; i < Cfg::TM; ++i) {
-                        unsigned ox = (unsigned)((wm0 + i * 32 + 4 * half) * ldm + wn0 + j * 32 + l31);
+                        unsigned ox = (unsigned)((wm0 + i * 32 + 4 * half) * m.ldx + wn0 + j * 32 + l31);
                         unsigned og = (unsigned)((wm0 + i * 32 + 4 * half) * ldd + wn0 + j * 32 + l31);
     #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             c.x[i][j][r] = ld1<XT>(xb, ox);
                             c.gold[i][j][r] = ld1<GT>(gb, og);
-                            ox += (r & 3) == 3 ? 5u * (unsigned)ldm : (unsigned)ldm;
+                            ox += (r & 3) == 3 ? 5u * (unsigned)m.ldx : (unsigned)m.ldx;
                             og += (r & 3) == 3 ? 5u * (unsigned)ldd : (unsigned)ldd;
                             c.run[i][j][r] = 0.f;
                         }
@@ -2135,7 +2175,7 @@ struct BwdDataGroupP {
                             const int row = SMG_ACC_ROW(wm0, i, r, half);
                             const bool ok = pbase + row < pa.HW && col < N;
                             // unconditional load from a clamped address (a branch around it would serialise the loads)
-                            const float v = ld1<XT>(mbuf, (int64_t)(c.m0 + (ok ? row : 0)) * ldm + (ok ? col : 0));
+                            const float v = ld1<XT>(m.x, (int64_t)(c.m0 + (ok ? row : 0)) * m.ldx + (ok ? col : 0));
                             c.x[i][j][r] = ok ? v : 0.f;
                             c.run[i][j][r] = 0.f;
                             c.gold[i][j][r] = 0.f;
@@ -2355,7 +2395,7 @@ struct BwdWeightP {
     static_assert(!Cfg::AT, "weight-gradient form");
     static constexpr bool F32IO = F32IO_ || BMODE == 3 || BMODE == 4;      // W_STEM, W_STEM1
     using GT = typename std::conditional<F32IO, e_f32, grd_t<PREC>>::type;      // output gradient (gs.g)
-    using XT = typename std::conditional<F32IO, e_f32, act_t<PREC>>::type;      // activations (gs.x, bbuf)
+    using XT = typename std::conditional<F32IO, e_f32, act_t<PREC>>::type;      // activations (gs.x, bsrc.x)
     static_assert(GT::size == XT::size, "one slot geometry");
     // operand kind 3: the dense layers' 1x1 weight gradient (finished gradient with a recorded maximum x BN + ReLU activation)
     static constexpr int kOp = (!AFF && BMODE == 0) ? bwd_op(PREC) : bwd_op_plain(PREC), kAE = 16 / GT::size, kBE = 16 / XT::size, GSZ = GT::size, XSZ = XT::size;
@@ -2363,13 +2403,9 @@ struct BwdWeightP {
     static constexpr bool kAUnit = !AFF && BMODE == 0 && kOp == 3;      // the gradient operand arrives in unit form (kD2K8): gs.g = units
     static constexpr bool kH = kOp == 3;      // the BN + ReLU operand B becomes fp16 (the gradient side of modes 1 / 2 is bf16): clamped (bnrelu4)
     const float* binv;              // operand kind 3: [streams][HWp / 64] inverse block scales of gs.g (bn_bwd_apply_split_kernel)
-    const float* basc;              // operand kind 3: {s, 1 / s} of the BN + ReLU operand B (scale_kernel)
     GradSrc gs;                     // the gradient operand A (MA channels)
     Plane pa; int MA;
-    const void* bbuf; int ldb; Plane pb; int NB;
-    const double* bsum; const double* bsq; int bstride; StatTab btab;
-    const float* bgamma; const float* bbeta;
-    float eps;
+    ActSrc bsrc; Plane pb; int NB;     // the BN + ReLU operand B, recomputed from the raw activation (NB channels; the stem: the image, x / ldx alone)
     int chunk, chunks_per_stream, n_chunks;   // virtual block z = tap * n_chunks + chunk index
     float* dw; int ldw_out;
     float* part;                              // if set: partial tiles [z][gx*BM][gy*BN] (plain stores,
@@ -2471,21 +2507,8 @@ struct BwdWeightP {
             sp[3 * Cfg::BM + k] = f.k;
         }
         if constexpr (BMODE != W_STEM && BMODE != W_STEM1) {
-            float* bp = sp + 4 * Cfg::BM;
-            const double binv = 1.0 / (double)pb.HW;
-            for (int j = threadIdx.x; j < Cfg::BN; j += 256) {
-                const int ch = c.n0 + j;
-                float mean = 0.f, invstd = 0.f, sc = 0.f, be = 0.f;
-                if (ch < NB) {
-                    tab_or_moments(btab, c.n, ch, bsum, bsq, (int64_t)c.n * bstride + ch, binv, eps, mean, invstd);
-                    const float sa = kOp == 3 ? basc[0] : 1.f;      // the activation scale, folded into the BN + ReLU parameters
-                    sc = bgamma[ch] * invstd * sa;
-                    be = bbeta[ch] * sa;
-                }
-                bp[j] = mean;
-                bp[Cfg::BN + j] = sc;
-                bp[2 * Cfg::BN + j] = be;
-            }
+            // (operand kind 3: the activation scale, folded into the BN + ReLU parameters)
+            act_params_cols<Cfg::BN, 256>(bsrc, c.n, c.n0, NB, 1.0 / (double)pb.HW, kOp == 3 ? bsrc.asc[0] : 1.f, sp + 4 * Cfg::BM);
         }
         if constexpr (kAUnit) {
             const float* bi = binv + (int64_t)c.n * (pa.HWp / kScaleBlock) + c.p0 / kScaleBlock;
@@ -2544,20 +2567,20 @@ struct BwdWeightP {
             // bounded to the HW rows (zero past them: the A rows there are zero, this keeps the product finite); channel quads
             // past NB read the neighbouring channels of the row - their columns are never stored
             o.ok = true;
-            o.v[0] = bload4(static_cast<const char*>(bbuf) + (int64_t)XSZ * c.n * pb.HWp * ldb, (unsigned)XSZ * (unsigned)(pb.HW * ldb), (unsigned)XSZ * (unsigned)(kr * ldb + ch),
-                            (unsigned)XSZ * (unsigned)((c.p0 + kt * Cfg::BK) * ldb));
+            o.v[0] = bload4(static_cast<const char*>(bsrc.x) + (int64_t)XSZ * c.n * pb.HWp * bsrc.ldx, (unsigned)XSZ * (unsigned)(pb.HW * bsrc.ldx), (unsigned)XSZ * (unsigned)(kr * bsrc.ldx + ch),
+                            (unsigned)XSZ * (unsigned)((c.p0 + kt * Cfg::BK) * bsrc.ldx));
         } else if constexpr (BMODE == W_THREE) {
             const int yy = r.y + c.tap / 3 - 1, xx = r.x + c.tap % 3 - 1;
             o.ok = o.ok && (unsigned)yy < (unsigned)pb.H && (unsigned)xx < (unsigned)pb.W;
-            o.v[0] = ld16(bbuf, (int64_t)XSZ * (((int64_t)c.n * pb.HWp + (o.ok ? yy * pb.W + xx : 0)) * ldb + (o.ok ? ch : 0)));
+            o.v[0] = ld16(bsrc.x, (int64_t)XSZ * (((int64_t)c.n * pb.HWp + (o.ok ? yy * pb.W + xx : 0)) * bsrc.ldx + (o.ok ? ch : 0)));
         } else if constexpr (BMODE == W_POOL) {
-            const int64_t b = (int64_t)XSZ * (((int64_t)c.n * pb.HWp + (o.ok ? (2 * r.y) * pb.W + 2 * r.x : 0)) * ldb + (o.ok ? ch : 0));
-            o.v[0] = ld16(bbuf, b);
-            o.v[1] = ld16(bbuf, b + (int64_t)XSZ * ldb);
-            o.v[2] = ld16(bbuf, b + (int64_t)XSZ * pb.W * ldb);
-            o.v[3] = ld16(bbuf, b + (int64_t)XSZ * (pb.W + 1) * ldb);
+            const int64_t b = (int64_t)XSZ * (((int64_t)c.n * pb.HWp + (o.ok ? (2 * r.y) * pb.W + 2 * r.x : 0)) * bsrc.ldx + (o.ok ? ch : 0));
+            o.v[0] = ld16(bsrc.x, b);
+            o.v[1] = ld16(bsrc.x, b + (int64_t)XSZ * bsrc.ldx);
+            o.v[2] = ld16(bsrc.x, b + (int64_t)XSZ * pb.W * bsrc.ldx);
+            o.v[3] = ld16(bsrc.x, b + (int64_t)XSZ * (pb.W + 1) * bsrc.ldx);
         } else if constexpr (BMODE == W_STEM1) {
-            const float* img = static_cast<const float*>(bbuf) + (int64_t)c.n * pb.HWp;
+            const float* img = static_cast<const float*>(bsrc.x) + (int64_t)c.n * pb.HWp;
             float tv[4];
             const bool pin = r.p < pa.HW;
             o.ok = true; o.m = 0u;
@@ -2574,7 +2597,7 @@ struct BwdWeightP {
             const int tap = ch >> 2;
             const int yy = 2 * r.y + tap / 7 - 3, xx = 2 * r.x + tap % 7 - 3;
             o.ok = o.ok && tap < 49 && (unsigned)yy < (unsigned)pb.H && (unsigned)xx < (unsigned)pb.W;
-            o.v[0] = ld16(bbuf, 16 * ((int64_t)c.n * pb.HWp + (o.ok ? yy * pb.W + xx : 0)));
+            o.v[0] = ld16(bsrc.x, 16 * ((int64_t)c.n * pb.HWp + (o.ok ? yy * pb.W + xx : 0)));
         }
         return o;
     }
@@ -2612,7 +2635,7 @@ struct BwdWeightP {
         const int t = threadIdx.x, lane = t & 63, wmn = (t >> 6) % (Cfg::WM * Cfg::WN), l31 = lane & 31, half = lane >> 5;
         const int wm0 = (wmn / Cfg::WN) * Cfg::TM * 32, wn0 = (wmn % Cfg::WN) * Cfg::TN * 32;
         if constexpr (kOp == 3) {          // products of scaled operands: exact power-of-two correction (the last block's scale x the activation scale)
-            const float gi = c.cur_inv * basc[1];
+            const float gi = c.cur_inv * bsrc.asc[1];
 #pragma unroll
             for (int i = 0; i < Cfg::TM; ++i)
 #pragma unroll

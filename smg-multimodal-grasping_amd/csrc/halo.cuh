@@ -78,13 +78,11 @@ __device__ __forceinline__ u32x4 dpp_col_shift(const u32x4& p, const u32x4& e) {
 }
 
 struct Halo3x3FwdArgs {
-    const void* src; int lds_; Plane pl;            // [n][HWp][C] raw bottleneck output (fp32 / bf16 / fp16 by mode)
+    // [n][HWp][C] raw bottleneck output (fp32 / bf16 / fp16 by mode) and its norm2: every channel is fresh - derived from the fp64
+    // sums, and the first tile of every stream stores mean / invstd in the table for the backward
+    ActSrc act; Plane pl;
     int C;                                          // input channels (128)
-    const double* ssum; const double* ssq; int sstride;     // fp64 statistics of src (norm2 input)
-    const float* gamma; const float* beta; float eps;
-    float* tw_mean; float* tw_invstd;               // [n][C]: the first tile of every stream stores mean / invstd for the backward
     const u32x4* wu;                                // weight units [chunk][piece][tap][k8][n] (PK_HF); operand kind 3: header unit in front
-    const float* asc;                               // operand kind 3: {s, 1 / s} of the BN + ReLU operand
     void* dst; int ldd, dcoff;
     double* dsum; double* dsq; int dstride;
     int tiles_x, n_tiles, streams;                   // 1-D grid of banded_grid(n_tiles, streams) workgroups (banded_tile)
@@ -173,7 +171,7 @@ static __global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : kHaloFwdWaves) void
     const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
     const int y0 = ty * TS, x0 = tx * TS;
     const int C = a.C, kq = t & 3;                           // this thread's 16-byte slot inside every chunk (E channels)
-    const float sa = OP == 3 ? a.asc[0] : 1.f;               // operand kind 3: the activation scale rides on gamma * invstd and beta
+    const float sa = OP == 3 ? a.act.asc[0] : 1.f;               // operand kind 3: the activation scale rides on gamma * invstd and beta
 
     int a_off[A_N];       // global pixel index, -1 = outside the image / unused slot
     int a_hp[A_N];        // halo pixel of the slot, -1 = unused
@@ -187,7 +185,7 @@ static __global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : kHaloFwdWaves) void
         a_off[i] = ok ? (iy * a.pl.W + ix) : -1;
         a_hp[i] = (idx < G::PX * 4) ? hp : -1;
     }
-    const char* src_n = static_cast<const char*>(a.src) + (int64_t)ESZ * n * a.pl.HWp * a.lds_;
+    const char* src_n = static_cast<const char*>(a.act.x) + (int64_t)ESZ * n * a.pl.HWp * a.act.ldx;
     const u32x4* wu = a.wu;
     constexpr int NSET = 1;              // register sets of loads in flight (WS with two sets, loads two chunks ahead: 15.3 -> 15.2 us per launch - one
                                          // chunk of taps covers the loads)
@@ -198,7 +196,7 @@ static __global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : kHaloFwdWaves) void
         const int c0 = chunk * CK + E * kq;
 #pragma unroll
         for (int i = 0; i < A_N; ++i)                               // unconditional loads from clamped addresses
-            ra[i] = ld16(src_n, (int64_t)ESZ * ((int64_t)(a_off[i] < 0 ? 0 : a_off[i]) * a.lds_ + c0));
+            ra[i] = ld16(src_n, (int64_t)ESZ * ((int64_t)(a_off[i] < 0 ? 0 : a_off[i]) * a.act.ldx + c0));
 #pragma unroll
         for (int i = 0; i < B_N; ++i) rb[i] = wu[(int64_t)chunk * G::BU + t + 256 * i];      // (slack behind the packed array)
     };
@@ -245,12 +243,9 @@ static __global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : kHaloFwdWaves) void
     g_load(0, Set0{});                       // (the first chunk's loads in front of the parameter prologue, which waits for its own fp64 sums: measured, no change -
                                      //  66.5 / 16.6 us per launch both ways; the prologue's 9.8k cycles are the moments' arithmetic and the first store)
     for (int k = threadIdx.x; k < C; k += (WS ? 512 : 256)) {            // BN parameters of this stream
-        float mean, invstd;
-        bn_moments(a.ssum, a.ssq, (int64_t)n * a.sstride + k, 1.0 / (double)a.pl.HW, a.eps, mean, invstd);
-        prm[k] = mean;
-        prm[C + k] = a.gamma[k] * invstd * sa;
-        prm[2 * C + k] = a.beta[k] * sa;
-        if (tile == 0) { a.tw_mean[(int64_t)n * C + k] = mean; a.tw_invstd[(int64_t)n * C + k] = invstd; }
+        const ActCoef f = act_src_coef<A_SUMS>(a.act, n, k, 1.0 / (double)a.pl.HW);
+        act_prm_store(prm + k, C, f, sa);
+        if (tile == 0) { a.act.tw_mean[(int64_t)n * a.act.tab.ld + k] = f.mean; a.act.tw_invstd[(int64_t)n * a.act.tab.ld + k] = f.invstd; }
     }
     __syncthreads();                 // prm visible
     if (!WS || role == 1) s_store(0, As, Bs, Set0{});
@@ -425,7 +420,7 @@ static __global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : kHaloFwdWaves) void
 
     // epilogue: raw output + per-(stream, channel) sum / sum of squares (fp64)
     if constexpr (OP == 3) {                      // products of scaled operands: exact power-of-two correction
-        const float inv = a.asc[1] * pack_inv_scale(a.wu);
+        const float inv = a.act.asc[1] * pack_inv_scale(a.wu);
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -491,9 +486,8 @@ __device__ __forceinline__ void grad_src_params(const GradSrc& s, int n, int hw,
 struct Halo3x3DgradArgs {
     GradSrc g; Plane pl;                             // finished output gradient (32 channels)
     const u32x4* wu;                                 // weight units [c/32][tap][piece][k8][c%32] (PK_HD)
-    BnTab bt;                                        // norm2 statistics of this layer (stored by the forward) + gamma / beta
+    ActSrc m;                                        // raw bottleneck [n][HWp][C] (mask + xhat source) and its norm2 (table stored by the forward)
     int C;                                           // bottleneck channels (128)
-    const void* mbuf;                                // raw bottleneck [n][HWp][C] (mask + xhat source)
     void* dst;                                       // dy [n][HWp][C]
     double* o1; double* o2; int ostride;             // per-stream sums [n][C]
     int tiles_x;
@@ -596,13 +590,8 @@ static __global__ __launch_bounds__(256, TS == 8 ? 4 : 2) void conv3x3_halo_dgra
         if (x_n) rx[i] = ld16(x_n, (int64_t)XSZ * (pix * a.g.ldx + E * q));
     }
     __builtin_amdgcn_sched_barrier(0);
-    for (int k = t; k < C; k += 256) {                  // norm2 parameters of this stream (layer table of the forward)
-        const float invstd = tab_invstd(a.bt, n)[k];
-        prm[k] = a.bt.gamma[k] * invstd;
-        prm[C + k] = a.bt.beta[k];
-        prm[2 * C + k] = tab_mean(a.bt, n)[k];
-        prm[3 * C + k] = invstd;
-    }
+    for (int k = t; k < C; k += 256)                    // norm2 parameters of this stream (layer table of the forward)
+        act_mask_store(prm + k, C, act_src_coef<A_TAB>(a.m, n, k, 1.0 / (double)a.pl.HW));
     float* gp = prm + 4 * C + 256;                     // GradSrc parameters [4][32]
     grad_src_params(a.g, n, a.pl.HW, gp);
     // operand kind 3: scale of the gradient operand and inverse of the (gradient x weight) scale - from the stream's recorded maximum
@@ -757,8 +746,8 @@ static __global__ __launch_bounds__(256, TS == 8 ? 4 : 2) void conv3x3_halo_dgra
         const int py = y0 + (kRegFrag ? G::rowi(wq, m, i) : G::row(wq, m, i)), px = x0 + G::col(i);
         const bool ok = !kEdge || (py < a.pl.H && px < a.pl.W);     // tiles may hang over the edge: clamped address
         const int64_t idx = ((int64_t)n * a.pl.HWp + (ok ? py * a.pl.W + px : 0)) * C + c0 + 4 * (l31 >> 2);
-        if constexpr (std::is_same<XT, e_f32>::value) xq[m][g] = *reinterpret_cast<const float4*>(static_cast<const float*>(a.mbuf) + idx);
-        else xq[m][g] = *reinterpret_cast<const uint2*>(static_cast<const unsigned short*>(a.mbuf) + idx);
+        if constexpr (std::is_same<XT, e_f32>::value) xq[m][g] = *reinterpret_cast<const float4*>(static_cast<const float*>(a.m.x) + idx);
+        else xq[m][g] = *reinterpret_cast<const uint2*>(static_cast<const unsigned short*>(a.m.x) + idx);
     };
     for (int s3 = 0; s3 < NSTAGE; s3 += 3 * SPR) {     // one output-channel group (three kernel rows) per trip
 #pragma unroll
@@ -939,9 +928,7 @@ static __global__ __launch_bounds__(256, TS == 8 ? 4 : 2) void conv3x3_halo_dgra
 
 struct Halo3x3WgradArgs {
     GradSrc g; Plane pl;                             // finished output gradient (32 channels)
-    const void* src; int C;                          // raw bottleneck [n][HWp][C]
-    BnTab bt;                                        // norm2 statistics of this layer (stored by the forward) + gamma / beta
-    const float* asc;                                // operand kind 3: {s, 1 / s} of the BN + ReLU operand
+    ActSrc b; int C;                                 // raw bottleneck [n][HWp][C] and its norm2 (table stored by the forward)
     float* part;                                     // partial sums [groups * streams][9][32][C]
     int tiles_x, n_tiles, tiles_per_wg;
     int groups, streams;                             // launch geometry: 1-D grid of 8 * ceil(groups * streams / 8) * (C / 32) workgroups
@@ -999,7 +986,7 @@ static __global__ __launch_bounds__(256, kHaloWgradWaves) void conv3x3_halo_wgra
     if constexpr (OP == 3) {
 #pragma unroll
         for (int r = 0; r < kAmaxRep / 4; ++r) am4[r] = *reinterpret_cast<const u32x4*>(a.g.amax + (int64_t)n * kAmaxRep + 4 * r);
-        sa = a.asc[0];
+        sa = a.b.asc[0];
     }
     auto grad_scale = [&]() -> ActScale {
         ActScale g{1.f, 1.f};
@@ -1008,22 +995,18 @@ static __global__ __launch_bounds__(256, kHaloWgradWaves) void conv3x3_halo_wgra
 #pragma unroll
             for (int r = 0; r < kAmaxRep / 4; ++r) m = max(max(m, max(am4[r].x, am4[r].y)), max(am4[r].z, am4[r].w));
             g = scale_of_max(m);
-            g.inv *= a.asc[1];
+            g.inv *= a.b.asc[1];
         }
         return g;
     };
-    if (t < 32) {
-        prm[t] = tab_mean(a.bt, n)[cc0 + t];
-        prm[32 + t] = a.bt.gamma[cc0 + t] * tab_invstd(a.bt, n)[cc0 + t] * sa;
-        prm[64 + t] = a.bt.beta[cc0 + t] * sa;
-    }
+    act_params_cols<32, 256, A_TAB>(a.b, n, cc0, C, 1.0 / (double)a.pl.HW, sa, prm);
     grad_src_params(a.g, n, a.pl.HW, gp);
     f32x16 acc[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-    const char* src_n = static_cast<const char*>(a.src) + (int64_t)XSZ * ((int64_t)n * a.pl.HWp * C + cc0);
+    const char* src_n = static_cast<const char*>(a.b.x) + (int64_t)XSZ * ((int64_t)n * a.pl.HWp * C + cc0);
     const char* g_n = static_cast<const char*>(a.g.g) + (int64_t)GSZ * n * a.pl.HWp * a.g.ldg;
     const char* x_n = a.g.x ? static_cast<const char*>(a.g.x) + (int64_t)XSZ * n * a.pl.HWp * a.g.ldx : nullptr;
     // transposing-read geometry: lane i of a 16-lane group fetches pixel-row (k) i/4, channel quad i%4 and receives channel i

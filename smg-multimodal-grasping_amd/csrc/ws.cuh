@@ -21,12 +21,9 @@
 namespace smg {
 
 struct Fwd1x1WsArgs {
-    const float* src; int lds_; Plane pl;          // [n][HWp][lds_] block buffer, K = first K channels
+    ActSrc act; Plane pl;                          // [n][HWp][ldx] block buffer (fp32) and the layer's norm1, K = first K channels
     int K;
-    BnTab bt; int fresh0; const double* fsum; const double* fsq; int fstride; float eps;
-    float* tw_mean; float* tw_invstd;
     const u32x4* wp; int N;                        // packed weight units [piece][K/8][N]; operand kind 3: header unit in front
-    const float* asc;                              // operand kind 3: {s, 1 / s} of the BN + ReLU operand
     float* dst; int ldd;                           // raw output [n][HWp][ldd]
     double* dsum; double* dsq; int dstride;        // per-(stream, channel) sum / sum of squares
     TileMap tm;                                    // XCD-aware order: the N tiles of one M tile are consecutive on one XCD
@@ -67,10 +64,10 @@ static __global__ __launch_bounds__(512, 1) void conv1x1_fwd_ws_kernel(const Fwd
 
     // ---- producers: staging geometry (loop-invariant lane offsets; descriptor loads, see gemm.cuh)
     const int aq = tp % (G::BK / 4), al = tp / (G::BK / 4);          // channel quad, first row; rows al, al + 32
-    const float* a_base = a.src + (int64_t)n * a.pl.HWp * a.lds_;
+    const float* a_base = static_cast<const float*>(a.act.x) + (int64_t)n * a.pl.HWp * a.act.ldx;
     unsigned a_voff[G::A_N];
 #pragma unroll
-    for (int i = 0; i < G::A_N; ++i) a_voff[i] = 4u * (unsigned)((pbase + al + 32 * i) * a.lds_ + 4 * aq);
+    for (int i = 0; i < G::A_N; ++i) a_voff[i] = 4u * (unsigned)((pbase + al + 32 * i) * a.act.ldx + 4 * aq);
     unsigned b_voff[G::B_N];
 #pragma unroll
     for (int i = 0; i < G::B_N; ++i) {
@@ -105,30 +102,9 @@ static __global__ __launch_bounds__(512, 1) void conv1x1_fwd_ws_kernel(const Fwd
         g_load(0, ra[0], rb[0]);
         g_load(KT > 1 ? 1 : 0, ra[1], rb[1]);
     }
-    // ---- BN parameters of the K input channels -> LDS (all 512 threads; the fresh channels from the fp64 sums)
-    {
-        const float* tmean = tab_mean(a.bt, n);
-        const float* tinv = tab_invstd(a.bt, n);
-        const float sa = OP == 3 ? a.asc[0] : 1.f;                       // operand kind 3: the activation scale rides on gamma * invstd and beta
-        for (int ch = 4 * t; ch < K && ch < a.fresh0; ch += 2048) {
-            const f32x4 m = ldv4(tmean + ch), iv = ldv4(tinv + ch), g = ldv4(a.bt.gamma + ch), be = ldv4(a.bt.beta + ch);
-            *reinterpret_cast<f32x4*>(sp + ch) = m;
-            *reinterpret_cast<f32x4*>(sp + K + ch) = g * iv * sa;
-            *reinterpret_cast<f32x4*>(sp + 2 * K + ch) = be * sa;
-        }
-        if (a.fresh0 < K && t < 32) {
-            const int ch = a.fresh0 + t;
-            float mean, invstd;
-            bn_moments(a.fsum, a.fsq, (int64_t)n * a.fstride + ch, 1.0 / (double)a.pl.HW, a.eps, mean, invstd);
-            sp[ch] = mean;
-            sp[K + ch] = a.bt.gamma[ch] * invstd * sa;
-            sp[2 * K + ch] = a.bt.beta[ch] * sa;
-            if (n0 == 0 && pbase == 0) {
-                a.tw_mean[(int64_t)n * a.bt.ld + ch] = mean;
-                a.tw_invstd[(int64_t)n * a.bt.ld + ch] = invstd;
-            }
-        }
-    }
+    // ---- BN parameters of the K input channels -> LDS (all 512 threads; the fresh channels from the fp64 sums; operand kind 3: the
+    // activation scale rides on gamma * invstd and beta)
+    act_params_fwd<512>(a.act, n, K, 1.0 / (double)a.pl.HW, OP == 3 ? a.act.asc[0] : 1.f, n0 == 0 && pbase == 0, sp);
     __syncthreads();
     if (role == 1) s_store(0, 0, ra[0], rb[0]);
     __syncthreads();
@@ -205,7 +181,7 @@ static __global__ __launch_bounds__(512, 1) void conv1x1_fwd_ws_kernel(const Fwd
     for (int j = 0; j < TN; ++j) v0[j] = v1[j] = 0.0;
     if (role == 0) {
         if constexpr (OP == 3) {               // products of scaled operands: exact power-of-two correction
-            const float inv = a.asc[1] * pack_inv_scale(a.wp);
+            const float inv = a.act.asc[1] * pack_inv_scale(a.wp);
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll

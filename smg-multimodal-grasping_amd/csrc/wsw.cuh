@@ -20,8 +20,7 @@ namespace smg {
 
 struct Wgrad1x1WsArgs {
     const u32x4* d2; const float* binv;            // gradient operand: units of the ring slot + [streams][HWp / 64] inverse block scales
-    const float* x; int ldb; Plane pl; int NB;     // block buffer [n][HWp][ldb], the layer's first NB channels
-    StatTab btab; const float* bgamma; const float* bbeta; const float* basc;      // norm1 of the layer: statistics table, affine, {s, 1 / s}
+    ActSrc b; Plane pl; int NB;                    // block buffer [n][HWp][ldx] (fp32), the layer's first NB channels, and its norm1 (from the forward's table)
     int chunk, chunks_per_stream, n_chunks;        // pixel chunks (multiples of 64) per stream / in all
     float* dw; int ldw_out;                        // gradient [128][cin] (atomics) ...
     float* part; int ldp;                          // ... or partial tiles [chunk][128][ldp] for the fixed-order reduce
@@ -58,8 +57,8 @@ static __global__ __launch_bounds__(512, 1) void conv1x1_wgrad_ws_kernel(const W
 
     // ---- producers: loop-invariant lane offsets (descriptor loads: uniform base, per-k-tile scalar offset)
     const u32x4* d2n = a.d2 + d2_stream_units(n, a.pl.HWp);
-    const float* xn = a.x + (int64_t)n * a.pl.HWp * a.ldb;
-    const unsigned d2_bytes = 16u * (unsigned)(2 * kD2K8 * a.pl.HWp), x_bytes = 4u * (unsigned)(a.pl.HW * a.ldb);      // rows past the plane read as zero
+    const float* xn = static_cast<const float*>(a.b.x) + (int64_t)n * a.pl.HWp * a.b.ldx;
+    const unsigned d2_bytes = 16u * (unsigned)(2 * kD2K8 * a.pl.HWp), x_bytes = 4u * (unsigned)(a.pl.HW * a.b.ldx);      // rows past the plane read as zero
     unsigned a_voff[G::A_N], b_voff[G::B_N];
 #pragma unroll
     for (int i = 0; i < G::A_N; ++i) {
@@ -68,13 +67,13 @@ static __global__ __launch_bounds__(512, 1) void conv1x1_wgrad_ws_kernel(const W
     }
     const int bq = tp % (G::BN / 4), bl = tp / (G::BN / 4);              // channel quad of the tile, first pixel row; rows bl + 8 i
 #pragma unroll
-    for (int i = 0; i < G::B_N; ++i) b_voff[i] = 4u * (unsigned)((bl + 8 * i) * a.ldb + n0 + 4 * bq);
+    for (int i = 0; i < G::B_N; ++i) b_voff[i] = 4u * (unsigned)((bl + 8 * i) * a.b.ldx + n0 + 4 * bq);
     u32x4 ra[2][G::A_N]; float4 rb[2][G::B_N];
     auto g_load = [&](int kt, u32x4 (&xa)[G::A_N], float4 (&xb)[G::B_N]) {
 #pragma unroll
         for (int i = 0; i < G::A_N; ++i) xa[i] = bload_u4(d2n, d2_bytes, a_voff[i], 16u * (unsigned)(p0 + kt * G::BK));
 #pragma unroll
-        for (int i = 0; i < G::B_N; ++i) xb[i] = bload4(xn, x_bytes, b_voff[i], 4u * (unsigned)((p0 + kt * G::BK) * a.ldb));
+        for (int i = 0; i < G::B_N; ++i) xb[i] = bload4(xn, x_bytes, b_voff[i], 4u * (unsigned)((p0 + kt * G::BK) * a.b.ldx));
     };
     KPrm3 bfix{};
     auto s_store = [&](int buf, const u32x4 (&xa)[G::A_N], const float4 (&xb)[G::B_N]) {
@@ -98,17 +97,7 @@ static __global__ __launch_bounds__(512, 1) void conv1x1_wgrad_ws_kernel(const W
         g_load(KT > 1 ? 1 : 0, ra[1], rb[1]);
     }
     // ---- parameters: BN + ReLU of the 128 columns (from the forward's table), the chunk's block scales
-    if (t < G::BN) {
-        const int ch = n0 + t;
-        float mean = 0.f, sc = 0.f, be = 0.f;
-        if (ch < a.NB) {
-            const float sa = a.basc[0];
-            mean = a.btab.mean[(int64_t)n * a.btab.ld + ch];
-            sc = a.bgamma[ch] * a.btab.invstd[(int64_t)n * a.btab.ld + ch] * sa;
-            be = a.bbeta[ch] * sa;
-        }
-        bp[t] = mean; bp[G::BN + t] = sc; bp[2 * G::BN + t] = be;
-    }
+    act_params_cols<G::BN, 512, A_TAB>(a.b, n, n0, a.NB, 1.0 / (double)a.pl.HW, a.b.asc[0], bp);
     {
         const float* bi = a.binv + (int64_t)n * (a.pl.HWp / kScaleBlock) + p0 / kScaleBlock;
         for (int j = t; j * kScaleBlock < KT * G::BK; j += 512) sinv[j] = bi[j];
@@ -215,7 +204,7 @@ static __global__ __launch_bounds__(512, 1) void conv1x1_wgrad_ws_kernel(const W
     }
 
     // ---- epilogue (consumers): exact power-of-two correction, then partial tile or atomics
-    const float gi = cur_inv * a.basc[1];
+    const float gi = cur_inv * a.b.asc[1];
     const int l31 = lane & 31;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
