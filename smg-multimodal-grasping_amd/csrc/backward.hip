@@ -87,7 +87,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         ValueBwdArgs a;
         a.h1 = head_norm1_src(e, Hd, P); a.p4 = p4; a.w2p = e->packed_f + e->pk_head1;
         a.dq = dq; a.out_ch = e->head_out; a.OH = e->OH; a.OW = e->OW; a.dh1 = e->DH1;
-        a.o1 = b1(e, e->st_H1); a.o2 = b2(e, e->st_H1); a.dbeta = Gr + Hd.n1.b; a.dgamma = Gr + Hd.n1.w; a.dw2 = Gr + Hd.c1.w;
+        a.st = stat_sink_bwd(e, e->st_H1, 0); a.aff = affine_sink(Gr, Hd.n1); a.dw2 = Gr + Hd.c1.w;
         // a dense dq (the mark of smg_loss_map / smg_loss_map_ce, or "head_bwd" = 2) takes the two-pass form without atomics on the weight
         // gradient, one-channel and 3-class heads alike
         const bool dense = !elem_head && (e->head_bwd == 2 || (e->head_bwd == 0 && e->f_dense_dq));
@@ -134,8 +134,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         p.wp = e->packed_u + e->pk_hd0; p.K8tot = kHeadMid / 8; p.ldn = 2 * kFeat; p.wcol0 = 0; p.N = 2 * kFeat;
         p.m = f0; p.pm = p4;
         p.dst = e->DF; p.ldd = 2 * kFeat; p.dcoff = 0;
-        p.o1 = b1(e, e->st_F); p.o2 = b2(e, e->st_F); p.ostride = 2 * kFeat; p.ocoff = 0;
-        p.dbeta = Gr + Hd.n0.b; p.dgamma = Gr + Hd.n0.w; p.rep_stride = 0;
+        p.st = stat_sink_bwd(e, e->st_F, 0); p.aff = affine_sink(Gr, Hd.n0);
         launch_gemm(e, st, p, dim3(NP * p4.HWp / Cfg::BM, 2 * kFeat / Cfg::BN), K_HD0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid,
                     4.0 * NP * p4.HW * (2 * kHeadMid + 2 * 2 * kFeat));
             };
@@ -146,8 +145,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         a.df = grad_src(e, e->DF, 2 * kFeat, e->F, 2 * kFeat, e->st_F, 0, P + Hd.n0.w); a.p4 = p4;
         a.x4 = norm5_src(e, T, P);
         a.user_ptr = e->d_user_ptr; a.user_pair = e->d_user_pair; a.user_slot = e->d_user_slot;
-        a.G4 = e->G[3]; a.SA = b1(e, e->st_X[3]); a.SB = b2(e, e->st_X[3]);
-        a.dbeta5 = Gr + T.norm5.b; a.dgamma5 = Gr + T.norm5.w; a.chunk = 16;
+        a.G4 = e->G[3]; a.st = stat_sink_bwd(e, e->st_X[3], 0); a.aff = affine_sink(Gr, T.norm5); a.chunk = 16;
         PREC_DISPATCH(e, launch_kernel(e, norm5_bwd_kernel<PREC>, dim3(4, NS, (p4.HW + 15) / 16), dim3(256), 0, st, K_OTHER, 0, 0, false, a));
     }
     }   // ph_a: head
@@ -276,6 +274,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             const DenseLayerRef& d = T.layers[b][i];
             float* bt = el(e, e->Bt, e->bt_off[b][i]);
             const ActSrc n2 = norm2_src(b, i);      // Bt through norm2: the 3x3 data gradient's mask (its weight gradient builds the same on the side stream)
+            const StatSink n2st = stat_sink_bwd(e, e->st_Bt[b][i], 0);      // norm2's sums: the halo and the generic 3x3 data gradient add to them
             const LayerBuf lb = buf_of(b, i);
             float* GSb = lb.GS;
             float* D2b = lb.D2;
@@ -283,7 +282,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             // (ring position + 2 - kRing; the side stream is in order, so the two before it are done as well)
             static_assert(kRing % 3 == 0 && kRing > 3, "the sparse ring wait covers three slots at a time");
             if (lb.ring >= kRing && lb.ring % 3 == 0) HIP_OK(hipStreamWaitEvent(st, e->ev_side[(lb.ring + 2) % kRing], 0));
-            // This layer's finished output-slice gradient GS = invstd*(G' - SA/n - xhat*SB/n), materialised once (dense
+            // This layer's finished output-slice gradient GS = invstd*(G' - s1/n - xhat*s2/n), materialised once (dense
             // [px][32]) for the 3x3 data- and weight-gradient kernels.  They can also apply it while loading the G' / X
             // slices (GradSrc with x set): one launch less on the dependency chain, but measured 0.5 ms per step slower on
             // many-stream batches - two strided 128-B-per-pixel reads replace one dense one in both consumers.
@@ -296,7 +295,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 // conv2 (3x3) data gradient with the gradient halo resident in LDS (halo.cuh)
                 Halo3x3DgradArgs a;
                 a.g = gsrc; a.pl = pl; a.C = kBottleneck; a.m = n2;
-                a.dst = split16 ? e->DY2 : D2b; a.o1 = b1(e, e->st_Bt[b][i]); a.o2 = b2(e, e->st_Bt[b][i]); a.ostride = kBottleneck;
+                a.dst = split16 ? e->DY2 : D2b; a.st = n2st;
                 a.wu = e->packed_u + e->pk_hd[b][i];
                 // (traced launches: dev stamps with SMG_TRACE_KIND=5)
                 const double flops = 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth;
@@ -323,8 +322,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                     p.wp = e->packed_u + e->pk_g3d[b][i]; p.K8tot = 9 * kGrowth / 8; p.ldn = kBottleneck; p.wcol0 = 0; p.N = kBottleneck;
                     p.m = n2; p.pm = pl;
                     p.dst = split16 ? e->DY2 : D2b; p.ldd = kBottleneck; p.dcoff = 0;
-                    p.o1 = b1(e, e->st_Bt[b][i]); p.o2 = b2(e, e->st_Bt[b][i]); p.ostride = kBottleneck; p.ocoff = 0;
-                    p.dbeta = Gr + d.n2.b; p.dgamma = Gr + d.n2.w;
+                    p.st = n2st; p.aff = affine_sink(Gr, d.n2);
                     launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, kBottleneck / Cfg::BN), K_D3, 2.0 * NS * pl.HW * 9 * kBottleneck * kGrowth,
                                 ESZ(e) * NS * pl.HW * (kGrowth + 2 * kBottleneck));
                 };
@@ -336,12 +334,12 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             if (split16) {   // norm2 backward applied once: D2 (unit form, per-block scales) <- gamma2*invstd*(dy - s1/n - xhat*s2/n)
                 BnBwdApplySplitArgs a{};
                 a.src = dy2; a.pl = pl; a.out = reinterpret_cast<u32x4*>(D2b); a.binv = lb.D2S;
-                if (!e->generic3x3) { a.dbeta = Gr + d.n2.b; a.dgamma = Gr + d.n2.w; }   // the halo dgrad leaves these to us
+                if (!e->generic3x3) a.aff = affine_sink(Gr, d.n2);      // the halo dgrad leaves these to us
                 launch_kernel(e, bn_bwd_apply_split_kernel, dim3(pl.HWp / kScaleBlock, NS), dim3(256), 0, st, K_OTHER, 0, 4.0 * NS * pl.HW * 3 * kBottleneck, false, a);
             } else {   // 16-bit modes: norm2 backward applied once, in place: D2 <- gamma2*invstd*(dy - s1/n - xhat*s2/n)
                 BnBwdApplyArgs a{};
                 a.src = dy2; a.pl = pl; a.C = kBottleneck; a.out = D2b; a.ldo = kBottleneck;
-                if (!e->generic3x3) { a.dbeta = Gr + d.n2.b; a.dgamma = Gr + d.n2.w; }   // the halo dgrad leaves these to us
+                if (!e->generic3x3) a.aff = affine_sink(Gr, d.n2);      // the halo dgrad leaves these to us
                 PREC_DISPATCH(e, launch_kernel(e, bn_bwd_apply_kernel<PREC>, dim3((pl.HWp + bn_apply_rows(PREC) - 1) / bn_apply_rows(PREC), NS), dim3(256), 0, st,
                                                K_OTHER, 0, ESZ(e) * NS * pl.HW * 3 * kBottleneck, false, a));
             }
@@ -375,8 +373,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                     p.wp = e->packed_u + e->pk_d1[b][i]; p.K8tot = kBottleneck / 8; p.ldn = d.cin; p.wcol0 = cs; p.N = d.cin - cs;
                     p.m = norm1_src(b, i, cs); p.pm = pl;
                     p.dst = e->G[b]; p.ldd = Ct; p.dcoff = cs;
-                    p.o1 = b1(e, e->st_X[b]); p.o2 = b2(e, e->st_X[b]); p.ostride = Ct; p.ocoff = cs;
-                    p.dbeta = e->dbscr + e->db_off[b][i] + cs; p.dgamma = e->dbscr + e->db_off[b][i] + d.cin + cs; p.rep_stride = e->db_total;
+                    p.st = stat_sink_bwd(e, e->st_X[b], cs); p.aff = affine_sink_scr(e, e->db_off[b][i], d.cin, cs);
                     launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, (p.N + Cfg::BN - 1) / Cfg::BN), K_D1, 2.0 * NS * pl.HW * p.N * kBottleneck,
                                 ESZ(e) * NS * pl.HW * (kBottleneck + 3.0 * p.N));          // dy in; x in, G' read + written
                 };
@@ -393,12 +390,12 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                         const LayerBuf lk = buf_of(b, g_lo + k);
                         p.seg[k].g = lk.D2; p.seg[k].wp = e->packed_u + e->pk_d1[b][g_lo + k]; p.seg[k].ldn = dk.cin; p.seg[k].binv = lk.D2S;
                         p.seg[k].gamma = P + dk.n1.w; p.seg[k].beta = P + dk.n1.b;
-                        p.seg[k].dbeta = e->dbscr + e->db_off[b][g_lo + k]; p.seg[k].dgamma = e->dbscr + e->db_off[b][g_lo + k] + dk.cin;
+                        p.seg[k].aff = affine_sink_scr(e, e->db_off[b][g_lo + k], dk.cin, 0);
                     }
                     p.ldg = kBottleneck; p.pa = pl; p.KA = kBottleneck; p.N = cs;
                     p.m = act_src(e, e->X[b], Ct, e->st_X[b], 0, nullptr, nullptr, stat_table(e, e->sx_tab[b], e->max_streams, Ct));      // (gamma / beta: per segment)
                     p.dst = e->G[b]; p.ldd = Ct;
-                    p.o1 = b1(e, e->st_X[b]); p.o2 = b2(e, e->st_X[b]); p.ostride = Ct; p.rep_stride = e->db_total;
+                    p.st = stat_sink_bwd(e, e->st_X[b], 0);
                     launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, (cs + Cfg::BN - 1) / Cfg::BN), K_D1, 2.0 * NS * pl.HW * cs * kBottleneck * p.nseg,
                                 ESZ(e) * NS * pl.HW * ((double)p.nseg * kBottleneck + 3.0 * cs));
                 };
@@ -442,8 +439,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 p.wp = e->packed_u + e->pk_td[b - 1]; p.K8tot = C0 / 8; p.ldn = Cp; p.wcol0 = 0; p.N = Cp;
                 p.m = xt; p.pm = pp;
                 p.dst = e->G[b - 1]; p.ldd = Cp; p.dcoff = 0;
-                p.o1 = b1(e, e->st_X[b - 1]); p.o2 = b2(e, e->st_X[b - 1]); p.ostride = Cp; p.ocoff = 0;
-                p.dbeta = e->dbscr + e->db_toff[b - 1]; p.dgamma = e->dbscr + e->db_toff[b - 1] + Cp; p.rep_stride = e->db_total;
+                p.st = stat_sink_bwd(e, e->st_X[b - 1], 0); p.aff = affine_sink_scr(e, e->db_toff[b - 1], Cp, 0);
                 launch_gemm(e, st, p, dim3(NS * pl.HWp / Cfg::BM, Cp / Cfg::BN), K_TD, 2.0 * NS * pl.HW * Cp * C0,
                             ESZ(e) * NS * (2.0 * pl.HW * C0 + 2.0 * pp.HW * Cp));
             };
@@ -459,7 +455,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         a.argmax = e->argmax; a.stemv = e->stemv;
         a.stem = act_src(e, nullptr, 64, e->st_stem, 0, P + T.norm0.w, nullptr); a.ps = e->p_stem;      // (the stem plane is not read here)
         a.img = e->img4; a.pi = e->p_img;
-        a.o1 = b1(e, e->st_stem); a.o2 = b2(e, e->st_stem);
+        a.st = stat_sink_bwd(e, e->st_stem, 0);
         a.tiles_x = (p1.W + kTailTW - 1) / kTailTW; a.n_tiles = a.tiles_x * ((p1.H + kTailTH - 1) / kTailTH);
         // one 64 x 64 partial tile per workgroup.  Runs of 8 tiles or more: as long as it takes for ONE round of workgroups (three are
         // resident per CU) and for the partial tiles to fit the workspace
@@ -488,8 +484,7 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         Pool0BwdArgs a;
         a.g1 = grad_src(e, e->G[0], kBlockCtot[0], e->X[0], kBlockCtot[0], e->st_X[0], 0, nullptr); a.p1 = e->p_blk[0];
         a.argmax = e->argmax; a.stem = act_src(e, e->stem, 64, e->st_stem, 0, P + T.norm0.w, P + T.norm0.b); a.ps = e->p_stem;
-        a.DY0 = e->DY0; a.o1 = b1(e, e->st_stem); a.o2 = b2(e, e->st_stem);
-        a.dbeta = Gr + T.norm0.b; a.dgamma = Gr + T.norm0.w;
+        a.DY0 = e->DY0; a.st = stat_sink_bwd(e, e->st_stem, 0); a.aff = affine_sink(Gr, T.norm0);
         if (e->p_stem.H % 8 || e->p_stem.W % 8) return fail(-22, "stem plane must tile by 8 (input_size multiple of 16)");
         a.tiles_per_wg = 8;          // 4..20 measure the same; 1 costs 0.7 ms per step in atomics
         const int n_t = (e->p_stem.H / 8) * (e->p_stem.W / 8);
@@ -524,10 +519,11 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         // half must not touch a single element of them (it would re-write a stale local value over the reduced one).
         const int first_b = 2 * kBlockLayers[0];
         const int seg0 = ph_b ? 0 : first_b, seg1 = ph_a ? e->n_dbseg : first_b;
+        const GradSrc dy0 = grad_src(e, nullptr, 64, nullptr, 64, e->st_stem, 0, nullptr);      // norm0's sums: the statistics side alone
         launch_kernel(e, db_flush_kernel, dim3(4, seg1 - seg0 + 1), dim3(256), 0, st, K_OTHER, 0, 0, false,
                       reinterpret_cast<const DbSegD*>(e->d_dbseg + (size_t)e->f_trunk * e->n_dbseg) + seg0,
                       e->dbscr, e->db_total, kDbRep, Gr,
-                      ph_b ? b1(e, e->st_stem) : nullptr, ph_b ? b2(e, e->st_stem) : nullptr, NS, Gr + T.norm0.b, Gr + T.norm0.w);
+                      ph_b ? dy0.s1 : nullptr, ph_b ? dy0.s2 : nullptr, NS, Gr + T.norm0.b, Gr + T.norm0.w);
     }
     launch_reduce2(e, s2, tiles.drain());
     HIP_OK(hipEventRecord(e->ev_end, s2));          // join: everything after the backward (or this half of it) sees every gradient

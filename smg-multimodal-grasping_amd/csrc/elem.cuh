@@ -276,7 +276,7 @@ static __global__ void bn_stat_kernel(const BnStatArgs a) {
 struct Pool0Args {
     ActSrc stem; Plane ps;                 // raw stem output [n][HWp][64] (fp32), its statistics [n][64] and norm0
     void* x1; int ldx; Plane po;            // block-1 buffer (activation storage of the mode)
-    double* dsum; double* dsq; int dstride;
+    StatSink st;                            // sum x | sum x^2 of the 64 pooled channels
     unsigned char* argmax;                  // [n][po.HWp][64]
     float* stemv;                           // [n][po.HWp][64] the raw stem value at the argmax (stem_tail_kernel), or nullptr
 };
@@ -323,7 +323,7 @@ static __global__ __launch_bounds__(256) void pool0_kernel(const Pool0Args a) {
         const int q = t >> 6, c = t & 63;
         double tot = 0.0;
         for (int k = 0; k < 16; ++k) tot += red[q][k][c];
-        atomicAdd((q ? a.dsq : a.dsum) + (int64_t)n * a.dstride + c + fstat_rep(), tot);
+        stat_sink_add<S_FWD>(a.st, n, c, q, tot);
     }
 }
 
@@ -336,7 +336,7 @@ struct FeatArgs {
     ActSrc x4; Plane p4;                    // [n][HWp][1024] (activation storage of the mode), its statistics [n][1024] and norm5
     const int* pair_a; const int* pair_b;
     float* F;                               // [pair][HWp][2048]
-    double* fsum; double* fsq;              // [pair][2048]
+    StatSink st;                            // [pair][2048]
     int chunk;
 };
 
@@ -368,10 +368,7 @@ static __global__ __launch_bounds__(256) void feat_kernel(const FeatArgs a) {
         for (int c = 0; c < 4; ++c) { sm[c] += od[c]; sq[c] += od[c] * od[c]; }
     }
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        atomicAdd(a.fsum + (int64_t)j * 2048 + ch + c + fstat_rep(), sm[c]);
-        atomicAdd(a.fsq + (int64_t)j * 2048 + ch + c + fstat_rep(), sq[c]);
-    }
+    for (int c = 0; c < 4; ++c) stat_sink_add2<S_FWD>(a.st, j, ch + c, sm[c], sq[c]);
 }
 
 // ------------------------------------------------------------------------------------
@@ -422,16 +419,15 @@ struct ValueBwdArgs {
     const float* w2p;                         // packed [out][400][64]
     const float* dq; int out_ch, OH, OW;
     float* dh1;                               // [pair][HWp][64]
-    double* o1; double* o2;                   // [pair][64]
-    float* dbeta; float* dgamma;              // norm1 grads
+    StatSink st; AffineSink aff;              // [pair][64] sums and norm1's affine gradients
     float* dw2;                               // native [out][64][20][20]
 };
 
 // The two ends the backward kernels below share.  Front: norm1's per-channel parameters of pair j,
 // prm[t] = gamma * invstd | beta | mean | invstd (the caller's barrier publishes them).  Back: the threads' sums of dy and dy * xhat
 // have met in red[2][16][64] (written and published by the caller: a barrier inside the inlined function leaves a dead exec-mask
-// instruction behind in the dense kernels); per channel a 16-way sum in slot order, one double atomic to o1 / o2 and one float
-// atomic to dbeta / dgamma per workgroup.
+// instruction behind in the dense kernels); per channel a 16-way sum in slot order, one double atomic to the statistic sink and one float
+// atomic to the affine sink per workgroup.
 __device__ __forceinline__ void value_bwd_params(const ValueBwdArgs& a, int j, int t, float* prm) {
     if (t < 64) act_mask_store(prm + t, 64, act_src_coef<A_SUMS>(a.h1, j, t, 1.0 / (double)a.p4.HW));
 }
@@ -440,8 +436,8 @@ __device__ __forceinline__ void value_bwd_sums(const ValueBwdArgs& a, int j, int
         const int q = t >> 6, c = t & 63;
         float tot = 0.f;
         for (int k = 0; k < 16; ++k) tot += red[q][k][c];
-        atomicAdd((q ? a.o2 : a.o1) + (int64_t)j * 64 + c + stat_rep(), (double)tot);
-        atomicAdd((q ? a.dgamma : a.dbeta) + c, tot);
+        stat_sink_add<S_BWD>(a.st, j, c, q, (double)tot);
+        affine_sink_add(a.aff, c, q, tot);
     }
 }
 
@@ -681,15 +677,14 @@ static __global__ __launch_bounds__(256) void value_wgrad_dense_kernel(const Val
 // norm5 backward (no ReLU) fused with the head's norm0 backward and the two-stream
 // concat backward: for stream s, sum over every (pair, slot) that consumed its
 // features the BN-corrected gradient of F, then start the block-4 gradient buffer:
-//   G'_4[s] = gamma5 * dy5,  SA/SB += gamma5 * sums,  dbeta5/dgamma5 += sums.
+//   G'_4[s] = gamma5 * dy5,  s1/s2 += gamma5 * sums,  norm5's dbeta/dgamma += sums.
 // ------------------------------------------------------------------------------------
 struct Norm5BwdArgs {
     GradSrc df; Plane p4;                           // the head's gradient of F through norm0: fp32 [pair][HWp][2048], statistics [pair][2048]
     ActSrc x4;                                      // [n][HWp][1024] (activation storage), its statistics [n][1024] and norm5: the descriptor FeatArgs holds
     const int* user_ptr; const int* user_pair; const int* user_slot;  // CSR over streams
     void* G4;                                       // [n][HWp][1024] (gradient storage of the mode)
-    double* SA; double* SB;                         // [n][1024]
-    float* dbeta5; float* dgamma5;
+    StatSink st; AffineSink aff;                    // s1 / s2 of X4 [n][1024] and norm5's affine gradients
     int chunk;
 };
 
@@ -787,10 +782,8 @@ static __global__ __launch_bounds__(256) void norm5_bwd_kernel(const Norm5BwdArg
     if (ph || u0 == u1) return;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        atomicAdd(a.SA + (int64_t)s * 1024 + c5 + c + stat_rep(), (double)(g5[c] * s1[c]));
-        atomicAdd(a.SB + (int64_t)s * 1024 + c5 + c + stat_rep(), (double)(g5[c] * s2[c]));
-        atomicAdd(a.dbeta5 + c5 + c, s1[c]);
-        atomicAdd(a.dgamma5 + c5 + c, s2[c]);
+        stat_sink_add2<S_BWD>(a.st, s, c5 + c, (double)(g5[c] * s1[c]), (double)(g5[c] * s2[c]));
+        affine_sink_add2(a.aff, c5 + c, s1[c], s2[c]);
     }
 }
 
@@ -805,8 +798,7 @@ struct Pool0BwdArgs {
     const unsigned char* argmax;                             // [n][p1.HWp][64]
     ActSrc stem; Plane ps;                                   // raw stem output [n][HWp][64] (fp32), its statistics [n][64] and norm0
     float* DY0;                                              // [n][ps.HWp][64]
-    double* o1; double* o2;                                  // [n][64]
-    float* dbeta; float* dgamma;
+    StatSink st; AffineSink aff;                             // [n][64]; norm0's (db_flush_kernel adds them from the sums, not this kernel)
     int tiles_per_wg;                                        // consecutive 8x8 tiles per workgroup (one flush of the sums)
 };
 
@@ -907,7 +899,7 @@ static __global__ __launch_bounds__(256) void pool0_bwd_kernel(const Pool0BwdArg
         const int q = t >> 6, c = t & 63;
         float tot = 0.f;
         for (int k = 0; k < 16; ++k) tot += red[q][k][c];
-        atomicAdd((q ? a.o2 : a.o1) + (int64_t)n * 64 + c + stat_rep(), (double)tot);
+        stat_sink_add<S_BWD>(a.st, n, c, q, (double)tot);
         // (norm0's dbeta / dgamma are these sums over the streams: db_flush_kernel adds them - 3400 workgroups on one address per
         // channel here were the tail of this kernel)
     }
@@ -936,7 +928,7 @@ struct StemTailArgs {
     const unsigned char* argmax; const float* stemv;         // [n][p1.HWp][64] (pool0_kernel)
     ActSrc stem; Plane ps;                                   // stem stats [n][64] and norm0 (no plane: x unset)
     const float* img; Plane pi;                              // one-channel image [n][pi.HWp]
-    double* o1; double* o2;                                  // [n][64]
+    StatSink st;                                             // [n][64]
     float* part;                                             // [n][gridDim.x][64][64]
     int tiles_x, n_tiles, tiles_per_wg;
 };
@@ -1061,7 +1053,7 @@ static __global__ __launch_bounds__(256) void stem_tail_kernel(const StemTailArg
         const int q = t >> 6, c = t & 63;
         float tot = 0.f;
         for (int k = 0; k < 16; ++k) tot += red[(q * 16 + k) * 64 + c];
-        atomicAdd((q ? a.o2 : a.o1) + (int64_t)n * 64 + c + stat_rep(), (double)tot);      // (db_flush_kernel: norm0's dbeta / dgamma)
+        stat_sink_add<S_BWD>(a.st, n, c, q, (double)tot);      // (db_flush_kernel: norm0's dbeta / dgamma)
     }
 }
 
@@ -1231,7 +1223,7 @@ struct BnBwdApplyArgs {
     GradSrc src;                                  // G' and x of the C channels, gradient / activation storage of the mode
     Plane pl; int C;
     void* out; int ldo;
-    float* dbeta; float* dgamma;                  // if set: the affine gradients, dbeta += sum_n s1[n], dgamma += sum_n s2[n]
+    AffineSink aff;                               // if set: the affine gradients, dbeta += sum_n s1[n], dgamma += sum_n s2[n]
                                                   // (one fp32 atomic per stream and channel instead of one per producer tile)
     unsigned* amax;                               // if set: [streams][kAmaxRep] - the largest |out| of each stream as float bits (atomicMax per
                                                   // workgroup): the scale of the consumers' fp16-split operand (gemm.cuh, operand kind 3)
@@ -1270,10 +1262,8 @@ static __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdApp
         prm[a.C + t] = f.q1;
         prm[2 * a.C + t] = f.mean;
         prm[3 * a.C + t] = f.k;
-        if (a.dbeta && blockIdx.x == 0) {         // (the whole sums, not coefficients)
-            atomicAdd(a.dbeta + t, (float)stat_get(a.src.s1, (int64_t)n * a.src.sstride + t));
-            atomicAdd(a.dgamma + t, (float)stat_get(a.src.s2, (int64_t)n * a.src.sstride + t));
-        }
+        if (a.aff.dbeta && blockIdx.x == 0)       // (the whole sums, not coefficients)
+            affine_sink_add2(a.aff, t, (float)stat_get(a.src.s1, (int64_t)n * a.src.sstride + t), (float)stat_get(a.src.s2, (int64_t)n * a.src.sstride + t));
     }
     __syncthreads();
     float vmax = 0.f;
@@ -1321,7 +1311,7 @@ struct BnBwdApplySplitArgs {
     Plane pl;
     u32x4* out;                                   // units of this ring slot
     float* binv;                                  // [streams][HWp / 64] inverse block scales
-    float* dbeta; float* dgamma;                  // norm2's affine gradients (one fp32 atomic per stream and channel)
+    AffineSink aff;                               // norm2's affine gradients (one fp32 atomic per stream and channel)
 };
 static __global__ __launch_bounds__(256) void bn_bwd_apply_split_kernel(const BnBwdApplySplitArgs a) {
     constexpr int C = 8 * kD2K8;
@@ -1349,10 +1339,7 @@ static __global__ __launch_bounds__(256) void bn_bwd_apply_split_kernel(const Bn
         prm[C + t] = (float)(s1 * inv);
         prm[2 * C + t] = mean;
         prm[3 * C + t] = invstd * (float)(s2 * inv);
-        if (a.dbeta && blockIdx.x == 0) {
-            atomicAdd(a.dbeta + t, (float)s1);
-            atomicAdd(a.dgamma + t, (float)s2);
-        }
+        if (a.aff.dbeta && blockIdx.x == 0) affine_sink_add2(a.aff, t, (float)s1, (float)s2);
     }
     __syncthreads();
     float vmax = 0.f;

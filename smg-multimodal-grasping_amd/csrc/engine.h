@@ -77,7 +77,6 @@ static const char* kKindNames[K_COUNT] = {"stem7x7_fwd", "conv1x1_fwd", "conv3x3
 constexpr int kGroup = GROUP_MAX;          // dense layers per 1x1-dgrad group
 constexpr int kRing = kGroup + 2;
 
-constexpr int kDbRep = 8;
 struct DbSeg { int64_t grad_off; int scr_off; int n; };      // n floats at scr_off (per replica) -> grads[grad_off ..]
 
 struct ProfRec { hipEvent_t a, b; int kind; double flops; int stage; double bytes; };
@@ -112,7 +111,7 @@ struct smg_engine {
     double* bstat = nullptr; int64_t bstat_span = 0;
     // dbeta / dgamma of the trunk's norm1 / transition norms: the data-gradient GEMMs add one value per (workgroup, column) to ONE
     // address per channel - thousands of same-address atomics per launch, which the L2 serialises (about 50-90 ns each: the
-    // kernels' tails).  They go to kDbRep replicas of a compact scratch instead (replica = workgroup index mod kDbRep);
+    // kernels' tails).  They go to kDbRep replicas of a compact scratch instead (AffineSink, gemm.cuh, picks the replica);
     // db_flush_kernel sums the replicas into the gradient array at the end of the backward (half) and re-zeroes them.
     float* dbscr = nullptr; int db_total = 0; int db_off[4][24] = {}; int db_toff[3] = {}; struct DbSeg* d_dbseg = nullptr; int n_dbseg = 0;
     StatArr st_stem, st_X[4], st_F, st_H1; std::vector<StatArr> st_Bt[4];      // one carve for both arenas: fsum / fsq and b1 / b2 take the same handles
@@ -413,6 +412,15 @@ static inline GradSrc grad_done(const float* g, int ldg, const unsigned* amax = 
     r.g = g; r.ldg = ldg; r.amax = amax;
     return r;
 }
+
+// The sums a launch WRITES (StatSink, gemm.cuh; what it reads: act_src / grad_src), channels c0 on: forward arena, streams (or pairs) s0 on | backward arena
+static inline StatSink stat_sink_fwd(smg_engine* e, const StatArr& s, int s0, int c0) {
+    return StatSink{fsum(e, s) + (int64_t)s0 * s.stride + c0, fsq(e, s) + (int64_t)s0 * s.stride + c0, s.stride};
+}
+static inline StatSink stat_sink_bwd(smg_engine* e, const StatArr& s, int c0) { return StatSink{b1(e, s) + c0, b2(e, s) + c0, s.stride}; }
+// One BatchNorm's affine gradients (AffineSink, gemm.cuh): its slots of the gradient array | channels c0 on of the C-channel segment at `at` (db_off / db_toff) of the scratch
+static inline AffineSink affine_sink(float* grads, const BnRef& n) { return AffineSink{grads + n.b, grads + n.w, 0}; }
+static inline AffineSink affine_sink_scr(const smg_engine* e, int at, int C, int c0) { return AffineSink{e->dbscr + at + c0, e->dbscr + at + C + c0, e->db_total}; }
 
 // position of dense layer (block b, layer i; 0-based) in the backward's ring sequence of GS / D2 / D2S slots (slot = position % kRing)
 static inline int ring_pos(int b, int i) {

@@ -107,7 +107,6 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
         int unit = 0;
         auto on = [&]() { const bool r = unit >= u_lo && unit < u_hi; ++unit; return r; };
         auto xs = [&](int b) { return el(e, e->X[b], (int64_t)s0 * e->p_blk[b].HWp * kBlockCtot[b]); };
-        auto st_off = [&](double* base, int stride) { return base + (int64_t)s0 * stride; };      // (the sums a launch WRITES; what it reads: act_src_fwd)
         const bool stem1 = B->heightmaps_dev != nullptr;                      // heightmap form: the three channels are identical by construction
         float* img4 = stem1 ? e->img4 + (int64_t)s0 * e->p_img.HWp : e->img4 + (int64_t)s0 * e->p_img.HWp * 4;
         float* stem = e->stem + (int64_t)s0 * e->p_stem.HWp * 64;
@@ -129,7 +128,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                 p.act.x = img4; p.act.ldx = 4; p.ps = e->p_img; p.po = e->p_stem; p.K = 0;
                 p.wp = e->packed_u + (SM == F_STEM1 ? e->pk_conv0_1 : e->pk_conv0); p.K8tot = (SM == F_STEM1 ? 64 : 224) / 8; p.N = 64;
                 p.dst = stem; p.ldd = 64; p.dcoff = 0;
-                p.dsum = st_off(fsum(e, e->st_stem), 64); p.dsq = st_off(fsq(e, e->st_stem), 64); p.dstride = 64;
+                p.st = stat_sink_fwd(e, e->st_stem, s0, 0);
                 launch_gemm(e, cs, p, dim3(ns * e->p_stem.HWp / Cfg::BM, 1), K_STEM, 2.0 * ns * e->p_stem.HW * 64 * 147,
                             4.0 * ns * ((double)e->p_img.HW * (SM == F_STEM1 ? 1 : 4) + (double)e->p_stem.HW * 64));
             };
@@ -140,7 +139,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
             Pool0Args a;
             a.stem = act_src_fwd(e, stem, 64, e->st_stem, s0, P + T.norm0.w, P + T.norm0.b); a.ps = e->p_stem;
             a.x1 = xs(0); a.ldx = kBlockCtot[0]; a.po = e->p_blk[0];
-            a.dsum = st_off(fsum(e, e->st_X[0]), kBlockCtot[0]); a.dsq = st_off(fsq(e, e->st_X[0]), kBlockCtot[0]); a.dstride = kBlockCtot[0];
+            a.st = stat_sink_fwd(e, e->st_X[0], s0, 0);
             a.argmax = e->argmax + (int64_t)s0 * e->p_blk[0].HWp * 64;
             // the pooled-resolution tail of the backward (one-channel stem, mode 0) reads the stem values at the argmax, not the plane
             // (stored whatever the number of streams: "deterministic" may be set between this forward and its backward)
@@ -151,12 +150,12 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
             e->prof_stage = b;
             const Plane pl = e->p_blk[b];
             const int Ct = kBlockCtot[b];
-            double* xsum = st_off(fsum(e, e->st_X[b]), Ct); double* xsq = st_off(fsq(e, e->st_X[b]), Ct);
             for (size_t i = 0; i < T.layers[b].size(); ++i) {
                 if (!on()) continue;
                 const DenseLayerRef& d = T.layers[b][i];
                 float* bt = el(e, e->Bt, e->bt_off[b][i] + (int64_t)s0 * pl.HWp * kBottleneck);
-                double* bsum = st_off(fsum(e, e->st_Bt[b][i]), kBottleneck); double* bsq = st_off(fsq(e, e->st_Bt[b][i]), kBottleneck);
+                const StatSink bst = stat_sink_fwd(e, e->st_Bt[b][i], s0, 0);            // the bottleneck's sums: the ws and the generic 1x1 add to them
+                const StatSink xst = stat_sink_fwd(e, e->st_X[b], s0, d.cin);            // the 32 appended channels': the halo and the generic 3x3
                 {   // norm1 + relu + conv1 (1x1, cin -> 128)
                     // the layer's input through norm1: the 32 channels the layer below appended are fresh (the block's first layer: none, bn_stat)
                     const ActSrc n1 = act_src_fwd(e, xs(b), Ct, e->st_X[b], s0, P + d.n1.w, P + d.n1.b, stat_table(e, e->sx_tab[b], e->max_streams, Ct),
@@ -169,7 +168,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                         p.act = n1; p.ps = pl; p.po = pl; p.K = d.cin;
                         p.wp = e->packed_u + e->pk_c1[b][i]; p.K8tot = d.cin / 8; p.N = kBottleneck;
                         p.dst = bt; p.ldd = kBottleneck; p.dcoff = 0;
-                        p.dsum = bsum; p.dsq = bsq; p.dstride = kBottleneck;
+                        p.st = bst;
                         launch_gemm(e, cs, p, dim3(ns * pl.HWp / Cfg::BM, kBottleneck / Cfg::BN), K_C1, 2.0 * ns * pl.HW * d.cin * kBottleneck,
                                     ESZ(e) * ns * pl.HW * (d.cin + kBottleneck));
                     };
@@ -184,7 +183,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                         Fwd1x1WsArgs a{};
                         a.act = n1; a.pl = pl; a.K = d.cin;
                         a.wp = e->packed_u + e->pk_c1[b][i]; a.N = kBottleneck;
-                        a.dst = bt; a.ldd = kBottleneck; a.dsum = bsum; a.dsq = bsq; a.dstride = kBottleneck;
+                        a.dst = bt; a.ldd = kBottleneck; a.st = bst;
                         using WG_ = WsGeoT<np_of(fwd_op(0))>;                // one workgroup per 64-row tile covers all 128 output columns
                         const int nM = ns * pl.HWp / 64, nN = kBottleneck / WG_::BN;
                         a.tm = TileMap{nM, nN, 0};
@@ -204,7 +203,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                     Halo3x3FwdArgs a;
                     a.act = n2; a.pl = pl; a.C = kBottleneck;
                     a.dst = xs(b); a.ldd = Ct; a.dcoff = d.cin;
-                    a.dsum = xsum; a.dsq = xsq; a.dstride = Ct;
+                    a.st = xst;
                     a.wu = e->packed_u + e->pk_hf[b][i];
                     const double flops = 2.0 * ns * pl.HW * 9 * kBottleneck * kGrowth, bytes = ESZ(e) * ns * pl.HW * (kBottleneck + kGrowth);
                     if (halo_tile(pl, ns) == 8) {      // (traced launches, as the 16 x 16 ones: dev stamps with SMG_TRACE_KIND=2)
@@ -231,7 +230,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                         p.act = n2; p.ps = pl; p.po = pl; p.K = kBottleneck;
                         p.wp = e->packed_u + e->pk_g3f[b][i]; p.K8tot = 9 * kBottleneck / 8; p.N = kGrowth;
                         p.dst = xs(b); p.ldd = Ct; p.dcoff = d.cin;
-                        p.dsum = xsum; p.dsq = xsq; p.dstride = Ct;
+                        p.st = xst;
                         launch_gemm(e, cs, p, dim3(ns * pl.HWp / Cfg::BM, 1), K_C3, 2.0 * ns * pl.HW * 9 * kBottleneck * kGrowth,
                                     ESZ(e) * ns * pl.HW * (kBottleneck + kGrowth));
                     };
@@ -255,7 +254,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
                     p.act = tt; p.ps = pl; p.po = pn; p.K = Ct;
                     p.wp = e->packed_u + e->pk_t[b]; p.K8tot = Ct / 8; p.N = Ct / 2;
                     p.dst = xs(b + 1); p.ldd = Cn; p.dcoff = 0;
-                    p.dsum = st_off(fsum(e, e->st_X[b + 1]), Cn); p.dsq = st_off(fsq(e, e->st_X[b + 1]), Cn); p.dstride = Cn;
+                    p.st = stat_sink_fwd(e, e->st_X[b + 1], s0, 0);
                     launch_gemm(e, cs, p, dim3(ns * pn.HWp / Cfg::BM, (Ct / 2) / Cfg::BN), K_TRANS, 2.0 * ns * pn.HW * Ct * (Ct / 2),
                                 ESZ(e) * ns * ((double)pl.HW * Ct + (double)pn.HW * (Ct / 2)));
                 };
@@ -289,7 +288,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
         FeatArgs a;
         a.x4 = norm5_src(e, T, P); a.p4 = p4;
         a.pair_a = e->d_pair_a; a.pair_b = e->d_pair_b; a.F = e->F;
-        a.fsum = fsum(e, e->st_F); a.fsq = fsq(e, e->st_F); a.chunk = 64;
+        a.st = stat_sink_fwd(e, e->st_F, 0, 0); a.chunk = 64;
         PREC_DISPATCH(e, launch_kernel(e, feat_kernel<PREC>, dim3(2, NP, (p4.HW + 63) / 64), dim3(256), 0, st, K_OTHER, 0, 0, false, a));
     }
     {   // head norm0 + relu + conv0 (1x1, 2048 -> 64)
@@ -302,7 +301,7 @@ int do_forward(smg_engine* e, const smg_net* net, int trunk_id, int head_id, con
         p.act = th; p.ps = p4; p.po = p4; p.K = 2 * kFeat;
         p.wp = e->packed_u + e->pk_head0; p.K8tot = 2 * kFeat / 8; p.N = kHeadMid;
         p.dst = e->H1; p.ldd = kHeadMid; p.dcoff = 0;
-        p.dsum = fsum(e, e->st_H1); p.dsq = fsq(e, e->st_H1); p.dstride = kHeadMid;
+        p.st = stat_sink_fwd(e, e->st_H1, 0, 0);
         launch_gemm(e, st, p, dim3(NP * p4.HWp / Cfg::BM, 1), K_HEAD0, 2.0 * NP * p4.HW * 2 * kFeat * kHeadMid, 4.0 * NP * p4.HW * (2 * kFeat + kHeadMid));
             };
             PREC_DISPATCH(e, if (p4.HWp % 128 == 0) run(CfgP128x64{}, PTAG); else run(CfgP64x64{}, PTAG));

@@ -388,14 +388,10 @@ __device__ __forceinline__ f32x4 bloadv4(const void* ubase, unsigned bytes, unsi
     return __builtin_bit_cast(f32x4, bload_u4(ubase, bytes, voff, soff));
 }
 
-
-// The BACKWARD fp64 statistic arena (s1 / s2 sums) exists in kStatRep replicas kStatRepStride doubles apart: a producer's workgroup
-// adds to replica (workgroup index mod kStatRep) - hundreds of same-address fp64 atomics per (stream, channel) and launch serialise
-// in the L2 - and every reader sums the replicas (stat_get).  Same box, ms per step, replicas 1 / 2 / 4 / 8: headline (17 streams,
-// 160^2 planes) 21.64 / 21.71 / 21.74 / 21.88 - the readers pay; config 5's share (5 streams, 456^2 planes: 800-1600 row tiles per
-// stream) 27.2 / 25.7 / 25.4 / 25.6; config 3 27.2 / - / 27.2 / 27.5.  Two it is.  The forward arena stays single: its readers (every
-// workgroup's parameter prologue, 32-128 channels each) outnumber its writers (replicated eightfold: headline + 0.6 ms).
-// The stride is a compile-time constant so that no kernel needs another argument; the engine checks that its arena fits.
+// The BACKWARD fp64 statistic arena (s1 / s2 sums) exists in kStatRep replicas kStatRepStride doubles apart (a compile-time stride:
+// no kernel needs another argument; the engine checks that its arena fits): a producer's workgroup adds to a replica of its own
+// (stat_sink_add below, the one place that picks it) and every reader sums them (stat_get).  Same box, ms per step, replicas 1 / 2 /
+// 4 / 8: headline 21.64 / 21.71 / 21.74 / 21.88 - the readers pay; config 5 27.2 / 25.7 / 25.4 / 25.6; config 3 27.2 / - / 27.2 / 27.5.
 constexpr int kStatRep = 2;
 constexpr int64_t kStatRepStride = (int64_t)1 << 23;
 __device__ __forceinline__ double stat_get(const double* p, int64_t idx) {
@@ -414,8 +410,6 @@ __device__ __forceinline__ double fstat_get(const double* p, int64_t idx) {
     for (int r = 1; r < kFStatRep; ++r) v += p[idx + r * kStatRepStride];
     return v;
 }
-__device__ __forceinline__ int64_t fstat_rep() { return (int64_t)((blockIdx.x + blockIdx.y + blockIdx.z) % kFStatRep) * kStatRepStride; }
-__device__ __forceinline__ int64_t stat_rep() { return (int64_t)((blockIdx.x + blockIdx.y + blockIdx.z) % kStatRep) * kStatRepStride; }
 // The backward's per-layer kernels take (mean, invstd) of a forward activation from the fp32 table the forward finished (the very
 // floats bn_moments would produce from the fp64 sums) when the caller hands one over: two float loads instead of fp64 loads,
 // a divide and a square root per channel and workgroup - and no reader of the forward sums left on the per-layer path.
@@ -643,6 +637,36 @@ __device__ __forceinline__ GradCoef grad_src_coef(const GradSrc& s, int n, int c
     const float q1 = (float)(stat_get(s.s1, idx) * inv);
     const float q2 = (float)(stat_get(s.s2, idx) * inv);
     return GradCoef{(s.gamma ? s.gamma[ch] : 1.f) * invstd, q1, mean, invstd * q2};
+}
+
+// The pair of fp64 arrays a launch adds its per-(stream, channel) sums to (forward arena: sum x | sum x^2, backward: s1 | s2) - what
+// the next ActSrc / GradSrc reads.  THE descriptor of that destination: every kernel tail that adds to a statistic arena holds one,
+// and the host builds it in one place (engine.h: stat_sink_fwd / stat_sink_bwd), both pointers at the first channel of the launch's
+// first stream (stream and channel offsets folded in); sstride = doubles per stream.
+struct StatSink { double* a; double* b; int sstride; };
+enum { S_FWD = 0, S_BWD = 1 };      // the arena (kFStatRep / kStatRep replicas): a compile-time choice, as every site knows it
+// One finished total -> member q (0: a, 1: b) of (stream n, channel ch) in this workgroup's replica - the replica rule of both arenas
+// lives HERE alone; add2: both members from one thread.  The sinks travel BY VALUE: by reference (into the argument block, from
+// inside the 3x3 halo data gradient's nested lambdas) that kernel's 16-bit bounds-checked form went from 127 to 165 VGPRs, 4 to 3 waves.
+template <int ARENA> __device__ __forceinline__ void stat_sink_add(const StatSink s, int n, int ch, int q, double v) {
+    constexpr int kRep = ARENA == S_FWD ? kFStatRep : kStatRep;
+    atomicAdd((q ? s.b : s.a) + (int64_t)n * s.sstride + ch + (int64_t)((blockIdx.x + blockIdx.y + blockIdx.z) % kRep) * kStatRepStride, v);
+}
+template <int ARENA> __device__ __forceinline__ void stat_sink_add2(const StatSink s, int n, int ch, double va, double vb) {
+    stat_sink_add<ARENA>(s, n, ch, 0, va);
+    stat_sink_add<ARENA>(s, n, ch, 1, vb);
+}
+// A BatchNorm's affine gradients, dbeta | dgamma at the launch's first channel: the norm's slots of the gradient array (rep_stride
+// = 0) or a segment of the replicated scratch (engine.h: dbscr; rep_stride floats between its kDbRep replicas, this workgroup's =
+// index mod kDbRep).  Branch-free: replica index x stride.  The host builds it in engine.h: affine_sink / affine_sink_scr.
+constexpr int kDbRep = 8;
+struct AffineSink { float* dbeta; float* dgamma; int rep_stride; };
+__device__ __forceinline__ void affine_sink_add(const AffineSink s, int ch, int q, float v) {      // q = 0: dbeta, 1: dgamma
+    atomicAdd((q ? s.dgamma : s.dbeta) + (int64_t)(blockIdx.x % kDbRep) * s.rep_stride + ch, v);
+}
+__device__ __forceinline__ void affine_sink_add2(const AffineSink s, int ch, float db, float dg) {
+    affine_sink_add(s, ch, 0, db);
+    affine_sink_add(s, ch, 1, dg);
 }
 
 // XCD-aware tile order.  Workgroup b is observed to run on XCD b % 8 (MI355X_MICROARCH.md, used for
@@ -1282,7 +1306,7 @@ struct FwdConvP {
     const u32x4* wp; int K8tot;     // packed weight units [piece][K8tot][N] (pack_weights_kernel)
     int N;
     void* dst; int ldd; int dcoff;
-    double* dsum; double* dsq; int dstride;
+    StatSink st;                    // sum x | sum x^2 of the N output channels
     TileMap tm;
     static constexpr int kSwizzle = 1;
     // k-tiles of global loads in flight: the one-MFMA-tile-per-wave configurations of the small planes do 0.1 us of MFMAs per
@@ -1532,9 +1556,7 @@ struct FwdConvP {
         double tot[2];
         block_col_reduce<Cfg, 2, double>(v, reinterpret_cast<double*>(smem), tot);
         if (t < Cfg::BN && c.n0 + t < N) {
-            const int64_t si = (int64_t)c.n * dstride + dcoff + c.n0 + t;
-            atomicAdd(dsum + si + fstat_rep(), tot[0]);
-            atomicAdd(dsq + si + fstat_rep(), tot[1]);
+            stat_sink_add2<S_FWD>(st, c.n, c.n0 + t, tot[0], tot[1]);
         }
     }
 };
@@ -1575,8 +1597,7 @@ struct BwdDataP {
     int N;
     ActSrc m; Plane pm;             // the mask / xhat source: the activation whose BN + ReLU feeds this convolution's input, N channels
     void* dst; int ldd; int dcoff;
-    double* o1; double* o2; int ostride; int ocoff;
-    float* dbeta; float* dgamma; int rep_stride;      // rep_stride != 0: kDbRep replicas of a scratch (engine.h), this workgroup's = index mod 8
+    StatSink st; AffineSink aff;    // s1 | s2 of the N output channels, and the affine gradients of the norm behind them
     TileMap tm;
     static constexpr int kSwizzle = 1;
     static constexpr int kPrefetch = (Cfg::TM * Cfg::TN <= 2) ? kPdDgrad : kPdDgradBig;
@@ -1950,12 +1971,8 @@ struct BwdDataP {
         if (t < Cfg::BN && c.n0 + t < N) {
             const int col = c.n0 + t;
             const float wgt = (EMODE == E_STORE) ? 1.f : ep[4 * Cfg::BN + t];
-            const int64_t oi = (int64_t)c.n * ostride + ocoff + col;
-            atomicAdd(o1 + oi + stat_rep(), (double)(wgt * tot[0]));
-            atomicAdd(o2 + oi + stat_rep(), (double)(wgt * tot[1]));
-            const int64_t rep = (int64_t)(blockIdx.x & 7) * rep_stride;
-            atomicAdd(dbeta + rep + col, tot[0]);
-            atomicAdd(dgamma + rep + col, tot[1]);
+            stat_sink_add2<S_BWD>(st, c.n, col, (double)(wgt * tot[0]), (double)(wgt * tot[1]));
+            affine_sink_add2(aff, col, tot[0], tot[1]);
         }
 #ifdef SMG_TRACE_EPI
         if (etr) { etr[3] = smg_stamp(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); etr[4] = smg_stamp(); }
@@ -1977,7 +1994,7 @@ struct BwdDataP {
 // touches G' once.  The channels produced inside the group (needed by the very next layer) are still
 // done per layer by E_ACCUM on a narrow column range.
 //   per-segment sums  -> dbeta_i, dgamma_i          (sum dy_i, sum dy_i * xhat)
-//   running-sum sums  -> SA, SB of the block input  (sum_i gamma_i * those, = sums of the running sum)
+//   running-sum sums  -> s1, s2 of the block input  (sum_i gamma_i * those, = sums of the running sum)
 // ------------------------------------------------------------------------------------
 constexpr int GROUP_MAX = 4;
 struct GroupSeg {
@@ -1985,7 +2002,7 @@ struct GroupSeg {
     const void* g;                  // finished bottleneck gradient D2_i: units (operand kind 3, see kD2K8) or [n][HWp][KA] fp32 / bf16 by mode
     const u32x4* wp; int ldn;       // conv1 weight, packed data-gradient units [piece][KA/8][cin_i]
     const float* gamma; const float* beta;
-    float* dbeta; float* dgamma;
+    AffineSink aff;                 // norm1 of layer i, in the replicated scratch
 };
 
 template <class Cfg_, int PREC = 0>
@@ -2003,8 +2020,7 @@ struct BwdDataGroupP {
     int N;                                              // output channels [0, N)
     ActSrc m;                                           // block buffer X (mask / xhat source) and its statistics; gamma / beta live per segment
     void* dst; int ldd;                                 // G'
-    double* o1; double* o2; int ostride;                // SA / SB [n][C]
-    int rep_stride;                                     // replicas of the dbeta / dgamma scratch (see BwdDataP)
+    StatSink st;                                        // s1 / s2 of the block input [n][C]
     TileMap tm;
     static constexpr int kSwizzle = 1;
     // deep k-tiles with ONE tile of loads in flight (the staging registers of two half-as-deep tiles, half the barriers): mode 0
@@ -2359,16 +2375,10 @@ struct BwdDataGroupP {
 #endif
         if (t < Cfg::BN && c.n0 + t < N) {
             const int col = c.n0 + t;
-            const int64_t oi = (int64_t)c.n * ostride + col;
-            atomicAdd(o1 + oi + stat_rep(), (double)tot[0]);
-            atomicAdd(o2 + oi + stat_rep(), (double)tot[1]);
-            const int64_t rep = (int64_t)(blockIdx.x & 7) * rep_stride;
+            stat_sink_add2<S_BWD>(st, c.n, col, (double)tot[0], (double)tot[1]);
 #pragma unroll
             for (int z = 0; z < GROUP_MAX; ++z)
-                if (z < nseg) {
-                    atomicAdd(seg[z].dbeta + rep + col, tot[2 + 2 * z]);
-                    atomicAdd(seg[z].dgamma + rep + col, tot[3 + 2 * z]);
-                }
+                if (z < nseg) affine_sink_add2(seg[z].aff, col, tot[2 + 2 * z], tot[3 + 2 * z]);
         }
 #ifdef SMG_TRACE_EPI
         if (etr) { etr[3] = smg_stamp(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); etr[4] = smg_stamp(); }

@@ -84,7 +84,7 @@ struct Halo3x3FwdArgs {
     int C;                                          // input channels (128)
     const u32x4* wu;                                // weight units [chunk][piece][tap][k8][n] (PK_HF); operand kind 3: header unit in front
     void* dst; int ldd, dcoff;
-    double* dsum; double* dsq; int dstride;
+    StatSink st;                                    // sum x | sum x^2 of the 32 output channels
     int tiles_x, n_tiles, streams;                   // 1-D grid of banded_grid(n_tiles, streams) workgroups (banded_tile)
 };
 
@@ -461,7 +461,7 @@ static __global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : kHaloFwdWaves) void
     if (t < 64) {
         const int q = t >> 5, c = t & 31;
         const double tot = red[q * 128 + c] + red[q * 128 + 32 + c] + red[q * 128 + 64 + c] + red[q * 128 + 96 + c];
-        atomicAdd((q ? a.dsq : a.dsum) + (int64_t)n * a.dstride + a.dcoff + c + fstat_rep(), tot);
+        stat_sink_add<S_FWD>(a.st, n, c, q, tot);
     }
     if (trace) { trace[4] = smg_stamp(); trace[6] = __builtin_amdgcn_s_memrealtime(); }
 }
@@ -470,7 +470,7 @@ static __global__ __launch_bounds__(WS ? 512 : 256, WS ? 4 : kHaloFwdWaves) void
 // The finished gradient of a layer's 32 output channels, as the 3x3 backward kernels read it (GradSrc, gemm.cuh): either a dense
 // [n][HWp][32] array (x == nullptr), or the G' and X slices of the block buffers with the deferred BN backward
 // applied on load (what bn_bwd_apply_kernel would have written):
-//   g = invstd * ((G' - SA/n) - (x - mean) * invstd * SB/n)
+//   g = invstd * ((G' - s1/n) - (x - mean) * invstd * s2/n)
 // parameters a | q1 | mean | k of affine2() for the 32 channels -> gp[4][32]  (threads 0..31)
 __device__ __forceinline__ void grad_src_params(const GradSrc& s, int n, int hw, float* gp) {
     const int t = threadIdx.x;
@@ -489,7 +489,7 @@ struct Halo3x3DgradArgs {
     ActSrc m;                                        // raw bottleneck [n][HWp][C] (mask + xhat source) and its norm2 (table stored by the forward)
     int C;                                           // bottleneck channels (128)
     void* dst;                                       // dy [n][HWp][C]
-    double* o1; double* o2; int ostride;             // per-stream sums [n][C]
+    StatSink st;                                     // per-stream sums [n][C]
     int tiles_x;
     int cg_per_wg;                                   // output-channel groups (NCW chunks of 32) per workgroup; blockIdx.z picks the run
 };
@@ -907,7 +907,7 @@ static __global__ __launch_bounds__(256, TS == 8 ? 4 : 2) void conv3x3_halo_dgra
 #pragma unroll
                 for (int w = 0; w < G::WQ; ++w) tot += red[q * 128 + (j * G::WQ + w) * 32 + cc];
                 const int ch = ((cg0 + stage / (3 * SPR)) * NCW + j) * 32 + cc;
-                atomicAdd((q ? a.o2 : a.o1) + (int64_t)n * a.ostride + ch + stat_rep(), (double)tot);
+                stat_sink_add<S_BWD>(a.st, n, ch, q, (double)tot);
             }
 #ifndef SMG_TRACE_INIT
             if (trace && s3 == 0) trace[3] = __builtin_amdgcn_s_memtime();

@@ -25,7 +25,7 @@ struct Fwd1x1WsArgs {
     int K;
     const u32x4* wp; int N;                        // packed weight units [piece][K/8][N]; operand kind 3: header unit in front
     float* dst; int ldd;                           // raw output [n][HWp][ldd]
-    double* dsum; double* dsq; int dstride;        // per-(stream, channel) sum / sum of squares
+    StatSink st;                                   // per-(stream, channel) sum / sum of squares
     TileMap tm;                                    // XCD-aware order: the N tiles of one M tile are consecutive on one XCD
 };
 
@@ -237,7 +237,7 @@ static __global__ __launch_bounds__(512, 1) void conv1x1_fwd_ws_kernel(const Fwd
     if (t < 2 * G::BN) {
         const int q = t / G::BN, c = t % G::BN;
         const double tot = red[(q * 2) * G::BN + c] + red[(q * 2 + 1) * G::BN + c];
-        atomicAdd((q ? a.dsq : a.dsum) + (int64_t)n * a.dstride + n0 + c + fstat_rep(), tot);
+        stat_sink_add<S_FWD>(a.st, n, n0 + c, q, tot);
     }
 }
 
