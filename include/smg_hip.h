@@ -450,10 +450,21 @@ int smg_layout_head_range(int head_out, int head_id, int64_t* offset, int64_t* c
 
 /* ---- debug / test access (used by tests/ only) ------------------------------------ */
 /* Copies an internal buffer to host as float32 (16-bit storage is widened).  name: "img", "stem", "x1".."x4",
- * "feat", "g1".."g4", "bt<block>_<layer>", "fs_bt<block>_<layer>", "asc" ...; precision mode 0 only: "dy2" (raw 3x3 data
- * gradient of the dense layer the backward processed last), "gs_<block>_<layer>" / "d2_<block>_<layer>" (that layer's ring
- * slot: its finished output-slice gradient [streams][HWp][32] / bottleneck gradient [streams][HWp][128], the latter rebuilt from
- * its fp16 units and block scales - exactly the operand the consumers' MFMAs see).  Block / layer are 1-based.
+ * "feat", "g1".."g4", "bt<block>_<layer>", "asc" ...; "fs_bt<block>_<layer>" / "fs_x<block>": the forward's fp64 sums of a
+ * bottleneck / of a block buffer as raw doubles, [sum | sumsq][streams][128 | Ctot of the block] (the backward sums into another
+ * arena: they are intact at a debug_stop); "bs_x<block>": the BACKWARD's fp64 sums s1 | s2 of a block buffer, [s1 | s2][streams][Ctot],
+ * its replicas added up - behind a debug_stop the columns [cin, cin + 32) of the stopped layer hold what its GS was formed from.
+ * Behind a debug_stop backward, in every precision mode:
+ *   "gsnap"  G' of the stopped layer's block in front of that layer's 1x1 data gradients, in the mode's gradient storage;
+ *   "dy2"    the raw 3x3 data gradient of the stopped layer, [streams][HWp of its block][128]: mode 0 reads the DY2 buffer (the
+ *            layer the backward processed last, [streams][HWp of block 1][128] allocated); in modes 1 / 2 it lives in the layer's
+ *            ring slot, which the norm2 backward overwrites in place - the stop copies the slot between the two kernels;
+ *   "gs_<block>_<layer>" / "d2_<block>_<layer>"  that layer's ring slot: its finished output-slice gradient [streams][HWp][32] /
+ *            bottleneck gradient [streams][HWp][128].  Mode 0: d2 rebuilt from its fp16 units and block scales - exactly the
+ *            operand the consumers' MFMAs see.  Modes 1 / 2: plain bf16.  There gs_ holds the layer's gradient only where the
+ *            walk MATERIALISED it - calls of more than 4 streams; with fewer the 3x3 kernels apply the BN backward on load and the
+ *            slot keeps an earlier layer's words.  Rows [HW, HWp) of a slot are not written by the 16-bit kernels in either form.
+ * A snapshot taken in one precision mode is refused (-22) in another.  Block / layer are 1-based.
  * Returns the element count or a negative error. */
 int64_t smg_debug_read(smg_engine* e, const char* name, float* host_out, int64_t cap, void* stream);
 /* Geometry of the engine: fills H (per block spatial size), HWp (padded rows). */

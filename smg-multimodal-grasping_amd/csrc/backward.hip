@@ -249,6 +249,20 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
         e->have_fwd = false; e->bw_phase0_done = false; e->prof_stage = -1;
         return 0;
     };
+    // debug_stop only: a device-to-device copy of `elems` mode-typed elements of `src` on the chain stream, into a lazily grown debug buffer
+    // (its capacity counts floats, so it holds the elements of every mode; n: the elements of THIS snapshot); smg_debug_read widens it by
+    // the mode recorded here
+    auto dbg_snapshot = [&](float*& buf, int64_t& cap, int64_t& n, const float* src, int64_t elems) -> int {
+        if (cap < elems) {
+            if (buf) (void)hipFree(buf);
+            buf = nullptr; cap = 0;
+            HIP_OK(hipMalloc((void**)&buf, (size_t)elems * sizeof(float)));
+            cap = elems;
+        }
+        HIP_OK(hipMemcpyAsync(buf, src, (size_t)elems * (e->prec ? 2 : 4), hipMemcpyDeviceToDevice, st));
+        e->dbg_snap_prec = e->prec; n = elems;
+        return 0;
+    };
     // pool0's backward and conv0's weight gradient at pooled resolution (elem.cuh: stem_tail_kernel; mode 0, one-channel stem) - like the
     // partial-tile form of the 1x1 weight gradient for calls of more than four streams or under "deterministic": a call of a few
     // streams is launch-bound on the side stream, where the moments and the combine are three launches more than the pair they
@@ -337,6 +351,9 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
                 if (!e->generic3x3) a.aff = affine_sink(Gr, d.n2);      // the halo dgrad leaves these to us
                 launch_kernel(e, bn_bwd_apply_split_kernel, dim3(pl.HWp / kScaleBlock, NS), dim3(256), 0, st, K_OTHER, 0, 4.0 * NS * pl.HW * 3 * kBottleneck, false, a);
             } else {   // 16-bit modes: norm2 backward applied once, in place: D2 <- gamma2*invstd*(dy - s1/n - xhat*s2/n)
+                if (e->dbg_stop == b * 100 + i) {      // tests: the raw 3x3 data gradient, which the apply is about to overwrite ("dy2")
+                    if (int rc = dbg_snapshot(e->dbg_dy2, e->dbg_dy2_floats, e->dbg_dy2_n, D2b, (int64_t)NS * pl.HWp * kBottleneck)) return rc;
+                }
                 BnBwdApplyArgs a{};
                 a.src = dy2; a.pl = pl; a.C = kBottleneck; a.out = D2b; a.ldo = kBottleneck;
                 if (!e->generic3x3) a.aff = affine_sink(Gr, d.n2);      // the halo dgrad leaves these to us
@@ -352,15 +369,8 @@ int do_backward(smg_engine* e, const smg_net* net, const float* dq, hipStream_t 
             // the very next layer - are accumulated per layer; everything below the group's lowest layer is done
             // once for the whole group by BwdDataGroupP (gemm.cuh), which touches G' and x once instead of once
             // per layer.
-            if (e->dbg_stop == b * 100 + i && e->prec == 0) {      // tests: G' of the block in front of this layer's 1x1 data gradients
-                const int64_t nf = (int64_t)NS * pl.HWp * Ct;
-                if (e->dbg_gsnap_floats < nf) {
-                    if (e->dbg_gsnap) (void)hipFree(e->dbg_gsnap);
-                    e->dbg_gsnap = nullptr; e->dbg_gsnap_floats = 0;
-                    HIP_OK(hipMalloc((void**)&e->dbg_gsnap, (size_t)nf * sizeof(float)));
-                    e->dbg_gsnap_floats = nf;
-                }
-                HIP_OK(hipMemcpyAsync(e->dbg_gsnap, e->G[b], (size_t)nf * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if (e->dbg_stop == b * 100 + i) {      // tests: G' of the block in front of this layer's 1x1 data gradients, in the mode's element size
+                if (int rc = dbg_snapshot(e->dbg_gsnap, e->dbg_gsnap_floats, e->dbg_gsnap_n, e->G[b], (int64_t)NS * pl.HWp * Ct)) return rc;
             }
             const int L = (int)T.layers[b].size();
             const int g_lo = i - ((L - 1 - i) % kGroup == kGroup - 1 ? 0 : std::min(i, kGroup - 1 - (L - 1 - i) % kGroup));

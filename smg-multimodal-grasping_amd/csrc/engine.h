@@ -181,7 +181,11 @@ struct smg_engine {
     int dbg_stop = -1;         // smg_engine_set_option("debug_stop", block * 100 + layer) (0-based): the backward returns behind that dense layer's
                                // launches (block * 100 + 50: in front of the block's first layer) - the GEMM-level tests read the ring
                                // slots, DY2 and G' at that point (smg_debug_read); -1 = off
-    float* dbg_gsnap = nullptr; int64_t dbg_gsnap_floats = 0;      // ... and G' of the block as it was in front of that layer's 1x1 data gradients ("gsnap")
+    float* dbg_gsnap = nullptr; int64_t dbg_gsnap_floats = 0; int64_t dbg_gsnap_n = 0;      // ... and G' of the block as it was in front of that layer's 1x1 data gradients ("gsnap":
+                               // dbg_gsnap_n ELEMENTS of the mode it was taken in, dbg_snap_prec; the allocation holds dbg_gsnap_floats floats)
+    float* dbg_dy2 = nullptr; int64_t dbg_dy2_floats = 0; int64_t dbg_dy2_n = 0;      // modes 1 / 2: the stopped layer's ring slot between its 3x3 data gradient
+                               // and the in-place norm2 apply ("dy2": dbg_dy2_n bf16 elements, [streams][HWp of the block][128])
+    int dbg_snap_prec = -1;    // the precision mode of the debug_stop backward that took the two snapshots
     // profiling
     bool prof = false; std::vector<ProfRec> recs; std::vector<hipEvent_t> ev_pool;
     // totals per kind in slot 0, and the share of dense block b (kernels issued inside its layer loops) in slot 1 + b

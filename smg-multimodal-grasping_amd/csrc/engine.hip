@@ -424,6 +424,7 @@ void smg_engine_destroy(smg_engine* e) {
                     e->d_stage, e->scene_val, e->scene_idx, e->scene_lpart, e->scene_gpart, e->scene_cnt, e->mom_part, e->mom};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->dbg_gsnap) (void)hipFree(e->dbg_gsnap);
+    if (e->dbg_dy2) (void)hipFree(e->dbg_dy2);
     step_graph_drop(e);
     if (e->h_stage_g) (void)hipHostFree(e->h_stage_g);
     if (e->ev_graph) (void)hipEventDestroy(e->ev_graph);
@@ -963,6 +964,24 @@ int smg_adam_step(float* params, const float* grads, float* m, float* v, int64_t
     return 0;
 }
 
+// n 16-bit words of a mode-typed buffer widened to fp32: bf16 (the upper half of the float), or fp16 (mode 2's activations)
+static void widen16(const unsigned short* raw, int64_t n, bool f16, float* out) {
+    for (int64_t i = 0; i < n; ++i) {
+        unsigned u;
+        const unsigned h = raw[(size_t)i];
+        if (!f16) u = h << 16;
+        else {
+            const unsigned sign = (h & 0x8000u) << 16, ex = (h >> 10) & 31u, man = h & 1023u;
+            if (ex == 0) {
+                float v = (float)man * (1.0f / 16777216.0f);        // subnormal: man * 2^-24
+                std::memcpy(&u, &v, 4); u |= sign;
+            } else if (ex == 31) u = sign | 0x7F800000u | (man << 13);
+            else u = sign | ((ex + 112u) << 23) | (man << 13);
+        }
+        std::memcpy(&out[i], &u, 4);
+    }
+}
+
 int64_t smg_debug_read(smg_engine* e, const char* name, float* host_out, int64_t cap, void* stream) {
     if (!e || !name) return fail(-22, "NULL argument");
     const int NS = e->max_streams, NP = e->max_pairs;
@@ -994,10 +1013,44 @@ int64_t smg_debug_read(smg_engine* e, const char* name, float* host_out, int64_t
         if (std::sscanf(name, "bt%d_%d", &b, &i) != 2 || b < 1 || b > 4 || i < 1 || i > kBlockLayers[b - 1]) return fail(-22, "bad bt name");
         src = el(e, e->Bt, e->bt_off[b - 1][i - 1]); n = (int64_t)NS * e->p_blk[b - 1].HWp * kBottleneck;      // bt_off counts ELEMENTS of the mode
     } else if (s == "gsnap") {    // G' of the debug_stop layer's block in front of that layer's 1x1 data gradients (first f_streams streams)
-        src = e->dbg_gsnap; n = e->dbg_gsnap_floats;
+        src = e->dbg_gsnap; n = e->dbg_gsnap_n;
         if (!src) return fail(-22, "gsnap: no debug_stop backward has run");
-    } else if (s == "dy2") {      // precision mode 0: the raw 3x3 data gradient of the dense layer the backward processed last, [streams][HWp of its block][128]
+        if (e->dbg_snap_prec != e->prec) return fail(-22, "gsnap: taken in another precision mode");
+    } else if (s == "dy2" && e->prec == 0) {      // the raw 3x3 data gradient of the dense layer the backward processed last, [streams][HWp of its block][128]
         src = e->DY2; n = (int64_t)NS * e->p_blk[0].HWp * kBottleneck;
+    } else if (s == "dy2") {      // modes 1 / 2: the debug_stop layer's ring slot as the 3x3 data gradient left it, in front of the in-place norm2 apply (bf16)
+        src = e->dbg_dy2; n = e->dbg_dy2_n;
+        if (!src) return fail(-22, "dy2: no debug_stop backward has run in a 16-bit mode");
+        if (e->dbg_snap_prec != e->prec) return fail(-22, "dy2: taken in another precision mode");
+    } else if (s.size() == 5 && s.substr(0, 4) == "fs_x") {   // "fs_x<block>": the fp64 forward sums of a block buffer, raw doubles [sum | sumsq][streams][Ctot] in the float buffer
+        const int b = s[4] - '1';                            // (the backward writes the other arena, b1 / b2: intact at a backward stop)
+        if (b < 0 || b > 3) return fail(-22, "bad fs_x name");
+        const int64_t nd = (int64_t)NS * kBlockCtot[b];
+        n = 4 * nd;                                          // floats = 2 x doubles
+        if (!host_out) return n;
+        if (cap < n) return fail(-22, "fs_x: buffer too small");
+        HIP_OK(hipSetDevice(e->device));
+        HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+        HIP_OK(hipMemcpy(host_out, fsum(e, e->st_X[b]), (size_t)nd * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(host_out + 2 * nd, fsq(e, e->st_X[b]), (size_t)nd * sizeof(double), hipMemcpyDeviceToHost));
+        return n;
+    } else if (s.size() == 5 && s.substr(0, 4) == "bs_x") {   // "bs_x<block>": the fp64 BACKWARD sums of a block buffer, raw doubles [s1 | s2][streams][Ctot], the
+        const int b = s[4] - '1';                            // kStatRep replicas added up as stat_get adds them (gemm.cuh)
+        if (b < 0 || b > 3) return fail(-22, "bad bs_x name");
+        const int64_t nd = (int64_t)NS * kBlockCtot[b];
+        n = 4 * nd;                                          // floats = 2 x doubles
+        if (!host_out) return n;
+        if (cap < n) return fail(-22, "bs_x: buffer too small");
+        HIP_OK(hipSetDevice(e->device));
+        HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+        std::vector<double> tot((size_t)2 * nd, 0.0), rep((size_t)nd);
+        for (int q = 0; q < 2; ++q)
+            for (int r = 0; r < kStatRep; ++r) {
+                HIP_OK(hipMemcpy(rep.data(), (q ? b2(e, e->st_X[b]) : b1(e, e->st_X[b])) + (int64_t)r * kStatRepStride, (size_t)nd * sizeof(double), hipMemcpyDeviceToHost));
+                for (int64_t k = 0; k < nd; ++k) tot[(size_t)(q * nd + k)] += rep[(size_t)k];
+            }
+        std::memcpy(host_out, tot.data(), tot.size() * sizeof(double));
+        return n;
     } else if (s.size() >= 5 && (s.substr(0, 3) == "gs_" || s.substr(0, 3) == "d2_")) {
         // "gs_<block>_<layer>" / "d2_<block>_<layer>" (1-based): the ring slot of that dense layer's finished gradients - valid until kRing
         // further layers have run (debug_stop).  d2 in precision mode 0: rebuilt from the units, (h + l) * the block's inverse scale.
@@ -1011,9 +1064,14 @@ int64_t smg_debug_read(smg_engine* e, const char* name, float* host_out, int64_t
         if (!host_out) return n;
         const int ns_out = (int)std::min<int64_t>(NS, cap / per_stream);      // a prefix of whole streams
         n = ns_out * per_stream;
-        if (e->prec != 0) return fail(-22, "ring buffer debug reads exist in precision mode 0 only");
         HIP_OK(hipSetDevice(e->device));
         HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+        if (e->prec != 0) {       // modes 1 / 2: plain [streams][HWp][32 | 128] in bf16 (GS only where it was materialised: calls of more than 4 streams)
+            std::vector<unsigned short> raw((size_t)n);
+            HIP_OK(hipMemcpy(raw.data(), gs ? e->GS[slot] : e->D2[slot], raw.size() * sizeof(unsigned short), hipMemcpyDeviceToHost));
+            widen16(raw.data(), n, false, host_out);
+            return n;
+        }
         if (gs || kSplitOp != 3) {
             HIP_OK(hipMemcpy(host_out, gs ? e->GS[slot] : e->D2[slot], n * sizeof(float), hipMemcpyDeviceToHost));
             return n;
@@ -1054,28 +1112,15 @@ int64_t smg_debug_read(smg_engine* e, const char* name, float* host_out, int64_t
     if (cap < n) n = cap;
     HIP_OK(hipSetDevice(e->device));
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    const bool typed = e->prec != 0 && (s[0] == 'x' || s[0] == 'g' || s.substr(0, 2) == "bt");   // 16-bit storage in modes 1 / 2
+    const bool typed = e->prec != 0 && (s[0] == 'x' || s[0] == 'g' || s.substr(0, 2) == "bt" || s == "dy2");   // 16-bit storage in modes 1 / 2 ("gsnap" and "dy2": gradients)
     if (!typed) {
         HIP_OK(hipMemcpy(host_out, src, n * sizeof(float), hipMemcpyDeviceToHost));
         return n;
     }
     std::vector<unsigned short> raw((size_t)n);
     HIP_OK(hipMemcpy(raw.data(), src, n * sizeof(unsigned short), hipMemcpyDeviceToHost));
-    const bool f16 = e->prec == 2 && s[0] != 'g';               // activations of mode 2; gradients are bf16 in both 16-bit modes
-    for (int64_t i = 0; i < n; ++i) {
-        unsigned u;
-        const unsigned h = raw[(size_t)i];
-        if (!f16) u = h << 16;
-        else {
-            const unsigned sign = (h & 0x8000u) << 16, ex = (h >> 10) & 31u, man = h & 1023u;
-            if (ex == 0) {
-                float v = (float)man * (1.0f / 16777216.0f);        // subnormal: man * 2^-24
-                std::memcpy(&u, &v, 4); u |= sign;
-            } else if (ex == 31) u = sign | 0x7F800000u | (man << 13);
-            else u = sign | ((ex + 112u) << 23) | (man << 13);
-        }
-        std::memcpy(&host_out[i], &u, 4);
-    }
+    const bool f16 = e->prec == 2 && s[0] != 'g' && s != "dy2";               // activations of mode 2; gradients are bf16 in both 16-bit modes
+    widen16(raw.data(), n, f16, host_out);
     return n;
 }
 

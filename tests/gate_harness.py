@@ -20,6 +20,10 @@ SCENES = {"S640x6": dict(seed=0, size=224, S=640, rots=[0, 3, 7, 10, 13], dq=[[1
           "S672x3": dict(seed=8, size=236, S=672, rots=[2, 11], dq=[[1.0, -0.5, 0.25, -2.0], [-0.75, 1.5, -1e-3, 0.4]]),
           "S640x2": dict(seed=0, size=224, S=640, rots=[3], dq=[[1.0]]),                                                    # the single-sample step
           "S640x17": dict(seed=0, size=224, S=640, rots=list(range(16)), dq=[[_DQ[j % 8]] for j in range(16)])}            # forward chains of 8 and 9
+# the dense-layer stops of the 16-bit backward gates (test_gpu_storage_gates.test_backward_layer; test_cpu_storage_ref shows their keep-masks'
+# 1 % cap on the CPU), (block, layer) 1-based by geometry: every block, a top of a group (per-layer form only), a bottom of a four-layer
+# group (nseg = 4), a block's first layer, block 4's last layer
+BWD_LAYERS16 = {"S640": [(1, 3), (2, 6), (3, 21), (4, 1), (4, 16)], "S672": [(1, 6), (2, 9), (3, 24), (4, 13), (4, 16)]}
 # by S: H and HWp of the stem plane and of blocks 1-4 (eng.H[1:6] / eng.HWp[1:6]); HWp % 128 picks the 128-row or the 64-row configuration.
 # Plane indices everywhere: 0 = input, 1 = stem, 2..5 = blocks 1..4 (a dense layer of `block` lives on plane 1 + block).
 GEOMETRY = {640: ([320, 160, 80, 40, 20], [102400, 25600, 6400, 1600, 448]),

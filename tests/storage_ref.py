@@ -28,7 +28,9 @@ and invstd differ from the reference's by what rounding did to the plane.  store
 storage ulp per element, hence |delta mean| <= mean(h) and |delta var| <= 2 mean(|x - mean| h) + mean(h^2).  The element-wise gates
 add it to their bound (bn_store_slack, xhat_sum_slack), the keep-mask widens by it (keep16 / keep_s); no factor is widened.  Where the
 values before the store follow from an fp32 buffer - pool0's channels of x1, from the stem plane - the engine's statistics are
-recomputed instead of bounded (plane_stats / x1_stats): the product gates then need no slack."""
+recomputed instead of bounded (plane_stats / x1_stats): the product gates then need no slack.  The backward gates of the dense layers
+go one step further (second half of this file): smg_debug_read hands out the engine's forward sums (fs_bt, fs_x), and the reference
+takes the engine's OWN statistics (engine_stats)."""
 import numpy as np
 
 import dense_ref as dr
@@ -219,3 +221,202 @@ def keep_s(v, g, b, S):
     """keep16 with the statistics S"""
     sc = np.abs(np.asarray(v, dtype=np.float64) - S.mean) * S.inv * np.abs(g) + np.abs(b)
     return np.abs(bn_pre_s(v, g, b, S)) > 1e-5 * sc + slack_s(v, g, S)
+
+
+# ---- the dense layers' BACKWARD in the 16-bit modes ----------------------------------------------------------------------------------------
+# In modes 1 / 2 the backward of a dense layer runs (backward.hip, `split16` false): conv3x3_halo_dgrad_kernel<16 | 8, PREC, edge> on the
+# MATERIALISED gs_ (calls of more than 4 streams: gs_materialised = NS > 4; bn_bwd_apply_kernel<PREC> at C = 32 wrote it) or with the BN
+# backward applied ON LOAD (affine2 of the G' / x slices, then pack_unit<OP>: halo.cuh s_store), bn_bwd_apply_kernel<PREC> at C = 128 IN
+# PLACE on the ring slot that holds the raw 3x3 data gradient, conv3x3_halo_wgrad_kernel, BwdWeightP<.., W_ONE>, and the two
+# read-modify-write 1x1 data gradients BwdDataP<.., E_ACCUM> / BwdDataGroupP.  Where each rounds:
+#   * gradients are bf16 in both modes (engine.h GrdT<1 | 2> = e_bf16) and every backward product takes bf16 operands (bwd_op_plain);
+#   * the 3x3 data gradient: operand GS as stored (bf16: no further rounding) or the fp32 affine2 rounded once (pack_unit<OP>), the PK_HD
+#     weights rounded to bf16 (pack_weights_kernel), fp32 accumulators, the ReLU mask from the forward's fp32 table (bn1(x, mean, sc, be) >
+#     0), one rounding by stq<GT> (halo.cuh epilogue: `dyv = in && bn1(..) > 0 ? acc : 0`, `s1 += dyv`, then stq<GT>: the sums s1 / s2 of
+#     norm2 see the fp32 dyv, the slot its bf16 rounding);
+#   * the norm2 backward in place: affine2 of the stored dy2 and the stored bottleneck in fp32, rounded once (elem.cuh bn_bwd_apply_kernel:
+#     pack_unit<1>), rows < HW only (`r < a.pl.HW`);
+#   * the 1x1 data gradients: D2 as stored, the PK_D1 pack rounded to bf16, fp32 accumulators, mask and gamma in fp32, `gold + gam * dy`
+#     (BwdDataP::epilogue) or `gold + run` with run the fp32 sum over the group's segments (BwdDataGroupP::epilogue), ONE rounding to bf16
+#     (st1<GT> / store_acc_rows<GT>), rows p < pa.HW only;
+#   * the weight gradients: both operands rounded to bf16 when staged (GS / D2 are bf16 already), fp32 reduction.
+# The statistics: the backward's per-layer kernels read (mean, invstd) of x<b> and of the bottleneck from the fp32 table the forward
+# finished - "the very floats bn_moments would produce from the fp64 sums" (gemm.cuh StatTab): mean = (float)(sum / n), invstd =
+# (float)(1 / sqrt(var + eps)).  debug_read("fs_x<b>") / ("fs_bt<b>_<l>") hand out those sums, so the reference takes the engine's OWN
+# statistics (engine_stats) and the keep-mask's margin is the table's fp32 rounding and nothing more.
+
+# bn_bwd_apply_kernel<PREC> at C = 128 behind the halo data gradient, against bn_bwd_sum_mag_s; ts = the halo tile (16 or 8): the halo
+# epilogue sums s1 / s2 in fp32 over the ts * ts pixels of its tile (per lane, then shfl, then across the waves: ts^2 - 1 adds whatever
+# the tree), then fp64 atomics.  As stage_ref.K_DY5_USER counts the same affine2 with 64-row tile sums:
+#   a = gamma * invstd: invstd rounded (1), the product (1)                                              2
+#   q1 = (float)(s1 / HW): the cast (1) + the tile's ts^2 - 1 fp32 adds                                  ts^2
+#   x - mean: mean rounded (1), the subtraction (1)                                                      2
+#   k = invstd * q2: invstd (1), the cast (1), the product (1), ts^2 - 1 adds, and each term
+#       dyv * ((x - mean) * invstd) rounds 5 times (mean, subtraction, invstd, two products)             ts^2 + 7
+#   g - q1 (1), the fused multiply-add (1), the product with a (1)                                       3
+def k_d2_apply(ts):
+    return 2 + ts * ts + 2 + (ts * ts + 7) + 3
+
+
+# norm2's dbeta / dgamma in the 16-bit modes: bn_bwd_apply_kernel adds (float)s1[n] / (float)s2[n] per stream with one fp32 atomic each
+# (elem.cuh: affine_sink_add2 under blockIdx.x == 0): per term the tile's ts^2 - 1 fp32 adds, for dgamma the 5 roundings of
+# dyv * ((x - mean) * invstd); then the cast (1) and NS - 1 atomic adds.  Against sum |term|.
+def k_affine2(ts, ns, gamma):
+    return (ts * ts - 1) + (5 if gamma else 0) + 1 + (ns - 1)
+
+
+# bn_bwd_apply_kernel<PREC> at C = 32 (the MATERIALISED GS) for block 4's LAST layer, against bn_bwd_sum_mag_s of the G' / x slices.  Its
+# slice of G' has been stored exactly ONCE when the layer runs - by norm5_bwd_kernel (elem.cuh), which also summed s1 / s2 - so what the
+# store did to the sums is derivable (sums_before_store_slack with h = half a bf16 ulp of gsnap).  Every lower layer's slice has been
+# read-modify-written by the layers above it, each store rounding a running value that no buffer keeps: no slack can be derived there, and
+# those layers' GS is gated with the engine's own sums instead (gs_from_sums, above).  norm5_bwd_kernel: a thread sums dd over its pixels in fp32 (<= 80
+# terms: 5 chunks x 16 pixels on a single-user stream, users / 4 x 16 + 2 on the shared one: stage_ref.k_sums5), multiplies by gamma5,
+# fp64 atomics from there; the stored value is sum over the users of fl(gamma5 * dd) (1 + users roundings).
+#   a = invstd (the table's rounding)                                                                    1
+#   q1 = (float)(s1 / HW): the cast (1), gamma5 * s1 (1), 79 adds, the stored terms' own 1 + users       82 + users
+#   x - mean: mean rounded (1), the subtraction (1)                                                      2
+#   k = invstd * q2: invstd, the cast, the product (3), gamma5 * s2 (1), 79 adds, 1 + users, and each
+#       term dd * ((x - mean5) * inv5) rounds 5 times                                                    89 + users
+#   g - q1 (1), the fused multiply-add (1), the product with a (1)                                       3
+def k_gs_top(users):
+    return 1 + (82 + users) + 2 + (89 + users) + 3
+
+
+# bn_bwd_apply_kernel<PREC> at C = 32 (the MATERIALISED GS) at ANY layer, with the sums s1 / s2 the kernel read handed in (debug_read
+# "bs_x<b>": the backward arena's fp64 sums of the block buffer; the stopped layer's own 1x1 data gradients add to columns [0, cin) only,
+# so those of its slice [cin, cin + 32) are what the apply read).  grad_src_coef / bnb1 (gemm.cuh), as dense_ref.K_GS_LOAD counts them:
+#   a = 1.f * invstd (the table's rounding)                 1
+#   q1 = (float)(s1 / HW): the cast                         1
+#   mean (the table's rounding), x - mean                   2
+#   k = invstd * (float)(s2 / HW): invstd, cast, product    3
+#   g - q1, the fused multiply-add, the product with a      3
+# against |a| (|g| + |q1| + (|x| + |mean|) |k|).  No slack: nothing of the reference is taken from a rounded buffer's sums.
+K_GS_APPLY = 1 + 1 + 2 + 3 + 3
+
+
+def gs_from_sums(gp, x, S, bs, HW):
+    """gp, x [HW][32]: the stored G' / x slices, S their forward statistics (engine_stats), bs [2][32] the engine's s1 | s2 of the slice:
+    (fp64 GS = invstd * ((g - s1 / HW) - (x - mean) * invstd * s2 / HW), the magnitudes K_GS_APPLY counts against)"""
+    g, x = np.asarray(gp, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    q1, k = np.asarray(bs[0], dtype=np.float64) / HW, S.inv * np.asarray(bs[1], dtype=np.float64) / HW
+    return S.inv * ((g - q1) - (x - S.mean) * k), S.inv * (np.abs(g) + np.abs(q1) + (np.abs(x) + np.abs(S.mean)) * np.abs(k))
+
+
+def engine_stats(fs, HW):
+    """fs [2][C]: the engine's fp64 sums (sum | sumsq) of one stream's plane -> PlaneStats with mean and invstd as bn_moments forms
+    them in fp64 (gemm.cuh), and as slack the one fp32 rounding of each on their way into the table"""
+    mean = np.asarray(fs[0], dtype=np.float64) / HW
+    inv = 1.0 / np.sqrt(np.maximum(np.asarray(fs[1], dtype=np.float64) / HW - mean * mean, 0.0) + sr.EPS)
+    return PlaneStats(mean, inv, np.abs(mean) * sr.U, np.full(mean.shape, sr.U))
+
+
+def plane_sums(v):
+    """[sum | sumsq][C] in fp64 of a plane: what fs_* would hold had the producer summed the stored values"""
+    v = np.asarray(v, dtype=np.float64)
+    return np.stack([v.sum(0), (v * v).sum(0)])
+
+
+def bn_bwd_terms_s(dy, x, S, gamma=None):
+    """stage_ref.bn_bwd_terms with the statistics S of x: (a, q1, mean, k)"""
+    dy = np.asarray(dy, dtype=np.float64)
+    xh = (np.asarray(x, dtype=np.float64) - S.mean) * S.inv
+    a = S.inv if gamma is None else S.inv * np.asarray(gamma, dtype=np.float64)
+    return a, dy.mean(0), S.mean, S.inv * (dy * xh).mean(0)
+
+
+def bn_bwd_s(dy, x, S, gamma=None):
+    a, q1, mean, k = bn_bwd_terms_s(dy, x, S, gamma)
+    return a * ((np.asarray(dy, dtype=np.float64) - q1) - (np.asarray(x, dtype=np.float64) - mean) * k)
+
+
+def bn_bwd_sum_mag_s(dy, x, S, gamma=None):
+    """stage_ref.bn_bwd_sum_mag with the statistics S"""
+    dy = np.abs(np.asarray(dy, dtype=np.float64))
+    x = np.asarray(x, dtype=np.float64)
+    a = S.inv if gamma is None else np.abs(S.inv * np.asarray(gamma, dtype=np.float64))
+    return a * (dy + dy.mean(0) + (np.abs(x) + np.abs(S.mean)) * S.inv * (dy * np.abs((x - S.mean) * S.inv)).mean(0))
+
+
+def bn_bwd32_s(dy, x, S, gamma=None, tile_sums=True):
+    """stage_ref.bn_bwd32 with the statistics S (affine2 in fp32, the coefficients rounded once; q1 and k from engine-style tile sums)"""
+    a, q1, mean, k = bn_bwd_terms_s(dy, x, S, gamma)
+    dy, x = np.asarray(dy, dtype=f32), np.asarray(x, dtype=f32)
+    if tile_sums:
+        xh = ((x - mean.astype(f32)) * S.inv.astype(f32)).astype(f32)
+        q1 = sr.tile_sum32(dy) / len(dy)
+        k = S.inv * (sr.tile_sum32((dy * xh).astype(f32)) / len(dy))
+    a, q1, mean, k = a.astype(f32), q1.astype(f32), mean.astype(f32), k.astype(f32)
+    return (a * ((dy - q1) - (x - mean) * k).astype(f32)).astype(f32)
+
+
+def gs_on_load16(gp, x, S):
+    """The GS operand of the 3x3 kernels where it is NOT materialised (calls of <= 4 streams): (the fp64 GS, the fp32 affine2 of the G' /
+    x slices with engine-style tile sums rounded once to the backward operand type bf16 - halo.cuh s_store: pack_unit<OP>(affine2(..)))"""
+    return bn_bwd_s(gp, x, S), rnd(bn_bwd32_s(gp, x, S), "bf16")
+
+
+def conv2_dgrad_chain16(gs32, H, W, w2, on, pix):
+    """the storage chain of the 3x3 data gradient on the pixels `pix`: GS (bf16 already, or gs_on_load16's), the PK_HD weights rounded to
+    bf16, fp32 accumulation, the ReLU mask `on` [HW][128], one rounding to bf16 (stq<GT>)"""
+    ch = _fp32_chain(dr.im2col(rnd(gs32, "bf16"), H, W, pix, flip=True), rnd(dr.w2_bwd_mat(w2).astype(f32), "bf16"))
+    return rnd((ch * on[pix]).astype(f32), "bf16")
+
+
+def sums_before_store_slack(dy, x, S, gamma=None):
+    """What bn_bwd_s moves by, per element, when the sums s1 = sum dy and s2 = sum dy * xhat were taken from the fp32 values IN FRONT of
+    dy's 16-bit store (halo.cuh epilogue: `s1 += dyv` before stq<GT>): every stored element lies within h = half a bf16 ulp of what was
+    summed, so |delta q1| <= mean(h), |delta q2| <= mean(h |xhat|), and the result a * ((dy - q1) - xhat * q2) moves by at most
+    |a| * (mean(h) + |xhat| * mean(h |xhat|)).  Also returns the two sums' own slack (per channel): (element slack, sum h, sum h |xhat|)."""
+    h = half_ulp(dy, "bf16")
+    xh = np.abs((np.asarray(x, dtype=np.float64) - S.mean) * S.inv)
+    a = np.abs(S.inv if gamma is None else S.inv * np.asarray(gamma, dtype=np.float64))
+    return a * (h.mean(0) + xh * (h * xh).mean(0)), h.sum(0), (h * xh).sum(0)
+
+
+def norm2_inplace(dy2, bt, g2, S, ts):
+    """bn_bwd_apply_kernel<PREC> at C = 128, in place: (fp64 D2 from the STORED dy2 and the stored bottleneck with the engine's
+    statistics S, its bound: k_d2_apply(ts) fp32 roundings of bn_bwd_sum_mag_s + sums_before_store_slack, + half a bf16 ulp)"""
+    ref = bn_bwd_s(dy2, bt, S, g2)
+    return ref, stored_bound(ref, k_d2_apply(ts), bn_bwd_sum_mag_s(dy2, bt, S, g2), "bf16", sums_before_store_slack(dy2, bt, S, g2)[0])
+
+
+def conv1_dgrad16(G0, X, S, params, d2s, c0, c1, take=None, chain=True):
+    """dense_ref.conv1_dgrad for the 16-bit modes, one stream: S = the engine's statistics of the block buffer X (engine_stats of
+    fs_x<b>), G0 = the widened gsnap.  The chain: D2 as stored (bf16), the PK_D1 weights rounded to bf16, fp32 accumulation, mask and
+    gamma in fp32, the segments summed in fp32 (BwdDataGroupP: `run`), added to G0, ONE rounding to bf16.  sum |term| includes |G0|: the
+    stored SUM is what gets rounded.  Returns (reference, sum |term|, chain or None, keep)."""
+    take = slice(None) if take is None else take
+    Sc = S.cols(slice(c0, c1))
+    x = np.asarray(X, dtype=np.float64)[take, c0:c1]
+    ref = np.asarray(G0, dtype=np.float64)[take, c0:c1]
+    mag = np.abs(ref) + 1e-300
+    run = np.zeros(ref.shape, dtype=f32)
+    keep = np.ones(ref.shape, dtype=bool)
+    for (g1, b1, w1), d2 in zip(params, d2s):
+        g1, b1, w1 = g1[c0:c1], b1[c0:c1], w1[:, c0:c1]
+        d2 = np.asarray(d2)[take]
+        keep &= keep_s(x, g1, b1, Sc)
+        m = bn_pre_s(x, g1, b1, Sc) > 0
+        ref = ref + g1.astype(np.float64) * m * (d2.astype(np.float64) @ w1.astype(np.float64))
+        mag = mag + np.abs(g1).astype(np.float64) * m * (np.abs(d2).astype(np.float64) @ np.abs(w1).astype(np.float64))
+        if chain:
+            run = (run + (g1 * m).astype(f32) * _fp32_chain(rnd(d2, "bf16"), rnd(np.ascontiguousarray(w1.T, dtype=f32), "bf16"))).astype(f32)
+    return ref, mag, rnd((np.asarray(G0, dtype=f32)[take, c0:c1] + run).astype(f32), "bf16") if chain else None, keep
+
+
+def conv2_wgrad_ops16(GS32, BT, H, W, g2, b2, stats, cols):
+    """dense_ref.conv2_wgrad_ops for the 16-bit modes: GS32 = per stream the operand's fp32 value (the stored gs_, or gs_on_load16's),
+    the activation relu(bn2(bt)) with the engine's statistics; storage_blocked rounds both to bf16.  (Gs64, Gs32, A64, A32)"""
+    cols = np.asarray(cols)
+    A64 = np.concatenate([dr.im2col(act64_s(bt, g2, b2, S), H, W, cols=cols) for bt, S in zip(BT, stats)])
+    A32 = np.concatenate([dr.im2col(act32_s(bt, g2, b2, S), H, W, cols=cols) for bt, S in zip(BT, stats)])
+    G = np.concatenate([np.asarray(g, dtype=f32) for g in GS32])
+    return G.astype(np.float64), G, A64, A32
+
+
+def conv1_wgrad_ops16(D2, X, g1, b1, stats, rows, cols):
+    """dense_ref.conv1_wgrad_ops for the 16-bit modes: the stored D2 against relu(bn1(x)) with the engine's statistics"""
+    A64 = np.concatenate([act64_s(x[:, cols], g1[cols], b1[cols], S.cols(cols)) for x, S in zip(X, stats)])
+    A32 = np.concatenate([act32_s(x[:, cols], g1[cols], b1[cols], S.cols(cols)) for x, S in zip(X, stats)])
+    D = np.concatenate([np.asarray(d, dtype=f32)[:, rows] for d in D2])
+    return D.astype(np.float64), D, A64, A32

@@ -10,6 +10,15 @@
     is applied to - the cap is a condition on the rule, shown here on the reference's planes alone (at most 0.72 % in bf16, 0.13 % in
     fp16).
 
+  * the dense layers' backward in the 16-bit modes (storage_ref's second half): the *_s restatements at fp64 against the tiny dense block
+    test_cpu_dense_ref holds to torch autograd, the data-gradient chains against torch's bf16 matmul, the slack of sums taken in front
+    of a bf16 store, what each backward gate catches (a zeroed 8-row tile row of dy2 91 - 132 x the gate, swapped halves of every 32-bit
+    word 300 - 305 x, a mask from the other stream's statistics 62 - 85 x, a dropped segment of the grouped form 46 - 55 x, the
+    accumulate stored as an overwrite 1000 - 1470 x, one stream's pixels missing from a weight gradient 118 - 138 x, its last pixel
+    chunk 7.3 - 30 x) and
+    the keep-masks of every gated layer with the engine's statistics: at most 0.0043 % borderline; the materialised GS from sums handed in
+    (gs_from_sums) and what its element bound trips on (a dropped 128-row workgroup 512 x, everything else 3600 x and more).
+
 Measured (-s prints every one; bf16 / fp16, x the gate): a transition's last tile left zero on the padded planes of S = 672 7.1 - 58 /
 57 - 459; conv1 of layer (4,8) dropping its last 64-row tile 32 - 61 / 261 - 486, reading its newest 32-channel slice one slot too
 far 48 - 49 / 394; conv2 storing the wrong half of every 16-bit pair 243 - 252 / 1900; a heightmap-form stem summing two of three
@@ -26,7 +35,7 @@ import torch
 import dense_ref as dr
 import stage_ref as sr
 import storage_ref as st
-from gate_harness import conv1_fwd_cfg, forward_chains, halo_tile, transition_cfg
+from gate_harness import BWD_LAYERS16, conv1_fwd_cfg, forward_chains, halo_tile, transition_cfg
 from helpers import _WGRAD_GATE, MEAN, STD, orc
 from test_cpu_stage_ref import SCENES, _hp, _oracle_planes, _tiny_head, _tp
 
@@ -305,3 +314,267 @@ def test_keep_mask_of_the_16_bit_gates_leaves_out_at_most_one_percent(case, mode
             keep = st.keep_s(X, g, b, S)
             print("%s %s transition %d stream %d: %.4f %% borderline" % (case, mode, t, s, 100 * (1 - keep.mean())))
             assert 1 - keep.mean() <= 0.01
+
+
+# ---- the dense layers' backward in the 16-bit modes ---------------------------------------------------------------------------------------------
+
+
+def test_backward_restatements_at_fp64_equal_the_walk_autograd_proved():
+    """storage_ref's *_s forms with the statistics handed in as the engine's sums (engine_stats of plane_sums) against the tiny dense
+    block of test_cpu_dense_ref (whose every buffer test_dense_layer_forward_and_backward_equal_torch holds to torch autograd): GS, the
+    norm2 backward, both forms of the conv1 data gradient, both weight gradients.  The sums' slack is the table's fp32 rounding."""
+    import test_cpu_dense_ref as t
+    for H, W in t.PLANES:
+        o = t._walk(H, W)
+        for s in range(t.NS):
+            Sx = st.engine_stats(st.plane_sums(o.X[s]), o.HW)
+            mean, inv = sr.bn_stats(o.X[s])
+            assert np.allclose(Sx.mean, mean, rtol=1e-12, atol=1e-14) and np.allclose(Sx.inv, inv, rtol=1e-10) and (Sx.R == sr.U).all()
+            for i in range(t.L):
+                p, cin = o.prm[i], t.CIN0 + t.GROWTH * i
+                sl = slice(cin, cin + t.GROWTH)
+                _near(st.bn_bwd_s(o.G0[s][i][:, sl], o.X[s][:, sl], Sx.cols(sl)), o.GS[s][i], "GS")
+                Sb = st.engine_stats(st.plane_sums(o.BT[s][i]), o.HW)
+                _near(st.bn_bwd_s(o.DY[s][i], o.BT[s][i], Sb, p["g2"]), o.D2[s][i], "D2")
+                assert (st.bn_bwd_sum_mag_s(o.DY[s][i], o.BT[s][i], Sb, p["g2"]) >= np.abs(o.D2[s][i]) * (1 - 1e-9)).all()
+                for layers, c0, c1 in dr.dgrad1_segments(t.L, i, t.CIN0, t.GROWTH):
+                    prm = [(o.prm[l]["g1"], o.prm[l]["b1"], o.prm[l]["w1"]) for l in layers]
+                    d2s = [o.D2[s][l] for l in layers]
+                    ref, mag, _, _ = dr.conv1_dgrad(o.G0[s][i], o.X[s], prm, d2s, c0, c1, chain=False)
+                    r16, m16, ch, keep = st.conv1_dgrad16(o.G0[s][i], o.X[s], Sx, prm, d2s, c0, c1)
+                    _near(r16, ref, "conv1 data gradient"); _near(m16, mag, "its magnitude")
+                    assert np.array_equal(st.rnd(ch, "bf16"), ch) and keep.mean() > 0.99
+        for i in range(t.L):
+            p, cin = o.prm[i], t.CIN0 + t.GROWTH * i
+            Sb = [st.engine_stats(st.plane_sums(o.BT[s][i]), o.HW) for s in range(t.NS)]
+            Sx = [st.engine_stats(st.plane_sums(o.X[s]), o.HW) for s in range(t.NS)]
+            G64, _, A64, _ = st.conv2_wgrad_ops16([o.GS[s][i] for s in range(t.NS)], [o.BT[s][i] for s in range(t.NS)], H, W, p["g2"], p["b2"], Sb, np.arange(9 * t.BOTT))
+            _near(np.concatenate([o.GS[s][i] for s in range(t.NS)]).T @ A64, o.dW2[i], "conv2 weight gradient")
+            _, _, A64, _ = st.conv1_wgrad_ops16([o.D2[s][i] for s in range(t.NS)], o.X, p["g1"], p["b1"], Sx, np.arange(t.BOTT), np.arange(cin))
+            _near(np.concatenate([o.D2[s][i] for s in range(t.NS)]).T @ A64, o.dW1[i], "conv1 weight gradient")
+
+
+def _near(a, b, what):
+    assert np.abs(np.asarray(a) - b).max() <= 1e-9 * max(np.abs(b).max(), 1e-30), what
+
+
+def test_backward_chains_against_torch_bf16_matmul():
+    """the 3x3 data-gradient chain and the accumulate chain against torch's own bf16 matmul of bf16 tensors (fp32 accumulation in
+    another order, bf16 result): two roundings of nearly equal values, at most one bf16 ulp apart and mostly equal"""
+    r = np.random.default_rng(11)
+    H = W = 6
+    gs = st.rnd((r.standard_normal((H * W, 4)) * 1e-2).astype(np.float32), "bf16")
+    w2 = (r.standard_normal((4, 8, 3, 3)) * 0.2).astype(np.float32)
+    on = r.random((H * W, 8)) > 0.3
+    pix = np.arange(H * W)
+    ch = st.conv2_dgrad_chain16(gs, H, W, w2, on, pix)
+    ta = torch.from_numpy(dr.im2col(gs, H, W, pix, flip=True)).to(torch.bfloat16)
+    tw = torch.from_numpy(dr.w2_bwd_mat(w2).astype(np.float32)).to(torch.bfloat16)
+    ref = (torch.matmul(ta, tw.T).float().numpy() * on).astype(np.float64)
+    assert (np.abs(ch - ref) <= 2 * st.half_ulp(ref, "bf16") + 1e-300).all() and (ch == ref).mean() >= 0.9
+    assert not ch[~on].any()
+    # the accumulate: one segment, gamma = 1, every ReLU on, statistics of the plane - rnd(G0 + D2 @ W) against torch
+    x = r.standard_normal((H * W, 12)).astype(np.float32) + 5.0
+    S = st.engine_stats(st.plane_sums(x), H * W)
+    g1, b1 = np.ones(12, dtype=np.float32), np.full(12, 9.0, dtype=np.float32)
+    w1 = (r.standard_normal((8, 12)) * 0.3).astype(np.float32)
+    d2 = st.rnd((r.standard_normal((H * W, 8)) * 1e-2).astype(np.float32), "bf16")
+    G0 = st.rnd((r.standard_normal((H * W, 12)) * 1e-2).astype(np.float32), "bf16")
+    ref64, mag, ch, keep = st.conv1_dgrad16(G0, x, S, [(g1, b1, w1)], [d2], 0, 12)
+    assert keep.all() and (mag >= np.abs(ref64) * (1 - 1e-12)).all()
+    prod = torch.matmul(torch.from_numpy(d2).to(torch.bfloat16).float(), torch.from_numpy(w1).to(torch.bfloat16).float())
+    ref = (torch.from_numpy(G0) + prod).to(torch.bfloat16).float().numpy().astype(np.float64)
+    assert (np.abs(ch - ref) <= 2 * st.half_ulp(ref, "bf16")).all() and (ch == ref).mean() >= 0.9
+
+
+def test_sums_before_store_slack_bounds_what_the_store_does_to_the_norm2_backward():
+    """dy rounded to bf16 AFTER its sums were taken: bn_bwd_s with the sums of the unrounded dy (the engine's) against bn_bwd_s of the
+    stored dy alone differs by at most sums_before_store_slack per element; the two sums by its per-channel terms"""
+    r = np.random.default_rng(12)
+    for HW in (400, 1764):
+        dy = (r.standard_normal((HW, 16)) * 10.0 ** r.uniform(-6, -2, 16) * (r.random((HW, 16)) > 0.4)).astype(np.float32)
+        bt = (r.standard_normal((HW, 16)) * 2 + r.standard_normal(16)).astype(np.float32)
+        g2 = r.standard_normal(16)
+        S = st.engine_stats(st.plane_sums(bt), HW)
+        dys = st.rnd(dy, "bf16")
+        a, q1, mean, k = st.bn_bwd_terms_s(dy, bt, S, g2)          # the engine's coefficients: sums of the unrounded values
+        engine = a * ((dys.astype(np.float64) - q1) - (bt.astype(np.float64) - mean) * k)
+        sl, h1, h2 = st.sums_before_store_slack(dys, bt, S, g2)
+        worst = float((np.abs(engine - st.bn_bwd_s(dys, bt, S, g2)) / (sl + 1e-300)).max())
+        print("%d pixels: the sums taken before the bf16 store move the norm2 backward by at most %.3f of the slack" % (HW, worst))
+        assert worst <= 1.0
+        xh = (bt.astype(np.float64) - S.mean) * S.inv
+        assert (np.abs(dy.astype(np.float64).sum(0) - dys.astype(np.float64).sum(0)) <= h1).all()
+        assert (np.abs((dy * xh).sum(0) - (dys * xh).sum(0)) <= h2 * (1 + 1e-12)).all()
+        assert st.k_d2_apply(16) == 526 and st.k_d2_apply(8) == 142 and st.k_affine2(8, 6, True) == 63 + 5 + 1 + 5 and st.k_gs_top(5) == 187
+
+
+_BWD = {}
+
+
+def _bwd_planes(case, block, layer):
+    """One dense layer's backward buffers on the oracle's planes of `case` (the rotation and the masked stream), as mode bf16 holds them:
+    x<b> and the bottleneck rounded to bf16 with the statistics of the values IN FRONT of the store (what the engine sums), a synthetic
+    G' (the oracle walk keeps no gradients: bf16 noise of the size the gates meet, 1e-3), and from it GS, dy2, D2 and - for a layer at
+    the bottom of a group - the D2 of the group's other layers (synthetic), each rounded once to bf16 where the kernels round."""
+    if (case, block, layer) in _BWD:
+        return _BWD[(case, block, layer)]
+    P = _oracle_planes(case)
+    sd, H = P["sd"], P["S"] // (2 ** (block + 1))
+    HW, cin, Lb = H * H, dr.cin_of(block, layer), dr.LAYERS[block - 1]
+    lp = lambda l, n: _tp(sd, "denseblock%d.denselayer%d.%s" % (block, l, n))      # noqa: E731
+    r = np.random.default_rng(block * 100 + layer)
+    o = dict(H=H, HW=HW, cin=cin, g2=lp(layer, "norm2.weight"), b2=lp(layer, "norm2.bias"), w2=lp(layer, "conv2.weight"), streams=[])
+    o["segs"] = dr.dgrad1_segments(Lb, layer - 1, dr.CIN0[block - 1])
+    o["prm"] = {l: (lp(l + 1, "norm1.weight"), lp(l + 1, "norm1.bias"), lp(l + 1, "conv1.weight").reshape(128, -1)) for sg in o["segs"] for l in sg[0]}
+    o["prm"][layer - 1] = (lp(layer, "norm1.weight"), lp(layer, "norm1.bias"), lp(layer, "conv1.weight").reshape(128, cin))
+    for s in range(2):
+        X32 = P["x"][block - 1][s]
+        Sx, X = st.engine_stats(st.plane_sums(X32), HW), st.rnd(X32, "bf16")
+        g1, b1, w1 = o["prm"][layer - 1]
+        bt32 = (st.act64_s(X[:, :cin], g1, b1, Sx.cols(slice(0, cin))) @ w1.astype(np.float64).T).astype(np.float32)
+        Sb, BT = st.engine_stats(st.plane_sums(bt32), HW), st.rnd(bt32, "bf16")
+        G0 = st.rnd((r.standard_normal(X.shape) * 1e-3).astype(np.float32), "bf16")
+        sl = slice(cin, cin + 32)
+        GS = st.rnd(st.bn_bwd_s(G0[:, sl], X[:, sl], Sx.cols(sl)).astype(np.float32), "bf16")
+        on = st.bn_pre_s(BT, o["g2"], o["b2"], Sb) > 0
+        dy64, dymag = dr.conv2_dgrad(GS, H, H, o["w2"])
+        DY = st.rnd((on * dy64).astype(np.float32), "bf16")
+        D2 = {layer - 1: st.rnd(st.bn_bwd_s(DY, BT, Sb, o["g2"]).astype(np.float32), "bf16")}
+        for l in o["prm"]:
+            if l not in D2:
+                D2[l] = st.rnd((r.standard_normal((HW, 128)) * np.abs(D2[layer - 1]).mean() * 1.25).astype(np.float32), "bf16")
+        o["streams"].append(dict(X=X, Sx=Sx, BT=BT, Sb=Sb, G0=G0, GS=GS, on=on, dy64=on * dy64, dymag=dymag, DY=DY, D2=D2))
+    _BWD[(case, block, layer)] = o
+    return o
+
+
+@pytest.mark.parametrize("case,block,layer", [("S640", 4, 13), ("S672", 4, 13), ("S672", 3, 21)])
+def test_what_the_16_bit_backward_gates_catch(case, block, layer):
+    """The perturbations the issue of these gates lists, on a layer at the bottom of a four-layer group (grouped form, nseg = 4, and the
+    per-layer form beside it is empty: the grouped segment is the layer's whole data gradient), each against the gate the GPU test
+    applies: 2 x the storage chain for the data gradients (whole plane, kept elements), the element bound for the in-place norm2
+    backward, _WGRAD_GATE x the blocked reduction over the bf16 operands for the weight gradients."""
+    o = _bwd_planes(case, block, layer)
+    H, HW, cin = o["H"], o["HW"], o["cin"]
+    pix = np.arange(HW)
+    tag = "%s (%d,%d)" % (case, block, layer)
+    for s, d in enumerate(o["streams"]):
+        ref, mag = d["dy64"], d["dymag"]
+        keep2 = st.keep_s(d["BT"], o["g2"], o["b2"], d["Sb"])
+        gate = 2.0 * dr.rms(st.conv2_dgrad_chain16(d["GS"], H, H, o["w2"], d["on"], pix), ref, mag, keep2)
+        bad = d["DY"].copy()
+        bad.reshape(H, H, 128)[8:16] = 0
+        _report("%s stream %d: one 8-row tile row of dy2 left zero" % (tag, s), dr.rms(bad, ref, mag, keep2), gate)
+        swapped = d["DY"].reshape(HW, 64, 2)[:, :, ::-1].reshape(HW, 128)
+        _report("%s stream %d: dy2 stored with the two halves of every 32-bit word swapped" % (tag, s), dr.rms(swapped, ref, mag, keep2), gate)
+        other = o["streams"][1 - s]["Sb"]
+        on_o = st.bn_pre_s(d["BT"], o["g2"], o["b2"], other) > 0
+        _report("%s stream %d: the ReLU mask of dy2 from the other stream's statistics" % (tag, s), dr.rms(on_o * dr.conv2_dgrad(d["GS"], H, H, o["w2"])[0], ref, mag, keep2), gate)
+        # the in-place norm2 backward: the same swap and a dropped 64-row tile against the element bound
+        r2, bound = st.norm2_inplace(d["DY"], d["BT"], o["g2"], d["Sb"], 8)
+        assert (np.abs(d["D2"][layer - 1] - r2) <= bound).all()
+        sw = d["D2"][layer - 1].reshape(HW, 64, 2)[:, :, ::-1].reshape(HW, 128)
+        worst = float((np.abs(sw - r2) / (bound + 1e-300)).max())
+        print("perturbation: %s stream %d: D2 with adjacent channels swapped: %.3g x the element bound" % (tag, s, worst))
+        assert worst > 1.0
+        (layers, c0, c1), = [sg for sg in o["segs"] if sg[1] == 0]
+        assert len(layers) == 4 and len(o["segs"]) == 1
+        prm, d2s = [o["prm"][l] for l in layers], [d["D2"][l] for l in layers]
+        ref, mag, ch, keep = st.conv1_dgrad16(d["G0"], d["X"], d["Sx"], prm, d2s, c0, c1)
+        gate = 2.0 * dr.rms(ch, ref, mag, keep)
+        lost = st.conv1_dgrad16(d["G0"], d["X"], d["Sx"], prm[:-1], d2s[:-1], c0, c1, chain=False)[0]
+        _report("%s stream %d: one segment of the grouped 1x1 data gradient dropped" % (tag, s), dr.rms(lost, ref, mag, keep), gate)
+        _report("%s stream %d: the accumulate stored as an overwrite (G0 lost)" % (tag, s), dr.rms(ref - d["G0"][:, c0:c1], ref, mag, keep), gate)
+        sw = ch.reshape(HW, (c1 - c0) // 2, 2)[:, :, ::-1].reshape(HW, c1 - c0)
+        _report("%s stream %d: G' stored with adjacent channels swapped" % (tag, s), dr.rms(sw, ref, mag, keep), gate)
+        Sx_o = o["streams"][1 - s]["Sx"]
+        oth = st.conv1_dgrad16(d["G0"], d["X"], Sx_o, prm, d2s, c0, c1, chain=False)[0]
+        _report("%s stream %d: the norm1 masks from the other stream's statistics" % (tag, s), dr.rms(oth, ref, mag, keep), gate)
+    # weight gradients over both streams
+    S2 = o["streams"]
+    cols = np.arange(0, 9 * 128, 9)
+    G64, G32, A64, A32 = st.conv2_wgrad_ops16([d["GS"] for d in S2], [d["BT"] for d in S2], H, H, o["g2"], o["b2"], [d["Sb"] for d in S2], cols)
+    g1, b1, _ = o["prm"][layer - 1]
+    rows, c1x = np.arange(0, 128, 8), np.arange(0, cin, max(1, cin // 128))
+    D64, D32, B64, B32 = st.conv1_wgrad_ops16([d["D2"][layer - 1] for d in S2], [d["X"] for d in S2], g1, b1, [d["Sx"] for d in S2], rows, c1x)
+    for name, a64, a32, w64, w32 in (("conv2", G64, G32, A64, A32), ("conv1", D64, D32, B64, B32)):
+        ref, mag = a64.T @ w64, np.abs(a64).T @ np.abs(w64) + 1e-300
+        gate = _WGRAD_GATE * dr.rms(st.storage_blocked(a32, w32, "bf16", "bf16"), ref, mag)
+        one = slice(HW, 2 * HW)
+        _report("%s: one stream's pixels missing from the %s weight gradient" % (tag, name), dr.rms(ref - a64[one].T @ w64[one], ref, mag), gate)
+        tail = slice(2 * HW - (HW - (HW // 64) * 64 or 64), 2 * HW)
+        _report("%s: the last pixel chunk (%d rows) missing from the %s weight gradient" % (tag, tail.stop - tail.start, name), dr.rms(ref - a64[tail].T @ w64[tail], ref, mag), gate)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("case", sorted(BWD_LAYERS16))
+def test_keep_masks_of_the_16_bit_backward_gates_leave_out_at_most_one_percent(case, mode):
+    """The 1 % condition of the backward gates, before any GPU run: the oracle's planes rounded to the mode's activation storage, the
+    statistics those of the values in front of the store within the table's fp32 rounding (engine_stats) - norm2's mask of every gated
+    layer's bottleneck and the combined norm1 masks of every segment of its conv1 data gradient.  (The oracle's streams are one rotation
+    and the masked stream; the GPU gates assert the same cap on the streams they use.)"""
+    m = st.MODES[mode]
+    P = _oracle_planes(case)
+    sd = P["sd"]
+    worst = 0.0
+    for block, layer in BWD_LAYERS16[case]:
+        cin, Lb, HW = dr.cin_of(block, layer), dr.LAYERS[block - 1], len(P["x"][block - 1][0])
+        lp = lambda l, n: _tp(sd, "denseblock%d.denselayer%d.%s" % (block, l, n))      # noqa: E731
+        for s in range(2):
+            X32 = P["x"][block - 1][s]
+            Sx, X = st.engine_stats(st.plane_sums(X32), HW), st.rnd(X32, m["act"])
+            bt32 = (st.act64_s(X[:, :cin], lp(layer, "norm1.weight"), lp(layer, "norm1.bias"), Sx.cols(slice(0, cin))) @ lp(layer, "conv1.weight").reshape(128, cin).astype(np.float64).T).astype(np.float32)
+            sh2 = 1 - st.keep_s(st.rnd(bt32, m["act"]), lp(layer, "norm2.weight"), lp(layer, "norm2.bias"), st.engine_stats(st.plane_sums(bt32), HW)).mean()
+            sh1 = 0.0
+            for layers, c0, c1 in dr.dgrad1_segments(Lb, layer - 1, dr.CIN0[block - 1]):
+                keep = np.ones((HW, c1 - c0), dtype=bool)
+                for l in layers:
+                    keep &= st.keep_s(X[:, c0:c1], lp(l + 1, "norm1.weight")[c0:c1], lp(l + 1, "norm1.bias")[c0:c1], Sx.cols(slice(c0, c1)))
+                sh1 = max(sh1, 1 - keep.mean())
+            print("%s %s block %d layer %2d stream %d: borderline %.4f %% (norm2 mask), %.4f %% (norm1 masks of a segment, worst)" % (case, mode, block, layer, s, 100 * sh2, 100 * sh1))
+            worst = max(worst, sh1, sh2)
+    assert worst <= 0.01, worst
+
+
+def test_backward_layers_follow_the_rules():
+    for case, layers in BWD_LAYERS16.items():
+        assert len(layers) <= 5 and {b for b, _ in layers} == {1, 2, 3, 4} and (4, 16) in layers
+        forms = {(b, l): [(len(ls), c0) for ls, c0, _ in dr.dgrad1_segments(dr.LAYERS[b - 1], l - 1, dr.CIN0[b - 1])] for b, l in layers}
+        assert any(len(f) == 1 and f[0][1] > 0 for f in forms.values()), "a layer in the per-layer form only"
+        assert any((4, 0) in f for f in forms.values()), "a bottom of a four-layer group"
+    assert any(l == 1 for ls in BWD_LAYERS16.values() for _, l in ls), "a block's first layer"
+
+
+@pytest.mark.parametrize("case,block,layer", [("S640", 4, 13), ("S672", 3, 21)])
+def test_what_the_materialised_gs_gate_catches(case, block, layer):
+    """storage_ref.gs_from_sums - GS from the stored G' / x slices with the sums s1 / s2 HANDED IN (the engine's, debug_read "bs_x<b>") -
+    equals bn_bwd_s when the sums are those of the slice; and the element bound of the GPU gate (K_GS_APPLY roundings + half a bf16
+    ulp, no slack) on the oracle's planes: a dropped 128-row workgroup of bn_bwd_apply_kernel<PREC>, adjacent channels swapped, the x
+    slice of the neighbouring layer, the other stream's sums, sums over HWp instead of HW."""
+    o = _bwd_planes(case, block, layer)
+    HW, cin = o["HW"], o["cin"]
+    sl = slice(cin, cin + 32)
+    tag = "%s (%d,%d)" % (case, block, layer)
+    sums = []
+    for d in o["streams"]:
+        Sc = d["Sx"].cols(sl)
+        g, x = d["G0"][:, sl].astype(np.float64), d["X"][:, sl].astype(np.float64)
+        sums.append(np.stack([g.sum(0), (g * ((x - Sc.mean) * Sc.inv)).sum(0)]))
+    for s, d in enumerate(o["streams"]):
+        Sc = d["Sx"].cols(sl)
+        ref, mag = st.gs_from_sums(d["G0"][:, sl], d["X"][:, sl], Sc, sums[s], HW)
+        _near(ref, st.bn_bwd_s(d["G0"][:, sl], d["X"][:, sl], Sc), "GS from its sums")
+        bound = st.stored_bound(ref, st.K_GS_APPLY, mag, "bf16")
+        assert (np.abs(d["GS"] - ref) <= bound).all()
+        bad = d["GS"].copy()
+        bad[(HW // 128) * 128 - 128:(HW // 128) * 128] = 0
+        cases = [("a 128-row workgroup of the apply left zero", bad),
+                 ("adjacent channels swapped", d["GS"].reshape(HW, 16, 2)[:, :, ::-1].reshape(HW, 32)),
+                 ("the x slice of the layer below", st.gs_from_sums(d["G0"][:, sl], d["X"][:, cin - 32:cin], Sc, sums[s], HW)[0]),
+                 ("the other stream's sums", st.gs_from_sums(d["G0"][:, sl], d["X"][:, sl], Sc, sums[1 - s], HW)[0]),
+                 ("the sums divided by HWp", st.gs_from_sums(d["G0"][:, sl], d["X"][:, sl], Sc, sums[s], -(-HW // 64) * 64)[0])]
+        for what, v in cases:
+            worst = float((np.abs(v - ref) / (bound + 1e-300)).max())
+            print("perturbation: %s stream %d: materialised GS, %s: %.3g x the element bound" % (tag, s, what, worst))
+            assert worst > 1.0

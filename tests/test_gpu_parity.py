@@ -1244,6 +1244,52 @@ def test_debug_read_of_bottlenecks_in_16bit_storage(gpu):
     net.set_precision("fp32")
 
 
+def test_debug_read_of_the_dense_backward_in_every_storage_mode(gpu):
+    """smg_debug_read behind a debug_stop backward - "gsnap", "dy2", "gs_<b>_<l>", "d2_<b>_<l>", and "fs_x<b>" / "bs_x<b>" - in mode 0 as before and
+    in bf16 and fp16 storage, on the single-sample scene behind layer (4,14) (the middle of a group: its 1x1 data gradient writes columns
+    896..927 of g4 only).  Every gradient read in 16-bit storage is a bf16 value, every activation a value of the mode's type; gsnap equals g4 on the columns the layer does not write
+    and differs on those it does; d2_ is no longer the raw dy2 the in-place norm2 backward overwrote; the forward sums reproduce the
+    stored plane's statistics; a snapshot of one mode is refused in another."""
+    import stage_ref as sr
+    import storage_ref as st
+    from gate_harness import SCENES, GateCtx
+    from smg_hip import SmgError
+    net = product_net(0)
+    x = GateCtx(net, {}, SCENES["S640x2"], gpu)
+    HW, HWp, NS = 400, 448, 2
+    try:
+        for mode in ("fp32", "bf16", "fp16"):
+            net.set_precision(mode)
+            x.backward_to(300 + 13)
+            G0, G1 = x.rd("gsnap", NS, 5, 1024), x.rd("g4", NS, 5, 1024)
+            DY, D2, GS = x.rd("dy2", NS, 5, 128), x.rd("d2_4_14", NS, 5, 128), x.rd("gs_4_14", NS, 5, 32)
+            X4 = x.rd("x4", NS, 5, 1024)
+            assert all(np.isfinite(v).all() and np.abs(v).max() > 0 for v in (G0, G1, DY, D2, X4)) and np.isfinite(GS).all()
+            assert np.array_equal(G0[:, :, :896], G1[:, :, :896]) and np.array_equal(G0[:, :, 928:], G1[:, :, 928:])
+            assert not np.array_equal(G0[:, :, 896:928], G1[:, :, 896:928])
+            assert not np.array_equal(DY, D2)
+            if mode != "fp32":          # gradients are bf16 in both 16-bit modes, activations bf16 / fp16: widened by their own type
+                for v in (G0, G1, DY, D2, GS):
+                    assert np.array_equal(st.rnd(v, "bf16"), v)
+                assert np.array_equal(st.rnd(X4, mode), X4) and (mode == "bf16" or not np.array_equal(st.rnd(X4, "bf16"), X4))
+                assert len(x.eng.debug_read("dy2")) == NS * HWp * 128
+            assert len(x.eng.debug_read("gsnap")) == NS * HWp * 1024          # the last snapshot's elements, not the buffer's capacity
+            bs = x.eng.debug_read("bs_x4").view(np.float64).reshape(2, -1, 1024)
+            assert np.isfinite(bs).all() and np.abs(bs[:, :NS, 928:960]).max() > 0
+            fs = x.eng.debug_read("fs_x4").view(np.float64).reshape(2, -1, 1024)
+            for n in range(NS):
+                S = st.engine_stats(fs[:, n], HW)
+                mean, inv = sr.bn_stats(X4[n])
+                M, R = st.store_stat_slack(X4[n], mode) if mode != "fp32" else (0.0, 0.0)          # (16-bit: the sums were taken in front of the store)
+                assert (np.abs(S.mean - mean) <= M + 1e-5 * np.abs(X4[n]).max()).all() and (np.abs(S.inv / inv - 1) <= R + 1e-3).all()
+        net.set_precision("fp32")
+        x.forward()                                                  # (the model hands the mode to the engine with its next call)
+        with pytest.raises(SmgError):                                # (mode 0 reads "dy2" from its own buffer: nothing to refuse there)
+            x.eng.debug_read("gsnap")
+    finally:
+        net.set_precision("fp32")
+
+
 @pytest.mark.parametrize("block,layer", [(1, 1), (2, 12), (3, 24)])
 def test_layer_products_within_fp32_chain_error(gpu, block, layer):
     """GEMM-level gate on the PRODUCT's kernels at real layer shapes (K = 64 / 480 / 992 for the 1x1, K = 1152 for the 3x3):

@@ -43,15 +43,42 @@ Forward: dense layers (1,1) (1,6) (2,1) (2,12) (3,24) (4,1) (4,16) on the first 
 bt<b>_<l>, conv2 from the bottleneck into x<b>[:, cin:cin+32]; stem conv0 in the heightmap form (operands rounded to the mode's forward
 operand type - FwdConvP's kOp = fwd_op_plain(PREC) - into the fp32 stem plane); pool0 into the 16-bit x1; the three transitions;
 feat_kernel from the 16-bit x4 into fp32; the head's norm0 + ReLU + conv0 (fp32 in and out, 16-bit operands); x<b>'s padding rows finite.
-Backward, the dq of the stage gates (gate_harness.SCENES), one debug_stop per gate: at 350 the head conv0 data and weight gradients (bf16
+Backward of the stages, the dq of the stage gates (gate_harness.SCENES), one debug_stop per gate: at 350 the head conv0 data and weight gradients (bf16
 operands, fp32 buffers), norm5_bwd_kernel into the bf16 g4 on every stream, norm5's affine gradients; at 250 / 150 / 50 the E_UNPOOL
 data gradient into g<t> and the W_POOL weight gradient of transitions 3 / 2 / 1.
 
-Out of scope: the dense layers' backward in modes 1 / 2 (smg_debug_read refuses dy2, gs_*, d2_* and gsnap outside mode 0; a whole
-block's backward end to end would be a chained error, not an operator gate); input sizes that are no multiple of 32; the Adam and
-loss kernels.
+Backward of the DENSE LAYERS (58 of the net's 64 layers; in modes 1 / 2 none of mode 0's hot kernels run: no split operands, no
+unit-form D2, no wave-specialised 1x1 weight gradient, no gs_on_side).  smg_debug_read now answers in every mode: "gsnap", "dy2" (the
+stop copies the ring slot between the 3x3 data gradient and the norm2 backward that overwrites it in place), "gs_<b>_<l>" / "d2_<b>_<l>"
+and - new - "fs_x<b>" / "bs_x<b>", the forward's and the backward's fp64 sums of a block buffer.  With fs_bt and fs_x every ReLU mask and every xhat of the reference
+comes from the statistics the kernels used (storage_ref.engine_stats: the keep-mask's margin is the table's fp32 rounding), the sums
+themselves are gated against the stored planes (test_block_buffer_sums_are_taken_before_the_store), and no stream is over the 1 % cap
+(DGRAD16_OVER_THE_CAP is empty; the largest borderline share met is 0.0063 %).  VARIANTS16_BWD is the walk's choice with `split16`
+false, asserted from eng.H / eng.HWp.  Five stops per (mode, geometry), BWD_LAYERS16, chosen by rule
+(test_backward_layers_follow_the_rules): S = 640 x 6 streams - GS materialised (bn_bwd_apply_kernel<PREC> at C = 32), exact tiles;
+S = 672 x 3 streams - the BN backward applied on load in both 3x3 kernels, bounds-checked 16 x 16 and ragged 8 x 8 tiles, block 4's conv1
+weight gradient on fp32 atomics.  Per stop (test_backward_layer): the storage type of every slot; the 3x3 data gradient
+(conv3x3_halo_dgrad_kernel<16 | 8, PREC, edge>) within 2.0 x the storage chain, exact zeros where the ReLU is clearly off; the in-place
+norm2 backward (bn_bwd_apply_kernel<PREC> at C = 128) element by element within the counted roundings + the slack of sums taken in front
+of dy2's store + half a bf16 ulp; norm2's dgamma / dbeta within the counted roundings of sum |term| + that slack; both weight gradients
+(conv3x3_halo_wgrad_kernel, BwdWeightP<.., W_ONE>) within _WGRAD_GATE x the blocked reduction over the bf16 operands; the 1x1 data
+gradients in the form(s) the layer takes (BwdDataP<.., E_ACCUM> per layer, BwdDataGroupP with nseg = 4) within 2.0 x the storage chain,
+|gsnap| in the magnitude, and the columns no segment covers bit-equal to gsnap.  The slots' padding rows [HW, HWp) are written by no
+16-bit kernel (test_backward_layer cites the stores and every consumer's bound): on blocks 3 - 4 EVERY word there is non-zero (S = 640
+block 4: 36864 = 6 x 48 x 128; S = 672: 10752 on block 3, 2688 on block 4) and every gate above holds regardless.
+Measured on the MI355X (profiles/storage_gates_bwd.txt; both modes alike): 3x3 data gradient 1.00 - 1.01 of the chain on the sample,
+0.89 - 1.01 on the whole plane; in-place norm2 backward at 0.89 - 0.99 of its bound (the half ulp, reached); norm2's dbeta at 0.02 - 0.14,
+dgamma at 0.03 - 0.20 of theirs; conv2 weight gradient 1.00 - 1.25, conv1 weight gradient 1.00 of the blocked reduction (gate 3.0); 1x1 data
+gradient 1.00 on the sample, 0.92 - 1.10 on the whole plane; the materialised GS (bn_bwd_apply_kernel<PREC> at C = 32, every S = 640 stop, the engine's own s1 / s2 from bs_x) at 1.00 of its
+bound (the half ulp, reached), on (4,16) also at 0.86 - 0.88 with the sums of gsnap; fs_x within 0.96
+of its slack (median channel 0.017 and up).  No gate was missed and no kernel changed.  The transition gate takes its masks from fs_x as
+well: its exception table DGRAD_OVER_THE_CAP is empty now, and the stream it left out (bf16, S = 640, transition 1, stream 0) sits at
+1.00 of the chain with 0.0000 % of its signs borderline.
 
-Raw output of a run on the MI355X: profiles/storage_gates.txt."""
+Out of scope: the stem / pool0 backward of
+the 16-bit modes; input sizes that are no multiple of 32; the Adam and loss kernels.
+
+Raw output of a run on the MI355X: profiles/storage_gates.txt, profiles/storage_gates_bwd.txt (the dense layers' backward)."""
 import numpy as np
 import pytest
 import torch
@@ -59,7 +86,7 @@ import torch
 import dense_ref as dr
 import stage_ref as sr
 import storage_ref as st
-from gate_harness import (CT, HEAD, SCENES, TRUNK, GateCtx, bounded, conv1_fwd_cfg, forward_chains, gate, gpu, halo_tile,  # noqa: F401  (gpu: the fixture)
+from gate_harness import (BWD_LAYERS16, CT, HEAD, SCENES, TRUNK, GateCtx, bounded, conv1_fwd_cfg, forward_chains, gate, gpu, halo_tile,  # noqa: F401  (gpu: the fixture)
                           transition_cfg, wgrad_gate)
 from helpers import MEAN, STD, product_net
 
@@ -71,13 +98,12 @@ VARIANTS16 = {"S640": ([("P128x128", 16, False), ("P64x64", 8, False), ("P32x64"
               "S672": ([("P128x128", 16, True), ("P64x64", 8, False), ("P32x64", 8, False), ("P32x64", 8, False)], ["P64x128", "P128x128", "P64x128"], "P128x64", "P64x64")}
 FWD_LAYERS = [(1, 1), (1, 6), (2, 1), (2, 12), (3, 24), (4, 1), (4, 16)]
 # Streams whose E_UNPOOL data-gradient gate is LEFT OUT because the keep-mask's condition - at most 1 % of the plane's ReLU signs
-# undetermined by the stored plane - does not hold there: {(mode, geometry, transition): streams}.  The test asserts this set exactly.
-# bf16, S = 640, transition 1, stream 0 (rotation 0, the unrotated scene): 1.33 % of x1.  The 3x3 kernels summed the statistics of
-# x1[:, 64:] before the bf16 store; the scene's flat background rounds one way on most of the plane, the engine's mean sits up to half
-# a bf16 ulp off the stored plane's, and in a few channels the whole background's pre-activation lies inside that uncertainty: which
-# sign the kernel's mask took there cannot be told from the buffers smg_debug_read exposes (the block buffers' sums are not among
-# them; pool0's 64 channels are determined by the fp32 stem plane, and are taken from it).  fp16 leaves 0.33 % on the same stream.
-DGRAD_OVER_THE_CAP = {("bf16", "S640", 1): (0,)}
+# undetermined - does not hold there: {(mode, geometry, transition): streams}.  The test asserts this set exactly.  EMPTY since the mask
+# comes from the engine's own forward sums (debug_read "fs_x<t>": storage_ref.engine_stats).  Before, with the stored plane's statistics
+# and the slack of sums taken before the store, bf16 / S = 640 / transition 1 / stream 0 (rotation 0, the unrotated scene) had 1.33 % of
+# x1 borderline - the scene's flat background rounds one way on most of the plane, the engine's mean sits up to half a bf16 ulp off the
+# stored plane's, and in a few channels the whole background's pre-activation lay inside that uncertainty - and was left out.
+DGRAD_OVER_THE_CAP = {}
 _STATE = {}
 
 
@@ -130,6 +156,7 @@ def _fwd(x):
             print("%s %s x%d: %d padding rows per stream, largest |value| %.3e" % (x.mode, x.case, b + 1, padrows.shape[1], np.abs(padrows).max() if padrows.size else 0.0))
             assert np.isfinite(padrows).all()
             B["x%d" % (b + 1)] = full[:, :HW]
+            B["fsx%d" % (b + 1)] = x.eng.debug_read("fs_x%d" % (b + 1)).view(np.float64).reshape(2, -1, CT[b])[:, :x.NS].copy()
             assert np.array_equal(st.rnd(B["x%d" % (b + 1)], x.act), B["x%d" % (b + 1)])          # every stored value is a value of the storage type
         for b, l in FWD_LAYERS:
             B["bt%d_%d" % (b, l)] = x.rd("bt%d_%d" % (b, l), x.NS, 1 + b, 128)[x.dense_streams].copy()
@@ -219,6 +246,31 @@ def test_bottleneck_sums_are_taken_before_the_store(mc, block, layer):
               % (x.mode, x.case, block, layer, n, rm.max(), np.median(rm), ri.max(), np.median(ri)))
         assert rm.max() <= 1.0 and ri.max() <= 1.0
         assert np.median(rm) > 1e-3
+
+
+def test_block_buffer_sums_are_taken_before_the_store(mc):
+    """fs_x<b>: the engine's fp64 sums of a block buffer against the fp64 sums of the STORED plane, every stream and block - as
+    test_bottleneck_sums_are_taken_before_the_store holds fs_bt: within storage_ref.store_stat_slack plus, on the transition's channels
+    [0, C0) of x2..x4, the fp32 strip sums of its whole tiles (stage_ref.strip_sum_slack; pool0 and the 3x3 kernels sum per element in
+    fp64).  The backward gates take every ReLU mask from these sums: a reference built on them is not built on an unchecked number."""
+    x = mc
+    B = _fwd(x)
+    for b in range(1, 5):
+        HW = x.H[1 + b] ** 2
+        BM = 128 if x.HWp[1 + b] % 128 == 0 else 64          # transition_cfg: the tile rows of the transition that produced [0, C0)
+        C0 = 0 if b == 1 else CT[b - 2] // 2                     # x1: pool0 (64) and the 3x3 kernels only
+        for n in range(x.NS):
+            X, S = B["x%d" % b][n], st.engine_stats(B["fsx%d" % b][:, n], HW)
+            mean, inv = sr.bn_stats(X)
+            M, R = st.store_stat_slack(X, x.act)
+            Ms, Rs = np.zeros(len(M)), np.zeros(len(M))
+            if C0:
+                Ms[:C0], Rs[:C0] = sr.strip_sum_slack(X[:, :C0], (HW // BM) * BM)
+            rm, ri = np.abs(S.mean - mean) / (M + Ms * sr.U + 1e-300), np.abs(S.inv / inv - 1) / (R + Rs * sr.U + 1e-300)
+            print("%s %s x%d stream %d: engine mean off the stored plane's by at most %.3f of the bound (median %.4f), invstd %.3f (median %.4f)"
+                  % (x.mode, x.case, b, n, rm.max(), np.median(rm), ri.max(), np.median(ri)))
+            assert rm.max() <= 1.0 and ri.max() <= 1.0
+            assert np.median(rm) > 1e-3
 
 
 # ---- forward: the stages around the dense layers ---------------------------------------------------------------------------------------------
@@ -364,7 +416,8 @@ def test_transition_backward(mc, t):
     """Stop (t - 1) * 100 + 50.  E_UNPOOL: the corrected gradient dX of x<t+1>[:, :C0] (affine2 of the stored bf16 G' and the stored
     activation, q1 / k from the engine-style tile sums) rounded once to bf16, the data-gradient pack of the weights rounded to bf16,
     fp32 accumulation, 1/4 and gamma_t and the ReLU mask in fp32, one rounding to the bf16 g<t> (stq<GT>).  W_POOL: dX and the 2 x 2
-    average of relu(bn_t(x<t>)) both rounded to bf16 (bwd_op_plain), reduced in fp32."""
+    average of relu(bn_t(x<t>)) both rounded to bf16 (bwd_op_plain), reduced in fp32.  The ReLU mask and the pooled activation take
+    the ENGINE's forward sums of x<t> (fs_x<t>, held by test_block_buffer_sums_are_taken_before_the_store): no stream is left out."""
     x = mc
     grads = x.backward_to((t - 1) * 100 + 50)
     H, Cp = x.H[1 + t], CT[t - 1]
@@ -378,10 +431,10 @@ def test_transition_backward(mc, t):
     qy, qx = q // Hn, q % Hn
     pix = np.stack([(2 * qy + dy) * H + 2 * qx + dx for dy in (0, 1) for dx in (0, 1)], axis=1).ravel()
     cols = np.arange(0, Cp, max(1, Cp // 128))
-    stem = x.rd("stem", x.NS, 1, 64) if t == 1 else None          # (untouched at stop 50: the stem's backward has not run)
+    fsx = x.eng.debug_read("fs_x%d" % t).view(np.float64).reshape(2, -1, Cp)          # (the backward sums into another arena: intact at the stop)
     dX64s, dX32s, stats, over = [], [], [], []
     for n in range(x.NS):
-        S = st.x1_stats(X[n], stem[n], x.H[1], x.tp("norm0.weight"), x.tp("norm0.bias"), x.act) if t == 1 else st.plane_stats(X[n], x.act)
+        S = st.engine_stats(fsx[:, n], H * H)
         stats.append(S)
         dX = sr.bn_bwd(Gn[n], Xn[n])
         on = st.bn_pre_s(X[n], g, b, S) > 0
@@ -391,7 +444,7 @@ def test_transition_backward(mc, t):
         mag = np.abs(g) * on * 0.25 * sr.unpool2(sr.bn_bwd_mag(Gn[n], Xn[n]) @ np.abs(w.astype(np.float64)), H, H) + 1e-300
         keep = st.keep_s(X[n], g, b, S)
         share = 1 - keep.mean()
-        print("%s %s transition %d stream %d: %.4f %% of the ReLU signs borderline at 16-bit statistics" % (x.mode, x.case, t, n, 100 * share))
+        print("%s %s transition %d stream %d: %.4f %% of the ReLU signs borderline at the engine's statistics" % (x.mode, x.case, t, n, 100 * share))
         if share > 0.01:          # the cap is a condition of the gate: no data-gradient gate on this stream (see DGRAD_OVER_THE_CAP)
             over.append(n)
             continue
@@ -406,3 +459,170 @@ def test_transition_backward(mc, t):
     P32 = np.concatenate([sr.avgpool2(st.act32_s(X[n][:, c8], g[c8], b[c8], stats[n].cols(c8)), H, H) for n in range(x.NS)])
     _wgrad_gate("%s %s transition %d wgrad" % (x.mode, x.case, t), grads[TRUNK + "transition%d.conv.weight" % t].reshape(C0, Cp)[::8, ::8],
                 np.concatenate(dX64s)[:, ::8], P64, np.concatenate(dX32s)[:, ::8], P32, x.bwd)
+
+
+# ---- backward: the dense layers ------------------------------------------------------------------------------------------------------------------
+# per block: (3x3 tile, bounds-checked 16 x 16, ragged tiles, GS form, per-layer 1x1 data gradient, grouped, conv1 weight gradient)
+VARIANTS16_BWD = {"S640": [(16, False, False, "materialised", "P128x64", "G128x64x32", "partial tiles"), (8, False, False, "materialised", "P128x64", "G128x64x32", "partial tiles"),
+                           (8, False, False, "materialised", "P64x64", "P64x64", "partial tiles"), (8, False, True, "materialised", "P64x64", "P64x64", "partial tiles")],
+                  "S672": [(16, True, True, "on load", "P128x64", "G128x64x32", "partial tiles"), (8, False, True, "on load", "P64x64", "P64x64", "partial tiles"),
+                           (8, False, True, "on load", "P128x64", "G128x64x32", "partial tiles"), (8, False, True, "on load", "P64x64", "P64x64", "atomics")]}
+# the stops: gate_harness.BWD_LAYERS16 - at most five per (mode, geometry), chosen by rule (test_cpu_storage_ref.test_backward_layers_follow_the_rules)
+# streams whose ReLU signs are undetermined on more than 1 % of a plane: {(mode, geometry, block, layer, "norm2" | "norm1"): streams},
+# asserted exactly.  Empty: the masks come from the engine's own sums (fs_bt, fs_x), their margin is the table's fp32 rounding.
+DGRAD16_OVER_THE_CAP = {}
+
+
+def test_geometry_selects_the_backward_variants_of_the_16_bit_table(mc):
+    """backward.hip with `split16` false: halo_tile (wgrad_plan.h, no precision in it) and the bounds-checked instantiation for 16 x 16
+    tiles that hang over the edge; gs_materialised = NS > 4; CfgP128x64 / CfgP64x64 and GemmCfg<128, 64, 32> / CfgP64x64 by HWp % 128;
+    w1_partial_tiles (wgrad_plan.h: NS > 4 or more than 1600 pixels) - never the wave-specialised kernel (w1_ws needs split16)"""
+    x = mc
+    _fwd(x)
+    got = []
+    for b in range(4):
+        H, HWp = x.H[2 + b], x.HWp[2 + b]
+        t = halo_tile(H, x.NS)
+        big = HWp % 128 == 0
+        got.append((t, t == 16 and H % 16 != 0, H % t != 0, "materialised" if x.NS > 4 else "on load", "P128x64" if big else "P64x64", "G128x64x32" if big else "P64x64",
+                    "partial tiles" if x.NS > 4 or H * H > 1600 else "atomics"))
+    print("%s %s: %d streams, backward: %s" % (x.mode, x.case, x.NS, got))
+    assert got == VARIANTS16_BWD[x.case]
+
+
+@pytest.mark.parametrize("k", range(5))
+def test_backward_layer(mc, k):
+    """Stop behind dense layer BWD_LAYERS16[geometry][k]: the ring slots (gs_ where GS was materialised, d2_), the raw 3x3 data gradient
+    as it stood in the slot in front of the in-place norm2 backward (dy2), G' in front of (gsnap) and behind (g<b>) the layer's 1x1 data
+    gradients, the layer's finished parameter gradients.  Every ReLU mask and every xhat comes from the ENGINE's forward sums (fs_bt,
+    fs_x: storage_ref.engine_stats), which test_bottleneck_sums_are_taken_before_the_store and
+    test_block_buffer_sums_are_taken_before_the_store hold; the yardsticks are storage_ref's (its comment block cites every rounding).
+
+    Padding rows [HW, HWp) of the slots, read from the source before asserting: conv3x3_halo_dgrad_kernel stores in-plane pixels only
+    (halo.cuh epilogue: `!kEdge || (py < a.pl.H && px < a.pl.W)`, and a tile's pixels address (y, x) < (H, W)), bn_bwd_apply_kernel<PREC>
+    stores rows `r < a.pl.HW` only (elem.cuh) and no 16-bit kernel zeroes them (the unit-form apply of mode 0 does:
+    bn_bwd_apply_split_kernel) - they hold an earlier layer's rows, possibly of another block's plane.  Every consumer bounds its reads:
+    the 1x1 kernels stage A through bload4's size limit and mask `p < pa.HW` (gemm.cuh), the apply clamps its row (`r < a.pl.HW ? r :
+    0`), the halo kernels address pixels.  What follows is asserted: the gates below hold whatever lies there; the words are counted.
+
+    GS element by element (S = 640, where bn_bwd_apply_kernel<PREC> at C = 32 materialises it), at every stop: the fp64 BN backward of
+    gsnap[:, cin:cin+32] and the x slice with the sums s1 / s2 the kernel read, handed out by debug_read("bs_x<b>") - the counted roundings
+    plus half a bf16 ulp, no slack.  The sums cannot come from gsnap: BwdDataP::epilogue adds the UNROUNDED increments to s1 / s2 while G'
+    is rounded at every read-modify-write store above this layer, and the running values those stores rounded are in no buffer (the test
+    prints how far the engine's s1 is from the stored plane's sum).  Block 4's last layer, whose slice was stored exactly once
+    (norm5_bwd_kernel), is ALSO held in that form: sums from gsnap, storage_ref.k_gs_top roundings, the one store's derived slack."""
+    x = mc
+    block, layer = BWD_LAYERS16[x.case][k]
+    b, i = block - 1, layer - 1
+    grads = x.backward_to(b * 100 + i)
+    H, HWp, Ct, cin, Lb = x.H[1 + block], x.HWp[1 + block], CT[b], dr.cin_of(block, layer), dr.LAYERS[b]
+    HW = H * H
+    tag = "%s %s (%d,%d)" % (x.mode, x.case, block, layer)
+    ts, mat = halo_tile(H, x.NS), x.NS > 4
+    assert (ts, "materialised" if mat else "on load") == (VARIANTS16_BWD[x.case][b][0], VARIANTS16_BWD[x.case][b][3])
+    X, BT = x.rd("x%d" % block, x.NS, 1 + block, Ct), x.rd("bt%d_%d" % (block, layer), x.NS, 1 + block, 128)
+    fsx = x.eng.debug_read("fs_x%d" % block).view(np.float64).reshape(2, -1, Ct)
+    fsb = x.eng.debug_read("fs_bt%d_%d" % (block, layer)).view(np.float64).reshape(2, -1, 128)
+    Sx, Sb = [st.engine_stats(fsx[:, n], HW) for n in range(x.NS)], [st.engine_stats(fsb[:, n], HW) for n in range(x.NS)]
+    DYp, D2p = x.rd("dy2", x.NS, 1 + block, 128, pad=True), x.rd("d2_%d_%d" % (block, layer), x.NS, 1 + block, 128, pad=True)
+    DY, D2 = DYp[:, :HW], D2p[:, :HW]
+    G0, G1 = x.rd("gsnap", x.NS, 1 + block, Ct), x.rd("g%d" % block, x.NS, 1 + block, Ct)
+    GS = x.rd("gs_%d_%d" % (block, layer), x.NS, 1 + block, 32) if mat else None
+    g1, b1, w1 = x.lp(block, layer, "norm1.weight"), x.lp(block, layer, "norm1.bias"), x.lp(block, layer, "conv1.weight").reshape(128, cin)
+    g2, b2, w2 = x.lp(block, layer, "norm2.weight"), x.lp(block, layer, "norm2.bias"), x.lp(block, layer, "conv2.weight")
+    pix, sl = dr.sample(HW), slice(cin, cin + 32)
+    over = {}
+
+    # ---- storage type: every value read through the debug names is a bf16 value; the slot's padding rows: counted, never asserted
+    for name, v in (("dy2", DYp), ("d2_", D2p), ("gsnap", G0), ("g%d" % block, G1)) + ((("gs_", GS),) if mat else ()):
+        assert np.array_equal(st.rnd(v, x.grd), v), name
+    print("%s: %d padding rows per stream; non-zero words there: dy2 %d, d2_ %d" % (tag, HWp - HW, np.count_nonzero(DYp[:, HW:]), np.count_nonzero(D2p[:, HW:])))
+    assert np.isfinite(G1).all() and np.isfinite(D2).all()
+
+    # ---- the GS operand of the two 3x3 kernels, per stream: as stored, or the BN backward of the G' / x slices applied on load
+    if mat:
+        gs64, gs32 = [GS[n].astype(np.float64) for n in range(x.NS)], [GS[n] for n in range(x.NS)]
+    else:
+        gs64, gs32 = zip(*[st.gs_on_load16(G0[n][:, sl], X[n][:, sl], Sx[n].cols(sl)) for n in range(x.NS)])
+
+    # ---- the materialised GS, element by element at EVERY stop: bn_bwd_apply_kernel<PREC> at C = 32 from the stored G' / x slices with the
+    # sums s1 / s2 the kernel read (bs_x<b>: this layer's own data gradients add to columns [0, cin) only) - no slack
+    if mat:
+        bsx = x.eng.debug_read("bs_x%d" % block).view(np.float64).reshape(2, -1, Ct)
+        for n in x.dense_streams:
+            Sc = Sx[n].cols(sl)
+            ref, mag = st.gs_from_sums(G0[n][:, sl], X[n][:, sl], Sc, bsx[:, n, sl], HW)
+            stored = G0[n][:, sl].astype(np.float64)
+            print("%s stream %d: the engine's s1 of the slice against the sum of the STORED G': off by at most %.3g of sum |G'| (the stores above this layer rounded after summing)"
+                  % (tag, n, float((np.abs(bsx[0, n, sl] - stored.sum(0)) / (np.abs(stored).sum(0) + 1e-300)).max())))
+            bounded("%s materialised GS stream %d (engine's sums, %d roundings + half a bf16 ulp)" % (tag, n, st.K_GS_APPLY), GS[n], ref, st.stored_bound(ref, st.K_GS_APPLY, mag, "bf16"))
+    # ... and on block 4's last layer, whose slice of G' was stored exactly once, also in the form that takes the sums from gsnap
+    if mat and (block, layer) == (4, dr.LAYERS[3]):
+        for n in x.dense_streams:
+            users = x.NP if n == x.NS - 1 else 1
+            Sc = Sx[n].cols(sl)
+            ref, mag = st.bn_bwd_s(G0[n][:, sl], X[n][:, sl], Sc), st.bn_bwd_sum_mag_s(G0[n][:, sl], X[n][:, sl], Sc)
+            bounded("%s materialised GS stream %d (%d user%s, %d roundings + the store of G' + half a bf16 ulp)" % (tag, n, users, "s" if users > 1 else "", st.k_gs_top(users)),
+                    GS[n], ref, st.stored_bound(ref, st.k_gs_top(users), mag, "bf16", st.sums_before_store_slack(G0[n][:, sl], X[n][:, sl], Sc)[0]))
+
+    for n in x.dense_streams:
+        # ---- conv2 data gradient: mask from fs_bt, exact zeros where the ReLU is clearly off
+        keep = st.keep_s(BT[n], g2, b2, Sb[n])
+        on = st.bn_pre_s(BT[n], g2, b2, Sb[n]) > 0
+        share = 1 - keep.mean()
+        print("%s stream %d: %.4f %% of norm2's ReLU signs borderline at the table's fp32 rounding" % (tag, n, 100 * share))
+        if share > 0.01:
+            over.setdefault((x.mode, x.case, block, layer, "norm2"), []).append(n)
+        else:
+            ref, mag = dr.conv2_dgrad(gs64[n], H, H, w2)
+            ref = on * ref
+            chain = st.conv2_dgrad_chain16(gs32[n], H, H, w2, on, pix)
+            gate("%s conv2 dgrad stream %d (GS %s)" % (tag, n, "materialised" if mat else "on load"), _rms(DY[n][pix], ref[pix], mag[pix], keep[pix]),
+                 _rms(chain, ref[pix], mag[pix], keep[pix]), 2.0, e_whole=_rms(DY[n], ref, mag, keep), n=int(keep[pix].sum()), yard="storage chain")
+            assert not DY[n][keep & ~on].any(), "conv2 dgrad: non-zero where the ReLU is clearly off"
+
+        # ---- norm2 backward in place, rows < HW: from the STORED dy2, counted roundings + the sums taken before dy2's store + half a bf16 ulp
+        ref, bound = st.norm2_inplace(DY[n], BT[n], g2, Sb[n], ts)
+        bounded("%s norm2 backward in place, stream %d (%d roundings)" % (tag, n, st.k_d2_apply(ts)), D2[n], ref, bound)
+
+        # ---- conv1 data gradient in the form(s) the layer takes; masks from fs_x
+        for layers, c0, c1 in dr.dgrad1_segments(Lb, i, dr.CIN0[b]):
+            prm = [(x.lp(block, l + 1, "norm1.weight"), x.lp(block, l + 1, "norm1.bias"), x.lp(block, l + 1, "conv1.weight").reshape(128, -1)) for l in layers]
+            d2s = [D2[n] if l == i else x.rd("d2_%d_%d" % (block, l + 1), x.NS, 1 + block, 128, [n])[0] for l in layers]
+            ref, mag, _, keep = st.conv1_dgrad16(G0[n], X[n], Sx[n], prm, d2s, c0, c1, chain=False)
+            share = 1 - keep.mean()
+            form = "grouped" if len(layers) > 1 or c0 == 0 else "per-layer"
+            print("%s stream %d, %s form: %.4f %% of the norm1 ReLU signs borderline" % (tag, n, form, 100 * share))
+            if share > 0.01:
+                over.setdefault((x.mode, x.case, block, layer, "norm1"), []).append(n)
+                continue
+            rs, ms, ch, ks = st.conv1_dgrad16(G0[n], X[n], Sx[n], prm, d2s, c0, c1, take=pix)
+            gate("%s conv1 dgrad stream %d, %s form, layers %s, columns %d..%d" % (tag, n, form, [l + 1 for l in layers], c0, c1),
+                 _rms(G1[n][pix, c0:c1], rs, ms, ks), _rms(ch, rs, ms, ks), 2.0, e_whole=_rms(G1[n][:, c0:c1], ref, mag, keep), n=int(ks.sum()), yard="storage chain")
+    assert {k_: tuple(v) for k_, v in over.items()} == {k_: v for k_, v in DGRAD16_OVER_THE_CAP.items() if k_[:4] == (x.mode, x.case, block, layer)}, over
+
+    # ---- columns no segment of this layer covers: bit-equal to the snapshot, every stream (what "gsnap" is for)
+    cov = np.zeros(Ct, dtype=bool)
+    for _, c0, c1 in dr.dgrad1_segments(Lb, i, dr.CIN0[b]):
+        cov[c0:c1] = True
+    assert np.array_equal(G1[:, :, ~cov], G0[:, :, ~cov]) and not np.array_equal(G1[:, :, cov], G0[:, :, cov])
+
+    # ---- norm2's affine gradients over ALL streams: (float)s1[n] / (float)s2[n], one fp32 atomic per stream
+    db = dg = dbm = dgm = h1 = h2 = 0.0
+    for n in range(x.NS):
+        d64 = DY[n].astype(np.float64)
+        xh = (BT[n].astype(np.float64) - Sb[n].mean) * Sb[n].inv
+        _, s1, s2 = st.sums_before_store_slack(DY[n], BT[n], Sb[n])
+        db, dg, dbm, dgm, h1, h2 = db + d64.sum(0), dg + (d64 * xh).sum(0), dbm + np.abs(d64).sum(0), dgm + np.abs(d64 * xh).sum(0), h1 + s1, h2 + s2
+    pre = TRUNK + "denseblock%d.denselayer%d." % (block, layer)
+    bounded("%s norm2.bias gradient (%d roundings of sum |term| + the store)" % (tag, st.k_affine2(ts, x.NS, False)), grads[pre + "norm2.bias"], db, st.k_affine2(ts, x.NS, False) * sr.U * dbm + h1)
+    bounded("%s norm2.weight gradient (%d roundings of sum |term| + the store)" % (tag, st.k_affine2(ts, x.NS, True)), grads[pre + "norm2.weight"], dg, st.k_affine2(ts, x.NS, True) * sr.U * dgm + h2)
+
+    # ---- conv2 weight gradient on every 9th of the 9 * 128 im2col columns, conv1 weight gradient on 16 rows x <= 128 columns: ALL streams x pixels
+    cols = np.arange(0, 9 * 128, 9)
+    _, _, A64, A32 = st.conv2_wgrad_ops16(gs32, BT, H, H, g2, b2, Sb, cols)
+    _wgrad_gate("%s conv2 wgrad" % tag, dr.w2_grad_mat(grads[pre + "conv2.weight"])[:, cols], np.concatenate(gs64), A64, np.concatenate(gs32), A32, x.bwd)
+    del A64, A32
+    rows, cols = np.arange(0, 128, 8), np.arange(0, cin, max(1, cin // 128))
+    D64, D32, A64, A32 = st.conv1_wgrad_ops16(D2, X, g1, b1, Sx, rows, cols)
+    _wgrad_gate("%s conv1 wgrad K %d (%s)" % (tag, cin, VARIANTS16_BWD[x.case][b][6]), grads[pre + "conv1.weight"].reshape(128, cin)[np.ix_(rows, cols)], D64, A64, D32, A32, x.bwd)
