@@ -234,6 +234,30 @@ int smg_scene_argmax_objects(smg_engine* e, const float* q_dev, int64_t map_stri
                              int hm_size, const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
                              const int* map_group, int n_groups, int* idx_out_dev, float* val_out_dev, void* stream);
 
+/* The K best SEPARATED pixels per object: smg_scene_argmax_objects repeated greedily on the device, the scene-frame maps never
+ * written.  Every argument of smg_scene_argmax_objects means what it means there, and geometry, validity, values, selection and
+ * grouping are exactly that call's: steps 1-7 above, a value rounded to float32 once, selection by "not exactly 0" (-0.0 does not
+ * select, a NaN does), the union of the two mask terms, groups that need not be contiguous, the flattened index into
+ * [n_maps][hm_size][hm_size] of the whole call.
+ * idx_out_dev int32 [n_groups][K], val_out_dev float32 [n_groups][K], rank-major per group:
+ *   rank 0 of a group is smg_scene_argmax_objects' result for it, bit for bit;
+ *   rank j >= 1 is the best pixel by smg_argmax's rules (a NaN wins, the lowest flattened index on ties) among the group's selected
+ *     valid pixels that are not SUPPRESSED.  A candidate at heightmap pixel (iy, ix) - in ANY map of the group - is suppressed when
+ *     for some earlier pick (py, px) of the same group (py, px = the pick's index % hm_size^2, decoded) (iy - py)^2 + (ix - px)^2
+ *     <= radius^2, in integer arithmetic: a pick removes its disc in every rotation of its object.  radius = 0 removes only the
+ *     picked pixel, in all the group's maps;
+ *   when nothing is left, this rank and every later one are (-1, -inf).
+ * Every element of both outputs is written by every successful call.  K rounds on the caller's stream, each the selected walk (a
+ * pixel is tested against its group's earlier picks - read from idx_out_dev itself, no host round trip - before the geometry, so
+ * a suppressed pixel costs no double-precision arithmetic) and the grouped reduce into slot [group][j]; per-workgroup partials in a
+ * scratch the engine owns, no atomics: two identical calls are bit-identical, and the result equals the same greedy rule run on
+ * smg_scene_maps' output with the unselected pixels set to -inf.
+ * Returns -22 and launches nothing for every refusal of smg_scene_argmax_objects, for K < 1, K > 32 (kSceneTopK), radius < 0 and
+ * n_groups * K beyond int32. */
+int smg_scene_topk_objects(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host,
+                           int hm_size, const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
+                           const int* map_group, int n_groups, int K, int radius, int* idx_out_dev, float* val_out_dev, void* stream);
+
 /* Huber loss on K labelled heightmap pixels per pair, one-channel heads only (head_out != 1 returns -22): q and dq are
  * [n_pairs][1][OH][OW]; pixels_dev int32 [n_pairs][K][2] = (iy, ix); label_dev, weight_dev float32 [n_pairs][K] (weight_dev NULL =
  * all ones, a weight of exactly 0 masks its point).  With v_k the interpolated value of point k in its pair's rotation (double,
@@ -318,6 +342,20 @@ int smg_scene_class_argmax(smg_engine* e, const float* q_dev, int n_maps, const 
 int smg_scene_class_argmax_objects(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
                                    const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
                                    const int* map_group, int n_groups, int* idx_out_dev, float* val_out_dev, void* stream);
+
+/* smg_scene_topk_objects for the 3-class head - the K best separated pixels per object by P(class cls), cls in {0,1,2}: the
+ * arguments of smg_scene_class_argmax_objects plus K and radius, idx_out_dev int32 [n_groups][K], val_out_dev float32 [n_groups][K].
+ * The value of a pixel is scene_class_prob(c, cls), the expression smg_scene_class_maps stores; rank 0 of a group is
+ * smg_scene_class_argmax_objects' result, bit for bit; ranks j >= 1, suppression (in heightmap pixels, across all the group's maps),
+ * exhaustion (-1, -inf), "every element written", "no atomics, bit-identical between identical calls" are smg_scene_topk_objects',
+ * word for word, and the result equals that greedy rule run on plane cls of smg_scene_class_maps' output with the unselected pixels
+ * set to -inf.  A suppressed or unselected pixel costs no exponential.
+ * Returns -22 and launches nothing for every refusal of smg_scene_class_argmax_objects, for K < 1, K > 32, radius < 0 and
+ * n_groups * K beyond int32. */
+int smg_scene_class_topk_objects(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                                 const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
+                                 const int* map_group, int n_groups, int K, int radius, int* idx_out_dev, float* val_out_dev,
+                                 void* stream);
 
 /* Cross entropy (CrossEntropyLoss2d, class weights {1,1,0}) on K labelled heightmap pixels per pair: q and dq are
  * [n_pairs][3][OH][OW]; pixels_dev int32 [n_pairs][K][2] = (iy, ix); label_dev float32 [n_pairs][K] class indices as in

@@ -2,10 +2,11 @@
 // heightmap's pixel grid.  In the order of the file:
 //   scene_point / scene_interp / scene_class   the coordinate chain of one heightmap pixel and the value(s) of the map there: one Q
 //                                  value, or the softmax of the three interpolated logits of a 3-class head
-//   scene_walk<PLANES, ARGMAX, SELECT>  the one tiling behind smg_scene_maps / smg_scene_class_maps (ARGMAX false: the maps are
+//   scene_walk<PLANES, ARGMAX, SELECT, PICKS>  the one tiling behind smg_scene_maps / smg_scene_class_maps (ARGMAX false: the maps are
 //                                  stored), smg_scene_argmax / smg_scene_class_argmax (true: the best (rotation, pixel), nothing
 //                                  stored) and smg_scene_argmax_objects / smg_scene_class_argmax_objects (SELECT: every map on the
-//                                  pixels its masks select, one result per group of maps)
+//                                  pixels its masks select, one result per group of maps; PICKS: one round of smg_scene_topk_objects /
+//                                  smg_scene_class_topk_objects, which also skips the discs around the group's earlier picks)
 //   scene_values_kernel<PLANES>    smg_scene_values / smg_scene_class_values: the same value(s) at K LISTED pixels per map, the
 //                                  corners read from global memory, nothing staged
 //   SceneHuber / SceneCe           the per-point terms of the two losses, each written once
@@ -89,6 +90,12 @@ __device__ __forceinline__ float scene_class_prob(const SceneClass c, int cls) {
 // result the map competes for.
 struct SceneSelect { int a[kSceneMaps], b[kSceneMaps], group[kSceneMaps]; };
 
+// The greedy top-K of smg_scene_topk_objects / smg_scene_class_topk_objects: the most ranks a call may ask for, and what round n's
+// walk knows of the rounds before it - idx [n_groups][K] = the output itself, whose slots 0 .. n - 1 of every group are final, and
+// r2 = the squared suppression radius (clamped to 32 bits by the host).
+constexpr int kSceneTopK = 32;
+struct ScenePicks { const int* idx; int K, n; unsigned r2; };
+
 // Which of the 4 consecutive pixels i0 .. i0 + 3 mask `term` selects, OR-ed into s: a pixel is selected when its double is not
 // exactly 0 - the bit pattern without its sign is tested, so -0.0 does not select, a NaN does, and the value never enters any
 // arithmetic.  vec: two 16-byte loads (masks 16-byte aligned and hm^2 a multiple of 4, so the thread's 32 bytes are aligned and
@@ -122,17 +129,36 @@ __device__ __forceinline__ void scene_select4(const double* masks, int term, int
 // (scene_select4, `mvec` = its 16-byte loads).  The masks are read BEFORE the geometry: a pixel that is not selected is skipped like
 // an invalid one and never enters the double-precision chain - objects are compact, so whole waves skip it.  A workgroup without a
 // selected valid pixel leaves an empty slot (index 0x7fffffff).
-template <int PLANES, bool ARGMAX, bool SELECT = false>
+// PICKS (with SELECT; smg_scene_topk_objects, smg_scene_class_topk_objects): round pk->n of the greedy top-K.  The map's group has
+// pk->n earlier picks in pk->idx [n_groups][pk->K] (written by the reduces of the earlier rounds, earlier on the stream); a selected
+// pixel within the disc pk->r2 (squared radius, integer arithmetic) of one of them - in whichever map of the group it was picked -
+// is skipped like an unselected one, before the geometry.  The picks are decoded once per workgroup, idx % hm^2 -> (py << 16 | px),
+// into kSceneTopK ints of dynamic LDS behind the planes.  A group whose last pick is -1 has nothing left: the workgroup leaves an
+// empty slot and walks nothing.
+template <int PLANES, bool ARGMAX, bool SELECT = false, bool PICKS = false>
 __device__ __forceinline__ void scene_walk(const float* q, int64_t map_stride, int map0, const SceneAffine& aff, const SceneGeo& g, int cls,
                                            float* out, int vec4, float* part_val, int* part_idx,
-                                           const SceneSelect* sel = nullptr, const double* masks = nullptr, int mvec = 0) {
+                                           const SceneSelect* sel = nullptr, const double* masks = nullptr, int mvec = 0,
+                                           const ScenePicks* pk = nullptr) {
     static_assert(ARGMAX || !SELECT, "the selected walk is an argmax");
+    static_assert(SELECT || !PICKS, "the picks suppress selected pixels");
     extern __shared__ float sq[];
     __shared__ float bv[256];
     __shared__ int bi[256];
     const int t = threadIdx.x, m = blockIdx.y;
     const int P = g.OH * g.OW;
     const float* qm = q + (int64_t)(map0 + m) * map_stride;
+    if constexpr (PICKS) {
+        const int* mine = pk->idx + (int64_t)sel->group[m] * pk->K;
+        if (pk->n > 0 && mine[pk->n - 1] < 0) {             // (the same for every thread: nobody reaches the barrier)
+            if (t == 0) { const int slot = blockIdx.y * gridDim.x + blockIdx.x; part_val[slot] = -INFINITY; part_idx[slot] = 0x7fffffff; }
+            return;
+        }
+        if (t < pk->n) {                                    // (pk->n <= kSceneTopK; every earlier pick is >= 0 here)
+            const int at = mine[t] % (g.hm * g.hm), py = at / g.hm;
+            reinterpret_cast<unsigned*>(sq + PLANES * P)[t] = (unsigned)py << 16 | (unsigned)(at - py * g.hm);
+        }
+    }
     for (int i = t; i < PLANES * P; i += 256) sq[i] = qm[i];
     __syncthreads();
     const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
@@ -152,6 +178,21 @@ __device__ __forceinline__ void scene_walk(const float* q, int64_t map_stride, i
                 s[0] = s[1] = s[2] = s[3] = false;
                 scene_select4(masks, ta, npix, i0, mvec, s);
                 scene_select4(masks, tb, npix, i0, mvec, s);
+            }
+        }
+        if constexpr (PICKS) {
+            if (s[0] || s[1] || s[2] || s[3]) {
+                const unsigned* pick = reinterpret_cast<const unsigned*>(sq + PLANES * P);
+                for (int p = 0; p < pk->n; ++p) {
+                    const int py = (int)(pick[p] >> 16), px = (int)(pick[p] & 0xffffu);
+                    int y = iy, x = ix;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k, ++x) {
+                        if (x == g.hm) { x = 0; ++y; }
+                        const int dy = y - py, dx = x - px;        // (hm^2 < 2^31, checked by the host: each square fits an int, their sum 32 bits unsigned)
+                        if ((unsigned)(dy * dy) + (unsigned)(dx * dx) <= pk->r2) s[k] = false;
+                    }
+                }
             }
         }
 #pragma unroll
@@ -222,6 +263,18 @@ static __global__ __launch_bounds__(256) void scene_class_argmax_objects_kernel(
                                                                                 int mvec, float* part_val, int* part_idx) {
     scene_walk<3, true, true>(q, map_stride, map0, aff, g, cls, nullptr, 0, part_val, part_idx, &sel, masks, mvec);
 }
+// One round of smg_scene_topk_objects / smg_scene_class_topk_objects: the selected walk that also skips the discs of the group's
+// earlier picks (dynamic LDS: the planes + kSceneTopK ints).  Round 0 (pk.n == 0) walks what scene_argmax_objects_kernel walks.
+static __global__ __launch_bounds__(256) void scene_topk_objects_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                        const SceneSelect sel, const SceneGeo g, const double* masks, int mvec,
+                                                                        const ScenePicks pk, float* part_val, int* part_idx) {
+    scene_walk<1, true, true, true>(q, map_stride, map0, aff, g, 0, nullptr, 0, part_val, part_idx, &sel, masks, mvec, &pk);
+}
+static __global__ __launch_bounds__(256) void scene_class_topk_objects_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                              const SceneSelect sel, const SceneGeo g, int cls, const double* masks,
+                                                                              int mvec, const ScenePicks pk, float* part_val, int* part_idx) {
+    scene_walk<3, true, true, true>(q, map_stride, map0, aff, g, cls, nullptr, 0, part_val, part_idx, &sel, masks, mvec, &pk);
+}
 
 // The second launch of smg_scene_argmax / smg_scene_class_argmax: one workgroup reduces the n partials (thread t takes slots t,
 // t + 256, ... in that order) and, with `carry`, the result a previous group of maps left in the outputs.  Empty slots hold index
@@ -245,14 +298,16 @@ static __global__ __launch_bounds__(256) void scene_argmax_reduce_kernel(const f
 // The grouped form, the second launch of smg_scene_argmax_objects / smg_scene_class_argmax_objects: one workgroup per group (blockIdx.x) scans the slots of this
 // launch's `n_maps` maps (`tiles` slots each, map-major) whose map belongs to its group - thread t takes slots t, t + 256, ... in that
 // order - and, with `carry`, the result an earlier launch of maps left in the group's outputs.  Every group's pair is written: a
-// group without a map in any launch, or without a selected valid pixel, ends at index -1, value -inf.
+// group without a map in any launch, or without a selected valid pixel, ends at index -1, value -inf.  A group's pair lies at
+// element grp * stride of the outputs: stride 1 for the argmax, K for rank j of a top-K (the caller passes the outputs + j).
 static __global__ __launch_bounds__(256) void scene_argmax_group_reduce_kernel(const float* part_val, const int* part_idx, int tiles, int n_maps,
-                                                                               const SceneSelect sel, int carry, int* idx_out, float* val_out) {
+                                                                               const SceneSelect sel, int carry, int* idx_out, float* val_out, int stride) {
     __shared__ float bv[256];
     __shared__ int bi[256];
     const int t = threadIdx.x, grp = blockIdx.x;
+    idx_out += (int64_t)grp * stride; val_out += (int64_t)grp * stride;
     float best = -INFINITY; int at = 0x7fffffff;
-    if (t == 0 && carry && idx_out[grp] >= 0) { best = val_out[grp]; at = idx_out[grp]; }
+    if (t == 0 && carry && *idx_out >= 0) { best = *val_out; at = *idx_out; }
     for (int i = t; i < tiles * n_maps; i += 256) {
         if (sel.group[i / tiles] != grp) continue;
         const float x = part_val[i]; const int j = part_idx[i];
@@ -260,7 +315,7 @@ static __global__ __launch_bounds__(256) void scene_argmax_group_reduce_kernel(c
     }
     bv[t] = best; bi[t] = at;
     block_argmax(bv, bi, t);
-    if (t == 0) { idx_out[grp] = bi[0] == 0x7fffffff ? -1 : bi[0]; val_out[grp] = bv[0]; }
+    if (t == 0) { *idx_out = bi[0] == 0x7fffffff ? -1 : bi[0]; *val_out = bv[0]; }
 }
 
 // ---- the value of a map at K listed heightmap pixels (smg_scene_values, smg_scene_class_values) ----

@@ -725,16 +725,18 @@ class Trainer(object):
                                      group_of, groups, idx, val, stream)
         return self._best_scene_objects("best_scene_actions", depth_heightmap, mask_depth, is_ets, is_target, argmax)
 
-    def _best_scene_objects(self, what, depth_heightmap, mask_depth, is_ets, is_target, argmax):
-        """The body of best_scene_actions and best_scene_class_actions (the caller has checked method and geometry): one forward per
-        primitive, one argmax(engine, q, n_maps, affines, hm, masks, mask_a, mask_b, group of every map, n_groups, idx pointer, val
-        pointer, stream) on its maps, one read-back, and the host decode of index -> (object, rotation, pixel)."""
+    def _scene_object_picks(self, what, depth_heightmap, mask_depth, is_ets, is_target, pick, k=1):
+        """The loop behind best_scene_actions, ranked_scene_actions and their class forms (the caller has checked method and
+        geometry): one forward per primitive, one pick(engine, q, n_maps, affines, hm, masks, mask_a, mask_b, group of every map,
+        n_groups, idx pointer, val pointer, stream) on its maps - which writes `k` (index, value) pairs per group - and one
+        read-back.  Returns (calls = per primitive (first group, groups, maps per group), indices [all groups, k], values float64
+        [all groups, k], the pair list or None, hm); the maps behind the result stay in self._last_object_q."""
         n = int(np.asarray(mask_depth).shape[0])
         if n < 1:
             raise ValueError("%s: mask_depth holds no object" % what)
         hm = int(np.shape(depth_heightmap)[-1])
         n_pairs = n * (n - 1) // 2 if is_ets else 0
-        idx = val = None
+        idx = val = pair_list = None
         calls, kept = [], {}              # per primitive: (offset into idx / val, groups, maps per group)
         for style, name in ((0, "grasp"), (1, "suction"), (2, "pairs")):
             if style == 2:
@@ -746,26 +748,34 @@ class Trainer(object):
                 mask_a, mask_b = [g for g, _ in pair_list], [s_ for _, s_ in pair_list]
             else:
                 model, q, m, groups, per = self._object_maps(what, depth_heightmap, mask_depth, style, is_target)
-                rots = [(r, per) for k in range(groups) for r in range(per)]
-                mask_a, mask_b = [k for k in range(groups) for r in range(per)], [-1] * (groups * per)
+                rots = [(r, per) for k_ in range(groups) for r in range(per)]
+                mask_a, mask_b = [k_ for k_ in range(groups) for r in range(per)], [-1] * (groups * per)
             if idx is None:
-                idx = torch.empty(2 * n + n_pairs, dtype=torch.int32, device=q.device)
-                val = torch.empty(2 * n + n_pairs, dtype=torch.float32, device=q.device)
+                idx = torch.empty((2 * n + n_pairs, k), dtype=torch.int32, device=q.device)
+                val = torch.empty((2 * n + n_pairs, k), dtype=torch.float32, device=q.device)
             off = sum(c[1] for c in calls)
             eng, aff, _, stream = self._scene_call(model, q, depth_heightmap, rots)
-            argmax(eng, q, len(rots), aff, hm, m, mask_a, mask_b, [j // per for j in range(len(rots))], groups,
-                   idx[off:].data_ptr(), val[off:].data_ptr(), stream)
+            pick(eng, q, len(rots), aff, hm, m, mask_a, mask_b, [j // per for j in range(len(rots))], groups,
+                 idx[off:].data_ptr(), val[off:].data_ptr(), stream)
             calls.append((off, groups, per))
             kept[name] = q
         self._last_object_q = kept        # the maps behind the result, object-major: "grasp" / "suction" [n * R, HEAD_OUT, OH, OW], "pairs" [n_pairs, HEAD_OUT, OH, OW]
-        i_all, v_all = idx.cpu().numpy(), val.cpu().numpy().astype(np.float64)
+        return calls, idx.cpu().numpy(), val.cpu().numpy().astype(np.float64), pair_list, hm
+
+    @staticmethod
+    def _scene_entry(i, conf, hm, per):
+        """A flattened index into [groups * per, hm, hm] and its value -> (rotation, (iy, ix), conf), or None for index -1."""
+        i = int(i)
+        return None if i < 0 else ((i // (hm * hm)) % per, ((i // hm) % hm, i % hm), conf)
+
+    def _best_scene_objects(self, what, depth_heightmap, mask_depth, is_ets, is_target, argmax):
+        """The body of best_scene_actions and best_scene_class_actions (the caller has checked method and geometry):
+        _scene_object_picks with one pair per group, and the host decode of index -> (object, rotation, pixel)."""
+        calls, i_all, v_all, pair_list, hm = self._scene_object_picks(what, depth_heightmap, mask_depth, is_ets, is_target, argmax)
 
         def decode(off, groups, per):
             """Per group (rotation, (iy, ix), conf) or None, and the overall best group or None."""
-            entries = []
-            for k in range(groups):
-                i = int(i_all[off + k])
-                entries.append(None if i < 0 else ((i // (hm * hm)) % per, ((i // hm) % hm, i % hm), v_all[off + k]))
+            entries = [self._scene_entry(i_all[off + k, 0], v_all[off + k, 0], hm, per) for k in range(groups)]
             have = [k for k in range(groups) if entries[k] is not None]
             return entries, (have[int(np.argmax([entries[k][2] for k in have]))] if have else None)
         out = {"per_object": {}}
@@ -781,6 +791,79 @@ class Trainer(object):
             out["bestgs_conf"] = -np.inf
             if best is not None:
                 out.update(bestgs_num=pair_list[best], bestgs_pixel=entries[best][1], bestgs_conf=entries[best][2])
+        return out
+
+    @staticmethod
+    def _require_ranks(what, k, radius):
+        if int(k) != k or k < 1 or k > 32:
+            raise ValueError("%s: k must be an integer from 1 to 32 (the engine's kSceneTopK)" % what)
+        if int(radius) != radius or radius < 0:
+            raise ValueError("%s: radius must be an integer >= 0, in heightmap pixels" % what)
+        return int(k), int(radius)
+
+    def _ranked_scene_objects(self, what, depth_heightmap, mask_depth, k, is_ets, is_target, topk):
+        """The body of ranked_scene_actions and ranked_scene_class_actions (the caller has checked method, geometry, k and
+        radius): _scene_object_picks with k pairs per group and the host decode of every rank."""
+        calls, i_all, v_all, pair_list, hm = self._scene_object_picks(what, depth_heightmap, mask_depth, is_ets, is_target, topk, k)
+
+        def decode(off, groups, per):
+            lists = [[self._scene_entry(i_all[off + g, j], v_all[off + g, j], hm, per) for j in range(k)] for g in range(groups)]
+            return [[e for e in entries if e is not None] for entries in lists]        # (an exhausted group's -1 tail is dropped)
+
+        def order(lists, item):
+            """Every entry of the lists in the order repeated np.argmax takes them: a NaN first, then descending, then (group, rank)."""
+            flat = [(g, j, e) for g, entries in enumerate(lists) for j, e in enumerate(entries)]
+            flat.sort(key=lambda x: (0, 0.0, x[0], x[1]) if np.isnan(x[2][2]) else (1, -x[2][2], x[0], x[1]))
+            return [item(g, e) for g, _, e in flat]
+        out = {"per_object": {}, "pairs": [], "per_pair": [], "ranked": {"pairs": []}}
+        for call, name in zip(calls, ("grasp", "suction")):
+            out["per_object"][name] = decode(*call)
+            out["ranked"][name] = order(out["per_object"][name], lambda g, e: (g,) + e)
+        if len(calls) == 3:
+            out["pairs"], out["per_pair"] = list(pair_list), decode(*calls[2])
+            out["ranked"]["pairs"] = order(out["per_pair"], lambda g, e: (pair_list[g], e[1], e[2]))
+        return out
+
+    def ranked_scene_actions(self, depth_heightmap, mask_depth, k, radius, is_ets=True, is_target=False):
+        """best_scene_actions with up to `k` SEPARATED actions per object instead of one: the fallbacks a control loop tries on the
+        same object when the best pose turns out unreachable.  The same forwards - one per primitive, the maps kept in
+        self._last_object_q -, one smg_scene_topk_objects per primitive and one read-back.  Rank 0 of an object is
+        best_scene_actions' entry; rank j is the best of the object's own pixels (over all its rotations) that lie farther than
+        `radius` heightmap pixels from every earlier pick of that object, whichever rotation picked it (radius 0: any other pixel).
+        Returns per_object = {"grasp": [...], "suction": [...]}: per object a list of up to k (rotation, (iy, ix), conf) in rank
+        order, shorter (or empty) where the object has no pixel left; pairs = [(g, s)] and per_pair, the same lists per pair
+        (both [] with fewer than two objects or is_ets False); ranked = {"grasp": [(object, rotation, (iy, ix), conf)], "suction":
+        [...], "pairs": [((g, s), (iy, ix), conf)]}: all entries of a primitive by confidence, as repeated np.argmax orders them (a
+        NaN first, then descending, the lower (object, rank) on ties).  ranked_to_best turns one of them into the dict that
+        get_label_value_scene and backprop_scene read.  1 <= k <= 32 and radius >= 0, else ValueError."""
+        self._require_scene("ranked_scene_actions", depth_heightmap)
+        k, radius = self._require_ranks("ranked_scene_actions", k, radius)
+
+        def topk(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream):
+            eng.scene_topk_objects(q.data_ptr(), q.shape[2] * q.shape[3], n_maps, aff, hm, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
+                                   group_of, groups, k, radius, idx, val, stream)
+        return self._ranked_scene_objects("ranked_scene_actions", depth_heightmap, mask_depth, k, is_ets, is_target, topk)
+
+    @staticmethod
+    def ranked_to_best(ranked, primitive_action, j):
+        """Entry `j` of ranked_scene_actions' / ranked_scene_class_actions' result (the dict, or its "ranked" part) for the primitive
+        'grasp' / 'suction' / 'grasp_then_suction', as a dict with best_scene_actions' keys: the chosen primitive's bestg_id /
+        bests_id = (object, rotation) or bestgs_num = (g, s), its _pixel and _conf; the other primitives None / None / -inf (pair:
+        0).  A fallback that was executed goes through get_label_value_scene and backprop_scene as the best action would."""
+        if primitive_action not in _ACTION_STYLE:
+            raise ValueError("ranked_to_best: unknown primitive %r" % (primitive_action,))
+        lists = ranked.get("ranked", ranked)
+        name = ("grasp", "suction", "pairs")[_ACTION_STYLE[primitive_action]]
+        if int(j) != j or not 0 <= j < len(lists[name]):
+            raise ValueError("ranked_to_best: no entry %r among the %d ranked %s actions" % (j, len(lists[name]), primitive_action))
+        out = dict(bestg_id=None, bestg_pixel=None, bestg_conf=-np.inf, bests_id=None, bests_pixel=None, bests_conf=-np.inf,
+                   bestgs_num=None, bestgs_pixel=None, bestgs_conf=0)
+        e = lists[name][int(j)]
+        if name == "pairs":
+            out.update(bestgs_num=tuple(e[0]), bestgs_pixel=tuple(e[1]), bestgs_conf=e[2])
+        else:
+            key = "bestg" if name == "grasp" else "bests"
+            out.update({key + "_id": (e[0], e[1]), key + "_pixel": tuple(e[2]), key + "_conf": e[3]})
         return out
 
     @staticmethod
@@ -1035,6 +1118,23 @@ class Trainer(object):
             eng.scene_class_argmax_objects(q.data_ptr(), n_maps, aff, hm, cls, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
                                            group_of, groups, idx, val, stream)
         return self._best_scene_objects("best_scene_class_actions", depth_heightmap, mask_depth, is_ets, False, argmax)
+
+    def ranked_scene_class_actions(self, depth_heightmap, mask_depth, k, radius, is_ets=True, cls=0):
+        """ranked_scene_actions for the reactive net: best_scene_class_actions' forwards, one smg_scene_class_topk_objects per
+        primitive on the logits and one read-back - up to `k` pixels per object (per pair) by P(class `cls`), each farther than
+        `radius` heightmap pixels from the earlier picks of its object.  Returns ranked_scene_actions' dict (per_object, pairs,
+        per_pair, ranked); rank 0 of every list is best_scene_class_actions' entry.  Reactive method only; 1 <= k <= 32,
+        radius >= 0 and cls in {0, 1, 2}, else ValueError."""
+        self._require_class_objects("ranked_scene_class_actions", depth_heightmap, mask_depth)
+        if cls not in (0, 1, 2):
+            raise ValueError("ranked_scene_class_actions: cls must be 0, 1 or 2")
+        self._scene_geometry(np.shape(depth_heightmap)[-1])
+        k, radius = self._require_ranks("ranked_scene_class_actions", k, radius)
+
+        def topk(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream):
+            eng.scene_class_topk_objects(q.data_ptr(), n_maps, aff, hm, cls, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
+                                         group_of, groups, k, radius, idx, val, stream)
+        return self._ranked_scene_objects("ranked_scene_class_actions", depth_heightmap, mask_depth, k, is_ets, False, topk)
 
     def train_batch_scene_class_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, grad_sync=None,
                                        return_q=False):
