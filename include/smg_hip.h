@@ -258,6 +258,36 @@ int smg_scene_topk_objects(smg_engine* e, const float* q_dev, int64_t map_stride
                            int hm_size, const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
                            const int* map_group, int n_groups, int K, int radius, int* idx_out_dev, float* val_out_dev, void* stream);
 
+/* The COLLAPSED map - the picture between "all the maps" and "one pick": per group of maps and heightmap pixel the best value over
+ * the group's maps and which map gives it, the scene-frame maps never written.  q_dev, map_stride, n_maps, affine_host, hm_size,
+ * masks_dev, n_masks, map_mask_a, map_mask_b, map_group and n_groups mean what they mean for smg_scene_argmax_objects (selection by
+ * "not exactly 0": -0.0 does not select, a NaN does; the union of the two terms; both terms -1 = every pixel; groups that need not
+ * be contiguous), with one addition: masks_dev == NULL with n_masks == 0 is allowed - every term must then be -1.  That is the sweep
+ * form (one group, the R rotations of forward_dense), which has no masks tensor.
+ * val_out_dev float32 [n_groups][hm_size][hm_size], arg_out_dev int32 [n_groups][hm_size][hm_size].  For group g and pixel i the
+ * CANDIDATES are the maps m of the call with map_group[m] == g whose mask terms select i and in whose rotation i is valid (step 6):
+ *   val[g][i] = the float smg_scene_maps stores at (m, i) for the best candidate - the same expression, so bit for bit equal;
+ *   arg[g][i] = that m, an index into the call's maps (a caller turns it into a rotation with a table lookup);
+ *   "best" by smg_argmax's rules with m as the index: the lowest m on ties, the first NaN wins - np.argmax over the group's maps
+ *     in call order;
+ *   with no candidate the pair is (-inf, -1).
+ * Every element of both outputs is written by every successful call; a group without a map is (-inf, -1) everywhere.  Against
+ * smg_scene_argmax_objects: the maximum of val[g] is that call's value for group g, bit for bit; where the maximum is attained
+ * more than once the two calls may name different (map, pixel): the argmax orders by the flattened [m][pixel] index, this map is
+ * read lowest pixel first, then lowest map.
+ * One workgroup owns a tile of pixels of one group and visits the group's maps in ascending m, one map staged at a time; the masks
+ * are read before the geometry, so an unselected pixel costs no double-precision arithmetic.  Maps are launched 32 at a time; a
+ * launch after the first reads the outputs back as the running best, and leaves alone the groups it holds no map of.  No atomics,
+ * no scratch of the engine: two identical calls are bit-identical.  16-byte stores per output when hm_size^2 is a multiple of 4
+ * and that output is 16-byte aligned, else 4-byte ones.
+ * Returns -22 and launches nothing for a NULL pointer (masks_dev aside), head_out != 1, n_maps < 1, a negative map_stride,
+ * n_masks < 0, masks_dev NULL with n_masks > 0 or not NULL with n_masks == 0, a mask index outside [-1, n_masks), n_groups < 1, a
+ * group outside [0, n_groups), n_groups * hm_size^2 beyond int32, and the geometry refusals above (hm_size, a 1 x 1 map, an affine
+ * with a translation). */
+int smg_scene_best_maps(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
+                        const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
+                        int n_groups, float* val_out_dev, int* arg_out_dev, void* stream);
+
 /* Huber loss on K labelled heightmap pixels per pair, one-channel heads only (head_out != 1 returns -22): q and dq are
  * [n_pairs][1][OH][OW]; pixels_dev int32 [n_pairs][K][2] = (iy, ix); label_dev, weight_dev float32 [n_pairs][K] (weight_dev NULL =
  * all ones, a weight of exactly 0 masks its point).  With v_k the interpolated value of point k in its pair's rotation (double,
@@ -356,6 +386,18 @@ int smg_scene_class_topk_objects(smg_engine* e, const float* q_dev, int n_maps, 
                                  const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
                                  const int* map_group, int n_groups, int K, int radius, int* idx_out_dev, float* val_out_dev,
                                  void* stream);
+
+/* smg_scene_best_maps for the 3-class head - per group and heightmap pixel the largest P(class cls), cls in {0,1,2}, over the
+ * group's maps and the map that gives it: q_dev is [n_maps][3][OH][OW], every other argument, the candidates, the tie and NaN
+ * rules, the empty pair (-inf, -1), "every element written", the carry between launches and "no atomics, bit-identical between
+ * identical calls" are smg_scene_best_maps', word for word.  val[g][i] is the float smg_scene_class_maps(cls) stores at (m, i) for
+ * the best candidate - scene_class_prob of the interpolated logits, the same expression, bit for bit (a NaN in any of the twelve
+ * corner logits makes it NaN, and the first such map wins the pixel).  An unselected pixel costs no exponential.
+ * Returns -22 and launches nothing for every refusal of smg_scene_best_maps with head_out != 3 in place of head_out != 1 and no
+ * map_stride, and for cls outside {0,1,2}. */
+int smg_scene_class_best_maps(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                              const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
+                              int n_groups, float* val_out_dev, int* arg_out_dev, void* stream);
 
 /* Cross entropy (CrossEntropyLoss2d, class weights {1,1,0}) on K labelled heightmap pixels per pair: q and dq are
  * [n_pairs][3][OH][OW]; pixels_dev int32 [n_pairs][K][2] = (iy, ix); label_dev float32 [n_pairs][K] class indices as in

@@ -530,7 +530,7 @@ static SceneAffine scene_affine(const float* affine_host, int m0, int n) {
     return a;
 }
 
-// What the fourteen scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
+// What the sixteen scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
 // evaluates them and passes each one's text, or nullptr where it does not apply; the first that applies is reported as
 // "<who>: <text>"), the geometry, the one refusal that stands behind it (`after`), the n affines.  Then the device is selected and g
 // is valid.  Nothing has been launched when this returns non-zero.
@@ -679,6 +679,73 @@ int smg_scene_topk_objects(smg_engine* e, const float* q_dev, int64_t map_stride
                                 [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks& picks) {
         hipLaunchKernelGGL(scene_topk_objects_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float) + kSceneTopK * sizeof(int),
                            (hipStream_t)stream, q_dev, map_stride, m0, a, sel, g, masks_dev, mvec, picks, e->scene_val, e->scene_idx);
+    });
+}
+
+// smg_scene_best_maps / smg_scene_class_best_maps: per group and heightmap pixel the best value over the group's maps and the map
+// that gives it (scene_best_walk).  One body for both forms, as scene_argmax_objects is: `own` = the refusals of the entry point's
+// own arguments (head, n_maps, map_stride, cls), reported first; walk(grid, n, m0, affines, select, g, mvec, vvec, avec) launches
+// the form's kernel for maps [m0, m0 + n) on grid = (pixel tiles, groups).  No scratch of the engine and no second launch: the
+// outputs themselves carry the running best from one launch of kSceneMaps maps to the next, the first launch writes every element.
+// (gridDim.y = n_groups: a heightmap that passes scene_geometry has hm > 224, so n_groups * hm^2 < 2^31 keeps it below 65 536.)
+struct SceneBestArgs { const double* masks_dev; int n_masks; const int *map_mask_a, *map_mask_b, *map_group; int n_groups; float* val_out_dev; int* arg_out_dev; };
+extern "C++" template <class F>
+static int scene_best_maps(smg_engine* e, const char* who, const void* q_dev, std::initializer_list<const char*> own, int n_maps,
+                           const float* affine_host, int hm_size, const SceneBestArgs& o, void* stream, F walk) {
+    if (!e || !q_dev || !affine_host || !o.map_mask_a || !o.map_mask_b || !o.map_group || !o.val_out_dev || !o.arg_out_dev)
+        return fail(-22, std::string(who) + ": NULL argument");
+    for (const char* text : own)
+        if (text) return fail(-22, std::string(who) + ": " + text);
+    const bool counts_ok = n_maps >= 1 && o.n_masks >= 0 && o.n_groups >= 1;
+    const char *bad_mask = nullptr, *bad_group = nullptr;
+    for (int m = 0; counts_ok && m < n_maps; ++m) {
+        if (o.map_mask_a[m] < -1 || o.map_mask_a[m] >= o.n_masks || o.map_mask_b[m] < -1 || o.map_mask_b[m] >= o.n_masks) bad_mask = "a mask index outside [-1, n_masks)";
+        if (o.map_group[m] < 0 || o.map_group[m] >= o.n_groups) bad_group = "a group outside [0, n_groups)";
+    }
+    SceneGeo g;
+    if (int rc = scene_prelude(e, who, {o.n_masks < 0 ? "n_masks < 0" : nullptr,
+                                        o.n_masks > 0 && !o.masks_dev ? "masks_dev is NULL with n_masks > 0" : nullptr,
+                                        o.n_masks == 0 && o.masks_dev ? "masks_dev is not NULL with n_masks == 0" : nullptr,
+                                        o.n_groups < 1 ? "n_groups < 1" : nullptr, bad_mask, bad_group},
+                               hm_size, (int64_t)o.n_groups * hm_size * hm_size > 0x7fffffff ? "n_groups * hm_size^2 does not fit int32" : nullptr,
+                               affine_host, n_maps, &g)) return rc;
+    const dim3 grid((unsigned)(((int64_t)hm_size * hm_size + kSceneBestTile - 1) / kSceneBestTile), (unsigned)o.n_groups);
+    const int mvec = (int64_t)hm_size * hm_size % 4 == 0 && (reinterpret_cast<uintptr_t>(o.masks_dev) & 15) == 0;       // scene_vec4's split, on the masks
+    const int vvec = scene_vec4(hm_size, o.val_out_dev), avec = scene_vec4(hm_size, reinterpret_cast<const float*>(o.arg_out_dev));
+    return scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
+        SceneSelect sel;
+        for (int m = 0; m < kSceneMaps; ++m) {
+            const bool in = m < n;
+            sel.a[m] = in ? o.map_mask_a[m0 + m] : -1; sel.b[m] = in ? o.map_mask_b[m0 + m] : -1; sel.group[m] = in ? o.map_group[m0 + m] : -1;
+        }
+        walk(grid, n, m0, a, sel, g, mvec, vvec, avec);
+    });
+}
+
+int smg_scene_best_maps(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
+                        const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
+                        int n_groups, float* val_out_dev, int* arg_out_dev, void* stream) {
+    return scene_best_maps(e, "smg_scene_best_maps", q_dev,
+                           {e && e->head_out != 1 ? "values of a one-channel head (head_out == 1); the 3-class form is smg_scene_class_best_maps" : nullptr,
+                            n_maps < 1 || map_stride < 0 ? "n_maps < 1 or a negative map_stride" : nullptr},
+                           n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, val_out_dev, arg_out_dev}, stream,
+                           [&](dim3 grid, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, int vvec, int avec) {
+        hipLaunchKernelGGL(scene_best_maps_kernel, grid, dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
+                           q_dev, map_stride, m0, n, a, sel, g, masks_dev, mvec, val_out_dev, arg_out_dev, vvec, avec);
+    });
+}
+
+int smg_scene_class_best_maps(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                              const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
+                              int n_groups, float* val_out_dev, int* arg_out_dev, void* stream) {
+    return scene_best_maps(e, "smg_scene_class_best_maps", q_dev,
+                           {e && e->head_out != 3 ? "class probabilities need a 3-class head (head_out == 3)" : nullptr,
+                            n_maps < 1 ? "n_maps < 1" : nullptr, cls < 0 || cls > 2 ? "cls must be 0, 1 or 2" : nullptr},
+                           n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, val_out_dev, arg_out_dev}, stream,
+                           [&](dim3 grid, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, int vvec, int avec) {
+        const int64_t P3 = (int64_t)3 * g.OH * g.OW;
+        hipLaunchKernelGGL(scene_class_best_maps_kernel, grid, dim3(256), (size_t)P3 * sizeof(float), (hipStream_t)stream,
+                           q_dev, P3, m0, n, a, sel, g, cls, masks_dev, mvec, val_out_dev, arg_out_dev, vvec, avec);
     });
 }
 

@@ -7,6 +7,9 @@
 //                                  stored) and smg_scene_argmax_objects / smg_scene_class_argmax_objects (SELECT: every map on the
 //                                  pixels its masks select, one result per group of maps; PICKS: one round of smg_scene_topk_objects /
 //                                  smg_scene_class_topk_objects, which also skips the discs around the group's earlier picks)
+//   scene_best_walk<PLANES>        smg_scene_best_maps / smg_scene_class_best_maps: per GROUP of maps and heightmap pixel the best
+//                                  value over the group's maps and the map that gives it - parallel over groups and pixel tiles,
+//                                  the group's maps staged one at a time, launches of maps carried through the outputs
 //   scene_values_kernel<PLANES>    smg_scene_values / smg_scene_class_values: the same value(s) at K LISTED pixels per map, the
 //                                  corners read from global memory, nothing staged
 //   SceneHuber / SceneCe           the per-point terms of the two losses, each written once
@@ -316,6 +319,114 @@ static __global__ __launch_bounds__(256) void scene_argmax_group_reduce_kernel(c
     bv[t] = best; bi[t] = at;
     block_argmax(bv, bi, t);
     if (t == 0) { *idx_out = bi[0] == 0x7fffffff ? -1 : bi[0]; *val_out = bv[0]; }
+}
+
+// ---- the collapsed map: per group and heightmap pixel the best value over the group's maps and which map gives it ----
+// (smg_scene_best_maps, smg_scene_class_best_maps).  scene_walk is parallel over MAPS; this walk is parallel over GROUPS: one
+// workgroup = one tile of kSceneBestTile consecutive heightmap pixels of one group (blockIdx.y = group, blockIdx.x = tile), thread t
+// owns pixels 4 t .. 4 t + 3 of the tile and keeps their running best (value, map index of the whole call) in 8 registers.  The
+// workgroup visits the launch's maps in ascending order and skips those of other groups (sel.group[m], a kernel argument: the same
+// for every thread); a map of its own is staged in dynamic LDS (PLANES x OH x OW floats, one map at a time, a barrier before and
+// after) and every thread offers its pixels: the mask terms first (scene_select4; read again only when the terms differ from the
+// previous map's, which for an object's rotations they never do), then scene_point, then the very expression scene_walk stores -
+// scene_interp, or scene_class_prob(scene_class, cls) - compared by argmax_better with the map index as the index.  An unselected or
+// invalid pixel is skipped, not compared.  Maps are visited in ascending index, so the lowest map wins a tie and the first NaN stays.
+// The tile is 1024 pixels, not scene_walk's 8192: the groups are few (one for a sweep), so the pixel tiles have to supply the
+// workgroups - 400 per group at hm = 640 - and eight registers of running bests leave the double-precision chain its occupancy; the
+// price is that a map is staged once per 1024 pixels, 6 (18) loads per thread from L2 beside 4 pixels of the chain.
+// Launches after the first (map0 > 0) carry the outputs: the thread reads its four pairs back as the running best (index -1 =
+// nothing held), and a workgroup whose group has no map in this launch returns at once and leaves its pixels as they are.  In the
+// first launch it stores the empty pair (-inf, -1) instead.  That decision reads kernel arguments only and is taken before any
+// barrier.  Every element of both outputs is written by the first launch; no atomics, no scratch of the engine.
+// Stores (and the carry's loads) are one 16-byte unit per output when hm^2 is a multiple of 4 and that output is 16-byte aligned
+// (`vvec` / `avec`: scene_vec4's split, taken per output), else guarded 4-byte ones; `mvec` is the same split on the masks.
+constexpr int kSceneBestTile = 1024;     // heightmap pixels per workgroup: 256 threads x 4 consecutive pixels, one pass
+template <int PLANES>
+__device__ __forceinline__ void scene_best_walk(const float* q, int64_t map_stride, int map0, int n_maps, const SceneAffine& aff,
+                                                const SceneSelect& sel, const SceneGeo& g, int cls, const double* masks, int mvec,
+                                                float* val_out, int* arg_out, int vvec, int avec) {
+    extern __shared__ float sq[];
+    const int t = threadIdx.x, grp = blockIdx.y;
+    bool any = false;
+    for (int m = 0; m < n_maps; ++m) any = any || sel.group[m] == grp;
+    if (!any && map0 > 0) return;                       // (the same for every thread: nobody reaches a barrier)
+    const int P = g.OH * g.OW;
+    const int npix = g.hm * g.hm;                       // (the host refuses n_groups * hm^2 beyond 2^31 - 1)
+    const int i0 = blockIdx.x * kSceneBestTile + 4 * t;
+    const bool mine = i0 < npix;
+    const int iy0 = i0 / g.hm, ix0 = i0 - iy0 * g.hm;
+    float* vo = val_out + (int64_t)grp * npix + i0;
+    int* ao = arg_out + (int64_t)grp * npix + i0;
+    float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    int at[4] = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
+    if (map0 > 0 && mine) {                             // what the earlier launches left
+        int a[4] = {-1, -1, -1, -1};
+        if (vvec) { const float4 v = *reinterpret_cast<const float4*>(vo); best[0] = v.x; best[1] = v.y; best[2] = v.z; best[3] = v.w; }
+        else
+            for (int k = 0; k < 4; ++k) if (i0 + k < npix) best[k] = vo[k];
+        if (avec) { const int4 v = *reinterpret_cast<const int4*>(ao); a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w; }
+        else
+            for (int k = 0; k < 4; ++k) if (i0 + k < npix) a[k] = ao[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) at[k] = a[k] < 0 ? 0x7fffffff : a[k];
+    }
+    int la = -2, lb = -2;                               // the mask terms s[] was read for (-2: none yet)
+    bool s[4] = {true, true, true, true};
+    for (int m = 0; m < n_maps; ++m) {
+        if (sel.group[m] != grp) continue;              // (uniform)
+        __syncthreads();                                // the previous map's readers are done
+        const float* qm = q + (int64_t)(map0 + m) * map_stride;
+        for (int i = t; i < PLANES * P; i += 256) sq[i] = qm[i];
+        __syncthreads();
+        if (mine) {
+            const int ta = sel.a[m], tb = sel.b[m];
+            if (ta != la || tb != lb) {
+                la = ta; lb = tb;
+                const bool every = ta < 0 && tb < 0;
+                s[0] = s[1] = s[2] = s[3] = every;
+                if (!every) {
+                    scene_select4(masks, ta, npix, i0, mvec, s);
+                    scene_select4(masks, tb, npix, i0, mvec, s);
+                }
+            }
+            const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
+            int iy = iy0, ix = ix0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k, ++ix) {
+                if (ix == g.hm) { ix = 0; ++iy; }
+                if (i0 + k < npix && s[k]) {
+                    const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
+                    if (p.valid) {
+                        float v;
+                        if constexpr (PLANES == 1) v = (float)scene_interp(p, sq, g.OW);
+                        else v = scene_class_prob(scene_class(p, sq, P, g.OW), cls);
+                        if (argmax_better(v, map0 + m, best[k], at[k])) { best[k] = v; at[k] = map0 + m; }
+                    }
+                }
+            }
+        }
+    }
+    if (!mine) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) if (at[k] == 0x7fffffff) at[k] = -1;
+    if (vvec) *reinterpret_cast<float4*>(vo) = make_float4(best[0], best[1], best[2], best[3]);
+    else
+        for (int k = 0; k < 4; ++k) if (i0 + k < npix) vo[k] = best[k];
+    if (avec) *reinterpret_cast<int4*>(ao) = make_int4(at[0], at[1], at[2], at[3]);
+    else
+        for (int k = 0; k < 4; ++k) if (i0 + k < npix) ao[k] = at[k];
+}
+static __global__ __launch_bounds__(256) void scene_best_maps_kernel(const float* q, int64_t map_stride, int map0, int n_maps, const SceneAffine aff,
+                                                                     const SceneSelect sel, const SceneGeo g, const double* masks, int mvec,
+                                                                     float* val_out, int* arg_out, int vvec, int avec) {
+    scene_best_walk<1>(q, map_stride, map0, n_maps, aff, sel, g, 0, masks, mvec, val_out, arg_out, vvec, avec);
+}
+// smg_scene_class_best_maps: the same walk on the three logit planes (dynamic LDS 3 x OH x OW floats); an unselected pixel never
+// reaches scene_class and its three double exponentials.
+static __global__ __launch_bounds__(256) void scene_class_best_maps_kernel(const float* q, int64_t map_stride, int map0, int n_maps, const SceneAffine aff,
+                                                                           const SceneSelect sel, const SceneGeo g, int cls, const double* masks, int mvec,
+                                                                           float* val_out, int* arg_out, int vvec, int avec) {
+    scene_best_walk<3>(q, map_stride, map0, n_maps, aff, sel, g, cls, masks, mvec, val_out, arg_out, vvec, avec);
 }
 
 // ---- the value of a map at K listed heightmap pixels (smg_scene_values, smg_scene_class_values) ----

@@ -1358,6 +1358,109 @@ class Trainer(object):
         return self._scene_values_pairs(depth_heightmap, mask_depth, pixels, False,
                                         self._class_values_reader("scene_class_object_pair_values", cls, logits), return_device)
 
+    # ---- the collapsed map: per heightmap pixel the best value over the rotations and the rotation that gives it -----------------
+    @staticmethod
+    def _best_maps_out(val, arg, rotations, return_device):
+        """The kernel's (value, map index) pair -> (conf, rotation): `rotations` = the rotation of every map of the call, looked
+        up on the device (index -1, no candidate, stays -1).  Host: float64 and int32; device: the float32 and int32 tensors."""
+        table = torch.tensor([-1] + [int(r) for r in rotations], dtype=torch.int32, device=arg.device)
+        rot = table[(arg + 1).long()]
+        if return_device:
+            return val, rot
+        return val.cpu().numpy().astype(np.float64), rot.cpu().numpy()
+
+    def _best_rotation_sweep(self, what, model, depth_heightmap, style, forward, best_maps, return_device):
+        """The body of best_rotation_map and best_rotation_class_map (the caller has checked method and geometry): `forward()` -
+        the sweep's one engine call, maps [R, ...] on the device - and one best_maps(engine, q, R, affines, hm, masks None, mask_a,
+        mask_b, groups, n_groups 1, val pointer, arg pointer, stream) with every term -1: one group, no masks tensor."""
+        if style not in (0, 1):
+            raise ValueError("%s: styles 0 (grasp) and 1 (suction); style 2 evaluates rotation 0 alone, there is nothing to collapse" % what)
+        q = forward()
+        R = int(q.shape[0])
+        rots = self._scene_rotations(model, style, -1)
+        eng, aff, hm, stream = self._scene_call(model, q, depth_heightmap, rots)
+        val = torch.empty((1, hm, hm), dtype=torch.float32, device=q.device)
+        arg = torch.empty((1, hm, hm), dtype=torch.int32, device=q.device)
+        best_maps(eng, q, R, aff, hm, None, [-1] * R, [-1] * R, [0] * R, 1, val.data_ptr(), arg.data_ptr(), stream)
+        return self._best_maps_out(val[0], arg[0], [r for r, _ in rots], return_device)
+
+    def _best_rotation_objects(self, what, depth_heightmap, mask_depth, style, is_target, on_object, best_maps, return_device):
+        """The body of best_rotation_object_maps and best_rotation_class_object_maps: _object_maps' one engine call, then one
+        best_maps over its n * R maps, object-major, the group = the object, on the masks tensor that forward used (on_object) or
+        on every pixel (no masks tensor).  The maps stay in self._last_object_q["grasp" / "suction"]."""
+        model, q, m, n, R = self._object_maps(what, depth_heightmap, mask_depth, style, is_target)
+        self._keep_object_q("grasp" if style == 0 else "suction", q)
+        eng, aff, hm, stream = self._scene_call(model, q, depth_heightmap, [(r, R) for k in range(n) for r in range(R)])
+        val = torch.empty((n, hm, hm), dtype=torch.float32, device=q.device)
+        arg = torch.empty((n, hm, hm), dtype=torch.int32, device=q.device)
+        mask_a = [k for k in range(n) for r in range(R)] if on_object else [-1] * (n * R)
+        best_maps(eng, q, n * R, aff, hm, m if on_object else None, mask_a, [-1] * (n * R), [j // R for j in range(n * R)], n,
+                  val.data_ptr(), arg.data_ptr(), stream)
+        return self._best_maps_out(val, arg, [r for k in range(n) for r in range(R)], return_device)
+
+    @staticmethod
+    def _q_best_maps(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, val, arg, stream):
+        eng.scene_best_maps(q.data_ptr(), q.shape[-2] * q.shape[-1], n_maps, aff, hm, None if m is None else m.data_ptr(),
+                            0 if m is None else int(m.shape[0]), mask_a, mask_b, group_of, groups, val, arg, stream)
+
+    @staticmethod
+    def _class_best_maps(cls):
+        def best_maps(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, val, arg, stream):
+            eng.scene_class_best_maps(q.data_ptr(), n_maps, aff, hm, cls, None if m is None else m.data_ptr(),
+                                      0 if m is None else int(m.shape[0]), mask_a, mask_b, group_of, groups, val, arg, stream)
+        return best_maps
+
+    def best_rotation_map(self, depth_heightmap, m_depth_heightmap, style=0, is_target=False, return_device=False):
+        """The affordance picture of the sweep: for every heightmap pixel the best Q value over the rotations and the rotation that
+        gives it -> (conf float64 [hm, hm], rotation int32 [hm, hm]), equal to forward_scene(...) reduced by max / argmax over
+        axis 0 (the lowest rotation on ties, the first NaN wins); (-inf, -1) where no rotation has a window of the head.  One
+        forward_dense sweep and one smg_scene_best_maps with one group and no masks: the R scene-frame maps are never written.  A
+        caller multiplies a per-pixel prior of its own - reachability, clearance - into conf on the device (`return_device`: the
+        float32 and int32 tensors) and picks from the product.  Styles 0 / 1: style 2 and the object pairs evaluate rotation 0
+        alone, so there is nothing to collapse (forward_scene gives that one map).  Reinforcement method, heightmaps larger than
+        224^2."""
+        self._require_scene("best_rotation_map", depth_heightmap)
+        return self._best_rotation_sweep(
+            "best_rotation_map", self.model_target if is_target else self.model, depth_heightmap, style,
+            lambda: self.forward_dense(depth_heightmap, m_depth_heightmap, style, is_target, return_device=True),
+            self._q_best_maps, return_device)
+
+    def best_rotation_object_maps(self, depth_heightmap, mask_depth, style=0, is_target=False, on_object=True, return_device=False):
+        """best_rotation_map per object -> (conf float64 [n, hm, hm], rotation int32 [n, hm, hm]): forward_objects_dense's single
+        engine call and one smg_scene_best_maps over its n * R maps, the group = the object; the n * R scene-frame maps are never
+        written.  on_object restricts object k to its own pixels (mask_depth[k] != 0), read from the masks tensor the forward used;
+        False gives every pixel with a window.  Elsewhere the pair is (-inf, -1).  The maximum of conf[k] is best_scene_actions'
+        per_object confidence of object k.  The maps stay in self._last_object_q["grasp" / "suction"], as after
+        best_scene_actions.  Styles 0 / 1 (the pairs of style 2 have one rotation: nothing to collapse).  Reinforcement method,
+        heightmaps larger than 224^2."""
+        self._require_scene("best_rotation_object_maps", depth_heightmap)
+        return self._best_rotation_objects("best_rotation_object_maps", depth_heightmap, mask_depth, style, is_target, on_object,
+                                           self._q_best_maps, return_device)
+
+    def best_rotation_class_map(self, depth_heightmap, m_depth_heightmap, style=0, cls=0, return_device=False):
+        """best_rotation_map for the reactive net: per heightmap pixel the largest P(class `cls`) over the rotations - the logits
+        interpolated, the softmax at the pixel, forward_scene_class_maps(cls=cls) reduced by max / argmax over axis 0 - and its
+        rotation.  One forward_class_maps sweep, one smg_scene_class_best_maps.  There is no is_target: the reactive method has no
+        target net.  Styles 0 / 1, cls in {0, 1, 2}, heightmaps larger than 224^2."""
+        self._require_scene_class("best_rotation_class_map", depth_heightmap)
+        if cls not in (0, 1, 2):
+            raise ValueError("best_rotation_class_map: cls must be 0, 1 or 2")
+        return self._best_rotation_sweep(
+            "best_rotation_class_map", self.model, depth_heightmap, style,
+            lambda: self.forward_class_maps(depth_heightmap, m_depth_heightmap, style, logits=True, return_device=True),
+            self._class_best_maps(cls), return_device)
+
+    def best_rotation_class_object_maps(self, depth_heightmap, mask_depth, style=0, on_object=True, cls=0, return_device=False):
+        """best_rotation_object_maps for the reactive net: forward_class_objects' single engine call and one
+        smg_scene_class_best_maps on its logits; conf is P(class `cls`).  The method and geometry refusals are
+        best_scene_class_actions'; the logits stay in self._last_object_q["grasp" / "suction"]."""
+        self._require_class_objects("best_rotation_class_object_maps", depth_heightmap, mask_depth)
+        if cls not in (0, 1, 2):
+            raise ValueError("best_rotation_class_object_maps: cls must be 0, 1 or 2")
+        self._scene_geometry(np.shape(depth_heightmap)[-1])
+        return self._best_rotation_objects("best_rotation_class_object_maps", depth_heightmap, mask_depth, style, False, on_object,
+                                           self._class_best_maps(cls), return_device)
+
     # ---- the two calls that close the loop of code/main.py on a heightmap larger than 224^2 --------------------------------------
     @staticmethod
     def _scene_action(what, best, action, depth_heightmap, mask_depth):
