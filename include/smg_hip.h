@@ -258,6 +258,42 @@ int smg_scene_topk_objects(smg_engine* e, const float* q_dev, int64_t map_stride
                            int hm_size, const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
                            const int* map_group, int n_groups, int K, int radius, int* idx_out_dev, float* val_out_dev, void* stream);
 
+/* EXPLORATION: n_draws Boltzmann draws per object - (map, pixel) drawn with probability proportional to exp(beta * Q) over the
+ * object's selected valid pixels - on the device, the scene-frame maps never written.  Every argument shared with
+ * smg_scene_argmax_objects means what it means there, and geometry, validity, values, selection, the union of the two mask terms,
+ * groups that need not be contiguous and the flattened index into [n_maps][hm_size][hm_size] of the whole call are that call's.
+ * beta = 1 / temperature: beta = 0 draws uniformly among the group's candidates, a large beta approaches the argmax.
+ * The draw uses the Gumbel-max identity: argmax_i (beta v_i + G_i) with independent standard Gumbel noise G_i is a draw from
+ * softmax(beta v).  The noise is a counter-based hash, so the call is a pure function of its arguments.  For a candidate with
+ * flattened index i (i < 2^31), draw d >= 0 and the 64-bit seed, all integers mod 2^64:
+ *     x = seed + (d << 32) + i
+ *     mix(x): x += 0x9E3779B97F4A7C15; z = x
+ *             z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9
+ *             z = (z ^ z >> 27) * 0x94D049BB133111EB
+ *             return z ^ z >> 31                         (the splitmix64 finaliser)
+ *     h = mix(mix(x))
+ *     u = ((h >> 12) + 0.5) * 2^-52                      (double, exact; strictly inside (0, 1), at most 1 - 2^-53)
+ *     G = -log(-log(u))                                  (double; finite, in about [-3.61, 36.74])
+ * and the SCORE of the candidate with map value v (the float32 smg_scene_maps stores there) is
+ *     s = (float) fma(beta, (double) v, G)               (rounded to float32 once)
+ * formed by one device function (scene_sample_score) wherever a kernel needs it.
+ * idx_out_dev int32 [n_groups][n_draws], val_out_dev float32 [n_groups][n_draws], draw-major per group: for group g and draw d the
+ * candidate with the best score among the group's selected valid pixels, by smg_argmax's rules applied to the SCORE (the lowest
+ * flattened index on ties; a NaN value gives a NaN score and wins).  idx is its flattened index, val the float smg_scene_maps
+ * stores there, bit for bit - the value, not the score.  A group without a map or without a candidate gets (-1, -inf) in every
+ * draw; every element of both outputs is written by every successful call.  Draw d does not depend on n_draws, and the draws do
+ * not depend on one another.
+ * n_draws rounds on the caller's stream, each the selected walk (masks before geometry: only a selected valid pixel pays the
+ * hash and the two logarithms) and the grouped reduce into slot [group][d]; the reduce recomputes the scores from (value, index),
+ * so the outputs carry the running winner between launches of 32 maps and nothing beyond the engine's per-workgroup partials is
+ * needed.  No atomics: two identical calls are bit-identical.
+ * Returns -22 and launches nothing for every refusal of smg_scene_argmax_objects, for n_draws < 1, n_draws > 32 (kSceneDraws),
+ * n_groups * n_draws beyond int32, and a beta that is negative, NaN or infinite. */
+int smg_scene_sample_objects(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host,
+                             int hm_size, const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
+                             const int* map_group, int n_groups, int n_draws, double beta, uint64_t seed,
+                             int* idx_out_dev, float* val_out_dev, void* stream);
+
 /* The COLLAPSED map - the picture between "all the maps" and "one pick": per group of maps and heightmap pixel the best value over
  * the group's maps and which map gives it, the scene-frame maps never written.  q_dev, map_stride, n_maps, affine_host, hm_size,
  * masks_dev, n_masks, map_mask_a, map_mask_b, map_group and n_groups mean what they mean for smg_scene_argmax_objects (selection by
@@ -386,6 +422,18 @@ int smg_scene_class_topk_objects(smg_engine* e, const float* q_dev, int n_maps, 
                                  const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
                                  const int* map_group, int n_groups, int K, int radius, int* idx_out_dev, float* val_out_dev,
                                  void* stream);
+
+/* smg_scene_sample_objects for the 3-class head - n_draws Boltzmann draws per object by P(class cls), cls in {0,1,2}: the arguments
+ * of smg_scene_class_argmax_objects plus n_draws, beta and seed, idx_out_dev int32 [n_groups][n_draws], val_out_dev float32
+ * [n_groups][n_draws].  The value v of a candidate is scene_class_prob(c, cls), the expression smg_scene_class_maps stores; the
+ * noise, the score, the rules, (-1, -inf), "every element written", "draw d does not depend on n_draws" and "no atomics,
+ * bit-identical between identical calls" are smg_scene_sample_objects', word for word.  An unselected pixel costs no exponential.
+ * Returns -22 and launches nothing for every refusal of smg_scene_class_argmax_objects, for n_draws < 1, n_draws > 32,
+ * n_groups * n_draws beyond int32, and a beta that is negative, NaN or infinite. */
+int smg_scene_class_sample_objects(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                                   const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
+                                   const int* map_group, int n_groups, int n_draws, double beta, uint64_t seed,
+                                   int* idx_out_dev, float* val_out_dev, void* stream);
 
 /* smg_scene_best_maps for the 3-class head - per group and heightmap pixel the largest P(class cls), cls in {0,1,2}, over the
  * group's maps and the map that gives it: q_dev is [n_maps][3][OH][OW], every other argument, the candidates, the tie and NaN

@@ -530,7 +530,7 @@ static SceneAffine scene_affine(const float* affine_host, int m0, int n) {
     return a;
 }
 
-// What the sixteen scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
+// What the eighteen scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
 // evaluates them and passes each one's text, or nullptr where it does not apply; the first that applies is reported as
 // "<who>: <text>"), the geometry, the one refusal that stands behind it (`after`), the n affines.  Then the device is selected and g
 // is valid.  Nothing has been launched when this returns non-zero.
@@ -619,11 +619,14 @@ int smg_scene_argmax(smg_engine* e, const float* q_dev, int64_t map_stride, int 
 // [m0, m0 + n).  The greedy top-K is sequential in the rank: K rounds on the caller's stream, round j = the walk over all launches
 // of maps with the group's picks 0 .. j - 1 suppressed (picks.n = j; the walk reads them from idx_out_dev itself, which the reduces
 // of the earlier rounds wrote earlier on the stream) and the reduce into slot [group][j].  The argmax forms are K = 1: one round,
-// no picks, and a walk that ignores them.
+// no picks, and a walk that ignores them.  The Boltzmann sample (smg_scene_sample_objects, smg_scene_class_sample_objects; `noise`
+// not NULL, K = n_draws, radius 0) uses the same rounds: round d = the walk by the score of draw d (noise.d = d) and
+// scene_sample_group_reduce_kernel into slot [group][d]; its rounds do not read one another's results.
 struct SceneObjectArgs { const double* masks_dev; int n_masks; const int *map_mask_a, *map_mask_b, *map_group; int n_groups; int* idx_out_dev; float* val_out_dev; };
 extern "C++" template <class F>
 static int scene_argmax_objects(smg_engine* e, const char* who, const void* q_dev, std::initializer_list<const char*> own, int n_maps,
-                                const float* affine_host, int hm_size, const SceneObjectArgs& o, int K, int radius, void* stream, F walk) {
+                                const float* affine_host, int hm_size, const SceneObjectArgs& o, int K, int radius,
+                                const SceneNoise* noise, void* stream, F walk) {
     if (!e || !q_dev || !affine_host || !o.masks_dev || !o.map_mask_a || !o.map_mask_b || !o.map_group || !o.idx_out_dev || !o.val_out_dev)
         return fail(-22, std::string(who) + ": NULL argument");
     for (const char* text : own)
@@ -636,24 +639,31 @@ static int scene_argmax_objects(smg_engine* e, const char* who, const void* q_de
     }
     SceneGeo g;
     if (int rc = scene_prelude(e, who, {o.n_masks < 1 ? "n_masks < 1" : nullptr, o.n_groups < 1 ? "n_groups < 1" : nullptr, bad_mask, bad_group,
-                                        K < 1 ? "K < 1" : nullptr, K > kSceneTopK ? "K exceeds kSceneTopK (32)" : nullptr,
+                                        K < 1 ? (noise ? "n_draws < 1" : "K < 1") : nullptr,
+                                        K > (noise ? kSceneDraws : kSceneTopK) ? (noise ? "n_draws exceeds kSceneDraws (32)" : "K exceeds kSceneTopK (32)") : nullptr,
                                         radius < 0 ? "radius < 0" : nullptr,
-                                        (int64_t)o.n_groups * K > 0x7fffffff ? "n_groups * K does not fit int32" : nullptr},
+                                        (int64_t)o.n_groups * K > 0x7fffffff ? (noise ? "n_groups * n_draws does not fit int32" : "n_groups * K does not fit int32") : nullptr,
+                                        noise && !(noise->beta >= 0.0 && noise->beta < INFINITY) ? "beta must be finite and not negative" : nullptr},
                                hm_size, scene_index_fits(n_maps, hm_size), affine_host, n_maps, &g)) return rc;
     const int tiles = scene_tiles(hm_size);
     const int mvec = (int64_t)hm_size * hm_size % 4 == 0 && (reinterpret_cast<uintptr_t>(o.masks_dev) & 15) == 0;       // scene_vec4's split, on the masks
     const unsigned r2 = (unsigned)std::min<int64_t>((int64_t)radius * radius, 0xffffffffll);        // (no two pixels lie farther apart: hm^2 < 2^31)
     for (int j = 0; j < K; ++j) {
         const ScenePicks picks{o.idx_out_dev, K, j, r2};
+        const SceneNoise nz{noise ? noise->seed : 0ull, noise ? noise->beta : 0.0, j};
         if (int rc = scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
                 SceneSelect sel;
                 for (int m = 0; m < kSceneMaps; ++m) {
                     const bool in = m < n;
                     sel.a[m] = in ? o.map_mask_a[m0 + m] : -1; sel.b[m] = in ? o.map_mask_b[m0 + m] : -1; sel.group[m] = in ? o.map_group[m0 + m] : -1;
                 }
-                walk(tiles, n, m0, a, sel, g, mvec, picks);
-                hipLaunchKernelGGL(scene_argmax_group_reduce_kernel, dim3(o.n_groups), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
-                                   (const int*)e->scene_idx, tiles, n, sel, m0 > 0 ? 1 : 0, o.idx_out_dev + j, o.val_out_dev + j, K);
+                walk(tiles, n, m0, a, sel, g, mvec, picks, nz);
+                if (noise)
+                    hipLaunchKernelGGL(scene_sample_group_reduce_kernel, dim3(o.n_groups), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
+                                       (const int*)e->scene_idx, tiles, n, sel, m0 > 0 ? 1 : 0, nz, o.idx_out_dev + j, o.val_out_dev + j, K);
+                else
+                    hipLaunchKernelGGL(scene_argmax_group_reduce_kernel, dim3(o.n_groups), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
+                                       (const int*)e->scene_idx, tiles, n, sel, m0 > 0 ? 1 : 0, o.idx_out_dev + j, o.val_out_dev + j, K);
             })) return rc;
     }
     return 0;
@@ -663,8 +673,8 @@ int smg_scene_argmax_objects(smg_engine* e, const float* q_dev, int64_t map_stri
                              const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
                              int n_groups, int* idx_out_dev, float* val_out_dev, void* stream) {
     return scene_argmax_objects(e, "smg_scene_argmax_objects", q_dev, {n_maps < 1 || map_stride < 0 ? "n_maps < 1 or a negative map_stride" : nullptr},
-                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, 1, 0, stream,
-                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks&) {
+                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, 1, 0, nullptr, stream,
+                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks&, const SceneNoise&) {
         hipLaunchKernelGGL(scene_argmax_objects_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
                            q_dev, map_stride, m0, a, sel, g, masks_dev, mvec, e->scene_val, e->scene_idx);
     });
@@ -675,10 +685,23 @@ int smg_scene_topk_objects(smg_engine* e, const float* q_dev, int64_t map_stride
                            const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
                            int n_groups, int K, int radius, int* idx_out_dev, float* val_out_dev, void* stream) {
     return scene_argmax_objects(e, "smg_scene_topk_objects", q_dev, {n_maps < 1 || map_stride < 0 ? "n_maps < 1 or a negative map_stride" : nullptr},
-                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, K, radius, stream,
-                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks& picks) {
+                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, K, radius, nullptr, stream,
+                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks& picks, const SceneNoise&) {
         hipLaunchKernelGGL(scene_topk_objects_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float) + kSceneTopK * sizeof(int),
                            (hipStream_t)stream, q_dev, map_stride, m0, a, sel, g, masks_dev, mvec, picks, e->scene_val, e->scene_idx);
+    });
+}
+
+// n_draws Boltzmann draws per group: every round's walk keeps the candidate with the best Gumbel-perturbed score (scene_sample_score).
+int smg_scene_sample_objects(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
+                             const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
+                             int n_groups, int n_draws, double beta, uint64_t seed, int* idx_out_dev, float* val_out_dev, void* stream) {
+    const SceneNoise noise{(unsigned long long)seed, beta, 0};
+    return scene_argmax_objects(e, "smg_scene_sample_objects", q_dev, {n_maps < 1 || map_stride < 0 ? "n_maps < 1 or a negative map_stride" : nullptr},
+                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, n_draws, 0, &noise, stream,
+                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks&, const SceneNoise& nz) {
+        hipLaunchKernelGGL(scene_sample_objects_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
+                           q_dev, map_stride, m0, a, sel, g, masks_dev, mvec, nz, e->scene_val, e->scene_idx);
     });
 }
 
@@ -848,8 +871,8 @@ int smg_scene_class_argmax_objects(smg_engine* e, const float* q_dev, int n_maps
     return scene_argmax_objects(e, "smg_scene_class_argmax_objects", q_dev,
                                 {e && e->head_out != 3 ? "class probabilities need a 3-class head (head_out == 3)" : nullptr,
                                  n_maps < 1 ? "n_maps < 1" : nullptr, cls < 0 || cls > 2 ? "cls must be 0, 1 or 2" : nullptr},
-                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, 1, 0, stream,
-                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks&) {
+                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, 1, 0, nullptr, stream,
+                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks&, const SceneNoise&) {
         const int64_t P3 = (int64_t)3 * g.OH * g.OW;
         hipLaunchKernelGGL(scene_class_argmax_objects_kernel, dim3(tiles, n), dim3(256), (size_t)P3 * sizeof(float), (hipStream_t)stream,
                            q_dev, P3, m0, a, sel, g, cls, masks_dev, mvec, e->scene_val, e->scene_idx);
@@ -863,11 +886,27 @@ int smg_scene_class_topk_objects(smg_engine* e, const float* q_dev, int n_maps, 
     return scene_argmax_objects(e, "smg_scene_class_topk_objects", q_dev,
                                 {e && e->head_out != 3 ? "class probabilities need a 3-class head (head_out == 3)" : nullptr,
                                  n_maps < 1 ? "n_maps < 1" : nullptr, cls < 0 || cls > 2 ? "cls must be 0, 1 or 2" : nullptr},
-                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, K, radius, stream,
-                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks& picks) {
+                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, K, radius, nullptr, stream,
+                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks& picks, const SceneNoise&) {
         const int64_t P3 = (int64_t)3 * g.OH * g.OW;
         hipLaunchKernelGGL(scene_class_topk_objects_kernel, dim3(tiles, n), dim3(256), (size_t)P3 * sizeof(float) + kSceneTopK * sizeof(int),
                            (hipStream_t)stream, q_dev, P3, m0, a, sel, g, cls, masks_dev, mvec, picks, e->scene_val, e->scene_idx);
+    });
+}
+
+// smg_scene_sample_objects for the 3-class head: the same rounds with the selected walk on the three logit planes.
+int smg_scene_class_sample_objects(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                                   const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
+                                   int n_groups, int n_draws, double beta, uint64_t seed, int* idx_out_dev, float* val_out_dev, void* stream) {
+    const SceneNoise noise{(unsigned long long)seed, beta, 0};
+    return scene_argmax_objects(e, "smg_scene_class_sample_objects", q_dev,
+                                {e && e->head_out != 3 ? "class probabilities need a 3-class head (head_out == 3)" : nullptr,
+                                 n_maps < 1 ? "n_maps < 1" : nullptr, cls < 0 || cls > 2 ? "cls must be 0, 1 or 2" : nullptr},
+                                n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, idx_out_dev, val_out_dev}, n_draws, 0, &noise, stream,
+                                [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks&, const SceneNoise& nz) {
+        const int64_t P3 = (int64_t)3 * g.OH * g.OW;
+        hipLaunchKernelGGL(scene_class_sample_objects_kernel, dim3(tiles, n), dim3(256), (size_t)P3 * sizeof(float), (hipStream_t)stream,
+                           q_dev, P3, m0, a, sel, g, cls, masks_dev, mvec, nz, e->scene_val, e->scene_idx);
     });
 }
 

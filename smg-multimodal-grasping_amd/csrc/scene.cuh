@@ -2,11 +2,13 @@
 // heightmap's pixel grid.  In the order of the file:
 //   scene_point / scene_interp / scene_class   the coordinate chain of one heightmap pixel and the value(s) of the map there: one Q
 //                                  value, or the softmax of the three interpolated logits of a 3-class head
-//   scene_walk<PLANES, ARGMAX, SELECT, PICKS>  the one tiling behind smg_scene_maps / smg_scene_class_maps (ARGMAX false: the maps are
+//   scene_walk<PLANES, ARGMAX, SELECT, PICKS, NOISE>  the one tiling behind smg_scene_maps / smg_scene_class_maps (ARGMAX false: the maps are
 //                                  stored), smg_scene_argmax / smg_scene_class_argmax (true: the best (rotation, pixel), nothing
 //                                  stored) and smg_scene_argmax_objects / smg_scene_class_argmax_objects (SELECT: every map on the
 //                                  pixels its masks select, one result per group of maps; PICKS: one round of smg_scene_topk_objects /
-//                                  smg_scene_class_topk_objects, which also skips the discs around the group's earlier picks)
+//                                  smg_scene_class_topk_objects, which also skips the discs around the group's earlier picks;
+//                                  NOISE: one draw of smg_scene_sample_objects / smg_scene_class_sample_objects, the selected walk
+//                                  that keeps the candidate with the best Gumbel-perturbed score, scene_sample_score)
 //   scene_best_walk<PLANES>        smg_scene_best_maps / smg_scene_class_best_maps: per GROUP of maps and heightmap pixel the best
 //                                  value over the group's maps and the map that gives it - parallel over groups and pixel tiles,
 //                                  the group's maps staged one at a time, launches of maps carried through the outputs
@@ -99,6 +101,34 @@ struct SceneSelect { int a[kSceneMaps], b[kSceneMaps], group[kSceneMaps]; };
 constexpr int kSceneTopK = 32;
 struct ScenePicks { const int* idx; int K, n; unsigned r2; };
 
+// The Boltzmann draw of smg_scene_sample_objects / smg_scene_class_sample_objects: draw d of a call picks, per group, the candidate
+// with the best SCORE s = (float)fma(beta, (double)v, G), v = the candidate's float32 map value and G = standard Gumbel noise that is
+// a pure function of (seed, d, the candidate's flattened index i into [n_maps][hm][hm], i < 2^31) - the Gumbel-max identity: the
+// argmax of beta v + G over independent G is a draw from softmax(beta v).  All integers mod 2^64:
+//   x = seed + (d << 32) + i
+//   mix(x): x += 0x9E3779B97F4A7C15; z = x; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+//           return z ^ z >> 31                                   (the splitmix64 finaliser)
+//   h = mix(mix(x))
+//   u = ((h >> 12) + 0.5) * 2^-52      exact in double, strictly inside (0, 1): from 2^-53 to 1 - 2^-53
+//   G = -log(-log(u))                  double, finite, in about [-3.61, 36.74]
+// The score is rounded to float32 once.  scene_sample_score is the ONE place that forms it: the walk and the grouped reduce both
+// call it, so the two cannot round differently.  A NaN value gives a NaN score (and wins, by argmax_better's rules).
+constexpr int kSceneDraws = 32;          // the most draws a call may ask for
+struct SceneNoise { unsigned long long seed; double beta; int d; };
+__device__ __forceinline__ unsigned long long scene_mix(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    unsigned long long z = x;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ float scene_sample_score(float v, int flat, const SceneNoise& nz) {
+    const unsigned long long h = scene_mix(scene_mix(nz.seed + ((unsigned long long)(unsigned)nz.d << 32) + (unsigned long long)(unsigned)flat));
+    const double u = ((double)(h >> 12) + 0.5) * 0x1p-52;
+    const double G = -log(-log(u));
+    return (float)fma(nz.beta, (double)v, G);
+}
+
 // Which of the 4 consecutive pixels i0 .. i0 + 3 mask `term` selects, OR-ed into s: a pixel is selected when its double is not
 // exactly 0 - the bit pattern without its sign is tested, so -0.0 does not select, a NaN does, and the value never enters any
 // arithmetic.  vec: two 16-byte loads (masks 16-byte aligned and hm^2 a multiple of 4, so the thread's 32 bytes are aligned and
@@ -138,13 +168,20 @@ __device__ __forceinline__ void scene_select4(const double* masks, int term, int
 // is skipped like an unselected one, before the geometry.  The picks are decoded once per workgroup, idx % hm^2 -> (py << 16 | px),
 // into kSceneTopK ints of dynamic LDS behind the planes.  A group whose last pick is -1 has nothing left: the workgroup leaves an
 // empty slot and walks nothing.
-template <int PLANES, bool ARGMAX, bool SELECT = false, bool PICKS = false>
+// NOISE (with SELECT; smg_scene_sample_objects, smg_scene_class_sample_objects): draw nz->d of the Boltzmann sample.  Masks before
+// geometry as above; only a selected valid pixel pays the hash and the two double logarithms of scene_sample_score.  The thread and
+// the workgroup keep the candidate with the best SCORE by argmax_better's rules applied to the score (lowest flattened index on
+// ties, a NaN score wins), and the slot receives that candidate's VALUE and index: the tree runs on (score, index), then the one
+// thread that holds the winning index - flattened indices are unique - writes its value.  The grouped reduce recomputes the score
+// from (value, index).
+template <int PLANES, bool ARGMAX, bool SELECT = false, bool PICKS = false, bool NOISE = false>
 __device__ __forceinline__ void scene_walk(const float* q, int64_t map_stride, int map0, const SceneAffine& aff, const SceneGeo& g, int cls,
                                            float* out, int vec4, float* part_val, int* part_idx,
                                            const SceneSelect* sel = nullptr, const double* masks = nullptr, int mvec = 0,
-                                           const ScenePicks* pk = nullptr) {
+                                           const ScenePicks* pk = nullptr, const SceneNoise* nz = nullptr) {
     static_assert(ARGMAX || !SELECT, "the selected walk is an argmax");
     static_assert(SELECT || !PICKS, "the picks suppress selected pixels");
+    static_assert(SELECT || !NOISE, "the sample is drawn among selected pixels");
     extern __shared__ float sq[];
     __shared__ float bv[256];
     __shared__ int bi[256];
@@ -169,6 +206,7 @@ __device__ __forceinline__ void scene_walk(const float* q, int64_t map_stride, i
     const int base = blockIdx.x * kSceneTile;
     const int planes = PLANES == 3 && cls < 0 ? 3 : 1;  // planes stored per map
     float best = -INFINITY; int at = 0x7fffffff;
+    float held = -INFINITY;                             // NOISE: the value of the candidate whose score `best` is
     for (int pass = 0; pass < kSceneTile / 1024; ++pass) {
         const int i0 = base + 4 * (pass * 256 + t);
         if (i0 >= npix) break;
@@ -215,7 +253,10 @@ __device__ __forceinline__ void scene_walk(const float* q, int64_t map_stride, i
                     }
                     if (ARGMAX) {
                         const int flat = (map0 + m) * npix + i;       // (< 2^31: checked by the host)
-                        if (argmax_better(v[0][k], flat, best, at)) { best = v[0][k]; at = flat; }
+                        if constexpr (NOISE) {
+                            const float sc = scene_sample_score(v[0][k], flat, *nz);
+                            if (argmax_better(sc, flat, best, at)) { best = sc; at = flat; held = v[0][k]; }
+                        } else if (argmax_better(v[0][k], flat, best, at)) { best = v[0][k]; at = flat; }
                     }
                 }
             }
@@ -234,7 +275,12 @@ __device__ __forceinline__ void scene_walk(const float* q, int64_t map_stride, i
     if (ARGMAX) {
         bv[t] = best; bi[t] = at;
         block_argmax(bv, bi, t);
-        if (t == 0) { const int slot = blockIdx.y * gridDim.x + blockIdx.x; part_val[slot] = bv[0]; part_idx[slot] = bi[0]; }
+        const int slot = blockIdx.y * gridDim.x + blockIdx.x;
+        if constexpr (NOISE) {
+            const int win = bi[0];
+            if (win == 0x7fffffff) { if (t == 0) { part_val[slot] = -INFINITY; part_idx[slot] = win; } }
+            else if (at == win) { part_val[slot] = held; part_idx[slot] = win; }
+        } else if (t == 0) { part_val[slot] = bv[0]; part_idx[slot] = bi[0]; }
     }
 }
 static __global__ __launch_bounds__(256) void scene_map_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
@@ -278,6 +324,18 @@ static __global__ __launch_bounds__(256) void scene_class_topk_objects_kernel(co
                                                                               int mvec, const ScenePicks pk, float* part_val, int* part_idx) {
     scene_walk<3, true, true, true>(q, map_stride, map0, aff, g, cls, nullptr, 0, part_val, part_idx, &sel, masks, mvec, &pk);
 }
+// One draw of smg_scene_sample_objects / smg_scene_class_sample_objects: the selected walk by the Gumbel-perturbed score (dynamic LDS:
+// the planes).  The slots receive the winning candidate's value and index.
+static __global__ __launch_bounds__(256) void scene_sample_objects_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                          const SceneSelect sel, const SceneGeo g, const double* masks, int mvec,
+                                                                          const SceneNoise nz, float* part_val, int* part_idx) {
+    scene_walk<1, true, true, false, true>(q, map_stride, map0, aff, g, 0, nullptr, 0, part_val, part_idx, &sel, masks, mvec, nullptr, &nz);
+}
+static __global__ __launch_bounds__(256) void scene_class_sample_objects_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                                const SceneSelect sel, const SceneGeo g, int cls, const double* masks,
+                                                                                int mvec, const SceneNoise nz, float* part_val, int* part_idx) {
+    scene_walk<3, true, true, false, true>(q, map_stride, map0, aff, g, cls, nullptr, 0, part_val, part_idx, &sel, masks, mvec, nullptr, &nz);
+}
 
 // The second launch of smg_scene_argmax / smg_scene_class_argmax: one workgroup reduces the n partials (thread t takes slots t,
 // t + 256, ... in that order) and, with `carry`, the result a previous group of maps left in the outputs.  Empty slots hold index
@@ -303,22 +361,48 @@ static __global__ __launch_bounds__(256) void scene_argmax_reduce_kernel(const f
 // order - and, with `carry`, the result an earlier launch of maps left in the group's outputs.  Every group's pair is written: a
 // group without a map in any launch, or without a selected valid pixel, ends at index -1, value -inf.  A group's pair lies at
 // element grp * stride of the outputs: stride 1 for the argmax, K for rank j of a top-K (the caller passes the outputs + j).
-static __global__ __launch_bounds__(256) void scene_argmax_group_reduce_kernel(const float* part_val, const int* part_idx, int tiles, int n_maps,
-                                                                               const SceneSelect sel, int carry, int* idx_out, float* val_out, int stride) {
+// NOISE (smg_scene_sample_objects / smg_scene_class_sample_objects, `stride` = n_draws, the outputs + d): the slots and the carried pair hold VALUES; each is
+// compared by the score scene_sample_score recomputes from (value, index, nz) - the function the walk used, so the same float - and
+// the winner's value is what is written: the outputs carry the running winner between launches with no further scratch.
+template <bool NOISE>
+__device__ __forceinline__ void scene_group_reduce(const float* part_val, const int* part_idx, int tiles, int n_maps, const SceneSelect& sel, int carry,
+                                                   int* idx_out, float* val_out, int stride, const SceneNoise* nz = nullptr) {
     __shared__ float bv[256];
     __shared__ int bi[256];
     const int t = threadIdx.x, grp = blockIdx.x;
     idx_out += (int64_t)grp * stride; val_out += (int64_t)grp * stride;
     float best = -INFINITY; int at = 0x7fffffff;
-    if (t == 0 && carry && *idx_out >= 0) { best = *val_out; at = *idx_out; }
+    float held = -INFINITY;                             // NOISE: the value whose score `best` is
+    if (t == 0 && carry && *idx_out >= 0) {
+        at = *idx_out;
+        if constexpr (NOISE) { held = *val_out; best = scene_sample_score(held, at, *nz); }
+        else best = *val_out;
+    }
     for (int i = t; i < tiles * n_maps; i += 256) {
         if (sel.group[i / tiles] != grp) continue;
         const float x = part_val[i]; const int j = part_idx[i];
-        if (j != 0x7fffffff && argmax_better(x, j, best, at)) { best = x; at = j; }
+        if (j == 0x7fffffff) continue;
+        if constexpr (NOISE) {
+            const float sc = scene_sample_score(x, j, *nz);
+            if (argmax_better(sc, j, best, at)) { best = sc; at = j; held = x; }
+        } else if (argmax_better(x, j, best, at)) { best = x; at = j; }
     }
     bv[t] = best; bi[t] = at;
     block_argmax(bv, bi, t);
-    if (t == 0) { *idx_out = bi[0] == 0x7fffffff ? -1 : bi[0]; *val_out = bv[0]; }
+    if constexpr (NOISE) {
+        const int win = bi[0];                          // (a slot's index and the carried one are all different: one thread holds the winner)
+        if (win == 0x7fffffff) { if (t == 0) { *idx_out = -1; *val_out = -INFINITY; } }
+        else if (at == win) { *idx_out = win; *val_out = held; }
+    } else if (t == 0) { *idx_out = bi[0] == 0x7fffffff ? -1 : bi[0]; *val_out = bv[0]; }
+}
+static __global__ __launch_bounds__(256) void scene_argmax_group_reduce_kernel(const float* part_val, const int* part_idx, int tiles, int n_maps,
+                                                                               const SceneSelect sel, int carry, int* idx_out, float* val_out, int stride) {
+    scene_group_reduce<false>(part_val, part_idx, tiles, n_maps, sel, carry, idx_out, val_out, stride);
+}
+static __global__ __launch_bounds__(256) void scene_sample_group_reduce_kernel(const float* part_val, const int* part_idx, int tiles, int n_maps,
+                                                                               const SceneSelect sel, int carry, const SceneNoise nz,
+                                                                               int* idx_out, float* val_out, int stride) {
+    scene_group_reduce<true>(part_val, part_idx, tiles, n_maps, sel, carry, idx_out, val_out, stride, &nz);
 }
 
 // ---- the collapsed map: per group and heightmap pixel the best value over the group's maps and which map gives it ----

@@ -58,7 +58,7 @@ def lib():
         raise SmgError("%s is ABI version %d, this binding needs %d: rebuild it (make -C csrc)" % (LIB_PATH, L.smg_version(), ABI_VERSION))
     for added in ("smg_loss_scene_map_ce", "smg_scene_argmax_objects", "smg_scene_class_argmax_objects", "smg_scene_values",
                   "smg_scene_class_values", "smg_scene_topk_objects", "smg_scene_class_topk_objects", "smg_scene_best_maps",
-                  "smg_scene_class_best_maps"):       # (added without a version step: a version-9 library built before them lacks the symbol)
+                  "smg_scene_class_best_maps", "smg_scene_sample_objects", "smg_scene_class_sample_objects"):       # (added without a version step: a version-9 library built before them lacks the symbol)
         if not hasattr(L, added):
             raise SmgError("%s is ABI version %d but lacks %s, a stale build: rebuild it (make -C csrc)" % (LIB_PATH, ABI_VERSION, added))
     L.smg_abi_struct_bytes.argtypes = [C.c_int]
@@ -93,6 +93,9 @@ def lib():
                                          C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_scene_best_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int,
                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smg_scene_sample_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_double, C.c_uint64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -107,6 +110,9 @@ def lib():
                                                C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_scene_class_best_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_int,
                                             C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smg_scene_class_sample_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_double, C.c_uint64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene_ce.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
     L.smg_loss_scene_map_ce.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -139,7 +145,7 @@ EXPORTS = (
     "smg_last_error", "smg_version", "smg_abi_struct_bytes", "smg_engine_set_option", "smg_layout_count", "smg_layout_param_floats", "smg_layout_buffer_floats",
     "smg_layout_nbt_count", "smg_layout_entry", "smg_layout_trunk_range", "smg_layout_head_range",
     "smg_engine_create", "smg_engine_destroy", "smg_engine_workspace_bytes", "smg_engine_geometry",
-    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_values", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_scene_topk_objects", "smg_scene_best_maps", "smg_loss_scene","smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_values", "smg_scene_class_argmax", "smg_scene_class_argmax_objects", "smg_scene_class_topk_objects", "smg_scene_class_best_maps", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
+    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_values", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_scene_topk_objects", "smg_scene_sample_objects", "smg_scene_best_maps", "smg_loss_scene","smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_values", "smg_scene_class_argmax", "smg_scene_class_argmax_objects", "smg_scene_class_topk_objects", "smg_scene_class_sample_objects", "smg_scene_class_best_maps", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
     "smg_profile_enable", "smg_profile_kinds", "smg_profile_kind_name", "smg_profile_read", "smg_profile_read_bytes",
 )
 
@@ -353,6 +359,18 @@ class Engine(object):
         check(lib().smg_scene_best_maps(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), masks or None, int(n_masks), ma, mb, gr,
                                         int(n_groups), val_out, arg_out, stream))
 
+    def scene_sample_objects(self, q, map_stride, n_maps, affine, hm_size, masks, n_masks, mask_a, mask_b, groups, n_groups, n_draws, beta,
+                             seed, idx_out, val_out, stream):
+        """smg_scene_sample_objects: scene_argmax_objects' arguments plus `n_draws` (1 .. 32), `beta` = 1 / temperature (finite,
+        >= 0) and a 64-bit `seed` - per group n_draws independent draws of a selected valid (map, pixel) with probability
+        proportional to exp(beta * value), by the Gumbel-max rule on counter-based noise (include/smg_hip.h states the hash).
+        idx_out int32 [n_groups, n_draws] = flattened index into [n_maps, hm, hm] or -1, val_out float32 [n_groups, n_draws] = the
+        map value at the pick; a group without a candidate is (-1, -inf) in every draw.  A pure function of its arguments."""
+        a, p = self._affines(affine, n_maps)
+        sel, (ma, mb, gr) = self._selects(n_maps, mask_a, mask_b, groups)
+        check(lib().smg_scene_sample_objects(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), masks, int(n_masks), ma, mb, gr,
+                                             int(n_groups), int(n_draws), float(beta), int(seed), idx_out, val_out, stream))
+
     def loss_scene(self, q, affine, hm_size, n_pairs, K, pixels, labels, weights, loss_out, dq_out, stream):
         """smg_loss_scene: the weighted Huber on K heightmap pixels (int32 [n_pairs, K, 2] = iy, ix) per pair, dq on the map;
         `weights` None = all ones.  Marks the saved forward so that its backward runs the dense head form."""
@@ -410,6 +428,15 @@ class Engine(object):
         sel, (ma, mb, gr) = self._selects(n_maps, mask_a, mask_b, groups)
         check(lib().smg_scene_class_best_maps(self.h, q, int(n_maps), p, int(hm_size), int(cls), masks or None, int(n_masks), ma, mb, gr,
                                               int(n_groups), val_out, arg_out, stream))
+
+    def scene_class_sample_objects(self, q, n_maps, affine, hm_size, cls, masks, n_masks, mask_a, mask_b, groups, n_groups, n_draws, beta,
+                                   seed, idx_out, val_out, stream):
+        """smg_scene_class_sample_objects: scene_sample_objects on the logit maps `q` [n_maps, 3, OH, OW] - scene_class_argmax_objects'
+        arguments plus `n_draws`, `beta` and `seed`; the value is P(class cls), idx_out / val_out are [n_groups, n_draws]."""
+        a, p = self._affines(affine, n_maps)
+        sel, (ma, mb, gr) = self._selects(n_maps, mask_a, mask_b, groups)
+        check(lib().smg_scene_class_sample_objects(self.h, q, int(n_maps), p, int(hm_size), int(cls), masks, int(n_masks), ma, mb, gr,
+                                                   int(n_groups), int(n_draws), float(beta), int(seed), idx_out, val_out, stream))
 
     def loss_scene_ce(self, q, affine, hm_size, n_pairs, K, pixels, labels, loss_out, dq_out, stream):
         """smg_loss_scene_ce: the cross entropy (class weights {1, 1, 0}) on K heightmap pixels (int32 [n_pairs, K, 2] = iy, ix) per

@@ -720,16 +720,17 @@ class Trainer(object):
         reward of get_label_value in this frame)."""
         self._require_scene("best_scene_actions", depth_heightmap)
 
-        def argmax(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream):
+        def argmax(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream, style):
             eng.scene_argmax_objects(q.data_ptr(), q.shape[2] * q.shape[3], n_maps, aff, hm, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
                                      group_of, groups, idx, val, stream)
         return self._best_scene_objects("best_scene_actions", depth_heightmap, mask_depth, is_ets, is_target, argmax)
 
-    def _scene_object_picks(self, what, depth_heightmap, mask_depth, is_ets, is_target, pick, k=1):
-        """The loop behind best_scene_actions, ranked_scene_actions and their class forms (the caller has checked method and
-        geometry): one forward per primitive, one pick(engine, q, n_maps, affines, hm, masks, mask_a, mask_b, group of every map,
-        n_groups, idx pointer, val pointer, stream) on its maps - which writes `k` (index, value) pairs per group - and one
-        read-back.  Returns (calls = per primitive (first group, groups, maps per group), indices [all groups, k], values float64
+    def _scene_object_picks(self, what, depth_heightmap, mask_depth, is_ets, is_target, pick, k=1, joint=False):
+        """The loop behind best_scene_actions, ranked_scene_actions, sampled_scene_actions and their class forms (the caller has
+        checked method and geometry): one forward per primitive, one pick(engine, q, n_maps, affines, hm, masks, mask_a, mask_b,
+        group of every map, n_groups, idx pointer, val pointer, stream, style) on its maps - which writes `k` (index, value) pairs
+        per group - and one read-back.  The groups are the objects (the pairs), or with `joint` ONE group of all the primitive's
+        maps.  Returns (calls = per primitive (first group, groups, maps per object), indices [all groups, k], values float64
         [all groups, k], the pair list or None, hm); the maps behind the result stay in self._last_object_q."""
         n = int(np.asarray(mask_depth).shape[0])
         if n < 1:
@@ -755,8 +756,10 @@ class Trainer(object):
                 val = torch.empty((2 * n + n_pairs, k), dtype=torch.float32, device=q.device)
             off = sum(c[1] for c in calls)
             eng, aff, _, stream = self._scene_call(model, q, depth_heightmap, rots)
-            pick(eng, q, len(rots), aff, hm, m, mask_a, mask_b, [j // per for j in range(len(rots))], groups,
-                 idx[off:].data_ptr(), val[off:].data_ptr(), stream)
+            group_of = [j // per for j in range(len(rots))]
+            if joint:
+                groups, group_of = 1, [0] * len(rots)
+            pick(eng, q, len(rots), aff, hm, m, mask_a, mask_b, group_of, groups, idx[off:].data_ptr(), val[off:].data_ptr(), stream, style)
             calls.append((off, groups, per))
             kept[name] = q
         self._last_object_q = kept        # the maps behind the result, object-major: "grasp" / "suction" [n * R, HEAD_OUT, OH, OW], "pairs" [n_pairs, HEAD_OUT, OH, OW]
@@ -801,10 +804,11 @@ class Trainer(object):
             raise ValueError("%s: radius must be an integer >= 0, in heightmap pixels" % what)
         return int(k), int(radius)
 
-    def _ranked_scene_objects(self, what, depth_heightmap, mask_depth, k, is_ets, is_target, topk):
-        """The body of ranked_scene_actions and ranked_scene_class_actions (the caller has checked method, geometry, k and
-        radius): _scene_object_picks with k pairs per group and the host decode of every rank."""
-        calls, i_all, v_all, pair_list, hm = self._scene_object_picks(what, depth_heightmap, mask_depth, is_ets, is_target, topk, k)
+    def _ranked_scene_objects(self, what, depth_heightmap, mask_depth, k, is_ets, is_target, topk, joint=False):
+        """The body of ranked_scene_actions, sampled_scene_actions and their class forms (the caller has checked method, geometry
+        and the pick's own arguments): _scene_object_picks with k pairs per group and the host decode of every rank (draw).
+        `joint` (the sampled forms): one group per primitive, decoded to (object, rotation, pixel, conf) per draw."""
+        calls, i_all, v_all, pair_list, hm = self._scene_object_picks(what, depth_heightmap, mask_depth, is_ets, is_target, topk, k, joint)
 
         def decode(off, groups, per):
             lists = [[self._scene_entry(i_all[off + g, j], v_all[off + g, j], hm, per) for j in range(k)] for g in range(groups)]
@@ -813,8 +817,22 @@ class Trainer(object):
         def order(lists, item):
             """Every entry of the lists in the order repeated np.argmax takes them: a NaN first, then descending, then (group, rank)."""
             flat = [(g, j, e) for g, entries in enumerate(lists) for j, e in enumerate(entries)]
-            flat.sort(key=lambda x: (0, 0.0, x[0], x[1]) if np.isnan(x[2][2]) else (1, -x[2][2], x[0], x[1]))
+            flat.sort(key=lambda x: (0, 0.0, x[0], x[1]) if np.isnan(x[2][-1]) else (1, -x[2][-1], x[0], x[1]))       # (the confidence is an entry's last item)
             return [item(g, e) for g, _, e in flat]
+        if joint:
+            def whole(off, per):
+                """The draws of the primitive's one group: (map // per, rotation, (iy, ix), conf), a -1 dropped."""
+                drawn = [(int(i_all[off, j]), self._scene_entry(i_all[off, j], v_all[off, j], hm, per)) for j in range(k)]
+                return [(i // (hm * hm) // per,) + e for i, e in drawn if e is not None]
+            out = {"joint": {"pairs": []}, "pairs": [], "per_pair": [], "ranked": {}}
+            for (off, _, per), name in zip(calls, ("grasp", "suction")):
+                out["joint"][name] = whole(off, per)
+            if len(calls) == 3:
+                out["pairs"] = list(pair_list)
+                out["joint"]["pairs"] = [(pair_list[g], pixel, conf) for g, _, pixel, conf in whole(calls[2][0], 1)]
+            for name, entries in out["joint"].items():
+                out["ranked"][name] = order([[e] for e in entries], lambda g, e: e)
+            return out
         out = {"per_object": {}, "pairs": [], "per_pair": [], "ranked": {"pairs": []}}
         for call, name in zip(calls, ("grasp", "suction")):
             out["per_object"][name] = decode(*call)
@@ -839,10 +857,50 @@ class Trainer(object):
         self._require_scene("ranked_scene_actions", depth_heightmap)
         k, radius = self._require_ranks("ranked_scene_actions", k, radius)
 
-        def topk(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream):
+        def topk(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream, style):
             eng.scene_topk_objects(q.data_ptr(), q.shape[2] * q.shape[3], n_maps, aff, hm, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
                                    group_of, groups, k, radius, idx, val, stream)
         return self._ranked_scene_objects("ranked_scene_actions", depth_heightmap, mask_depth, k, is_ets, is_target, topk)
+
+    @staticmethod
+    def _require_draws(what, n_draws, temperature, seed):
+        """-> (n_draws, beta = 1 / temperature, seed) of the sampled forms, or ValueError."""
+        if isinstance(n_draws, bool) or int(n_draws) != n_draws or not 1 <= n_draws <= 32:
+            raise ValueError("%s: n_draws must be an integer from 1 to 32 (the engine's kSceneDraws)" % what)
+        if not temperature > 0:                            # (a NaN fails this too)
+            raise ValueError("%s: temperature must be > 0 (inf draws uniformly)" % what)
+        if isinstance(seed, (bool, float)) or int(seed) != seed or not 0 <= seed < 2 ** 64:
+            raise ValueError("%s: seed must be an integer in [0, 2^64)" % what)
+        return int(n_draws), 1.0 / float(temperature), int(seed)
+
+    @staticmethod
+    def _style_seed(seed, style):
+        """The seed of the sample call for primitive `style`: without the step the primitives would share one noise field."""
+        return (seed + style * 0x9E3779B97F4A7C15) % 2 ** 64
+
+    def sampled_scene_actions(self, depth_heightmap, mask_depth, n_draws, temperature, seed, is_ets=True, is_target=False, joint=False):
+        """EXPLORATION for best_scene_actions: instead of the best pixel, `n_draws` independent Boltzmann draws per object - a
+        (rotation, pixel) of the object's own pixels drawn with probability proportional to exp(Q / temperature).  The same
+        forwards - one per primitive, the maps kept in self._last_object_q -, one smg_scene_sample_objects per primitive and one
+        read-back; nothing of [n * R, hm, hm] is written.  temperature = inf draws uniformly over the object's pixels with a
+        window, a small temperature approaches best_scene_actions.  The draw is a pure function of (maps, masks, temperature,
+        seed): the noise is the counter-based hash include/smg_hip.h states, and primitive s uses the seed
+        (seed + s * 0x9E3779B97F4A7C15) mod 2^64.  Draw d does not depend on n_draws.
+        Returns ranked_scene_actions' keys: per_object = {"grasp": [...], "suction": [...]}, per object a list of up to n_draws
+        (rotation, (iy, ix), conf) in DRAW order (empty where the object has no pixel with a window), conf = the Q value there;
+        pairs and per_pair; ranked = all draws of a primitive by confidence.  ranked_to_best serves unchanged, so a sampled action
+        that was executed goes through get_label_value_scene and backprop_scene like the best one.
+        joint=True: all objects of a primitive form ONE group, the draw is over (object, rotation, pixel) jointly; per_object is
+        replaced by joint = {"grasp": [(object, rotation, (iy, ix), conf)], "suction": [...], "pairs": [((g, s), (iy, ix), conf)]}
+        in draw order, per_pair is [], and ranked is built from it.
+        1 <= n_draws <= 32, temperature > 0 and 0 <= seed < 2^64, else ValueError."""
+        self._require_scene("sampled_scene_actions", depth_heightmap)
+        n_draws, beta, seed = self._require_draws("sampled_scene_actions", n_draws, temperature, seed)
+
+        def sample(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream, style):
+            eng.scene_sample_objects(q.data_ptr(), q.shape[2] * q.shape[3], n_maps, aff, hm, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
+                                     group_of, groups, n_draws, beta, self._style_seed(seed, style), idx, val, stream)
+        return self._ranked_scene_objects("sampled_scene_actions", depth_heightmap, mask_depth, n_draws, is_ets, is_target, sample, joint)
 
     @staticmethod
     def ranked_to_best(ranked, primitive_action, j):
@@ -1114,7 +1172,7 @@ class Trainer(object):
             raise ValueError("best_scene_class_actions: cls must be 0, 1 or 2")
         self._scene_geometry(np.shape(depth_heightmap)[-1])
 
-        def argmax(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream):
+        def argmax(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream, style):
             eng.scene_class_argmax_objects(q.data_ptr(), n_maps, aff, hm, cls, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
                                            group_of, groups, idx, val, stream)
         return self._best_scene_objects("best_scene_class_actions", depth_heightmap, mask_depth, is_ets, False, argmax)
@@ -1131,10 +1189,26 @@ class Trainer(object):
         self._scene_geometry(np.shape(depth_heightmap)[-1])
         k, radius = self._require_ranks("ranked_scene_class_actions", k, radius)
 
-        def topk(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream):
+        def topk(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream, style):
             eng.scene_class_topk_objects(q.data_ptr(), n_maps, aff, hm, cls, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
                                          group_of, groups, k, radius, idx, val, stream)
         return self._ranked_scene_objects("ranked_scene_class_actions", depth_heightmap, mask_depth, k, is_ets, False, topk)
+
+    def sampled_scene_class_actions(self, depth_heightmap, mask_depth, n_draws, temperature, seed, is_ets=True, joint=False, cls=0):
+        """sampled_scene_actions for the reactive net: best_scene_class_actions' forwards, one smg_scene_class_sample_objects per
+        primitive on the logits and one read-back - `n_draws` draws per object (per pair, or with `joint` per primitive) with
+        probability proportional to exp(P(class `cls`) / temperature).  Returns sampled_scene_actions' dict.  Reactive method only,
+        no is_target; 1 <= n_draws <= 32, temperature > 0, 0 <= seed < 2^64 and cls in {0, 1, 2}, else ValueError."""
+        self._require_class_objects("sampled_scene_class_actions", depth_heightmap, mask_depth)
+        if cls not in (0, 1, 2):
+            raise ValueError("sampled_scene_class_actions: cls must be 0, 1 or 2")
+        self._scene_geometry(np.shape(depth_heightmap)[-1])
+        n_draws, beta, seed = self._require_draws("sampled_scene_class_actions", n_draws, temperature, seed)
+
+        def sample(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream, style):
+            eng.scene_class_sample_objects(q.data_ptr(), n_maps, aff, hm, cls, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
+                                           group_of, groups, n_draws, beta, self._style_seed(seed, style), idx, val, stream)
+        return self._ranked_scene_objects("sampled_scene_class_actions", depth_heightmap, mask_depth, n_draws, is_ets, False, sample, joint)
 
     def train_batch_scene_class_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, grad_sync=None,
                                        return_q=False):
