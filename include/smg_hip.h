@@ -294,6 +294,44 @@ int smg_scene_sample_objects(smg_engine* e, const float* q_dev, int64_t map_stri
                              const int* map_group, int n_groups, int n_draws, double beta, uint64_t seed,
                              int* idx_out_dev, float* val_out_dev, void* stream);
 
+/* The NORMALISER of that policy: per object the log-sum-exp and the Boltzmann mean of its candidates, on the device, the
+ * scene-frame maps never written.  Every argument shared with smg_scene_argmax_objects means what it means there, and geometry,
+ * validity, values, selection, the union of the two mask terms and groups that need not be contiguous are that call's: the
+ * CANDIDATES of group g are the selected valid pixels of its maps, each with the float32 value v smg_scene_maps stores there.
+ * beta = 1 / temperature, as for smg_scene_sample_objects.
+ * stats_out_dev float64 [n_groups][4], the row of group g = {count, vmax, lse, mean}:
+ *     count = the number of candidates, exact
+ *     vmax  = the largest candidate value M; as a float32 it is smg_scene_argmax_objects' val[g], bit for bit
+ *     lse   = log sum_i exp(beta v_i) = fma(beta, M, log S)
+ *     mean  = sum_i v_i exp(beta v_i) / sum_i exp(beta v_i) = T / S, the expectation of v under softmax(beta v)
+ * so that log pi(i) = beta v_i - lse, the entropy is lse - beta mean, and mellowmax is (lse - log count) / beta.  A group without
+ * a map or without a candidate gets (0, -inf, -inf, NaN); every element is written by every successful call.
+ * The sums are kept as a streaming STATE (n, M, S, T) of a set of candidates: n = how many, M = the largest value,
+ * S = sum exp(beta (v - M)) and T = sum v exp(beta (v - M)), both double; no exponent is ever positive, so nothing overflows
+ * whatever beta and the offset of v.  The empty set is (0, -inf, 0, 0).
+ *   ADD one candidate v to a state:
+ *     the first candidate:  (1, v, 1, v)
+ *     v <= M, or M a NaN:   e = exp(beta (v - M));  S += e;  T = fma(v, e, T)
+ *     else (a NaN v too):   r = exp(beta (M - v));  S = fma(S, r, 1);  T = fma(T, r, v);  M = v
+ *     then n += 1
+ *   MERGE A (the earlier set) with B:
+ *     an empty side yields the other side unchanged; else
+ *     M = MA if MA > MB or MA is a NaN, else MB
+ *     S = SA exp(beta (MA - M)) + SB exp(beta (MB - M)),  T likewise,  n = nA + nB      (one of the two factors is exp(0) = 1)
+ * Order: a thread adds its pixels in ascending order; a fixed tree merges the 256 threads of a workgroup, whose state goes to a
+ * scratch the engine owns; one workgroup per group merges that launch's slots of the group (thread t the slots t, t + 256, ...,
+ * then the same tree).  Maps are launched 32 at a time: from the second launch on the reduce starts from the raw state the
+ * earlier launches left in the group's row of stats_out_dev, and one last launch (one thread per group) turns the rows into
+ * {count, vmax, lse, mean} in place.  No atomics: two identical calls are bit-identical.  Against float64 log-sum-exp over the
+ * same float32 values the result differs by rounding only (tests/scene_softmax_ref.py derives the bound).
+ * A NaN candidate is counted and makes vmax, lse and mean of its group NaN (a NaN wins, as for the argmax); other groups are
+ * untouched.  Infinite values are outside the contract: the call does not fault and count stays exact.
+ * Returns -22 and launches nothing for every refusal of smg_scene_argmax_objects (its outputs replaced by stats_out_dev), for a
+ * beta that is negative, NaN or infinite, and for a stats_out_dev that is not 8-byte aligned. */
+int smg_scene_softmax_objects(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host,
+                              int hm_size, const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
+                              const int* map_group, int n_groups, double beta, double* stats_out_dev, void* stream);
+
 /* The COLLAPSED map - the picture between "all the maps" and "one pick": per group of maps and heightmap pixel the best value over
  * the group's maps and which map gives it, the scene-frame maps never written.  q_dev, map_stride, n_maps, affine_host, hm_size,
  * masks_dev, n_masks, map_mask_a, map_mask_b, map_group and n_groups mean what they mean for smg_scene_argmax_objects (selection by
@@ -434,6 +472,18 @@ int smg_scene_class_sample_objects(smg_engine* e, const float* q_dev, int n_maps
                                    const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
                                    const int* map_group, int n_groups, int n_draws, double beta, uint64_t seed,
                                    int* idx_out_dev, float* val_out_dev, void* stream);
+
+/* smg_scene_softmax_objects for the 3-class head - {count, vmax, lse, mean} per object of the policy proportional to
+ * exp(beta P(class cls)), cls in {0,1,2}: the arguments of smg_scene_class_argmax_objects plus beta, stats_out_dev float64
+ * [n_groups][4].  The value v of a candidate is scene_class_prob(c, cls), the expression smg_scene_class_maps stores; vmax as a
+ * float32 is smg_scene_class_argmax_objects' val, bit for bit; the state, its update and merge, the order, the empty row, the
+ * NaN rule, "every element written" and "no atomics, bit-identical between identical calls" are smg_scene_softmax_objects', word
+ * for word.  An unselected pixel costs no exponential.
+ * Returns -22 and launches nothing for every refusal of smg_scene_class_argmax_objects (its outputs replaced by stats_out_dev),
+ * for a beta that is negative, NaN or infinite, and for a stats_out_dev that is not 8-byte aligned. */
+int smg_scene_class_softmax_objects(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                                    const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b,
+                                    const int* map_group, int n_groups, double beta, double* stats_out_dev, void* stream);
 
 /* smg_scene_best_maps for the 3-class head - per group and heightmap pixel the largest P(class cls), cls in {0,1,2}, over the
  * group's maps and the map that gives it: q_dev is [n_maps][3][OH][OW], every other argument, the candidates, the tie and NaN

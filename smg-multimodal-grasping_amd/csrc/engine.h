@@ -146,6 +146,9 @@ struct smg_engine {
     float* d_affine = nullptr;
     // smg_scene_argmax: one (value, index) partial per workgroup of a launch (kSceneMaps maps x scene_tiles tiles of the largest heightmap this S serves)
     float* scene_val = nullptr; int* scene_idx = nullptr; int scene_tiles = 0;
+    // smg_scene_softmax_objects on top of them: the (S, T) sums of each workgroup's log-sum-exp state (kSceneMaps x scene_tiles double pairs;
+    // its M goes to scene_val, its count to scene_idx)
+    double2* scene_st = nullptr;
     // smg_loss_scene_map / smg_loss_scene_map_ce: one loss partial per map element of a launch (kSceneMaps pairs x OH x OW doubles)
     double* scene_lpart = nullptr;
     // smg_loss_scene_map_ce on top of scene_lpart: the unnormalised gradient partials ([kSceneMaps pairs][3][OH * OW] doubles) and the point

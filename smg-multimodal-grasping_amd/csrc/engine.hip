@@ -83,6 +83,7 @@ static int engine_build(smg_engine* e) {
     e->scene_tiles = (int)(((int64_t)(S / 2) * (S / 2) + kSceneTile - 1) / kSceneTile);      // (a heightmap of side hm pads to S >= 2 hm)
     ALLOC(e->scene_val, (int64_t)kSceneMaps * e->scene_tiles);
     ALLOC(e->scene_idx, (int64_t)kSceneMaps * e->scene_tiles);
+    ALLOC(e->scene_st, (int64_t)kSceneMaps * e->scene_tiles);
     ALLOC(e->scene_lpart, (int64_t)kSceneMaps * e->OH * e->OW);
     ALLOC(e->scene_gpart, (int64_t)kSceneMaps * e->OH * e->OW * 3);
     ALLOC(e->scene_cnt, (int64_t)kSceneMaps * e->OH * e->OW);
@@ -421,7 +422,7 @@ void smg_engine_destroy(smg_engine* e) {
     (void)hipDeviceSynchronize();
     void* ptrs[] = {e->img4, e->stem, e->DY0, e->argmax, e->X[0], e->X[1], e->X[2], e->X[3], e->G[0], e->G[1], e->G[2], e->G[3],
                     e->Bt, e->DY2, e->part, e->F, e->DF, e->H1, e->DH1, e->fstat, e->bstat, e->dbscr, e->d_dbseg, e->asc, e->d_asc, e->gamax, e->packed_u, e->packed_f, e->stab, e->d_pack, e->d_bnupd,
-                    e->d_stage, e->scene_val, e->scene_idx, e->scene_lpart, e->scene_gpart, e->scene_cnt, e->mom_part, e->mom};
+                    e->d_stage, e->scene_val, e->scene_idx, e->scene_st, e->scene_lpart, e->scene_gpart, e->scene_cnt, e->mom_part, e->mom};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->dbg_gsnap) (void)hipFree(e->dbg_gsnap);
     if (e->dbg_dy2) (void)hipFree(e->dbg_dy2);
@@ -530,7 +531,7 @@ static SceneAffine scene_affine(const float* affine_host, int m0, int n) {
     return a;
 }
 
-// What the eighteen scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
+// What the twenty scene entry points check behind their NULL test, in this order: the entry point's own refusals `before` (the caller
 // evaluates them and passes each one's text, or nullptr where it does not apply; the first that applies is reported as
 // "<who>: <text>"), the geometry, the one refusal that stands behind it (`after`), the n affines.  Then the device is selected and g
 // is valid.  Nothing has been launched when this returns non-zero.
@@ -623,11 +624,13 @@ int smg_scene_argmax(smg_engine* e, const float* q_dev, int64_t map_stride, int 
 // not NULL, K = n_draws, radius 0) uses the same rounds: round d = the walk by the score of draw d (noise.d = d) and
 // scene_sample_group_reduce_kernel into slot [group][d]; its rounds do not read one another's results.
 struct SceneObjectArgs { const double* masks_dev; int n_masks; const int *map_mask_a, *map_mask_b, *map_group; int n_groups; int* idx_out_dev; float* val_out_dev; };
-extern "C++" template <class F>
-static int scene_argmax_objects(smg_engine* e, const char* who, const void* q_dev, std::initializer_list<const char*> own, int n_maps,
-                                const float* affine_host, int hm_size, const SceneObjectArgs& o, int K, int radius,
-                                const SceneNoise* noise, void* stream, F walk) {
-    if (!e || !q_dev || !affine_host || !o.masks_dev || !o.map_mask_a || !o.map_mask_b || !o.map_group || !o.idx_out_dev || !o.val_out_dev)
+// What every per-object entry point refuses, in this order (shared by scene_argmax_objects and scene_softmax_objects): a NULL
+// pointer (`outs_ok` = the form's own outputs are there), the entry point's `own` refusals, n_masks, n_groups, the mask indices and
+// the groups, the form's `more` refusals, then scene_prelude's geometry, the flattened index and the affines.
+static int scene_objects_prelude(const smg_engine* e, const char* who, const void* q_dev, std::initializer_list<const char*> own, int n_maps,
+                                 const float* affine_host, int hm_size, const SceneObjectArgs& o, bool outs_ok,
+                                 std::initializer_list<const char*> more, SceneGeo* g) {
+    if (!e || !q_dev || !affine_host || !o.masks_dev || !o.map_mask_a || !o.map_mask_b || !o.map_group || !outs_ok)
         return fail(-22, std::string(who) + ": NULL argument");
     for (const char* text : own)
         if (text) return fail(-22, std::string(who) + ": " + text);
@@ -637,26 +640,43 @@ static int scene_argmax_objects(smg_engine* e, const char* who, const void* q_de
         if (o.map_mask_a[m] < -1 || o.map_mask_a[m] >= o.n_masks || o.map_mask_b[m] < -1 || o.map_mask_b[m] >= o.n_masks) bad_mask = "a mask index outside [-1, n_masks)";
         if (o.map_group[m] < 0 || o.map_group[m] >= o.n_groups) bad_group = "a group outside [0, n_groups)";
     }
+    for (const char* text : {o.n_masks < 1 ? "n_masks < 1" : nullptr, o.n_groups < 1 ? "n_groups < 1" : nullptr, bad_mask, bad_group})
+        if (text) return fail(-22, std::string(who) + ": " + text);
+    for (const char* text : more)
+        if (text) return fail(-22, std::string(who) + ": " + text);
+    return scene_prelude(e, who, {}, hm_size, scene_index_fits(n_maps, hm_size), affine_host, n_maps, g);
+}
+// the mask terms and groups of maps [m0, m0 + n), as the kernel argument
+static SceneSelect scene_select(const SceneObjectArgs& o, int m0, int n) {
+    SceneSelect sel;
+    for (int m = 0; m < kSceneMaps; ++m) {
+        const bool in = m < n;
+        sel.a[m] = in ? o.map_mask_a[m0 + m] : -1; sel.b[m] = in ? o.map_mask_b[m0 + m] : -1; sel.group[m] = in ? o.map_group[m0 + m] : -1;
+    }
+    return sel;
+}
+// whole 16-byte mask loads: scene_vec4's split, on the masks
+static int scene_mask_vec(int hm_size, const double* masks_dev) { return (int64_t)hm_size * hm_size % 4 == 0 && (reinterpret_cast<uintptr_t>(masks_dev) & 15) == 0; }
+extern "C++" template <class F>
+static int scene_argmax_objects(smg_engine* e, const char* who, const void* q_dev, std::initializer_list<const char*> own, int n_maps,
+                                const float* affine_host, int hm_size, const SceneObjectArgs& o, int K, int radius,
+                                const SceneNoise* noise, void* stream, F walk) {
     SceneGeo g;
-    if (int rc = scene_prelude(e, who, {o.n_masks < 1 ? "n_masks < 1" : nullptr, o.n_groups < 1 ? "n_groups < 1" : nullptr, bad_mask, bad_group,
-                                        K < 1 ? (noise ? "n_draws < 1" : "K < 1") : nullptr,
+    if (int rc = scene_objects_prelude(e, who, q_dev, own, n_maps, affine_host, hm_size, o, o.idx_out_dev && o.val_out_dev,
+                                       {K < 1 ? (noise ? "n_draws < 1" : "K < 1") : nullptr,
                                         K > (noise ? kSceneDraws : kSceneTopK) ? (noise ? "n_draws exceeds kSceneDraws (32)" : "K exceeds kSceneTopK (32)") : nullptr,
                                         radius < 0 ? "radius < 0" : nullptr,
                                         (int64_t)o.n_groups * K > 0x7fffffff ? (noise ? "n_groups * n_draws does not fit int32" : "n_groups * K does not fit int32") : nullptr,
                                         noise && !(noise->beta >= 0.0 && noise->beta < INFINITY) ? "beta must be finite and not negative" : nullptr},
-                               hm_size, scene_index_fits(n_maps, hm_size), affine_host, n_maps, &g)) return rc;
+                                       &g)) return rc;
     const int tiles = scene_tiles(hm_size);
-    const int mvec = (int64_t)hm_size * hm_size % 4 == 0 && (reinterpret_cast<uintptr_t>(o.masks_dev) & 15) == 0;       // scene_vec4's split, on the masks
+    const int mvec = scene_mask_vec(hm_size, o.masks_dev);
     const unsigned r2 = (unsigned)std::min<int64_t>((int64_t)radius * radius, 0xffffffffll);        // (no two pixels lie farther apart: hm^2 < 2^31)
     for (int j = 0; j < K; ++j) {
         const ScenePicks picks{o.idx_out_dev, K, j, r2};
         const SceneNoise nz{noise ? noise->seed : 0ull, noise ? noise->beta : 0.0, j};
         if (int rc = scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
-                SceneSelect sel;
-                for (int m = 0; m < kSceneMaps; ++m) {
-                    const bool in = m < n;
-                    sel.a[m] = in ? o.map_mask_a[m0 + m] : -1; sel.b[m] = in ? o.map_mask_b[m0 + m] : -1; sel.group[m] = in ? o.map_group[m0 + m] : -1;
-                }
+                const SceneSelect sel = scene_select(o, m0, n);
                 walk(tiles, n, m0, a, sel, g, mvec, picks, nz);
                 if (noise)
                     hipLaunchKernelGGL(scene_sample_group_reduce_kernel, dim3(o.n_groups), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
@@ -666,6 +686,34 @@ static int scene_argmax_objects(smg_engine* e, const char* who, const void* q_de
                                        (const int*)e->scene_idx, tiles, n, sel, m0 > 0 ? 1 : 0, o.idx_out_dev + j, o.val_out_dev + j, K);
             })) return rc;
     }
+    return 0;
+}
+
+// smg_scene_softmax_objects / smg_scene_class_softmax_objects: per group the log-sum-exp and the Boltzmann mean of the candidates
+// scene_argmax_objects sees - the same refusals (scene_objects_prelude; idx / val of `o` are not used) plus beta and the alignment
+// of stats_out_dev.  Per launch of kSceneMaps maps: walk(tiles, n, m0, affines, select, g, mvec) = the form's scene_softmax_walk
+// into the per-workgroup slots (scene_val = M, scene_idx = n, scene_st = (S, T)), then the grouped reduce, which from the second
+// launch on also merges the raw state the earlier ones left in the group's row of stats_out_dev; one last launch finishes the rows.
+extern "C++" template <class F>
+static int scene_softmax_objects(smg_engine* e, const char* who, const void* q_dev, std::initializer_list<const char*> own, int n_maps,
+                                 const float* affine_host, int hm_size, const SceneObjectArgs& o, double beta, double* stats_out_dev,
+                                 void* stream, F walk) {
+    SceneGeo g;
+    if (int rc = scene_objects_prelude(e, who, q_dev, own, n_maps, affine_host, hm_size, o, stats_out_dev != nullptr,
+                                       {!(beta >= 0.0 && beta < INFINITY) ? "beta must be finite and not negative" : nullptr,
+                                        (reinterpret_cast<uintptr_t>(stats_out_dev) & 7) != 0 ? "stats_out_dev is not 8-byte aligned" : nullptr},
+                                       &g)) return rc;
+    const int tiles = scene_tiles(hm_size);
+    const int mvec = scene_mask_vec(hm_size, o.masks_dev);
+    if (int rc = scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
+            const SceneSelect sel = scene_select(o, m0, n);
+            walk(tiles, n, m0, a, sel, g, mvec);
+            hipLaunchKernelGGL(scene_softmax_group_reduce_kernel, dim3(o.n_groups), dim3(256), 0, (hipStream_t)stream, (const float*)e->scene_val,
+                               (const int*)e->scene_idx, (const double2*)e->scene_st, tiles, n, sel, m0 > 0 ? 1 : 0, beta, stats_out_dev);
+        })) return rc;
+    hipLaunchKernelGGL(scene_softmax_finish_kernel, dim3((unsigned)(((int64_t)o.n_groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       stats_out_dev, o.n_groups, beta);
+    HIP_OK(hipGetLastError());
     return 0;
 }
 
@@ -702,6 +750,18 @@ int smg_scene_sample_objects(smg_engine* e, const float* q_dev, int64_t map_stri
                                 [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec, const ScenePicks&, const SceneNoise& nz) {
         hipLaunchKernelGGL(scene_sample_objects_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
                            q_dev, map_stride, m0, a, sel, g, masks_dev, mvec, nz, e->scene_val, e->scene_idx);
+    });
+}
+
+// The normaliser of smg_scene_sample_objects' policy: {count, vmax, lse, mean} per group, the selected walk with the streaming state.
+int smg_scene_softmax_objects(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
+                              const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
+                              int n_groups, double beta, double* stats_out_dev, void* stream) {
+    return scene_softmax_objects(e, "smg_scene_softmax_objects", q_dev, {n_maps < 1 || map_stride < 0 ? "n_maps < 1 or a negative map_stride" : nullptr},
+                                 n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, nullptr, nullptr}, beta, stats_out_dev, stream,
+                                 [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec) {
+        hipLaunchKernelGGL(scene_softmax_objects_kernel, dim3(tiles, n), dim3(256), (size_t)g.OH * g.OW * sizeof(float), (hipStream_t)stream,
+                           q_dev, map_stride, m0, a, sel, g, masks_dev, mvec, beta, e->scene_val, e->scene_idx, e->scene_st);
     });
 }
 
@@ -907,6 +967,21 @@ int smg_scene_class_sample_objects(smg_engine* e, const float* q_dev, int n_maps
         const int64_t P3 = (int64_t)3 * g.OH * g.OW;
         hipLaunchKernelGGL(scene_class_sample_objects_kernel, dim3(tiles, n), dim3(256), (size_t)P3 * sizeof(float), (hipStream_t)stream,
                            q_dev, P3, m0, a, sel, g, cls, masks_dev, mvec, nz, e->scene_val, e->scene_idx);
+    });
+}
+
+// smg_scene_softmax_objects for the 3-class head: the same launches with the walk on the three logit planes, the value P(class cls).
+int smg_scene_class_softmax_objects(smg_engine* e, const float* q_dev, int n_maps, const float* affine_host, int hm_size, int cls,
+                                    const double* masks_dev, int n_masks, const int* map_mask_a, const int* map_mask_b, const int* map_group,
+                                    int n_groups, double beta, double* stats_out_dev, void* stream) {
+    return scene_softmax_objects(e, "smg_scene_class_softmax_objects", q_dev,
+                                 {e && e->head_out != 3 ? "class probabilities need a 3-class head (head_out == 3)" : nullptr,
+                                  n_maps < 1 ? "n_maps < 1" : nullptr, cls < 0 || cls > 2 ? "cls must be 0, 1 or 2" : nullptr},
+                                 n_maps, affine_host, hm_size, {masks_dev, n_masks, map_mask_a, map_mask_b, map_group, n_groups, nullptr, nullptr}, beta, stats_out_dev, stream,
+                                 [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g, int mvec) {
+        const int64_t P3 = (int64_t)3 * g.OH * g.OW;
+        hipLaunchKernelGGL(scene_class_softmax_objects_kernel, dim3(tiles, n), dim3(256), (size_t)P3 * sizeof(float), (hipStream_t)stream,
+                           q_dev, P3, m0, a, sel, g, cls, masks_dev, mvec, beta, e->scene_val, e->scene_idx, e->scene_st);
     });
 }
 

@@ -9,6 +9,9 @@
 //                                  smg_scene_class_topk_objects, which also skips the discs around the group's earlier picks;
 //                                  NOISE: one draw of smg_scene_sample_objects / smg_scene_class_sample_objects, the selected walk
 //                                  that keeps the candidate with the best Gumbel-perturbed score, scene_sample_score)
+//   scene_softmax_walk<PLANES>     smg_scene_softmax_objects / smg_scene_class_softmax_objects: the selected walk that accumulates a
+//                                  streaming log-sum-exp state (SceneSoft) per workgroup instead of an argmax, its grouped reduce
+//                                  and the one-thread-per-group finish
 //   scene_best_walk<PLANES>        smg_scene_best_maps / smg_scene_class_best_maps: per GROUP of maps and heightmap pixel the best
 //                                  value over the group's maps and the map that gives it - parallel over groups and pixel tiles,
 //                                  the group's maps staged one at a time, launches of maps carried through the outputs
@@ -403,6 +406,155 @@ static __global__ __launch_bounds__(256) void scene_sample_group_reduce_kernel(c
                                                                                const SceneSelect sel, int carry, const SceneNoise nz,
                                                                                int* idx_out, float* val_out, int stride) {
     scene_group_reduce<true>(part_val, part_idx, tiles, n_maps, sel, carry, idx_out, val_out, stride, &nz);
+}
+
+// ---- the normaliser of the Boltzmann policy: per group the log-sum-exp and the Boltzmann mean of its candidates ----
+// (smg_scene_softmax_objects, smg_scene_class_softmax_objects).  The candidates of a group are smg_scene_argmax_objects': the
+// selected valid pixels of the group's maps, each with the float32 value v smg_scene_maps stores there.  The STATE of a set of
+// candidates is (n, M, S, T): n = how many, M = the largest value, S = sum exp(beta (v - M)) and T = sum v exp(beta (v - M)) in
+// double; the empty set is (0, -inf, 0, 0).  M is a candidate's float32 itself, so it is exact.
+// scene_soft_add puts one candidate in, at the price of one double exp:
+//   the first candidate:  (1, v, 1, v)
+//   v <= M, or M a NaN:   e = exp(beta (v - M));  S += e;  T = fma(v, e, T)                  (a NaN M stays)
+//   else (a NaN v too):   r = exp(beta (M - v));  S = fma(S, r, 1);  T = fma(T, r, v);  M = v
+// scene_soft_merge joins A (the earlier one) and B: an empty side yields the other side unchanged; else M = MA if MA > MB or MA is
+// a NaN, else MB (so a NaN on either side stays), S = SA exp(beta (MA - M)) + SB exp(beta (MB - M)), T likewise, n = nA + nB.  One
+// of the two factors is exp(0) = 1.  A NaN candidate makes M, S and T of every state it enters NaN and is counted like any other;
+// infinite values are outside the contract (exp(beta (inf - inf)) is a NaN, nothing faults, n stays exact).
+// Everything runs in a fixed order - a thread's pixels ascending, scene_soft_tree over the 256 threads, the slots t, t + 256, ... of
+// a group, the carried state first - and there are no atomics: identical calls are bit-identical.
+struct SceneSoft { int n; float M; double S, T; };
+__device__ __forceinline__ SceneSoft scene_soft_empty() { SceneSoft a; a.n = 0; a.M = -INFINITY; a.S = 0.0; a.T = 0.0; return a; }
+__device__ __forceinline__ void scene_soft_add(SceneSoft& a, float v, double beta) {
+    if (a.n == 0) { a.M = v; a.S = 1.0; a.T = (double)v; }
+    else {
+        const bool below = v <= a.M || a.M != a.M;
+        const double e = exp(beta * (below ? (double)v - (double)a.M : (double)a.M - (double)v));
+        if (below) { a.S += e; a.T = fma((double)v, e, a.T); }
+        else { a.S = fma(a.S, e, 1.0); a.T = fma(a.T, e, (double)v); a.M = v; }
+    }
+    ++a.n;
+}
+__device__ __forceinline__ SceneSoft scene_soft_merge(const SceneSoft A, const SceneSoft B, double beta) {
+    if (B.n == 0) return A;
+    if (A.n == 0) return B;
+    SceneSoft r;
+    r.n = A.n + B.n;
+    r.M = A.M > B.M || A.M != A.M ? A.M : B.M;
+    const double fa = exp(beta * ((double)A.M - (double)r.M)), fb = exp(beta * ((double)B.M - (double)r.M));
+    r.S = A.S * fa + B.S * fb;
+    r.T = A.T * fa + B.T * fb;
+    return r;
+}
+// The fixed tree over the workgroup's 256 states: (S, T) as two doubles per thread (4 KB of LDS), M and n beside them; at every
+// level thread t < s merges its state (the earlier one) with that of thread t + s.  Thread 0 returns the workgroup's state.
+__device__ __forceinline__ SceneSoft scene_soft_tree(SceneSoft a, double beta, int t) {
+    __shared__ double2 st[256];
+    __shared__ float sm[256];
+    __shared__ int sn[256];
+    st[t] = make_double2(a.S, a.T); sm[t] = a.M; sn[t] = a.n;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+            SceneSoft b;
+            b.n = sn[t + s]; b.M = sm[t + s]; b.S = st[t + s].x; b.T = st[t + s].y;
+            a = scene_soft_merge(a, b, beta);
+            st[t] = make_double2(a.S, a.T); sm[t] = a.M; sn[t] = a.n;
+        }
+        __syncthreads();
+    }
+    return a;
+}
+// The walk: scene_walk's tiling, selection and order - one workgroup = one tile of kSceneTile consecutive pixels of one map
+// (blockIdx.y), the planes staged in dynamic LDS (PLANES x OH x OW floats), the masks read BEFORE the geometry (scene_select4), then
+// scene_point, then the very expression scene_walk stores: (float)scene_interp, or scene_class_prob(scene_class, cls).  Only a
+// selected valid pixel pays the exponential of scene_soft_add.  The workgroup's state goes to slot blockIdx.y * gridDim.x +
+// blockIdx.x: M into part_val, n into part_idx, (S, T) into part_st.  A workgroup without a candidate leaves the empty state.
+template <int PLANES>
+__device__ __forceinline__ void scene_softmax_walk(const float* q, int64_t map_stride, int map0, const SceneAffine& aff, const SceneSelect& sel,
+                                                   const SceneGeo& g, int cls, const double* masks, int mvec, double beta,
+                                                   float* part_val, int* part_idx, double2* part_st) {
+    extern __shared__ float sq[];
+    const int t = threadIdx.x, m = blockIdx.y;
+    const int P = g.OH * g.OW;
+    const float* qm = q + (int64_t)(map0 + m) * map_stride;
+    for (int i = t; i < PLANES * P; i += 256) sq[i] = qm[i];
+    __syncthreads();
+    const double a00 = (double)aff.a[m][0], a01 = (double)aff.a[m][1], a10 = (double)aff.a[m][2], a11 = (double)aff.a[m][3];
+    const int npix = g.hm * g.hm;                       // (the host refuses maps of 2^31 pixels or more)
+    const int base = blockIdx.x * kSceneTile;
+    const int ta = sel.a[m], tb = sel.b[m];
+    SceneSoft a = scene_soft_empty();
+    for (int pass = 0; pass < kSceneTile / 1024; ++pass) {
+        const int i0 = base + 4 * (pass * 256 + t);
+        if (i0 >= npix) break;
+        int iy = i0 / g.hm, ix = i0 - iy * g.hm;
+        bool s[4] = {true, true, true, true};
+        if (ta >= 0 || tb >= 0) {
+            s[0] = s[1] = s[2] = s[3] = false;
+            scene_select4(masks, ta, npix, i0, mvec, s);
+            scene_select4(masks, tb, npix, i0, mvec, s);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k, ++ix) {
+            if (ix == g.hm) { ix = 0; ++iy; }
+            if (i0 + k < npix && s[k]) {
+                const ScenePoint p = scene_point(g, a00, a01, a10, a11, iy, ix);
+                if (p.valid) {
+                    float v;
+                    if constexpr (PLANES == 1) v = (float)scene_interp(p, sq, g.OW);
+                    else v = scene_class_prob(scene_class(p, sq, P, g.OW), cls);
+                    scene_soft_add(a, v, beta);
+                }
+            }
+        }
+    }
+    a = scene_soft_tree(a, beta, t);
+    if (t == 0) {
+        const int slot = blockIdx.y * gridDim.x + blockIdx.x;
+        part_val[slot] = a.M; part_idx[slot] = a.n; part_st[slot] = make_double2(a.S, a.T);
+    }
+}
+static __global__ __launch_bounds__(256) void scene_softmax_objects_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                           const SceneSelect sel, const SceneGeo g, const double* masks, int mvec,
+                                                                           double beta, float* part_val, int* part_idx, double2* part_st) {
+    scene_softmax_walk<1>(q, map_stride, map0, aff, sel, g, 0, masks, mvec, beta, part_val, part_idx, part_st);
+}
+static __global__ __launch_bounds__(256) void scene_class_softmax_objects_kernel(const float* q, int64_t map_stride, int map0, const SceneAffine aff,
+                                                                                 const SceneSelect sel, const SceneGeo g, int cls, const double* masks,
+                                                                                 int mvec, double beta, float* part_val, int* part_idx, double2* part_st) {
+    scene_softmax_walk<3>(q, map_stride, map0, aff, sel, g, cls, masks, mvec, beta, part_val, part_idx, part_st);
+}
+// The grouped reduce, the second launch per launch of maps: one workgroup per group (blockIdx.x) merges the slots of this launch's
+// `n_maps` maps (`tiles` slots each, map-major) whose map belongs to its group - thread t takes slots t, t + 256, ... in that order,
+// then the tree.  With `carry` thread 0 starts from the state the earlier launches left in the group's row of stats
+// ([n_groups][4] doubles = n, M, S, T: the row carries the RAW state between launches, n and M exactly as doubles, so there is no
+// per-group scratch).  Every group's row is written: a group without a map, or without a candidate, holds the empty state.
+static __global__ __launch_bounds__(256) void scene_softmax_group_reduce_kernel(const float* part_val, const int* part_idx, const double2* part_st,
+                                                                                int tiles, int n_maps, const SceneSelect sel, int carry,
+                                                                                double beta, double* stats) {
+    const int t = threadIdx.x, grp = blockIdx.x;
+    double* row = stats + (int64_t)grp * 4;
+    SceneSoft a = scene_soft_empty();
+    if (t == 0 && carry) { a.n = (int)row[0]; a.M = (float)row[1]; a.S = row[2]; a.T = row[3]; }
+    for (int i = t; i < tiles * n_maps; i += 256) {
+        if (sel.group[i / tiles] != grp) continue;
+        SceneSoft b;
+        b.n = part_idx[i]; b.M = part_val[i]; b.S = part_st[i].x; b.T = part_st[i].y;
+        a = scene_soft_merge(a, b, beta);
+    }
+    a = scene_soft_tree(a, beta, t);
+    if (t == 0) { row[0] = (double)a.n; row[1] = (double)a.M; row[2] = a.S; row[3] = a.T; }
+}
+// The last launch, one thread per group: the raw state becomes the row {count, vmax, lse = fma(beta, M, log S), mean = T / S}, in
+// place; a group without a candidate gets (0, -inf, -inf, NaN).
+static __global__ __launch_bounds__(256) void scene_softmax_finish_kernel(double* stats, int n_groups, double beta) {
+    const int grp = blockIdx.x * 256 + threadIdx.x;
+    if (grp >= n_groups) return;
+    double* row = stats + (int64_t)grp * 4;
+    const double n = row[0], M = row[1], S = row[2], T = row[3];
+    if (n == 0.0) { row[1] = -INFINITY; row[2] = -INFINITY; row[3] = NAN; }
+    else { row[2] = fma(beta, M, log(S)); row[3] = T / S; }
 }
 
 // ---- the collapsed map: per group and heightmap pixel the best value over the group's maps and which map gives it ----

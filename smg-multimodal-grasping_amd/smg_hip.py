@@ -58,7 +58,8 @@ def lib():
         raise SmgError("%s is ABI version %d, this binding needs %d: rebuild it (make -C csrc)" % (LIB_PATH, L.smg_version(), ABI_VERSION))
     for added in ("smg_loss_scene_map_ce", "smg_scene_argmax_objects", "smg_scene_class_argmax_objects", "smg_scene_values",
                   "smg_scene_class_values", "smg_scene_topk_objects", "smg_scene_class_topk_objects", "smg_scene_best_maps",
-                  "smg_scene_class_best_maps", "smg_scene_sample_objects", "smg_scene_class_sample_objects"):       # (added without a version step: a version-9 library built before them lacks the symbol)
+                  "smg_scene_class_best_maps", "smg_scene_sample_objects", "smg_scene_class_sample_objects", "smg_scene_softmax_objects",
+                  "smg_scene_class_softmax_objects"):       # (added without a version step: a version-9 library built before them lacks the symbol)
         if not hasattr(L, added):
             raise SmgError("%s is ABI version %d but lacks %s, a stale build: rebuild it (make -C csrc)" % (LIB_PATH, ABI_VERSION, added))
     L.smg_abi_struct_bytes.argtypes = [C.c_int]
@@ -96,6 +97,8 @@ def lib():
     L.smg_scene_sample_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int,
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_double, C.c_uint64,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smg_scene_softmax_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int,
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_double, C.c_void_p, C.c_void_p]
     L.smg_loss_scene.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -113,6 +116,8 @@ def lib():
     L.smg_scene_class_sample_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_double, C.c_uint64,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+    L.smg_scene_class_softmax_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_double, C.c_void_p, C.c_void_p]
     L.smg_loss_scene_ce.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
     L.smg_loss_scene_map_ce.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -145,7 +150,7 @@ EXPORTS = (
     "smg_last_error", "smg_version", "smg_abi_struct_bytes", "smg_engine_set_option", "smg_layout_count", "smg_layout_param_floats", "smg_layout_buffer_floats",
     "smg_layout_nbt_count", "smg_layout_entry", "smg_layout_trunk_range", "smg_layout_head_range",
     "smg_engine_create", "smg_engine_destroy", "smg_engine_workspace_bytes", "smg_engine_geometry",
-    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_values", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_scene_topk_objects", "smg_scene_sample_objects", "smg_scene_best_maps", "smg_loss_scene","smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_values", "smg_scene_class_argmax", "smg_scene_class_argmax_objects", "smg_scene_class_topk_objects", "smg_scene_class_sample_objects", "smg_scene_class_best_maps", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
+    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_values", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_scene_topk_objects", "smg_scene_sample_objects", "smg_scene_softmax_objects", "smg_scene_best_maps", "smg_loss_scene","smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_values", "smg_scene_class_argmax", "smg_scene_class_argmax_objects", "smg_scene_class_topk_objects", "smg_scene_class_sample_objects", "smg_scene_class_softmax_objects", "smg_scene_class_best_maps", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
     "smg_profile_enable", "smg_profile_kinds", "smg_profile_kind_name", "smg_profile_read", "smg_profile_read_bytes",
 )
 
@@ -371,6 +376,17 @@ class Engine(object):
         check(lib().smg_scene_sample_objects(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), masks, int(n_masks), ma, mb, gr,
                                              int(n_groups), int(n_draws), float(beta), int(seed), idx_out, val_out, stream))
 
+    def scene_softmax_objects(self, q, map_stride, n_maps, affine, hm_size, masks, n_masks, mask_a, mask_b, groups, n_groups, beta,
+                              stats_out, stream):
+        """smg_scene_softmax_objects: the normaliser of scene_sample_objects' policy - scene_argmax_objects' arguments plus `beta`
+        = 1 / temperature (finite, >= 0).  stats_out float64 [n_groups, 4] = per group {count, vmax, lse, mean} over its selected
+        valid pixels: how many, the largest value, log sum exp(beta * value) and the Boltzmann mean of the value; a group without a
+        candidate is (0, -inf, -inf, NaN).  log pi of a drawn pick is beta * value - lse."""
+        a, p = self._affines(affine, n_maps)
+        sel, (ma, mb, gr) = self._selects(n_maps, mask_a, mask_b, groups)
+        check(lib().smg_scene_softmax_objects(self.h, q, int(map_stride), int(n_maps), p, int(hm_size), masks, int(n_masks), ma, mb, gr,
+                                              int(n_groups), float(beta), stats_out, stream))
+
     def loss_scene(self, q, affine, hm_size, n_pairs, K, pixels, labels, weights, loss_out, dq_out, stream):
         """smg_loss_scene: the weighted Huber on K heightmap pixels (int32 [n_pairs, K, 2] = iy, ix) per pair, dq on the map;
         `weights` None = all ones.  Marks the saved forward so that its backward runs the dense head form."""
@@ -437,6 +453,15 @@ class Engine(object):
         sel, (ma, mb, gr) = self._selects(n_maps, mask_a, mask_b, groups)
         check(lib().smg_scene_class_sample_objects(self.h, q, int(n_maps), p, int(hm_size), int(cls), masks, int(n_masks), ma, mb, gr,
                                                    int(n_groups), int(n_draws), float(beta), int(seed), idx_out, val_out, stream))
+
+    def scene_class_softmax_objects(self, q, n_maps, affine, hm_size, cls, masks, n_masks, mask_a, mask_b, groups, n_groups, beta,
+                                    stats_out, stream):
+        """smg_scene_class_softmax_objects: scene_softmax_objects on the logit maps `q` [n_maps, 3, OH, OW] - scene_class_argmax_objects'
+        arguments plus `beta`; the value is P(class cls), stats_out is float64 [n_groups, 4]."""
+        a, p = self._affines(affine, n_maps)
+        sel, (ma, mb, gr) = self._selects(n_maps, mask_a, mask_b, groups)
+        check(lib().smg_scene_class_softmax_objects(self.h, q, int(n_maps), p, int(hm_size), int(cls), masks, int(n_masks), ma, mb, gr,
+                                                    int(n_groups), float(beta), stats_out, stream))
 
     def loss_scene_ce(self, q, affine, hm_size, n_pairs, K, pixels, labels, loss_out, dq_out, stream):
         """smg_loss_scene_ce: the cross entropy (class weights {1, 1, 0}) on K heightmap pixels (int32 [n_pairs, K, 2] = iy, ix) per

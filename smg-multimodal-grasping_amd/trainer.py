@@ -725,19 +725,23 @@ class Trainer(object):
                                      group_of, groups, idx, val, stream)
         return self._best_scene_objects("best_scene_actions", depth_heightmap, mask_depth, is_ets, is_target, argmax)
 
-    def _scene_object_picks(self, what, depth_heightmap, mask_depth, is_ets, is_target, pick, k=1, joint=False):
+    def _scene_object_picks(self, what, depth_heightmap, mask_depth, is_ets, is_target, pick, k=1, joint=False, stats=None, betas=()):
         """The loop behind best_scene_actions, ranked_scene_actions, sampled_scene_actions and their class forms (the caller has
         checked method and geometry): one forward per primitive, one pick(engine, q, n_maps, affines, hm, masks, mask_a, mask_b,
         group of every map, n_groups, idx pointer, val pointer, stream, style) on its maps - which writes `k` (index, value) pairs
         per group - and one read-back.  The groups are the objects (the pairs), or with `joint` ONE group of all the primitive's
         maps.  Returns (calls = per primitive (first group, groups, maps per object), indices [all groups, k], values float64
-        [all groups, k], the pair list or None, hm); the maps behind the result stay in self._last_object_q."""
+        [all groups, k], the pair list or None, hm, statistics); the maps behind the result stay in self._last_object_q.
+        `stats` (scene_policy_stats, and the sampled forms' with_stats): after the pick, one stats(engine, q, n_maps, affines, hm,
+        masks, mask_a, mask_b, group of every map, n_groups, row pointer, stream, beta) per entry of `betas` on the same maps and
+        masks, enqueued before the read-back; statistics = float64 [len(betas), all groups, 4] = {count, vmax, lse, mean}, else
+        None.  `pick` None: the statistics alone (indices and values are None)."""
         n = int(np.asarray(mask_depth).shape[0])
         if n < 1:
             raise ValueError("%s: mask_depth holds no object" % what)
         hm = int(np.shape(depth_heightmap)[-1])
         n_pairs = n * (n - 1) // 2 if is_ets else 0
-        idx = val = pair_list = None
+        idx = val = pair_list = rows = None
         calls, kept = [], {}              # per primitive: (offset into idx / val, groups, maps per group)
         for style, name in ((0, "grasp"), (1, "suction"), (2, "pairs")):
             if style == 2:
@@ -751,19 +755,27 @@ class Trainer(object):
                 model, q, m, groups, per = self._object_maps(what, depth_heightmap, mask_depth, style, is_target)
                 rots = [(r, per) for k_ in range(groups) for r in range(per)]
                 mask_a, mask_b = [k_ for k_ in range(groups) for r in range(per)], [-1] * (groups * per)
-            if idx is None:
+            if idx is None and pick is not None:
                 idx = torch.empty((2 * n + n_pairs, k), dtype=torch.int32, device=q.device)
                 val = torch.empty((2 * n + n_pairs, k), dtype=torch.float32, device=q.device)
+            if rows is None and stats is not None:
+                rows = torch.empty((len(betas), 2 * n + n_pairs, 4), dtype=torch.float64, device=q.device)
             off = sum(c[1] for c in calls)
             eng, aff, _, stream = self._scene_call(model, q, depth_heightmap, rots)
             group_of = [j // per for j in range(len(rots))]
             if joint:
                 groups, group_of = 1, [0] * len(rots)
-            pick(eng, q, len(rots), aff, hm, m, mask_a, mask_b, group_of, groups, idx[off:].data_ptr(), val[off:].data_ptr(), stream, style)
+            if pick is not None:
+                pick(eng, q, len(rots), aff, hm, m, mask_a, mask_b, group_of, groups, idx[off:].data_ptr(), val[off:].data_ptr(), stream, style)
+            for j, beta in enumerate(betas if stats is not None else ()):
+                stats(eng, q, len(rots), aff, hm, m, mask_a, mask_b, group_of, groups, rows[j, off:].data_ptr(), stream, beta)
             calls.append((off, groups, per))
             kept[name] = q
         self._last_object_q = kept        # the maps behind the result, object-major: "grasp" / "suction" [n * R, HEAD_OUT, OH, OW], "pairs" [n_pairs, HEAD_OUT, OH, OW]
-        return calls, idx.cpu().numpy(), val.cpu().numpy().astype(np.float64), pair_list, hm
+        rows = None if rows is None else rows.cpu().numpy()
+        if pick is None:
+            return calls, None, None, pair_list, hm, rows
+        return calls, idx.cpu().numpy(), val.cpu().numpy().astype(np.float64), pair_list, hm, rows
 
     @staticmethod
     def _scene_entry(i, conf, hm, per):
@@ -774,7 +786,7 @@ class Trainer(object):
     def _best_scene_objects(self, what, depth_heightmap, mask_depth, is_ets, is_target, argmax):
         """The body of best_scene_actions and best_scene_class_actions (the caller has checked method and geometry):
         _scene_object_picks with one pair per group, and the host decode of index -> (object, rotation, pixel)."""
-        calls, i_all, v_all, pair_list, hm = self._scene_object_picks(what, depth_heightmap, mask_depth, is_ets, is_target, argmax)
+        calls, i_all, v_all, pair_list, hm, _ = self._scene_object_picks(what, depth_heightmap, mask_depth, is_ets, is_target, argmax)
 
         def decode(off, groups, per):
             """Per group (rotation, (iy, ix), conf) or None, and the overall best group or None."""
@@ -804,11 +816,20 @@ class Trainer(object):
             raise ValueError("%s: radius must be an integer >= 0, in heightmap pixels" % what)
         return int(k), int(radius)
 
-    def _ranked_scene_objects(self, what, depth_heightmap, mask_depth, k, is_ets, is_target, topk, joint=False):
+    def _ranked_scene_objects(self, what, depth_heightmap, mask_depth, k, is_ets, is_target, topk, joint=False, stats=None, beta=None):
         """The body of ranked_scene_actions, sampled_scene_actions and their class forms (the caller has checked method, geometry
         and the pick's own arguments): _scene_object_picks with k pairs per group and the host decode of every rank (draw).
-        `joint` (the sampled forms): one group per primitive, decoded to (object, rotation, pixel, conf) per draw."""
-        calls, i_all, v_all, pair_list, hm = self._scene_object_picks(what, depth_heightmap, mask_depth, is_ets, is_target, topk, k, joint)
+        `joint` (the sampled forms): one group per primitive, decoded to (object, rotation, pixel, conf) per draw.
+        `stats` (the sampled forms' with_stats): the statistics call at `beta` on the same maps; the result gains "stats" and
+        "logp" (_with_logp)."""
+        calls, i_all, v_all, pair_list, hm, rows = self._scene_object_picks(what, depth_heightmap, mask_depth, is_ets, is_target, topk, k, joint,
+                                                                            stats, () if stats is None else (beta,))
+        if stats is not None:
+            return self._with_logp(self._ranked_decode(calls, i_all, v_all, pair_list, hm, k, joint), calls, rows[0], beta, joint)
+        return self._ranked_decode(calls, i_all, v_all, pair_list, hm, k, joint)
+
+    def _ranked_decode(self, calls, i_all, v_all, pair_list, hm, k, joint):
+        """_ranked_scene_objects' host decode of what _scene_object_picks read back."""
 
         def decode(off, groups, per):
             lists = [[self._scene_entry(i_all[off + g, j], v_all[off + g, j], hm, per) for j in range(k)] for g in range(groups)]
@@ -878,7 +899,8 @@ class Trainer(object):
         """The seed of the sample call for primitive `style`: without the step the primitives would share one noise field."""
         return (seed + style * 0x9E3779B97F4A7C15) % 2 ** 64
 
-    def sampled_scene_actions(self, depth_heightmap, mask_depth, n_draws, temperature, seed, is_ets=True, is_target=False, joint=False):
+    def sampled_scene_actions(self, depth_heightmap, mask_depth, n_draws, temperature, seed, is_ets=True, is_target=False, joint=False,
+                              with_stats=False):
         """EXPLORATION for best_scene_actions: instead of the best pixel, `n_draws` independent Boltzmann draws per object - a
         (rotation, pixel) of the object's own pixels drawn with probability proportional to exp(Q / temperature).  The same
         forwards - one per primitive, the maps kept in self._last_object_q -, one smg_scene_sample_objects per primitive and one
@@ -893,6 +915,10 @@ class Trainer(object):
         joint=True: all objects of a primitive form ONE group, the draw is over (object, rotation, pixel) jointly; per_object is
         replaced by joint = {"grasp": [(object, rotation, (iy, ix), conf)], "suction": [...], "pairs": [((g, s), (iy, ix), conf)]}
         in draw order, per_pair is [], and ranked is built from it.
+        with_stats=True: one smg_scene_softmax_objects per primitive is enqueued on the same maps and masks before the read-back,
+        and two keys are added - stats = scene_policy_stats' dict at this temperature, and logp = {"grasp": [...], "suction":
+        [...], "pairs": [...]}, lists parallel to per_object / per_pair (or to joint) with log pi = conf / temperature - lse of the
+        entry's group in float64: the behaviour policy's log-probability of every draw.
         1 <= n_draws <= 32, temperature > 0 and 0 <= seed < 2^64, else ValueError."""
         self._require_scene("sampled_scene_actions", depth_heightmap)
         n_draws, beta, seed = self._require_draws("sampled_scene_actions", n_draws, temperature, seed)
@@ -900,7 +926,128 @@ class Trainer(object):
         def sample(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream, style):
             eng.scene_sample_objects(q.data_ptr(), q.shape[2] * q.shape[3], n_maps, aff, hm, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
                                      group_of, groups, n_draws, beta, self._style_seed(seed, style), idx, val, stream)
-        return self._ranked_scene_objects("sampled_scene_actions", depth_heightmap, mask_depth, n_draws, is_ets, is_target, sample, joint)
+        return self._ranked_scene_objects("sampled_scene_actions", depth_heightmap, mask_depth, n_draws, is_ets, is_target, sample, joint,
+                                          self._q_softmax if with_stats else None, beta)
+
+    # ---- the normaliser of the Boltzmann policy: log-sum-exp, mean, entropy and mellowmax per object ---------------------------------
+    @staticmethod
+    def _q_softmax(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, rows, stream, beta):
+        eng.scene_softmax_objects(q.data_ptr(), q.shape[2] * q.shape[3], n_maps, aff, hm, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
+                                  group_of, groups, beta, rows, stream)
+
+    @staticmethod
+    def _class_softmax(cls):
+        def stats(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, rows, stream, beta):
+            eng.scene_class_softmax_objects(q.data_ptr(), n_maps, aff, hm, cls, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
+                                            group_of, groups, beta, rows, stream)
+        return stats
+
+    @staticmethod
+    def _require_betas(what, temperature):
+        """-> (betas = 1 / temperature per entry, whether `temperature` was a sequence), validated as _require_draws validates it."""
+        seq = not np.isscalar(temperature)
+        ts = [float(t) for t in temperature] if seq else [float(temperature)]
+        if not ts or not all(t > 0 for t in ts):               # (a NaN fails this too)
+            raise ValueError("%s: temperature must be > 0 (inf is the uniform policy)" % what)
+        return [1.0 / t for t in ts], seq
+
+    @staticmethod
+    def _policy_stats(rows, beta):
+        """Rows [..., groups, 4] = {count, vmax, lse, mean} and beta (a scalar, or [temperatures, 1]) -> scene_policy_stats' dict of
+        one primitive: entropy = lse - beta mean, mellowmax = (lse - log count) / beta (beta = 0, the uniform policy: the mean)."""
+        rows = np.asarray(rows, dtype=np.float64)
+        beta = np.asarray(beta, dtype=np.float64)
+        count, vmax, lse, mean = (rows[..., c] for c in range(4))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            soft = np.where(beta > 0, (lse - np.log(count)) / np.where(beta > 0, beta, 1.0), mean)
+            return dict(count=count, vmax=vmax, lse=lse, mean=mean, entropy=lse - beta * mean, mellowmax=soft, beta=beta)
+
+    def _policy_stats_out(self, calls, rows, betas, seq):
+        """The statistics _scene_object_picks read back ([temperatures, all groups, 4]) as {"grasp", "suction", "pairs"} of
+        _policy_stats dicts; a scalar temperature drops the leading axis, "pairs" has no group when no pair was evaluated."""
+        beta = np.asarray(betas, dtype=np.float64).reshape(-1, 1) if seq else np.float64(betas[0])
+        out = {}
+        for j, name in enumerate(("grasp", "suction", "pairs")):
+            off, groups = (calls[j][0], calls[j][1]) if j < len(calls) else (0, 0)
+            part = rows[:, off:off + groups]
+            out[name] = self._policy_stats(part if seq else part[0], beta)
+        return out
+
+    def scene_policy_stats(self, depth_heightmap, mask_depth, temperature, is_ets=True, is_target=False, joint=False):
+        """What sampled_scene_actions' policy looks like, without drawing from it: per object (per pair) the statistics of the
+        Boltzmann policy pi proportional to exp(Q / temperature) over the object's own pixels with a window and all its rotations.
+        best_scene_actions' forwards - one per primitive, the maps kept in self._last_object_q -, one smg_scene_softmax_objects per
+        primitive and temperature, and one read-back; nothing of [n * R, hm, hm] is written.
+        Returns {"grasp": d, "suction": d, "pairs": d}, each d a dict of float64 arrays over the objects (pairs; no entry with
+        fewer than two objects or is_ets False): count = the candidates, vmax = the largest Q, lse = log sum exp(Q / temperature)
+        - so that log pi(a) = Q(a) / temperature - lse -, mean = the expectation of Q under pi (the expected-SARSA bootstrap),
+        entropy = lse - mean / temperature (exp of it = the effective number of candidates), mellowmax = temperature *
+        (lse - log count), the soft maximum that lies between the arithmetic mean of Q and `mean` (entropy <= log count); and beta
+        = 1 / temperature.  An object without a candidate has
+        count 0, vmax and lse -inf and NaN elsewhere.  joint=True: one group per primitive, over (object, rotation, pixel).
+        `temperature` may be a sequence: the forwards run once, the maps are reused, and every array gains a leading temperature
+        axis.  temperature > 0 (inf: the uniform policy, mellowmax = mean), else ValueError."""
+        self._require_scene("scene_policy_stats", depth_heightmap)
+        betas, seq = self._require_betas("scene_policy_stats", temperature)
+        calls, _, _, _, _, rows = self._scene_object_picks("scene_policy_stats", depth_heightmap, mask_depth, is_ets, is_target, None,
+                                                           joint=joint, stats=self._q_softmax, betas=betas)
+        return self._policy_stats_out(calls, rows, betas, seq)
+
+    @staticmethod
+    def merge_policy_stats(*stats):
+        """The merge rule of include/smg_hip.h on the host: the statistics dicts (scene_policy_stats' per primitive, same
+        temperature(s)) taken together as ONE candidate set - all groups of all arguments merged in order.  Each group's state is
+        recovered as n = count, M = vmax, S = exp(lse - beta M), T = mean S; an empty group is skipped; else M = max (a NaN
+        stays), S = SA exp(beta (MA - M)) + SB exp(beta (MB - M)), T likewise, n = nA + nB.  Returns the dict of the merged set,
+        its arrays with a last axis of one group: merging the three joint=True primitives gives the policy over all actions,
+        merging one primitive's per-object dict gives its joint=True row."""
+        if not stats:
+            raise ValueError("merge_policy_stats: nothing to merge")
+        beta = np.asarray(stats[0]["beta"], dtype=np.float64)
+        for d in stats[1:]:
+            if not np.array_equal(np.asarray(d["beta"], dtype=np.float64), beta):
+                raise ValueError("merge_policy_stats: the statistics were taken at different temperatures")
+        b = beta[..., 0] if beta.ndim else beta                # per temperature, without the group axis
+        lead = np.shape(stats[0]["count"])[:-1]
+        n, M = np.zeros(lead), np.full(lead, -np.inf)
+        S, T = np.zeros(lead), np.zeros(lead)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for d in stats:
+                for g in range(np.shape(d["count"])[-1]):
+                    nb, Mb = np.asarray(d["count"])[..., g], np.asarray(d["vmax"])[..., g]
+                    has = nb > 0
+                    Sb = np.where(has, np.exp(np.asarray(d["lse"])[..., g] - np.where(has, b * Mb, 0.0)), 0.0)
+                    Tb = np.where(has, np.asarray(d["mean"])[..., g], 0.0) * Sb
+                    Mn = np.where((M > Mb) | np.isnan(M), M, Mb)
+                    fa, fb = np.exp(b * (M - Mn)), np.exp(b * (Mb - Mn))
+                    first = n == 0
+                    Sm = np.where(first, Sb, S * np.where(first, 0.0, fa) + Sb * fb)
+                    Tm = np.where(first, Tb, T * np.where(first, 0.0, fa) + Tb * fb)
+                    S, T = np.where(has, Sm, S), np.where(has, Tm, T)
+                    M = np.where(has, np.where(first, Mb, Mn), M)
+                    n = n + np.where(has, nb, 0.0)
+            some = n > 0
+            lse = np.where(some, np.where(some, b * M, 0.0) + np.log(np.where(some, S, 1.0)), -np.inf)
+            mean = np.where(some, T / np.where(some, S, 1.0), np.nan)
+        rows = np.stack([n, M, lse, mean], axis=-1)[..., None, :]
+        return Trainer._policy_stats(rows, beta)
+
+    @staticmethod
+    def _with_logp(out, calls, rows, beta, joint):
+        """The sampled forms' with_stats: `out` (their decoded dict) gains stats (rows = [all groups, 4] at this beta) and logp =
+        beta conf - lse of the entry's group, lists parallel to per_object / per_pair, or to joint."""
+        stats, logp = {}, {}
+        for j, name in enumerate(("grasp", "suction", "pairs")):
+            off, groups = (calls[j][0], calls[j][1]) if j < len(calls) else (0, 0)
+            stats[name] = Trainer._policy_stats(rows[off:off + groups], np.float64(beta))
+            lse = stats[name]["lse"]
+            if joint:
+                logp[name] = [beta * np.float64(e[-1]) - lse[0] for e in out["joint"][name]]
+            else:
+                lists = out["per_pair"] if name == "pairs" else out["per_object"][name]
+                logp[name] = [[beta * np.float64(e[-1]) - lse[g] for e in entries] for g, entries in enumerate(lists)]
+        out["stats"], out["logp"] = stats, logp
+        return out
 
     @staticmethod
     def ranked_to_best(ranked, primitive_action, j):
@@ -1194,10 +1341,12 @@ class Trainer(object):
                                          group_of, groups, k, radius, idx, val, stream)
         return self._ranked_scene_objects("ranked_scene_class_actions", depth_heightmap, mask_depth, k, is_ets, False, topk)
 
-    def sampled_scene_class_actions(self, depth_heightmap, mask_depth, n_draws, temperature, seed, is_ets=True, joint=False, cls=0):
+    def sampled_scene_class_actions(self, depth_heightmap, mask_depth, n_draws, temperature, seed, is_ets=True, joint=False, cls=0,
+                                    with_stats=False):
         """sampled_scene_actions for the reactive net: best_scene_class_actions' forwards, one smg_scene_class_sample_objects per
         primitive on the logits and one read-back - `n_draws` draws per object (per pair, or with `joint` per primitive) with
-        probability proportional to exp(P(class `cls`) / temperature).  Returns sampled_scene_actions' dict.  Reactive method only,
+        probability proportional to exp(P(class `cls`) / temperature).  Returns sampled_scene_actions' dict; with_stats adds its
+        stats and logp keys (one smg_scene_class_softmax_objects per primitive before the read-back).  Reactive method only,
         no is_target; 1 <= n_draws <= 32, temperature > 0, 0 <= seed < 2^64 and cls in {0, 1, 2}, else ValueError."""
         self._require_class_objects("sampled_scene_class_actions", depth_heightmap, mask_depth)
         if cls not in (0, 1, 2):
@@ -1208,7 +1357,22 @@ class Trainer(object):
         def sample(eng, q, n_maps, aff, hm, m, mask_a, mask_b, group_of, groups, idx, val, stream, style):
             eng.scene_class_sample_objects(q.data_ptr(), n_maps, aff, hm, cls, m.data_ptr(), int(m.shape[0]), mask_a, mask_b,
                                            group_of, groups, n_draws, beta, self._style_seed(seed, style), idx, val, stream)
-        return self._ranked_scene_objects("sampled_scene_class_actions", depth_heightmap, mask_depth, n_draws, is_ets, False, sample, joint)
+        return self._ranked_scene_objects("sampled_scene_class_actions", depth_heightmap, mask_depth, n_draws, is_ets, False, sample, joint,
+                                          self._class_softmax(cls) if with_stats else None, beta)
+
+    def scene_class_policy_stats(self, depth_heightmap, mask_depth, temperature, is_ets=True, joint=False, cls=0):
+        """scene_policy_stats for the reactive net: best_scene_class_actions' forwards, one smg_scene_class_softmax_objects per
+        primitive and temperature on the logits and one read-back - the statistics of the policy proportional to
+        exp(P(class `cls`) / temperature) per object (per pair, or with `joint` per primitive).  Returns scene_policy_stats' dict.
+        Reactive method only, no is_target; temperature > 0 and cls in {0, 1, 2}, else ValueError."""
+        self._require_class_objects("scene_class_policy_stats", depth_heightmap, mask_depth)
+        if cls not in (0, 1, 2):
+            raise ValueError("scene_class_policy_stats: cls must be 0, 1 or 2")
+        self._scene_geometry(np.shape(depth_heightmap)[-1])
+        betas, seq = self._require_betas("scene_class_policy_stats", temperature)
+        calls, _, _, _, _, rows = self._scene_object_picks("scene_class_policy_stats", depth_heightmap, mask_depth, is_ets, False, None,
+                                                           joint=joint, stats=self._class_softmax(cls), betas=betas)
+        return self._policy_stats_out(calls, rows, betas, seq)
 
     def train_batch_scene_class_pixels(self, depth_heightmap, m_depth_heightmap, style, rotations, pixels, labels, grad_sync=None,
                                        return_q=False):
@@ -1571,6 +1735,31 @@ class Trainer(object):
         else:
             m, style, rot, pixel = self._scene_action("get_label_value_scene", best, exploit_action, depth_heightmap, mask_depth)
             future_reward = self.scene_values(depth_heightmap, m, [pixel], style, is_target=True, specific_rotation=rot)[0, 0]
+        expected_reward = current_reward + self.future_reward_discount * future_reward
+        print('Expected reward: %f + %f x %f = %f' % (current_reward, self.future_reward_discount, future_reward, expected_reward))
+        return expected_reward, current_reward
+
+    def get_label_value_scene_soft(self, primitive_action, objects_number, suction_success, grasp_success, gs_success,
+                                   depth_heightmap, mask_depth, temperature, kind, is_ets=True):
+        """get_label_value_scene with a bootstrap that is consistent with Boltzmann exploration at `temperature` (reinforcement
+        method only, else ValueError).  Rewards and the two zero-future cases are get_label_value_scene's; otherwise the future
+        reward comes from the TARGET net's policy over ALL actions of the scene - scene_policy_stats(is_target=True, joint=True),
+        its primitives merged (merge_policy_stats) -: kind "expected" = the Boltzmann-weighted expectation of Q, the merged mean
+        (expected SARSA); kind "mellowmax" = temperature * (lse - log count), the non-expansive soft maximum, which lies between
+        the arithmetic mean of the target's Q and that expectation.  Prints the reference's line, returns (expected_reward, current_reward)."""
+        if self.method != 'reinforcement':
+            raise ValueError("get_label_value_scene_soft: the soft bootstrap needs method == 'reinforcement'")
+        if kind not in ("expected", "mellowmax"):
+            raise ValueError("get_label_value_scene_soft: kind must be 'expected' or 'mellowmax'")
+        if not np.isscalar(temperature):
+            raise ValueError("get_label_value_scene_soft: one temperature")
+        current_reward, no_future = self._reward_now(primitive_action, objects_number, suction_success, grasp_success, gs_success)
+        if no_future:
+            future_reward = 0
+        else:
+            stats = self.scene_policy_stats(depth_heightmap, mask_depth, temperature, is_ets=is_ets, is_target=True, joint=True)
+            merged = self.merge_policy_stats(*(stats[name] for name in ("grasp", "suction", "pairs")))
+            future_reward = float(merged["mean" if kind == "expected" else "mellowmax"][0])
         expected_reward = current_reward + self.future_reward_discount * future_reward
         print('Expected reward: %f + %f x %f = %f' % (current_reward, self.future_reward_discount, future_reward, expected_reward))
         return expected_reward, current_reward
