@@ -395,6 +395,51 @@ int smg_loss_scene(smg_engine* e, const float* q_dev, const float* affine_host, 
 int smg_loss_scene_map(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs,
                        const float* label_dev, const float* weight_dev, float* loss_dev, float* dq_dev, void* stream);
 
+/* TRAINING the Boltzmann policy of smg_scene_sample_objects: per group of pairs the negative log-likelihood of an executed action
+ * and the entropy of the policy, with their gradient on the maps.  One-channel heads only (head_out != 1 returns -22): q and dq are
+ * [n_pairs][1][OH][OW].  masks_dev, n_masks, pair_mask_a, pair_mask_b, pair_group and n_groups mean what they mean for
+ * smg_scene_argmax_objects, a "map" there being a pair here: selection by "not exactly 0" (-0.0 does not select, a NaN does), the
+ * union of the two terms, both terms -1 = every pixel, groups that need not be contiguous, the same geometry and validity.  The
+ * CANDIDATES of group g are the selected valid pixels of its pairs, each with the float32 v_i smg_scene_maps stores there, and
+ * pi_i = exp(beta v_i - lse_g), beta = 1 / temperature.
+ * action_dev int32 [n_groups]: the executed action of the group as a flattened index into [n_pairs][hm_size][hm_size], -1 = none.
+ * weight_dev float64 [n_groups][2] = {w_nll, w_ent}; w_nll may be negative (an advantage).  Both are device pointers: the call
+ * stays asynchronous.  With lse and mean of smg_scene_softmax_objects:
+ *     H_g    = lse_g - beta mean_g                                    (the entropy of pi)
+ *     loss_g = w_nll (lse_g - beta v_act) - w_ent H_g
+ *     dloss_g/dv_i = pi_i (A + B (v_i - mean_g)) + C [i == act_g],    A = w_nll beta,  B = w_ent beta^2,  C = -w_nll beta
+ *     dq[j][oy][ox] = sum over the candidates i of pair j of dloss/dv_i * (bilinear weight of (oy, ox) at pixel i)
+ * The float32 rounding of v_i is treated as the identity in the gradient, so with w_nll = 1, w_ent = 0 the loss is the very number
+ * the sampled forms report as -logp = -(beta v - lse).  With act_g == -1 the w_nll term and C are absent, and w_nll is ignored
+ * whatever it holds (a NaN included).
+ * Outputs: stats_out_dev float64 [n_groups][4] receives, bit for bit, what smg_scene_softmax_objects writes for the same arguments;
+ * loss_dev float32 [n_groups]; dq_dev [n_pairs][1][OH][OW], every element written by every successful call.
+ *   A group without a candidate: stats (0, -inf, -inf, NaN), loss 0 if act == -1 (else NaN), its pairs' dq exactly 0.
+ *   An action that is not a candidate of its group - out of range, in a pair of another group, not selected, without a window -
+ *     makes loss[g] NaN; the pi and entropy parts of that group's dq are still written.  No address is ever formed from the action
+ *     (it is only compared with the indices of the pixels that are walked); a caller refuses such actions first.
+ *   A NaN candidate makes its group's loss NaN and every element of its pairs' dq NaN; other groups are untouched, bit for bit.
+ * Three phases on the caller's stream.  (1) The normaliser: smg_scene_softmax_objects' launches, unchanged, over all launches of
+ * 32 pairs - every group's lse and mean are final before the gradient starts, so a group split by the 32-pair boundary needs no
+ * care.  (2) The gather: one workgroup per (pair, map element), as smg_loss_scene_map; the masks are tested at the pixel, then
+ * v = the very expression the walks store, pi = exp(fma(beta, v, -lse)); the element's sum is accumulated in double, reduced by a
+ * fixed tree, rounded to float32 once and written once, zeros included.  The one thread that meets the action at its home element
+ * (the corner (y0, x0) of its pixel) writes v_act: flattened indices are unique and a pixel has one home, so there is one writer.
+ * (3) One thread per group forms loss_g in double and rounds once.  No atomics, no scratch of the engine beyond the normaliser's:
+ * identical calls are bit-identical, and a pair's dq does not depend on which launch carries it.
+ * Returns -22 and launches nothing for every refusal of smg_scene_argmax_objects (n_maps read as n_pairs), head_out != 1, a NULL
+ * pointer, a beta that is negative, NaN or infinite, and a stats_out_dev or weight_dev that is not 8-byte aligned.
+ * Marks the saved forward "dense dq" exactly as smg_loss_scene does. */
+int smg_loss_scene_policy(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs,
+                          const double* masks_dev, int n_masks, const int* pair_mask_a, const int* pair_mask_b,
+                          const int* pair_group, int n_groups, double beta,
+                          const int* action_dev,      /* int32 [n_groups], -1 = no action */
+                          const double* weight_dev,   /* float64 [n_groups][2] = {w_nll, w_ent} */
+                          double* stats_out_dev,      /* float64 [n_groups][4] = smg_scene_softmax_objects' row */
+                          float* loss_dev,            /* float32 [n_groups] */
+                          float* dq_dev,              /* [n_pairs][1][OH][OW], every element written */
+                          void* stream);
+
 /* ---- the reactive net's class maps in the scene frame --------------------------------------------------------------------------
  * The same services for a 3-class head (head_out != 3 returns -22 and launches nothing): q_dev is [n_maps][3][OH][OW], the
  * head output.  The geometry is steps 1-7 above, unchanged.  At a heightmap pixel that is valid in a map's rotation, in double:

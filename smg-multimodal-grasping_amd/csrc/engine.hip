@@ -694,15 +694,10 @@ static int scene_argmax_objects(smg_engine* e, const char* who, const void* q_de
 // of stats_out_dev.  Per launch of kSceneMaps maps: walk(tiles, n, m0, affines, select, g, mvec) = the form's scene_softmax_walk
 // into the per-workgroup slots (scene_val = M, scene_idx = n, scene_st = (S, T)), then the grouped reduce, which from the second
 // launch on also merges the raw state the earlier ones left in the group's row of stats_out_dev; one last launch finishes the rows.
+// scene_softmax_launches = the launches alone, behind a prelude that has passed: smg_loss_scene_policy's phase 1 enters there.
 extern "C++" template <class F>
-static int scene_softmax_objects(smg_engine* e, const char* who, const void* q_dev, std::initializer_list<const char*> own, int n_maps,
-                                 const float* affine_host, int hm_size, const SceneObjectArgs& o, double beta, double* stats_out_dev,
-                                 void* stream, F walk) {
-    SceneGeo g;
-    if (int rc = scene_objects_prelude(e, who, q_dev, own, n_maps, affine_host, hm_size, o, stats_out_dev != nullptr,
-                                       {!(beta >= 0.0 && beta < INFINITY) ? "beta must be finite and not negative" : nullptr,
-                                        (reinterpret_cast<uintptr_t>(stats_out_dev) & 7) != 0 ? "stats_out_dev is not 8-byte aligned" : nullptr},
-                                       &g)) return rc;
+static int scene_softmax_launches(smg_engine* e, int n_maps, const float* affine_host, int hm_size, const SceneObjectArgs& o, const SceneGeo& g,
+                                  double beta, double* stats_out_dev, void* stream, F walk) {
     const int tiles = scene_tiles(hm_size);
     const int mvec = scene_mask_vec(hm_size, o.masks_dev);
     if (int rc = scene_groups(affine_host, n_maps, [&](int m0, int n, const SceneAffine& a) {
@@ -715,6 +710,17 @@ static int scene_softmax_objects(smg_engine* e, const char* who, const void* q_d
                        stats_out_dev, o.n_groups, beta);
     HIP_OK(hipGetLastError());
     return 0;
+}
+extern "C++" template <class F>
+static int scene_softmax_objects(smg_engine* e, const char* who, const void* q_dev, std::initializer_list<const char*> own, int n_maps,
+                                 const float* affine_host, int hm_size, const SceneObjectArgs& o, double beta, double* stats_out_dev,
+                                 void* stream, F walk) {
+    SceneGeo g;
+    if (int rc = scene_objects_prelude(e, who, q_dev, own, n_maps, affine_host, hm_size, o, stats_out_dev != nullptr,
+                                       {!(beta >= 0.0 && beta < INFINITY) ? "beta must be finite and not negative" : nullptr,
+                                        (reinterpret_cast<uintptr_t>(stats_out_dev) & 7) != 0 ? "stats_out_dev is not 8-byte aligned" : nullptr},
+                                       &g)) return rc;
+    return scene_softmax_launches(e, n_maps, affine_host, hm_size, o, g, beta, stats_out_dev, stream, walk);
 }
 
 int smg_scene_argmax_objects(smg_engine* e, const float* q_dev, int64_t map_stride, int n_maps, const float* affine_host, int hm_size,
@@ -864,6 +870,44 @@ int smg_loss_scene_map(smg_engine* e, const float* q_dev, const float* affine_ho
                                q_dev, m0, a, g, label_dev, weight_dev, e->scene_lpart, dq_dev);
             hipLaunchKernelGGL(loss_scene_map_reduce_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (const double*)e->scene_lpart, P, m0, loss_dev);
         })) return rc;
+    e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0), as after smg_loss_scene
+    return 0;
+}
+
+// smg_loss_scene_policy: the log-likelihood and entropy loss of the Boltzmann policy per group of pairs, three phases on the caller's
+// stream (scene.cuh).  Phase 1 is smg_scene_softmax_objects' launches on the pairs as maps, OH * OW apart: every group's row of
+// stats_out_dev is final before phase 2 starts, so a group split by the kSceneMaps boundary needs no care.  Phase 2 gathers dq per
+// (pair, map element), kSceneMaps pairs per launch; phase 3 turns loss_dev from v_act into the losses.  No scratch of the engine
+// beyond the softmax path's slots.
+int smg_loss_scene_policy(smg_engine* e, const float* q_dev, const float* affine_host, int hm_size, int n_pairs,
+                          const double* masks_dev, int n_masks, const int* pair_mask_a, const int* pair_mask_b, const int* pair_group,
+                          int n_groups, double beta, const int* action_dev, const double* weight_dev, double* stats_out_dev,
+                          float* loss_dev, float* dq_dev, void* stream) {
+    const SceneObjectArgs o{masks_dev, n_masks, pair_mask_a, pair_mask_b, pair_group, n_groups, nullptr, nullptr};
+    SceneGeo g;
+    if (int rc = scene_objects_prelude(e, "smg_loss_scene_policy", q_dev,
+                                       {e && e->head_out != 1 ? "the policy loss needs a one-channel head (head_out == 1)" : nullptr,
+                                        n_pairs < 1 ? "n_pairs < 1" : nullptr},
+                                       n_pairs, affine_host, hm_size, o, action_dev && weight_dev && stats_out_dev && loss_dev && dq_dev,
+                                       {!(beta >= 0.0 && beta < INFINITY) ? "beta must be finite and not negative" : nullptr,
+                                        (reinterpret_cast<uintptr_t>(stats_out_dev) & 7) != 0 ? "stats_out_dev is not 8-byte aligned" : nullptr,
+                                        (reinterpret_cast<uintptr_t>(weight_dev) & 7) != 0 ? "weight_dev is not 8-byte aligned" : nullptr},
+                                       &g)) return rc;
+    const int P = g.OH * g.OW;
+    const unsigned group_blocks = (unsigned)(((int64_t)n_groups + 255) / 256);
+    hipLaunchKernelGGL(loss_scene_policy_prefill_kernel, dim3(group_blocks), dim3(256), 0, (hipStream_t)stream, loss_dev, n_groups);
+    if (int rc = scene_softmax_launches(e, n_pairs, affine_host, hm_size, o, g, beta, stats_out_dev, stream,
+                                        [&](int tiles, int n, int m0, const SceneAffine& a, const SceneSelect& sel, const SceneGeo& g_, int mvec) {
+            hipLaunchKernelGGL(scene_softmax_objects_kernel, dim3(tiles, n), dim3(256), (size_t)P * sizeof(float), (hipStream_t)stream,
+                               q_dev, (int64_t)P, m0, a, sel, g_, masks_dev, mvec, beta, e->scene_val, e->scene_idx, e->scene_st);
+        })) return rc;
+    if (int rc = scene_groups(affine_host, n_pairs, [&](int m0, int n, const SceneAffine& a) {
+            hipLaunchKernelGGL(loss_scene_policy_kernel, dim3(P, n), dim3(256), 0, (hipStream_t)stream, q_dev, m0, a, scene_select(o, m0, n), g,
+                               masks_dev, beta, action_dev, (const double*)weight_dev, (const double*)stats_out_dev, loss_dev, dq_dev);
+        })) return rc;
+    hipLaunchKernelGGL(loss_scene_policy_finish_kernel, dim3(group_blocks), dim3(256), 0, (hipStream_t)stream, (const double*)stats_out_dev,
+                       action_dev, weight_dev, n_groups, beta, loss_dev);
+    HIP_OK(hipGetLastError());
     e->f_dense_dq = true;        // the backward of this forward takes the dense head form ("head_bwd" = 0), as after smg_loss_scene
     return 0;
 }

@@ -21,6 +21,8 @@
 //   scene_list_walk                the loss on K LISTED pixels per pair (smg_loss_scene_ce; smg_loss_scene's kernel keeps the same
 //                                  loop in a copy of its own, for the reason its comment gives)
 //   scene_box_walk                 the loss on a whole label IMAGE per pair (smg_loss_scene_map, smg_loss_scene_map_ce)
+//   ScenePolicy                    the Boltzmann policy's log-likelihood and entropy loss per group of pairs (smg_loss_scene_policy):
+//                                  scene_box_walk's third Loss, behind the softmax kernels' normaliser
 // The __global__ kernels are thin instantiations of these; the block trees they end in are block_argmax and block_sum (elem.cuh).
 //
 // Geometry (include/smg_hip.h has the derivation), all in double, coordinates (x = column, y = row):
@@ -1043,6 +1045,97 @@ static __global__ __launch_bounds__(256) void loss_scene_map_ce_finish_kernel(co
     const double* gm = gpart + (int64_t)m * 3 * P;
     float* dj = dq + (int64_t)j * 3 * P;
     for (int i = t; i < 3 * P; i += 256) dj[i] = W > 0 ? (float)(gm[i] / dW) : 0.f;
+}
+
+// ---- the loss of the Boltzmann policy: log-likelihood of an executed action and entropy, per group (smg_loss_scene_policy) ----
+// The candidates of group g are smg_scene_softmax_objects': the selected valid pixels of its pairs, each with the float32 v the walks
+// store; pi_i = exp(beta v_i - lse).  With act = the group's executed action (a flattened index into [n_pairs][hm][hm], -1 = none)
+// and the weights {w_nll, w_ent}:
+//     H    = lse - beta mean
+//     loss = w_nll (lse - beta v_act) - w_ent H
+//     dloss/dv_i = pi_i (A + B (v_i - mean)) + C [i == act],      A = w_nll beta,  B = w_ent beta^2,  C = -w_nll beta
+// (the float32 rounding of v_i counts as the identity); with act == -1 the w_nll terms are absent and w_nll is not read into any
+// arithmetic.  Three phases on one stream: the normaliser (the softmax kernels above, unchanged) fills every group's row {count,
+// vmax, lse, mean}; loss_scene_policy_kernel gathers dq; loss_scene_policy_finish_kernel forms the losses.
+//
+// ScenePolicy is the gather's Loss.  `at` is the pixel's flattened index ((pair j) * hm + iy) * hm + ix, the number an action is
+// compared with - no address is ever formed from the action.  mask(at) tests the pair's two mask terms at the pixel by
+// scene_select4's rule on the single double - the bit pattern without its sign, so -0.0 does not select and a NaN does - read as two
+// 4-byte words: masks that are only 4-byte aligned work.  terms() forms v by the very expression the walks store and the one
+// thread that meets the action at its HOME element writes v into the group's slot of `loss` (flattened indices are unique and a
+// pixel has one home: a single writer; the slot holds the caller's NaN prefill until then).
+struct ScenePolicy {
+    static constexpr int kPlanes = 1;
+    const float* Q;
+    const unsigned* masks;           // the masks tensor as 4-byte words
+    int ta, tb, npix;
+    int64_t first;                   // the flattened index of the pair's pixel 0
+    double beta, lse, mean, A, B, C;
+    int act;
+    float* vact;
+    __device__ __forceinline__ bool term(int t, int64_t pix) const {
+        const unsigned* w = masks + 2 * ((int64_t)t * npix + pix);
+        return ((w[1] << 1) | w[0]) != 0u;
+    }
+    __device__ __forceinline__ bool mask(int64_t at) const {
+        if (ta < 0 && tb < 0) return true;
+        const int64_t pix = at - first;
+        return (ta >= 0 && term(ta, pix)) || (tb >= 0 && term(tb, pix));
+    }
+    __device__ __forceinline__ bool counts(bool selected) const { return selected; }
+    __device__ __forceinline__ void terms(const SceneGeo& g, const ScenePoint& p, bool, int64_t at, bool home, double& l, double* gk) const {
+        const float v = (float)scene_interp(p, Q, g.OW);
+        const double pi = exp(fma(beta, (double)v, -lse));
+        const bool is = act >= 0 && (int64_t)act == at;
+        gk[0] = pi * (A + B * ((double)v - mean)) + (is ? C : 0.0);
+        if (is && home) *vact = v;
+        l = 0.0;
+    }
+};
+// Phase 2: one workgroup per (pair, map element) - blockIdx.x = element, blockIdx.y = pair of this launch - as loss_scene_map_kernel.
+// The group's {lse, mean} come from its finished row of `stats`, {A, B, C} from `weight` [n_groups][2] and `action` [n_groups].
+// dq[j][el] = the element's sum, accumulated in double, reduced by block_sum's tree, rounded once, written once, zeros included; a
+// group without a candidate never reaches terms(), so its pairs' dq is exactly 0.  A group whose lse is a NaN (a NaN candidate)
+// gets NaN in EVERY element of its pairs, also where no candidate touches the element.
+static __global__ __launch_bounds__(256) void loss_scene_policy_kernel(const float* q, int pair0, const SceneAffine aff, const SceneSelect sel,
+                                                                       const SceneGeo g, const double* masks, double beta, const int* action,
+                                                                       const double* weight, const double* stats, float* loss, float* dq) {
+    __shared__ double racc[256];
+    const int t = threadIdx.x, m = blockIdx.y, j = pair0 + m, el = blockIdx.x;
+    const int P = g.OH * g.OW, grp = sel.group[m];
+    const double lse = stats[(int64_t)grp * 4 + 2], mean = stats[(int64_t)grp * 4 + 3];
+    const int act = action[grp];
+    const double w_nll = act >= 0 ? weight[2 * (int64_t)grp] : 0.0, w_ent = weight[2 * (int64_t)grp + 1];
+    const int npix = g.hm * g.hm;                       // (the host refuses n_pairs * hm^2 beyond 2^31 - 1)
+    double acc[1] = {0.0}, lsum = 0.0; int cnt = 0;
+    scene_box_walk(g, (double)aff.a[m][0], (double)aff.a[m][1], (double)aff.a[m][2], (double)aff.a[m][3], j, el / g.OW, el % g.OW,
+                   ScenePolicy{q + (int64_t)j * P, reinterpret_cast<const unsigned*>(masks), sel.a[m], sel.b[m], npix, (int64_t)j * npix,
+                               beta, lse, mean, w_nll * beta, w_ent * (beta * beta), -(w_nll * beta), act, loss + grp},
+                   acc, lsum, cnt);
+    racc[t] = acc[0];
+    block_sum(t, racc);
+    if (t == 0) dq[(int64_t)j * P + el] = lse != lse ? NAN : (float)racc[0];
+}
+// Before phase 2: every group's slot of `loss` is a NaN until the action is met.
+static __global__ __launch_bounds__(256) void loss_scene_policy_prefill_kernel(float* loss, int n_groups) {
+    const int grp = blockIdx.x * 256 + threadIdx.x;
+    if (grp < n_groups) loss[grp] = NAN;
+}
+// Phase 3, one thread per group: loss[g] turns in place from v_act into the loss, in double, rounded once.  A group without a
+// candidate: 0 with act == -1, else NaN.  An action that was no candidate of its group left the prefill: the loss stays NaN.
+static __global__ __launch_bounds__(256) void loss_scene_policy_finish_kernel(const double* stats, const int* action, const double* weight,
+                                                                              int n_groups, double beta, float* loss) {
+    const int grp = blockIdx.x * 256 + threadIdx.x;
+    if (grp >= n_groups) return;
+    const double* row = stats + (int64_t)grp * 4;
+    const int act = action[grp];
+    double r;
+    if (row[0] == 0.0) r = act < 0 ? 0.0 : (double)NAN;
+    else {
+        r = -(weight[2 * (int64_t)grp + 1] * (row[2] - beta * row[3]));
+        if (act >= 0) r = weight[2 * (int64_t)grp] * (row[2] - beta * (double)loss[grp]) + r;
+    }
+    loss[grp] = (float)r;
 }
 
 }  // namespace smg

@@ -59,7 +59,7 @@ def lib():
     for added in ("smg_loss_scene_map_ce", "smg_scene_argmax_objects", "smg_scene_class_argmax_objects", "smg_scene_values",
                   "smg_scene_class_values", "smg_scene_topk_objects", "smg_scene_class_topk_objects", "smg_scene_best_maps",
                   "smg_scene_class_best_maps", "smg_scene_sample_objects", "smg_scene_class_sample_objects", "smg_scene_softmax_objects",
-                  "smg_scene_class_softmax_objects"):       # (added without a version step: a version-9 library built before them lacks the symbol)
+                  "smg_scene_class_softmax_objects", "smg_loss_scene_policy"):       # (added without a version step: a version-9 library built before them lacks the symbol)
         if not hasattr(L, added):
             raise SmgError("%s is ABI version %d but lacks %s, a stale build: rebuild it (make -C csrc)" % (LIB_PATH, ABI_VERSION, added))
     L.smg_abi_struct_bytes.argtypes = [C.c_int]
@@ -103,6 +103,9 @@ def lib():
                                  C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_loss_scene_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
+    L.smg_loss_scene_policy.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_scene_class_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.smg_scene_class_values.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.smg_scene_class_argmax.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -150,7 +153,7 @@ EXPORTS = (
     "smg_last_error", "smg_version", "smg_abi_struct_bytes", "smg_engine_set_option", "smg_layout_count", "smg_layout_param_floats", "smg_layout_buffer_floats",
     "smg_layout_nbt_count", "smg_layout_entry", "smg_layout_trunk_range", "smg_layout_head_range",
     "smg_engine_create", "smg_engine_destroy", "smg_engine_workspace_bytes", "smg_engine_geometry",
-    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_values", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_scene_topk_objects", "smg_scene_sample_objects", "smg_scene_softmax_objects", "smg_scene_best_maps", "smg_loss_scene","smg_loss_scene_map", "smg_scene_class_maps", "smg_scene_class_values", "smg_scene_class_argmax", "smg_scene_class_argmax_objects", "smg_scene_class_topk_objects", "smg_scene_class_sample_objects", "smg_scene_class_softmax_objects", "smg_scene_class_best_maps", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
+    "smg_forward", "smg_loss", "smg_loss_map", "smg_loss_map_ce", "smg_scene_maps", "smg_scene_values", "smg_scene_argmax", "smg_scene_argmax_objects", "smg_scene_topk_objects", "smg_scene_sample_objects", "smg_scene_softmax_objects", "smg_scene_best_maps", "smg_loss_scene","smg_loss_scene_map", "smg_loss_scene_policy", "smg_scene_class_maps", "smg_scene_class_values", "smg_scene_class_argmax", "smg_scene_class_argmax_objects", "smg_scene_class_topk_objects", "smg_scene_class_sample_objects", "smg_scene_class_softmax_objects", "smg_scene_class_best_maps", "smg_loss_scene_ce", "smg_loss_scene_map_ce", "smg_backward", "smg_backward_phase", "smg_train_step_graph", "smg_layout_trunk_split", "smg_adam_step", "smg_argmax", "smg_heightmap", "smg_engine_set_precision", "smg_debug_read",
     "smg_profile_enable", "smg_profile_kinds", "smg_profile_kind_name", "smg_profile_read", "smg_profile_read_bytes",
 )
 
@@ -399,6 +402,19 @@ class Engine(object):
         rotation contribute nothing.  Marks the saved forward so that its backward runs the dense head form."""
         a, p = self._affines(affine, n_pairs)
         check(lib().smg_loss_scene_map(self.h, q, p, int(hm_size), int(n_pairs), label_maps, weight_maps, loss_out, dq_out, stream))
+
+    def loss_scene_policy(self, q, affine, hm_size, n_pairs, masks, n_masks, mask_a, mask_b, groups, n_groups, beta, actions, weights,
+                          stats_out, loss_out, dq_out, stream):
+        """smg_loss_scene_policy: the log-likelihood and entropy loss of the Boltzmann policy pi = softmax(beta v) per group of pairs
+        - scene_softmax_objects' selection on the pairs of q [n_pairs, 1, OH, OW] plus, on the device, `actions` int32 [n_groups]
+        (the executed action as a flattened index into [n_pairs, hm, hm], -1 = none) and `weights` float64 [n_groups, 2] =
+        {w_nll, w_ent}.  loss_out float32 [n_groups] = w_nll (lse - beta v_act) - w_ent (lse - beta mean), stats_out float64
+        [n_groups, 4] = scene_softmax_objects' rows, dq_out its gradient on the maps, every element written.  Marks the saved
+        forward so that its backward runs the dense head form."""
+        a, p = self._affines(affine, n_pairs)
+        sel, (ma, mb, gr) = self._selects(n_pairs, mask_a, mask_b, groups)
+        check(lib().smg_loss_scene_policy(self.h, q, p, int(hm_size), int(n_pairs), masks, int(n_masks), ma, mb, gr, int(n_groups), float(beta),
+                                          actions, weights, stats_out, loss_out, dq_out, stream))
 
     def scene_class_maps(self, q, n_maps, affine, hm_size, cls, out, stream):
         """smg_scene_class_maps: the class probabilities of the n_maps logit maps at `q` (device, [n_maps, 3, OH, OW]) in the scene

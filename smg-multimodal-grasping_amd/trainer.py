@@ -540,13 +540,14 @@ class Trainer(object):
         flat = [r for rs in rotations for r in rs] if np.ndim(depth_heightmap) == 3 else list(rotations)
         return [0 if style == 2 else int(r) for r in flat]
 
-    def _train_maps(self, depth_heightmap, m_depth_heightmap, style, rotations, q_shape, upload, loss_call, grad_sync, return_q):
+    def _train_maps(self, depth_heightmap, m_depth_heightmap, style, rotations, q_shape, upload, loss_call, grad_sync, return_q, n_loss=None):
         """The step that train_batch_maps, train_batch_class_maps and the four train_batch_scene_* methods share, entered once their
         own arguments are checked: the forward of every (scene, rotation) sample kept for the backward, ONE engine loss call on its
         q [n, channels, side, side] (`q_shape` = the expected (channels, side)), one backward pass, ONE Adam step.
         `upload(dev)` returns the device tensors of the labels and is called BEFORE the forward is enqueued (behind it, a pageable
         copy would hold the host until the forward has run); `loss_call(eng, q, tensors, n, loss, dq, stream)` enqueues the loss
-        that fills loss [n] and dq (shaped like q).  Returns the loss vector (and q if asked)."""
+        that fills loss [n] - or [n_loss] where the loss is not per sample (train_batch_scene_policy's is per group) - and dq (shaped
+        like q).  Returns the loss vector (and q if asked)."""
         model = self.model
         self.optimizer.zero_grad()
         model._require_gpu()
@@ -559,7 +560,7 @@ class Trainer(object):
         eng, token, trunk_id, head_id = model._saved
         assert tuple(q.shape) == (n, q_shape[0], q_shape[1], q_shape[1]), (tuple(q.shape), n, q_shape)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        loss = torch.empty(n if n_loss is None else n_loss, dtype=torch.float32, device=dev)
         dq = torch.empty_like(q)
         loss_call(eng, q, tensors, n, loss, dq, stream)
         self._backward_and_step(token, dq, trunk_id, head_id, grad_sync)
@@ -1148,6 +1149,82 @@ class Trainer(object):
                                loss.data_ptr(), dq.data_ptr(), stream)
         return self._train_maps(depth_heightmap, m_depth_heightmap, style, rotations, (1, side),
                                 lambda dev: (_f32_on(dev, label_maps), _f32_on(dev, weight_maps)), loss_call, grad_sync, return_q)
+
+    def train_batch_scene_policy(self, depth_heightmap, m_depth_heightmap, style, rotations, select_masks, sample_masks, sample_groups, actions,
+                                 temperature, nll_weights=None, entropy_weights=None, grad_sync=None, return_q=False, return_stats=False):
+        """TRAIN the Boltzmann policy sampled_scene_actions explores with: the samples (scene, rotation) form groups, the policy
+        of a group is pi proportional to exp(Q / temperature) over the selected pixels with a window of all its samples, and the
+        loss of group g is  w_nll (lse - v_act / temperature) - w_ent H  (smg_loss_scene_policy): the negative log-likelihood of the
+        executed action - w_nll 1 clones a demonstration, an advantage makes it the policy-gradient step, it may be negative - and
+        the entropy H = lse - mean / temperature as a bonus.  `select_masks` [n_masks, hm, hm] (a pixel is selected where its mask
+        is not exactly 0); `sample_masks[j]` = the mask index of sample j, a pair of indices (their union) or -1 (every pixel);
+        `sample_groups[j]` = its group in [0, n_groups), n_groups = len(actions); `actions[g]` = None or (sample j, (iy, ix));
+        `nll_weights` / `entropy_weights` [n_groups], None = all ones / all zeros.  One forward, ONE loss call, one backward
+        (dense head form), ONE Adam step (_train_maps).  ValueError before anything runs for: an action whose sample is not in
+        its group, a pixel outside the heightmap, without a window in that sample's rotation (scene_to_map) or not selected by the
+        sample's masks, a temperature that is no positive scalar, weights that are not finite.  Reinforcement method only.
+        Returns the loss [n_groups] (then q [n_samples, 1, OH, OW] and / or the float64 rows [n_groups, 4] = {count, vmax, lse,
+        mean} of smg_scene_softmax_objects if asked), device tensors."""
+        what = "train_batch_scene_policy"
+        _, _, side = self._require_scene(what, depth_heightmap)
+        rots = self._flat_rotations(depth_heightmap, style, rotations)
+        n, num, hm = len(rots), self.model.gnum_rotations, int(np.shape(depth_heightmap)[-1])
+        if not np.isscalar(temperature) or not float(temperature) > 0:                 # (a NaN fails this too)
+            raise ValueError("%s: temperature must be one number > 0 (inf is the uniform policy)" % what)
+        beta = 1.0 / float(temperature)
+        masks = np.ascontiguousarray(select_masks, dtype=np.float64)
+        if masks.ndim != 3 or masks.shape[0] < 1 or masks.shape[1:] != (hm, hm):
+            raise ValueError("%s: select_masks must be [n_masks >= 1, %d, %d], got %s" % (what, hm, hm, masks.shape))
+        if len(sample_masks) != n or len(sample_groups) != n:
+            raise ValueError("%s: one sample_masks entry and one sample_groups entry per sample (%d)" % (what, n))
+        mask_a, mask_b = [], []
+        for sm in sample_masks:
+            a, b = (int(sm), -1) if np.isscalar(sm) else (int(sm[0]), int(sm[1])) if len(sm) == 2 else (None, None)
+            if a is None or not (-1 <= a < masks.shape[0] and -1 <= b < masks.shape[0]):
+                raise ValueError("%s: sample_masks entries are a mask index, a pair of indices or -1, inside [-1, %d)" % (what, masks.shape[0]))
+            mask_a.append(a)
+            mask_b.append(b)
+        n_groups = len(actions)
+        groups = [int(g) for g in sample_groups]
+        if n_groups < 1 or not all(0 <= g < n_groups for g in groups):
+            raise ValueError("%s: sample_groups must lie in [0, len(actions) = %d)" % (what, n_groups))
+        wgt = np.empty((n_groups, 2), dtype=np.float64)
+        for c, (name, w, default) in enumerate((("nll_weights", nll_weights, 1.0), ("entropy_weights", entropy_weights, 0.0))):
+            w = np.full(n_groups, default) if w is None else np.asarray(w, dtype=np.float64).reshape(-1)
+            if w.shape != (n_groups,) or not np.isfinite(w).all():
+                raise ValueError("%s: %s must be %d finite numbers" % (what, name, n_groups))
+            wgt[:, c] = w
+        if n * hm * hm > 0x7fffffff:
+            raise ValueError("%s: the flattened action index does not fit int32" % what)
+        act = np.full(n_groups, -1, dtype=np.int32)
+        for g, a in enumerate(actions):
+            if a is None:
+                continue
+            j, (iy, ix) = a
+            if int(j) != j or not 0 <= j < n or groups[int(j)] != g:
+                raise ValueError("%s: the action of group %d names sample %r, which is not in that group" % (what, g, j))
+            j = int(j)
+            if int(iy) != iy or int(ix) != ix or not (0 <= iy < hm and 0 <= ix < hm):
+                raise ValueError("%s: the action pixel %r of group %d lies outside the %d x %d heightmap" % (what, (iy, ix), g, hm, hm))
+            iy, ix = int(iy), int(ix)
+            if not self.scene_to_map(hm, rots[j], num, [[iy, ix]])[2][0]:
+                raise ValueError("%s: the action pixel %r of group %d has no Q window in rotation %d of %d (scene_to_map)" % (what, (iy, ix), g, rots[j], num))
+            if (mask_a[j] >= 0 or mask_b[j] >= 0) and not any(t >= 0 and masks[t, iy, ix] != 0 for t in (mask_a[j], mask_b[j])):
+                raise ValueError("%s: the action pixel %r of group %d is not selected by the masks of sample %d" % (what, (iy, ix), g, j))
+            act[g] = (j * hm + iy) * hm + ix
+        kept = {}
+
+        def loss_call(eng, q, tensors, n, loss, dq, stream):
+            kept["stats"] = torch.empty((n_groups, 4), dtype=torch.float64, device=q.device)
+            eng.loss_scene_policy(q.data_ptr(), self._scene_affines(rots, num), hm, n, tensors[0].data_ptr(), int(masks.shape[0]), mask_a, mask_b,
+                                  groups, n_groups, beta, tensors[1].data_ptr(), tensors[2].data_ptr(), kept["stats"].data_ptr(),
+                                  loss.data_ptr(), dq.data_ptr(), stream)
+        out = self._train_maps(depth_heightmap, m_depth_heightmap, style, rotations, (1, side),
+                               lambda dev: (torch.as_tensor(masks, device=dev), _i32_on(dev, act), torch.as_tensor(wgt, device=dev)),
+                               loss_call, grad_sync, return_q, n_loss=n_groups)
+        if not return_stats:
+            return out
+        return (out + (kept["stats"],)) if return_q else (out, kept["stats"])
 
     # ---- dense class maps (reactive method on heightmaps larger than 224^2: three logits per 20x20 window of the feature plane) ---
     def _require_reactive(self, what):
@@ -1776,6 +1853,33 @@ class Trainer(object):
         m, style, rot, pixel = self._scene_action("backprop_scene", best, primitive_action, depth_heightmap, mask_depth)
         step = self.train_batch_scene_pixels if self.method == 'reinforcement' else self.train_batch_scene_class_pixels
         loss = step(depth_heightmap, m, style, [rot], [[pixel]], [label_value])
+        loss_value = np.asarray(loss.cpu().numpy()[0])
+        print('Training loss: %f' % (loss_value))
+        return loss_value
+
+    def backprop_scene_policy(self, depth_heightmap, primitive_action, best, objects_mask, temperature, weight=1.0, entropy_weight=0.0):
+        """The policy step on the EXECUTED action: `best` is the dict best_scene_actions, ranked_to_best or the sampled forms
+        return, decoded by _scene_action.  The executed object's masked heightmap goes through all R rotations (rotation 0 alone
+        for 'grasp_then_suction'); they form ONE group, selected by the object's mask (the union of both for a pair), whose action
+        is the executed (rotation, pixel): one train_batch_scene_policy.  `weight` is the NLL weight - 1 clones a demonstration,
+        an advantage makes it the policy-gradient step -, `entropy_weight` the entropy bonus, `temperature` the policy's.
+        `objects_mask` is [n, H, H] or [n, H, H, 1] and is not reshaped in place.  Reinforcement method only.  Prints the
+        reference's line and returns the loss as a 0-d array."""
+        if self.method != 'reinforcement':
+            raise ValueError("backprop_scene_policy: reinforcement method only (the reactive net is trained by its class labels)")
+        mask_depth = np.asarray(objects_mask)
+        if mask_depth.ndim == 4:
+            mask_depth = mask_depth[..., 0]
+        m, style, rot, pixel = self._scene_action("backprop_scene_policy", best, primitive_action, depth_heightmap, mask_depth)
+        ids = best[("bestg_id", "bests_id", "bestgs_num")[style]]
+        if style == 2:
+            masks, rotations, which = np.stack([mask_depth[ids[0]], mask_depth[ids[1]]]), [0], (0, 1)
+        else:
+            masks, rotations, which = mask_depth[ids[0]][None], list(range(self.model.gnum_rotations)), 0
+            if not 0 <= rot < len(rotations):
+                raise ValueError("backprop_scene_policy: rotation %d is outside the %d trained rotations" % (rot, len(rotations)))
+        loss = self.train_batch_scene_policy(depth_heightmap, m, style, rotations, masks, [which] * len(rotations), [0] * len(rotations),
+                                             [(0 if style == 2 else rot, pixel)], temperature, [weight], [entropy_weight])
         loss_value = np.asarray(loss.cpu().numpy()[0])
         print('Training loss: %f' % (loss_value))
         return loss_value
